@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- training-step throughput of the CTC hot path on N x MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|cfg4|cfg1] [--no-cpu-baseline]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg2|cfg3|cfg4|cfg1] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one full pass of the hot path over one synthetic minibatch that is already resident in HBM:
@@ -10,6 +10,13 @@ the flat gradient -> fused Adam.  Default workload = BASELINE.json configs[1] ("
 per GPU, T=800, F=40, V=62, dropout 0.1, batch_norm, Adam lr 1e-3 wd 5e-4), weak scaling (fixed per-GPU batch).
 Rank 0 prints ONE JSON line; `value` = acoustic frames/s of the whole job.  `--mode decode` times cfg5 instead
 (beam W=20 + bigram LM over 128 utterances x 800 frames; utterances/s).
+
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = wall clock of one timed step).
+`--full` adds everything else the line used to carry: the exchange-step measurement of `comm`, the rooflines (with their
+rocprofv3 --pmc child passes), host enqueue time, the run_epoch loops, sync_bn_cost, the decode leg, other_workloads, the
+bf16 GEMM mode and the CPU baseline (each of them can still be left out with its --no-* switch).
+`--dump-outputs DIR` writes what the last timed step computed (loss, flat gradient, flat parameters after Adam) as
+DIR/<name>.npy (float32); inputs are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import gc
@@ -38,6 +45,22 @@ CNN_LAYERS = [[(1, 32), (3, 3), (1, 2), (1, 1), None], [(32, 32), (3, 3), (2, 2)
 PEAK_F32_MFMA_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md "Peak FP32 (matrix)"
 PEAK_HBM_GBS = 8000.0             # HBM3E spec; ~6300 GB/s measured achievable
 PREWARM = 40                      # untimed steps before the --warmup steps (start-up transient of a fresh process, see run_train)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 0                     # fixed sample of an output that does not fit
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES, seed=DUMP_SEED):
+    """Write every host array of `arrays` as outdir/<name>.npy.  Arrays of 1 MB or less are written whole; the larger ones share
+    what is left of `limit` equally, and one that does not fit in its share is replaced by a fixed, seeded sample of its
+    flattened elements (sorted indices, the same for every run of the same shape)."""
+    os.makedirs(outdir, exist_ok=True)
+    big = [k for k, a in arrays.items() if a.nbytes > 10 ** 6]
+    share = (limit - sum(a.nbytes for k, a in arrays.items() if k not in big) - 4096 * len(arrays)) // max(len(big), 1)
+    for name, a in arrays.items():
+        if name in big and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def gemm_weights(c, feat_in):
@@ -399,7 +422,7 @@ def sync_bn_cost(args, steps=20):
     for name, extra in (("per_shard_bn", []), ("sync_bn", ["--sync-bn"])):
         env = dict(os.environ, CTCN_FORCE_COLLECTIVES="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29700 + (os.getpid() + len(out)) % 200), WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", args.workload, "--steps", str(steps), "--warmup", "3", "--precision", str(args.precision),
-               "--no-decode", "--no-cpu-baseline", "--no-others", "--no-pmc", "--no-ragged", "--no-sync-bn-cost", "--train-only"] + extra
+               "--full", "--no-decode", "--no-cpu-baseline", "--no-others", "--no-pmc", "--no-ragged", "--no-sync-bn-cost", "--train-only"] + extra
         try:
             p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
             d = json.loads(p.stdout.strip().splitlines()[-1])
@@ -609,19 +632,23 @@ def _run_train(args, rank, world, local, monitor, rccl_log):
     per_rank_s = parallel.gather_over_ranks(dt, dev)     # every rank's own wall clock over the K steps (the headline uses the MAX)
     dt = parallel.max_over_ranks(dt, dev)
     last_loss = float(losses[-1].detach()) * world if losses else float("nan")
+    if args.dump_outputs and rank == 0:     # before anything below trains the model further
+        dump_outputs(args.dump_outputs, {"loss": losses[-1].detach().float().reshape(1).cpu().numpy(),
+                                         "grad": opt.grad.detach().cpu().numpy(), "params": opt.flat.detach().cpu().numpy()})
     # Everything below that issues a collective must run on EVERY rank (the other ranks are gone after the return): the exchange-step
-    # measurement here, on all ranks; the rank-0-only probes further down contain no collective, and the two that do (host enqueue time,
-    # epoch loop) are single-rank measurements that N > 1 skips.
-    comm_marks = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
+    # measurement here (--full), on all ranks; the rank-0-only probes further down contain no collective, and the two that do (host
+    # enqueue time, epoch loop) are single-rank measurements that N > 1 skips.
+    comm_marks = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)] if args.full else []
     comm_err = None
-    try:
-        for mk in comm_marks:
-            step(mk)
-        torch.cuda.synchronize()
-    except Exception as e:          # noqa: BLE001
-        comm_err = repr(e)
-    if torch.distributed.is_initialized():
-        torch.distributed.barrier()
+    if comm_marks:
+        try:
+            for mk in comm_marks:
+                step(mk)
+            torch.cuda.synchronize()
+        except Exception as e:          # noqa: BLE001
+            comm_err = repr(e)
+        if torch.distributed.is_initialized():
+            torch.distributed.barrier()
     if monitor is not None:         # this rank's own record: its clock, its hand-off status word (0 = healthy), the recurrence kernels it ran
         monitor.finish(ms_per_step=per_rank_s[rank] / args.steps * 1e3 if rank < len(per_rank_s) else None, status=0,
                        kernels=list(_ops.rnn_last_kernels()), kernel_counts=_ops.kernel_counts(), exchange_error=comm_err)
@@ -652,7 +679,7 @@ def _run_train(args, rank, world, local, monitor, rccl_log):
         import torch.distributed as tdist
         if comm_err is not None:
             raise RuntimeError(comm_err)
-        exposed = sorted(a.elapsed_time(b) * 1e3 for a, b in comm_marks)
+        exposed = sorted(a.elapsed_time(b) * 1e3 for a, b in comm_marks) or [None]        # (the exchange steps run with --full only)
         on = parallel._collectives_on()
         rccl_lines = summarize_rccl_log(rccl_log) if rccl_log and os.path.exists(rccl_log) else None
         res["per_rank_ms_per_step"] = [t / args.steps * 1e3 for t in per_rank_s]
@@ -666,7 +693,7 @@ def _run_train(args, rank, world, local, monitor, rccl_log):
                                 "early slices are all-reduced on the side stream behind their layer's weight-gradient GEMMs, next to the recurrence of the layer below")
     except Exception as e:
         res["comm"] = {"error": repr(e)}
-    if args.train_only:
+    if args.train_only or not args.full:
         print(json.dumps(res))
         return
     try:
@@ -979,17 +1006,26 @@ if __name__ == "__main__":
                          "the GLOBAL batch, sharded B/N utterances per rank")
     ap.add_argument("--sync-bn", action="store_true", help="BatchNorm statistics over the global batch (N-GPU == 1-GPU math); default: per shard")
     ap.add_argument("--mode", default="train", choices=["train", "decode"])
+    ap.add_argument("--full", action="store_true",
+                    help="train mode: after the headline, everything else the line can carry (comm exchange steps, rooflines, epoch loops, "
+                         "sync_bn_cost, decode leg, other workloads, bf16 GEMM mode, CPU baseline); default: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="train mode: write the last timed step's loss, flat gradient and flat parameters as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-decode", action="store_true", help="skip the cfg5 beam-decode leg of the default (N=1, train) run")
     ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic with rocprofv3 --pmc child passes (the committed profile is quoted instead)")
     ap.add_argument("--no-others", action="store_true", help="skip the `other_workloads` object (cfg1 / cfg3 / cfg4 / ref_yaml) of the default cfg2 run")
     ap.add_argument("--no-ragged", action="store_true", help="skip `epoch_loop_ragged` (run_epoch over minibatches of ragged utterances)")
     ap.add_argument("--no-sync-bn-cost", action="store_true", help="skip `sync_bn_cost` (two forced-collectives child runs, without / with --sync-bn)")
-    ap.add_argument("--train-only", action="store_true", help="the timed step loop and the comm object only (what the sync_bn_cost children run)")
+    ap.add_argument("--train-only", action="store_true", help="with --full: the timed step loop and the comm object (exchange steps included) only (what the sync_bn_cost children run)")
     ap.add_argument("--cpu-steps", type=int, default=1, help="timed CPU train steps per thread setting of the sweep")
     ap.add_argument("--precision", type=int, default=int(os.environ.get("CTCN_PRECISION", "1")), choices=[0, 1],
                     help="0: exact f32 MFMA GEMMs; 1: bf16x3 split-operand MFMA GEMMs (f32-class accuracy)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.mode != "train":
+        ap.error("--dump-outputs: train mode only")
     relaunch = self_launch_argv(a, sys.argv[1:], os.environ)
     if relaunch is not None:
         os.execvpe(relaunch[0][0], relaunch[0], relaunch[1])

@@ -2412,7 +2412,7 @@ def test_bench_under_torchrun_with_rccl_collectives(dev, workload, comm):
     env = dict(os.environ, CTCN_FORCE_COLLECTIVES="1", CTCN_COMM=comm, HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONDONTWRITEBYTECODE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", workload,
-           "--sync-bn", "--no-cpu-baseline", "--no-decode", "--no-others", "--no-pmc"]
+           "--sync-bn", "--full", "--no-cpu-baseline", "--no-decode", "--no-others", "--no-pmc"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -2438,7 +2438,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo(dev, scaling):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29641" if scaling == "weak" else "29643", WORLD_SIZE="2", LOCAL_RANK="0", CTCN_DIST_BACKEND="gloo",
                HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONDONTWRITEBYTECODE="1", CTCN_QUIET="1")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "cfg1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "cfg1", "--full", "--no-cpu-baseline",
            "--no-decode", "--no-others", "--no-pmc", "--scaling", scaling]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r)), cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(2)]
     outs = [p.communicate(timeout=280) for p in procs]

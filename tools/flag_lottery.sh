@@ -12,7 +12,7 @@ while IFS= read -r flags; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $flags -c $R/ctc_pytorch_amd/csrc/rnn.hip -o /tmp/rnn_v$i.o 2> $O/build_$i.err || { echo "variant $i [$flags]: build failed" | tee -a $O/lottery.txt; continue; }
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o /tmp/libctcn_v$i.so $others /tmp/rnn_v$i.o 2>> $O/build_$i.err || { echo "variant $i: link failed" | tee -a $O/lottery.txt; continue; }
   for rep in 1 2; do
-    CTCN_LIBCTCN=/tmp/libctcn_v$i.so timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-decode --no-pmc --no-ragged --no-sync-bn-cost --no-others > $O/bench_${i}_$rep.json 2> $O/bench_${i}_$rep.err
+    CTCN_LIBCTCN=/tmp/libctcn_v$i.so timeout 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-decode --no-pmc --no-ragged --no-sync-bn-cost --no-others > $O/bench_${i}_$rep.json 2> $O/bench_${i}_$rep.err
     python - "$O/bench_${i}_$rep.json" "$i" "$flags" <<'PY' | tee -a $O/lottery.txt
 import json, sys
 try:

@@ -13,7 +13,7 @@ case $S in
   tail -n 25 $O/pytest_shipped.log
   CTCN_OPT_XCD_INTERLEAVE_FORCE=1 CTCN_STATE_LOG=$O/state_forced.jsonl CTCN_TRAJ_LOG=$O/traj_forced.jsonl timeout 1500 python -m pytest tests -m gpu -q --maxfail=20 --timeout 600 -p no:cacheprovider -p no:randomly > $O/pytest_forced.log 2>&1; echo "pytest forced rc=$?" >> $O/summary.log
   tail -n 8 $O/pytest_forced.log
-  timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log
+  timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log
   cat $O/summary.log
   ;;
 2)
@@ -25,7 +25,7 @@ case $S in
   done
   tail -n 40 $O/nondet.txt
   timeout 900 python -m pytest tests -m gpu -q --maxfail=8 --timeout 600 -p no:cacheprovider -k "bench_ or xcd_order or beam or dropout or conv_front" > $O/pytest_sub.log 2>&1; echo "pytest rc=$?" > $O/summary.log; tail -n 6 $O/pytest_sub.log
-  timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log; tail -c 600 $O/bench_default.err
+  timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log; tail -c 600 $O/bench_default.err
   cat $O/summary.log
   ;;
 3)
@@ -81,8 +81,8 @@ case $S in
   python tools/traj_compare.py $O/traj_*.jsonl > $O/traj_compare.txt 2>&1
   cat $O/summary.log $O/traj_compare.txt | cut -c1-400
   for i in 1 2 3; do grep -q "first difference" $O/traj_compare_$i.txt || rm -f $O/traj_full_$i.jsonl; done
-  timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log
-  CTCN_OPT_RNN_PROJ_ORDER=0 timeout 600 python bench.py --no-cpu-baseline --no-decode --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_order0.json 2> $O/bench_order0.err
+  timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log
+  CTCN_OPT_RNN_PROJ_ORDER=0 timeout 600 python bench.py --full --no-cpu-baseline --no-decode --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_order0.json 2> $O/bench_order0.err
   ;;
 8)
   # round-6 evidence (profiles/r06_*) + three more traced full suites with the projection order fix
@@ -98,7 +98,7 @@ case $S in
   ;;
 9)
   # the kernel-stats pass of the driver command without the ragged-epoch legs (every recurrence launch is the T = 800 one), and two more suites
-  ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o cfg2 -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/r06_bench_under_rocprof.json 2> $O/stats.log )
+  ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o cfg2 -- python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/r06_bench_under_rocprof.json 2> $O/stats.log )
   db=$(find $O/stats -name "*.db" | head -1)
   [ -n "$db" ] && python tools/prof_timeline.py $db -1 all > $O/r06_cfg2_step_timeline.txt 2>&1
   [ -n "$db" ] && python tools/prof_stats.py $db > $O/r06_cfg2_train_decode_kernel_stats.txt 2>&1
@@ -117,7 +117,7 @@ case $S in
   # option rnn_early_sum (item waves sum the parked partial tiles as the exchange waves finish them): parity subset, then A/B of the step
   timeout 900 python -m pytest tests -m gpu -q --maxfail=8 --timeout 600 -p no:cacheprovider -k "rnn or model_three or large_shape or lstm or gru or run_epoch or foreign or soak or stateless" > $O/pytest_sub.log 2>&1; echo "pytest rc=$?" > $O/summary.log; tail -n 5 $O/pytest_sub.log | cut -c1-200
   for rep in 1 2; do for v in 1 0; do
-    CTCN_OPT_RNN_EARLY_SUM=$v timeout 600 python bench.py --no-cpu-baseline --no-decode --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_early${v}_$rep.json 2> $O/bench_early${v}_$rep.err
+    CTCN_OPT_RNN_EARLY_SUM=$v timeout 600 python bench.py --full --no-cpu-baseline --no-decode --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_early${v}_$rep.json 2> $O/bench_early${v}_$rep.err
   done; done
   python - $O <<'PY'
 import json, sys, glob
@@ -140,7 +140,7 @@ PY
     tail -n 2 $O/pytest_full_$i.log | cut -c1-200
     grep -q "first difference" $O/traj_compare_$i.txt || rm -f $O/traj_full_$i.jsonl
   done
-  timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log
+  timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log
   cat $O/summary.log $O/traj_compare_*.txt | cut -c1-300
   python - $O/bench_default.json <<'PY'
 import json, sys
@@ -287,7 +287,7 @@ PY
     tail -n 12 $O/pytest_full_$i.log | cut -c1-200
     grep -q "first difference" $O/traj_compare_$i.txt || rm -f $O/traj_full_$i.jsonl
   done
-  timeout 1200 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log
+  timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log
   cat $O/summary.log $O/traj_compare_*.txt | cut -c1-300
   python - $O/bench_default.json <<'PY'
 import json, sys
@@ -305,7 +305,7 @@ PY
   for rep in 1 2; do for lib in keep ${LIBB:-base}; do
     [ $lib = keep ] && cp $O/libctcn_keep.so ctc_pytorch_amd/libctcn.so || cp tools/libctcn_$lib.so ctc_pytorch_amd/libctcn.so
     for wl in cfg4 cfg2; do
-      timeout 400 python bench.py --workload $wl --steps 20 --warmup 3 --no-decode --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_${lib}_${wl}_$rep.json 2> $O/bench_${lib}_${wl}_$rep.err
+      timeout 400 python bench.py --full --workload $wl --steps 20 --warmup 3 --no-decode --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_${lib}_${wl}_$rep.json 2> $O/bench_${lib}_${wl}_$rep.err
     done
   done; done
   cp $O/libctcn_keep.so ctc_pytorch_amd/libctcn.so; rm -f $O/libctcn_keep.so
@@ -323,7 +323,7 @@ PY
 29)
   # cfg4 forward: sweep of the exchange waves' pause before their first poll (option tag_poll_delay, x 64 cycles; 8 was tuned at cfg2)
   for v in ${SWEEP:-8 12 16 20 24 8}; do
-    CTCN_OPT_TAG_POLL_DELAY=$v timeout 400 python bench.py --workload ${WL:-cfg4} --steps 20 --warmup 3 --no-decode --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_$v.json 2> $O/bench_$v.err
+    CTCN_OPT_TAG_POLL_DELAY=$v timeout 400 python bench.py --full --workload ${WL:-cfg4} --steps 20 --warmup 3 --no-decode --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_$v.json 2> $O/bench_$v.err
     python - $O/bench_$v.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -346,7 +346,7 @@ PY
   for rep in 1 2; do for lib in keep ${LIBS:-fn4k nft6 nola}; do
     [ $lib = keep ] && cp $O/libctcn_keep.so ctc_pytorch_amd/libctcn.so || cp tools/libctcn_$lib.so ctc_pytorch_amd/libctcn.so
     for wl in ${WLS:-cfg2}; do
-      timeout 400 python bench.py --workload $wl --steps 20 --warmup 3 --no-decode --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_${lib}_${wl}_$rep.json 2> $O/bench_${lib}_${wl}_$rep.err
+      timeout 400 python bench.py --full --workload $wl --steps 20 --warmup 3 --no-decode --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_${lib}_${wl}_$rep.json 2> $O/bench_${lib}_${wl}_$rep.err
     done
   done; done
   cp $O/libctcn_keep.so ctc_pytorch_amd/libctcn.so; rm -f $O/libctcn_keep.so

@@ -3,8 +3,8 @@ cd "$GRAFT_REPO_ROOT"; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06b; rm -rf $O; mkdi
 export TMPDIR=/tmp PYTHONDONTWRITEBYTECODE=1
 timeout 900 python -m pytest tests -m gpu -x -q --durations=12 2>&1 | tail -30 > $O/gpu_suite.txt
 tail -3 $O/gpu_suite.txt
-timeout 600 python bench.py --steps 20 --warmup 3 > $O/r06_bench_default.json 2> $O/bench_default.err
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o cfg2 -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/r06_bench_under_rocprof.json 2> $O/stats.log )
+timeout 600 python bench.py --full --steps 20 --warmup 3 > $O/r06_bench_default.json 2> $O/bench_default.err
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o cfg2 -- python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-others --no-pmc --no-ragged --no-sync-bn-cost > $O/r06_bench_under_rocprof.json 2> $O/stats.log )
 db=$(find $O/stats -name "*.db" | head -1)
 [ -n "$db" ] && python tools/prof_timeline.py $db -1 all > $O/r06_cfg2_step_timeline.txt 2>&1
 [ -n "$db" ] && python tools/prof_stats.py $db > $O/r06_cfg2_train_decode_kernel_stats.txt 2>&1

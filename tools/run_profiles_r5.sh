@@ -8,21 +8,21 @@
 set -u
 cd "$GRAFT_REPO_ROOT"; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp PYTHONDONTWRITEBYTECODE=1
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o cfg2 -- python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-others --no-pmc > $O/r05_bench_under_rocprof.json 2> $O/stats.log )
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $O/stats -o cfg2 -- python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-others --no-pmc > $O/r05_bench_under_rocprof.json 2> $O/stats.log )
 db=$(find $O/stats -name "*.db" | head -1)
 [ -n "$db" ] && python tools/prof_timeline.py $db -1 all > $O/r05_cfg2_step_timeline.txt 2>&1
 [ -n "$db" ] && python tools/prof_stats.py $db > $O/r05_cfg2_train_decode_kernel_stats.txt 2>&1
 rm -rf $O/stats
 for wl in cfg4 cfg3 ref_yaml cfg1; do
-  ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof_$wl -o p -- python $R/bench.py --workload $wl --steps 8 --warmup 2 --no-decode --no-cpu-baseline --no-others --no-pmc > $O/r05_${wl}_under_rocprof.json 2> $O/prof_$wl.log )
+  ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats -d $O/prof_$wl -o p -- python $R/bench.py --full --workload $wl --steps 8 --warmup 2 --no-decode --no-cpu-baseline --no-others --no-pmc > $O/r05_${wl}_under_rocprof.json 2> $O/prof_$wl.log )
   db=$(find $O/prof_$wl -name "*.db" | head -1)
   [ -n "$db" ] && python tools/prof_timeline.py $db -1 all > $O/r05_${wl}_step_timeline.txt 2>&1 && python tools/prof_stats.py $db > $O/r05_${wl}_kernel_stats.txt 2>&1
   rm -rf $O/prof_$wl
 done
-timeout 900 python bench.py --steps 20 --warmup 3 > $O/r05_bench_default.json 2> $O/bench_default.err
-timeout 400 python bench.py --workload cfg2 --precision 0 --steps 10 --warmup 3 --no-decode --no-cpu-baseline --no-others --no-pmc > $O/r05_bench_cfg2_f32.json 2> $O/bench_f32.err
+timeout 900 python bench.py --full --steps 20 --warmup 3 > $O/r05_bench_default.json 2> $O/bench_default.err
+timeout 400 python bench.py --full --workload cfg2 --precision 0 --steps 10 --warmup 3 --no-decode --no-cpu-baseline --no-others --no-pmc > $O/r05_bench_cfg2_f32.json 2> $O/bench_f32.err
 for wl in cfg1 cfg3 cfg4 ref_yaml; do
-  timeout 400 python bench.py --workload $wl --steps 20 --warmup 3 --no-decode > $O/r05_bench_$wl.json 2> $O/bench_$wl.err
+  timeout 400 python bench.py --full --workload $wl --steps 20 --warmup 3 --no-decode > $O/r05_bench_$wl.json 2> $O/bench_$wl.err
 done
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch -o f -- python $R/tools/pmc_probe.py > $O/fetch.log 2>&1 )
 ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write -o w -- python $R/tools/pmc_probe.py > $O/write.log 2>&1 )
