@@ -505,11 +505,12 @@ bool conv_slices(const ConvGeom &g, ConvSlices &sl) {
     if (sl.nco > CCH) sl.nco = sl.nco / CCH * CCH;                  // whole register passes
     sl.nci = (int)std::max((size_t)1, std::min((size_t)g.Ci, budget / ((size_t)sl.nco * KK)));
   }
-  sl.wnco = g.Co; sl.wnci = g.Ci;
+  // (the wgrad kernel's 256 threads hold one bias column each: at most 256 output channels per launch)
+  sl.wnco = std::min(g.Co, 256); sl.wnci = g.Ci;
   if (bank > (size_t)256 * WPT || (size_t)WG_P * ((size_t)g.Ci * KK + g.Co) > budget) {
     if ((size_t)WG_P * (KK + 1) > budget || KK > 256 * WPT) return false;
     sl.wnci = (int)std::max((size_t)1, std::min((size_t)g.Ci, (budget / WG_P - 1) / KK));
-    sl.wnco = std::max(1, std::min(g.Co, 256 * WPT / (sl.wnci * KK)));
+    sl.wnco = std::max(1, std::min(std::min(g.Co, 256), 256 * WPT / (sl.wnci * KK)));
     while ((size_t)WG_P * ((size_t)sl.wnci * KK + sl.wnco) > budget && sl.wnco > 1) --sl.wnco;
   }
   return true;

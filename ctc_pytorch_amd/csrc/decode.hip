@@ -775,6 +775,14 @@ constexpr int SURV_MAX = 256;
 constexpr int FAST_NCT = 1024 - 192;                           // candidate threads: waves 3..15
 constexpr int FAST_NTH = 1024, FAST_NWV = FAST_NTH / 64;      // 16 waves: the parallel phases are instruction-issue bound (~10 cycles per
                                                                // dependent instruction and wave), so more waves per SIMD is what shortens them
+// ln P_LM * alpha rounded on its own before it joins a sum -- as the LDS table holds it (LM_LDS) and as the reference computes it.  Without
+// the pragma the compiler fuses the product into the sum (v_fma_f64) in the global-memory variant only, and its scores then differed from the
+// LDS variant's in the last bits (beam_occ2 = 1 / 2 where the LM does not fit beside the trie, and V > 70 at any setting).
+__device__ __forceinline__ double lm_scaled(double lm, double alpha) {
+#pragma clang fp contract(off)
+  return lm * alpha;
+}
+
 template <int NPT, bool LM_LDS>
 __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   constexpr int NTH = FAST_NTH, NWV = FAST_NWV;
@@ -982,7 +990,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
       for (int i = 0; i < NPT; ++i) {
         const int bi = min(ci[i], FAST_WMAX - 1), k = max(ck[i], 0);
         const int c1c = min(max(c1[i], 0), V);
-        lmv[i] = LM_LDS ? lmA[c1c * V1 + k] : a.lm[(size_t)c1c * V1 + k] * a.alpha;
+        lmv[i] = LM_LDS ? lmA[c1c * V1 + k] : lm_scaled(a.lm[(size_t)c1c * V1 + k], a.alpha);
         lk[i] = lg[k];
         pbv[i] = bm_pB[bi];
         ptv[i] = bm_pT[bi];
@@ -1164,7 +1172,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
       // (context class of the parent labelling: its last class travels with the slot -- z_plast -- and its length is this one's minus one:
       // the LM term is read next to the ln p terms, not behind the parent slot)
       const int c1 = z_len > 1 ? max(z_plast, 0) : V, k = max(z_last, 0);
-      const double lmv = LM_LDS ? lmA[c1 * V1 + k] : a.lm[(size_t)c1 * V1 + k] * a.alpha;
+      const double lmv = LM_LDS ? lmA[c1 * V1 + k] : lm_scaled(a.lm[(size_t)c1 * V1 + k], a.alpha);
       const double base = (c1 == k && rep_ok) ? p_pB : p_pT;
       const double pr = lgl + lmv + base;                           // == cand[mi * V + kk(z_last)]
       double s_nb = LOG_ZERO;
@@ -1646,10 +1654,13 @@ extern "C" int ctcn_beam_decode_nbest(const float *x, int input_is_prob, const i
   a.stats = g_beam_stats_dev;
 #endif
   const size_t cand_bytes = (size_t)W * V * sizeof(double);
-  const int gthreads = ctcn_get_option("beam_generic_threads");          // 0 (default): by beam width; 256 / 1024: forced (measurements)
+  const int gthreads = ctcn_get_option("beam_generic_threads");          // 0 (default): by beam width; 256 / 512 / 1024: forced (measurements)
   // (measured, tools/beam_generic_probe.py, 128 x 800 batches: 3 720 candidates per frame 7.9 -> 6.3 ms with 1 024 threads, 12 000: 21 -> 16 ms; 1 240: 4.7 -> 4.9)
-  const bool wide = gthreads == 1024 || (gthreads != 256 && gthreads != 512 && (W > 64 || (long)W * V > 3500));
-  const bool mid = gthreads == 512;
+  // The kernel gives every beam slot one thread (merge, stay entries, materialisation): a forced count is raised to the smallest instantiated
+  // one >= W, so the option never changes a result (256 threads at W = 300 left slots 256.. un-merged and read stale LDS).
+  const int need = gthreads == 0 ? ((W > 64 || (long)W * V > 3500) ? 1024 : 256) : std::max(gthreads, W);
+  const bool wide = need > 512;
+  const bool mid = !wide && need > 256;
   const void *kern = wide ? reinterpret_cast<const void *>(beam_kernel<1024>) : mid ? reinterpret_cast<const void *>(beam_kernel<512>) : reinterpret_cast<const void *>(beam_kernel<256>);
   // The kernel's STATIC LDS is ~46 KB since the selection holds its survivors there; the candidate table joins it in LDS only if the
   // whole block then fits what this device gives one workgroup (160 KB on gfx950; a 64-KB device falls back to the global table

@@ -936,9 +936,20 @@ def dropout(x, p, training):
         return x
     if p < 0.0 or p > 1.0:
         raise ValueError("dropout probability has to be between 0 and 1, but got %r" % (p,))
-    if p == 1.0:                    # torch: everything dropped (a memset; the gradient through it is zero, i.e. nothing to propagate)
-        return torch.zeros_like(x)
+    if p == 1.0:                    # torch: everything dropped (a memset), still in the graph: x.grad is zeros, not None
+        return _DropAll.apply(x)
     return _Dropout.apply(x, p)
+
+
+class _DropAll(torch.autograd.Function):
+    """dropout(p = 1): zeros forward and backward; no launch (torch keeps the node, so backward() through it works and leaves zero gradients)."""
+    @staticmethod
+    def forward(ctx, x):
+        return torch.zeros_like(x)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return torch.zeros_like(gy)
 
 
 # --------------------------------------------------------------------------------------------------

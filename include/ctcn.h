@@ -117,7 +117,8 @@ int ctcn_device_xcds(void);
  * measured SLOWER (cfg5, three searches in flight: 279 k -> 248 k utt/s peaky, 128 k -> 97 k flat; profiles/r05_beam_occ2_ab.txt) and kept
  * as an experiment switch.
  * "beam_generic_threads" = 0 (default): the generic beam kernel runs 256 threads per utterance, 1 024 beyond W = 64 or 3 500 candidates per frame;
- * 256 / 512 / 1024 force one (measurements).
+ * 256 / 512 / 1024 force one (measurements); a forced count below W is raised to the smallest of the three >= W (one thread per beam slot), so
+ * the option never changes a result.
  * "beam_bitonic" = 1 (default): the generic beam kernel ranks up to 256 survivors of its pruning bound (the reference's W = 200 leaves ~1.1 W) by a
  * bitonic sort on waves 0-3 (DPP / v_permlane swaps); 0 = by counting pairs, as it does for more survivors.  Same labellings and scores.
  * "beam_cand_global" = 0 (default): 1 keeps the generic kernel's candidate table in global memory (L2) even where the LDS would hold it; the LM

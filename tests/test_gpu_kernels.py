@@ -771,6 +771,152 @@ def test_batchnorm_large_rows_vs_torch(dev):
     assert maxabs(rm, bn.running_mean) < 1e-5 and maxabs(rv, bn.running_var) < 1e-5
 
 
+# name: (outer, C, inner, variant)   variant: None | "rows4_off" (option bn_rows4 = 0, held bit for bit to = 1) | "offset" (x at storage offset 1)
+BN_BRANCH_CASES = {
+    "rows_c14": (1000, 14, 1, None),            # C % 4 != 0: dword column sums, bn_apply_kernel / bn_dx_kernel on rows
+    "rows_c62": (2001, 62, 1, None),
+    "rows_c321": (777, 321, 1, None),           # ragged 64-column blocks
+    "rows_c640_dword": (3000, 640, 1, "rows4_off"),
+    "rows_c64_offset1": (1500, 64, 1, "offset"),    # 4-B aligned base: the dword kernels although C % 4 == 0
+    "nchw_ich3": (2, 8, 40000, None),           # few planes: each cut into ich = 3 inner pieces
+    "nchw_opc4": (200, 64, 37, None),           # many planes: opc = 4 planes per chunk
+    "nchw_vec0": (3, 16, 399, None),            # inner % 4 != 0: scalar loads
+}
+
+
+def _bn_gpu(dev, x0, g0, b0, dy0, rm0, rv0, outer, C, inner, relu, offset):
+    from ctc_pytorch_amd import ops
+    if offset:
+        buf = torch.zeros(x0.size + 1, device=dev)
+        buf[1:].copy_(torch.from_numpy(x0).reshape(-1))
+        x = buf[1:].view(x0.shape)
+        assert x.data_ptr() % 16 == 4
+    else:
+        x = torch.from_numpy(x0).to(dev)
+    x.requires_grad_(True)
+    g = torch.from_numpy(g0).to(dev).requires_grad_(True)
+    b = torch.from_numpy(b0).to(dev).requires_grad_(True)
+    rm, rv = torch.from_numpy(rm0).to(dev), torch.from_numpy(rv0).to(dev)
+    y = ops.batch_norm(x, g, b, rm, rv, outer, C, inner, True, 0.1, 1e-5, relu)
+    y.backward(torch.from_numpy(dy0).to(dev))
+    ye = ops.batch_norm(x.detach(), g.detach(), b.detach(), rm, rv, outer, C, inner, False, 0.1, 1e-5, relu)
+    torch.cuda.synchronize()
+    return [t.detach().cpu().clone() for t in (y, x.grad, g.grad, b.grad, rm, rv, ye)]
+
+
+@pytest.mark.parametrize("relu", [False, True])
+@pytest.mark.parametrize("case", sorted(BN_BRANCH_CASES))
+def test_batchnorm_branch_matrix_vs_oracle(dev, case, relu):
+    """BatchNorm's launch branches that the model shapes never take -- dword column sums (C % 4 != 0, a 4-B aligned base, bn_rows4 = 0),
+    bn_apply_kernel / bn_dx_kernel on rows, NCHW chunking with ich > 1 / opc > 1, NCHW without 16-B loads -- against oracle/np_ref.py in
+    float64: training forward (+ ReLU), dx / dgamma / dbeta, the running statistics, the eval forward from them.  Gates of
+    test_batchnorm_large_rows_vs_torch: outputs and dx 2e-5 absolute (scaled by magnitude), dgamma / dbeta rel-L2 1e-5."""
+    from ctc_pytorch_amd import ops
+    outer, C, inner, variant = BN_BRANCH_CASES[case]
+    rs = np.random.RandomState(outer + 7 * C + inner)
+    shape = (outer, C) if inner == 1 else (outer, C, inner)
+    x0 = (rs.standard_normal(shape) * 2.5 + rs.standard_normal((1, C) + (1,) * (len(shape) - 2))).astype(np.float32)
+    g0 = (rs.random_sample(C) + 0.5).astype(np.float32)
+    b0 = (rs.standard_normal(C) * 0.3).astype(np.float32)
+    dy0 = rs.standard_normal(shape).astype(np.float32)
+    rm0 = (rs.standard_normal(C) * 0.1).astype(np.float32)
+    rv0 = (rs.random_sample(C) + 0.5).astype(np.float32)
+    if variant == "rows4_off":
+        ops.set_option("bn_rows4", 0)
+        try:
+            got = _bn_gpu(dev, x0, g0, b0, dy0, rm0, rv0, outer, C, inner, relu, False)
+        finally:
+            ops.set_option("bn_rows4", 1)
+        # (the two kernels' float64 column sums agree to float64 rounding and reach every output through float32)
+        for a, c in zip(got, _bn_gpu(dev, x0, g0, b0, dy0, rm0, rv0, outer, C, inner, relu, False)):
+            assert torch.equal(a, c)
+    else:
+        got = _bn_gpu(dev, x0, g0, b0, dy0, rm0, rv0, outer, C, inner, relu, variant == "offset")
+    y, dx, dg, db, rm, rv, ye = got
+    to2 = lambda a: np.asarray(a, dtype=np.float64).reshape(outer, C, inner).transpose(0, 2, 1).reshape(-1, C)
+    x2, dy2 = to2(x0), to2(dy0)
+    n = x2.shape[0]
+    y_ref, mean, var = R.bn_train_fwd(x2, g0.astype(np.float64), b0.astype(np.float64))
+    mask = np.ones_like(y_ref)
+    if relu:
+        mask = (to2(y.numpy()) > 0).astype(np.float64)         # the kernel's own ReLU mask (float32 values at 0 can fall either way) ...
+        sure = np.abs(y_ref) > 1e-4
+        assert np.array_equal(mask[sure], (y_ref[sure] > 0).astype(np.float64))     # ... which is the oracle's away from 0
+        y_ref = np.maximum(y_ref, 0.0)
+    dx_ref, dg_ref, db_ref = R.bn_train_bwd(x2, g0.astype(np.float64), mean, var, dy2 * mask)
+    scale = lambda a: max(1.0, float(np.abs(a).max()))
+    assert maxabs(to2(y.numpy()), y_ref) < 2e-5 * scale(y_ref)
+    assert maxabs(to2(dx.numpy()), dx_ref) < 2e-5 * scale(dx_ref)
+    assert rel_l2(dg, dg_ref) < 1e-5 and rel_l2(db, db_ref) < 1e-5
+    rm_ref, rv_ref = R.bn_running_update(rm0.astype(np.float64), rv0.astype(np.float64), mean, var, n, 0.1)
+    assert maxabs(rm, rm_ref) < 1e-5 * scale(rm_ref) and maxabs(rv, rv_ref) < 1e-5 * scale(rv_ref)
+    ye_ref = R.bn_eval_fwd(x2, g0.astype(np.float64), b0.astype(np.float64), rm.numpy().astype(np.float64), rv.numpy().astype(np.float64))
+    if relu:
+        ye_ref = np.maximum(ye_ref, 0.0)
+    assert maxabs(to2(ye.numpy()), ye_ref) < 2e-5 * scale(ye_ref)
+
+
+@pytest.mark.parametrize("V", [1, 2, 63, 64, 65, 128, 129, 200, 1000, 4097])
+def test_log_softmax_argmax_edges_vs_oracle(dev, V):
+    """ops.log_softmax forward / backward and ctcn_argmax (alone, and fused into ctcn_log_softmax_fwd) at class counts either side of the
+    64-lane wave, 1 and 4 097, on 23 rows (no multiple of the 4 rows per workgroup): Gaussian rows, exact ties (logits quantised to
+    integers), rows with -inf entries, rows shifted by +-1e4.  Against oracle/np_ref.py in float64, per row with eps = 2^-23:
+      log-probs: 4 eps (|max z| + ln V + 1) -- the float32 rounding of max + ln(sum) and of x - lse -- plus (V / 64 + 8) eps for the
+      float32 sum of exp (V / 64 terms per lane, six butterfly levels, 1-ulp expf);
+      dlogits (against log_softmax_bwd of the kernel's own log-probs): 4 eps (max|g| + max p (V / 64 + 8) sum|g|) -- the float32 sum of g
+      and the rounding of g - p * sum;
+      -inf entries stay -inf with dlogits = g.  The arg-max equals np_ref.argmax_first of the kernel's own log-probs exactly (lowest
+      index on ties)."""
+    from ctc_pytorch_amd import _lib, ops
+    rs = np.random.RandomState(V)
+    rows = 23
+    z = rs.standard_normal((rows, V)) * 3.0
+    z[3:8] = np.round(z[3:8] / 2.0)                         # exact ties
+    if V > 1:
+        for r in range(8, 12):                              # -inf entries (the row's first maximum stays finite)
+            k = rs.randint(0, V, size=max(1, V // 3))
+            z[r, k] = -np.inf
+            z[r, rs.randint(0, V)] = 5.0
+        z[12:15] += 1e4
+        z[15:18] -= 1e4
+        z[18, :] = 0.0                                      # all equal: arg-max 0
+    z = z.astype(np.float32)
+    g = rs.standard_normal((rows, V)).astype(np.float32)
+    zt = torch.from_numpy(z).to(dev).requires_grad_(True)
+    lp = ops.log_softmax(zt)
+    lp.backward(torch.from_numpy(g).to(dev))
+    torch.cuda.synchronize()
+    L = _lib.lib()
+    am = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+    assert L.ctcn_argmax(ctypes.c_void_p(lp.data_ptr()), ctypes.c_void_p(am.data_ptr()), rows, V, None) == 0
+    lp2 = torch.empty_like(lp)
+    am2 = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+    assert L.ctcn_log_softmax_fwd(ctypes.c_void_p(zt.data_ptr()), ctypes.c_void_p(lp2.data_ptr()), ctypes.c_void_p(am2.data_ptr()), rows, V, None) == 0
+    torch.cuda.synchronize()
+    lp_k = lp.detach().cpu().numpy()
+    dz = zt.grad.cpu().numpy().astype(np.float64)
+    assert np.array_equal(lp2.cpu().numpy(), lp_k)
+    eps = 2.0 ** -23
+    fin = np.isfinite(z)
+    with np.errstate(invalid="ignore"):
+        lp_ref = R.log_softmax(z)
+    assert np.array_equal(np.isfinite(lp_k), fin) and np.all(lp_k[~fin] == -np.inf)
+    zmax = np.abs(np.where(fin, z, 0.0)).max(axis=1)
+    tol_lp = 4 * eps * (zmax + np.log(V) + 1.0) + (V / 64 + 8) * eps
+    err_lp = np.where(fin, np.abs(lp_k.astype(np.float64) - np.where(fin, lp_ref, 0.0)), 0.0).max(axis=1)
+    assert np.all(err_lp <= tol_lp), (err_lp / tol_lp).max()
+    dz_ref = R.log_softmax_bwd(lp_k.astype(np.float64), g.astype(np.float64))
+    p = np.exp(lp_k.astype(np.float64))
+    g64 = np.abs(g.astype(np.float64))
+    tol_dz = 4 * eps * (g64.max(axis=1) + p.max(axis=1) * (V / 64 + 8) * g64.sum(axis=1))
+    assert np.all(np.abs(dz - dz_ref).max(axis=1) <= tol_dz)
+    assert np.array_equal(dz[~fin], g.astype(np.float64)[~fin])
+    want = R.argmax_first(lp_k)
+    assert np.array_equal(am.cpu().numpy(), want) and np.array_equal(am2.cpu().numpy(), want)
+    if V > 1:
+        assert np.array_equal(want[18:19], [0])
+
+
 def _load_conv_model(dev):
     from ctc_pytorch_amd import nn
     from ctc_pytorch_amd.models.model_ctc import CTC_Model
@@ -867,7 +1013,13 @@ CONV_CASES = [  # B, Ci, Hi, Wi, Co, kh, kw, sh, sw, ph, pw
     (2, 32, 12, 30, 32, 3, 21, 2, 2, 0, 0),    # ... layer 2: 32 x 32 x 3 x 21 = 258 KB of filters
     (1, 20, 6, 9, 70, 5, 5, 1, 2, 2, 1),       # more than 64 output channels, 140 KB, ragged slices
     (1, 3, 40, 40, 2, 29, 29, 3, 2, 14, 14),   # 841 taps per channel pair (the direct kernels' limit is ~900): one-channel slices in the weight gradient
+    # more than 256 output channels: the direct weight-gradient kernel's 256 threads hold one bias column each (launches of <= 256 channels)
+    (2, 1, 9, 40, 300, 1, 11, 1, 1, 0, 5),     # a Conv1d-like front end, bank unsliced
+    (1, 1, 5, 64, 512, 1, 11, 1, 2, 0, 5),
+    (2, 3, 7, 9, 260, 3, 3, 1, 1, 1, 1),
+    (1, 4, 6, 20, 300, 3, 3, 1, 1, 1, 1),      # 10 800 taps > 256 * WPT: the sliced weight gradient (284 channels per slice before the clamp)
 ]
+_CONV_WIDE = CONV_CASES[-4:]
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
@@ -900,6 +1052,68 @@ def test_conv2d_vs_oracle(dev, case, mfma):
     assert maxabs(y, y_ref) < 2e-6 * scale(y_ref) * np.sqrt(Ci * kh * kw)
     assert maxabs(xt.grad, dx_ref) < 2e-6 * scale(dx_ref) * np.sqrt(Co * kh * kw)
     assert rel_l2(wt.grad, dw_ref) < 2e-6 and rel_l2(bt.grad, db_ref) < 2e-6
+
+
+@pytest.mark.parametrize("case", _CONV_WIDE)
+@pytest.mark.parametrize("mfma", [1, 0])
+def test_conv2d_bwd_wide_bias_from_nan_workspace(dev, case, mfma):
+    """ctcn_conv2d_bwd called directly with its workspace, dw and dbias filled with NaN beforehand: every partial the reduction reads must
+    have been written by this call (a bias column left unwritten -- output channels >= 256 -- shows as NaN whatever the caching allocator
+    would have left there).  dx, dw and dbias against the float64 oracle under test_conv2d_vs_oracle's gates."""
+    from ctc_pytorch_amd import _lib
+    B, Ci, Hi, Wi, Co, kh, kw, sh, sw, ph, pw = case
+    rs = np.random.RandomState(sum(case) + 1)
+    x = rs.standard_normal((B, Ci, Hi, Wi)).astype(np.float32)
+    w = (rs.standard_normal((Co, Ci, kh, kw)) / np.sqrt(Ci * kh * kw)).astype(np.float32)
+    Ho, Wo = (Hi + 2 * ph - kh) // sh + 1, (Wi + 2 * pw - kw) // sw + 1
+    dy = rs.standard_normal((B, Co, Ho, Wo)).astype(np.float32)
+    dx_ref, dw_ref, db_ref = R.conv2d_bwd(x.astype(np.float64), w.astype(np.float64), (sh, sw), (ph, pw), dy.astype(np.float64))
+    L = _lib.lib()
+    L.ctcn_set_option(b"conv_mfma", mfma)
+    try:
+        nbytes = L.ctcn_conv2d_ws_bytes(*case)
+        ws = torch.full(((max(nbytes, 4) + 3) // 4,), float("nan"), dtype=torch.float32, device=dev)
+        xt, wt, dyt = (torch.from_numpy(a).to(dev) for a in (x, w, dy))
+        dx = torch.full(x.shape, float("nan"), dtype=torch.float32, device=dev)
+        dw = torch.full(w.shape, float("nan"), dtype=torch.float32, device=dev)
+        db = torch.full((Co,), float("nan"), dtype=torch.float32, device=dev)
+        P = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = L.ctcn_conv2d_bwd(P(xt), P(wt), P(dyt), P(dx), P(dw), P(db), *case, 0.0, P(ws), ws.numel() * 4,
+                               ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+    finally:
+        L.ctcn_set_option(b"conv_mfma", 1)
+    assert rc == 0, L.ctcn_last_error()
+    scale = lambda a: max(1.0, float(np.abs(a).max()))
+    for t in (dx, dw, db):
+        assert bool(torch.isfinite(t).all())
+    assert maxabs(dx, dx_ref) < 2e-6 * scale(dx_ref) * np.sqrt(Co * kh * kw)
+    assert rel_l2(dw, dw_ref) < 2e-6 and rel_l2(db, db_ref) < 2e-6
+
+
+def test_conv1d_300_channels_vs_torch_cpu(dev):
+    """nn.Conv1d(1, 300, 11) (LayerCNN's one-element kernel branch with a wide bank) forward and backward against torch's CPU Conv1d in
+    float64 with the same parameters: y, dx, dweight and dbias -- the bias gradient of channels 256 .. 299 included."""
+    from ctc_pytorch_amd import nn
+    torch.manual_seed(11)
+    ref = tnn.Conv1d(1, 300, 11).double()
+    m = nn.Conv1d(1, 300, 11)
+    with torch.no_grad():
+        m.weight.copy_(ref.weight.float()); m.bias.copy_(ref.bias.float())
+        ref.weight.copy_(m.weight.double()); ref.bias.copy_(m.bias.double())
+    m = m.to(dev)
+    x = torch.randn(3, 1, 57)
+    xr = x.double().requires_grad_(True)
+    yr = ref(xr)
+    dy = torch.randn(yr.shape)
+    yr.backward(dy.double())
+    xg = x.to(dev).requires_grad_(True)
+    y = m(xg)
+    y.backward(dy.to(dev))
+    assert tuple(y.shape) == tuple(yr.shape)
+    assert maxabs(y, yr) < 2e-6 * max(1.0, float(yr.abs().max())) * np.sqrt(11)
+    assert maxabs(xg.grad, xr.grad) < 2e-6 * max(1.0, float(xr.grad.abs().max())) * np.sqrt(300 * 11)
+    assert rel_l2(m.weight.grad, ref.weight.grad) < 2e-6 and rel_l2(m.bias.grad, ref.bias.grad) < 2e-6
 
 
 @pytest.mark.parametrize("shape,k", [((2, 3, 9, 8), (2, 2)), ((1, 2, 7, 5), (3, 1)), ((2, 1, 4, 6), (1, 3)), ((1, 1, 5, 5), (5, 5)),
@@ -2203,12 +2417,16 @@ def test_beam_wide_vs_c_oracle(dev, regime, W):
 
 @pytest.mark.parametrize("regime", ["peaky", "flat"])
 @pytest.mark.parametrize("W,threads,cand_global,bitonic", [(200, 512, 1, 1), (200, 512, 0, 1), (200, 1024, 1, 1), (61, 512, 1, 1), (300, 512, 1, 1), (200, 256, 1, 1),
-                                                             (200, 0, 0, 0), (128, 0, 0, 0), (200, 512, 1, 0)])
+                                                             (200, 0, 0, 0), (128, 0, 0, 0), (200, 512, 1, 0),
+                                                             (257, 256, 0, 1), (300, 256, 0, 1), (513, 512, 0, 1), (600, 512, 0, 1), (1024, 512, 0, 1)])
 def test_beam_generic_kernel_occupancy_options(dev, regime, W, threads, cand_global, bitonic):
     """The generic search at other thread counts / candidate-table placements (options beam_generic_threads = 512, beam_cand_global: two
     512-thread searches per CU -- tools/wide_beam_probe.py) and with its survivors ranked by pair counts instead of
     the bitonic sort (beam_bitonic = 0) returns the labellings, status words and float64 scores of the C oracle and, bit for bit, of the
-    default configuration."""
+    default configuration.  A forced thread count below W (the kernel gives every beam slot one thread) is raised to the next instantiated
+    one: 257 / 300 at 256 threads, 513 / 600 / 1 024 at 512 -- these returned wrong labellings before (slots >= the thread count were never
+    merged or materialised).  Those beams fill within three frames at V = 62, so their utterances are cut short: the C oracle's time grows
+    with W^2."""
     from ctc_pytorch_amd import ops
     from ctc_pytorch_amd.utils.NgramLM import LanguageModel
     V, T, B = 62, 120, 6
@@ -2216,6 +2434,9 @@ def test_beam_generic_kernel_occupancy_options(dev, regime, W, threads, cand_glo
     tab = LanguageModel(os.path.join(G, "lm_phone_bg.arpa")).table([i2c[i] for i in range(V)])
     lp = synth.make_logprobs(seed=83 if regime == "peaky" else 84, T=T, B=B, V=V, regime=regime)
     lens = [120, 97, 64, 110, 33, 81]
+    if threads and W > threads:
+        cap = 12 if W <= 300 else (8 if W <= 600 else 5)
+        lens = [min(l, cap) for l in lens]
     probs = torch.exp(torch.from_numpy(lp))
     want, wscore, wst = beam_ref.decode_ids(probs.numpy().transpose(1, 0, 2), lens, tab, 0.01, W)
     base = ops.beam_decode(probs.to(dev), lens, tab, 0.01, W, 0, input_is_prob=True)
@@ -2231,6 +2452,81 @@ def test_beam_generic_kernel_occupancy_options(dev, regime, W, threads, cand_glo
     assert list(st) == list(wst) and got == [list(map(int, s_)) for s_ in want]
     assert np.all(np.abs(np.asarray(score) - np.asarray(wscore)) <= 4 * np.spacing(np.abs(np.asarray(wscore))))
     assert got == base[0] and np.array_equal(np.asarray(score), np.asarray(base[1])) and list(st) == list(base[2])
+
+
+def _fast_layout(T, V, W, occ2):
+    """Test-side restatement of decode.hip's fast_layout rule: (ok, lm_lds, trie_slots).  ok false = ctcn_beam_decode silently takes the
+    generic kernel instead, so the occ2 cases assert the branch they are meant to cover with it."""
+    npt = -(-W * V // 832)                                          # FAST_NCT = 1 024 - 192 candidate threads
+    core = (W * V + 2 * V) * 8 + (W * V + T) * 4
+    lm = (V + 1) * (V + 1) * 8
+    budget = (68 if occ2 else 144) * 1024
+    want_lm = lm <= 40 * 1024 and occ2 != 2
+    slots = 16384
+    while slots > 1024 and core + slots * 4 + (lm if want_lm else 0) > budget:
+        slots >>= 1
+    lm_lds = occ2 != 2 and core + slots * 4 + lm <= budget
+    lds = core + slots * 4 + (lm if lm_lds else 0)
+    ok = W <= 60 and 0 < npt <= 4 and V <= 256 and W * T + 2 < (1 << 24) and T < (1 << 22) and lds <= budget
+    return ok, lm_lds, slots
+
+
+_OCC2_ORACLE = {}
+
+# name: (V, T, B, W, regime, alpha, nbest, {occ2: (lm_lds, trie_slots)} or None)
+OCC2_CASES = {
+    "cfg5_flat": (62, 800, 16, 20, "flat", 0.1, 1, {1: (True, 4096), 2: (False, 8192)}),   # ~10 000 labellings: past the small LDS trie
+    "w52_lm_global": (62, 160, 8, 52, "peaky", 0.1, 1, {1: (False, 1024), 2: (False, 4096)}),  # occ2 = 1: the LM does not fit next to the trie
+    "v3_w2": (3, 70, 14, 2, "flat", 0.0, 1, None),
+    "v4_w5": (4, 70, 14, 5, "flat", 0.5, 1, None),
+    "v8_w33": (8, 70, 14, 33, "flat", 0.3, 1, None),
+    "v5_w52": (5, 70, 14, 52, "flat", 1.0, 1, None),
+    "nbest": (62, 160, 12, 20, "peaky", 0.1, 3, None),
+}
+
+
+@pytest.mark.parametrize("occ2", [1, 2])
+@pytest.mark.parametrize("case", sorted(OCC2_CASES))
+def test_beam_occ2_variants_vs_c_oracle(dev, case, occ2):
+    """Option beam_occ2 = 1 / 2: the fast beam search compiled for two workgroups per CU, LM table in LDS or in global memory, with a 4 096 /
+    8 192-slot LDS trie (16 384 by default), so that it spills to the global node table far earlier.  Labellings and status equal the C
+    restatement of BeamSearch.py, float64 scores within 4 ulp, and everything bit for bit equal to beam_occ2 = 0.  Cases: a cfg5-shaped flat
+    batch (the trie overflows), W = 52 where occ2 = 1 leaves the LM in global memory, small alphabets with beams wider than V and 0 / 1 / T
+    frame utterances (test_beam_fuzz_small_alphabets_vs_c_oracle's), an n-best output.  Every case must take the fast kernel (_fast_layout)."""
+    from ctc_pytorch_amd import ops
+    from ctc_pytorch_amd.utils.NgramLM import LanguageModel
+    V, T, B, W, regime, alpha, nbest, expect = OCC2_CASES[case]
+    ok, lm_lds, slots = _fast_layout(T, V, W, occ2)
+    assert ok, case
+    if expect is not None:
+        assert (lm_lds, slots) == expect[occ2], (case, lm_lds, slots)
+    rs = np.random.RandomState(1000 * V + W)
+    lp = synth.make_logprobs(seed=V * 7 + W, T=T, B=B, V=V, regime=regime)
+    if V == 62:
+        i2c = synth.int2char(V)
+        tab = LanguageModel(os.path.join(G, "lm_phone_bg.arpa")).table([i2c[i] for i in range(V)])
+        lens = list(rs.randint(T // 2, T + 1, size=B))
+    else:
+        tab = -3.0 * rs.random_sample((V + 1, V + 1))
+        lens = list(rs.randint(T // 3, T + 1, size=B))
+        lens[0], lens[1], lens[2] = 0, 1, T
+    probs = torch.exp(torch.from_numpy(lp))
+    if case not in _OCC2_ORACLE:                       # (the C oracle once per case, for both variants)
+        _OCC2_ORACLE[case] = beam_ref.decode_ids_nbest(probs.numpy().transpose(1, 0, 2), lens, tab, alpha, W, nbest)
+    want, wscore, wst = _OCC2_ORACLE[case]
+    runs = {}
+    for o in (0, occ2):
+        ops.set_option("beam_occ2", o)
+        try:
+            runs[o] = ops.beam_decode_nbest(probs.to(dev), lens, tab, alpha, W, nbest, 0, input_is_prob=True)
+        finally:
+            ops.set_option("beam_occ2", 0)
+    got, score, st = runs[occ2]
+    assert list(st) == list(wst), case
+    assert got == want, case
+    score, wscore = np.asarray(score), np.asarray(wscore)
+    assert np.all(np.abs(score - wscore) <= 4 * np.spacing(np.abs(wscore))), case
+    assert got == runs[0][0] and np.array_equal(score, np.asarray(runs[0][1])) and list(st) == list(runs[0][2])
 
 
 def test_beam_width_above_the_maximum_is_refused(dev):

@@ -127,6 +127,20 @@ def test_dropout_stream_offsets_are_disjoint_across_threads():
         ops._drop_counter[0] = snap
 
 
+def test_dropout_p1_keeps_the_graph():
+    """ops.dropout(p = 1) returns zeros that stay in the autograd graph, as torch's dropout does: y requires grad, backward() works with
+    nothing else needing a gradient, and the upstream parameter's gradient is zeros rather than None.  No launch: CPU tensors."""
+    from ctc_pytorch_amd import ops
+    x = torch.randn(3, 5, dtype=torch.float32).requires_grad_(True)
+    y = ops.dropout(x, 1.0, True)
+    assert y.requires_grad and torch.equal(y, torch.zeros(3, 5))
+    (y * 2.0).sum().backward()
+    assert x.grad is not None and torch.equal(x.grad, torch.zeros(3, 5))
+    want = torch.nn.functional.dropout(x, 1.0, True)
+    assert want.requires_grad == y.requires_grad and torch.equal(want.detach(), y.detach())
+    assert ops.dropout(x, 1.0, False) is x                  # eval: the identity
+
+
 def test_layer_cnn_one_element_kernel_branch_surface():
     """LayerCNN's Conv1d / BatchNorm1d / MaxPool1d branch (reference model_ctc.py:48-50, 54-55): the module tree and the state_dict (keys, order,
     the (Co, Ci, k) weight shape) are the reference's -- tests/golden/layer_cnn1d.npz holds its state_dict -- and the torch-CPU stack of the
