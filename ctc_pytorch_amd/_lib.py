@@ -74,6 +74,10 @@ _SIGS = {
     "ctcn_ctc_fwd_both": (I, [P, P, P, P, P, P, P, I, I, I, I, P]),
     "ctcn_ctc_grad": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "ctcn_sum_f32": (I, [P, P, I, P]),
+    "ctcn_ctc_fwd_ex": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
+    "ctcn_ctc_grad_ex": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, I, I, I, I, P]),
+    "ctcn_ctc_reduce": (I, [P, P, P, I, I, I, P]),
+    "ctcn_ctc_pack_targets": (I, [P, ctypes.c_int64, P, P, I, I, P]),
     "ctcn_adam_step": (I, [P, P, P, P, Z, F, F, F, F, F, I, P]),
     "ctcn_greedy_collapse": (I, [P, Z, Z, P, P, P, I, I, I, P]),
     "ctcn_edit_distance": (I, [P, P, P, P, P, I, I, I, I, P]),

@@ -1,9 +1,13 @@
 // ctc.hip -- log_softmax (+arg-max), CTC alpha/beta lattice and gradient for gfx950.
 //
 // replaces: nn.LogSoftmax(dim=-1) (reference timit/models/model_ctc.py:140,168,181), torch.max(out,-1)
-// (timit/steps/train_ctc.py:51, timit/utils/ctcDecoder.py:163) and nn.CTCLoss(reduction='sum') forward +
-// autograd backward (train_ctc.py:144,47-48,63).  Arithmetic: SURVEY Appendix A.6-A.8; blank = 0,
-// zero_infinity = False (an infeasible utterance gives nll = +inf and NaN gradient rows, as torch).
+// (timit/steps/train_ctc.py:51, timit/utils/ctcDecoder.py:163) and nn.CTCLoss forward + autograd backward
+// (train_ctc.py:144,47-48,63).  Arithmetic: SURVEY Appendix A.6-A.8.  torch's whole nn.CTCLoss contract: any blank index (a
+// run-time argument: the lattice's skip rule is a parity test on the state, not a comparison with the blank's value), the
+// reductions 'none' / 'sum' / 'mean' (the gradient scale of utterance b is gscale[b * stride], times 1 / (B * max(L_b, 1)) for
+// 'mean'; the reductions themselves are ctcn_ctc_reduce, elementwise.hip) and zero_infinity (an infeasible utterance gives
+// nll = +inf; its gradient rows are NaN as in torch, or exact zeros with zero_infinity).  Concatenated 1-D targets are packed
+// into the padded (B, Lmax) layout the lattice reads by ctc_pack_targets_kernel.
 //
 // Kernels (all HBM/latency-bound, no MFMA):
 //   log_softmax fwd : one wave per row, lanes over classes, max / sum-exp by wave shuffles; the arg-max
@@ -96,7 +100,8 @@ __device__ __forceinline__ float lse3(float x0, float x1, float x2) {
 template <int DIR, int NS, bool ADD>
 __device__ __forceinline__ void ctc_lattice_body(float *smem, const float *__restrict__ lp, const int64_t *__restrict__ targets,
                                                  const int64_t *__restrict__ in_len, const int64_t *__restrict__ tgt_len,
-                                                 float *__restrict__ alpha, float *__restrict__ nll, int T, int B, int V, int Lmax) {
+                                                 float *__restrict__ alpha, float *__restrict__ nll, int T, int B, int V, int Lmax,
+                                                 int blank) {
   constexpr int PF = 4;
   constexpr bool ACC = DIR < 0 && ADD;
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -110,7 +115,7 @@ __device__ __forceinline__ void ctc_lattice_body(float *smem, const float *__res
   const int S = 2 * L + 1;
   float *buf0 = smem, *buf1 = smem + Smax;
   int *ext = reinterpret_cast<int *>(smem + 2 * Smax);
-  for (int s = tid; s < S; s += CTC_THREADS) ext[s] = (s & 1) ? (int)targets[(size_t)b * Lmax + (s >> 1)] : 0;
+  for (int s = tid; s < S; s += CTC_THREADS) ext[s] = (s & 1) ? (int)targets[(size_t)b * Lmax + (s >> 1)] : blank;
   __syncthreads();
   if (Tb <= 0) {
     if (DIR > 0 && tid == 0) nll[b] = L == 0 ? 0.0f : INFINITY;
@@ -125,8 +130,9 @@ __device__ __forceinline__ void ctc_lattice_body(float *smem, const float *__res
     my_ext[k] = 0; my_skip[k] = false;
     if (s < S) {
       my_ext[k] = ext[s];
-      if (DIR > 0) my_skip[k] = s >= 2 && ext[s] != 0 && ext[s] != ext[s - 2];
-      else my_skip[k] = s + 2 < S && ext[s] != 0 && ext[s] != ext[s + 2];
+      // label states (odd s) skip over the blank between two different labels; a label may equal any class value, the blank's included
+      if (DIR > 0) my_skip[k] = s >= 2 && (s & 1) && ext[s] != ext[s - 2];
+      else my_skip[k] = s + 2 < S && (s & 1) && ext[s] != ext[s + 2];
     }
   }
   const int t_first = DIR > 0 ? 0 : Tb - 1;
@@ -213,9 +219,9 @@ template <int DIR, int NS>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_lattice_kernel(const float *__restrict__ lp, const int64_t *__restrict__ targets,
                                                                   const int64_t *__restrict__ in_len,
                                                                   const int64_t *__restrict__ tgt_len, float *__restrict__ alpha,
-                                                                  float *__restrict__ nll, int T, int B, int V, int Lmax) {
+                                                                  float *__restrict__ nll, int T, int B, int V, int Lmax, int blank) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  ctc_lattice_body<DIR, NS, true>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax);
+  ctc_lattice_body<DIR, NS, true>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank);
 }
 
 // (Measured and dropped: one wave per (utterance, pass) with the lattice in registers -- lane l holding states 2l and 2l + 1,
@@ -231,10 +237,10 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_lattices_kernel(const float *
                                                                    const int64_t *__restrict__ in_len,
                                                                    const int64_t *__restrict__ tgt_len, float *__restrict__ alpha,
                                                                    float *__restrict__ beta, float *__restrict__ nll, int T, int B, int V,
-                                                                   int Lmax) {
+                                                                   int Lmax, int blank) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  if (blockIdx.y == 0) ctc_lattice_body<1, NS, false>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax);
-  else ctc_lattice_body<-1, NS, false>(smem, lp, targets, in_len, tgt_len, beta, nll, T, B, V, Lmax);
+  if (blockIdx.y == 0) ctc_lattice_body<1, NS, false>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank);
+  else ctc_lattice_body<-1, NS, false>(smem, lp, targets, in_len, tgt_len, beta, nll, T, B, V, Lmax, blank);
 }
 
 // online log-sum-exp accumulator
@@ -254,26 +260,29 @@ struct Lse {
 // lane scanning all L labels at every frame (O(V L) per frame: 81 us at cfg2), the workgroup sorts the label positions by class once
 // (counting sort in LDS, positions of a class in increasing order) and a class lane walks its own positions only -- the same terms
 // added in the same order, so the result is bit-identical to the scan.
+// Upstream gradient of utterance b: gscale[b * gs_stride] (stride 0: the scalar of 'sum' / 'mean', 1: the (B,) vector of 'none'), divided
+// by B * max(L_b, 1) for 'mean'.  zinf (zero_infinity): the rows of an utterance with nll = +inf are exact zeros.
 constexpr int GRAD_TCH = 16;
 template <bool SEP>
 __global__ __launch_bounds__(256) void ctc_grad_kernel(const float *__restrict__ lp, const int64_t *__restrict__ targets,
                                                        const int64_t *__restrict__ in_len, const int64_t *__restrict__ tgt_len,
                                                        const float *__restrict__ ab, const float *__restrict__ bt,
                                                        const float *__restrict__ nll,
-                                                       const float *__restrict__ gscale, float *__restrict__ grad, int T, int B, int V,
-                                                       int Lmax) {
+                                                       const float *__restrict__ gscale, int gs_stride, int mean, int zinf, int blank,
+                                                       float *__restrict__ grad, int T, int B, int V, int Lmax) {
   extern __shared__ int gsm[];                 // start[V + 1] | pos[Lmax]
   int *start = gsm, *pos = gsm + V + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.y, t0 = blockIdx.x * GRAD_TCH, t1 = min(T, t0 + GRAD_TCH);
   const bool bad = in_len[b] < 0 || in_len[b] > T || tgt_len[b] < 0 || tgt_len[b] > Lmax;          // see ctc_lattice_body
-  const int Tb = bad ? 0 : (int)in_len[b], L = bad ? 0 : (int)tgt_len[b];
+  const bool zero = !bad && zinf && nll[b] == INFINITY;
+  const int Tb = bad ? 0 : zero ? 0 : (int)in_len[b], L = bad ? 0 : (int)tgt_len[b];
   const int64_t *tg = targets + (size_t)b * Lmax;
   if (!bad && t0 < Tb) {
     // class c (thread c) counts its label positions, a serial prefix sum over the V classes, then every class writes its positions
     for (int c = threadIdx.x; c < V; c += blockDim.x) {
       int n = 0;
-      if (c > 0)
+      if (c != blank)
         for (int j = 0; j < L; ++j) n += (int)tg[j] == c;
       start[c + 1] = n;
     }
@@ -285,14 +294,15 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float *__restrict__
     __syncthreads();
     for (int c = threadIdx.x; c < V; c += blockDim.x) {
       int k = start[c];
-      if (c > 0)
+      if (c != blank)
         for (int j = 0; j < L; ++j)
           if ((int)tg[j] == c) pos[k++] = j;
     }
     __syncthreads();
   }
   const int Smax = 2 * Lmax + 1;
-  const float gs = gscale[0];
+  float gs = gscale[(size_t)b * gs_stride];
+  if (mean) gs /= (float)B * (float)max(L, 1);
   for (int t = t0 + wave; t < t1; t += 4) {
     const size_t pair = (size_t)t * B + b;
     float *g = grad + pair * V;
@@ -300,7 +310,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float *__restrict__
       for (int c = lane; c < V; c += 64) g[c] = __uint_as_float(0x7fc00000u);
       continue;
     }
-    if (t >= Tb) {
+    if (t >= Tb) {                              // past the input, or an infeasible utterance under zero_infinity
       for (int c = lane; c < V; c += 64) g[c] = 0.0f;
       continue;
     }
@@ -318,7 +328,7 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float *__restrict__
     const float lcab0 = M == -INFINITY ? -INFINITY : M + logf(ssum);
     for (int c = lane; c < V; c += 64) {
       float lcab;
-      if (c == 0) lcab = lcab0;
+      if (c == blank) lcab = lcab0;
       else {
         Lse a{-INFINITY, 0.0f};
         for (int k = start[c]; k < start[c + 1]; ++k) a.add(AB(2 * pos[k] + 1));
@@ -431,6 +441,25 @@ __global__ __launch_bounds__(64) void edit_distance_wave_kernel(const int32_t *_
   }
 }
 
+// Concatenated 1-D targets (torch's second layout) -> the padded (B, Lmax) rows the lattice reads, zero-filled past each length.  One
+// workgroup per utterance; its offset is the exclusive prefix sum of the lengths before it (negative lengths count as 0: the lattice
+// answers NaN for them), summed by the workgroup in a fixed order.  Nothing past flat[n_flat) is read.
+__global__ __launch_bounds__(256) void ctc_pack_targets_kernel(const int64_t *__restrict__ flat, int64_t n_flat, const int64_t *__restrict__ tgt_len,
+                                                               int64_t *__restrict__ padded, int Lmax) {
+  __shared__ long long part[4];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long long off = 0;
+  for (int i = threadIdx.x; i < b; i += 256) off += tgt_len[i] > 0 ? tgt_len[i] : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) off += __shfl_xor(off, o, 64);
+  if (lane == 0) part[wave] = off;
+  __syncthreads();
+  off = part[0] + part[1] + part[2] + part[3];
+  const int64_t L = tgt_len[b];
+  int64_t *row = padded + (size_t)b * Lmax;
+  for (int j = threadIdx.x; j < Lmax; j += 256) row[j] = (j < L && off + j < n_flat) ? flat[off + j] : 0;
+}
+
 }  // namespace
 
 extern "C" int ctcn_edit_distance(const int32_t *a, const int32_t *a_len, const int64_t *b, const int64_t *b_len, int32_t *out,
@@ -475,50 +504,69 @@ extern "C" int ctcn_log_softmax_bwd(const float *lp, const float *dlp, float *dl
   return CTCN_OK;
 }
 
+// The lattice passes of every CTC entry point: alpha alone (ctcn_ctc_fwd, ctcn_ctc_fwd_ex without beta), the beta pass added into alpha
+// in place (ctcn_ctc_bwd's one-buffer reserve), or alpha and beta side by side in one launch (ctcn_ctc_fwd_both, ctcn_ctc_fwd_ex).
+enum CtcPasses { CTC_ALPHA, CTC_BETA_INTO_ALPHA, CTC_ALPHA_BETA };
+static int ctc_lattices(const char *who, CtcPasses passes, const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len,
+                        float *alpha, float *beta, float *nll, int T, int B, int V, int Lmax, int blank, hipStream_t st) {
+  if (2 * Lmax + 1 > CTC_THREADS * CTC_NS) { ctcn_set_error("%s: label length %d > %d unsupported", who, Lmax, (CTC_THREADS * CTC_NS - 1) / 2); return CTCN_EUNSUPPORTED; }
+  const size_t sm = (size_t)(3 * (2 * Lmax + 1)) * sizeof(float);
+  const int ns = ceil_div(2 * Lmax + 1, CTC_THREADS);
+  if (passes == CTC_ALPHA) {
+#define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattice_kernel<1, NS>), dim3(B), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank)
+    if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
+#undef CTC_LAUNCH
+  } else if (passes == CTC_BETA_INTO_ALPHA) {
+#define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattice_kernel<-1, NS>), dim3(B), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, alpha, (float *)nullptr, T, B, V, Lmax, blank)
+    if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
+#undef CTC_LAUNCH
+  } else {
+#define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattices_kernel<NS>), dim3(B, 2), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, alpha, beta, nll, T, B, V, Lmax, blank)
+    if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
+#undef CTC_LAUNCH
+  }
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+// The gradient of every CTC entry point.  beta == NULL: alpha holds alpha + beta (ctcn_ctc_bwd's in-place reserve).
+static int ctc_grad(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, const float *alpha,
+                    const float *beta, const float *nll, const float *gscale, int gs_stride, int reduction, int zero_infinity, int blank,
+                    float *grad_lp, int T, int B, int V, int Lmax, hipStream_t st) {
+  const size_t sm = (size_t)(V + 1 + Lmax) * sizeof(int);
+  const int mean = reduction == CTCN_REDUCTION_MEAN, zinf = zero_infinity != 0;
+  if (beta == nullptr)
+    hipLaunchKernelGGL(ctc_grad_kernel<false>, dim3(ceil_div(T, GRAD_TCH), B), dim3(256), sm, st, lp, targets, in_len, tgt_len, alpha,
+                       (const float *)nullptr, nll, gscale, gs_stride, mean, zinf, blank, grad_lp, T, B, V, Lmax);
+  else
+    hipLaunchKernelGGL(ctc_grad_kernel<true>, dim3(ceil_div(T, GRAD_TCH), B), dim3(256), sm, st, lp, targets, in_len, tgt_len, alpha, beta,
+                       nll, gscale, gs_stride, mean, zinf, blank, grad_lp, T, B, V, Lmax);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
 extern "C" int ctcn_ctc_fwd(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, float *alpha,
                             float *nll, int T, int B, int V, int Lmax, void *stream) {
   CTCN_REQUIRE(lp && in_len && tgt_len && alpha && nll && (targets || Lmax == 0), "ctcn_ctc_fwd: null pointer");
   CTCN_REQUIRE(T > 0 && B > 0 && V > 0 && Lmax >= 0, "ctcn_ctc_fwd: bad dims");
-  if (2 * Lmax + 1 > CTC_THREADS * CTC_NS) { ctcn_set_error("ctcn_ctc_fwd: label length %d > %d unsupported", Lmax, (CTC_THREADS * CTC_NS - 1) / 2); return CTCN_EUNSUPPORTED; }
-  const size_t sm = (size_t)(3 * (2 * Lmax + 1)) * sizeof(float);
-  const int ns = ceil_div(2 * Lmax + 1, CTC_THREADS);
-#define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattice_kernel<1, NS>), dim3(B), dim3(CTC_THREADS), sm, (hipStream_t)stream, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax)
-  if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
-#undef CTC_LAUNCH
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
+  return ctc_lattices("ctcn_ctc_fwd", CTC_ALPHA, lp, targets, in_len, tgt_len, alpha, nullptr, nll, T, B, V, Lmax, 0, (hipStream_t)stream);
 }
 
 extern "C" int ctcn_ctc_bwd(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, float *alpha,
                             const float *nll, const float *gscale, float *grad_lp, int T, int B, int V, int Lmax, void *stream) {
   CTCN_REQUIRE(lp && in_len && tgt_len && alpha && nll && gscale && grad_lp && (targets || Lmax == 0), "ctcn_ctc_bwd: null pointer");
   CTCN_REQUIRE(T > 0 && B > 0 && V > 0 && Lmax >= 0, "ctcn_ctc_bwd: bad dims");
-  if (2 * Lmax + 1 > CTC_THREADS * CTC_NS) { ctcn_set_error("ctcn_ctc_bwd: label length %d unsupported", Lmax); return CTCN_EUNSUPPORTED; }
-  const size_t sm = (size_t)(3 * (2 * Lmax + 1)) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  const int ns = ceil_div(2 * Lmax + 1, CTC_THREADS);
-#define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattice_kernel<-1, NS>), dim3(B), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, alpha, (float *)nullptr, T, B, V, Lmax)
-  if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
-#undef CTC_LAUNCH
-  CTCN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_grad_kernel<false>, dim3(ceil_div(T, GRAD_TCH), B), dim3(256), (size_t)(V + 1 + Lmax) * sizeof(int), st, lp, targets, in_len, tgt_len,
-                     alpha, (const float *)nullptr, nll, gscale, grad_lp, T, B, V, Lmax);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
+  const int rc = ctc_lattices("ctcn_ctc_bwd", CTC_BETA_INTO_ALPHA, lp, targets, in_len, tgt_len, alpha, nullptr, nullptr, T, B, V, Lmax, 0, st);
+  if (rc != CTCN_OK) return rc;
+  return ctc_grad(lp, targets, in_len, tgt_len, alpha, nullptr, nll, gscale, 0, CTCN_REDUCTION_SUM, 0, 0, grad_lp, T, B, V, Lmax, st);
 }
 
 extern "C" int ctcn_ctc_fwd_both(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, float *alpha,
                                  float *beta, float *nll, int T, int B, int V, int Lmax, void *stream) {
   CTCN_REQUIRE(lp && in_len && tgt_len && alpha && beta && nll && (targets || Lmax == 0), "ctcn_ctc_fwd_both: null pointer");
   CTCN_REQUIRE(T > 0 && B > 0 && V > 0 && Lmax >= 0, "ctcn_ctc_fwd_both: bad dims");
-  if (2 * Lmax + 1 > CTC_THREADS * CTC_NS) { ctcn_set_error("ctcn_ctc_fwd_both: label length %d > %d unsupported", Lmax, (CTC_THREADS * CTC_NS - 1) / 2); return CTCN_EUNSUPPORTED; }
-  const size_t sm = (size_t)(3 * (2 * Lmax + 1)) * sizeof(float);
-  const int ns = ceil_div(2 * Lmax + 1, CTC_THREADS);
-#define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattices_kernel<NS>), dim3(B, 2), dim3(CTC_THREADS), sm, (hipStream_t)stream, lp, targets, in_len, tgt_len, alpha, beta, nll, T, B, V, Lmax)
-  if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
-#undef CTC_LAUNCH
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
+  return ctc_lattices("ctcn_ctc_fwd_both", CTC_ALPHA_BETA, lp, targets, in_len, tgt_len, alpha, beta, nll, T, B, V, Lmax, 0, (hipStream_t)stream);
 }
 
 extern "C" int ctcn_ctc_grad(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, const float *alpha,
@@ -526,8 +574,34 @@ extern "C" int ctcn_ctc_grad(const float *lp, const int64_t *targets, const int6
                              void *stream) {
   CTCN_REQUIRE(lp && in_len && tgt_len && alpha && beta && nll && gscale && grad_lp && (targets || Lmax == 0), "ctcn_ctc_grad: null pointer");
   CTCN_REQUIRE(T > 0 && B > 0 && V > 0 && Lmax >= 0, "ctcn_ctc_grad: bad dims");
-  hipLaunchKernelGGL(ctc_grad_kernel<true>, dim3(ceil_div(T, GRAD_TCH), B), dim3(256), (size_t)(V + 1 + Lmax) * sizeof(int), (hipStream_t)stream, lp, targets,
-                     in_len, tgt_len, alpha, beta, nll, gscale, grad_lp, T, B, V, Lmax);
+  return ctc_grad(lp, targets, in_len, tgt_len, alpha, beta, nll, gscale, 0, CTCN_REDUCTION_SUM, 0, 0, grad_lp, T, B, V, Lmax, (hipStream_t)stream);
+}
+
+extern "C" int ctcn_ctc_fwd_ex(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, float *alpha,
+                               float *beta, float *nll, int T, int B, int V, int Lmax, int blank, void *stream) {
+  CTCN_REQUIRE(lp && in_len && tgt_len && alpha && nll && (targets || Lmax == 0), "ctcn_ctc_fwd_ex: null pointer");
+  CTCN_REQUIRE(T > 0 && B > 0 && V > 0 && Lmax >= 0 && alpha != beta, "ctcn_ctc_fwd_ex: bad dims");
+  CTCN_REQUIRE(blank >= 0 && blank < V, "ctcn_ctc_fwd_ex: blank %d outside [0, %d)", blank, V);
+  return ctc_lattices("ctcn_ctc_fwd_ex", beta ? CTC_ALPHA_BETA : CTC_ALPHA, lp, targets, in_len, tgt_len, alpha, beta, nll, T, B, V, Lmax, blank,
+                      (hipStream_t)stream);
+}
+
+extern "C" int ctcn_ctc_grad_ex(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, const float *alpha,
+                                const float *beta, const float *nll, const float *gscale, int gscale_stride, int reduction, int zero_infinity,
+                                int blank, float *grad_lp, int T, int B, int V, int Lmax, void *stream) {
+  CTCN_REQUIRE(lp && in_len && tgt_len && alpha && nll && gscale && grad_lp && (targets || Lmax == 0), "ctcn_ctc_grad_ex: null pointer");
+  CTCN_REQUIRE(T > 0 && B > 0 && V > 0 && Lmax >= 0, "ctcn_ctc_grad_ex: bad dims");
+  CTCN_REQUIRE(blank >= 0 && blank < V, "ctcn_ctc_grad_ex: blank %d outside [0, %d)", blank, V);
+  CTCN_REQUIRE(reduction == CTCN_REDUCTION_NONE || reduction == CTCN_REDUCTION_MEAN || reduction == CTCN_REDUCTION_SUM,
+               "ctcn_ctc_grad_ex: reduction %d", reduction);
+  CTCN_REQUIRE(gscale_stride == 0 || gscale_stride == 1, "ctcn_ctc_grad_ex: gscale_stride %d (0 or 1)", gscale_stride);
+  return ctc_grad(lp, targets, in_len, tgt_len, alpha, beta, nll, gscale, gscale_stride, reduction, zero_infinity, blank, grad_lp, T, B, V,
+                  Lmax, (hipStream_t)stream);
+}
+
+extern "C" int ctcn_ctc_pack_targets(const int64_t *flat, int64_t n_flat, const int64_t *tgt_len, int64_t *padded, int B, int Lmax, void *stream) {
+  CTCN_REQUIRE(tgt_len && padded && (flat || n_flat == 0) && n_flat >= 0 && B > 0 && Lmax > 0, "ctcn_ctc_pack_targets: bad args");
+  hipLaunchKernelGGL(ctc_pack_targets_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, flat, n_flat, tgt_len, padded, Lmax);
   CTCN_LAUNCH_CHECK();
   return CTCN_OK;
 }

@@ -59,6 +59,35 @@ __global__ void sum_kernel(const float *__restrict__ x, float *__restrict__ out,
   if (threadIdx.x == 0) out[0] = (status && *status != 0) ? __uint_as_float(0x7fc00000u) : (float)(s[0] + s[1] + s[2] + s[3]);
 }
 
+// nn.CTCLoss's reduction of the per-utterance losses, nll' = nll with +inf replaced by 0 under zero_infinity:
+// 'sum' out[0] = sum_b nll'_b, 'mean' out[0] = (1/B) sum_b nll'_b / max(L_b, 1), 'none' out[b] = nll'_b.  The sums are sum_kernel's: one
+// workgroup, the same fixed order and double partials ('sum' without zero_infinity gives its bits), and the same status-word rule.
+__global__ void ctc_reduce_kernel(const float *__restrict__ nll, const int64_t *__restrict__ tgt_len, float *__restrict__ out, int B,
+                                  int reduction, int zinf, const int *__restrict__ status) {
+  __shared__ double s[4];
+  const bool failed = status && *status != 0;
+  if (reduction == CTCN_REDUCTION_NONE) {
+    for (int i = threadIdx.x; i < B; i += 256) {
+      const float v = nll[i];
+      out[i] = failed ? __uint_as_float(0x7fc00000u) : (zinf && v == INFINITY) ? 0.0f : v;
+    }
+    return;
+  }
+  double a = 0.0;
+  for (int i = threadIdx.x; i < B; i += 256) {
+    const float v = (zinf && nll[i] == INFINITY) ? 0.0f : nll[i];
+    if (reduction == CTCN_REDUCTION_MEAN) a += (double)v / (double)(tgt_len[i] > 1 ? tgt_len[i] : 1);
+    else a += (double)v;
+  }
+  a = wave_sum_d(a);
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double t = s[0] + s[1] + s[2] + s[3];
+    out[0] = failed ? __uint_as_float(0x7fc00000u) : (float)(reduction == CTCN_REDUCTION_MEAN ? t / B : t);
+  }
+}
+
 // (B,C,T,F) -> (T,B,C*F): out[((t*B+b)*C + c)*F + f] = in[((b*C+c)*T + t)*F + f]
 __global__ void bctf_to_tbcf_kernel(const float *__restrict__ in, float *__restrict__ out, int B, int C, int T, int F, int to_tbcf) {
   const size_t total = (size_t)B * C * T * F;
@@ -148,6 +177,16 @@ extern "C" int ctcn_adam_step(float *p, const float *g, float *m, float *v, size
 extern "C" int ctcn_sum_f32(const float *x, float *out, int n, void *stream) {
   CTCN_REQUIRE(x && out && n >= 0, "ctcn_sum_f32: bad args");
   hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, out, n, (const int *)ctcn_status_word());
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_ctc_reduce(const float *nll, const int64_t *tgt_len, float *out, int B, int reduction, int zero_infinity, void *stream) {
+  CTCN_REQUIRE(nll && out && B > 0 && (tgt_len || reduction != CTCN_REDUCTION_MEAN), "ctcn_ctc_reduce: bad args");
+  CTCN_REQUIRE(reduction == CTCN_REDUCTION_NONE || reduction == CTCN_REDUCTION_MEAN || reduction == CTCN_REDUCTION_SUM,
+               "ctcn_ctc_reduce: reduction %d", reduction);
+  hipLaunchKernelGGL(ctc_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, nll, tgt_len, out, B, reduction, zero_infinity != 0,
+                     (const int *)ctcn_status_word());
   CTCN_LAUNCH_CHECK();
   return CTCN_OK;
 }

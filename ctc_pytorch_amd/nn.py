@@ -175,20 +175,26 @@ class LogSoftmax(_tnn.Module):
 
 
 class CTCLoss(_tnn.Module):
-    """nn.CTCLoss(blank=0, reduction='sum', zero_infinity=False) as called at train_ctc.py:144,47."""
+    """nn.CTCLoss(blank=0, reduction='mean', zero_infinity=False) with torch's whole contract: any blank in [0, C), reduction 'none' /
+    'sum' / 'mean' (each loss divided by its target length clamped to >= 1, then averaged over the batch), zero_infinity, padded (B, S) or
+    concatenated 1-D targets, lengths as tensors (host or device), lists or tuples, unbatched (T, C) input.  The reference calls it with
+    reduction='sum' (train_ctc.py:144,47).  float32 log-probs on the device only.
+
+    Under data parallelism 'mean' averages over the rank's OWN shard: the drivers (steps/train_ctc.main, bench.py) keep 'sum' / B_global,
+    which is what the reference's single-process mean of the global batch amounts to."""
 
     def __init__(self, blank=0, reduction="mean", zero_infinity=False):
         super().__init__()
-        if blank != 0:
-            raise NotImplementedError("blank index 0 only (data_loader.py:16)")
-        if zero_infinity:
-            raise NotImplementedError("zero_infinity=False only (train_ctc.py:144)")
-        if reduction not in ("sum", "none"):
-            raise NotImplementedError("reduction='sum' (train_ctc.py:144) or 'none'")
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError("%s is not a valid value for reduction" % (reduction,))
+        if int(blank) < 0:
+            raise ValueError("blank must be >= 0, got %d" % int(blank))
+        self.blank = int(blank)
         self.reduction = reduction
+        self.zero_infinity = bool(zero_infinity)
 
     def forward(self, log_probs, targets, input_lengths, target_lengths):
-        return ops.ctc_loss(log_probs, targets, torch.as_tensor(input_lengths), torch.as_tensor(target_lengths), self.reduction)
+        return ops.ctc_loss(log_probs, targets, input_lengths, target_lengths, self.blank, self.reduction, self.zero_infinity)
 
 
 class MaxPool2d(_tnn.Module):

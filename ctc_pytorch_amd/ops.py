@@ -4,6 +4,7 @@ Every function here enqueues hand-written gfx950 kernels on torch's current HIP 
 for device memory, autograd bookkeeping and nothing else.  Tensors must live on a ROCm device -- a CPU
 tensor raises (the product has no CPU path; the CPU restatement lives in oracle/ and is test-only).
 """
+import collections
 import ctypes
 import os
 import numpy as np
@@ -1067,66 +1068,115 @@ def argmax_last(lp):
     return out
 
 
+_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}           # CTCN_REDUCTION_* of include/ctcn.h (torch's at::Reduction values)
+
+CtcArgs = collections.namedtuple("CtcArgs", "lp targets in_len tgt_len Lmax flat batched")
+
+
+def _lengths(x):
+    """input_lengths / target_lengths as torch.nn.CTCLoss takes them (tensor on the host or the device, list, tuple, int) -> 1-D int64 tensor,
+    left where it is."""
+    t = x if torch.is_tensor(x) else torch.as_tensor(x, dtype=torch.int64)
+    return t.reshape(-1).to(dtype=torch.int64)
+
+
+def ctc_prepare(log_probs, targets, input_lengths, target_lengths):
+    """Host-side normalisation of torch.nn.CTCLoss's arguments -> CtcArgs(lp (T,B,V), targets (B,S) padded or 1-D concatenated, in_len (B),
+    tgt_len (B) int64, Lmax = the padded row length the lattice reads, flat, batched).  Pure: no kernel, no device allocation.  Unbatched
+    (T,C) log-probs come with 1-element or 0-d lengths and 1-D targets and are treated as a batch of one.  Lengths that are already on the
+    host are checked against the tensors here (torch raises for them); device lengths are checked by the kernels (NaN for the utterance),
+    except that concatenated targets need Lmax = max(target_lengths): one host read of the lengths, as torch's own CUDA path does."""
+    if log_probs.dim() not in (2, 3):
+        raise ValueError("ctc_pytorch_amd.CTCLoss: log_probs must be (T, B, C) or unbatched (T, C), got %s" % (tuple(log_probs.shape),))
+    batched = log_probs.dim() == 3
+    lp = log_probs if batched else log_probs.unsqueeze(1)
+    T, B, _ = lp.shape
+    targets = targets if torch.is_tensor(targets) else torch.as_tensor(targets, dtype=torch.int64)
+    in_len, tgt_len = _lengths(input_lengths), _lengths(target_lengths)
+    if targets.dim() not in (1, 2):
+        raise ValueError("ctc_pytorch_amd.CTCLoss: targets must be (B, S) padded or 1-D concatenated, got %s" % (tuple(targets.shape),))
+    flat = targets.dim() == 1
+    if in_len.numel() != B or tgt_len.numel() != B or (not flat and targets.shape[0] != B):
+        raise ValueError("ctc_pytorch_amd.CTCLoss: batch size mismatch (log_probs %d, targets %s, input_lengths %d, target_lengths %d)"
+                         % (B, tuple(targets.shape), in_len.numel(), tgt_len.numel()))
+    if flat:
+        tl_host = tgt_len.cpu()
+        if int(tl_host.min()) < 0:
+            raise ValueError("ctc_pytorch_amd.CTCLoss: target_lengths must be >= 0, got min %d" % int(tl_host.min()))
+        if int(tl_host.sum()) > targets.numel():
+            raise ValueError("ctc_pytorch_amd.CTCLoss: sum(target_lengths) = %d > %d concatenated targets" % (int(tl_host.sum()), targets.numel()))
+        Lmax = int(tl_host.max())
+    else:
+        Lmax = targets.shape[1]
+    # torch.nn.CTCLoss raises on lengths outside the tensors; lengths still on the host are checked here for free, lengths
+    # already on the device are checked by the kernels (NaN loss and NaN gradient rows for the offending utterance)
+    for name, t, hi in (("input_lengths", in_len, T), ("target_lengths", tgt_len, Lmax)):
+        if not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) > hi):
+            raise ValueError("ctc_pytorch_amd.CTCLoss: %s must lie in [0, %d], got min %d max %d" % (name, hi, int(t.min()), int(t.max())))
+    return CtcArgs(lp, targets, in_len, tgt_len, Lmax, flat, batched)
+
+
 class _CTCLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, lp, targets, in_len, tgt_len, reduce_sum):
-        _need_gpu(lp)
-        lp = _f32c(lp)
+    def forward(ctx, lp, targets, in_len, tgt_len, Lmax, flat, blank, reduction, zero_infinity):
         T, B, V = lp.shape
         dev = lp.device
-        targets = targets.to(device=dev, dtype=torch.int64)
-        if targets.dim() == 1:
-            raise NotImplementedError("ctc_pytorch_amd.CTCLoss: concatenated 1-D targets are not used by the reference "
-                                      "(train_ctc.py:47 passes (B,Lmax)); pass padded 2-D targets")
-        targets = targets.contiguous()
-        # torch.nn.CTCLoss raises on lengths outside the tensors; lengths still on the host are checked here for free, lengths
-        # already on the device are checked by the kernels (NaN loss and NaN gradient rows for the offending utterance)
-        for name, t, hi in (("input_lengths", in_len, T), ("target_lengths", tgt_len, targets.shape[1])):
-            if not t.is_cuda and t.numel() and (int(t.min()) < 0 or int(t.max()) > hi):
-                raise ValueError("ctc_pytorch_amd.CTCLoss: %s must lie in [0, %d], got min %d max %d" % (name, hi, int(t.min()), int(t.max())))
-        if in_len.numel() != B or tgt_len.numel() != B or targets.shape[0] != B:
-            raise ValueError("ctc_pytorch_amd.CTCLoss: batch size mismatch (log_probs %d, targets %d, input_lengths %d, target_lengths %d)"
-                             % (B, targets.shape[0], in_len.numel(), tgt_len.numel()))
-        in_len = in_len.to(device=dev, dtype=torch.int64).contiguous()
-        tgt_len = tgt_len.to(device=dev, dtype=torch.int64).contiguous()
-        Lmax = targets.shape[1]
+        targets = targets.to(device=dev, dtype=torch.int64).contiguous()
+        in_len = in_len.to(device=dev).contiguous()
+        tgt_len = tgt_len.to(device=dev).contiguous()
+        L = _lib.lib()
+        if flat:                    # concatenated -> the padded rows the lattice reads, on the device
+            padded = torch.empty((B, Lmax), dtype=torch.int64, device=dev)
+            if Lmax > 0:
+                _lib.check(L.ctcn_ctc_pack_targets(_ptr(targets), targets.numel(), _ptr(tgt_len), _ptr(padded), B, Lmax, _lib.stream_ptr()),
+                           "ctc_pack_targets")
+            targets = padded
         alpha = torch.empty((T, B, 2 * Lmax + 1), dtype=torch.float32, device=dev)
         nll = torch.empty(B, dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        if ctx.needs_input_grad[0]:
-            # a gradient will be wanted: beta now, beside alpha, in the same launch (two independent T-step chains)
-            beta = torch.empty_like(alpha)
-            _lib.check(L.ctcn_ctc_fwd_both(_ptr(lp), _ptr(targets), _ptr(in_len), _ptr(tgt_len), _ptr(alpha), _ptr(beta), _ptr(nll),
-                                           T, B, V, Lmax, _lib.stream_ptr()), "ctc_fwd_both")
+        # a gradient will be wanted: beta now, beside alpha, in the same launch (two independent T-step chains)
+        beta = torch.empty_like(alpha) if ctx.needs_input_grad[0] else None
+        _lib.check(L.ctcn_ctc_fwd_ex(_ptr(lp), _ptr(targets), _ptr(in_len), _ptr(tgt_len), _ptr(alpha), _ptr(beta), _ptr(nll),
+                                     T, B, V, Lmax, blank, _lib.stream_ptr()), "ctc_fwd_ex")
+        if beta is not None:
             ctx.save_for_backward(lp, targets, in_len, tgt_len, alpha, beta, nll)
-        else:
-            _lib.check(L.ctcn_ctc_fwd(_ptr(lp), _ptr(targets), _ptr(in_len), _ptr(tgt_len), _ptr(alpha), _ptr(nll), T, B, V, Lmax,
-                                      _lib.stream_ptr()), "ctc_fwd")
         ctx.dims = (T, B, V, Lmax)
-        ctx.reduce_sum = reduce_sum
-        if not reduce_sum:
-            return nll.clone()
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        _lib.check(L.ctcn_sum_f32(_ptr(nll), _ptr(out), B, _lib.stream_ptr()), "sum")
+        ctx.mode = (blank, reduction, zero_infinity)
+        out = torch.empty(B if reduction == _REDUCTIONS["none"] else (), dtype=torch.float32, device=dev)
+        _lib.check(L.ctcn_ctc_reduce(_ptr(nll), _ptr(tgt_len), _ptr(out), B, reduction, int(zero_infinity), _lib.stream_ptr()), "ctc_reduce")
         return out
 
     @staticmethod
     def backward(ctx, g):
         lp, targets, in_len, tgt_len, alpha, beta, nll = ctx.saved_tensors
         T, B, V, Lmax = ctx.dims
-        if not ctx.reduce_sum:
-            raise NotImplementedError("ctc_pytorch_amd.CTCLoss(reduction='none').backward: use reduction='sum' (train_ctc.py:144)")
-        g = g.to(dtype=torch.float32).contiguous()
+        blank, reduction, zero_infinity = ctx.mode
+        g = g.to(dtype=torch.float32)
+        if g.dim() == 1 and g.stride(0) in (0, 1):         # 'none': (B,) upstream gradient, or the expanded scalar of nll.sum()
+            stride = g.stride(0)
+        else:
+            g = _f32c(g)
+            stride = 0 if g.dim() == 0 else 1
         grad = torch.empty_like(lp)
-        _lib.check(_lib.lib().ctcn_ctc_grad(_ptr(lp), _ptr(targets), _ptr(in_len), _ptr(tgt_len), _ptr(alpha), _ptr(beta), _ptr(nll),
-                                            _ptr(g), _ptr(grad), T, B, V, Lmax, _lib.stream_ptr()), "ctc_grad")
-        return grad, None, None, None, None
+        _lib.check(_lib.lib().ctcn_ctc_grad_ex(_ptr(lp), _ptr(targets), _ptr(in_len), _ptr(tgt_len), _ptr(alpha), _ptr(beta), _ptr(nll),
+                                               _ptr(g), stride, reduction, int(zero_infinity), blank, _ptr(grad), T, B, V, Lmax,
+                                               _lib.stream_ptr()), "ctc_grad_ex")
+        return grad, None, None, None, None, None, None, None, None
 
 
-def ctc_loss(lp, targets, in_len, tgt_len, reduction="sum"):
-    if reduction not in ("sum", "none"):
-        raise NotImplementedError("ctc_pytorch_amd.CTCLoss: reduction=%r (the reference uses 'sum', train_ctc.py:144)" % reduction)
-    return _CTCLoss.apply(lp, targets, in_len, tgt_len, reduction == "sum")
+def ctc_loss(lp, targets, in_len, tgt_len, blank=0, reduction="sum", zero_infinity=False):
+    """torch.nn.functional.ctc_loss on the HIP kernels, in its argument order: any blank in [0, C), reduction 'none' / 'sum' / 'mean'
+    (default 'sum', the reference's, train_ctc.py:144; nn.CTCLoss keeps torch's 'mean'), zero_infinity, padded (B, S) or concatenated 1-D
+    targets, unbatched (T, C) log-probs.  float32 log-probs on the device only (no CPU fallback)."""
+    if reduction not in _REDUCTIONS:
+        raise ValueError("%s is not a valid value for reduction" % (reduction,))
+    _need_gpu(lp)
+    lp = _f32c(lp)
+    a = ctc_prepare(lp, targets, in_len, tgt_len)
+    V = a.lp.shape[2]
+    if not 0 <= int(blank) < V:
+        raise ValueError("ctc_pytorch_amd.CTCLoss: blank must lie in [0, %d), got %d" % (V, int(blank)))
+    out = _CTCLoss.apply(a.lp, a.targets, a.in_len, a.tgt_len, a.Lmax, a.flat, int(blank), _REDUCTIONS[reduction], bool(zero_infinity))
+    return out if a.batched else out.squeeze(0)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -27,6 +27,11 @@ extern "C" {
 #define CTCN_EUNSUPPORTED (-3)
 #define CTCN_EWORKSPACE (-4)  /* workspace too small */
 
+/* reduction of the CTC loss (the values of torch's at::Reduction) */
+#define CTCN_REDUCTION_NONE 0
+#define CTCN_REDUCTION_MEAN 1
+#define CTCN_REDUCTION_SUM 2
+
 #define CTCN_CELL_LSTM 0 /* gate rows i,f,g,o */
 #define CTCN_CELL_GRU 1  /* gate rows r,z,n */
 #define CTCN_CELL_TANH 2 /* Elman RNN, tanh */
@@ -368,6 +373,27 @@ int ctcn_ctc_grad(const float *lp, const int64_t *targets, const int64_t *in_len
                   int T, int B, int V, int Lmax, void *stream);
 /* out[0] = sum_b nll[b]  (deterministic order) */
 int ctcn_sum_f32(const float *x, float *out, int n, void *stream);
+/* The whole nn.CTCLoss(blank, reduction, zero_infinity) contract; the four entry points above are these with blank = 0,
+ * reduction 'sum', zero_infinity = 0 (bit for bit).
+ * fwd_ex: ctcn_ctc_fwd_both with beta != NULL, ctcn_ctc_fwd with beta == NULL (alpha only: no gradient wanted).  The extended
+ *   label string is blank, target[0], blank, ..., blank; blank must lie in [0, V) and labels should differ from it (as in torch).
+ * grad_ex: ctcn_ctc_grad with beta != NULL; beta == NULL means alpha already holds alpha + beta.  The gradient of utterance b is
+ *   scaled by gscale[b * gscale_stride] (stride 0: the DEVICE scalar upstream gradient of 'sum' / 'mean'; 1: the (B) upstream
+ *   gradient of 'none'), divided by B * max(tgt_len[b], 1) when reduction == CTCN_REDUCTION_MEAN.  zero_infinity != 0: the rows
+ *   of an utterance with nll = +inf are 0 instead of NaN.  Rows of utterances with lengths outside the tensors stay NaN.
+ * reduce: nll' = nll with +inf replaced by 0 if zero_infinity; NONE: out (B) = nll'; SUM: out[0] = sum_b nll'_b; MEAN:
+ *   out[0] = (1/B) sum_b nll'_b / max(tgt_len[b], 1) (tgt_len may be NULL unless MEAN).  One workgroup, fixed order, double
+ *   partials; NaN (every output) while the status word of ctcn_set_status_buffer is set, as ctcn_sum_f32.
+ * pack_targets: concatenated targets flat (n_flat) int64 + tgt_len (B) -> padded (B, Lmax) int64, row b = flat[o_b .. o_b +
+ *   tgt_len[b]) (o_b = sum of the lengths before b, negative ones counted as 0) truncated to Lmax, zeros after; nothing past
+ *   flat[n_flat) is read.  Lmax > 0. */
+int ctcn_ctc_fwd_ex(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, float *alpha,
+                    float *beta, float *nll, int T, int B, int V, int Lmax, int blank, void *stream);
+int ctcn_ctc_grad_ex(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, const float *alpha,
+                     const float *beta, const float *nll, const float *gscale, int gscale_stride, int reduction, int zero_infinity,
+                     int blank, float *grad_lp, int T, int B, int V, int Lmax, void *stream);
+int ctcn_ctc_reduce(const float *nll, const int64_t *tgt_len, float *out, int B, int reduction, int zero_infinity, void *stream);
+int ctcn_ctc_pack_targets(const int64_t *flat, int64_t n_flat, const int64_t *tgt_len, int64_t *padded, int B, int Lmax, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Adam with L2-coupled weight decay over one flat buffer; replaces torch.optim.Adam.step
