@@ -78,6 +78,8 @@ _SIGS = {
     "ctcn_ctc_grad_ex": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, I, I, I, I, P]),
     "ctcn_ctc_reduce": (I, [P, P, P, I, I, I, P]),
     "ctcn_ctc_pack_targets": (I, [P, ctypes.c_int64, P, P, I, I, P]),
+    "ctcn_ctc_align_ws_bytes": (Z, [I, I, I]),
+    "ctcn_ctc_align": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, Z, P]),
     "ctcn_adam_step": (I, [P, P, P, P, Z, F, F, F, F, F, I, P]),
     "ctcn_greedy_collapse": (I, [P, Z, Z, P, P, P, I, I, I, P]),
     "ctcn_edit_distance": (I, [P, P, P, P, P, I, I, I, I, P]),

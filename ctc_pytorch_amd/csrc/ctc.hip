@@ -460,6 +460,208 @@ __global__ __launch_bounds__(256) void ctc_pack_targets_kernel(const int64_t *__
   for (int j = threadIdx.x; j < Lmax; j += 256) row[j] = (j < L && off + j < n_flat) ? flat[off + j] : 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Forced alignment (ctcn_ctc_align): the alpha chain in the max-plus semiring plus a back-pointer trace.
+//   v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if the loss allows the skip) + lp[t, ext(s)]   -- ONE float32 add, never fused
+//   ties: the smallest move wins (a candidate replaces the best so far only if strictly greater), so the result is a function of the
+//   input alone and a float32 restatement on the host is bit-identical.
+// One workgroup per utterance, the forward chain laid out as ctc_lattice_body (state s = tid + k * CTC_THREADS, double-buffered LDS row,
+// gathers PF frames ahead, one LDS barrier per frame).  The move of (t, s) is a 2-bit code; the 16 lanes tid & ~15 .. tid | 15 hold 16
+// consecutive states, so two wave ballots hand the first lane of each group of 16 the packed word of its group (low bits in [0,16), high
+// bits in [16,32)): one dword store per 16 states, no sub-dword write, no LDS atomic.  Rows of W = ceil(Smax / 16) words per frame live
+//   BPLDS : in dynamic LDS behind the value rows (cfg2: 800 frames x 8 words = 25 KB), where the trace -- a chain of Tb dependent reads
+//           walked by one lane -- pays LDS latency per frame;
+//   else  : in the caller's workspace (B, T, W), brought back ALIGN_GWORDS words at a time by the whole workgroup for the lane to walk.
+// The trace runs in chunks of up to ALIGN_CH frames: lane 0 writes the chunk's states into LDS, then the workgroup, a thread per frame, writes
+// paths / frame_scores and the span ends (a state that differs from its neighbour in time).
+// -DCTCN_ALIGN_FORWARD_ONLY (measurement builds, tools/align_bench.py): the kernel stops after the forward chain -- outputs are NOT valid.  The -1 / 0 fills of padding are stores issued
+// before the chain, which never waits for them.
+constexpr int ALIGN_CH = 1024;                     // frames per trace chunk (its states wait in LDS for the output phase)
+constexpr int ALIGN_WALK = 8;                      // frames the walking lane takes per LDS round trip (2 * 7 < 16: two words per row cover them)
+constexpr int ALIGN_GWORDS = 2048;                 // workspace branch: LDS words for the rows of a chunk (>= 8 frames at Smax = 4095)
+constexpr size_t ALIGN_LDS_LIMIT = 64 * 1024;      // dynamic LDS of a launch that has not opted in to more (of the CU's 160 KB)
+
+static inline int align_row_words(int Lmax) { return ceil_div(2 * Lmax + 1, 16); }
+static inline size_t align_lds_fixed(int Lmax) { return (size_t)(3 * (2 * Lmax + 1) + ALIGN_CH + 2) * sizeof(float); }
+// host arithmetic on the shapes only: the same (T, Lmax) always takes the same branch
+static inline bool align_rows_in_lds(int T, int Lmax) {
+  return align_lds_fixed(Lmax) + (size_t)T * align_row_words(Lmax) * sizeof(uint32_t) <= ALIGN_LDS_LIMIT;
+}
+
+template <int NS, bool BPLDS>
+__global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(const float *__restrict__ lp, const int64_t *__restrict__ targets,
+                                                                const int64_t *__restrict__ in_len, const int64_t *__restrict__ tgt_len,
+                                                                int32_t *__restrict__ paths, float *__restrict__ frame_scores,
+                                                                float *__restrict__ score, int32_t *__restrict__ ok, int32_t *__restrict__ starts,
+                                                                int32_t *__restrict__ ends, uint32_t *__restrict__ ws, int T, int B, int V, int Lmax,
+                                                                int blank) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int PF = 4;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int Smax = 2 * Lmax + 1, W = (Smax + 15) >> 4;
+  const bool bad = in_len[b] < 0 || in_len[b] > T || tgt_len[b] < 0 || tgt_len[b] > Lmax;        // see ctc_lattice_body
+  const int Tb = bad ? 0 : (int)in_len[b], L = bad ? 0 : (int)tgt_len[b];
+  int32_t *prow = paths + (size_t)b * T;
+  float *frow = frame_scores + (size_t)b * T;
+  int32_t *srow = starts ? starts + (size_t)b * Lmax : nullptr, *erow = ends ? ends + (size_t)b * Lmax : nullptr;
+  // padding: frames past the input, tokens past the label
+  for (int t = Tb + tid; t < T; t += CTC_THREADS) { prow[t] = -1; frow[t] = 0.0f; }
+  for (int j = L + tid; j < Lmax; j += CTC_THREADS) {
+    if (srow) srow[j] = -1;
+    if (erow) erow[j] = -1;
+  }
+  auto no_alignment = [&](float sc) {
+    for (int t = tid; t < Tb; t += CTC_THREADS) { prow[t] = -1; frow[t] = 0.0f; }
+    for (int j = tid; j < L; j += CTC_THREADS) {
+      if (srow) srow[j] = -1;
+      if (erow) erow[j] = -1;
+    }
+    if (tid == 0) { score[b] = sc; ok[b] = 0; }
+  };
+  if (bad) { no_alignment(__uint_as_float(0x7fc00000u)); return; }
+  if (Tb == 0) {
+    if (L > 0) no_alignment(-INFINITY);
+    else if (tid == 0) { score[b] = 0.0f; ok[b] = 1; }
+    return;
+  }
+  const int S = 2 * L + 1;
+  float *buf0 = smem, *buf1 = smem + Smax;
+  int *ext = reinterpret_cast<int *>(smem + 2 * Smax);
+  int *st = ext + Smax;                                             // st[1 + i]: state at frame t0 + i of the chunk; st[0], st[n + 1]: its neighbours in time
+  uint32_t *bpl = reinterpret_cast<uint32_t *>(st + ALIGN_CH + 2);  // BPLDS: row of frame t at bpl + t * W; else the rows of the current chunk
+  uint32_t *bpg = BPLDS ? nullptr : ws + (size_t)b * T * W;         // row of frame t at bpg + t * W
+  for (int s = tid; s < S; s += CTC_THREADS) ext[s] = (s & 1) ? (int)targets[(size_t)b * Lmax + (s >> 1)] : blank;
+  __syncthreads();
+  int my_ext[NS];
+  bool my_skip[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const int s = tid + k * CTC_THREADS;
+    my_ext[k] = 0; my_skip[k] = false;
+    if (s < S) {
+      my_ext[k] = ext[s];
+      my_skip[k] = s >= 2 && (s & 1) && ext[s] != ext[s - 2];
+    }
+  }
+  {
+    const float *lpt = lp + (size_t)b * V;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      const int s = tid + k * CTC_THREADS;
+      if (s < S) buf0[s] = s <= 1 ? lpt[my_ext[k]] : -INFINITY;
+    }
+  }
+  __syncthreads();
+  float *prev = buf0, *cur = buf1;
+  float nq[PF][NS];
+#pragma unroll
+  for (int i = 0; i < PF; ++i) {
+    const float *lpt = lp + ((size_t)min(1 + i, Tb - 1) * B + b) * V;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) nq[i][k] = tid + k * CTC_THREADS < S ? lpt[my_ext[k]] : 0.0f;
+  }
+  const int wsh = lane & 48;                        // this lane's group of 16 inside the two ballots
+  for (int n0 = 1; n0 < Tb; n0 += PF) {
+    float cq[PF][NS];
+#pragma unroll
+    for (int i = 0; i < PF; ++i)
+#pragma unroll
+      for (int k = 0; k < NS; ++k) cq[i][k] = nq[i][k];
+    if (n0 + PF < Tb) {
+#pragma unroll
+      for (int i = 0; i < PF; ++i) {
+        const float *lpt = lp + ((size_t)min(n0 + PF + i, Tb - 1) * B + b) * V;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) nq[i][k] = tid + k * CTC_THREADS < S ? lpt[my_ext[k]] : 0.0f;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < PF; ++i) {
+      const int t = n0 + i;
+      if (t < Tb) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+          const int s = tid + k * CTC_THREADS;
+          int code = 0;
+          if (s < S) {
+            float best = prev[s];
+            const float x1 = s >= 1 ? prev[s - 1] : -INFINITY;
+            const float x2 = my_skip[k] ? prev[s - 2] : -INFINITY;
+            if (x1 > best) { best = x1; code = 1; }
+            if (x2 > best) { best = x2; code = 2; }
+            cur[s] = __fadd_rn(best, cq[i][k]);
+          }
+          const unsigned long long m0 = __ballot(code & 1), m1 = __ballot(code & 2);
+          if ((lane & 15) == 0 && s < S) {
+            const uint32_t w = (uint32_t)((m0 >> wsh) & 0xffffull) | ((uint32_t)((m1 >> wsh) & 0xffffull) << 16);
+            if (BPLDS) bpl[(size_t)t * W + (s >> 4)] = w;
+            else bpg[(size_t)t * W + (s >> 4)] = w;
+          }
+        }
+        lds_barrier();       // LDS only: the row stores of the workspace branch and the prefetches stay in flight
+        float *tmp = prev; prev = cur; cur = tmp;
+      }
+    }
+  }
+  __syncthreads();           // the last value row, every back-pointer row (LDS or workspace) and the fills are done
+  const float l1 = prev[S - 1], l2 = S > 1 ? prev[S - 2] : -INFINITY;
+  const bool second = S > 1 && l2 > l1;
+  const float sc = second ? l2 : l1;
+  if (sc == -INFINITY) { no_alignment(sc); return; }
+  if (tid == 0) { score[b] = sc; ok[b] = 1; }
+#ifdef CTCN_ALIGN_FORWARD_ONLY
+  return;
+#endif
+  const int CH = BPLDS ? ALIGN_CH : min(ALIGN_CH, ALIGN_GWORDS / W);
+  int s = second ? S - 2 : S - 1, s_above = -1;     // the walk's state: meaningful in thread 0 only
+  for (int t1 = Tb; t1 > 0;) {
+    const int n = min(t1, CH), t0 = t1 - n;
+    if (!BPLDS)
+      for (int i = tid; i < n * W; i += CTC_THREADS) bpl[i] = bpg[(size_t)t0 * W + i];
+    __syncthreads();
+    if (tid == 0) {
+      const uint32_t *rows = BPLDS ? bpl + (size_t)t0 * W : bpl;
+      st[n + 1] = s_above;
+      // ALIGN_WALK frames per LDS round trip: the state drops by at most 2 per frame, so over 8 frames it stays inside the word of s and
+      // the word below it -- both are fetched for the 8 rows at once and the 8 dependent steps run in registers
+      for (int i = n - 1; i >= 0; i -= ALIGN_WALK) {
+        const int wi = s >> 4, wl = max(wi - 1, 0);
+        uint32_t hi[ALIGN_WALK], lo[ALIGN_WALK];
+#pragma unroll
+        for (int k = 0; k < ALIGN_WALK; ++k) {
+          const uint32_t *row = rows + (size_t)max(i - k, 0) * W;
+          hi[k] = row[wi];
+          lo[k] = row[wl];
+        }
+#pragma unroll
+        for (int k = 0; k < ALIGN_WALK; ++k) {
+          if (i - k >= 0) {
+            st[i - k + 1] = s;
+            if (i - k == 0) s_above = s;
+            if (t0 + i - k > 0) {                   // frame 0 has no predecessor (and no row)
+              const uint32_t w = ((s >> 4) == wi ? hi[k] : lo[k]) >> (s & 15);
+              s -= (int)((w & 1u) | ((w >> 15) & 2u));
+            }
+          }
+        }
+      }
+      st[0] = t0 > 0 ? s : -1;
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += CTC_THREADS) {
+      const int t = t0 + i, si = st[i + 1];
+      const int c = ext[si];
+      prow[t] = c;
+      frow[t] = lp[((size_t)t * B + b) * V + c];
+      if (si & 1) {
+        if (srow && st[i] != si) srow[si >> 1] = t;
+        if (erow && st[i + 2] != si) erow[si >> 1] = t + 1;
+      }
+    }
+    t1 = t0;
+  }
+}
+
 }  // namespace
 
 extern "C" int ctcn_edit_distance(const int32_t *a, const int32_t *a_len, const int64_t *b, const int64_t *b_len, int32_t *out,
@@ -597,6 +799,38 @@ extern "C" int ctcn_ctc_grad_ex(const float *lp, const int64_t *targets, const i
   CTCN_REQUIRE(gscale_stride == 0 || gscale_stride == 1, "ctcn_ctc_grad_ex: gscale_stride %d (0 or 1)", gscale_stride);
   return ctc_grad(lp, targets, in_len, tgt_len, alpha, beta, nll, gscale, gscale_stride, reduction, zero_infinity, blank, grad_lp, T, B, V,
                   Lmax, (hipStream_t)stream);
+}
+
+extern "C" size_t ctcn_ctc_align_ws_bytes(int T, int B, int Lmax) {
+  if (T <= 0 || B <= 0 || Lmax < 0 || align_rows_in_lds(T, Lmax)) return 0;
+  return (size_t)B * (size_t)T * align_row_words(Lmax) * sizeof(uint32_t);
+}
+
+extern "C" int ctcn_ctc_align(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, int32_t *paths,
+                              float *frame_scores, float *score, int32_t *ok, int32_t *starts, int32_t *ends, int T, int B, int V, int Lmax,
+                              int blank, void *ws, size_t ws_bytes, void *stream) {
+  CTCN_REQUIRE(lp && in_len && tgt_len && paths && frame_scores && score && ok && (targets || Lmax == 0), "ctcn_ctc_align: null pointer");
+  CTCN_REQUIRE(T > 0 && B > 0 && V > 0 && Lmax >= 0, "ctcn_ctc_align: bad dims");
+  CTCN_REQUIRE(blank >= 0 && blank < V, "ctcn_ctc_align: blank %d outside [0, %d)", blank, V);
+  if (2 * Lmax + 1 > CTC_THREADS * CTC_NS) { ctcn_set_error("ctcn_ctc_align: label length %d > %d unsupported", Lmax, (CTC_THREADS * CTC_NS - 1) / 2); return CTCN_EUNSUPPORTED; }
+  const bool in_lds = align_rows_in_lds(T, Lmax);
+  const size_t need = ctcn_ctc_align_ws_bytes(T, B, Lmax);
+  if (!in_lds) {
+    CTCN_REQUIRE(ws && ((uintptr_t)ws & 3) == 0, "ctcn_ctc_align: workspace of ctcn_ctc_align_ws_bytes needed (T %d, Lmax %d), 4-byte aligned", T, Lmax);
+    if (ws_bytes < need) { ctcn_set_error("ctcn_ctc_align: workspace %zu < %zu bytes", ws_bytes, need); return CTCN_EWORKSPACE; }
+  }
+  const size_t sm = align_lds_fixed(Lmax) + (in_lds ? (size_t)T * align_row_words(Lmax) : (size_t)ALIGN_GWORDS) * sizeof(uint32_t);
+  const int ns = ceil_div(2 * Lmax + 1, CTC_THREADS);
+  hipStream_t st = (hipStream_t)stream;
+#define CTC_LAUNCH(NS, LDS) hipLaunchKernelGGL((ctc_align_kernel<NS, LDS>), dim3(B), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, paths, frame_scores, score, ok, starts, ends, (uint32_t *)ws, T, B, V, Lmax, blank)
+  if (in_lds) {
+    if (ns <= 1) CTC_LAUNCH(1, true); else if (ns <= 2) CTC_LAUNCH(2, true); else if (ns <= 4) CTC_LAUNCH(4, true); else if (ns <= 8) CTC_LAUNCH(8, true); else CTC_LAUNCH(16, true);
+  } else {
+    if (ns <= 1) CTC_LAUNCH(1, false); else if (ns <= 2) CTC_LAUNCH(2, false); else if (ns <= 4) CTC_LAUNCH(4, false); else if (ns <= 8) CTC_LAUNCH(8, false); else CTC_LAUNCH(16, false);
+  }
+#undef CTC_LAUNCH
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
 }
 
 extern "C" int ctcn_ctc_pack_targets(const int64_t *flat, int64_t n_flat, const int64_t *tgt_len, int64_t *padded, int B, int Lmax, void *stream) {

@@ -1179,6 +1179,53 @@ def ctc_loss(lp, targets, in_len, tgt_len, blank=0, reduction="sum", zero_infini
     return out if a.batched else out.squeeze(0)
 
 
+CtcAlignment = collections.namedtuple("CtcAlignment", "paths frame_scores scores ok starts ends")
+
+
+def ctc_forced_align(log_probs, targets, input_lengths, target_lengths, blank=0):
+    """CTC forced alignment (ctcn_ctc_align; the capability of torchaudio.functional.forced_align + merge_tokens): the best path through
+    the lattice of the KNOWN transcript.  Takes what ctc_loss takes (padded (B, S) or concatenated 1-D targets, lengths as tensors or lists on
+    either side, unbatched (T, C) log-probs, any blank in [0, C)) and raises the same ValueErrors, before it looks at the device.  Returns CtcAlignment of device tensors:
+    paths (B, T) int32 class id per frame (-1 past the input), frame_scores (B, T) float32 = log_probs[t, b, paths[b, t]] (0 past the
+    input), scores (B) float32 = the path's log-probability (a chain of single float32 adds), ok (B) int32 (0: no alignment exists --
+    scores -inf, paths -1, spans -1), starts / ends (B, Lmax) int32 = first and one-past-last frame of every target token (-1 past the
+    label).  Ties go to the smallest move (stay, then advance one state, then skip the blank).  Unbatched input drops the batch dimension.
+    No autograd (log_probs is detached); float32 on the device only (no CPU fallback)."""
+    a = ctc_prepare(log_probs, targets, input_lengths, target_lengths)          # pure: the argument errors come before any device work
+    T, B, V = a.lp.shape
+    if not 0 <= int(blank) < V:
+        raise ValueError("ctc_pytorch_amd.ctc_forced_align: blank must lie in [0, %d), got %d" % (V, int(blank)))
+    if T == 0 or B == 0:
+        raise ValueError("ctc_pytorch_amd.ctc_forced_align: empty log_probs %s" % (tuple(log_probs.shape),))
+    _need_gpu(log_probs)
+    lp = _f32c(a.lp.detach())
+    dev = lp.device
+    L = _lib.lib()
+    Lmax = a.Lmax
+    tg = a.targets.to(device=dev, dtype=torch.int64).contiguous()
+    in_len = a.in_len.to(device=dev).contiguous()
+    tgt_len = a.tgt_len.to(device=dev).contiguous()
+    if a.flat:
+        padded = torch.empty((B, Lmax), dtype=torch.int64, device=dev)
+        if Lmax > 0:
+            _lib.check(L.ctcn_ctc_pack_targets(_ptr(tg), tg.numel(), _ptr(tgt_len), _ptr(padded), B, Lmax, _lib.stream_ptr()), "ctc_pack_targets")
+        tg = padded
+    paths = torch.empty((B, T), dtype=torch.int32, device=dev)
+    frame_scores = torch.empty((B, T), dtype=torch.float32, device=dev)
+    scores = torch.empty(B, dtype=torch.float32, device=dev)
+    ok = torch.empty(B, dtype=torch.int32, device=dev)
+    starts = torch.empty((B, Lmax), dtype=torch.int32, device=dev)
+    ends = torch.empty((B, Lmax), dtype=torch.int32, device=dev)
+    need = L.ctcn_ctc_align_ws_bytes(T, B, Lmax)
+    # back-pointer rows that do not fit in LDS: a buffer of this call's own (stream-ordered: the caching allocator hands it out again only to later work)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    _lib.check(L.ctcn_ctc_align(_ptr(lp), _ptr(tg), _ptr(in_len), _ptr(tgt_len), _ptr(paths), _ptr(frame_scores), _ptr(scores), _ptr(ok),
+                                _ptr(starts), _ptr(ends), T, B, V, Lmax, int(blank), _ptr(ws), need, _lib.stream_ptr()), "ctc_align")
+    if not a.batched:
+        paths, frame_scores, scores, ok, starts, ends = (x.squeeze(0) for x in (paths, frame_scores, scores, ok, starts, ends))
+    return CtcAlignment(paths, frame_scores, scores, ok, starts, ends)
+
+
 # --------------------------------------------------------------------------------------------------
 # decode helpers (no autograd)
 # --------------------------------------------------------------------------------------------------

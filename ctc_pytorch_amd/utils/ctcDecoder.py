@@ -68,6 +68,44 @@ class Decoder(object):
             self.num_char += len(ref)
         return char_errs, word_errs
 
+    # ---- forced alignment ------------------------------------------------------------------------------
+    def align(self, prob_tensor, frame_seq_len, targets, target_sizes, frame_stride=1):
+        """Where each label of the KNOWN transcript sits in time (ops.ctc_forced_align: the best CTC path of the transcript; the reference
+        has no counterpart -- the capability of torchaudio's forced_align + merge_tokens).  prob_tensor: the (T, B, V) log-prob tensor
+        `decode` takes (moved to the device if it is not there); targets / target_sizes: the concatenated labels and sizes `phone_word_error` takes.  Returns one
+        entry per utterance: (spans, score) with spans = [(token, start, end, mean frame log-prob over the span), ...] in label order,
+        start / end = first and one-past-last frame times frame_stride (the front-end's subsampling: a plain multiplier), score = the
+        path's log-probability; None for an utterance that has no alignment.  One device-to-host copy per batch."""
+        sizes = [int(n) for n in target_sizes]
+        tg = targets if torch.is_tensor(targets) else torch.as_tensor(np.asarray(targets, dtype=np.int64))
+        lens = frame_seq_len if torch.is_tensor(frame_seq_len) else [int(n) for n in frame_seq_len]
+        a = ops.ctc_forced_align(_to_device(prob_tensor), tg.reshape(-1).to(torch.int64), lens, sizes, blank=self.blank_index)
+        B, T = a.paths.shape
+        parts = [a.frame_scores, a.scores, a.ok.view(torch.float32), a.starts.view(torch.float32), a.ends.view(torch.float32)]
+        blob = torch.cat([p.reshape(-1) for p in parts]).cpu().numpy()
+        cuts = np.cumsum([p.numel() for p in parts])[:-1]
+        fs, sc, ok, st, en = np.split(blob, cuts)
+        rows = self._unflatten_targets(tg.reshape(-1).cpu().numpy(), sizes)
+        return self._spans(fs.reshape(B, T), sc, ok.view(np.int32), st.view(np.int32).reshape(B, -1), en.view(np.int32).reshape(B, -1), rows,
+                           frame_stride)
+
+    def _spans(self, frame_scores, scores, ok, starts, ends, label_rows, frame_stride=1):
+        """Host half of `align`: the arrays of ops.ctc_forced_align (on the host) -> per utterance ([(token, start * frame_stride,
+        end * frame_stride, mean of frame_scores[start:end]), ...], score), or None where ok is 0.  No per-frame loop: the means are
+        differences of one running sum per utterance (float64)."""
+        out = []
+        for b, labels in enumerate(label_rows):
+            if not ok[b]:
+                out.append(None)
+                continue
+            n = len(labels)
+            s, e = starts[b, :n].astype(np.int64), ends[b, :n].astype(np.int64)
+            run = np.concatenate([[0.0], np.cumsum(frame_scores[b], dtype=np.float64)])
+            mean = (run[e] - run[s]) / np.maximum(e - s, 1)
+            spans = [(self.int_to_char[int(labels[j])], int(s[j]) * frame_stride, int(e[j]) * frame_stride, float(mean[j])) for j in range(n)]
+            out.append((spans, float(scores[b])))
+        return out
+
     # ---- id / string plumbing ----------------------------------------------------------------------------
     @staticmethod
     def _unflatten_targets(targets, target_sizes):

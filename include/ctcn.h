@@ -394,6 +394,29 @@ int ctcn_ctc_grad_ex(const float *lp, const int64_t *targets, const int64_t *in_
                      int blank, float *grad_lp, int T, int B, int V, int Lmax, void *stream);
 int ctcn_ctc_reduce(const float *nll, const int64_t *tgt_len, float *out, int B, int reduction, int zero_infinity, void *stream);
 int ctcn_ctc_pack_targets(const int64_t *flat, int64_t n_flat, const int64_t *tgt_len, int64_t *padded, int B, int Lmax, void *stream);
+/* CTC forced alignment: the best path of the KNOWN transcript through the lattice of ctcn_ctc_fwd_ex, its per-frame scores and the
+ * frames of every target token (the capability of torchaudio's forced_align + merge_tokens; the reference has no counterpart).
+ * For utterance b: Tb = in_len[b], L = tgt_len[b], S = 2L + 1, ext(s) = blank for even s, targets[b, s >> 1] for odd s (targets is
+ * the padded (B, Lmax) layout; ctcn_ctc_pack_targets converts concatenated ones), any blank in [0, V).
+ *   v[0][s] = lp[0, b, ext(s)] for s <= 1, -inf otherwise;
+ *   v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if allowed) + lp[t, b, ext(s)] -- ONE float32 add, never fused or reordered;
+ *   s-2 is allowed under the loss's rule (s odd, s >= 2, ext(s) != ext(s-2)).
+ *   Ties: the predecessor with the smallest move wins (s, then s-1, then s-2: a candidate replaces the best so far only if
+ *   strictly greater).  End state: S-1, or S-2 only if v[Tb-1][S-2] > v[Tb-1][S-1] (and S > 1).  The result is a function of the
+ *   input alone: a float32 restatement with the same tie rule gives the same bits.
+ * Outputs (every element is written, the caller need not clear them):
+ *   score (B) float32 = the end value; ok (B) int32 = (score != -inf);
+ *   paths (B, T) int32 = ext(s_t) for t < Tb, -1 beyond; frame_scores (B, T) float32 = lp[t, b, paths[b, t]], 0 beyond;
+ *   starts, ends (B, Lmax) int32, each may be NULL = first and one-past-last frame spent in state 2j + 1, -1 for j >= L.
+ *   No alignment (score == -inf): ok = 0, paths -1, frame_scores 0, spans -1.  Tb == 0: ok = (L == 0), score 0 / -inf.  Lengths
+ *   outside the tensors (Tb < 0, Tb > T, L < 0, L > Lmax): ok = 0, score NaN, fills as for no alignment.
+ * One workgroup per utterance; a 2-bit move per (t, s), packed 16 to a word, kept in LDS when T * ceil((2 Lmax + 1) / 16) words fit
+ * beside the value rows in 64 KB, otherwise in ws (the _ws_bytes query answers 0 in the first case, where ws may be NULL): arithmetic on
+ * (T, Lmax) alone, no learnt state.  Lmax == 0 is legal (all-blank paths); Lmax <= 2047 as for the loss, else CTCN_EUNSUPPORTED. */
+size_t ctcn_ctc_align_ws_bytes(int T, int B, int Lmax);
+int ctcn_ctc_align(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, int32_t *paths,
+                   float *frame_scores, float *score, int32_t *ok, int32_t *starts, int32_t *ends, int T, int B, int V, int Lmax,
+                   int blank, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Adam with L2-coupled weight decay over one flat buffer; replaces torch.optim.Adam.step
