@@ -81,6 +81,11 @@ _SIGS = {
     "ctcn_ctc_align_ws_bytes": (Z, [I, I, I]),
     "ctcn_ctc_align": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, Z, P]),
     "ctcn_adam_step": (I, [P, P, P, P, Z, F, F, F, F, F, I, P]),
+    "ctcn_grad_norm_ws_bytes": (Z, [Z, I]),
+    "ctcn_grad_norm": (I, [P, Z, I, P, I, P, P, P, I, P, Z, P]),
+    "ctcn_clip_control": (I, [P, F, F, F, F, I, P]),
+    "ctcn_adam_step_ex": (I, [P, P, P, P, Z, F, F, F, F, P, P]),
+    "ctcn_scale_by_device_scalar": (I, [P, Z, P, P]),
     "ctcn_greedy_collapse": (I, [P, Z, Z, P, P, P, I, I, I, P]),
     "ctcn_edit_distance": (I, [P, P, P, P, P, I, I, I, I, P]),
     "ctcn_step_stats": (I, [P, P, P, I, P, P, P]),

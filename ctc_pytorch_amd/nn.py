@@ -18,8 +18,57 @@ Sequential = _tnn.Sequential
 Parameter = _tnn.Parameter
 
 
-def __getattr__(name):          # everything else (init, utils, functional, ...) is plain torch.nn
+def __getattr__(name):          # everything else (init, functional, ...) is plain torch.nn
     return getattr(_tnn, name)
+
+
+def _flat_grad_of(params):
+    """The flat gradient buffer of optim.FlatAdam if `params` are all homed in it and together cover it exactly once, else None."""
+    grads = [getattr(p, "_ctcn_grad", None) for p in params]
+    if not grads or any(g is None for g in grads):
+        return None
+    flat = grads[0]._base
+    if flat is None or flat.dim() != 1 or not flat.is_contiguous():
+        return None
+    spans = sorted({(g.data_ptr(), g.numel()) for g in grads if g._base is not None and g._base.data_ptr() == flat.data_ptr()
+                    and g._base.numel() == flat.numel() and g.is_contiguous()})
+    if len(spans) != len({id(g) for g in grads}):
+        return None
+    cur = flat.data_ptr()
+    for ptr, n in spans:
+        if ptr != cur:
+            return None
+        cur += 4 * n
+    return flat if cur == flat.data_ptr() + 4 * flat.numel() else None
+
+
+def _clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ (the reference carries it at train_ctc.py:64).  When every parameter lives in one optim.FlatAdam and
+    together they cover its flat gradient buffer, the norm and the in-place scaling run on that buffer with the library's kernels
+    (ops.clip_grad_norm_: same semantics, deterministic norm) after the weight-gradient side stream has been joined -- torch's own
+    kernels on the 25 p.grad views would race with gradients still in flight there.  Any other parameter list is torch's business (the
+    side stream is still joined first if a parameter is FlatAdam-homed)."""
+    params = [parameters] if torch.is_tensor(parameters) else list(parameters)
+    flat = _flat_grad_of(params) if float(norm_type) in (2.0, float("inf")) else None
+    if any(getattr(p, "_ctcn_grad", None) is not None for p in params):
+        ops.join_side_stream()
+    if flat is None:
+        return _tnn.utils.clip_grad_norm_(params, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite, foreach=foreach)
+    return ops.clip_grad_norm_(flat, max_norm, norm_type, error_if_nonfinite)
+
+
+def _make_utils():
+    """`nn.utils`: torch.nn.utils with clip_grad_norm_ replaced; every other name (rnn, parameters_to_vector, ...) resolves to torch's."""
+    import sys
+    import types
+    m = types.ModuleType(__name__ + ".utils", _make_utils.__doc__)
+    m.clip_grad_norm_ = _clip_grad_norm_
+    m.__getattr__ = lambda name: getattr(_tnn.utils, name)
+    sys.modules[m.__name__] = m
+    return m
+
+
+utils = _make_utils()
 
 
 class _RecurrentMixin:

@@ -1472,3 +1472,99 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step):
     _need_gpu(p, g, m, v)
     _lib.check(_lib.lib().ctcn_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(beta1), float(beta2),
                                          float(eps), float(weight_decay), int(step), _lib.stream_ptr()), "adam_step")
+
+
+# --------------------------------------------------------------------------------------------------
+# gradient-norm clipping and the non-finite-step guard (ctcn_grad_norm / ctcn_clip_control / ctcn_adam_step_ex, include/ctcn.h)
+# --------------------------------------------------------------------------------------------------
+# words of a ctcn_clip_ctl held as an int32 tensor of 8 (the float fields are read through .view(torch.float32))
+CTL_NORM, CTL_NONFINITE, CTL_COEF, CTL_APPLY, CTL_STEP, CTL_SKIPPED, CTL_STEP_SIZE, CTL_SQRT_BC2 = range(8)
+
+
+def norm_type_code(norm_type):
+    """CTCN_NORM_L2 / CTCN_NORM_INF for the two norms the kernels compute; anything else raises NotImplementedError."""
+    try:
+        nt = float(norm_type)
+    except (TypeError, ValueError):
+        nt = None
+    if nt == 2.0:
+        return 2
+    if nt == float("inf"):
+        return 0
+    raise NotImplementedError("ctc_pytorch_amd: norm_type %r -- the gradient-norm kernels compute norm_type 2 and inf" % (norm_type,))
+
+
+def new_clip_ctl(device, step=0):
+    """A zeroed device control block (ctcn_clip_ctl) with the step count `step`."""
+    ctl = torch.zeros(8, dtype=torch.int32, device=device)
+    if step:
+        ctl[CTL_STEP] = int(step)
+    return ctl
+
+
+def _flat_f32(t, what):
+    _need_gpu(t)
+    if t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous():
+        raise TypeError("ctc_pytorch_amd.%s: expected one contiguous 1-D float32 buffer" % what)
+    return t
+
+
+def grad_norm(flat, norm_type=2.0, segments=None, ctl=None, ws=None, blocks=0):
+    """Norm (2 or inf) of the 1-D float32 device buffer `flat` as a 0-d device tensor, without a host sync; a function of the buffer's bits
+    alone (ctcn_grad_norm).  `segments`: offsets [o_0, ..., o_k] (list, or an int64 device tensor) -> returns (total, per-segment norms (k)).
+    `ctl`: a control block (new_clip_ctl) to write total_norm / nonfinite into -- the result is then a view of it; `ws`: a caller-kept
+    workspace (uint8 device tensor); `blocks`: force the grid (tests: the result must not move)."""
+    flat = _flat_f32(flat, "grad_norm")
+    code, dev, L = norm_type_code(norm_type), flat.device, _lib.lib()
+    seg_t = seg_norms = None
+    nseg = 0
+    if segments is not None:
+        seg_t = segments if torch.is_tensor(segments) else torch.tensor([int(o) for o in segments], dtype=torch.int64)
+        seg_t = seg_t.to(device=dev, dtype=torch.int64).contiguous()
+        nseg = int(seg_t.numel()) - 1
+        if nseg < 1:
+            raise ValueError("ctc_pytorch_amd.grad_norm: segments needs at least two offsets")
+        seg_norms = torch.empty(nseg, dtype=torch.float32, device=dev)
+    need = int(L.ctcn_grad_norm_ws_bytes(flat.numel(), nseg))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
+    if ctl is None:
+        ctl = torch.empty(2, dtype=torch.int32, device=dev)
+    _lib.check(L.ctcn_grad_norm(_ptr(flat), flat.numel(), code, _ptr(seg_t), nseg, _ptr(seg_norms), ctypes.c_void_p(ctl.data_ptr()),
+                                ctypes.c_void_p(ctl.data_ptr() + 4), int(blocks), _ptr(ws), ws.numel(), _lib.stream_ptr()), "grad_norm")
+    total = ctl.view(torch.float32)[CTL_NORM]
+    return total if segments is None else (total, seg_norms)
+
+
+def clip_control(ctl, max_norm, lr=0.0, beta1=0.9, beta2=0.999, skip_nonfinite=False):
+    """clip_coef, apply and the step bookkeeping of a control block whose total_norm / nonfinite ctcn_grad_norm has just written (ctcn_clip_control)."""
+    _need_gpu(ctl)
+    _lib.check(_lib.lib().ctcn_clip_control(_ptr(ctl), float(max_norm), float(lr), float(beta1), float(beta2), int(bool(skip_nonfinite)),
+                                            _lib.stream_ptr()), "clip_control")
+
+
+def clip_grad_norm_(flat, max_norm, norm_type=2.0, error_if_nonfinite=False, ctl=None):
+    """torch.nn.utils.clip_grad_norm_ over one flat float32 gradient buffer: returns the pre-clip norm (0-d device tensor) and scales `flat`
+    in place by min(1, max_norm / (norm + 1e-6)); a non-finite norm gives a NaN coefficient that poisons the gradients, as in torch, unless
+    error_if_nonfinite (which reads the flag back: the only host sync here).  The caller joins the side stream (FlatAdam.clip_grad_norm_ and
+    nn.utils.clip_grad_norm_ do).  `ctl`: a scratch control block of the caller's (new_clip_ctl), which then holds the coefficient used."""
+    flat = _flat_f32(flat, "clip_grad_norm_")
+    if not float(max_norm) > 0.0:
+        raise ValueError("ctc_pytorch_amd.clip_grad_norm_: max_norm must be > 0, got %r" % (max_norm,))
+    ctl = new_clip_ctl(flat.device) if ctl is None else ctl
+    total = grad_norm(flat, norm_type, ctl=ctl)
+    if error_if_nonfinite and int(ctl[CTL_NONFINITE].item()):
+        raise RuntimeError("The total norm of order %s for gradients from `parameters` is non-finite, so it cannot be clipped. To disable this "
+                           "error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`" % (float(norm_type),))
+    clip_control(ctl, max_norm)
+    _lib.check(_lib.lib().ctcn_scale_by_device_scalar(_ptr(flat), flat.numel(), ctypes.c_void_p(ctl.data_ptr() + 4 * CTL_COEF),
+                                                      _lib.stream_ptr()), "scale_by_device_scalar")
+    return total
+
+
+def adam_step_ex(p, g, m, v, beta1, beta2, eps, weight_decay, ctl):
+    """adam_step with the clip coefficient, the bias-corrected step size and the apply flag read from the device control block (ctcn_adam_step_ex);
+    `g` is not written."""
+    _need_gpu(p, g, m, v, ctl)
+    _lib.check(_lib.lib().ctcn_adam_step_ex(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(beta1), float(beta2), float(eps),
+                                            float(weight_decay), _ptr(ctl), _lib.stream_ptr()), "adam_step_ex")

@@ -11,7 +11,7 @@ BatchNorm running statistics stay ordinary buffers.
 """
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 def placement_order(names):
@@ -28,7 +28,21 @@ class FlatAdam:
     """Adam over the flattened parameters of `model`; same public surface as torch.optim.Optimizer where the
     reference touches it: zero_grad(), step(), state_dict(), load_state_dict(), param_groups[i]['lr']."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, norm_type=2.0, skip_nonfinite=False):
+        """max_grad_norm: clip the global gradient norm (norm_type 2 or inf) to it inside step(), torch's clip_grad_norm_ expression; the
+        gradient buffer itself is NOT rewritten (Adam applies the coefficient while it reads it -- clip_grad_norm_() below is the form that
+        leaves clipped gradients behind).  skip_nonfinite: a step whose gradient holds a NaN or Inf is dropped -- parameters, moments and
+        the bias-correction count stay as they were (what torch.amp.GradScaler.step does) -- and counted in `skipped_steps`.  Both off
+        (the default): step() is the plain fused Adam, the same launch as without these arguments.  Neither synchronises with the host."""
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("FlatAdam: max_grad_norm must be > 0 (or None), got %r" % (max_grad_norm,))
+        ops.norm_type_code(norm_type)                # NotImplementedError for anything but 2 and inf
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.norm_type = float(norm_type)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._ctl = self._norm_ws = None             # device control block (ctcn_clip_ctl) / norm workspace, made on the first guarded step
+        self._clip_ctl = self._last_norm_ctl = None  # scratch control block of clip_grad_norm_() / the block last_grad_norm reads
+        self._ctl_stale, self._host_exact = False, True
         self.model = model
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         if not named:
@@ -66,12 +80,75 @@ class FlatAdam:
         ops.join_side_stream()            # no-op unless weight gradients are still in flight on the side stream
         self.grad.zero_()
 
+    # ---- the number of APPLIED steps (Adam's bias-correction count).  One rule: the host integer is exact unless a GUARDED step ran since it
+    # was last read -- only the device knows whether that step was dropped -- and then the next read fetches the device counter (a sync),
+    # whatever max_grad_norm / skip_nonfinite are set to by then (both are plain attributes and may be switched on a live optimiser).
+    # A value written from the host (load_state_dict, a plain step) goes to the device counter before the next clipped / guarded step. ----
+    @property
+    def step_count(self):
+        if not self._host_exact:
+            self._step_host = int(self._ctl[ops.CTL_STEP].item())
+            self._host_exact = True
+        return self._step_host
+
+    @step_count.setter
+    def step_count(self, value):
+        self._step_host = int(value)
+        self._host_exact = True
+        self._ctl_stale = self._ctl is not None
+
+    @property
+    def skipped_steps(self):
+        """Steps the guard has dropped so far (reads the device counter: synchronises)."""
+        return 0 if self._ctl is None else int(self._ctl[ops.CTL_SKIPPED].item())
+
+    @property
+    def last_grad_norm(self):
+        """Global gradient norm measured by the last clipped / guarded step() or the last clip_grad_norm_(), before clipping: a 0-d DEVICE
+        tensor (a view of a control block: read it, or clone it, before the next such call), None before the first one."""
+        return None if self._last_norm_ctl is None else self._last_norm_ctl.view(torch.float32)[ops.CTL_NORM]
+
+    def _control(self):
+        if self._ctl is None:
+            self._ctl = ops.new_clip_ctl(self.grad.device, step=self._step_host)
+            need = _lib.lib().ctcn_grad_norm_ws_bytes(self.grad.numel(), 0)
+            self._norm_ws = torch.empty(max(int(need), 8), dtype=torch.uint8, device=self.grad.device)
+        elif self._ctl_stale:                # the host count moved (load_state_dict, plain steps) since the device counter was written
+            self._ctl[ops.CTL_STEP] = self.step_count
+        self._ctl_stale = False
+        return self._ctl
+
+    def clip_grad_norm_(self, max_norm, norm_type=None, error_if_nonfinite=False):
+        """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) on the flat gradient: joins the side stream, returns the pre-clip norm
+        (0-d device tensor) and leaves the clipped gradients in the buffer, for callers who want torch's two-call shape.  It has a scratch
+        control block of its own (made once): the step bookkeeping of step() is not touched."""
+        ops.join_side_stream()
+        if self._clip_ctl is None:
+            self._clip_ctl = ops.new_clip_ctl(self.grad.device)
+        self._last_norm_ctl = self._clip_ctl
+        return ops.clip_grad_norm_(self.grad, max_norm, self.norm_type if norm_type is None else norm_type, error_if_nonfinite, ctl=self._clip_ctl)
+
     def step(self):
         ops.join_side_stream()
         g = self.param_groups[0]
-        self.step_count += 1
-        ops.adam_step(self.flat, self.grad, self.m, self.v, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
-                      self.step_count)
+        if self.max_grad_norm is None and not self.skip_nonfinite:
+            self.step_count += 1
+            ops.adam_step(self.flat, self.grad, self.m, self.v, g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                          self._step_host)
+            return
+        # norm -> clip decision and step bookkeeping -> Adam reading them, all on the device: no host sync, no extra pass over the gradient.
+        # Data parallel: the buffer is the all-reduced one, bit-identical on every rank, and the norm is a function of its bits alone, so
+        # every rank takes the same decision with the same coefficient and no further collective.
+        ctl = self._control()
+        ops.grad_norm(self.grad, self.norm_type, ctl=ctl, ws=self._norm_ws)
+        ops.clip_control(ctl, float("inf") if self.max_grad_norm is None else self.max_grad_norm, g["lr"], g["betas"][0], g["betas"][1],
+                         self.skip_nonfinite)
+        ops.adam_step_ex(self.flat, self.grad, self.m, self.v, g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], ctl)
+        self._last_norm_ctl = ctl
+        if self.skip_nonfinite:
+            self._host_exact = False         # the device decided whether this step counts: step_count reads its counter on demand
+        else:
+            self._step_host += 1             # (one behind the truth by the same amount as before if _host_exact is already False)
 
     # ---- checkpoint surface: the torch.optim.Adam layout, so that 'optim_dict' of a package written by either side loads in
     # the other (train_ctc.py:198,223,246 snapshot / roll back / save optimizer.state_dict()) ---------------------------------
@@ -94,9 +171,10 @@ class FlatAdam:
                                     weight_decay=g["weight_decay"]).state_dict()["param_groups"][0]      # key set of this torch version
         group = dict(template, params=list(range(len(self.params))))
         state = {}
-        if self.step_count > 0:
+        steps = self.step_count                  # applied steps: with the guard on, read from the device counter (a dropped step does not count)
+        if steps > 0:
             for i, off, n, shape in self._slices():
-                state[i] = {"step": torch.tensor(float(self.step_count)), "exp_avg": self.m[off:off + n].view(shape).clone(),
+                state[i] = {"step": torch.tensor(float(steps)), "exp_avg": self.m[off:off + n].view(shape).clone(),
                             "exp_avg_sq": self.v[off:off + n].view(shape).clone()}
         return {"state": state, "param_groups": [group]}
 

@@ -103,6 +103,10 @@ def run_epoch(epoch_id, model, data_iter, loss_fn, device, optimizer=None, print
             loss.backward()
             if isinstance(optimizer, FlatAdam):
                 parallel.allreduce_grads(optimizer.grad)
+            # Gradient clipping and the non-finite guard (FlatAdam(max_grad_norm=, skip_nonfinite=)) run INSIDE step(), that is after
+            # the all-reduce: every rank measures the same global gradient -- the buffer is bit-identical on all of them and the norm
+            # is a function of its bits -- and clips it by the same factor or drops the same step, with no extra collective and no
+            # host sync.  (The reference's commented-out nn.utils.clip_grad_norm_(model.parameters(), 400) would sit here too.)
             optimizer.step()
         # loss, error count, token count and the sticky hand-off status word of the persistent kernels
         if inputs.is_cuda:
@@ -125,9 +129,20 @@ def run_epoch(epoch_id, model, data_iter, loss_fn, device, optimizer=None, print
     total_loss, total_errs, total_tokens, n_batches = acc["total_loss"], acc["total_errs"], acc["total_tokens"], acc["n_batches"]
     parallel.set_batch_split(None, None)
     average_loss = total_loss / max(n_batches, 1)
-    log("Epoch %d %s done, total_loss: %.4f, total_wer: %.4f" % (epoch_id, "Train" if is_training else "Valid", average_loss,
-                                                                total_errs / max(total_tokens, 1)))
+    clip_note = ""
+    if is_training and isinstance(optimizer, FlatAdam) and (optimizer.max_grad_norm is not None or optimizer.skip_nonfinite) and n_batches:
+        # read once per epoch, here, where the last step's statistics have been waited for (the loop itself never drains the device)
+        clip_note = ", dropped_steps: %d, last_grad_norm: %.4g" % (optimizer.skipped_steps, float(optimizer.last_grad_norm))
+    log("Epoch %d %s done, total_loss: %.4f, total_wer: %.4f%s" % (epoch_id, "Train" if is_training else "Valid", average_loss,
+                                                                  total_errs / max(total_tokens, 1), clip_note))
     return 1 - total_errs / max(total_tokens, 1), average_loss
+
+
+def optimizer_options(opts):
+    """FlatAdam's clipping / guard keywords from the driver options `max_grad_norm` (a positive number) and `skip_nonfinite_steps` (bool);
+    absent (or null / false) keys leave both features off: the run is then the unclipped, unguarded one."""
+    mg = getattr(opts, "max_grad_norm", None)
+    return {"max_grad_norm": None if mg is None else float(mg), "skip_nonfinite": bool(getattr(opts, "skip_nonfinite_steps", False))}
 
 
 class Config(object):
@@ -237,7 +252,7 @@ def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print):
     model = build_model_from_opts(opts, num_class).to(device)
     log("Number of parameters %d" % sum(p.numel() for p in model.parameters()))
     loss_fn = nn.CTCLoss(reduction="sum")
-    optimizer = FlatAdam(model, lr=opts.init_lr, weight_decay=opts.weight_decay)
+    optimizer = FlatAdam(model, lr=opts.init_lr, weight_decay=opts.weight_decay, **optimizer_options(opts))
     parallel.broadcast_params(optimizer.flat)
     ctl = LRController(opts.end_adjust_acc, opts.lr_decay)
     loss_results, dev_loss_results, dev_cer_results = [], [], []
@@ -288,5 +303,12 @@ if __name__ == "__main__":
     import yaml
     ap = argparse.ArgumentParser(description="cnn_lstm_ctc on MI355X")
     ap.add_argument("--conf", default="conf/ctc_config.yaml")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm to this value (default: the YAML's max_grad_norm, else off)")
+    ap.add_argument("--skip-nonfinite-steps", action="store_true", help="drop optimiser steps whose gradient holds NaN / Inf (default: the YAML's skip_nonfinite_steps, else off)")
     a = ap.parse_args()
-    main(yaml.safe_load(open(a.conf, "r")))
+    conf = yaml.safe_load(open(a.conf, "r"))
+    if a.max_grad_norm is not None:
+        conf["max_grad_norm"] = a.max_grad_norm
+    if a.skip_nonfinite_steps:
+        conf["skip_nonfinite_steps"] = True
+    main(conf)

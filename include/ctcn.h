@@ -425,6 +425,51 @@ int ctcn_adam_step(float *p, const float *g, float *m, float *v, size_t n, float
                    float eps, float weight_decay, int step, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Global gradient-norm clipping and a non-finite-step guard over the flat gradient; replaces
+ * torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) (the reference carries it commented out at train_ctc.py:64) in front
+ * of Adam, and the drop-the-step rule of torch.amp.GradScaler.step.  Everything is enqueued on `stream`; nothing synchronises, nothing
+ * is allocated, no state is kept: the decision lives in a caller-owned DEVICE control block. */
+#define CTCN_NORM_L2 2
+#define CTCN_NORM_INF 0
+typedef struct ctcn_clip_ctl {
+  float total_norm;   /* written by ctcn_grad_norm (pass &ctl->total_norm, &ctl->nonfinite) */
+  int32_t nonfinite;  /* 1: total_norm is NaN or Inf (an element of g is, or the float32 norm overflowed) */
+  float clip_coef;    /* min(1, max_norm / (total_norm + 1e-6)) in float32: torch's expression and epsilon; NaN stays NaN */
+  int32_t apply;      /* 0: ctcn_adam_step_ex writes nothing (the step was dropped) */
+  int32_t step;       /* applied steps so far = the bias-correction count; the caller initialises (0) and may rewrite it (checkpoints) */
+  int32_t skipped;    /* dropped steps so far; the caller initialises (0) */
+  float step_size;    /* (float)((double)lr / (1 - beta1^step)) */
+  float sqrt_bc2;     /* (float)sqrt(1 - beta2^step): the expressions ctcn_adam_step evaluates on the host, in double */
+} ctcn_clip_ctl;
+/* grad_norm: *total_norm = the norm of g[0..n) (norm_type CTCN_NORM_L2 or CTCN_NORM_INF), *nonfinite (may be NULL) as above.
+ *   L2: every float32 square is widened to double; chunk c = elements [16384 c, 16384 (c+1)) is summed in a fixed order whichever workgroup
+ *   takes it, the chunk partials are added in index order by one thread, and (float)sqrt(sum) is stored: the result is a function of the
+ *   bits of g alone (not of the grid, the device, the stream or the alignment of g), so every data-parallel rank derives the same
+ *   coefficient from its all-reduced buffer.  No atomics.  INF: max |g[i]|, exact.  NaN / Inf in g reach total_norm as they do in torch
+ *   (NaN wins over Inf).  n = 0 gives 0.
+ *   seg_offsets (nseg + 1 DEVICE int64, segment s = [seg_offsets[s], seg_offsets[s+1]) clipped to [0, n)) / seg_norms (nseg DEVICE float32):
+ *   the same norm per segment (one segment per parameter tensor: per-layer telemetry), 16 fixed slices per segment; nseg = 0: both NULL.
+ *   grid_blocks = 0 sizes the grid from ctcn_device_cus(); any other value forces that many workgroups (tests: the result must not move).
+ *   ws: ctcn_grad_norm_ws_bytes(n, nseg) bytes, 8-byte aligned, the caller's.
+ * clip_control (one thread, behind grad_norm): clip_coef from ctl->total_norm and max_norm (> 0; +inf: no clipping); then, if
+ *   skip_nonfinite and ctl->nonfinite: skipped += 1, step unchanged, apply = 0; otherwise step += 1, apply = 1; then step_size and
+ *   sqrt_bc2 from the (new) step.  lr and the betas are per-call host arguments (param_groups[0]['lr'] changes between epochs).
+ * adam_step_ex: ctcn_adam_step with gv = g * clip_coef + weight_decay * p (clip first, then the L2 decay, as clip_grad_norm_ followed by
+ *   Adam.step) and step_size / sqrt_bc2 / apply read from ctl.  g is NOT written back: the fused path saves that pass, so after the step
+ *   the gradient buffer still holds the unclipped gradient.  With clip_coef = 1 and apply = 1, p, m and v are ctcn_adam_step's bit for bit
+ *   for equal step_size / sqrt_bc2 -- those are rounded to float32 from doubles whose pow() is the device library's here and the host
+ *   libm's there: the two agree unless the last ulp of a double pow decides a float32 rounding.
+ * scale_by_device_scalar: x[i] *= *scalar in place (the stand-alone clip_grad_norm_, which leaves clipped gradients behind as torch
+ *   does; a NaN coefficient poisons them, as in torch with error_if_nonfinite = False). */
+size_t ctcn_grad_norm_ws_bytes(size_t n, int nseg);
+int ctcn_grad_norm(const float *g, size_t n, int norm_type, const int64_t *seg_offsets, int nseg, float *seg_norms, float *total_norm,
+                   int32_t *nonfinite, int grid_blocks, void *ws, size_t ws_bytes, void *stream);
+int ctcn_clip_control(ctcn_clip_ctl *ctl, float max_norm, float lr, float beta1, float beta2, int skip_nonfinite, void *stream);
+int ctcn_adam_step_ex(float *p, const float *g, float *m, float *v, size_t n, float beta1, float beta2, float eps, float weight_decay,
+                      const ctcn_clip_ctl *ctl, void *stream);
+int ctcn_scale_by_device_scalar(float *x, size_t n, const float *scalar, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Data-parallel exchange step: SUM all-reduce of the flat float32 gradient buffer (or a slice of it) over RCCL / xGMI,
  * one communicator per rank.  The reference is single-device (train_ctc.py:63-65 loss.backward(); optimizer.step()); utterance-
  * sharded data parallelism inserts this one collective between the two calls.  librccl.so is opened at run time.
