@@ -901,6 +901,15 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
     for (int tt = 0; tt < T; ++tt) st_slab(ry, vh, (unsigned)tt * sh_b, __uint_as_float(0x7fc00000u));
 }
 
+// The launchers below turn run-time values into template arguments: pick_int<V0, V1, ...>(v, f) calls f(std::integral_constant<int, Vi>)
+// for the Vi that equals v and returns its result; false when v is none of them (no such instantiation: the caller falls back).
+template <int... Vs, class F>
+bool pick_int(int v, F &&f) {
+  bool r = false;
+  (void)((v == Vs && ((r = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return r;
+}
+
 // Launch a persistent kernel only if every working workgroup is co-resident (occupancy query x CU count, with one
 // block of slack per CU when the API admits more than one: ROCm 7.2 can over-report by one, MI355X_MICROARCH.md).
 // Device-scope mode: the whole 3-D grid against all CUs.  XCD-local mode (a.local): a.nx * wpx workgroups, wpx of
@@ -920,28 +929,13 @@ bool launch_resident(Kern kern, dim3 grid, int threads, size_t lds, hipStream_t 
   return true;
 }
 
-template <int NT, int PREC, int CELL>
-bool launch_fwd_persist_nt(int kq4, dim3 grid, size_t lds, hipStream_t st, const PersistArgs &a, int wpx) {
-  switch (kq4) {
-    case 1: return launch_resident(rnn_fwd_persist<NT, 1, PREC, CELL>, grid, 256, lds, st, a, wpx);
-    case 2: return launch_resident(rnn_fwd_persist<NT, 2, PREC, CELL>, grid, 256, lds, st, a, wpx);
-    case 3: return launch_resident(rnn_fwd_persist<NT, 3, PREC, CELL>, grid, 256, lds, st, a, wpx);
-    case 4: return launch_resident(rnn_fwd_persist<NT, 4, PREC, CELL>, grid, 256, lds, st, a, wpx);
-    case 5: return launch_resident(rnn_fwd_persist<NT, 5, PREC, CELL>, grid, 256, lds, st, a, wpx);
-    case 6: return launch_resident(rnn_fwd_persist<NT, 6, PREC, CELL>, grid, 256, lds, st, a, wpx);
-    case 8: return launch_resident(rnn_fwd_persist<NT, 8, PREC, CELL>, grid, 256, lds, st, a, wpx);
-    default: return false;
-  }
-}
 template <int PREC, int CELL>
 bool launch_fwd_persist_p(int nt, int kq4, dim3 grid, size_t lds, hipStream_t st, const PersistArgs &a, int wpx) {
-  switch (nt) {
-    case 1: return launch_fwd_persist_nt<1, PREC, CELL>(kq4, grid, lds, st, a, wpx);
-    case 2: return launch_fwd_persist_nt<2, PREC, CELL>(kq4, grid, lds, st, a, wpx);
-    case 3: return launch_fwd_persist_nt<3, PREC, CELL>(kq4, grid, lds, st, a, wpx);
-    case 4: return launch_fwd_persist_nt<4, PREC, CELL>(kq4, grid, lds, st, a, wpx);
-    default: return false;
-  }
+  return pick_int<1, 2, 3, 4>(nt, [&](auto NT) {
+    return pick_int<1, 2, 3, 4, 5, 6, 8>(kq4, [&](auto KQ4) {
+      return launch_resident(rnn_fwd_persist<decltype(NT)::value, decltype(KQ4)::value, PREC, CELL>, grid, 256, lds, st, a, wpx);
+    });
+  });
 }
 bool launch_fwd_persist(int prec, int nt, int kq4, dim3 grid, size_t lds, hipStream_t st, const PersistArgs &a, int wpx) {
   if (prec && a.a.cell == CTCN_CELL_LSTM) return launch_fwd_persist_p<1, CTCN_CELL_LSTM>(nt, kq4, grid, lds, st, a, wpx);
@@ -1316,29 +1310,17 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
     }
 }
 
-template <int CELL, bool SLOW>
-bool launch_fwd_tagged_cs(int nbw, dim3 grid, hipStream_t st, const PersistArgs &a, int wpx) {
-  if (a.poll_depth & 256) {       // option "fwd_rsv_lds": reserve traffic through LDS (16-B aligned reserves)
-    switch (nbw) {
-      case 1: return launch_resident(rnn_fwd_tagged<1, CELL, true, SLOW>, grid, 1024, 0, st, a, wpx);
-      case 2: return launch_resident(rnn_fwd_tagged<2, CELL, true, SLOW>, grid, 1024, 0, st, a, wpx);
-      default: return false;
-    }
-  }
-  switch (nbw) {
-    case 1: return launch_resident(rnn_fwd_tagged<1, CELL, false, SLOW>, grid, 1024, 0, st, a, wpx);
-    case 2: return launch_resident(rnn_fwd_tagged<2, CELL, false, SLOW>, grid, 1024, 0, st, a, wpx);
-    default: return false;
-  }
-}
-template <int CELL>
-bool launch_fwd_tagged_c(int nbw, dim3 grid, hipStream_t st, const PersistArgs &a, int wpx) {
-  return (a.slow > 0 || a.slow_x > 0) ? launch_fwd_tagged_cs<CELL, true>(nbw, grid, st, a, wpx) : launch_fwd_tagged_cs<CELL, false>(nbw, grid, st, a, wpx);
-}
+// NBW 1 / 2, LSTM / GRU; RSV: option "fwd_rsv_lds" (reserve traffic through LDS, 16-B aligned reserves); SLOW: the parity harness's instantiations
 bool launch_fwd_tagged(int nbw, dim3 grid, hipStream_t st, const PersistArgs &a, int wpx) {
-  if (a.a.cell == CTCN_CELL_LSTM) return launch_fwd_tagged_c<CTCN_CELL_LSTM>(nbw, grid, st, a, wpx);
-  if (a.a.cell == CTCN_CELL_GRU) return launch_fwd_tagged_c<CTCN_CELL_GRU>(nbw, grid, st, a, wpx);
-  return false;
+  return pick_int<CTCN_CELL_LSTM, CTCN_CELL_GRU>(a.a.cell, [&](auto CELL) {
+    return pick_int<0, 1>(a.slow > 0 || a.slow_x > 0, [&](auto SLOW) {
+      return pick_int<0, 1>((a.poll_depth & 256) != 0, [&](auto RSV) {
+        return pick_int<1, 2>(nbw, [&](auto NBW) {
+          return launch_resident(rnn_fwd_tagged<decltype(NBW)::value, decltype(CELL)::value, decltype(RSV)::value != 0, decltype(SLOW)::value != 0>, grid, 1024, 0, st, a, wpx);
+        });
+      });
+    });
+  });
 }
 
 // ================================================================================================
@@ -2346,85 +2328,48 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
     for (int tt = 0; tt < T; ++tt) p.gates[(size_t)tt * slab_g + ((size_t)b * D + d) * K + j] = __uint_as_float(0x7fc00000u);
 }
 
-template <int NEW, int CELL>
-bool launch_bwd_scatter2_c(int nte, dim3 grid, hipStream_t st, const PersistArgs &a, int wpx) {
-  constexpr int THR = 256 + 64 * NEW;
-  if constexpr (CELL != CTCN_CELL_TANH) {
-    if (a.slow > 0 || a.slow_x > 0)           // the parity harness's SLOW instantiations (LSTM / GRU)
-      switch (nte) {
-        case 1: return launch_resident(rnn_bwd_scatter2<NEW, 1, CELL, true>, grid, THR, 0, st, a, wpx);
-        case 2: return launch_resident(rnn_bwd_scatter2<NEW, 2, CELL, true>, grid, THR, 0, st, a, wpx);
-        case 3: return launch_resident(rnn_bwd_scatter2<NEW, 3, CELL, true>, grid, THR, 0, st, a, wpx);
-        case 4: return launch_resident(rnn_bwd_scatter2<NEW, 4, CELL, true>, grid, THR, 0, st, a, wpx);
-        case 5: return launch_resident(rnn_bwd_scatter2<NEW, 5, CELL, true>, grid, THR, 0, st, a, wpx);
-        default: return false;
-      }
-  }
-  switch (nte) {
-    case 1: return launch_resident(rnn_bwd_scatter2<NEW, 1, CELL>, grid, THR, 0, st, a, wpx);
-    case 2: return launch_resident(rnn_bwd_scatter2<NEW, 2, CELL>, grid, THR, 0, st, a, wpx);
-    case 3: return launch_resident(rnn_bwd_scatter2<NEW, 3, CELL>, grid, THR, 0, st, a, wpx);
-    case 4: return launch_resident(rnn_bwd_scatter2<NEW, 4, CELL>, grid, THR, 0, st, a, wpx);
-    case 5: return launch_resident(rnn_bwd_scatter2<NEW, 5, CELL>, grid, THR, 0, st, a, wpx);
-    default: return false;
-  }
-}
+// The SLOW instantiations of the two scatter kernels exist for LSTM / GRU only (the parity harness; rnn_bwd_scatter: tagged hand-off only)
 // nsl slices -> exchange waves (8: two per SIMD, 768 threads, 168 VGPRs per wave) and tiles per exchange wave
 bool launch_bwd_scatter2(int nsl, dim3 grid, hipStream_t st, const PersistArgs &a, int wpx) {
   const int nte = (nsl + 7) / 8;
-  switch (a.a.cell) {
-    case CTCN_CELL_LSTM: return launch_bwd_scatter2_c<8, CTCN_CELL_LSTM>(nte, grid, st, a, wpx);
-    case CTCN_CELL_GRU: return launch_bwd_scatter2_c<8, CTCN_CELL_GRU>(nte, grid, st, a, wpx);
-    case CTCN_CELL_TANH: return launch_bwd_scatter2_c<8, CTCN_CELL_TANH>(nte, grid, st, a, wpx);
-    default: return false;
-  }
+  const bool slow = a.slow > 0 || a.slow_x > 0;
+  return pick_int<CTCN_CELL_LSTM, CTCN_CELL_GRU, CTCN_CELL_TANH>(a.a.cell, [&](auto CELL) {
+    auto go = [&](auto SLOW) {
+      return pick_int<1, 2, 3, 4, 5>(nte, [&](auto NTE) {
+        return launch_resident(rnn_bwd_scatter2<8, decltype(NTE)::value, decltype(CELL)::value, decltype(SLOW)::value>, grid, 256 + 64 * 8, 0, st, a, wpx);
+      });
+    };
+    if constexpr (decltype(CELL)::value != CTCN_CELL_TANH)
+      if (slow) return go(std::true_type{});
+    return go(std::false_type{});
+  });
 }
 
-template <bool TAGGED, int CELL>
-bool launch_bwd_scatter_c(int ntw, dim3 grid, hipStream_t st, const PersistArgs &a, int wpx) {
-  if constexpr (TAGGED && CELL != CTCN_CELL_TANH) {
-    if (a.slow > 0 || a.slow_x > 0)           // the parity harness's SLOW instantiations (tagged hand-off, LSTM / GRU)
-      switch (ntw) {
-        case 1: return launch_resident(rnn_bwd_scatter<1, 1, TAGGED, CELL, true>, grid, 1024, 0, st, a, wpx);
-        case 2: return launch_resident(rnn_bwd_scatter<2, 1, TAGGED, CELL, true>, grid, 1024, 0, st, a, wpx);
-        default: return false;
-      }
-  }
-  switch (ntw) {      // precision 1 only: the host never picks the scatter formulation for the f32 matmul
-    case 1: return launch_resident(rnn_bwd_scatter<1, 1, TAGGED, CELL>, grid, 1024, 0, st, a, wpx);
-    case 2: return launch_resident(rnn_bwd_scatter<2, 1, TAGGED, CELL>, grid, 1024, 0, st, a, wpx);
-    default: return false;
-  }
-}
 template <bool TAGGED>
 bool launch_bwd_scatter_p(int ntw, dim3 grid, hipStream_t st, const PersistArgs &a, int wpx) {
-  switch (a.a.cell) {
-    case CTCN_CELL_LSTM: return launch_bwd_scatter_c<TAGGED, CTCN_CELL_LSTM>(ntw, grid, st, a, wpx);
-    case CTCN_CELL_GRU: return launch_bwd_scatter_c<TAGGED, CTCN_CELL_GRU>(ntw, grid, st, a, wpx);
-    case CTCN_CELL_TANH: return launch_bwd_scatter_c<TAGGED, CTCN_CELL_TANH>(ntw, grid, st, a, wpx);
-    default: return false;
-  }
+  const bool slow = a.slow > 0 || a.slow_x > 0;
+  return pick_int<CTCN_CELL_LSTM, CTCN_CELL_GRU, CTCN_CELL_TANH>(a.a.cell, [&](auto CELL) {
+    auto go = [&](auto SLOW) {
+      return pick_int<1, 2>(ntw, [&](auto NTW) {
+        return launch_resident(rnn_bwd_scatter<decltype(NTW)::value, 1, TAGGED, decltype(CELL)::value, decltype(SLOW)::value>, grid, 1024, 0, st, a, wpx);
+      });
+    };
+    if constexpr (TAGGED && decltype(CELL)::value != CTCN_CELL_TANH)
+      if (slow) return go(std::true_type{});
+    return go(std::false_type{});
+  });
 }
 bool launch_bwd_scatter(int prec, int ntw, dim3 grid, hipStream_t st, const PersistArgs &a, int wpx) {
-  if (!prec) return false;
+  if (!prec) return false;      // precision 1 only: the host never picks the scatter formulation for the f32 matmul
   return a.tagmode ? launch_bwd_scatter_p<true>(ntw, grid, st, a, wpx) : launch_bwd_scatter_p<false>(ntw, grid, st, a, wpx);
 }
 
-template <int PREC>
-bool launch_bwd_persist_p(int kq4, dim3 grid, size_t lds, hipStream_t st, const PersistArgs &a, int wpx) {
-  switch (kq4) {
-    case 1: return launch_resident(rnn_bwd_persist<1, PREC>, grid, 1024, lds, st, a, wpx);
-    case 2: return launch_resident(rnn_bwd_persist<2, PREC>, grid, 1024, lds, st, a, wpx);
-    case 3: return launch_resident(rnn_bwd_persist<3, PREC>, grid, 1024, lds, st, a, wpx);
-    case 4: return launch_resident(rnn_bwd_persist<4, PREC>, grid, 1024, lds, st, a, wpx);
-    case 5: return launch_resident(rnn_bwd_persist<5, PREC>, grid, 1024, lds, st, a, wpx);
-    case 6: return launch_resident(rnn_bwd_persist<6, PREC>, grid, 1024, lds, st, a, wpx);
-    case 8: return launch_resident(rnn_bwd_persist<8, PREC>, grid, 1024, lds, st, a, wpx);
-    default: return false;
-  }
-}
 bool launch_bwd_persist(int prec, int kq4, dim3 grid, size_t lds, hipStream_t st, const PersistArgs &a, int wpx) {
-  return prec ? launch_bwd_persist_p<1>(kq4, grid, lds, st, a, wpx) : launch_bwd_persist_p<0>(kq4, grid, lds, st, a, wpx);
+  return pick_int<0, 1>(prec != 0, [&](auto PREC) {
+    return pick_int<1, 2, 3, 4, 5, 6, 8>(kq4, [&](auto KQ4) {
+      return launch_resident(rnn_bwd_persist<decltype(KQ4)::value, decltype(PREC)::value>, grid, 1024, lds, st, a, wpx);
+    });
+  });
 }
 
 // XCDs of the current device, if a 64-workgroup probe kernel (reads HW_REG_XCC_ID) finds its workgroups dealt evenly
@@ -2478,22 +2423,20 @@ int pick_kq4(int K, int nwaves, int mt, int budget) {
   return best;
 }
 
-template <int MT>
-void launch_fwd(int kq4, dim3 grid, hipStream_t st, const RnnArgs &a) {
-  switch (kq4) {
-    case 5: hipLaunchKernelGGL((rnn_fwd_step<MT, 5>), grid, dim3(256), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((rnn_fwd_step<MT, 4>), grid, dim3(256), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((rnn_fwd_step<MT, 2>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((rnn_fwd_step<MT, 1>), grid, dim3(256), 0, st, a); break;
-  }
+// per-timestep kernels: mt in {1, 2, 4}, kq4 one of pick_kq4's candidates
+void launch_fwd(int mt, int kq4, dim3 grid, hipStream_t st, const RnnArgs &a) {
+  pick_int<1, 2, 4>(mt, [&](auto MT) {
+    return pick_int<5, 4, 2, 1>(kq4, [&](auto KQ4) {
+      hipLaunchKernelGGL((rnn_fwd_step<decltype(MT)::value, decltype(KQ4)::value>), grid, dim3(256), 0, st, a);
+      return true;
+    });
+  });
 }
 void launch_bwd(int kq4, dim3 grid, hipStream_t st, const RnnArgs &a) {
-  switch (kq4) {
-    case 5: hipLaunchKernelGGL((rnn_bwd_step<5>), grid, dim3(1024), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((rnn_bwd_step<4>), grid, dim3(1024), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((rnn_bwd_step<2>), grid, dim3(1024), 0, st, a); break;
-    default: hipLaunchKernelGGL((rnn_bwd_step<1>), grid, dim3(1024), 0, st, a); break;
-  }
+  pick_int<5, 4, 2, 1>(kq4, [&](auto KQ4) {
+    hipLaunchKernelGGL((rnn_bwd_step<decltype(KQ4)::value>), grid, dim3(1024), 0, st, a);
+    return true;
+  });
 }
 
 int gates_of(int cell) { return cell == CTCN_CELL_LSTM ? 4 : (cell == CTCN_CELL_GRU ? 3 : 1); }
@@ -2534,11 +2477,19 @@ extern "C" size_t ctcn_rnn_scratch_bytes(int cell, int B, int H, int dirs) {
 // the backward recurrence leaves idle are already full with the weight-gradient GEMMs of the layer above (6.9 ms of side-stream work
 // per step against 6.4 ms of recurrences): the chunk GEMMs finish 0.5 ms AFTER the recurrence and the write-through stores cost it
 // 0.13 ms per launch.  Not kept.)
-// Dropout of the layer output fused into the forward recurrence (ctcn_rnn_fwd_dropout): the request is consumed by the tagged-gather
-// launch; any other path leaves it pending and the dropout kernel runs behind the recurrence instead (the same values either way).
-// (round 3: the ABI keeps no state between calls any more.  What used to be armed by ctcn_set_fwd_overlap / ctcn_set_prelaunch_event and
-// handed over in thread-locals by the _dropout entry points travels in the caller's `ctcn_rnn_call` (include/ctcn.h); a NULL pointer or a
-// zeroed struct is the plain call.)
+// Which physical XCD hosts group g of an XCD-local persistent recurrence (option "xcd_interleave", include/ctcn.h).  An order other than 0 is
+// applied only where the recurrence leaves XCDs idle (groups < XCDs) -- where it decides which XCDs the side-stream GEMMs get; a recurrence that
+// takes every XCD (cfg4) keeps group g on XCD g.  The host derives its xcd_allow masks from the same rule (ops._idle_xcd_mask: no idle XCD, no mask).
+static int xcd_order_for(int nx, int groups) {
+  // ("xcd_interleave_force": the parity harness applies the order to a launch that takes every XCD as well -- a relabelling of XCDs, bit-identical
+  // results: tests/test_gpu_kernels.py:test_rnn_results_do_not_depend_on_the_xcd_order)
+  return (nx == 8 && (groups < nx || ctcn_get_option("xcd_interleave_force") != 0)) ? std::min(std::max(ctcn_get_option("xcd_interleave"), 0), 5) : 0;
+}
+
+// Grid of an XCD-local persistent launch (the workgroups are dealt round-robin over the nx XCDs): on every XCD the wpx working workgroups
+// plus max(2, wpx / 8) spare ones, which exit at once
+static dim3 xcd_local_grid(int nx, int wpx) { return dim3(nx * (wpx + std::max(2, wpx / 8)), 1, 1); }
+
 // ---- the projection pipeline's plan (pure arithmetic; ctcn_diag_pipeline_chunks exposes it to the CPU tests) ---------------------------------
 // Returns the number of time chunks (even, 8..24) with which the input projection of a bidirectional layer is pipelined with its forward
 // recurrence -- the first pair of chunks in front of the launch, the others by XCD-filtered GEMMs on the side stream while the recurrence
@@ -2555,20 +2506,11 @@ extern "C" size_t ctcn_rnn_scratch_bytes(int cell, int B, int H, int dirs) {
 //  * eight CUs of every recurrence XCD stay free, counting the launch's spare workgroups: the side GEMMs' workgroups dealt to a recurrence XCD
 //    must start there to leave -- H = 384 (24 + 3 workgroups per XCD) with only its bottom layer's tiny projection pipelined: 16.4 | 15.7.
 // (Measured and not a rule: chunks that fill less than 3/4 of the side CUs but hold >= 72 steps -- B = 16 gains 1.6 %, B = 20 at T = 650 loses 1.7 %.)
-// Which physical XCD hosts group g of an XCD-local persistent recurrence (option "xcd_interleave", include/ctcn.h).  An order other than 0 is
-// applied only where the recurrence leaves XCDs idle (groups < XCDs) -- where it decides which XCDs the side-stream GEMMs get; a recurrence that
-// takes every XCD (cfg4) keeps group g on XCD g.  The host derives its xcd_allow masks from the same rule (ops._idle_xcd_mask: no idle XCD, no mask).
-static int xcd_order_for(int nx, int groups) {
-  // ("xcd_interleave_force": the parity harness applies the order to a launch that takes every XCD as well -- a relabelling of XCDs, bit-identical
-  // results: tests/test_gpu_kernels.py:test_rnn_results_do_not_depend_on_the_xcd_order)
-  return (nx == 8 && (groups < nx || ctcn_get_option("xcd_interleave_force") != 0)) ? std::min(std::max(ctcn_get_option("xcd_interleave"), 0), 5) : 0;
-}
-
 static int plan_projection_pipeline(int T, int B, int I, int H, int dirs, int G, int nxd, int cus, unsigned xcd_allow, int min_input) {
   if (nxd <= 1 || !xcd_allow || dirs != 2 || I < min_input) return 0;
   const int GH = G * H, N2 = 2 * GH, nidle = __builtin_popcount(xcd_allow), cus_side = cus / nxd * nidle;
   const int wpx = ceil_div(dirs * ceil_div(B, 16), nxd) * (H / 16);
-  if (wpx + std::max(2, wpx / 8) + 8 > cus / nxd) return 0;
+  if ((int)xcd_local_grid(1, wpx).x + 8 > cus / nxd) return 0;
   const int wnt = (N2 % 256 == 0 || (N2 > 512 && ceil_div(N2, 256) * 256 - N2 <= N2 / 8)) ? 2 : 1, tiles_n = ceil_div(N2, 128 * wnt);
   for (int n : {8, 10, 12, 14, 16, 20, 24}) {
     const int ct = ceil_div(T, n);
@@ -2586,10 +2528,82 @@ extern "C" int ctcn_diag_pipeline_chunks(int cell, int T, int B, int I, int H, i
 static const ctcn_rnn_call k_plain_call = {};
 __global__ void set_counter_kernel(unsigned *p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
 
-// the recurrence of ctcn_rnn_fwd_ex; `drop_pending`: in: the call asks for the dropped output, out: false once a recurrent kernel has stored it
-static int rnn_fwd_impl(int cell, int T, int B, int I, int H, int dirs, const float *x, const float *w_ih0,
-                        const float *w_hh0, const float *w_ih1, const float *w_hh1, float *y, float *gates,
-                        float *aux, int precision, void *ws, size_t ws_bytes, void *stream, const ctcn_rnn_call &call, bool &drop_pending) {
+static void note_kernel(int which, const char *name, const ctcn_rnn_call &call) {
+  g_last_kernel[which] = name;
+  if (call.launched) *call.launched = name;
+}
+
+// ---- what every persistent launch shares: the hand-off area in the workspace and the common part of PersistArgs -------------------------------
+// The hand-off area is the tail of the workspace, 256-B aligned: tiles (hx_bytes) | flags (fl_bytes, 256-B multiples), the last 256 B of the
+// flags being the role tickets.  The two are contiguous, so a launch whose tiles start from zero (tags / partial sums) clears all with one memset.
+struct Handoff { float *tiles; unsigned *flags, *tickets; size_t hx_bytes, fl_bytes; };
+static bool carve_handoff(void *ws, size_t ws_bytes, size_t hx_bytes, size_t fl_bytes, Handoff &h) {
+  if (!ws || ws_bytes < hx_bytes + fl_bytes + 512) return false;
+  char *tail = (char *)ws + ((ws_bytes - hx_bytes - fl_bytes) & ~(size_t)255);
+  h = {(float *)tail, (unsigned *)(tail + hx_bytes), (unsigned *)(tail + hx_bytes + fl_bytes - 256), hx_bytes, fl_bytes};
+  return true;
+}
+static hipError_t clear_handoff(const Handoff &h, bool tiles_too, hipStream_t st) {
+  return tiles_too ? hipMemsetAsync(h.tiles, 0, h.hx_bytes + h.fl_bytes, st) : hipMemsetAsync(h.flags, 0, h.fl_bytes, st);
+}
+// mode 1 = XCD-local (each group's slices on one XCD, hand-off through its L2), mode 0 = device scope (nx = 1)
+struct PersistGeom { int mode, nx, groups, nsl, nbt, hsu, wpx; };
+static PersistArgs persist_args(const RnnArgs &a, const Handoff &h, int *status, const PersistGeom &g) {
+  PersistArgs pa = {};
+  pa.a = a;
+  pa.hx = h.tiles; pa.flags = h.flags; pa.tickets = h.tickets;
+  pa.status = status;
+  pa.spin_limit = SPIN_LIMIT;
+  pa.local = g.mode; pa.nx = g.nx; pa.xperm = g.mode ? xcd_order_for(g.nx, g.groups) : 0;
+  pa.nsl = g.nsl; pa.nbt = g.nbt; pa.hsu = g.hsu; pa.wpx = g.wpx;
+  pa.poll_depth = ctcn_opt_poll_depth(); pa.tagmode = 0;                 // (the tagged launches set their own)
+#ifdef CTCN_PERSIST_STATS
+  pa.stats = nullptr;
+#endif
+  return pa;
+}
+
+// Both directions project the same x and the gate reserve holds their pre-activations side by side (row = dirs*GH floats): with the two W_ih
+// stacked as one (2*GH, I) matrix one product does the work of two (forward: one pass over x, one launch; backward: no read-modify-write of
+// dx between two K = GH products, 65 MB each way at cfg2).  s.w: the stacked matrix -- W_ih itself where the two are already contiguous
+// (optim.FlatAdam places them so), else a copy at the head of the workspace if that has 64 MB to spare (s.ws / s.ws_bytes: what is left of it),
+// else NULL: one product per direction.
+struct StackedWih { const float *w; void *ws; size_t ws_bytes; };
+static int stack_w_ih(const float *w_ih0, const float *w_ih1, int GH, int I, void *ws, size_t ws_bytes, hipStream_t st, StackedWih &s) {
+  const size_t wcat_bytes = align_up((size_t)2 * GH * I * sizeof(float), 256);
+  s = {nullptr, ws, ws_bytes};
+  if (w_ih1 == w_ih0 + (size_t)GH * I) {
+    s.w = w_ih0;
+  } else if (ws && ws_bytes > wcat_bytes + ((size_t)64 << 20)) {
+    float *wcat = (float *)ws;
+    CTCN_HIP(hipMemcpyAsync(wcat, w_ih0, (size_t)GH * I * sizeof(float), hipMemcpyDeviceToDevice, st));
+    CTCN_HIP(hipMemcpyAsync(wcat + (size_t)GH * I, w_ih1, (size_t)GH * I * sizeof(float), hipMemcpyDeviceToDevice, st));
+    s = {wcat, (char *)ws + wcat_bytes, ws_bytes - wcat_bytes};
+  }
+  return CTCN_OK;
+}
+
+// ---- ctcn_rnn_fwd_ex ------------------------------------------------------------------------------------------------------------------------
+// One forward call as its steps see it: shape, operands, stream, and every option a decision below depends on, read once (fwd_begin).
+struct FwdCall {
+  int cell, T, B, I, H, dirs, precision;
+  const float *x, *w_ih[2];
+  float *gates;
+  void *ws; size_t ws_bytes;
+  void *stream;
+  const ctcn_rnn_call &call;
+  int G, GH, nbt, groups;     // gates per unit, gate width, 16-row batch tiles, (direction, batch tile) groups
+  RnnArgs a;                  // what every recurrent kernel gets
+  int *status;
+  bool fits32;                // the persistent kernels address each tensor through one 32-bit-offset buffer resource
+  int nxd, cus;               // XCDs the XCD-local hand-off can use (1: none, or option "handoff" off); CUs of the device
+  bool recurrence_only, persistent, tagged, mixed_slices, any_chunking, fused_dropout;
+  int min_input, rsv_lds, tag_poll_delay, slow_items, slow_exchange;
+  hipStream_t st() const { return (hipStream_t)stream; }
+};
+
+static int fwd_validate(int cell, int T, int B, int I, int H, int dirs, const float *x, const float *w_ih0, const float *w_hh0, const float *w_ih1,
+                        const float *w_hh1, const float *y, const float *gates, const float *aux) {
   CTCN_REQUIRE(cell >= 0 && cell <= 2, "ctcn_rnn_fwd: unknown cell %d", cell);
   CTCN_REQUIRE(T > 0 && B > 0 && I > 0 && H > 0 && (dirs == 1 || dirs == 2), "ctcn_rnn_fwd: bad dims");
   if (H % 4 != 0) { ctcn_set_error("ctcn_rnn_fwd: hidden size %d must be a multiple of 4", H); return CTCN_EUNSUPPORTED; }
@@ -2597,258 +2611,260 @@ static int rnn_fwd_impl(int cell, int T, int B, int I, int H, int dirs, const fl
   CTCN_REQUIRE(cell == CTCN_CELL_TANH || aux, "ctcn_rnn_fwd: aux reserve required for LSTM/GRU");
   CTCN_REQUIRE(((uintptr_t)w_hh0 % 16 == 0) && ((uintptr_t)y % 16 == 0) && (dirs == 1 || (uintptr_t)w_hh1 % 16 == 0),
                "ctcn_rnn_fwd: w_hh / y must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int G = gates_of(cell);
-  const int GH = G * H;
-  const float *w_ih[2] = {w_ih0, w_ih1};
-  // both directions project the same x and the gate reserve holds their pre-activations side by side (row = dirs*GH floats):
-  // with the two W_ih stacked in the workspace one N = 2*GH product does the work of two (one pass over x, one launch)
-  bool proj_done = ctcn_opt_recurrence_only();
-  struct { void *stream, *event, *ws; size_t ws_bytes; unsigned xcd_allow; } const ov = {call.side_stream, call.side_event, call.side_ws, call.side_ws_bytes, call.xcd_allow};
-  int *const status_word = call.status ? call.status : ctcn_status_word();
-  // pipelined projection: needs the tagged-gather kernel (the only one that checks the chunk counter), both W_ih stacked, idle XCDs
-  const int nxd_p = ctcn_opt_handoff() ? ctcn_device_xcds() : 1;
-  // time chunks of the pipelined projection (plan_projection_pipeline, above): a fitting even count, or 8 when none fits (then the pipeline
-  // is used only with option "fwd_pipe_any_chunking")
-  int NCHUNK = ov.xcd_allow && nxd_p > 1 ? plan_projection_pipeline(T, B, I, H, dirs, G, nxd_p, ctcn_device_cus(), ov.xcd_allow, ctcn_get_option("fwd_pipe_min_input")) : 0;
-  const bool chunking_fits = NCHUNK > 0;
-  if (!chunking_fits) NCHUNK = 8;
-  const int chunk_T = ceil_div(T, NCHUNK);
-  const bool piped = !proj_done && ov.stream && ov.event && ov.ws && ov.xcd_allow != 0 && dirs == 2 && w_ih1 == w_ih0 + (size_t)GH * I &&
-                     ctcn_opt_rnn_persistent() && ctcn_get_option("rnn_fwd_tagged") && precision == 1 && cell != CTCN_CELL_TANH && H % 32 == 0 &&
-                     H / 32 <= 24 && nxd_p > 1 && T >= 4 * NCHUNK && chunk_T * (NCHUNK - 1) < T &&
-                     // only with such a chunking (round 4): the pipeline runs neck and neck with the recurrence where it fits (cfg2: a pair of
-                     // 2 x 2 560 rows takes the side stream ~130 us, the recurrence consumes it in 128: 13.64 -> 13.21 ms per step), and
-                     // falls behind where it does not -- cfg3 (400 recurrent steps: 8 chunks of 1 600 rows on the 128-row tiles, the fixed cost
-                     // of a pair spread over 50 steps instead of 80) ran 8.51 ms per step with it and 7.87 without.  Option
-                     // "fwd_pipe_any_chunking" = 1 lifts the restriction (the tests that hold the pipeline to the inline order use it)
-                     (chunking_fits || ctcn_get_option("fwd_pipe_any_chunking") != 0) &&
-                     // the LAST chunk holds at least two frames: the RSV prologue fetches the pre-activations of steps 0 and 1 without looking
-                     // at the chunk counter, and step 1 of the reverse direction is frame T - 2 -- with a one-frame last chunk (8 chunks:
-                     // T = 36 / 43 / 50 / 57) that frame belongs to pair 1, which the side stream writes after the launch
-                     T - chunk_T * (NCHUNK - 1) >= 2 &&
-                     (size_t)T * B * dirs * GH * sizeof(float) < ((size_t)1 << 32) &&
-                     // the side GEMMs' workgroups that land on a recurrence XCD must be able to START there (to exit at once): the
-                     // 1024-thread workgroups of the recurrence leave no room on their own CUs, so some CUs of the XCD must stay free --
-                     // otherwise the GEMM cannot finish before the recurrence does, which is waiting for it (H = 512: 32 of 32 CUs).
-                     // (Four is the deadlock guard, for any chunking; the plan asks for eight.)
-                     ceil_div(dirs * ceil_div(B, 16), nxd_p) * (H / 16) + 4 <= ctcn_device_cus() / nxd_p;
-  GemmPlanes pl_main, pl_side;                           // what this call's GEMMs left in the main / the side workspace (operand planes reused within the call)
-  auto project_chunk = [&](int c, void *wsp, size_t wsb, void *strm, unsigned allow, GemmPlanes &pl) -> int {
-    const int t0 = c * chunk_T, t1 = std::min(T, t0 + chunk_T);
-    return ctcn_gemm_on_xcds(0, 1, (t1 - t0) * B, 2 * GH, I, x + (size_t)t0 * B * I, I, w_ih0, I, gates + (size_t)t0 * B * 2 * GH, 2 * GH, 0.0f, precision,
-                             wsp, wsb, strm, allow, &pl);
-  };
-  if (getenv("CTCN_LOG_PIPE")) fprintf(stderr, "libctcn: rnn_fwd T=%d B=%d I=%d H=%d: projection pipeline %s (chunks %d x %d steps, fits=%d)\n", T, B, I, H, piped ? "ON" : "off", NCHUNK, chunk_T, (int)chunking_fits);
-  // (Round 5, tools/fwd_interference_probe.sh: layers 1-3 of cfg2 -- pipelined -- run 1 310 us against the 1 190 of layer 0, which has no pipeline.
-  // That is not the recurrence waiting for a chunk: with TWO pairs projected here instead of one -- 119 us more head start, the last side pair
-  // then ready before it is needed by the model 155 us per side pair / 119 us per pair consumed -- the step is 0.16 ms SLOWER (13.20 -> 13.36,
-  // three pairs: 13.78): the extra pair costs its 75 us here and takes only ~25 off the recurrence.  The slowdown goes with the TIME the bf16x3
-  // chunk GEMMs run next to the recurrence, ~30 us per pair, and is gone with the single-product tiles of option "gemm_bf16_single" (1 186-
-  // 1 190 us for all four layers) although they still run there for 70 % of the time: the matrix pipes' power, not the counter.)
-  // ORDER of the projection's row blocks (option "rnn_proj_order", default 0 = one product over ascending time; 1 = [T/2, T) then [0, T/2), pipelined:
-  // the last chunk before the first).  Round 6 built the second order while it took the cfg4 divergence for stale reads of the rows a GEMM wrote last;
-  // both orders deviated alike in the after-suite A/Bs (the cause: the parked tiles of rnn_fwd_tagged, above).  Same products, bit-identical results.
-  const bool safe_order = ctcn_get_option("rnn_proj_order") != 0 && T >= 16;
-  if (piped) {
-    int rc = project_chunk(safe_order ? NCHUNK - 1 : 0, ws, ws_bytes, stream, 0, pl_main);
-    pl_main.same_b = true;                                // W_ih: split into planes once per stream (reused when the chunk has the same size)
-    if (!rc) rc = project_chunk(safe_order ? 0 : NCHUNK - 1, ws, ws_bytes, stream, 0, pl_main);
-    if (rc) return rc;
-    proj_done = true;
+  return CTCN_OK;
+}
+
+static void fwd_begin(FwdCall &c, const float *w_hh0, const float *w_hh1, float *y, float *aux) {
+  c.G = gates_of(c.cell); c.GH = c.G * c.H; c.nbt = ceil_div(c.B, 16); c.groups = c.dirs * c.nbt;
+  RnnArgs &a = c.a;
+  a.cell = c.cell; a.T = c.T; a.B = c.B; a.H = c.H; a.D = c.dirs; a.G = c.G; a.step = 0;
+  a.w0 = w_hh0; a.w1 = w_hh1; a.y = y; a.gates = c.gates; a.aux = aux; a.dy = nullptr; a.state = nullptr;
+  c.status = c.call.status ? c.call.status : ctcn_status_word();
+  c.fits32 = (size_t)c.T * c.B * c.dirs * c.GH * sizeof(float) < ((size_t)1 << 32);
+  c.nxd = ctcn_opt_handoff() ? ctcn_device_xcds() : 1;
+  c.cus = ctcn_device_cus();
+  c.recurrence_only = ctcn_opt_recurrence_only() != 0;
+  c.persistent = ctcn_opt_rnn_persistent() != 0;
+  c.tagged = ctcn_get_option("rnn_fwd_tagged") != 0;
+  c.mixed_slices = ctcn_get_option("rnn_mixed_slices") != 0;
+  c.any_chunking = ctcn_get_option("fwd_pipe_any_chunking") != 0;
+  c.fused_dropout = ctcn_get_option("rnn_fused_dropout") != 0;
+  c.min_input = ctcn_get_option("fwd_pipe_min_input");
+  c.rsv_lds = ctcn_get_option("fwd_rsv_lds");
+  c.tag_poll_delay = ctcn_get_option("tag_poll_delay");
+  c.slow_items = ctcn_get_option("rnn_slow_items");
+  c.slow_exchange = ctcn_get_option("rnn_slow_exchange");
+}
+
+// The tagged gather (rnn_fwd_tagged), first choice of the persistent forward kernels: 16-unit slices, 1024-thread workgroups, XCD-local,
+// precision 1, LSTM / GRU.  The pipeline decision and the launch both ask here: the tagged gather is the only kernel that looks at the chunk counter.
+static bool tagged_gather_applies(const FwdCall &c) {
+  return c.persistent && c.T > 1 && c.fits32 && c.tagged && c.precision == 1 && c.cell != CTCN_CELL_TANH && c.H % 32 == 0 && c.H / 32 <= 24 && c.nxd > 1;
+}
+
+// The projection pipeline of this call: on / off, and its time chunks (plan_projection_pipeline, above): a fitting even count, or 8 when none
+// fits (then the pipeline is used only with option "fwd_pipe_any_chunking").  Needs the tagged gather, both W_ih stacked in memory, idle XCDs.
+struct PipePlan { bool on, fits; int nchunk, chunk_T; };
+static PipePlan decide_pipeline(const FwdCall &c) {
+  const ctcn_rnn_call &ov = c.call;
+  PipePlan p;
+  p.nchunk = ov.xcd_allow && c.nxd > 1 ? plan_projection_pipeline(c.T, c.B, c.I, c.H, c.dirs, c.G, c.nxd, c.cus, ov.xcd_allow, c.min_input) : 0;
+  p.fits = p.nchunk > 0;
+  if (!p.fits) p.nchunk = 8;
+  p.chunk_T = ceil_div(c.T, p.nchunk);
+  const int T = c.T, NCHUNK = p.nchunk, chunk_T = p.chunk_T;
+  p.on = !c.recurrence_only && ov.side_stream && ov.side_event && ov.side_ws && ov.xcd_allow != 0 && c.dirs == 2 && c.w_ih[1] == c.w_ih[0] + (size_t)c.GH * c.I &&
+         tagged_gather_applies(c) && T >= 4 * NCHUNK && chunk_T * (NCHUNK - 1) < T &&
+         // only with such a chunking (round 4): the pipeline runs neck and neck with the recurrence where it fits (cfg2: a pair of
+         // 2 x 2 560 rows takes the side stream ~130 us, the recurrence consumes it in 128: 13.64 -> 13.21 ms per step), and
+         // falls behind where it does not -- cfg3 (400 recurrent steps: 8 chunks of 1 600 rows on the 128-row tiles, the fixed cost
+         // of a pair spread over 50 steps instead of 80) ran 8.51 ms per step with it and 7.87 without.  Option
+         // "fwd_pipe_any_chunking" = 1 lifts the restriction (the tests that hold the pipeline to the inline order use it)
+         (p.fits || c.any_chunking) &&
+         // the LAST chunk holds at least two frames: the RSV prologue fetches the pre-activations of steps 0 and 1 without looking
+         // at the chunk counter, and step 1 of the reverse direction is frame T - 2 -- with a one-frame last chunk (8 chunks:
+         // T = 36 / 43 / 50 / 57) that frame belongs to pair 1, which the side stream writes after the launch
+         T - chunk_T * (NCHUNK - 1) >= 2 &&
+         // the side GEMMs' workgroups that land on a recurrence XCD must be able to START there (to exit at once): the
+         // 1024-thread workgroups of the recurrence leave no room on their own CUs, so some CUs of the XCD must stay free --
+         // otherwise the GEMM cannot finish before the recurrence does, which is waiting for it (H = 512: 32 of 32 CUs).
+         // (Four is the deadlock guard, for any chunking; the plan asks for eight.)
+         ceil_div(c.groups, c.nxd) * (c.H / 16) + 4 <= c.cus / c.nxd;
+  return p;
+}
+
+// the projection of time chunk `chunk` of the pipeline's plan, both directions in one product (W_ih stacked in memory)
+static int project_chunk(const FwdCall &c, const PipePlan &p, int chunk, void *ws, size_t ws_bytes, void *stream, unsigned allow, GemmPlanes &pl) {
+  const int t0 = chunk * p.chunk_T, t1 = std::min(c.T, t0 + p.chunk_T), N2 = 2 * c.GH;
+  return ctcn_gemm_on_xcds(0, 1, (t1 - t0) * c.B, N2, c.I, c.x + (size_t)t0 * c.B * c.I, c.I, c.w_ih[0], c.I, c.gates + (size_t)t0 * c.B * N2, N2, 0.0f, c.precision,
+                           ws, ws_bytes, stream, allow, &pl);
+}
+
+// (Round 5, tools/fwd_interference_probe.sh: layers 1-3 of cfg2 -- pipelined -- run 1 310 us against the 1 190 of layer 0, which has no pipeline.
+// That is not the recurrence waiting for a chunk: with TWO pairs projected here instead of one -- 119 us more head start, the last side pair
+// then ready before it is needed by the model 155 us per side pair / 119 us per pair consumed -- the step is 0.16 ms SLOWER (13.20 -> 13.36,
+// three pairs: 13.78): the extra pair costs its 75 us here and takes only ~25 off the recurrence.  The slowdown goes with the TIME the bf16x3
+// chunk GEMMs run next to the recurrence, ~30 us per pair, and is gone with the single-product tiles of option "gemm_bf16_single" (1 186-
+// 1 190 us for all four layers) although they still run there for 70 % of the time: the matrix pipes' power, not the counter.)
+// The pipeline's first pair of chunks -- the first and the last: step 0 of the two directions -- on the call's stream, in front of the launch.
+static int project_first_pair(const FwdCall &c, const PipePlan &p, GemmPlanes &pl_main) {
+  int rc = project_chunk(c, p, 0, c.ws, c.ws_bytes, c.stream, 0, pl_main);
+  pl_main.same_b = true;                                // W_ih: split into planes once per stream (reused when the chunk has the same size)
+  if (!rc) rc = project_chunk(c, p, p.nchunk - 1, c.ws, c.ws_bytes, c.stream, 0, pl_main);
+  return rc;
+}
+
+// the whole input projection in front of the recurrence
+static int project_all(const FwdCall &c) {
+  const int TB = c.T * c.B;
+  GemmPlanes pl;
+  if (c.dirs == 2) {
+    StackedWih s;
+    if (int rc = stack_w_ih(c.w_ih[0], c.w_ih[1], c.GH, c.I, c.ws, c.ws_bytes, c.st(), s)) return rc;
+    if (s.w) return ctcn_gemm_on_xcds(0, 1, TB, 2 * c.GH, c.I, c.x, c.I, s.w, c.I, c.gates, 2 * c.GH, 0.0f, c.precision, s.ws, s.ws_bytes, c.stream, 0u, &pl);
   }
-  const int nblk_rows = safe_order ? 2 : 1;              // row blocks of the un-pipelined projection: [T/2, T) then [0, T/2), or all rows at once
-  auto block_rows = [&](int blk, int &t0, int &t1) {
-    if (nblk_rows == 1) { t0 = 0; t1 = T; }
-    else if (blk == 0) { t0 = T / 2; t1 = T; }
-    else { t0 = 0; t1 = T / 2; }
-  };
-  if (!proj_done && dirs == 2) {
-    const size_t wcat_bytes = align_up((size_t)2 * GH * I * sizeof(float), 256);
-    if (w_ih1 == w_ih0 + (size_t)GH * I) {      // already one (2*GH, I) matrix (optim.FlatAdam places them so): no stacking copies
-      for (int blk = 0; blk < nblk_rows; ++blk) {
-        int t0, t1;
-        block_rows(blk, t0, t1);
-        if (blk > 0) pl_main.same_b = true;
-        int rc = ctcn_gemm_on_xcds(0, 1, (t1 - t0) * B, 2 * GH, I, x + (size_t)t0 * B * I, I, w_ih0, I, gates + (size_t)t0 * B * 2 * GH, 2 * GH, 0.0f, precision,
-                                   ws, ws_bytes, stream, 0u, &pl_main);
-        if (rc) return rc;
-      }
-      proj_done = true;
-    } else if (ws && ws_bytes > wcat_bytes + ((size_t)64 << 20)) {
-      float *wcat = (float *)ws;
-      CTCN_HIP(hipMemcpyAsync(wcat, w_ih0, (size_t)GH * I * sizeof(float), hipMemcpyDeviceToDevice, st));
-      CTCN_HIP(hipMemcpyAsync(wcat + (size_t)GH * I, w_ih1, (size_t)GH * I * sizeof(float), hipMemcpyDeviceToDevice, st));
-      GemmPlanes pl_cat;
-      for (int blk = 0; blk < nblk_rows; ++blk) {
-        int t0, t1;
-        block_rows(blk, t0, t1);
-        if (blk > 0) pl_cat.same_b = true;
-        int rc = ctcn_gemm_on_xcds(0, 1, (t1 - t0) * B, 2 * GH, I, x + (size_t)t0 * B * I, I, wcat, I, gates + (size_t)t0 * B * 2 * GH, 2 * GH, 0.0f, precision,
-                                   (char *)ws + wcat_bytes, ws_bytes - wcat_bytes, stream, 0u, &pl_cat);
-        if (rc) return rc;
-      }
-      proj_done = true;
+  // one direction per product (pl.same_a stays false: x is split into planes again for the second direction -- ADVICE.md)
+  for (int d = 0; d < c.dirs; ++d)
+    if (int rc = ctcn_gemm_on_xcds(0, 1, TB, c.GH, c.I, c.x, c.I, c.w_ih[d], c.I, c.gates + (size_t)d * c.GH, c.dirs * c.GH, 0.0f, c.precision, c.ws, c.ws_bytes,
+                                   c.stream, 0u, &pl))
+      return rc;
+  return CTCN_OK;
+}
+
+// the pipeline's remaining chunk pairs, next to the (already queued) recurrence on the XCDs it does not use: a counter update behind each pair
+static int project_side_pairs(const FwdCall &c, const PipePlan &p, unsigned *chunk_ready) {
+  const ctcn_rnn_call &ov = c.call;
+  hipStream_t sd = (hipStream_t)ov.side_stream;
+  GemmPlanes pl_side;
+  CTCN_HIP(hipStreamWaitEvent(sd, (hipEvent_t)ov.side_event, 0));
+  for (int pr = 1; pr < p.nchunk / 2; ++pr) {
+    // (W_ih is split into planes by the first of these calls only; splitting x of all six side chunks in that call as well --
+    // one pass instead of six -- delays the first pair and measured 35 us per step slower)
+    if (pr > 1) pl_side.same_b = true;
+    int rc = project_chunk(c, p, pr, ov.side_ws, ov.side_ws_bytes, ov.side_stream, ov.xcd_allow, pl_side);
+    pl_side.same_b = true;
+    if (!rc) rc = project_chunk(c, p, p.nchunk - 1 - pr, ov.side_ws, ov.side_ws_bytes, ov.side_stream, ov.xcd_allow, pl_side);
+    if (rc) {         // the recurrence is already queued and will wait for this counter: release it (its output is invalid, the
+                      // caller sees rc) instead of letting it spin to the hand-off timeout and poison the status word
+      hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(1), 0, sd, chunk_ready, (unsigned)p.nchunk);
+      return rc;
     }
-  }
-  for (int d = 0; d < dirs && !proj_done; ++d) {
-    // (one direction per product: a forward-only layer starts on the rows written first; the reverse direction of a two-product layer gets the blocks)
-    const int nb_d = d == 1 ? nblk_rows : 1;
-    for (int blk = 0; blk < nb_d; ++blk) {
-      int t0 = 0, t1 = T;
-      if (nb_d > 1) block_rows(blk, t0, t1);
-      pl_main.same_a = false; pl_main.same_b = blk > 0;
-      int rc = ctcn_gemm_on_xcds(0, 1, (t1 - t0) * B, GH, I, x + (size_t)t0 * B * I, I, w_ih[d], I, gates + (size_t)t0 * B * dirs * GH + (size_t)d * GH, dirs * GH, 0.0f,
-                                 precision, ws, ws_bytes, stream, 0u, &pl_main);
-      if (rc) return rc;
-    }
-  }
-  RnnArgs a;
-  a.cell = cell; a.T = T; a.B = B; a.H = H; a.D = dirs; a.G = G; a.step = 0;
-  a.w0 = w_hh0; a.w1 = w_hh1; a.y = y; a.gates = gates; a.aux = aux; a.dy = nullptr; a.state = nullptr;
-  const int HS = cell == CTCN_CELL_TANH ? 16 : 4;
-  const int MT = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
-  dim3 grid(ceil_div(H, HS), dirs, ceil_div(B, 16 * MT));
-  // the persistent kernels address each tensor through one 32-bit-offset buffer resource
-  const bool fits32 = (size_t)T * B * dirs * GH * sizeof(float) < ((size_t)1 << 32);
-  if (ctcn_opt_rnn_persistent() && T > 1 && H % 4 == 0 && fits32) {
-    // persistent recurrence: K = H split over 4 waves x 4 k-lanes x KQ4 float4 (one super-chunk)
-    int kq = ceil_div(H, 64);
-    if (kq == 7) kq = 8;
-    const int nbt = ceil_div(B, 16), groups = dirs * nbt;
-    const size_t lds = 0;
-    // mode 1 = XCD-local (each group's slices on one XCD, hand-off through its L2), mode 0 = device scope
-    // candidates in order of preference: XCD-local hand-off (each group's slices on one XCD, through its L2) with
-    // 8 / 12 / 16 / 4 hidden units per workgroup -- fewer units = less matmul per step, but the group must stay
-    // co-resident on one XCD -- then the device-scope hand-off.  The first one that is co-resident runs.
-    struct Cand { int mode, hsu, nbig, hsu_small; };
-    Cand cands[8];
-    int nc = 0;
-    const int nxd = ctcn_opt_handoff() ? ctcn_device_xcds() : 1;
-    if (cell == CTCN_CELL_TANH) {
-      if (nxd > 1) cands[nc++] = {1, 16, 0, 0};
-      cands[nc++] = {0, 16, 0, 0};
-    } else {
-      if (nxd > 1) {
-        // mixed slices: a 12-unit and b 4-unit workgroups, a + b = CUs of one XCD, 12 a + 4 b = H
-        const int cpx = ctcn_device_cus() / nxd, nbig = (H - 4 * cpx) / 8;
-        if (ctcn_get_option("rnn_mixed_slices") && H % 8 == 0 && (H - 4 * cpx) % 8 == 0 && nbig > 0 && nbig <= cpx && ceil_div(dirs * ceil_div(B, 16), nxd) == 1)
-          cands[nc++] = {1, 12, nbig, 4};
-        if (H % 8 == 0) cands[nc++] = {1, 8, 0, 0};
-        cands[nc++] = {1, 12, 0, 0}; cands[nc++] = {1, 16, 0, 0}; cands[nc++] = {1, 4, 0, 0};
-      }
-      cands[nc++] = {0, H % 8 == 0 ? 8 : 4, 0, 0};
-    }
-    const char *why = kq > 8 ? "hidden size above 512" : "no candidate geometry is co-resident on this device";
-    // first choice: the tagged gather (rnn_fwd_tagged): 16-unit slices, 1024-thread workgroups, XCD-local, precision 1, LSTM / GRU
-    if (ctcn_get_option("rnn_fwd_tagged") && precision == 1 && cell != CTCN_CELL_TANH && H % 32 == 0 && H / 32 <= 24 && nxd > 1) {
-      const int nsl = H / 16, wpx = ceil_div(groups, nxd) * nsl;
-      const size_t hx_bytes = align_up((size_t)2 * dirs * nbt * (H / 32) * 2048, 256), fl_bytes = 512;
-      if (ws && ws_bytes >= hx_bytes + fl_bytes + 512) {
-        PersistArgs pa = {};
-        pa.a = a;
-        char *tail = (char *)ws + ((ws_bytes - hx_bytes - fl_bytes) & ~(size_t)255);
-        pa.hx = (float *)tail;
-        pa.flags = (unsigned *)(tail + hx_bytes);
-        pa.status = status_word;
-        pa.spin_limit = SPIN_LIMIT;
-        pa.local = 1; pa.nx = nxd; pa.xperm = xcd_order_for(nxd, groups); pa.nsl = nsl; pa.nbt = nbt; pa.hsu = 16; pa.nbig = 0; pa.hsu_small = 0; pa.wpx = wpx;
-        // "fwd_rsv_lds": 0 off, 1 on, 2 (default) where it measured faster: more than 24 slices (cfg4, H = 512: 2.30 -> 2.24 us per step, 53.9 -> 53.2 ms
-        // per step; cfg2 1.60 -> 1.70, ref_yaml 1.51 -> 1.59: there the waterfall-paced dword traffic of the item waves is the better neighbour of
-        // the polls)
-        const int rsv_opt = ctcn_get_option("fwd_rsv_lds");
-        const bool rsv = (rsv_opt == 1 || (rsv_opt == 2 && nsl > 24)) && ((uintptr_t)gates | (uintptr_t)aux | (uintptr_t)y | (uintptr_t)(drop_pending ? call.y_drop : nullptr)) % 16 == 0;
-        pa.poll_depth = 1 | (rsv ? 256 : 0); pa.tagmode = 1; pa.poll_delay = ctcn_get_option("tag_poll_delay");
-        pa.tickets = (unsigned *)(tail + hx_bytes + fl_bytes - 256);
-#ifdef CTCN_PERSIST_STATS
-        pa.stats = nullptr;
-#endif
-        pa.chunk_T = piped ? chunk_T : 0; pa.nchunk = NCHUNK; pa.chunk_ready = pa.flags;       // (first word of the flag area; tickets sit 256 B further)
-        const bool fuse_drop = drop_pending && ctcn_get_option("rnn_fused_dropout") != 0;
-        if (fuse_drop) {
-          pa.ydrop = call.y_drop; pa.drop_p = call.drop_p; pa.drop_scale = 1.0f / (1.0f - call.drop_p);
-          pa.drop_seed = call.drop_seed; pa.drop_off = call.drop_offset;
-        }
-        pa.slow = ctcn_get_option("rnn_slow_items"); pa.slow_x = ctcn_get_option("rnn_slow_exchange");
-        CTCN_HIP(hipMemsetAsync(pa.hx, 0, hx_bytes + fl_bytes, st));            // zeroed tiles (tag 0) | chunk counter | role tickets
-        if (piped) CTCN_HIP(hipEventRecord((hipEvent_t)ov.event, st));
-        if (launch_fwd_tagged(ceil_div(H / 32, 12), dim3(nxd * (wpx + std::max(2, wpx / 8)), 1, 1), st, pa, wpx)) {
-          CTCN_LAUNCH_CHECK();
-          { g_last_kernel[0] = "rnn_fwd_tagged"; if (call.launched) *call.launched = "rnn_fwd_tagged"; }
-          if (fuse_drop) drop_pending = false;
-          if (piped) {          // the remaining chunk pairs, next to the recurrence on the XCDs it does not use
-            hipStream_t sd = (hipStream_t)ov.stream;
-            CTCN_HIP(hipStreamWaitEvent(sd, (hipEvent_t)ov.event, 0));
-            for (int pr = 1; pr < NCHUNK / 2; ++pr) {
-              // (W_ih is split into planes by the first of these calls only; splitting x of all six side chunks in that call as well --
-              // one pass instead of six -- delays the first pair and measured 35 us per step slower)
-              if (pr > 1) pl_side.same_b = true;
-              int rc = project_chunk(pr, ov.ws, ov.ws_bytes, ov.stream, ov.xcd_allow, pl_side);
-              pl_side.same_b = true;
-              if (!rc) rc = project_chunk(NCHUNK - 1 - pr, ov.ws, ov.ws_bytes, ov.stream, ov.xcd_allow, pl_side);
-              if (rc) {         // the recurrence is already queued and will wait for this counter: release it (its output is invalid, the
-                                // caller sees rc) instead of letting it spin to the hand-off timeout and poison the status word
-                hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(1), 0, sd, pa.chunk_ready, (unsigned)NCHUNK);
-                return rc;
-              }
-              hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(1), 0, sd, pa.chunk_ready, (unsigned)pr);
-            }
-            CTCN_LAUNCH_CHECK();
-          }
-          return CTCN_OK;
-        }
-        if (piped)              // not co-resident after all: finish the projection here, then the other kernels take over
-          for (int c = 1; c < NCHUNK - 1; ++c) { const int rc = project_chunk(c, ws, ws_bytes, stream, 0, pl_main); if (rc) return rc; }
-      }
-    }
-    for (int ci = 0; ci < nc && kq <= 8; ++ci) {
-      const int mode = cands[ci].mode, HSU = cands[ci].hsu;
-      const int nx = mode ? nxd : 1;
-      const int NT = cell == CTCN_CELL_TANH ? 1 : ceil_div(HSU, 4);
-      const int nbig = cands[ci].nbig, hsu_small = cands[ci].hsu_small;
-      const int nsl = nbig ? nbig + (H - nbig * HSU) / hsu_small : ceil_div(H, HSU);
-      const int wpx = ceil_div(groups, nx) * nsl;
-      const dim3 pgrid = mode ? dim3(nx * (wpx + std::max(2, wpx / 8)), 1, 1) : dim3(nsl, dirs, nbt);
-      const int prec = precision == 1 && HSU % 4 == 0 && H % 8 == 0 ? 1 : 0;       // bf16x3 recurrent matmul
-      const size_t hx_bytes = align_up((size_t)2 * dirs * nbt * (prec ? ceil_div(H, 32) * 512 : ceil_div(H, 16) * 256) * sizeof(float), 256);
-      const size_t fl_bytes = align_up((size_t)2 * dirs * nbt * nsl * sizeof(unsigned), 256) + 256;   // + role tickets
-      if (!ws || ws_bytes < hx_bytes + fl_bytes + 512) { why = "workspace too small for the hand-off tiles"; break; }
-      PersistArgs pa = {};
-      pa.a = a;
-      char *tail = (char *)ws + ((ws_bytes - hx_bytes - fl_bytes) & ~(size_t)255);
-      pa.hx = (float *)tail;
-      pa.flags = (unsigned *)(tail + hx_bytes);
-      pa.status = status_word;
-      pa.spin_limit = SPIN_LIMIT;
-      pa.local = mode; pa.nx = nx; pa.xperm = mode ? xcd_order_for(nx, groups) : 0; pa.nsl = nsl; pa.nbt = nbt; pa.hsu = HSU; pa.wpx = wpx; pa.poll_depth = ctcn_opt_poll_depth(); pa.tagmode = 0;
-      pa.nbig = nbig; pa.hsu_small = hsu_small;
-      pa.tickets = (unsigned *)(tail + hx_bytes + fl_bytes - 256);
-#ifdef CTCN_PERSIST_STATS
-      pa.stats = nullptr;
-#endif
-      if (prec) CTCN_HIP(hipMemsetAsync(pa.hx, 0, hx_bytes + fl_bytes, st));      // hand-off tiles | flags | tickets are contiguous
-      else CTCN_HIP(hipMemsetAsync(pa.flags, 0, fl_bytes, st));
-      if (launch_fwd_persist(prec, NT, kq, pgrid, lds, st, pa, wpx)) {
-        CTCN_LAUNCH_CHECK();
-        { g_last_kernel[0] = "rnn_fwd_persist"; if (call.launched) *call.launched = "rnn_fwd_persist"; }
-        return CTCN_OK;
-      }
-    }
-    log_fallback("ctcn_rnn_fwd", T, B, H, dirs, why);
-  } else if (ctcn_opt_rnn_persistent() && T > 1) {
-    log_fallback("ctcn_rnn_fwd", T, B, H, dirs, "a reserve tensor of 4 GB or more");
-  }
-  const int kq4 = pick_kq4(H, 4, MT, 20);
-  g_last_kernel[0] = "rnn_fwd_step";
-  if (call.launched) *call.launched = "rnn_fwd_step";
-  for (int s = 0; s < T; ++s) {
-    a.step = s;
-    if (MT == 1) launch_fwd<1>(kq4, grid, st, a);
-    else if (MT == 2) launch_fwd<2>(kq4, grid, st, a);
-    else launch_fwd<4>(kq4, grid, st, a);
+    hipLaunchKernelGGL(set_counter_kernel, dim3(1), dim3(1), 0, sd, chunk_ready, (unsigned)pr);
   }
   CTCN_LAUNCH_CHECK();
   return CTCN_OK;
+}
+
+// Dropout of the layer output fused into the forward recurrence (ctcn_rnn_fwd_dropout): the request is consumed by the tagged-gather
+// launch; any other path leaves it pending and the dropout kernel runs behind the recurrence instead (the same values either way).
+// `launched`: the recurrence is queued (with the side-stream chunk schedule of a pipelined projection); else the projection is complete
+// when this returns and the other kernels take over.
+static int fwd_try_tagged(const FwdCall &c, const PipePlan &p, GemmPlanes &pl_main, bool &drop_pending, bool &launched) {
+  const int H = c.H, nsl = H / 16, wpx = ceil_div(c.groups, c.nxd) * nsl;
+  hipStream_t st = c.st();
+  Handoff h;
+  if (carve_handoff(c.ws, c.ws_bytes, align_up((size_t)2 * c.dirs * c.nbt * (H / 32) * 2048, 256), 512, h)) {
+    PersistArgs pa = persist_args(c.a, h, c.status, {1, c.nxd, c.groups, nsl, c.nbt, 16, wpx});
+    // "fwd_rsv_lds": 0 off, 1 on, 2 (default) where it measured faster: more than 24 slices (cfg4, H = 512: 2.30 -> 2.24 us per step, 53.9 -> 53.2 ms
+    // per step; cfg2 1.60 -> 1.70, ref_yaml 1.51 -> 1.59: there the waterfall-paced dword traffic of the item waves is the better neighbour of
+    // the polls)
+    const bool rsv = (c.rsv_lds == 1 || (c.rsv_lds == 2 && nsl > 24)) &&
+                     ((uintptr_t)c.a.gates | (uintptr_t)c.a.aux | (uintptr_t)c.a.y | (uintptr_t)(drop_pending ? c.call.y_drop : nullptr)) % 16 == 0;
+    pa.poll_depth = 1 | (rsv ? 256 : 0); pa.tagmode = 1; pa.poll_delay = c.tag_poll_delay;
+    pa.chunk_T = p.on ? p.chunk_T : 0; pa.nchunk = p.nchunk; pa.chunk_ready = pa.flags;       // (first word of the flag area; tickets sit 256 B further)
+    const bool fuse_drop = drop_pending && c.fused_dropout;
+    if (fuse_drop) {
+      pa.ydrop = c.call.y_drop; pa.drop_p = c.call.drop_p; pa.drop_scale = 1.0f / (1.0f - c.call.drop_p);
+      pa.drop_seed = c.call.drop_seed; pa.drop_off = c.call.drop_offset;
+    }
+    pa.slow = c.slow_items; pa.slow_x = c.slow_exchange;
+    CTCN_HIP(clear_handoff(h, true, st));                                  // zeroed tiles (tag 0) | chunk counter | role tickets
+    if (p.on) CTCN_HIP(hipEventRecord((hipEvent_t)c.call.side_event, st));
+    launched = launch_fwd_tagged(ceil_div(H / 32, 12), xcd_local_grid(c.nxd, wpx), st, pa, wpx);
+    if (launched) {
+      CTCN_LAUNCH_CHECK();
+      note_kernel(0, "rnn_fwd_tagged", c.call);
+      if (fuse_drop) drop_pending = false;
+      return p.on ? project_side_pairs(c, p, pa.chunk_ready) : CTCN_OK;
+    }
+  }
+  if (p.on)                 // not co-resident after all (or no room for its tiles): finish the projection here
+    for (int ch = 1; ch < p.nchunk - 1; ++ch)
+      if (int rc = project_chunk(c, p, ch, c.ws, c.ws_bytes, c.stream, 0, pl_main)) return rc;
+  return CTCN_OK;
+}
+
+// rnn_fwd_persist: K = H split over 4 waves x 4 k-lanes x KQ4 float4 (one super-chunk).  Candidates in order of preference: XCD-local hand-off
+// with 8 / 12 / 16 / 4 hidden units per workgroup -- fewer units = less matmul per step, but the group must stay co-resident on one XCD --
+// then the device-scope hand-off.  The first one that is co-resident runs; `why`: the reason none did.
+static int fwd_try_persist(const FwdCall &c, bool &launched, const char *&why) {
+  const int H = c.H;
+  int kq = ceil_div(H, 64);
+  if (kq == 7) kq = 8;
+  struct Cand { int mode, hsu, nbig, hsu_small; };
+  Cand cands[8];
+  int nc = 0;
+  if (c.cell == CTCN_CELL_TANH) {
+    if (c.nxd > 1) cands[nc++] = {1, 16, 0, 0};
+    cands[nc++] = {0, 16, 0, 0};
+  } else {
+    if (c.nxd > 1) {
+      // mixed slices: a 12-unit and b 4-unit workgroups, a + b = CUs of one XCD, 12 a + 4 b = H
+      const int cpx = c.cus / c.nxd, nbig = (H - 4 * cpx) / 8;
+      if (c.mixed_slices && H % 8 == 0 && (H - 4 * cpx) % 8 == 0 && nbig > 0 && nbig <= cpx && ceil_div(c.groups, c.nxd) == 1)
+        cands[nc++] = {1, 12, nbig, 4};
+      if (H % 8 == 0) cands[nc++] = {1, 8, 0, 0};
+      cands[nc++] = {1, 12, 0, 0}; cands[nc++] = {1, 16, 0, 0}; cands[nc++] = {1, 4, 0, 0};
+    }
+    cands[nc++] = {0, H % 8 == 0 ? 8 : 4, 0, 0};
+  }
+  why = kq > 8 ? "hidden size above 512" : "no candidate geometry is co-resident on this device";
+  for (int ci = 0; ci < nc && kq <= 8; ++ci) {
+    const int mode = cands[ci].mode, HSU = cands[ci].hsu, nbig = cands[ci].nbig, hsu_small = cands[ci].hsu_small;
+    const int nx = mode ? c.nxd : 1;
+    const int NT = c.cell == CTCN_CELL_TANH ? 1 : ceil_div(HSU, 4);
+    const int nsl = nbig ? nbig + (H - nbig * HSU) / hsu_small : ceil_div(H, HSU);
+    const int wpx = ceil_div(c.groups, nx) * nsl;
+    const int prec = c.precision == 1 && HSU % 4 == 0 && H % 8 == 0 ? 1 : 0;       // bf16x3 recurrent matmul
+    const size_t hx_bytes = align_up((size_t)2 * c.groups * (prec ? ceil_div(H, 32) * 512 : ceil_div(H, 16) * 256) * sizeof(float), 256);
+    const size_t fl_bytes = align_up((size_t)2 * c.groups * nsl * sizeof(unsigned), 256) + 256;   // + role tickets
+    Handoff h;
+    if (!carve_handoff(c.ws, c.ws_bytes, hx_bytes, fl_bytes, h)) { why = "workspace too small for the hand-off tiles"; break; }
+    PersistArgs pa = persist_args(c.a, h, c.status, {mode, nx, c.groups, nsl, c.nbt, HSU, wpx});
+    pa.nbig = nbig; pa.hsu_small = hsu_small;
+    CTCN_HIP(clear_handoff(h, prec != 0, c.st()));
+    launched = launch_fwd_persist(prec, NT, kq, mode ? xcd_local_grid(nx, wpx) : dim3(nsl, c.dirs, c.nbt), 0, c.st(), pa, wpx);
+    if (launched) {
+      CTCN_LAUNCH_CHECK();
+      note_kernel(0, "rnn_fwd_persist", c.call);
+      break;
+    }
+  }
+  return CTCN_OK;
+}
+
+static int fwd_per_timestep(FwdCall &c) {
+  const int HS = c.cell == CTCN_CELL_TANH ? 16 : 4;
+  const int MT = c.B <= 16 ? 1 : (c.B <= 32 ? 2 : 4);
+  const dim3 grid(ceil_div(c.H, HS), c.dirs, ceil_div(c.B, 16 * MT));
+  const int kq4 = pick_kq4(c.H, 4, MT, 20);
+  note_kernel(0, "rnn_fwd_step", c.call);
+  for (int s = 0; s < c.T; ++s) {
+    c.a.step = s;
+    launch_fwd(MT, kq4, grid, c.st(), c.a);
+  }
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+// the recurrence of ctcn_rnn_fwd_ex; `drop_pending`: in: the call asks for the dropped output, out: false once a recurrent kernel has stored it
+// (round 3: the ABI keeps no state between calls.  What used to be armed by ctcn_set_fwd_overlap / ctcn_set_prelaunch_event and handed over in
+// thread-locals by the _dropout entry points travels in the caller's `ctcn_rnn_call` (include/ctcn.h); a NULL pointer or a zeroed struct is
+// the plain call.)
+static int rnn_fwd_impl(int cell, int T, int B, int I, int H, int dirs, const float *x, const float *w_ih0,
+                        const float *w_hh0, const float *w_ih1, const float *w_hh1, float *y, float *gates,
+                        float *aux, int precision, void *ws, size_t ws_bytes, void *stream, const ctcn_rnn_call &call, bool &drop_pending) {
+  if (int rc = fwd_validate(cell, T, B, I, H, dirs, x, w_ih0, w_hh0, w_ih1, w_hh1, y, gates, aux)) return rc;
+  FwdCall c = {cell, T, B, I, H, dirs, precision, x, {w_ih0, w_ih1}, gates, ws, ws_bytes, stream, call};
+  fwd_begin(c, w_hh0, w_hh1, y, aux);
+  const PipePlan plan = decide_pipeline(c);
+  if (getenv("CTCN_LOG_PIPE")) fprintf(stderr, "libctcn: rnn_fwd T=%d B=%d I=%d H=%d: projection pipeline %s (chunks %d x %d steps, fits=%d)\n", T, B, I, H, plan.on ? "ON" : "off", plan.nchunk, plan.chunk_T, (int)plan.fits);
+  GemmPlanes pl_main;                                    // what the pipeline's GEMMs on the call's stream left in the workspace
+  if (!c.recurrence_only)
+    if (int rc = plan.on ? project_first_pair(c, plan, pl_main) : project_all(c)) return rc;
+  if (c.persistent && T > 1 && !c.fits32) {
+    log_fallback("ctcn_rnn_fwd", T, B, H, dirs, "a reserve tensor of 4 GB or more");
+  } else if (c.persistent && T > 1) {
+    bool launched = false;
+    const char *why = nullptr;
+    if (tagged_gather_applies(c))
+      if (int rc = fwd_try_tagged(c, plan, pl_main, drop_pending, launched)) return rc;
+    if (!launched)
+      if (int rc = fwd_try_persist(c, launched, why)) return rc;
+    if (launched) return CTCN_OK;
+    log_fallback("ctcn_rnn_fwd", T, B, H, dirs, why);
+  }
+  return fwd_per_timestep(c);
 }
 
 extern "C" int ctcn_dropout(const float *x, float *y, size_t n, float p, uint64_t seed, uint64_t offset, void *stream);
@@ -2900,24 +2916,14 @@ static int rnn_bwd_gemms(int cell, int T, int B, int I, int H, int dirs, const f
   // quarters of the dx product on a third stream on the idle XCDs, started by a clock-bounded sleeper kernel 0.7-1.0 ms into the recurrence,
   // the remaining quarter behind the recurrence -- bounds what the real thing (progress counters, L2 write-back per chunk, wait kernels) could
   // give: 13.39 -> 13.20-13.25 ms per cfg2 step, 1.2-1.4 %.  Not built a third time.)
-  // dx = [da_fwd | da_rev] [W_ih_fwd ; W_ih_rev]: the reserve already holds both directions side by side (row = dirs*GH floats),
-  // so with the two weight matrices stacked in the workspace one K = 2*GH product replaces two K = GH products and the
-  // read-modify-write of dx between them (65 MB each way at cfg2)
+  // dx = [da_fwd | da_rev] [W_ih_fwd ; W_ih_rev]: one K = 2*GH product where the two W_ih can be had stacked (stack_w_ih)
   GemmPlanes pl;                               // operand planes this call's GEMMs leave in the workspace (da^T is shared by dW_ih and dW_hh)
   bool dx_done = false;
   if (dx && dirs == 2) {
-    const size_t wcat_bytes = align_up((size_t)2 * GH * I * sizeof(float), 256);
-    if (w_ih1 == w_ih0 + (size_t)GH * I) {      // the two W_ih are already stacked in memory
-      int rc = ctcn_gemm_on_xcds(0, 0, TB, I, 2 * GH, gates, 2 * GH, w_ih0, I, dx, I, 0.0f, precision, ws, ws_bytes, stream, xcd_allow);
-      if (rc) return rc;
-      dx_done = true;
-    } else if (ws && ws_bytes > wcat_bytes + ((size_t)64 << 20)) {
-      float *wcat = (float *)ws;
-      CTCN_HIP(hipMemcpyAsync(wcat, w_ih0, (size_t)GH * I * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-      CTCN_HIP(hipMemcpyAsync(wcat + (size_t)GH * I, w_ih1, (size_t)GH * I * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-      int rc = ctcn_gemm_on_xcds(0, 0, TB, I, 2 * GH, gates, 2 * GH, wcat, I, dx, I, 0.0f, precision, (char *)ws + wcat_bytes, ws_bytes - wcat_bytes,
-                                 stream, xcd_allow);
-      if (rc) return rc;
+    StackedWih s;
+    if (int rc = stack_w_ih(w_ih0, w_ih1, GH, I, ws, ws_bytes, (hipStream_t)stream, s)) return rc;
+    if (s.w) {
+      if (int rc = ctcn_gemm_on_xcds(0, 0, TB, I, 2 * GH, gates, 2 * GH, s.w, I, dx, I, 0.0f, precision, s.ws, s.ws_bytes, stream, xcd_allow)) return rc;
       dx_done = true;
     }
   }
@@ -2957,10 +2963,126 @@ static int rnn_bwd_gemms(int cell, int T, int B, int I, int H, int dirs, const f
   return CTCN_OK;
 }
 
-// `call.prelaunch_event` (hipEvent_t): recorded on the stream right before the recurrence is launched, i.e. behind this call's own preparatory
-// memsets / transposes: work that the host wants to run NEXT TO the recurrence on another stream waits for this event -- waiting for
-// "everything before ctcn_rnn_bwd" instead lets it start early and delay those small kernels (measured: a 5 us memset took 116-122 us when
-// the side stream's queue kernels were dispatched first).
+// ---- ctcn_rnn_bwd_ex ------------------------------------------------------------------------------------------------------------------------
+// One backward call as its steps see it (as FwdCall).
+struct BwdCall {
+  int cell, T, B, I, H, dirs, precision;
+  const float *dy;
+  void *ws; size_t ws_bytes;
+  void *stream;
+  const ctcn_rnn_call &call;
+  int G, GH;
+  RnnArgs a;                  // a.dy: dy, or call.dy_tmp once materialise_dropped_dy has run
+  dim3 grid;                  // (16-unit slices, directions, 16-row batch tiles): the per-timestep and the device-scope persistent grid
+  int *status;
+  bool fits32;                // one 32-bit-offset buffer resource per tensor
+  bool dy_dropped;            // dy needs no mask any more: no request, or the dropout kernel has produced call.dy_tmp
+  // `call.prelaunch_event` (hipEvent_t): recorded on the stream right before the recurrence is launched, i.e. behind this call's own preparatory
+  // memsets / transposes: work that the host wants to run NEXT TO the recurrence on another stream waits for this event -- waiting for
+  // "everything before ctcn_rnn_bwd" instead lets it start early and delay those small kernels (measured: a 5 us memset took 116-122 us when
+  // the side stream's queue kernels were dispatched first).
+  void *prelaunch_event;      // NULL once recorded
+  int nxd;                    // XCDs the XCD-local hand-off can use (1: none, or option "handoff" off)
+  bool persistent, bwd_scatter, fused_dropout;
+  int handoff_tags, item_gather, rsv_nt, poll_delay, slow_items, slow_exchange;
+  hipStream_t st() const { return (hipStream_t)stream; }
+};
+
+static void record_prelaunch(BwdCall &c) {
+  if (!c.prelaunch_event) return;
+  (void)hipEventRecord((hipEvent_t)c.prelaunch_event, c.st());
+  c.prelaunch_event = nullptr;
+}
+
+// dy is the gradient of the DROPPED output and the kernel about to run does not apply the mask itself: the stand-alone dropout kernel
+// writes the masked gradient to call.dy_tmp, once, and the recurrence reads that
+static int materialise_dropped_dy(BwdCall &c) {
+  if (c.dy_dropped) return CTCN_OK;
+  const ctcn_rnn_call &k = c.call;
+  if (int rc = ctcn_dropout(c.dy, k.dy_tmp, (size_t)c.T * c.B * c.dirs * c.H, k.drop_p, k.drop_seed, k.drop_offset, c.stream)) return rc;
+  c.a.dy = k.dy_tmp; c.dy_dropped = true;
+  return CTCN_OK;
+}
+
+// Which persistent backward kernel, and what it needs of the workspace.
+// scatter formulation (default): partial dh tiles travel, 1 KB per (owner, source) pair; gather formulation: the da tile
+// measured: scatter wins at H = 320 (2.46 vs 2.68 us per step), ties at H = 128, loses at H = 512 (nsl^2 KB of partial tiles
+// per group and step) and at precision 0 (f32 MFMA: 32 cycles x 16 per tile on 4 waves per SIMD)
+// item-wave gather (rnn_bwd_scatter2, option "bwd_item_gather"): tagged hand-off only, up to 40 slices (H <= 640), 16-B aligned reserves
+// (gates / aux are checked by the validation; dy, y and -- when the unfused dropout pass feeds the kernel -- dy_tmp here: 16-B LDS DMA and f32x4 stores)
+// "bwd_item_gather": 0 never, 1 (default) where it measured faster -- more than 20 slices, i.e. H > 320 (tools/mb_bwd2.hip: H = 384 1.58 vs
+// 1.63 us per step, H = 512 2.44 vs 3.38 for the gather formulation, the only other kernel there; H = 320 1.90 vs 1.88, H = 128 1.25 vs 1.19) --, 2 always
+struct BwdPlan { int kq, nbt, nsl, groups, prec, ntw; bool gather2, scatter, feasible; size_t hx_bytes, fl_bytes; };
+static BwdPlan bwd_choose_formulation(const BwdCall &c) {
+  BwdPlan p;
+  p.kq = ceil_div(c.GH, 256);
+  if (p.kq == 7) p.kq = 8;
+  p.nbt = c.grid.z; p.nsl = c.grid.x; p.groups = c.dirs * p.nbt;
+  const int nsl = p.nsl;
+  p.prec = c.precision == 1 && c.H % 8 == 0 ? 1 : 0;           // bf16x3 recurrent matmul
+  p.gather2 = (c.item_gather == 2 || (c.item_gather >= 1 && (nsl > 20 || !c.fits32))) && nsl <= 40 && c.handoff_tags && c.H % 4 == 0 &&
+              (uintptr_t)c.dy % 16 == 0 && (uintptr_t)c.a.y % 16 == 0 && (!c.call.dy_tmp || (uintptr_t)c.call.dy_tmp % 16 == 0);
+  p.scatter = c.bwd_scatter && p.prec && nsl <= (p.gather2 ? 40 : 24);
+  p.ntw = nsl <= 12 ? 1 : 2;                        // rnn_bwd_scatter: output tiles per scattering wave (12 of them; nsl <= 24)
+  p.hx_bytes = p.scatter ? align_up((size_t)2 * p.groups * nsl * nsl * 1024, 256)
+                         : align_up((size_t)2 * p.groups * (p.prec ? ceil_div(c.GH, 32) * 512 : ceil_div(c.GH, 16) * 256) * sizeof(float), 256);
+  p.fl_bytes = align_up((size_t)2 * p.groups * nsl * (p.scatter ? nsl : 1) * sizeof(unsigned), 256) + 256;   // + role tickets
+  // (a reserve of 4 GB or more: only rnn_bwd_scatter2 -- 64-bit reserve addresses -- may take it; the other persistent kernels address a
+  // reserve through one 32-bit buffer resource)
+  p.feasible = (p.kq <= 8 || p.scatter) && (c.fits32 || (p.scatter && p.gather2));
+  return p;
+}
+
+// one attempt at the chosen persistent kernel, XCD-local (mode 1) or device scope (mode 0); `done`: it is co-resident and queued
+static int bwd_try_persistent(BwdCall &c, const BwdPlan &p, const Handoff &h, int mode, bool &done) {
+  const int nx = mode ? c.nxd : 1, nsl = p.nsl, wpx = ceil_div(p.groups, nx) * nsl;
+  hipStream_t st = c.st();
+  PersistArgs pa = persist_args(c.a, h, c.status, {mode, nx, p.groups, nsl, p.nbt, 16, wpx});
+  const dim3 pgrid = mode ? xcd_local_grid(nx, wpx) : c.grid;
+  if (!p.scatter) {
+    if (int rc = materialise_dropped_dy(c)) return rc;
+    pa.a.dy = c.a.dy;
+    CTCN_HIP(clear_handoff(h, p.prec != 0, st));
+    record_prelaunch(c);
+    done = launch_bwd_persist(p.prec, p.kq, pgrid, 0, st, pa, wpx);
+    if (done) note_kernel(1, "rnn_bwd_persist", c.call);
+    return CTCN_OK;
+  }
+  pa.tagmode = c.handoff_tags;
+  pa.slow = c.slow_items; pa.slow_x = c.slow_exchange;
+  CTCN_HIP(clear_handoff(h, pa.tagmode != 0, st));
+  if (!c.dy_dropped && c.fused_dropout) {
+    pa.drop_bwd = 1; pa.drop_p = c.call.drop_p; pa.drop_scale = 1.0f / (1.0f - c.call.drop_p); pa.drop_seed = c.call.drop_seed; pa.drop_off = c.call.drop_offset;
+  } else {
+    if (int rc = materialise_dropped_dy(c)) return rc;
+    pa.a.dy = c.a.dy;
+  }
+  record_prelaunch(c);
+  if (p.gather2) {
+    pa.rsv_nt = c.rsv_nt;
+    pa.poll_delay = c.poll_delay < 0 ? (nsl <= 24 ? 16 : 24) : c.poll_delay;     // auto: the exchange phase grows with the tiles per wave (cfg4: 2.69 -> 2.55 us per step)
+    done = launch_bwd_scatter2(nsl, pgrid, st, pa, wpx);
+    if (done) note_kernel(1, "rnn_bwd_scatter2", c.call);
+  } else {
+    done = launch_bwd_scatter(p.prec, p.ntw, pgrid, st, pa, wpx);
+    if (done) note_kernel(1, "rnn_bwd_scatter", c.call);
+  }
+  return CTCN_OK;
+}
+
+static int bwd_per_timestep(BwdCall &c) {
+  if (int rc = materialise_dropped_dy(c)) return rc;
+  // (the carried dc / dh*z of the per-timestep kernels lives in `state`; the persistent kernels keep it in registers)
+  CTCN_HIP(hipMemsetAsync(c.a.state, 0, (size_t)c.B * c.dirs * c.H * sizeof(float), c.st()));
+  const int kq4 = pick_kq4(c.GH, 16, 1, 5);
+  note_kernel(1, "rnn_bwd_step", c.call);
+  for (int s = 0; s < c.T; ++s) {
+    c.a.step = s;
+    launch_bwd(kq4, c.grid, c.st(), c.a);
+  }
+  return CTCN_OK;
+}
+
 extern "C" int ctcn_rnn_bwd_ex(int cell, int T, int B, int I, int H, int dirs, const float *x, const float *w_ih0,
                                const float *w_hh0, const float *w_ih1, const float *w_hh1, const float *y,
                                float *gates, float *aux, const float *dy, float *dx, float *dw_ih0, float *dw_hh0,
@@ -2968,13 +3090,6 @@ extern "C" int ctcn_rnn_bwd_ex(int cell, int T, int B, int I, int H, int dirs, c
                                size_t ws_bytes, void *stream, const ctcn_rnn_call *call_p) {
   const ctcn_rnn_call &call = call_p ? *call_p : k_plain_call;
   CTCN_REQUIRE(!call.dy_tmp || (call.drop_p >= 0.0f && call.drop_p < 1.0f), "ctcn_rnn_bwd_ex: dropout p=%f outside [0,1)", (double)call.drop_p);
-  int *const status_word = call.status ? call.status : ctcn_status_word();
-  void *prelaunch_event = call.prelaunch_event;
-  auto record_prelaunch = [&](hipStream_t s_) {
-    if (!prelaunch_event) return;
-    (void)hipEventRecord((hipEvent_t)prelaunch_event, s_);
-    prelaunch_event = nullptr;
-  };
   CTCN_REQUIRE(cell >= 0 && cell <= 2, "ctcn_rnn_bwd: unknown cell %d", cell);
   CTCN_REQUIRE(T > 0 && B > 0 && I > 0 && H > 0 && (dirs == 1 || dirs == 2), "ctcn_rnn_bwd: bad dims");
   if (H % 4 != 0) { ctcn_set_error("ctcn_rnn_bwd: hidden size %d must be a multiple of 4", H); return CTCN_EUNSUPPORTED; }
@@ -2984,121 +3099,45 @@ extern "C" int ctcn_rnn_bwd_ex(int cell, int T, int B, int I, int H, int dirs, c
   CTCN_REQUIRE(cell == CTCN_CELL_TANH || aux, "ctcn_rnn_bwd: aux reserve required for LSTM/GRU");
   CTCN_REQUIRE((uintptr_t)gates % 16 == 0 && (uintptr_t)scratch % 16 == 0 && (cell == CTCN_CELL_TANH || (uintptr_t)aux % 16 == 0),
                "ctcn_rnn_bwd: gates / aux / scratch must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const int G = gates_of(cell);
-  const int GH = G * H;
-  struct { float p; unsigned long long seed, off; float *tmp; } const bd = {call.drop_p, (unsigned long long)call.drop_seed, (unsigned long long)call.drop_offset, call.dy_tmp};
-  bool dy_dropped = call.dy_tmp == nullptr;      // true once dy needs no mask any more: no request, or the dropout kernel has produced bd.tmp
-  const float *w_hh[2] = {w_hh0, w_hh1};
+  BwdCall c = {cell, T, B, I, H, dirs, precision, dy, ws, ws_bytes, stream, call};
+  c.G = gates_of(cell); c.GH = c.G * H;
+  const int GH = c.GH;
+  c.grid = dim3(ceil_div(H, 16), dirs, ceil_div(B, 16));
+  c.status = call.status ? call.status : ctcn_status_word();
+  c.fits32 = (size_t)T * B * dirs * GH * sizeof(float) < ((size_t)1 << 32);
+  c.dy_dropped = call.dy_tmp == nullptr;
+  c.prelaunch_event = call.prelaunch_event;
+  c.nxd = ctcn_opt_handoff() ? ctcn_device_xcds() : 1;
+  c.persistent = ctcn_opt_rnn_persistent() != 0; c.bwd_scatter = ctcn_opt_bwd_scatter() != 0; c.fused_dropout = ctcn_get_option("rnn_fused_dropout") != 0;
+  c.handoff_tags = ctcn_opt_handoff_tags(); c.item_gather = ctcn_get_option("bwd_item_gather"); c.rsv_nt = ctcn_get_option("rnn_rsv_nt");
+  c.poll_delay = ctcn_get_option("bwd_poll_delay"); c.slow_items = ctcn_get_option("rnn_slow_items"); c.slow_exchange = ctcn_get_option("rnn_slow_exchange");
+
+  // W_hh^T of both directions, then the carried state of the per-timestep kernels, in `scratch` (ctcn_rnn_scratch_bytes)
   float *whhT = (float *)scratch;
-  float *state = (float *)((char *)scratch + align_up((size_t)dirs * GH * H * sizeof(float), 256));
   if (dirs == 2) {
-    if (int rc = ctcn_transpose01_pair(w_hh[0], w_hh[1], whhT, whhT + (size_t)GH * H, GH, H, 1, stream)) return rc;
-  } else if (int rc = ctcn_transpose01(w_hh[0], whhT, GH, H, 1, stream)) {
+    if (int rc = ctcn_transpose01_pair(w_hh0, w_hh1, whhT, whhT + (size_t)GH * H, GH, H, 1, stream)) return rc;
+  } else if (int rc = ctcn_transpose01(w_hh0, whhT, GH, H, 1, stream)) {
     return rc;
   }
-  RnnArgs a;
-  a.cell = cell; a.T = T; a.B = B; a.H = H; a.D = dirs; a.G = G; a.step = 0;
+  RnnArgs &a = c.a;
+  a.cell = cell; a.T = T; a.B = B; a.H = H; a.D = dirs; a.G = c.G; a.step = 0;
   a.w0 = whhT; a.w1 = whhT + (size_t)GH * H; a.y = const_cast<float *>(y); a.gates = gates; a.aux = aux; a.dy = dy;
-  a.state = state;
-  dim3 grid(ceil_div(H, 16), dirs, ceil_div(B, 16));
+  a.state = (float *)((char *)scratch + align_up((size_t)dirs * GH * H * sizeof(float), 256));
+
   bool done = false;
-  const bool fits32 = (size_t)T * B * dirs * GH * sizeof(float) < ((size_t)1 << 32);   // one 32-bit-offset resource per tensor
-  // (a reserve of 4 GB or more: only rnn_bwd_scatter2 -- 64-bit reserve addresses -- may take it; the other persistent kernels address a
-  // reserve through one 32-bit buffer resource)
-  if (ctcn_opt_rnn_persistent() && T > 1) {
-    int kq = ceil_div(GH, 256);
-    if (kq == 7) kq = 8;
-    const int nbt = grid.z, nsl = grid.x, groups = dirs * nbt;
-    const int prec = precision == 1 && H % 8 == 0 ? 1 : 0;           // bf16x3 recurrent matmul
-    // scatter formulation (default): partial dh tiles travel, 1 KB per (owner, source) pair; gather formulation: the da tile
-    // measured: scatter wins at H = 320 (2.46 vs 2.68 us per step), ties at H = 128, loses at H = 512 (nsl^2 KB of partial tiles
-    // per group and step) and at precision 0 (f32 MFMA: 32 cycles x 16 per tile on 4 waves per SIMD)
-    // item-wave gather (rnn_bwd_scatter2, option "bwd_item_gather"): tagged hand-off only, up to 40 slices (H <= 640), 16-B aligned reserves
-    // (gates / aux are checked above; dy, y and -- when the unfused dropout pass feeds the kernel -- dy_tmp here: 16-B LDS DMA and f32x4 stores)
-    // "bwd_item_gather": 0 never, 1 (default) where it measured faster -- more than 20 slices, i.e. H > 320 (tools/mb_bwd2.hip: H = 384 1.58 vs
-    // 1.63 us per step, H = 512 2.44 vs 3.38 for the gather formulation, the only other kernel there; H = 320 1.90 vs 1.88, H = 128 1.25 vs 1.19) --, 2 always
-    const int ig = ctcn_get_option("bwd_item_gather");
-    const bool gather2 = (ig == 2 || (ig >= 1 && (nsl > 20 || !fits32))) && nsl <= 40 && ctcn_opt_handoff_tags() && H % 4 == 0 && (uintptr_t)dy % 16 == 0 && (uintptr_t)y % 16 == 0 &&
-                         (!call.dy_tmp || (uintptr_t)call.dy_tmp % 16 == 0);
-    const bool scatter = ctcn_opt_bwd_scatter() && prec && nsl <= (gather2 ? 40 : 24);
-    const int ntw = nsl <= 12 ? 1 : 2;                        // rnn_bwd_scatter: output tiles per scattering wave (12 of them; nsl <= 24)
-    const size_t hx_bytes = scatter ? align_up((size_t)2 * dirs * nbt * nsl * nsl * 1024, 256)
-                                    : align_up((size_t)2 * dirs * nbt * (prec ? ceil_div(GH, 32) * 512 : ceil_div(GH, 16) * 256) * sizeof(float), 256);
-    const size_t fl_bytes = align_up((size_t)2 * dirs * nbt * nsl * (scatter ? nsl : 1) * sizeof(unsigned), 256) + 256;   // + role tickets
-    const size_t lds = 0;
-    for (int mode = ctcn_opt_handoff() ? 1 : 0; mode >= 0 && !done && (kq <= 8 || scatter) && (fits32 || (scatter && gather2)) && ws && ws_bytes >= hx_bytes + fl_bytes + 512; --mode) {
-      const int nx = mode ? ctcn_device_xcds() : 1;
-      if (mode && nx <= 1) continue;
-      const int wpx = ceil_div(groups, nx) * nsl;
-      PersistArgs pa = {};
-      pa.a = a;
-      char *tail = (char *)ws + ((ws_bytes - hx_bytes - fl_bytes) & ~(size_t)255);
-      pa.hx = (float *)tail;
-      pa.flags = (unsigned *)(tail + hx_bytes);
-      pa.status = status_word;
-      pa.spin_limit = SPIN_LIMIT;
-      pa.local = mode; pa.nx = nx; pa.xperm = mode ? xcd_order_for(nx, groups) : 0; pa.nsl = nsl; pa.nbt = nbt; pa.hsu = 16; pa.nbig = 0; pa.hsu_small = 0; pa.wpx = wpx; pa.poll_depth = ctcn_opt_poll_depth(); pa.tagmode = 0;
-      pa.tickets = (unsigned *)(tail + hx_bytes + fl_bytes - 256);
-#ifdef CTCN_PERSIST_STATS
-      pa.stats = nullptr;
-#endif
-      const dim3 pgrid = mode ? dim3(nx * (wpx + std::max(2, wpx / 8)), 1, 1) : grid;
-      // flags + tickets, and the hand-off tiles where they start from zero (tags / partial sums): the two areas are contiguous -> one memset
-      if (scatter) {
-        pa.tagmode = ctcn_opt_handoff_tags();
-        pa.slow = ctcn_get_option("rnn_slow_items"); pa.slow_x = ctcn_get_option("rnn_slow_exchange");
-        if (pa.tagmode) CTCN_HIP(hipMemsetAsync(pa.hx, 0, hx_bytes + fl_bytes, st));
-        else CTCN_HIP(hipMemsetAsync(pa.flags, 0, fl_bytes, st));
-        if (!dy_dropped && ctcn_get_option("rnn_fused_dropout") != 0) {
-          pa.drop_bwd = 1; pa.drop_p = bd.p; pa.drop_scale = 1.0f / (1.0f - bd.p); pa.drop_seed = bd.seed; pa.drop_off = bd.off;
-        } else if (!dy_dropped) {
-          if (int rc = ctcn_dropout(dy, bd.tmp, (size_t)T * B * dirs * H, bd.p, bd.seed, bd.off, stream)) return rc;
-          a.dy = bd.tmp; pa.a.dy = bd.tmp; dy_dropped = true;
-        }
-        record_prelaunch(st);
-        if (gather2) {
-          pa.rsv_nt = ctcn_get_option("rnn_rsv_nt");
-          pa.poll_delay = ctcn_get_option("bwd_poll_delay");
-          if (pa.poll_delay < 0) pa.poll_delay = nsl <= 24 ? 16 : 24;        // auto: the exchange phase grows with the tiles per wave (cfg4: 2.69 -> 2.55 us per step)
-          done = launch_bwd_scatter2(nsl, pgrid, st, pa, wpx);
-          if (done) { g_last_kernel[1] = "rnn_bwd_scatter2"; if (call.launched) *call.launched = "rnn_bwd_scatter2"; }
-        } else {
-          done = launch_bwd_scatter(prec, ntw, pgrid, st, pa, wpx);
-          if (done) { g_last_kernel[1] = "rnn_bwd_scatter"; if (call.launched) *call.launched = "rnn_bwd_scatter"; }
-        }
-      } else {
-        if (!dy_dropped) {
-          if (int rc = ctcn_dropout(dy, bd.tmp, (size_t)T * B * dirs * H, bd.p, bd.seed, bd.off, stream)) return rc;
-          a.dy = bd.tmp; pa.a.dy = bd.tmp; dy_dropped = true;
-        }
-        if (prec) CTCN_HIP(hipMemsetAsync(pa.hx, 0, hx_bytes + fl_bytes, st));
-        else CTCN_HIP(hipMemsetAsync(pa.flags, 0, fl_bytes, st));
-        record_prelaunch(st);
-        done = launch_bwd_persist(prec, kq, pgrid, lds, st, pa, wpx);
-        if (done) { g_last_kernel[1] = "rnn_bwd_persist"; if (call.launched) *call.launched = "rnn_bwd_persist"; }
-      }
-    }
+  if (c.persistent && T > 1) {
+    const BwdPlan p = bwd_choose_formulation(c);
+    Handoff h;
+    if (p.feasible && carve_handoff(ws, ws_bytes, p.hx_bytes, p.fl_bytes, h))
+      for (int mode = c.nxd > 1 ? 1 : 0; mode >= 0 && !done; --mode)
+        if (int rc = bwd_try_persistent(c, p, h, mode, done)) return rc;
+    if (!done)
+      log_fallback("ctcn_rnn_bwd", T, B, H, dirs, !c.fits32 ? "a reserve tensor of 4 GB or more"
+                                                       : (ceil_div(GH, 256) > 8 ? "gate width G*H above 2048" : "not co-resident / workspace too small"));
   }
-  record_prelaunch(st);          // no-op if a persistent launch already consumed the event
-  if (!done && ctcn_opt_rnn_persistent() && T > 1)
-    log_fallback("ctcn_rnn_bwd", T, B, H, dirs, !fits32 ? "a reserve tensor of 4 GB or more"
-                                                     : (ceil_div(GH, 256) > 8 ? "gate width G*H above 2048" : "not co-resident / workspace too small"));
-  if (!done) {
-    if (!dy_dropped) {
-      if (int rc = ctcn_dropout(dy, bd.tmp, (size_t)T * B * dirs * H, bd.p, bd.seed, bd.off, stream)) return rc;
-      a.dy = bd.tmp; dy_dropped = true;
-    }
-    // (the carried dc / dh*z of the per-timestep kernels lives in `state`; the persistent kernels keep it in registers)
-    CTCN_HIP(hipMemsetAsync(state, 0, (size_t)B * dirs * H * sizeof(float), st));
-    const int kq4 = pick_kq4(GH, 16, 1, 5);
-    g_last_kernel[1] = "rnn_bwd_step";
-    if (call.launched) *call.launched = "rnn_bwd_step";
-    for (int s = 0; s < T; ++s) {
-      a.step = s;
-      launch_bwd(kq4, grid, st, a);
-    }
-  }
+  record_prelaunch(c);           // no-op if a persistent launch already consumed the event
+  if (!done)
+    if (int rc = bwd_per_timestep(c)) return rc;
   CTCN_LAUNCH_CHECK();
 
   if (ctcn_opt_recurrence_only()) return CTCN_OK;

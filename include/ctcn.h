@@ -94,11 +94,6 @@ int ctcn_device_xcds(void);
  * 5 -- both XCDs of a pair on the same side -- 13.26-13.31; cfg1 / cfg3 / shipped YAML unchanged.  A recurrence that takes EVERY XCD (cfg4:
  * groups = XCDs) keeps group g on XCD g whatever the option says: there is nothing to place.  (The cfg4 trajectory divergence first seen while the
  * order applied to that launch too had nothing to do with placement: round 6 traced it to the parked tiles of rnn_fwd_tagged)
- * "rnn_proj_order" = 0 (default): 1 issues the input projection of a recurrent layer as the row blocks [T/2, T) then [0, T/2) (pipelined form:
- * the last time chunk before the first) instead of one product over ascending time.  Same products, bit-identical results.  Built in round 6 as a
- * mitigation while the cfg4 trajectory divergence was taken for a stale read behind a kernel boundary; the after-suite A/Bs showed both orders
- * deviating alike and the cause turned out to be the single-buffered parked tiles of rnn_fwd_tagged (rnn.hip) -- kept as a
- * switch for the record, off.
  * "rnn_slow_items" = 0 (parity harness): N > 0 runs the SLOW instantiation of rnn_fwd_tagged, whose item waves sleep N x 64 cycles before they read
  * the parked partial tiles, at every step.  Results must not change (test_rnn_fwd_tagged_with_slow_item_waves): the hand-off inside a workgroup may
  * rest on barriers and buffer parity only, never on which wave is faster.  "rnn_slow_exchange" = N: the same for the exchange waves; both options also select

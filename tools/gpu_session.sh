@@ -71,19 +71,6 @@ case $S in
   # keep the logs of the runs that deviated, drop the bulky rest
   for i in 1 2 3 4; do grep -q "first difference" $O/traj_compare_$i.txt || rm -f $O/traj_full_$i.jsonl; done
   ;;
-7)
-  # the mitigation under test (option rnn_proj_order = 1, default): full traced suites -- the divergence showed in 2 of 4 of them with the old order
-  for i in 1 2 3; do
-    CTCN_TRAJ_LOG=$O/traj_full_$i.jsonl timeout 1500 python -m pytest tests -m gpu -q --maxfail=20 --timeout 600 -p no:cacheprovider --durations=12 > $O/pytest_full_$i.log 2>&1; echo "full $i rc=$?" >> $O/summary.log
-    python tools/traj_compare.py $O/traj_full_$i.jsonl > $O/traj_compare_$i.txt 2>&1
-    tail -n 3 $O/pytest_full_$i.log | cut -c1-200
-  done
-  python tools/traj_compare.py $O/traj_*.jsonl > $O/traj_compare.txt 2>&1
-  cat $O/summary.log $O/traj_compare.txt | cut -c1-400
-  for i in 1 2 3; do grep -q "first difference" $O/traj_compare_$i.txt || rm -f $O/traj_full_$i.jsonl; done
-  timeout 1200 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" >> $O/summary.log
-  CTCN_OPT_RNN_PROJ_ORDER=0 timeout 600 python bench.py --full --no-cpu-baseline --no-decode --no-pmc --no-ragged --no-sync-bn-cost > $O/bench_order0.json 2> $O/bench_order0.err
-  ;;
 8)
   # round-6 evidence (profiles/r06_*) + three more traced full suites with the projection order fix
   bash tools/run_profiles_r6.sh > $O/run_profiles.log 2>&1
@@ -160,94 +147,20 @@ PY
     done; } > $O/stale_probe.txt 2>&1
   cat $O/stale_probe.txt | cut -c1-250
   ;;
-14)
-  # the order fix A/B-ed IN the process that has just run the full suite (where the divergence lives), twice
-  for i in 1 2; do
-    CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_suite_ab.json CTCN_AFTER_SUITE_N=25 timeout 1800 python -m pytest tests -m gpu -q --maxfail=20 --timeout 600 -p no:cacheprovider -s > $O/pytest_full_$i.log 2>&1; echo "full $i rc=$?" >> $O/summary.log
-    grep "after_suite_ab" $O/pytest_full_$i.log | cut -c1-600
-  done
-  cat $O/summary.log
-  ;;
-15)
-  # which process condition does the cfg4 divergence need?  after the suite: as-is | GC off | emptied allocator pool | as-is again; and a FRESH process whose host lags
-  CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_suite_ab.json CTCN_AFTER_SUITE_N=16 timeout 1800 python -m pytest tests -m gpu -q --maxfail=20 --timeout 600 -p no:cacheprovider -s > $O/pytest_full_1.log 2>&1; echo "full rc=$?" >> $O/summary.log
-  grep "after_suite_ab" $O/pytest_full_1.log | cut -c1-1500
-  ( CTCN_STEP_LAG=0.04 timeout 600 python tools/traj_bisect.py cfg4 12 40 squat 2>&1 | grep -v "amdgpu.ids\|Warning" ) > $O/bisect_lag.txt; tail -n 6 $O/bisect_lag.txt | cut -c1-300
-  ;;
-16)
-  # which tests put the process into the state where cfg4 trajectories deviate?  (24 traced runs after each subset, in the subset's process)
-  SPAWN="two_ranks or bench_ or rank_invariant or rank_failure or torchrun"
-  i=0
-  for sel in "not ($SPAWN)" "$SPAWN" "beam or decode or greedy or join" "rnn or lstm or gru"; do
-    i=$((i+1))
-    CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_$i.json CTCN_AFTER_SUITE_N=24 CTCN_AFTER_SUITE_PHASES=order1 timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -s -k "$sel" > $O/pytest_$i.log 2>&1
-    echo "subset $i [$sel]: $(grep -o '"summary": "[^"]*"' $O/pytest_$i.log)  $(tail -n 1 $O/pytest_$i.log | cut -c1-100)" | tee -a $O/summary.log
-  done
-  ;;
-17)
-  # narrowing: which of the recurrent-layer tests; and does the workspace's content matter (fresh process, garbage in the workspaces before every run)?
-  i=0
-  for sel in "item_gather or persistent_equals or batch_chunks or stateless or 4gb or unaligned or xcd_order" "model_three or rnn_layer or rnn_module or side_stream_equals or projection_overlap"; do
-    i=$((i+1))
-    CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_$i.json CTCN_AFTER_SUITE_N=24 CTCN_AFTER_SUITE_PHASES=order1 timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -s -k "$sel" > $O/pytest_$i.log 2>&1
-    echo "subset $i [$sel]: $(grep -o '"summary": "[^"]*"' $O/pytest_$i.log)  $(tail -n 1 $O/pytest_$i.log | cut -c1-100)" | tee -a $O/summary.log
-  done
-  ( CTCN_WS_FILL=rand timeout 600 python tools/traj_bisect.py cfg4 12 30 2>&1 | grep -v "amdgpu.ids\|Warning" ) > $O/bisect_wsrand.txt; echo "fresh process, random workspaces: $(tail -n 1 $O/bisect_wsrand.txt)" | tee -a $O/summary.log
-  ;;
-18)
-  i=0
-  for sel in "item_gather_equals or item_gather_edge" "persistent_equals or batch_chunks" "stateless or 4gb or unaligned" "xcd_order"; do
-    i=$((i+1))
-    CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_$i.json CTCN_AFTER_SUITE_N=30 CTCN_AFTER_SUITE_PHASES=order1 timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -s -k "$sel" > $O/pytest_$i.log 2>&1
-    echo "subset $i [$sel]: $(grep -o '"summary": "[^"]*"' $O/pytest_$i.log)  $(tail -n 1 $O/pytest_$i.log | cut -c1-100)" | tee -a $O/summary.log
-  done
-  ;;
 19)
   # does an earlier persistent launch of cfg4's geometry at another T poison the process?  (T mod 4 decides the tags it leaves in the hand-off tiles)
   for T in 30 40 31 0; do ( timeout 400 python tools/prelude_ab.py $T 6 gru 30 2>&1 | grep -v "amdgpu.ids\|Warning" | tail -n 2 ) | tee -a $O/prelude.txt; done
-  ;;
-20)
-  i=0
-  for sel in "item_gather_equals" "item_gather_edge" "persistent_equals" "batch_chunks_equal" "batch_chunks_into_flat" "xcd_order"; do
-    i=$((i+1))
-    CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_$i.json CTCN_AFTER_SUITE_N=30 CTCN_AFTER_SUITE_PHASES=order1 timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -s -k "$sel" > $O/pytest_$i.log 2>&1
-    echo "subset $i [$sel]: $(grep -o '"summary": "[^"]*"' $O/pytest_$i.log)  $(tail -n 1 $O/pytest_$i.log | cut -c1-80)" | tee -a $O/summary.log
-    grep "process state" $O/pytest_$i.log | cut -c1-400 | tee -a $O/summary.log
-  done
   ;;
 21)
   # WHERE does a deviating bottom layer leave the others (element pattern), is it the projection or the recurrence, and which arm removes it
   CTCN_AFTER_SUITE=$R/tools/first_rows_probe.py CTCN_PROBE_OUT=$O/probe.jsonl CTCN_PROBE_N=${PROBE_N:-1000} CTCN_PROBE_RUNS=${PROBE_RUNS:-30} timeout 1500 python -m pytest tests -m gpu -q --timeout 900 -p no:cacheprovider -s -k "item_gather_edge or batch_chunks_equal" > $O/pytest.log 2>&1
   grep "^\[probe\]" $O/pytest.log | cut -c1-1800; tail -n 3 $O/pytest.log | cut -c1-300
   ;;
-22)
-  # does session 20's condition come back with the rnn_dbg build (a) after_suite_ab as in session 20, (b) the probe's runs part alone, squatters on every other run
-  i=0
-  for sel in "item_gather_edge" "batch_chunks_equal"; do
-    i=$((i+1))
-    CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_$i.json CTCN_AFTER_SUITE_N=30 CTCN_AFTER_SUITE_PHASES=order1 timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -s -k "$sel" > $O/pytest_$i.log 2>&1
-    echo "subset $i [$sel]: $(grep -o '"summary": "[^"]*"' $O/pytest_$i.log)  $(tail -n 1 $O/pytest_$i.log | cut -c1-80)" | tee -a $O/summary.log
-  done
-  CTCN_AFTER_SUITE=$R/tools/first_rows_probe.py CTCN_PROBE_OUT=$O/probe.jsonl CTCN_PROBE_PARTS=runs CTCN_PROBE_ARMS="base:" CTCN_PROBE_SQUAT=alt CTCN_PROBE_RUNS=40 timeout 1500 python -m pytest tests -m gpu -q --timeout 900 -p no:cacheprovider -s -k "item_gather_edge or batch_chunks_equal" > $O/pytest.log 2>&1
-  grep "^\[probe\]" $O/pytest.log | cut -c1-2500; tail -n 1 $O/pytest.log | cut -c1-300
-  ;;
-23)
-  # is the condition a property of the BUILD?  the previous library (HEAD~rnn_dbg) and the rnn_dbg one, alternating on one box (tools/libctcn_{prev,dbg}.so are built by hand)
-  cp ctc_pytorch_amd/libctcn.so $O/libctcn_keep.so
-  i=0
-  for rep in 1 2; do for lib in prev dbg; do for sel in "item_gather_edge" "batch_chunks_equal"; do
-    i=$((i+1))
-    cp tools/libctcn_$lib.so ctc_pytorch_amd/libctcn.so
-    CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_$i.json CTCN_AFTER_SUITE_N=30 CTCN_AFTER_SUITE_PHASES=order1 timeout 600 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -s -k "$sel" > $O/pytest_$i.log 2>&1
-    echo "$i lib $lib [$sel]: $(grep -o '"summary": "[^"]*"' $O/pytest_$i.log)  $(tail -n 1 $O/pytest_$i.log | cut -c1-80)" | tee -a $O/summary.log
-  done; done; done
-  cp $O/libctcn_keep.so ctc_pytorch_amd/libctcn.so; rm -f $O/libctcn_keep.so
-  ;;
 24)
   # the element pattern of a deviating bottom layer, with the library that shows the condition (tools/libctcn_prev.so)
   cp ctc_pytorch_amd/libctcn.so $O/libctcn_keep.so
   cp tools/libctcn_${LIBV:-prev}.so ctc_pytorch_amd/libctcn.so
-  CTCN_AFTER_SUITE=$R/tools/first_rows_probe.py CTCN_PROBE_OUT=$O/probe.jsonl CTCN_PROBE_PARTS=runs CTCN_PROBE_ARMS="${ARMS:-base:,rsv0:fwd_rsv_lds=0,order0:rnn_proj_order=0}" CTCN_PROBE_SQUAT=alt CTCN_PROBE_RUNS=${PROBE_RUNS:-40} timeout 1500 python -m pytest tests -m gpu -q --timeout 900 -p no:cacheprovider -s -k "batch_chunks_equal" > $O/pytest.log 2>&1
+  CTCN_AFTER_SUITE=$R/tools/first_rows_probe.py CTCN_PROBE_OUT=$O/probe.jsonl CTCN_PROBE_PARTS=runs CTCN_PROBE_ARMS="${ARMS:-base:,rsv0:fwd_rsv_lds=0}" CTCN_PROBE_SQUAT=alt CTCN_PROBE_RUNS=${PROBE_RUNS:-40} timeout 1500 python -m pytest tests -m gpu -q --timeout 900 -p no:cacheprovider -s -k "batch_chunks_equal" > $O/pytest.log 2>&1
   cp $O/libctcn_keep.so ctc_pytorch_amd/libctcn.so; rm -f $O/libctcn_keep.so
   grep "^\[probe\]" $O/pytest.log | cut -c1-3000; tail -n 1 $O/pytest.log | cut -c1-300
   ;;
@@ -261,7 +174,7 @@ PY
   ;;
 26)
   # the root cause under test: the SLOW instantiation (item waves delayed at every step) on the single-buffer build (must FAIL) and on the shipped
-  # double-buffered one (must pass); then the after-suite statistics of session 23 for both
+  # double-buffered one (must pass)
   cp ctc_pytorch_amd/libctcn.so $O/libctcn_keep.so
   for lib in single keep; do
     [ $lib = single ] && cp tools/libctcn_single.so ctc_pytorch_amd/libctcn.so || cp $O/libctcn_keep.so ctc_pytorch_amd/libctcn.so
@@ -269,13 +182,6 @@ PY
     echo "lib $lib, test_rnn_fwd_tagged_with_slow_item_waves: $(tail -n 1 $O/pytest_slow_$lib.log | cut -c1-120)" | tee -a $O/summary.log
     grep "^E .*differs" $O/pytest_slow_$lib.log | cut -c1-200 | head -n 6 | tee -a $O/summary.log
   done
-  i=0
-  for lib in keep single keep single; do for sel in "batch_chunks_equal"; do
-    i=$((i+1))
-    [ $lib = single ] && cp tools/libctcn_single.so ctc_pytorch_amd/libctcn.so || cp $O/libctcn_keep.so ctc_pytorch_amd/libctcn.so
-    CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_$i.json CTCN_AFTER_SUITE_N=40 CTCN_AFTER_SUITE_PHASES=order1 timeout 600 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -s -k "$sel" > $O/pytest_$i.log 2>&1
-    echo "$i lib $lib [$sel]: $(grep -o '"summary": "[^"]*"' $O/pytest_$i.log)  $(tail -n 1 $O/pytest_$i.log | cut -c1-80)" | tee -a $O/summary.log
-  done; done
   cp $O/libctcn_keep.so ctc_pytorch_amd/libctcn.so; rm -f $O/libctcn_keep.so
   ;;
 27)
@@ -329,15 +235,6 @@ import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("tag_poll_delay %s: %.3f ms (median %.3f)  fwd %.3f bwd %.3f us/step" % (sys.argv[2], d["ms_per_step"], d["ms_per_step_median"], d["recurrence"]["fwd_us_per_timestep"], d["recurrence"]["bwd_us_per_timestep"]))
 PY
-  done
-  ;;
-36)
-  # after the fix: the statistics of session 20 (traced cfg4 runs in the process of the subsets that showed the divergence) at HEAD
-  i=0
-  for sel in "item_gather_equals" "item_gather_edge" "batch_chunks_equal" "xcd_order or batch_chunks_into_flat"; do
-    i=$((i+1))
-    CTCN_AFTER_SUITE=$R/tools/after_suite_ab.py CTCN_AFTER_SUITE_OUT=$O/after_$i.json CTCN_AFTER_SUITE_N=40 CTCN_AFTER_SUITE_PHASES=order1 timeout 900 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -s -k "$sel" > $O/pytest_$i.log 2>&1
-    echo "subset $i [$sel]: $(grep -o '"summary": "[^"]*"' $O/pytest_$i.log)  $(tail -n 1 $O/pytest_$i.log | cut -c1-80)" | tee -a $O/summary.log
   done
   ;;
 37)
