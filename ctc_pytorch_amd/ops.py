@@ -216,13 +216,18 @@ def set_grad_ready_hook(fn):
     _grad_ready["hook"] = fn
 
 
-_side = {"fwd_overlap": os.environ.get("CTCN_FWD_OVERLAP", "1") != "0", "enabled": os.environ.get("CTCN_SIDE_STREAM", "1") != "0", "streams": {}, "pending": {}, "deferred": {}, "live": {}, "events": {}, "min_items": int(os.environ.get("CTCN_SIDE_MIN_ITEMS", str(1 << 21))), "min_items_bwd": int(os.environ.get("CTCN_SIDE_MIN_ITEMS_BWD", os.environ.get("CTCN_SIDE_MIN_ITEMS", str(1 << 18)))),
-         "small_split": os.environ.get("CTCN_SMALL_SPLIT", "1") != "0",
-         "capacity_slack": float(os.environ.get("CTCN_SIDE_CAPACITY_SLACK", "1.0"))}      # > 1: the weight-gradient side stream also where the rule says it cannot keep up (experiments)
+def _env_on(name):
+    return os.environ.get(name, "1") != "0"
 
 
 SIDE_MIN_ITEMS_FWD, SIDE_MIN_ITEMS_BWD = 1 << 21, 1 << 18
 SMALL_SPLIT_MAX_ITEMS = 1 << 23       # T*B*H above which an inline layer's two directions stay on one stream (their GEMMs fill the device one at a time)
+# the settings of the side stream (set_side_stream, set_fwd_overlap; the per-device runtime state is _DeviceSide)
+_side = {"fwd_overlap": _env_on("CTCN_FWD_OVERLAP"), "enabled": _env_on("CTCN_SIDE_STREAM"),
+         "min_items": int(os.environ.get("CTCN_SIDE_MIN_ITEMS", SIDE_MIN_ITEMS_FWD)),
+         "min_items_bwd": int(os.environ.get("CTCN_SIDE_MIN_ITEMS_BWD", os.environ.get("CTCN_SIDE_MIN_ITEMS", SIDE_MIN_ITEMS_BWD))),
+         "small_split": _env_on("CTCN_SMALL_SPLIT"),
+         "capacity_slack": float(os.environ.get("CTCN_SIDE_CAPACITY_SLACK", "1.0"))}      # > 1: the weight-gradient side stream also where the rule says it cannot keep up (experiments)
 
 
 def set_side_stream(flag, min_items=None, min_items_bwd=None):
@@ -247,6 +252,18 @@ def set_fwd_overlap(flag):
     _side["fwd_overlap"] = bool(flag)
 
 
+def _tiles16(n):
+    """16-row batch tiles of a batch / 16-unit slices (one workgroup, one CU each) of a hidden size."""
+    return (n + 15) // 16
+
+
+def _recurrence_xcds(B, dirs, nx):
+    """(groups, idle): the (direction, 16-row batch tile) groups of a persistent recurrence, one XCD each while XCDs last, and the mask of the
+    XCDs it leaves idle (0: none, or a device without XCDs to split)."""
+    groups = dirs * _tiles16(B)
+    return groups, (_idle_xcd_mask(nx, groups) if nx > 1 else 0)
+
+
 def side_stream_plan(cell, T, B, I, H, dirs, nx, cus, slack=1.0):
     """Where can the weight-gradient GEMMs (dW_ih, dW_hh) of a layer run while the recurrence of the layer below occupies its XCDs?  Returns
     the XCD mask for ctcn_rnn_bwd_weights' xcd_allow, 0 = nowhere (inline on the main stream).  Pure arithmetic (round 4; every constant from a
@@ -261,16 +278,16 @@ def side_stream_plan(cell, T, B, I, H, dirs, nx, cus, slack=1.0):
       unfiltered -- the GEMMs share the recurrence's XCDs and L2s -- with the same capacity test on the free CUs' share of the chip:
       B = 64 at H = 256: 14.97 | 16.36, at H = 128: 11.39 | 11.92.  (Unfiltered although XCDs ARE idle -- more CUs, shared L2s -- measured
       worse: cfg2 13.31 | filtered 13.22, the shipped-YAML shape 4.37 | 4.35.)"""
-    groups = dirs * ((B + 15) // 16)
     if nx <= 1:
         return 0
+    groups, idle = _recurrence_xcds(B, dirs, nx)
     per = cus // nx
-    wpx = ((groups + nx - 1) // nx) * ((H + 15) // 16)
+    wpx = ((groups + nx - 1) // nx) * _tiles16(H)
     used = wpx + max(2, wpx // 8)
     if groups < nx:
         if used + 2 > per:
             return 0
-        share, allow = (nx - groups) / float(nx), _idle_xcd_mask(nx, groups)
+        share, allow = (nx - groups) / float(nx), idle
     else:
         if per - used < 8:
             return 0
@@ -283,55 +300,110 @@ def side_stream_fits(cell, T, B, I, H, dirs, nx, cus, slack=1.0):
     return side_stream_plan(cell, T, B, I, H, dirs, nx, cus, slack) != 0
 
 
-def _side_stream(dev):
+def plan_fwd_pipeline(T, B, H, dirs, nx, settings=None):
+    """The forward's decision, pure: the XCD mask (ctcn_rnn_call.xcd_allow) for the pipelined input projection -- only the first pair of time
+    chunks is projected before the recurrence starts, the rest on the side stream, on the XCDs the persistent kernel leaves idle (group g =
+    (direction, 16-row batch tile) runs on XCD g) -- or 0: the whole projection in front of the recurrence, on the main stream."""
+    s = _side if settings is None else settings
+    idle = _recurrence_xcds(B, dirs, nx)[1]
+    return idle if s["enabled"] and s["fwd_overlap"] and dirs == 2 and T * B * H >= s["min_items"] else 0
+
+
+# where the weight-gradient GEMMs of one layer call run (plan_weight_grads)
+WG_INLINE = "inline"                  # dW pointers go into ctcn_rnn_bwd_ex, main stream
+WG_DEFERRED = "deferred side"         # one ctcn_rnn_bwd_weights(xcd_allow = mask) on the side stream, parked until the layer below launches its recurrence
+WG_SPLIT_END = "split, joined at end of backward"     # direction 1 on the side stream, direction 0 on main; joined by the engine callback
+WG_SPLIT_NOW = "split, joined at once"                # the same two calls, the main stream waits straight away
+
+
+def plan_weight_grads(cell, T, B, I, H, dirs, nx, cus, into_flat, chunk, bottom, above_parked, settings=None):
+    """The backward's decision, pure: (mode, xcd_allow) for the weight gradients of one layer call.  into_flat: all of them accumulate into
+    optim.FlatAdam's flat buffer; chunk: the call is one of several batch chunks of a layer (rnn_layer); bottom: no recurrence follows in this
+    backward pass; above_parked: the layer above has deferred work waiting for this layer's recurrence."""
+    s = _side if settings is None else settings
+    items = T * B * H
+    # one of several batch chunks: every chunk accumulates (beta = 1, read-modify-write) into the SAME gradient views, so all of them write on
+    # the main stream, in order -- a chunk whose weight GEMMs were deferred to the side stream would race with a sibling chunk's inline GEMMs
+    # on the same buffers (ADVICE r4; test_rnn_batch_chunks_into_flat_gradients)
+    if chunk or not (into_flat and s["enabled"] and T > 1):
+        return WG_INLINE, 0
+    # very small layers stay off the deferred path (below min_items_bwd = 2^18 (frame, row, unit) items: the test fixtures).  Round 1 measured cfg1
+    # slower with the side stream (2.27 ms inline, 2.8-4.5 with it) and set the threshold at 2^21; with the queue-form GEMMs and the deferred issue
+    # of rounds 2-3 the picture is the opposite (round 4: cfg1 2.02 -> 1.95 ms, the shipped-YAML shape 4.69 -> 4.36): set_side_stream.
+    # Above it: where the GEMMs can run next to the recurrence of the layer below -- idle XCDs, or free CUs on every XCD (side_stream_plan)
+    allow = side_stream_plan(cell, T, B, I, H, dirs, nx, cus, s["capacity_slack"]) if nx > 1 and items >= s["min_items_bwd"] else 0
+    if allow and not bottom:
+        return WG_DEFERRED, allow
+    # bottom recurrent layer: no recurrence follows, so its weight GEMMs get the whole device -- one direction per stream
+    # (eight small dependent launches per direction that do not fill 256 CUs one at a time: 440 -> ~250 us at cfg2)
+    if allow and dirs == 2:
+        return WG_SPLIT_END, 0
+    # small layers (weight GEMMs not deferred): the two directions' weight gradients are independent chains of small launches that do not
+    # fill the device one at a time -- one direction per stream, joined at once (nothing runs next to a recurrence)
+    # * not when the layer ABOVE has parked side work: the join waits for the whole side stream, which would then hold that layer's deferred
+    #   weight GEMMs -- and its early all-reduce -- in front of the main stream; a mixed large / small stack keeps this layer inline;
+    # * not for LARGE layers that stay inline because the capacity rule says the side stream cannot keep up -- cfg4: B = 64, H = 512 --:
+    #   their weight GEMMs are full-device queue kernels of 131 KB LDS per workgroup, two of which never share a CU, so the two streams ran
+    #   them one after the other anyway; round 5: 52.10 | 51.95 ms per cfg4 step with | without the split, and rocprofv3 charged the wait for
+    #   the other stream's GEMM to whatever small kernel came next on this one -- the "650-us split-K reduce" of profiles/r03_cfg4_*
+    if s["small_split"] and dirs == 2 and not above_parked and items < SMALL_SPLIT_MAX_ITEMS:
+        return WG_SPLIT_NOW, 0
+    return WG_INLINE, 0
+
+
+class _DeviceSide(object):
+    """Runtime state of one device's side stream: the stream and the prelaunch event (both created on first use), whether the stream holds
+    work the main stream has not joined (`pending`), the weight-gradient work parked until the next recurrence is launched (`deferred`, a
+    callable) and the number of recurrent layers whose backward is still to come (`live`: the deferral needs to know whether another
+    recurrence will follow in the backward pass)."""
+
+    def __init__(self, dev):
+        self.dev, self.stream, self.event, self.pending, self.deferred, self.live = dev, None, None, False, None, 0
+
+    def side_stream(self):
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.dev)
+        return self.stream
+
+    def prelaunch_event(self):
+        """The event that ctcn_rnn_bwd records right before it launches its recurrence (ctcn_rnn_call.prelaunch_event of ctcn_rnn_bwd_ex)."""
+        if self.event is None:
+            self.event = torch.cuda.Event()
+            self.event.record(torch.cuda.current_stream(self.dev))        # materialises the hipEvent_t behind ev.cuda_event
+        return self.event
+
+    def join(self):
+        """Issue the parked weight-gradient work on the side stream, ordered behind everything the main stream holds so far, and make the
+        main stream wait for the side stream."""
+        fn, self.deferred = self.deferred, None
+        if fn is not None:
+            fn()
+        if self.pending:
+            self.pending = False
+            torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+
+    def join_at_end(self):
+        """End-of-backward callback: join, and forget recurrent layers whose backward never came (a forward pass run with
+        gradients enabled but never differentiated would otherwise leave the count of pending recurrences too high)."""
+        self.join()
+        self.live = 0
+
+
+_devices = {}
+
+
+def _device_side(dev):
     key = (dev.type, dev.index)
-    st = _side["streams"].get(key)
-    if st is None:
-        st = torch.cuda.Stream(device=dev)
-        _side["streams"][key] = st
-    return st
-
-
-def _prelaunch_event(dev):
-    """Per-device event that ctcn_rnn_bwd records right before it launches its recurrence (ctcn_rnn_call.prelaunch_event of ctcn_rnn_bwd_ex)."""
-    key = (dev.type, dev.index)
-    ev = _side["events"].get(key)
-    if ev is None:
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(dev))        # materialises the hipEvent_t behind ev.cuda_event
-        _side["events"][key] = ev
-    return ev
-
-
-def _flush_deferred(dev_key):
-    """Issue the weight-gradient work parked for this device on the side stream, ordered behind everything the main
-    stream holds so far."""
-    fn = _side["deferred"].pop(dev_key, None)
-    if fn is not None:
-        fn()
-
-
-def _join_now(dev_key):
-    _flush_deferred(dev_key)
-    st = _side["pending"].pop(dev_key, None)
-    if st is not None:
-        torch.cuda.current_stream(st.device).wait_stream(st)
-
-
-def _join_side(dev_key):
-    """End-of-backward callback: join, and forget recurrent layers whose backward never came (a forward pass run with
-    gradients enabled but never differentiated would otherwise leave the count of pending recurrences too high)."""
-    def join():
-        _join_now(dev_key)
-        _side["live"][dev_key] = 0
-    return join
+    d = _devices.get(key)
+    if d is None:
+        d = _devices[key] = _DeviceSide(dev)
+    return d
 
 
 def join_side_stream(device=None):
     """Make the current stream wait for weight gradients still in flight on the side stream (no-op if none)."""
-    keys = list(set(_side["pending"]) | set(_side["deferred"])) if device is None else [(device.type, device.index)]
-    for k in keys:
-        _join_now(k)
+    for d in (list(_devices.values()) if device is None else [_device_side(device)]):
+        d.join()
 
 
 # --------------------------------------------------------------------------------------------------
@@ -447,6 +519,46 @@ def linear(x2d, w):
 # --------------------------------------------------------------------------------------------------
 # recurrent layer
 # --------------------------------------------------------------------------------------------------
+_Saved = collections.namedtuple("_Saved", "x y gates aux w_ih0 w_hh0 w_ih1 w_hh1")     # what _RNNLayer keeps for its backward (aux, w_ih1, w_hh1 may be None)
+
+
+def _new_rnn_call(dev):
+    """ctcn_rnn_call with the fields every call sets (everything a call needs beyond its tensors: the library keeps no state between calls), and
+    the slot that receives the name of the kernel THIS call launched (the process-wide ctcn_rnn_last_kernel is last-writer-wins across threads)."""
+    call, launched = _lib.RnnCall(), ctypes.c_char_p(None)
+    call.status = _lib.status_word(dev).data_ptr()
+    call.launched = ctypes.pointer(launched)
+    return call, launched
+
+
+def _note_launch(launched, step_kernel, cell, T, B, H, dirs):
+    """Count the recurrence kernel a layer call launched, and learn the shapes that need batch chunks: a call that fell back to the per-timestep
+    kernel `step_kernel` although rnn_persistent is on (rnn_layer chunks this shape's batch from the next call on)."""
+    _count_kernel(launched)
+    if T > 1 and B > 16 and (launched or b"") == step_kernel and get_option("rnn_persistent"):
+        _fallback_shapes.add((cell, H, dirs, B))
+
+
+def _note_rnn_fwd(I, s, y_drop, w):
+    """Development (tools/squat_stress.py trace): where a forward call's buffers live, what it read and wrote."""
+    adr = lambda t: t.data_ptr() if t is not None else 0
+    _debug_note[0]("rnn_fwd", dict(I=int(I), x=adr(s.x), gates=adr(s.gates), aux=adr(s.aux), y=adr(s.y), y_drop=adr(y_drop), ws=adr(w), w_ih=adr(s.w_ih0), w_hh=adr(s.w_hh0)),
+                   dict(x=s.x, y=s.y, gates=s.gates, aux=s.aux, y_drop=y_drop, w_ih=(s.w_ih0, s.w_ih1)))
+
+
+def _weight_grads(cell, dims, s, dws, prec, xcd_allow=0, side=None):
+    """Enqueue ctcn_rnn_bwd_weights on the current stream for the gradients in `dws` (dW_ih0, dW_hh0, dW_ih1, dW_hh1; None: not in this call),
+    accumulating (beta = 1).  side: the current stream is this side stream -- its own workspace, and the caching allocator must not recycle
+    the saved tensors under it."""
+    w, wp, wn = _ws(s.x, tag="main" if side is None else "side")
+    _lib.check(_lib.lib().ctcn_rnn_bwd_weights(cell, *dims, _ptr(s.x), _ptr(s.y), _ptr(s.gates), _ptr(s.aux), *[_ptr(d) for d in dws],
+                                               1.0, prec, xcd_allow, wp, wn, _lib.stream_ptr()), "rnn_bwd_weights")
+    if side is not None:
+        for t in (s.x, s.y, s.gates, s.aux):
+            if t is not None:
+                t.record_stream(side)
+
+
 class _RNNLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w_ih0, w_hh0, w_ih1, w_hh1, cell, training, drop_p=0.0):
@@ -462,20 +574,16 @@ class _RNNLayer(torch.autograd.Function):
         y = torch.empty((T, B, dirs * H), dtype=torch.float32, device=dev)
         gates = torch.empty((T, B, dirs, G * H), dtype=torch.float32, device=dev)
         aux = torch.empty((T, B, dirs, H), dtype=torch.float32, device=dev) if cell != 2 else None
+        s = _Saved(x, y, gates, aux, *ws)
         w, wp, wn = _ws(x)
         L = _lib.lib()
-        # pipelined input projection: only the first pair of time chunks is projected before the recurrence starts, the rest on the
-        # side stream, on the XCDs the persistent kernel leaves idle (group g = (direction, 16-row batch tile) runs on XCD g)
-        nx, groups = L.ctcn_device_xcds(), dirs * ((B + 15) // 16)
-        allow = _idle_xcd_mask(nx, groups) if nx > 1 else 0
-        piped = _side["enabled"] and _side["fwd_overlap"] and allow != 0 and dirs == 2 and T * B * H >= _side["min_items"]
-        call = _lib.RnnCall()                      # everything the call needs beyond its tensors (the library keeps no state between calls)
-        call.status = _lib.status_word(dev).data_ptr()
+        side = _device_side(dev)
+        call, launched = _new_rnn_call(dev)
+        piped = plan_fwd_pipeline(T, B, H, dirs, L.ctcn_device_xcds())
         if piped:
-            st = _side_stream(dev)
-            ev = _prelaunch_event(dev)
+            st = side.side_stream()
             w2, wp2, wn2 = _ws(x, tag="side")
-            call.side_stream, call.side_event, call.side_ws, call.side_ws_bytes, call.xcd_allow = st.cuda_stream, ev.cuda_event, w2.data_ptr(), wn2, allow
+            call.side_stream, call.side_event, call.side_ws, call.side_ws_bytes, call.xcd_allow = st.cuda_stream, side.prelaunch_event().cuda_event, w2.data_ptr(), wn2, piped
         # the layer's dropout (BatchRNN: rnn -> nn.Dropout) in the same call: the recurrence stores the dropped output itself where its
         # tagged-gather kernel applies; the random stream advances exactly as for a separate dropout of y
         ctx.drop = None
@@ -485,17 +593,11 @@ class _RNNLayer(torch.autograd.Function):
             seed, off = _next_dropout_stream(y.numel())
             ctx.drop = (float(drop_p), seed, off)
             call.y_drop, call.drop_p, call.drop_seed, call.drop_offset = y_drop.data_ptr(), float(drop_p), seed, off
-        launched = ctypes.c_char_p(None)            # the kernel THIS call launched (per call: the process-wide ctcn_rnn_last_kernel is last-writer-wins across threads)
-        call.launched = ctypes.pointer(launched)
         _lib.check(L.ctcn_rnn_fwd_ex(cell, T, B, I, H, dirs, _ptr(x), _ptr(ws[0]), _ptr(ws[1]), _ptr(ws[2]), _ptr(ws[3]),
                                      _ptr(y), _ptr(gates), _ptr(aux), get_precision(), wp, wn, _lib.stream_ptr(), ctypes.byref(call)), "rnn_fwd_ex")
-        _count_kernel(launched.value)
-        if T > 1 and B > 16 and (launched.value or b"") == b"rnn_fwd_step" and get_option("rnn_persistent"):
-            _fallback_shapes.add((cell, H, dirs, B))       # (rnn_layer chunks this shape's batch from the next call on)
-        if _debug_note[0] is not None:              # development (tools/squat_stress.py trace): where this call's buffers live, what it read and wrote
-            _debug_note[0]("rnn_fwd", dict(I=int(I), x=x.data_ptr(), gates=gates.data_ptr(), aux=aux.data_ptr() if aux is not None else 0, y=y.data_ptr(),
-                                           y_drop=y_drop.data_ptr() if y_drop is not None else 0, ws=w.data_ptr(), w_ih=ws[0].data_ptr(), w_hh=ws[1].data_ptr()),
-                           dict(x=x, y=y, gates=gates, aux=aux, y_drop=y_drop, w_ih=(ws[0], ws[2])))
+        _note_launch(launched.value, b"rnn_fwd_step", cell, T, B, H, dirs)
+        if _debug_note[0] is not None:
+            _note_rnn_fwd(I, s, y_drop, w)
         if piped:
             # by the time the recurrence ends the side stream's GEMMs have long finished (the kernel waited for their counter); the join
             # only tells the allocator and the following kernels so
@@ -503,17 +605,13 @@ class _RNNLayer(torch.autograd.Function):
             for t in (x, gates, ws[0], ws[2]):
                 if t is not None:
                     t.record_stream(st)
-        ctx.cell, ctx.dims, ctx.has_aux = cell, (T, B, I, H, dirs), aux is not None
+        ctx.cell, ctx.dims = cell, (T, B, I, H, dirs)
         ctx.early_ok = not _chunking[0]        # a batch chunk's weight gradients are partial sums: no early all-reduce of the layer's slice (parallel._slice_ready)
         ctx.consumed = False
-        # recurrent layers of this device whose backward is still to come (the deferral of the side work needs to know
-        # whether another recurrence will follow in the backward pass)
-        ctx.counted = any(ctx.needs_input_grad)
+        ctx.counted = any(ctx.needs_input_grad)     # a recurrent layer of this device whose backward is still to come (_DeviceSide.live)
         if ctx.counted:
-            key = (dev.type, dev.index)
-            _side["live"][key] = _side["live"].get(key, 0) + 1
-        saved = [x, y, gates] + ([aux] if aux is not None else []) + [t for t in ws if t is not None]
-        ctx.save_for_backward(*saved)
+            side.live += 1
+        ctx.save_for_backward(*s)
         return y if y_drop is None else y_drop
 
     @staticmethod
@@ -521,128 +619,63 @@ class _RNNLayer(torch.autograd.Function):
         if ctx.consumed:
             raise RuntimeError("ctc_pytorch_amd RNN layer: backward ran twice (the gate reserve is overwritten in place)")
         ctx.consumed = True
-        T, B, I, H, dirs = ctx.dims
+        dims = T, B, I, H, dirs = ctx.dims
         cell = ctx.cell
-        saved = list(ctx.saved_tensors)
-        x, y, gates = saved[:3]
-        k = 3
-        aux = None
-        if ctx.has_aux:
-            aux = saved[3]
-            k = 4
-        wts = saved[k:]
-        w_ih0, w_hh0 = wts[0], wts[1]
-        w_ih1, w_hh1 = (wts[2], wts[3]) if dirs == 2 else (None, None)
+        s = _Saved(*ctx.saved_tensors)
+        wts = (s.w_ih0, s.w_hh0, s.w_ih1, s.w_hh1)
         gy = _f32c(gy)
-        dev = x.device
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        gv = ctx.gviews
-        into_flat = gv[0] is not None and gv[1] is not None and (dirs == 1 or (gv[2] is not None and gv[3] is not None))
-        if into_flat:
-            d_ih0, d_hh0, d_ih1, d_hh1 = gv[0], gv[1], (gv[2] if dirs == 2 else None), (gv[3] if dirs == 2 else None)
-        else:
-            d_ih0, d_hh0 = torch.empty_like(w_ih0), torch.empty_like(w_hh0)
-            d_ih1 = torch.empty_like(w_ih1) if dirs == 2 else None
-            d_hh1 = torch.empty_like(w_hh1) if dirs == 2 else None
-        nb = _lib.lib().ctcn_rnn_scratch_bytes(cell, B, H, dirs)
-        scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
-        w, wp, wn = _ws(x)
+        dev = s.x.device
+        dx = torch.empty_like(s.x) if ctx.needs_input_grad[0] else None
+        # the weight gradients: accumulated (beta = 1) into optim.FlatAdam's views where every matrix of the layer has one, else fresh tensors
+        into_flat = all(g is not None for g, w in zip(ctx.gviews, wts) if w is not None)
+        dws = [None if w is None else (g if into_flat else torch.empty_like(w)) for g, w in zip(ctx.gviews, wts)]
         L = _lib.lib()
-        # XCDs a persistent recurrence of this shape leaves idle (group g = (direction, 16-row batch tile) runs on XCD g)
-        nx, groups = L.ctcn_device_xcds(), dirs * ((B + 15) // 16)
-        allow = _idle_xcd_mask(nx, groups) if nx > 1 else 0
-        # very small layers stay inline (below min_items_bwd = 2^18 (frame, row, unit) items: the test fixtures).  Round 1 measured cfg1 slower
-        # with the side stream (2.27 ms inline, 2.8-4.5 with it) and set the threshold at 2^21; with the queue-form GEMMs and the deferred issue
-        # of rounds 2-3 the picture is the opposite (round 4: cfg1 2.02 -> 1.95 ms, the shipped-YAML shape 4.69 -> 4.36): set_side_stream
-        side = into_flat and _side["enabled"] and nx > 1 and T > 1 and T * B * H >= _side["min_items_bwd"]
-        # one of several batch chunks of a layer (rnn_layer): every chunk accumulates (beta = 1, read-modify-write) into the SAME gradient
-        # views, so all of them write on the main stream, in order -- a chunk whose weight GEMMs were deferred to the side stream would race
-        # with a sibling chunk's inline GEMMs on the same buffers (test_rnn_batch_chunks_into_flat_gradients)
-        chunk = not ctx.early_ok
-        if chunk:
-            side = False
-        if side:                    # where the weight GEMMs can run next to the recurrence of the layer below: idle XCDs, or free CUs on every XCD
-            allow = side_stream_plan(cell, T, B, I, H, dirs, nx, L.ctcn_device_cus(), _side["capacity_slack"])
-            side = allow != 0
-        null = ctypes.c_void_p(None)
-        key = (dev.type, dev.index)
+        scratch = torch.empty(L.ctcn_rnn_scratch_bytes(cell, B, H, dirs), dtype=torch.uint8, device=dev)
+        w, wp, wn = _ws(s.x)
+        side = _device_side(dev)
         if ctx.counted:
-            _side["live"][key] = max(0, _side["live"].get(key, 0) - 1)
-        split_dirs = False
-        if dx is None or _side["live"].get(key, 0) == 0:
-            # bottom recurrent layer: no recurrence follows, so its weight GEMMs get the whole device -- one direction per stream
-            # (eight small dependent launches per direction that do not fill 256 CUs one at a time: 440 -> ~250 us at cfg2)
-            split_dirs = side and dirs == 2 and not chunk
-            side = False
-        # small layers (below min_items: weight GEMMs inline): the two directions' weight gradients are independent chains of small launches
-        # that do not fill the device one at a time -- one direction per stream, joined at once (nothing runs next to a recurrence)
-        # (not when the layer ABOVE has parked side work: the join below waits for the whole side stream, which would then hold that layer's
-        # deferred weight GEMMs -- and its early all-reduce -- in front of the main stream; a mixed large / small stack keeps this layer inline)
-        # (and not for LARGE layers that stay inline because the capacity rule says the side stream cannot keep up -- cfg4: B = 64, H = 512 --:
-        # their weight GEMMs are full-device queue kernels of 131 KB LDS per workgroup, two of which never share a CU, so the two streams ran
-        # them one after the other anyway; round 5: 52.10 | 51.95 ms per cfg4 step with | without the split, and rocprofv3 charged the wait for
-        # the other stream's GEMM to whatever small kernel came next on this one -- the "650-us split-K reduce" of profiles/r03_cfg4_*)
-        small_split = (not side and not split_dirs and not chunk and into_flat and _side["enabled"] and _side["small_split"] and dirs == 2 and T > 1
-                       and key not in _side["deferred"] and T * B * H < SMALL_SPLIT_MAX_ITEMS)
-        if small_split:
-            split_dirs = True
+            side.live = max(0, side.live - 1)
+        mode, allow = plan_weight_grads(cell, T, B, I, H, dirs, L.ctcn_device_xcds(), L.ctcn_device_cus(), into_flat=into_flat, chunk=not ctx.early_ok,
+                                        bottom=dx is None or side.live == 0, above_parked=side.deferred is not None)
         # the layer above: its weight GEMMs start together with this layer's recurrence -- the library records `ev` right
         # before that launch, behind its own small preparatory kernels, and the side stream waits for it
-        above, ev = _side["deferred"].pop(key, None), None
-        call = _lib.RnnCall()
-        call.status = _lib.status_word(dev).data_ptr()
+        above, side.deferred, ev = side.deferred, None, None
+        call, launched = _new_rnn_call(dev)
         if above is not None:
-            ev = _prelaunch_event(dev)
+            ev = side.prelaunch_event()
             call.prelaunch_event = ev.cuda_event
         gd = None
         if ctx.drop is not None:    # gy is the gradient of the dropped output: the same mask, applied by the recurrence as it consumes gy (or by
             p_, seed_, off_ = ctx.drop                      # a dropout pass into gd where that kernel does not apply)
             gd = torch.empty_like(gy)
             call.dy_tmp, call.drop_p, call.drop_seed, call.drop_offset = gd.data_ptr(), p_, seed_, off_
-        launched = ctypes.c_char_p(None)
-        call.launched = ctypes.pointer(launched)
+        prec = get_precision()
         try:
-            _lib.check(L.ctcn_rnn_bwd_ex(cell, T, B, I, H, dirs, _ptr(x), _ptr(w_ih0), _ptr(w_hh0), _ptr(w_ih1), _ptr(w_hh1),
-                                         _ptr(y), _ptr(gates), _ptr(aux), _ptr(gy), _ptr(dx),
-                                         null if (side or split_dirs) else _ptr(d_ih0), null if (side or split_dirs) else _ptr(d_hh0),
-                                         null if (side or split_dirs) else _ptr(d_ih1), null if (side or split_dirs) else _ptr(d_hh1),
-                                         1.0 if into_flat else 0.0, get_precision(), _ptr(scratch), wp, wn, _lib.stream_ptr(), ctypes.byref(call)), "rnn_bwd_ex")
+            _lib.check(L.ctcn_rnn_bwd_ex(cell, T, B, I, H, dirs, _ptr(s.x), *[_ptr(t) for t in wts], _ptr(s.y), _ptr(s.gates), _ptr(s.aux), _ptr(gy), _ptr(dx),
+                                         *[_ptr(d) if mode == WG_INLINE else None for d in dws],
+                                         1.0 if into_flat else 0.0, prec, _ptr(scratch), wp, wn, _lib.stream_ptr(), ctypes.byref(call)), "rnn_bwd_ex")
         except Exception:
-            if above is not None:                       # keep the parked work for the join
-                _side["deferred"][key] = above
+            side.deferred = above                       # keep the parked work for the join
             raise
-        _count_kernel(launched.value)
-        if T > 1 and B > 16 and (launched.value or b"") == b"rnn_bwd_step" and get_option("rnn_persistent"):
-            _fallback_shapes.add((cell, H, dirs, B))           # (rnn_layer chunks this shape's batch from the next call on)
+        _note_launch(launched.value, b"rnn_bwd_step", cell, T, B, H, dirs)
         if above is not None:
             above(ev)
-        if split_dirs:
-            st = _side_stream(dev)
-            prec = get_precision()
-            # (round 5, measured and not kept: the four products dealt by MATRIX instead of by direction -- the main stream the heavier pair, both
-            # dW_hh, so that the side stream is done first and the optimiser's wait for it falls through instead of costing the ~55 us of wake-up
-            # the step timeline shows in front of adam_kernel: cfg2 13.08 | 13.10 ms, cfg1 1.96 | 1.95, cfg3 7.68 | 7.69, shipped YAML 4.23 | 4.23)
-            # (round 5, measured and not kept: each direction's GEMMs restricted to one half of the XCDs, so that the two streams' full-device
-            # queue kernels run side by side instead of one after the other -- cfg2 13.221 | 13.220 ms, cfg3 7.898 | 7.935: the same work either way)
-            st.wait_stream(torch.cuda.current_stream(dev))          # (behind the layer above's weight GEMMs already queued there)
+        if mode in (WG_SPLIT_END, WG_SPLIT_NOW):
+            # one direction per stream (the variants measured and not kept -- the products dealt by matrix, each direction on half of the XCDs --
+            # are in DESIGN_HISTORY.md, "Weight-gradient side stream")
+            st, main = side.side_stream(), torch.cuda.current_stream(dev)
+            st.wait_stream(main)                        # (behind the layer above's weight GEMMs already queued there)
             with torch.cuda.stream(st):
-                w2, wp2, wn2 = _ws(x, tag="side")
-                _lib.check(L.ctcn_rnn_bwd_weights(cell, T, B, I, H, dirs, _ptr(x), _ptr(y), _ptr(gates), _ptr(aux), null, null,
-                                                  _ptr(d_ih1), _ptr(d_hh1), 1.0, prec, 0, wp2, wn2, st.cuda_stream), "rnn_bwd_weights")
-            _lib.check(L.ctcn_rnn_bwd_weights(cell, T, B, I, H, dirs, _ptr(x), _ptr(y), _ptr(gates), _ptr(aux), _ptr(d_ih0), _ptr(d_hh0),
-                                              null, null, 1.0, prec, 0, wp, wn, _lib.stream_ptr()), "rnn_bwd_weights")
+                _weight_grads(cell, dims, s, [None, None] + dws[2:], prec, side=st)
+            _weight_grads(cell, dims, s, dws[:2] + [None, None], prec)
             # (no gradient-ready hook: nothing is left to hide a collective behind; these slices go with the step-end all-reduce)
-            for t in (x, y, gates, aux):
-                if t is not None:
-                    t.record_stream(st)
-            if small_split:
-                torch.cuda.current_stream(dev).wait_stream(st)
+            if mode == WG_SPLIT_NOW:
+                main.wait_stream(st)
             else:
-                _side["pending"][key] = st
-                torch.autograd.Variable._execution_engine.queue_callback(_join_side(key))
-        if side:
-            st = _side_stream(dev)
-            prec = get_precision()
+                side.pending = True
+                torch.autograd.Variable._execution_engine.queue_callback(side.join_at_end)
+        elif mode == WG_DEFERRED:
+            st = side.side_stream()
 
             def weights_on_side_stream(after=None):
                 if after is None:
@@ -650,30 +683,22 @@ class _RNNLayer(torch.autograd.Function):
                 else:
                     st.wait_event(after)
                 with torch.cuda.stream(st):
-                    w2, wp2, wn2 = _ws(x, tag="side")
-                    _lib.check(L.ctcn_rnn_bwd_weights(cell, T, B, I, H, dirs, _ptr(x), _ptr(y), _ptr(gates), _ptr(aux), _ptr(d_ih0),
-                                                      _ptr(d_hh0), _ptr(d_ih1), _ptr(d_hh1), 1.0, prec, allow, wp2, wn2,
-                                                      st.cuda_stream), "rnn_bwd_weights")
-                    if _grad_ready["hook"] is not None and ctx.early_ok:      # this layer's weight gradients are final once `st` gets here (not so for one of several batch chunks)
-                        _grad_ready["hook"]([t for t in (d_ih0, d_hh0, d_ih1, d_hh1) if t is not None])
-                for t in (x, y, gates, aux):
-                    if t is not None:
-                        t.record_stream(st)         # the caching allocator must not recycle them under the side stream
-                _side["pending"][key] = st
+                    _weight_grads(cell, dims, s, dws, prec, allow, side=st)
+                    if _grad_ready["hook"] is not None:      # this layer's weight gradients are final once `st` gets here (a batch chunk, whose are not, is never deferred)
+                        _grad_ready["hook"]([t for t in dws if t is not None])
+                side.pending = True
 
-            _side["deferred"][key] = weights_on_side_stream        # issued when the recurrence of the layer below is launched
+            side.deferred = weights_on_side_stream      # issued when the recurrence of the layer below is launched
             # one join per layer is harmless and keeps the path safe if an earlier backward pass died before its callback ran
-            torch.autograd.Variable._execution_engine.queue_callback(_join_side(key))
-        if into_flat:
-            return dx, None, None, None, None, None, None, None
-        return dx, d_ih0, d_hh0, d_ih1, d_hh1, None, None, None
+            torch.autograd.Variable._execution_engine.queue_callback(side.join_at_end)
+        return (dx,) + ((None,) * 7 if into_flat else tuple(dws) + (None,) * 3)
 
 
 def persistent_batch_limit(H, dirs, nx, cus):
     """Rows one launch of the persistent recurrences can hold: a (direction, 16-row batch tile) group is ceil(H / 16) workgroups on ONE XCD,
     one workgroup per CU, so an XCD of cus / nx CUs takes floor((cus / nx) / ceil(H / 16)) groups -- bidirectional on 8 x 32 CUs: 64 rows for
     256 < H <= 512, 128 for H <= 256, 256 at H = 128.  0: the shape has no persistent launch at all."""
-    nsl = (H + 15) // 16
+    nsl = _tiles16(H)
     per_xcd = (cus // max(nx, 1)) // nsl if nsl else 0
     return 16 * ((per_xcd * max(nx, 1)) // dirs) if nx > 1 else 0
 

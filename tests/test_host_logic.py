@@ -763,6 +763,113 @@ def test_side_stream_capacity_rule_on_the_measured_shapes():
     assert plan(0, 800, 64, 640, 320) == 0 and plan(1, 1200, 64, 1024, 512) == 0
 
 
+def test_weight_gradient_plan_table():
+    """ops.plan_weight_grads / ops.plan_fwd_pipeline: WHERE a recurrent layer's weight-gradient GEMMs run (and whether its forward projection
+    is pipelined), as a table of (shape, flags) -> (mode, XCD mask) on an 8 x 32-CU device -- the gradient tests on the GPU pass just as well
+    when a layer silently moves from the side stream to inline; this one does not.
+
+    Where the expected values come from: NOT from the functions under test.  Rows marked `t` are copied from a call trace of the commit
+    BEFORE the decision was separated from its execution (its _RNNLayer.backward, 150 lines with the rule braided in), recorded on an MI355X:
+    every ctcn_rnn_fwd_ex / ctcn_rnn_bwd_ex / ctcn_rnn_bwd_weights call with its stream, null dW pointers and xcd_allow, the waits between
+    the two streams and the engine callbacks, over two training steps of cfg1-cfg4 and ref_yaml as bench.py runs them (FlatAdam), cfg2's
+    model at B = 96 / 128 and with torch.optim.Adam, a unidirectional GRU stack, the three shapes of
+    test_weight_gradient_side_stream_equals_inline with min_items = 0 and with the side stream off, a small stack and a mixed large / small
+    stack.  In that trace inline = dW pointers set in ctcn_rnn_bwd_ex; deferred = dW null, then one ctcn_rnn_bwd_weights with all four
+    gradients on the side stream behind the NEXT layer's prelaunch event; split = two calls, direction 1 on the side stream and direction 0
+    on the main stream, followed by main.wait_stream(side) (at once) or by an engine callback (end of backward).  above_parked of a row is
+    what that trace shows for the layer above it (deferred or not).  Rows marked `r` were not reachable on that device or in that run (one
+    XCD; a chunk of a shape that would otherwise be deferred; the settings switches) and are derived by reading the same commit's rule."""
+    from ctc_pytorch_amd import ops
+    assert ops.get_option("xcd_interleave") == 1
+    IN, DEF, END, NOW = ops.WG_INLINE, ops.WG_DEFERRED, ops.WG_SPLIT_END, ops.WG_SPLIT_NOW
+    assert len({IN, DEF, END, NOW}) == 4
+    base = dict(enabled=True, fwd_overlap=True, min_items=1 << 21, min_items_bwd=1 << 18, small_split=True, capacity_slack=1.0)
+    all_sizes, off = dict(base, min_items=0, min_items_bwd=0), dict(base, enabled=False, min_items=0, min_items_bwd=0)
+    LSTM, GRU = 0, 1
+    TOP, MID, BOT, BOT_FREE = (False, False), (False, True), (True, True), (True, False)      # (bottom, above_parked)
+    rows = [
+        # cell, T, B, I, H, dirs, (bottom, above_parked), settings, kwargs -> mode, mask
+        (LSTM, 300, 8, 256, 128, 2, TOP, base, {}, DEF, 0xFA),             # t cfg1
+        (LSTM, 300, 8, 40, 128, 2, BOT, base, {}, END, 0),                 # t
+        (LSTM, 800, 32, 640, 320, 2, TOP, base, {}, DEF, 0xAA),            # t cfg2
+        (LSTM, 800, 32, 640, 320, 2, MID, base, {}, DEF, 0xAA),            # t
+        (LSTM, 800, 32, 40, 320, 2, BOT, base, {}, END, 0),                # t
+        (LSTM, 400, 32, 640, 320, 2, TOP, base, {}, DEF, 0xAA),            # t cfg3 (400 frames behind the CNN)
+        (LSTM, 400, 32, 640, 320, 2, MID, base, {}, DEF, 0xAA),            # t
+        (LSTM, 400, 32, 320, 320, 2, BOT, base, {}, END, 0),               # t
+        (GRU, 1200, 64, 1024, 512, 2, TOP, base, {}, IN, 0),               # t cfg4: no idle XCD, no free CU; too large for the small split
+        (GRU, 1200, 64, 1024, 512, 2, TOP, base, {}, IN, 0),               # t (middle: nothing parked above an inline layer)
+        (GRU, 1200, 64, 40, 512, 2, BOT_FREE, base, {}, IN, 0),            # t
+        (LSTM, 200, 8, 768, 384, 2, TOP, base, {}, DEF, 0xFA),             # t ref_yaml
+        (LSTM, 200, 8, 768, 384, 2, MID, base, {}, DEF, 0xFA),             # t
+        (LSTM, 200, 8, 1952, 384, 2, BOT, base, {}, END, 0),               # t
+        (LSTM, 60, 8, 256, 128, 2, TOP, all_sizes, {}, DEF, 0xFA),         # t test_weight_gradient_side_stream_equals_inline, min_items = 0
+        (LSTM, 60, 8, 256, 128, 2, MID, all_sizes, {}, DEF, 0xFA),         # t
+        (LSTM, 60, 8, 40, 128, 2, BOT, all_sizes, {}, END, 0),             # t
+        (GRU, 25, 40, 384, 192, 2, TOP, all_sizes, {}, DEF, 0xA0),         # t
+        (GRU, 25, 40, 384, 192, 2, MID, all_sizes, {}, DEF, 0xA0),         # t
+        (GRU, 25, 40, 40, 192, 2, BOT, all_sizes, {}, END, 0),             # t
+        (LSTM, 30, 64, 192, 96, 2, TOP, all_sizes, {}, DEF, 0xFF),         # t no idle XCD: the free CUs of every XCD
+        (LSTM, 30, 64, 192, 96, 2, MID, all_sizes, {}, DEF, 0xFF),         # t
+        (LSTM, 30, 64, 40, 96, 2, BOT, all_sizes, {}, END, 0),             # t
+        (LSTM, 60, 8, 256, 128, 2, TOP, off, {}, IN, 0),                   # t the same three with set_side_stream(False, min_items=0)
+        (LSTM, 60, 8, 40, 128, 2, BOT_FREE, off, {}, IN, 0),               # t
+        (GRU, 25, 40, 384, 192, 2, TOP, off, {}, IN, 0),                   # t
+        (LSTM, 30, 64, 192, 96, 2, TOP, off, {}, IN, 0),                   # t
+        (LSTM, 800, 96, 640, 320, 2, TOP, base, {}, IN, 0),                # t cfg2's model at B = 96 (one persistent launch, not chunked)
+        (LSTM, 800, 96, 40, 320, 2, BOT_FREE, base, {}, IN, 0),            # t
+        (LSTM, 800, 128, 640, 320, 2, TOP, base, {}, IN, 0),               # t B = 128, first call (per-timestep kernels)
+        (LSTM, 800, 64, 640, 320, 2, TOP, base, dict(chunk=True), IN, 0),  # t B = 128 from the second call on: two chunks of 64 rows
+        (LSTM, 800, 64, 40, 320, 2, BOT_FREE, base, dict(chunk=True), IN, 0),   # t
+        (LSTM, 800, 32, 640, 320, 2, TOP, base, dict(chunk=True), IN, 0),  # r a chunk is inline whatever its shape
+        (LSTM, 800, 32, 40, 320, 2, BOT, base, dict(chunk=True), IN, 0),   # r
+        (LSTM, 60, 8, 256, 128, 2, TOP, base, dict(chunk=True), IN, 0),    # r (nor split)
+        (GRU, 200, 16, 256, 256, 1, TOP, base, {}, DEF, 0xFE),             # t unidirectional GRU stack
+        (GRU, 200, 16, 256, 256, 1, MID, base, {}, DEF, 0xFE),             # t
+        (GRU, 200, 16, 40, 256, 1, BOT, base, {}, IN, 0),                  # t bottom layer, one direction: nothing to split
+        (LSTM, 800, 32, 640, 320, 2, TOP, base, dict(into_flat=False), IN, 0),      # t torch.optim.Adam: gradients returned, not accumulated
+        (LSTM, 800, 32, 40, 320, 2, BOT_FREE, base, dict(into_flat=False), IN, 0),  # t
+        (LSTM, 40, 4, 40, 32, 2, BOT_FREE, base, {}, NOW, 0),              # t small stack (below min_items_bwd), bottom
+        (LSTM, 40, 4, 64, 32, 2, TOP, base, {}, NOW, 0),                   # t ... and top
+        (LSTM, 300, 8, 64, 128, 2, TOP, base, {}, DEF, 0xFA),              # t mixed stack: large top layer parks its work ...
+        (LSTM, 300, 8, 64, 32, 2, MID, base, {}, IN, 0),                   # t ... so the small layer under it stays inline ...
+        (LSTM, 300, 8, 40, 32, 2, BOT_FREE, base, {}, NOW, 0),             # t ... and the bottom one, with nothing parked above, is split
+        (LSTM, 300, 8, 64, 32, 2, TOP, dict(base, small_split=False), {}, IN, 0),   # r CTCN_SMALL_SPLIT=0
+        (LSTM, 800, 32, 640, 320, 2, TOP, dict(base, enabled=False), {}, IN, 0),    # r set_side_stream(False)
+        (LSTM, 800, 32, 40, 320, 2, BOT_FREE, dict(base, enabled=False), {}, IN, 0),  # r
+        (LSTM, 1, 32, 640, 320, 2, TOP, all_sizes, {}, IN, 0),             # r T = 1
+        (LSTM, 800, 48, 640, 320, 2, TOP, base, {}, IN, 0),                # r two idle XCDs cannot keep up, 12.3 M items: inline
+        (LSTM, 800, 48, 640, 320, 2, TOP, dict(base, capacity_slack=4.0), {}, DEF, 0xA0),   # r CTCN_SIDE_CAPACITY_SLACK
+    ]
+    for cell, T, B, I, H, dirs, (bottom, above), st, kw, mode, mask in rows:
+        flags = dict(dict(into_flat=True, chunk=False), bottom=bottom, above_parked=above, **kw)
+        assert ops.plan_weight_grads(cell, T, B, I, H, dirs, 8, 256, settings=st, **flags) == (mode, mask), (cell, T, B, I, H, dirs, flags)
+    # r: a device without XCDs to split has no side stream for the GEMMs, but the two directions of a layer that is not too large still
+    # take one stream each (the small split never asked for XCDs)
+    one = lambda *a, **k: ops.plan_weight_grads(*a, 1, 256, into_flat=True, chunk=False, settings=base, **k)
+    assert one(LSTM, 800, 32, 640, 320, 2, bottom=False, above_parked=False) == (NOW, 0)
+    assert one(GRU, 1200, 64, 1024, 512, 2, bottom=False, above_parked=False) == (IN, 0)
+    assert one(GRU, 200, 16, 256, 256, 1, bottom=False, above_parked=False) == (IN, 0)
+    # the module's own settings are what a call without `settings` reads (set_side_stream moves them)
+    old = (ops._side["enabled"], ops._side["min_items"], ops._side["min_items_bwd"])
+    try:
+        ops.set_side_stream(True, ops.SIDE_MIN_ITEMS_FWD, ops.SIDE_MIN_ITEMS_BWD)
+        assert ops.plan_weight_grads(LSTM, 800, 32, 640, 320, 2, 8, 256, into_flat=True, chunk=False, bottom=False, above_parked=True)[0] == DEF
+        ops.set_side_stream(False)
+        assert ops.plan_weight_grads(LSTM, 800, 32, 640, 320, 2, 8, 256, into_flat=True, chunk=False, bottom=False, above_parked=True) == (IN, 0)
+        assert ops.plan_fwd_pipeline(800, 32, 320, 2, 8) == 0
+    finally:
+        ops.set_side_stream(*old)
+    # the forward's projection pipeline (t: ctcn_rnn_call.side_stream / xcd_allow of the traced ctcn_rnn_fwd_ex calls)
+    fwd = lambda T, B, H, dirs, st=base, nx=8: ops.plan_fwd_pipeline(T, B, H, dirs, nx, settings=st)
+    assert fwd(800, 32, 320, 2) == 0xAA and fwd(400, 32, 320, 2) == 0xAA                      # cfg2, cfg3
+    assert fwd(300, 8, 128, 2) == 0 and fwd(200, 8, 384, 2) == 0                              # cfg1, ref_yaml: below min_items
+    assert fwd(1200, 64, 512, 2) == 0 and fwd(800, 96, 320, 2) == 0 and fwd(800, 64, 320, 2) == 0    # no idle XCD
+    assert fwd(200, 16, 256, 1) == 0                                                          # one direction
+    assert fwd(60, 8, 128, 2, all_sizes) == 0xFA and fwd(25, 40, 192, 2, all_sizes) == 0xA0 and fwd(30, 64, 96, 2, all_sizes) == 0
+    assert fwd(60, 8, 128, 2, off) == 0 and fwd(800, 32, 320, 2, dict(base, fwd_overlap=False)) == 0 and fwd(800, 32, 320, 2, nx=1) == 0   # (last two: r)
+
+
 def test_projection_pipeline_plan_on_the_measured_shapes():
     """ctcn_diag_pipeline_chunks = the pure plan behind ctcn_rnn_fwd_ex's projection pipeline (rnn.hip, round 4): chunk counts at the shapes
     whose A/B runs set its rules (8 XCDs x 32 CUs; `allow` = the XCDs a bidirectional recurrence of B rows leaves idle)."""
