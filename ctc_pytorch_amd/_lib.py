@@ -59,6 +59,11 @@ _SIGS = {
     "ctcn_bn_fwd_train_dropout": (I, [P, P, P, P, P, P, P, P, I, I, I, F, F, I, P, Z, P, P, F, U, U]),
     "ctcn_bn_bwd_dropout": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, F, P, Z, P, F, U, U]),
     "ctcn_dropout": (I, [P, P, Z, F, U, U, P]),
+    "ctcn_bn_masked_ws_bytes": (Z, [I, I, I]),
+    "ctcn_mask_frames": (I, [P, P, P, I, I, I, I, I, P]),
+    "ctcn_bn_fwd_train_masked": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, F, F, I, P, Z, P, P]),
+    "ctcn_bn_fwd_eval_masked": (I, [P, P, P, P, P, P, P, I, I, I, I, I, F, I, P]),
+    "ctcn_bn_bwd_masked": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, Z, P]),
     "ctcn_conv2d_ws_bytes": (Z, [I] * 11),
     "ctcn_conv2d_fwd": (I, [P, P, P, P] + [I] * 11 + [P]),
     "ctcn_conv2d_bwd": (I, [P, P, P, P, P, P] + [I] * 11 + [F, P, Z, P]),

@@ -669,3 +669,383 @@ extern "C" int ctcn_bn_bwd(const float *x, const float *y, const float *dy, cons
   CTCN_LAUNCH_CHECK();
   return CTCN_OK;
 }
+
+// ---- length-aware BatchNorm and frame mask ---------------------------------------------------------------------------
+// Every utterance b of a padded batch has lens[b] real frames; the rest of its time axis is padding.  Validity is a function of the frame:
+//   inner == 1 (rows = T * batch, time-major):  row r is valid iff r / batch < lens[r % batch]
+//   inner  > 1 (NCHW, outer = batch, inner = T' * frame):  element i of a plane (o, c) is valid iff i / frame < lens[o]
+// The statistics, dgamma / dbeta and the two dx reduction terms run over the valid elements only, with the count n = sum(lens) * frame taken
+// on the device (no host sync); y and dx are 0 at invalid elements BY SELECT, and no pass reads x / y / dy there -- a NaN in the padding
+// cannot reach anything, and a padded row costs no read.  The chunking, the float64 partials, their fixed-order sums and the per-element
+// expressions (bn_value, bn_dx_value) are those of the kernels above: with full lengths the sums are taken over the same values in the same order.
+namespace {
+
+struct FrameGeom { const int *lens; int batch, frame, tmax; };     // tmax: frames on the time axis (lens are clamped to [0, tmax])
+
+__device__ __forceinline__ int geom_len(const FrameGeom &g, int b) { return min(max(g.lens[b], 0), g.tmax); }
+__device__ __forceinline__ bool row_valid(const FrameGeom &g, int r) { return r / g.batch < g.lens[r % g.batch]; }
+// n = sum(lens) * frame, by one whole wave (every lane receives it; integers below 2^53: exact in any order)
+__device__ __forceinline__ double geom_count(const FrameGeom &g, int lane) {
+  double n = 0.0;
+  for (int b = lane; b < g.batch; b += 64) n += (double)geom_len(g, b);
+  return wave_sum_d(n) * (double)g.frame;
+}
+
+// colreduce_rows_kernel over the valid rows
+template <class F>
+__global__ __launch_bounds__(256) void mreduce_rows_kernel(F f, FrameGeom g, int rows, int C, int rows_per_chunk, double *__restrict__ part) {
+  __shared__ double sa[4][64], sb[4][64];
+  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + cx;
+  const int r0 = blockIdx.y * rows_per_chunk, r1 = min(rows, r0 + rows_per_chunk);
+  double a = 0.0, b = 0.0;
+  if (c < C) {
+    int r = r0 + ry;
+    for (; r + 28 < r1; r += 32) {
+      Pair p[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) p[u] = row_valid(g, r + 4 * u) ? f((size_t)(r + 4 * u) * C + c, c) : Pair{0.0, 0.0};
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { a += p[u].a; b += p[u].b; }
+    }
+    for (; r < r1; r += 4) {
+      if (!row_valid(g, r)) continue;
+      const Pair p = f((size_t)r * C + c, c);
+      a += p.a; b += p.b;
+    }
+  }
+  sa[ry][cx] = a; sb[ry][cx] = b;
+  __syncthreads();
+  if (ry == 0 && c < C) {
+    a = sa[0][cx] + sa[1][cx] + sa[2][cx] + sa[3][cx];
+    b = sb[0][cx] + sb[1][cx] + sb[2][cx] + sb[3][cx];
+    part[((size_t)blockIdx.y * C + c) * 2 + 0] = a;
+    part[((size_t)blockIdx.y * C + c) * 2 + 1] = b;
+  }
+}
+
+// colreduce_rows4_kernel over the valid rows (C % 4 == 0, 16-B aligned operands): an invalid row is neither requested nor added
+template <class F>
+__global__ __launch_bounds__(256) void mreduce_rows4_kernel(F f, FrameGeom g, int rows, int C, int rows_per_chunk, double *__restrict__ part) {
+  __shared__ double sa[16][65], sb[16][65];
+  const int l16 = threadIdx.x & 15, rp = threadIdx.x >> 4;
+  const int c0 = blockIdx.x * 64 + 4 * l16;
+  const int r0 = blockIdx.y * rows_per_chunk, r1 = min(rows, r0 + rows_per_chunk);
+  double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+  if (c0 < C && r0 < r1) {
+    const typename F::ColK k = f.colk(c0);
+    constexpr int U = F::ROWS_IN_FLIGHT;
+    for (int r = r0 + rp; r < r1; r += 16 * U) {
+      typename F::Quad q[U] = {};
+      bool v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int rr = r + 16 * u;
+        v[u] = rr < r1 && row_valid(g, rr);
+        if (v[u]) q[u] = f.load4((size_t)rr * C + c0);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (v[u]) f.cols4(q[u], k, a, b);
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { sa[rp][4 * l16 + e] = a[e]; sb[rp][4 * l16 + e] = b[e]; }
+  __syncthreads();
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (threadIdx.x < 64 && c < C) {
+    double ta = sa[0][threadIdx.x], tb = sb[0][threadIdx.x];
+#pragma unroll
+    for (int p = 1; p < 16; ++p) { ta += sa[p][threadIdx.x]; tb += sb[p][threadIdx.x]; }
+    part[((size_t)blockIdx.y * C + c) * 2 + 0] = ta;
+    part[((size_t)blockIdx.y * C + c) * 2 + 1] = tb;
+  }
+}
+
+// colreduce_nchw_kernel over the valid prefix [0, lens[o] * frame) of every plane; the (at most three) elements behind the last whole
+// quad of the prefix are added one by one after the 16-B pieces
+template <class F>
+__global__ __launch_bounds__(256) void mreduce_nchw_kernel(F f, FrameGeom g, int outer, int C, int inner, int opc, int ich, int ilen, int vec,
+                                                           double *__restrict__ part) {
+  __shared__ double sa[4], sb[4];
+  const int c = blockIdx.x;
+  const int oc = blockIdx.y / ich, ic = blockIdx.y - oc * ich;
+  const int o0 = oc * opc, o1 = min(outer, o0 + opc);
+  const int i0 = ic * ilen;
+  double a = 0.0, b = 0.0;
+  for (int o = o0; o < o1; ++o) {
+    const size_t base = ((size_t)o * C + c) * inner;
+    const int i1 = min(min(inner, i0 + ilen), geom_len(g, o) * g.frame);
+    if (vec) {
+      const int i1v = i1 & ~3;
+      int i = i0 + threadIdx.x * 4;
+      for (; i + 3 * 1024 < i1v; i += 4096) {
+        typename F::Quad q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = f.load4(base + i + 1024 * u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) f.add4(q[u], c, a, b);
+      }
+      for (; i < i1v; i += 1024) f.add4(f.load4(base + i), c, a, b);
+      if (i1v >= i0 && (int)threadIdx.x < i1 - i1v) {
+        const Pair p = f(base + i1v + threadIdx.x, c);
+        a += p.a; b += p.b;
+      }
+    } else {
+      for (int i = i0 + threadIdx.x; i < i1; i += 256) {
+        const Pair p = f(base + i, c);
+        a += p.a; b += p.b;
+      }
+    }
+  }
+  a = wave_sum_d(a); b = wave_sum_d(b);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) { sa[w] = a; sb[w] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part[((size_t)blockIdx.y * C + c) * 2 + 0] = sa[0] + sa[1] + sa[2] + sa[3];
+    part[((size_t)blockIdx.y * C + c) * 2 + 1] = sb[0] + sb[1] + sb[2] + sb[3];
+  }
+}
+
+// bn_finalize_stats_kernel with the count taken from the lengths
+__global__ void bn_finalize_stats_masked_kernel(const double *__restrict__ part, int nchunks, int C, FrameGeom g, float eps, float momentum,
+                                                float *__restrict__ mean_out, float *__restrict__ rstd_out, float *__restrict__ rm,
+                                                float *__restrict__ rv, long long *__restrict__ batches) {
+  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (batches && blockIdx.x == 0 && threadIdx.x == 0) *batches += 1;
+  if (c >= C) return;
+  const double count = geom_count(g, lane);
+  double s = 0.0, ss = 0.0;
+  for (int k = lane; k < nchunks; k += 64) { s += part[((size_t)k * C + c) * 2]; ss += part[((size_t)k * C + c) * 2 + 1]; }
+  s = wave_sum_d(s); ss = wave_sum_d(ss);
+  if (lane != 0) return;
+  const double mean = count > 0.0 ? s / count : 0.0;
+  double var = count > 0.0 ? ss / count - mean * mean : 0.0;
+  if (var < 0.0) var = 0.0;
+  mean_out[c] = (float)mean;
+  rstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
+  if (rm) rm[c] = (float)((1.0 - (double)momentum) * (double)rm[c] + (double)momentum * mean);
+  if (rv) {
+    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+    rv[c] = (float)((1.0 - (double)momentum) * (double)rv[c] + (double)momentum * unbiased);
+  }
+}
+
+// bn_finalize_bwd_kernel; sums[2 * C] receives 1 / n for the dx pass
+__global__ void bn_finalize_bwd_masked_kernel(const double *__restrict__ part, int nchunks, int C, FrameGeom g, float *__restrict__ dgamma,
+                                              float *__restrict__ dbeta, float *__restrict__ sums, float beta_acc) {
+  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= C) return;
+  const double count = geom_count(g, lane);
+  double s = 0.0, ss = 0.0;
+  for (int k = lane; k < nchunks; k += 64) { s += part[((size_t)k * C + c) * 2]; ss += part[((size_t)k * C + c) * 2 + 1]; }
+  s = wave_sum_d(s); ss = wave_sum_d(ss);
+  if (lane != 0) return;
+  if (c == 0) sums[2 * C] = count > 0.0 ? (float)(1.0 / count) : 0.0f;
+  sums[c] = (float)s; sums[C + c] = (float)ss;
+  if (dbeta) dbeta[c] = (float)s + (beta_acc != 0.0f ? beta_acc * dbeta[c] : 0.0f);
+  if (dgamma) dgamma[c] = (float)ss + (beta_acc != 0.0f ? beta_acc * dgamma[c] : 0.0f);
+}
+
+// The streaming passes: a thread takes V (4 or 1) consecutive elements.  V == 4 needs 16-B aligned tensors and C % 4 == 0 (inner == 1) or
+// inner % 4 == 0 (NCHW), so that a group lies in one row / one plane.  valid_mask: bit e set iff element i0 + e is valid.
+template <int V>
+__device__ __forceinline__ unsigned valid_mask(const FrameGeom &g, size_t i0, int C, int inner, int &c0) {
+  if (inner == 1) {
+    const size_t r = i0 / (unsigned)C;
+    c0 = (int)(i0 - r * (unsigned)C);
+    return row_valid(g, (int)r) ? (1u << V) - 1u : 0u;
+  }
+  const size_t pl = i0 / (unsigned)inner;              // plane o * C + c
+  const int in = (int)(i0 - pl * (unsigned)inner);
+  c0 = (int)(pl % (unsigned)C);
+  const int left = geom_len(g, (int)(pl / (unsigned)C)) * g.frame - in;
+  return left >= V ? (1u << V) - 1u : left > 0 ? (1u << left) - 1u : 0u;
+}
+template <int V>
+__device__ __forceinline__ void load_valid(const float *__restrict__ p, size_t i0, unsigned m, float (&v)[V]) {
+  if (V == 4 && m == 15u) { const f32x4 q = *reinterpret_cast<const f32x4 *>(p + i0); v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3]; return; }
+#pragma unroll
+  for (int e = 0; e < V; ++e) v[e] = (m >> e & 1u) ? p[i0 + e] : 0.0f;
+}
+template <int V>
+__device__ __forceinline__ void store_all(float *__restrict__ p, size_t i0, const float (&v)[V]) {
+  if (V == 4) { f32x4 q; q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; q[3] = v[3]; *reinterpret_cast<f32x4 *>(p + i0) = q; }
+  else p[i0] = v[0];
+}
+
+template <int V>
+__global__ void mask_frames_kernel(const float *x, float *y, FrameGeom g, size_t ngroups, int C, int inner) {
+  for (size_t gi = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gi < ngroups; gi += (size_t)gridDim.x * blockDim.x) {
+    int c0;
+    const unsigned m = valid_mask<V>(g, gi * V, C, inner, c0);
+    float v[V];
+    load_valid<V>(x, gi * V, m, v);
+    store_all<V>(y, gi * V, v);
+  }
+}
+
+template <int V>
+__global__ void bn_apply_masked_kernel(const float *__restrict__ x, float *__restrict__ y, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                       const float *__restrict__ mean, const float *__restrict__ rstd_or_var, float eps, int var_is_variance,
+                                       FrameGeom g, size_t ngroups, int C, int inner, int relu) {
+  for (size_t gi = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gi < ngroups; gi += (size_t)gridDim.x * blockDim.x) {
+    int c0;
+    const unsigned m = valid_mask<V>(g, gi * V, C, inner, c0);
+    float xv[V], o[V];
+    load_valid<V>(x, gi * V, m, xv);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int c = inner == 1 ? c0 + e : c0;
+      const float rs = var_is_variance ? 1.0f / sqrtf(rstd_or_var[c] + eps) : rstd_or_var[c];
+      float v = bn_value(xv[e], mean[c], rs, gamma[c], beta[c]);
+      if (relu) v = fmaxf(v, 0.0f);
+      o[e] = (m >> e & 1u) ? v : 0.0f;
+    }
+    store_all<V>(y, gi * V, o);
+  }
+}
+
+template <int V>
+__global__ void bn_dx_masked_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *dy, const float *__restrict__ gamma,
+                                    const float *__restrict__ mean, const float *__restrict__ rstd, const float *__restrict__ sums, float *dx,
+                                    FrameGeom g, size_t ngroups, int C, int inner, int relu) {
+  const float inv_n = sums[2 * C];
+  for (size_t gi = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gi < ngroups; gi += (size_t)gridDim.x * blockDim.x) {
+    int c0;
+    const unsigned m = valid_mask<V>(g, gi * V, C, inner, c0);
+    float xv[V], gv[V], yv[V], o[V];
+    load_valid<V>(x, gi * V, m, xv);
+    load_valid<V>(dy, gi * V, m, gv);
+    if (relu) load_valid<V>(y, gi * V, m, yv);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int c = inner == 1 ? c0 + e : c0;
+      float gr = gv[e];
+      if (relu && !(yv[e] > 0.0f)) gr = 0.0f;
+      const float xh = (xv[e] - mean[c]) * rstd[c];
+      const float d = bn_dx_value(gr, xh, gamma[c], rstd[c], sums[c], sums[C + c], inv_n);
+      o[e] = (m >> e & 1u) ? d : 0.0f;
+    }
+    store_all<V>(dx, gi * V, o);
+  }
+}
+
+bool geom_ok(int outer, int C, int inner, const int *lens, int batch, int frame, FrameGeom *g) {
+  if (!lens || outer <= 0 || C <= 0 || inner <= 0 || batch <= 0 || frame <= 0) return false;
+  if (inner == 1 ? (frame != 1 || outer % batch != 0) : (batch != outer || inner % frame != 0)) return false;
+  *g = FrameGeom{lens, batch, frame, inner == 1 ? outer / batch : inner / frame};
+  return true;
+}
+// 4: the 16-B form of the streaming passes applies
+int stream_vec(int C, int inner, uintptr_t ptrs) { return (ptrs & 15) == 0 && (inner == 1 ? C % 4 == 0 : inner % 4 == 0) ? 4 : 1; }
+int stream_blocks(size_t ngroups) { return (int)std::min((size_t)4096, std::max((size_t)1, ceil_div_z(ngroups, 256))); }
+
+template <class F>
+void launch_reduce_masked(F f, const FrameGeom &g, int outer, int C, int inner, double *part, int *nchunks_out, hipStream_t st) {
+  if (inner == 1) {
+    const int n = chunks_rows(outer, C);
+    const int rpc = ceil_div(outer, n);
+    const int nn = ceil_div(outer, rpc);
+    if (C % 4 == 0 && f.aligned16() && ctcn_get_option("bn_rows4") != 0)
+      hipLaunchKernelGGL((mreduce_rows4_kernel<F>), dim3(ceil_div(C, 64), nn), dim3(256), 0, st, f, g, outer, C, rpc, part);
+    else
+      hipLaunchKernelGGL((mreduce_rows_kernel<F>), dim3(ceil_div(C, 64), nn), dim3(256), 0, st, f, g, outer, C, rpc, part);
+    *nchunks_out = nn;
+  } else {
+    const NchwChunks k = chunks_nchw(outer, C, inner);
+    const int vec = inner % 4 == 0 && f.aligned16() ? 1 : 0;
+    hipLaunchKernelGGL((mreduce_nchw_kernel<F>), dim3(C, k.n), dim3(256), 0, st, f, g, outer, C, inner, k.opc, k.ich, k.ilen, vec, part);
+    *nchunks_out = k.n;
+  }
+}
+
+void launch_bn_apply_masked(hipStream_t st, const float *x, float *y, const float *gamma, const float *beta, const float *mean, const float *rstd_or_var,
+                            float eps, int var_is_variance, const FrameGeom &g, size_t total, int C, int inner, int relu) {
+  if (stream_vec(C, inner, (uintptr_t)x | (uintptr_t)y) == 4)
+    hipLaunchKernelGGL(bn_apply_masked_kernel<4>, dim3(stream_blocks(total / 4)), dim3(256), 0, st, x, y, gamma, beta, mean, rstd_or_var, eps,
+                       var_is_variance, g, total / 4, C, inner, relu);
+  else
+    hipLaunchKernelGGL(bn_apply_masked_kernel<1>, dim3(stream_blocks(total)), dim3(256), 0, st, x, y, gamma, beta, mean, rstd_or_var, eps,
+                       var_is_variance, g, total, C, inner, relu);
+}
+
+}  // namespace
+
+extern "C" size_t ctcn_bn_masked_ws_bytes(int outer, int C, int inner) {
+  const size_t n = ctcn_bn_ws_bytes(outer, C, inner);
+  return n ? n + 256 : 0;                       // (+ the 1 / n word behind the two float sums)
+}
+
+extern "C" int ctcn_mask_frames(const float *x, float *y, const int *lens, int batch, int frame, int outer, int C, int inner, void *stream) {
+  CTCN_REQUIRE(x && y, "ctcn_mask_frames: null pointer");
+  FrameGeom g;
+  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_mask_frames: bad dims / geometry");
+  const size_t total = (size_t)outer * C * inner;
+  if (stream_vec(C, inner, (uintptr_t)x | (uintptr_t)y) == 4)
+    hipLaunchKernelGGL(mask_frames_kernel<4>, dim3(stream_blocks(total / 4)), dim3(256), 0, (hipStream_t)stream, x, y, g, total / 4, C, inner);
+  else
+    hipLaunchKernelGGL(mask_frames_kernel<1>, dim3(stream_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, g, total, C, inner);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_bn_fwd_train_masked(const float *x, float *y, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                                        float *save_mean, float *save_rstd, const int *lens, int batch, int frame, int outer, int C, int inner,
+                                        float eps, float momentum, int relu, void *ws, size_t ws_bytes, void *stream, long long *num_batches_tracked) {
+  CTCN_REQUIRE(x && y && gamma && beta && save_mean && save_rstd && ws, "ctcn_bn_fwd_train_masked: null pointer");
+  FrameGeom g;
+  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_bn_fwd_train_masked: bad dims / geometry");
+  if (ws_bytes < ctcn_bn_masked_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_fwd_train_masked: workspace too small"); return CTCN_EWORKSPACE; }
+  hipStream_t st = (hipStream_t)stream;
+  double *part = (double *)ws;
+  int nchunks = 0;
+  launch_reduce_masked(StatVal{x}, g, outer, C, inner, part, &nchunks, st);
+  CTCN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bn_finalize_stats_masked_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, g, eps, momentum, save_mean, save_rstd,
+                     running_mean, running_var, num_batches_tracked);
+  CTCN_LAUNCH_CHECK();
+  launch_bn_apply_masked(st, x, y, gamma, beta, save_mean, save_rstd, eps, 0, g, (size_t)outer * C * inner, C, inner, relu);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_bn_fwd_eval_masked(const float *x, float *y, const float *gamma, const float *beta, const float *running_mean,
+                                       const float *running_var, const int *lens, int batch, int frame, int outer, int C, int inner, float eps,
+                                       int relu, void *stream) {
+  CTCN_REQUIRE(x && y && gamma && beta && running_mean && running_var, "ctcn_bn_fwd_eval_masked: null pointer");
+  FrameGeom g;
+  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_bn_fwd_eval_masked: bad dims / geometry");
+  launch_bn_apply_masked((hipStream_t)stream, x, y, gamma, beta, running_mean, running_var, eps, 1, g, (size_t)outer * C * inner, C, inner, relu);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_bn_bwd_masked(const float *x, const float *y, const float *dy, const float *gamma, const float *save_mean, const float *save_rstd,
+                                  float *dx, float *dgamma, float *dbeta, const int *lens, int batch, int frame, int outer, int C, int inner, int relu,
+                                  float beta_acc, void *ws, size_t ws_bytes, void *stream) {
+  CTCN_REQUIRE(x && dy && gamma && save_mean && save_rstd && dx && ws, "ctcn_bn_bwd_masked: null pointer");
+  CTCN_REQUIRE(!relu || y, "ctcn_bn_bwd_masked: y required for the fused relu mask");
+  FrameGeom g;
+  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_bn_bwd_masked: bad dims / geometry");
+  if (ws_bytes < ctcn_bn_masked_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_bwd_masked: workspace too small"); return CTCN_EWORKSPACE; }
+  hipStream_t st = (hipStream_t)stream;
+  double *part = (double *)ws;
+  const int nmax = inner == 1 ? chunks_rows(outer, C) : chunks_nchw(outer, C, inner).n;
+  float *sums = (float *)((char *)ws + align_up((size_t)(nmax + 1) * C * 2 * sizeof(double), 256));
+  int nchunks = 0;
+  launch_reduce_masked(BwdVal{x, y, dy, save_mean, save_rstd, relu, k_no_drop}, g, outer, C, inner, part, &nchunks, st);
+  CTCN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bn_finalize_bwd_masked_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, g, dgamma, dbeta, sums, beta_acc);
+  CTCN_LAUNCH_CHECK();
+  const size_t total = (size_t)outer * C * inner;
+  if (stream_vec(C, inner, (uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (relu ? (uintptr_t)y : 0)) == 4)
+    hipLaunchKernelGGL(bn_dx_masked_kernel<4>, dim3(stream_blocks(total / 4)), dim3(256), 0, st, x, y, dy, gamma, save_mean, save_rstd, sums, dx, g,
+                       total / 4, C, inner, relu);
+  else
+    hipLaunchKernelGGL(bn_dx_masked_kernel<1>, dim3(stream_blocks(total)), dim3(256), 0, st, x, y, dy, gamma, save_mean, save_rstd, sums, dx, g, total, C,
+                       inner, relu);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}

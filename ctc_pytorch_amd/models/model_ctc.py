@@ -39,13 +39,19 @@ class BatchRNN(nn.Module):
         self.rnn = _native_rnn(rnn_type)(input_size=input_size, hidden_size=hidden_size, bidirectional=bidirectional, bias=False)
         self.dropout = nn.Dropout(p=dropout)
 
-    def forward(self, x):                       # x: (T,B,C) time-major
+    def forward(self, x, lengths=None):         # x: (T,B,C) time-major
+        """lengths (frames per utterance, None: the reference's behaviour): the layer input is 0 at padded frames -- through the masked
+        BatchNorm, whose statistics then run over the real frames, or through the mask op.  Every cell is bias-free and starts from a zero
+        state, so the reverse direction reaches an utterance's last real frame with exactly the zero state (packed-sequence semantics);
+        the recurrent kernels themselves do not know about lengths."""
         if self.batch_norm is not None:
             T, B, C = x.shape
             x = ops.batch_norm(ops.contiguous(x), self.batch_norm.weight, self.batch_norm.bias, self.batch_norm.running_mean,
                                self.batch_norm.running_var, T * B, C, 1, self.batch_norm.training,
                                0.1 if self.batch_norm.momentum is None else self.batch_norm.momentum, self.batch_norm.eps,
-                               num_batches_tracked=self.batch_norm.num_batches_tracked)
+                               num_batches_tracked=self.batch_norm.num_batches_tracked, lengths=lengths)
+        elif lengths is not None:
+            x = ops.mask_frames(x, lengths, "tbc")
         if isinstance(self.rnn, (nn.LSTM, nn.GRU, nn.RNN)):
             # the dropout rides along with the recurrent layer (same mask, same values as self.dropout(x); the recurrence stores the
             # dropped output itself where its tagged-gather kernel applies)
@@ -91,7 +97,37 @@ class LayerCNN(nn.Module):
         if self._fused:
             self.batch_norm.fuse_relu = True
 
-    def forward(self, x):
+    def out_lengths(self, lengths):
+        """(frames after the convolution, frames after the pooling) for `lengths` input frames (numpy int64 or an integer tensor):
+        floor((len + 2 p_t - k_t) / s_t) + 1, then floor(len / pool_t).  The second entry is None when the block leaves the time axis alone
+        behind the convolution (no pooling, or a pooling over frequency only): there is then nothing to re-mask."""
+        k, s, p = _pair(self.conv.kernel_size)[0], _pair(self.conv.stride)[0], _pair(self.conv.padding)[0]
+        after_conv = (lengths + (2 * p - k)) // s + 1
+        pool_t = _pair(self.pooling.kernel_size)[0] if self.pooling is not None else 1
+        return after_conv, (after_conv // pool_t if pool_t != 1 else None)
+
+    def _forward_masked(self, x, len_conv, len_pool):
+        """forward() for a padded batch whose input is 0 at padded frames: conv -> masked BN (+ ReLU) or mask -> pool (-> mask, where the
+        pooling window mixes real and padded frames) -> dropout.  The output is again 0 at padded frames."""
+        if self.conv.weight.dim() != 4:
+            raise NotImplementedError("input_lengths with the Conv1d front-end")
+        x = self.conv(x)
+        if self._fused:
+            x = self.batch_norm(x, lengths=len_conv)        # masked BN + ReLU in one pass; the dropout below draws the fused pass's counters
+        else:
+            x = self.batch_norm(x, lengths=len_conv) if self.batch_norm is not None else ops.mask_frames(x, len_conv, "bctf")
+            x = self.activation(x)
+            if not isinstance(self.activation, nn.ReLU):    # (an activation with f(0) != 0)
+                x = ops.mask_frames(x, len_conv, "bctf")
+        if self.pooling is not None:
+            x = self.pooling(x)
+            if len_pool is not None:                        # (a time pooling: its last window can mix real and padded frames)
+                x = ops.mask_frames(x, len_pool, "bctf")
+        return self.dropout(x)
+
+    def forward(self, x, lengths=None):
+        if lengths is not None:
+            return self._forward_masked(x, *lengths)
         x = self.conv(x)
         # BN + ReLU + dropout in one pass (round 5): same values, same random stream.  Only when BOTH modules train and 0 < p < 1 (ADVICE r5: a
         # frozen BatchNorm in eval mode next to a training dropout, or p = 1, take the separate modules below, as the reference's stack does)
@@ -106,6 +142,10 @@ class LayerCNN(nn.Module):
         if self.pooling is not None:
             x = self.pooling(x)
         return self.dropout(x)
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
 def _native_act(act):
@@ -161,9 +201,90 @@ class CTC_Model(nn.Module):
             blocks[str(layer)] = BatchRNN(input_size=first_in if layer == 0 else width, batch_norm=bool(layer) and rnn_param["batch_norm"], **common)
         return nn.Sequential(blocks)
 
-    def forward(self, x, visualize=False):
+    def _stage_lengths(self, lengths):
+        """Frames per utterance along the model: (input, [(after conv n, after time pooling n or None) ...], output) -- integer arithmetic on
+        whatever `lengths` is (numpy, tensor)."""
+        blocks, cur = [], lengths
+        if self.add_cnn:
+            for block in self.conv:
+                len_conv, len_pool = block.out_lengths(cur)
+                blocks.append((len_conv, len_pool))
+                cur = len_conv if len_pool is None else len_pool
+        return lengths, blocks, cur
+
+    def output_lengths(self, input_lengths):
+        """Real frames of the log-probs for utterances of `input_lengths` input frames (int64 host tensor; host arithmetic): per conv layer
+        floor((len + 2 p_t - k_t) / s_t) + 1, per time pooling floor(len / pool_t).  What nn.CTCLoss takes as input_lengths."""
+        if torch.is_tensor(input_lengths) and input_lengths.is_cuda:       # (staged lengths stay on the device: the same integer arithmetic, no sync)
+            return self._stage_lengths(input_lengths.to(torch.int64))[2]
+        host = input_lengths.detach().numpy() if torch.is_tensor(input_lengths) else np.asarray(input_lengths)
+        return torch.from_numpy(np.ascontiguousarray(self._stage_lengths(host.astype(np.int64))[2]))
+
+    def _device_stage_lengths(self, input_lengths, B, T, dev):
+        """_stage_lengths as int32 device vectors.  Host-resident lengths are checked (ValueError) and go up in ONE copy for all stages;
+        a device tensor stays there (torch integer arithmetic on B numbers) -- nothing is read back either way."""
+        if torch.is_tensor(input_lengths) and input_lengths.is_cuda:
+            if input_lengths.dim() != 1 or input_lengths.numel() != B:
+                raise ValueError("input_lengths: expected %d entries, got %s" % (B, tuple(input_lengths.shape)))
+            first, blocks, last = self._stage_lengths(input_lengths.to(torch.int64))
+            i32 = lambda t: None if t is None else t.to(torch.int32)
+            blocks = [(i32(c), i32(p)) for c, p in blocks]
+            return i32(first), blocks, (blocks[-1][1] if blocks and blocks[-1][1] is not None else blocks[-1][0] if blocks else i32(first))
+        host = np.asarray(input_lengths.detach().numpy() if torch.is_tensor(input_lengths) else input_lengths)
+        if host.ndim != 1 or host.dtype.kind not in "iu":
+            raise ValueError("input_lengths: expected a flat sequence of integers")
+        if host.size != B:
+            raise ValueError("input_lengths: %d entries for a batch of %d" % (host.size, B))
+        ops.check_frame_lengths(host, T)
+        first, blocks, last = self._stage_lengths(host.astype(np.int64))
+        if int(last.min()) < 1:
+            raise ValueError("input_lengths: an utterance of %d frames leaves no output frame behind the front-end" % int(host.min()))
+        rows = [first] + [v for pair in blocks for v in pair if v is not None]
+        up = iter(torch.from_numpy(np.stack(rows).astype(np.int32)).to(dev, non_blocking=True).unbind(0))
+        first = next(up)
+        blocks = [(next(up), None if p is None else next(up)) for _, p in blocks]
+        return first, blocks, (blocks[-1][1] if blocks and blocks[-1][1] is not None else blocks[-1][0] if blocks else first)
+
+    def _forward_masked(self, x, visualize, input_lengths):
+        """forward() with the real frames of every utterance known: padding reaches no BatchNorm statistic, no recurrence and no gradient, and
+        an utterance's log-probs do not depend on what shares its batch.  Padded output frames are log_softmax(0): uniform, finite."""
+        B, T = x.shape[0], x.shape[1]
+        first, blocks, lens = self._device_stage_lengths(input_lengths, B, T, x.device)
+        visual = [x] if visualize else None
+        h = ops.mask_frames(x, first, "btf")
+        if self.add_cnn:
+            c = h.unsqueeze(1)
+            for block, stage in zip(self.conv, blocks):
+                c = block(c, lengths=stage)
+            if visualize:
+                visual.append(c)
+            h = ops.bctf_to_tbcf(c)
+            if visualize:
+                visual.append(h)
+        else:
+            h = ops.contiguous(h.transpose(0, 1))
+        for n, block in enumerate(self.rnns):
+            # (layer 0 has no BatchNorm and its input is the masked input / front-end output: already 0 at padded frames)
+            h = block(h, lengths=None if n == 0 and block.batch_norm is None else lens)
+        Tp = h.shape[0]
+        h = h.reshape(Tp * B, -1)
+        if isinstance(self.fc, nn.Sequential):
+            z = self.fc[1](self.fc[0](h, lengths=lens))
+        else:
+            z = self.fc(ops.mask_frames(h.view(Tp, B, -1), lens, "tbc").view(Tp * B, -1))
+        out = self.log_softmax(z.view(Tp, B, -1))
+        if visualize:
+            visual.append(out)
+            return out, visual
+        return out
+
+    def forward(self, x, visualize=False, input_lengths=None):
         """x: (B, T, F) float32 on a ROCm device -> log-probs (T', B, num_class); with visualize=True also the
-        list [x, (conv_out, rnn_in,) out] the reference returns (model_ctc.py:142-185)."""
+        list [x, (conv_out, rnn_in,) out] the reference returns (model_ctc.py:142-185).
+        input_lengths (int tensor on the host or the device, list or tuple; None: the reference's behaviour, padding treated as data): the
+        real frames of every utterance, see _forward_masked; output_lengths() maps them to the frames of the result."""
+        if input_lengths is not None:
+            return self._forward_masked(x, visualize, input_lengths)
         visual = [x] if visualize else None
         if self.add_cnn:
             c = self.conv(x.unsqueeze(1))

@@ -141,7 +141,10 @@ class BatchNorm1d(_tnn.BatchNorm1d):
 
     fuse_relu = False
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        """lengths (frames per utterance; None: every row counts): statistics over the real frames only and zeros at the padded ones
+        (ops.batch_norm_masked).  (N,C) rows are time-major, N = T * len(lengths); (N,C,L) as fed by BatchRNN is (T,C,B); a contiguous
+        (N,C,L) tensor is (B,C,T)."""
         if not (self.affine and self.track_running_stats):
             raise NotImplementedError("affine=True, track_running_stats=True only (nn.BatchNorm1d defaults)")
         C = self.num_features
@@ -150,18 +153,18 @@ class BatchNorm1d(_tnn.BatchNorm1d):
         nbt = self.num_batches_tracked              # (+= 1 by the statistics kernel in training: no launch of its own)
         if x.dim() == 2:
             return ops.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, x.shape[0], C, 1, training,
-                                  mom, self.eps, self.fuse_relu, nbt)
+                                  mom, self.eps, self.fuse_relu, nbt, lengths=lengths)
         if x.dim() != 3 or x.shape[1] != C:
             raise ValueError("BatchNorm1d expects (N,C) or (N,C,L)")
         xt = x.transpose(1, 2)                     # (N,L,C)
         if xt.is_contiguous():                     # the reference's x.transpose(-1,-2) of a (T,B,C) tensor
             N, Lq = xt.shape[0], xt.shape[1]
             y = ops.batch_norm(xt, self.weight, self.bias, self.running_mean, self.running_var, N * Lq, C, 1, training, mom,
-                               self.eps, self.fuse_relu, nbt)
+                               self.eps, self.fuse_relu, nbt, lengths=lengths)
             return y.view(N, Lq, C).transpose(1, 2)
         x = ops.contiguous(x)
         return ops.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, x.shape[0], C, x.shape[2], training,
-                              mom, self.eps, self.fuse_relu, nbt)
+                              mom, self.eps, self.fuse_relu, nbt, lengths=lengths, frame=None if lengths is None else 1)
 
 
 class BatchNorm2d(_tnn.BatchNorm2d):
@@ -169,8 +172,9 @@ class BatchNorm2d(_tnn.BatchNorm2d):
 
     fuse_relu = False
 
-    def forward(self, x, drop_p=0.0):
-        """drop_p > 0 (LayerCNN, training): the layer's dropout rides along with the apply pass (ops.batch_norm)."""
+    def forward(self, x, drop_p=0.0, lengths=None):
+        """drop_p > 0 (LayerCNN, training): the layer's dropout rides along with the apply pass (ops.batch_norm).
+        lengths (frames per image on axis 2; None: every element counts): statistics over the real frames, zeros at the padded ones."""
         if not (self.affine and self.track_running_stats):
             raise NotImplementedError("affine=True, track_running_stats=True only")
         if x.dim() != 4 or x.shape[1] != self.num_features:
@@ -179,7 +183,7 @@ class BatchNorm2d(_tnn.BatchNorm2d):
         x = ops.contiguous(x)
         return ops.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, x.shape[0], x.shape[1],
                               x.shape[2] * x.shape[3], self.training, mom, self.eps, self.fuse_relu, self.num_batches_tracked,
-                              drop_p=float(drop_p) if self.training else 0.0)
+                              drop_p=float(drop_p) if self.training else 0.0, lengths=lengths, frame=None if lengths is None else x.shape[3])
 
 
 class Linear(_tnn.Linear):

@@ -868,10 +868,14 @@ class _BatchNorm(torch.autograd.Function):
 
 
 def batch_norm(x, gamma, beta, running_mean, running_var, outer, C, inner, training, momentum=0.1, eps=1e-5, relu=False, num_batches_tracked=None,
-               drop_p=0.0):
+               drop_p=0.0, lengths=None, frame=None):
     """num_batches_tracked: nn.BatchNorm's int64 counter (device tensor) or None -- in training the statistics kernel adds 1 to it (no launch
     of its own).  drop_p > 0 (training only): returns dropout(batch_norm(x), drop_p) from ONE apply pass -- the same values, the same Philox
-    counters as a separate ops.dropout behind it (round 5; per-shard statistics only: with synchronised BatchNorm the two stay separate)."""
+    counters as a separate ops.dropout behind it (round 5; per-shard statistics only: with synchronised BatchNorm the two stay separate).
+    lengths (see batch_norm_masked): statistics over the real frames only, zeros at the padded ones; None runs the plain kernels."""
+    if lengths is not None:
+        return batch_norm_masked(x, gamma, beta, running_mean, running_var, outer, C, inner, training, lengths, frame, momentum, eps, relu,
+                                 num_batches_tracked, drop_p)
     if training and drop_p > 0.0 and (_sync_bn["reduce"] is not None or not _fuse_bn_dropout[0]):
         y = batch_norm(x, gamma, beta, running_mean, running_var, outer, C, inner, training, momentum, eps, relu, num_batches_tracked)
         return dropout(y, drop_p, training)
@@ -890,6 +894,159 @@ _fuse_bn_dropout = [os.environ.get("CTCN_FUSE_BN_DROPOUT", "1") != "0"]
 def set_fuse_bn_dropout(flag):
     """BatchNorm (+ ReLU) and the dropout behind it in one pass (default on; CTCN_FUSE_BN_DROPOUT=0: two passes, the same values)."""
     _fuse_bn_dropout[0] = bool(flag)
+
+
+# --------------------------------------------------------------------------------------------------
+# length-aware BatchNorm and frame mask
+# --------------------------------------------------------------------------------------------------
+def frame_lengths(lengths, device, batch=None, tmax=None):
+    """`lengths` (int tensor on the host or the device, list or tuple: real frames per utterance) as the int32 device vector the masked
+    kernels read.  Host-resident lengths are validated here (ValueError for len < 1, len > tmax or a wrong batch size) and uploaded with one
+    copy; a device tensor is taken as it is (the kernels clamp it) -- nothing is ever read back."""
+    if torch.is_tensor(lengths):
+        if lengths.dim() != 1 or lengths.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8, torch.int8):
+            raise ValueError("lengths: expected a 1-D integer tensor, got %s %s" % (lengths.dtype, tuple(lengths.shape)))
+        if batch is not None and lengths.numel() != batch:
+            raise ValueError("lengths: %d entries for a batch of %d" % (lengths.numel(), batch))
+        if lengths.is_cuda:
+            return lengths if lengths.dtype == torch.int32 and lengths.is_contiguous() else lengths.to(torch.int32).contiguous()
+        host = lengths.detach().numpy().astype(np.int64)
+    else:
+        host = np.asarray(lengths)
+        if host.ndim != 1 or host.dtype.kind not in "iu":
+            raise ValueError("lengths: expected a flat sequence of integers")
+        host = host.astype(np.int64)
+        if batch is not None and host.size != batch:
+            raise ValueError("lengths: %d entries for a batch of %d" % (host.size, batch))
+    check_frame_lengths(host, tmax)
+    return torch.from_numpy(host.astype(np.int32)).to(device, non_blocking=True)
+
+
+def check_frame_lengths(host, tmax=None):
+    if host.size and int(host.min()) < 1:
+        raise ValueError("lengths: every utterance needs at least one frame, got %d" % int(host.min()))
+    if tmax is not None and host.size and int(host.max()) > tmax:
+        raise ValueError("lengths: %d exceeds the %d frames of the batch" % (int(host.max()), tmax))
+
+
+def _frame_geom(outer, inner, lengths, frame):
+    """(batch, frame, tmax) of the C ABI's two layouts (include/ctcn.h): rows (inner == 1) or NCHW planes."""
+    nb = int(lengths.numel()) if torch.is_tensor(lengths) else len(lengths)
+    if inner == 1:
+        if nb < 1 or outer % nb != 0 or frame not in (None, 1):
+            raise ValueError("lengths: %d entries do not divide %d rows (time-major layout)" % (nb, outer))
+        return nb, 1, outer // nb
+    frame = 1 if frame is None else int(frame)
+    if nb != outer or frame < 1 or inner % frame != 0:
+        raise ValueError("lengths: %d entries / frame %d do not fit %d planes of %d elements" % (nb, frame, outer, inner))
+    return nb, frame, inner // frame
+
+
+class _MaskFrames(torch.autograd.Function):
+    """y = x at real frames, 0 at padded ones (by select: whatever the padding holds, NaN included, is not read); its own backward."""
+    @staticmethod
+    def forward(ctx, x, lens, geom):
+        _need_gpu(x, lens)
+        x = _f32c(x)
+        y = torch.empty_like(x)
+        ctx.lens, ctx.geom = lens, geom
+        batch, frame, outer, C, inner = geom
+        _lib.check(_lib.lib().ctcn_mask_frames(_ptr(x), _ptr(y), _ptr(lens), batch, frame, outer, C, inner, _lib.stream_ptr()), "mask_frames")
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        gy = _f32c(gy)
+        dx = torch.empty_like(gy)
+        batch, frame, outer, C, inner = ctx.geom
+        _lib.check(_lib.lib().ctcn_mask_frames(_ptr(gy), _ptr(dx), _ptr(ctx.lens), batch, frame, outer, C, inner, _lib.stream_ptr()), "mask_frames_bwd")
+        return dx, None, None
+
+
+MASK_LAYOUTS = ("tbc", "btf", "bctf")
+
+
+def mask_frames(x, lengths, layout):
+    """Zero the padded frames of `x`.  layout: "tbc" (T,B,C) time-major rows, "btf" (B,T,F) model input, "bctf" (B,C,T,F) feature maps."""
+    if layout == "tbc" and x.dim() == 3:
+        T, B, C = x.shape
+        dims, frame, tmax = (T * B, C, 1), None, T
+    elif layout == "btf" and x.dim() == 3:
+        B, T, F = x.shape
+        dims, frame, tmax = (B, 1, T * F), F, T
+    elif layout == "bctf" and x.dim() == 4:
+        B, C, T, F = x.shape
+        dims, frame, tmax = (B, C, T * F), F, T
+    else:
+        raise ValueError("mask_frames: layout %r (one of %s) does not fit a %d-D tensor" % (layout, ", ".join(MASK_LAYOUTS), x.dim()))
+    lens = frame_lengths(lengths, x.device, B, tmax)           # (checked before anything touches the device)
+    _need_gpu(x)
+    batch, frame, _ = _frame_geom(dims[0], dims[2], lens, frame)
+    return _MaskFrames.apply(x, lens, (batch, frame) + dims)
+
+
+class _BatchNormMasked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, rm, rv, lens, geom, training, momentum, eps, relu, nbt):
+        _need_gpu(x, gamma, beta, lens)
+        ctx.gviews = (_gview(gamma), _gview(beta))
+        x = _f32c(x)
+        y = torch.empty_like(x)
+        L = _lib.lib()
+        batch, frame, outer, C, inner = geom
+        if training:
+            mean = torch.empty(C, dtype=torch.float32, device=x.device)
+            rstd = torch.empty(C, dtype=torch.float32, device=x.device)
+            w, wp, wn = _ws(x)
+            _lib.check(L.ctcn_bn_fwd_train_masked(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(rm), _ptr(rv), _ptr(mean), _ptr(rstd), _ptr(lens),
+                                                  batch, frame, outer, C, inner, float(eps), float(momentum), int(relu), wp, wn, _lib.stream_ptr(),
+                                                  _ptr(nbt)), "bn_fwd_train_masked")
+            ctx.save_for_backward(x, y if relu else None, gamma, mean, rstd)
+        else:
+            _lib.check(L.ctcn_bn_fwd_eval_masked(_ptr(x), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(rm), _ptr(rv), _ptr(lens), batch, frame, outer, C, inner,
+                                                 float(eps), int(relu), _lib.stream_ptr()), "bn_fwd_eval_masked")
+        ctx.train_mode, ctx.lens, ctx.geom, ctx.relu = training, lens, geom, relu
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if not ctx.train_mode:
+            raise NotImplementedError("ctc_pytorch_amd: backward through eval-mode BatchNorm is not part of the hot path")
+        x, y, gamma, mean, rstd = ctx.saved_tensors
+        batch, frame, outer, C, inner = ctx.geom
+        gy = _f32c(gy)
+        dx = torch.empty_like(x)
+        into_flat = ctx.gviews[0] is not None and ctx.gviews[1] is not None
+        dgamma, dbeta = ctx.gviews if into_flat else (torch.empty(C, dtype=torch.float32, device=x.device), torch.empty(C, dtype=torch.float32, device=x.device))
+        w, wp, wn = _ws(x)
+        _lib.check(_lib.lib().ctcn_bn_bwd_masked(_ptr(x), _ptr(y), _ptr(gy), _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx), _ptr(dgamma), _ptr(dbeta),
+                                                 _ptr(ctx.lens), batch, frame, outer, C, inner, int(ctx.relu), 1.0 if into_flat else 0.0, wp, wn,
+                                                 _lib.stream_ptr()), "bn_bwd_masked")
+        if into_flat:
+            dgamma = dbeta = None
+        return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None
+
+
+def batch_norm_masked(x, gamma, beta, running_mean, running_var, outer, C, inner, training, lengths, frame=None, momentum=0.1, eps=1e-5, relu=False,
+                      num_batches_tracked=None, drop_p=0.0):
+    """batch_norm over the real frames of a padded batch: `lengths` = frames per utterance; inner == 1: x is (T * B, C) time-major rows;
+    inner > 1: x is (B, C, T' * frame) with `frame` elements per time step.  Statistics, running statistics and gradients use the
+    n = sum(lengths) * frame valid elements per channel (counted on the device); the output and dx are 0 at padded frames, which are never
+    read.  drop_p > 0: the separate ops.dropout follows (the values and Philox counters of the fused pass of batch_norm)."""
+    if training and _sync_bn["reduce"] is not None:
+        raise NotImplementedError("ctc_pytorch_amd: synchronised BatchNorm (parallel.enable_sync_bn) does not take lengths -- the count of valid "
+                                  "frames would have to be reduced across the ranks; run per-shard statistics or drop the lengths")
+    batch, frame, tmax = _frame_geom(outer, inner, lengths, frame)
+    lens = frame_lengths(lengths, x.device, batch, tmax)
+    _need_gpu(x)
+    nbt = num_batches_tracked
+    if nbt is not None and (not training or nbt.dtype != torch.int64 or not nbt.is_cuda):
+        if training:
+            nbt += 1
+        nbt = None
+    y = _BatchNormMasked.apply(x, gamma, beta, running_mean, running_var, lens, (batch, frame, int(outer), int(C), int(inner)), bool(training),
+                               momentum, eps, bool(relu), nbt)
+    return dropout(y, drop_p, training) if drop_p > 0.0 else y
 
 
 class _ReLU(torch.autograd.Function):

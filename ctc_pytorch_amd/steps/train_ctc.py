@@ -40,8 +40,21 @@ def frames_from_fraction(input_sizes, out_len):
     return (frac * np.float32(out_len)).astype(np.int64)
 
 
+def input_frames_from_fraction(input_sizes, T):
+    """The loader's float32 fractions len / T_max back as frames: round-to-nearest of the float32 product -- float32(t / tmax) * tmax can
+    fall just below t, so the truncation of frames_from_fraction would lose a frame.  Exact for every 1 <= t <= tmax <= 2000
+    (tests/test_length_mask_host.py).  A device tensor (DevicePrefetcher) stays on the device: no sync."""
+    if torch.is_tensor(input_sizes) and input_sizes.is_cuda:
+        return torch.round(input_sizes.float() * float(T)).long()
+    frac = np.asarray(input_sizes.detach().numpy() if torch.is_tensor(input_sizes) else input_sizes, dtype=np.float32)
+    return np.rint(frac * np.float32(T)).astype(np.int64)
+
+
 def run_epoch(epoch_id, model, data_iter, loss_fn, device, optimizer=None, print_every=20, is_training=True,
-              global_batch=None, log=print):
+              global_batch=None, log=print, mask_padding=False):
+    """mask_padding (YAML key `mask_padding`, default off = the reference's behaviour): the model is told every utterance's real frames
+    (CTC_Model.forward(input_lengths=)), so padding reaches no BatchNorm statistic and no recurrence, and the CTC loss takes
+    model.output_lengths(...) instead of floor(fraction * T_out)."""
     model.train() if is_training else model.eval()
     total_loss = 0.0
     total_tokens = 0
@@ -84,9 +97,16 @@ def run_epoch(epoch_id, model, data_iter, loss_fn, device, optimizer=None, print
         targets_d = targets.to(device, non_blocking=True)
         target_sizes_d = target_sizes.to(device, non_blocking=True)
         with torch.set_grad_enabled(is_training):
-            out = model(inputs)
+            if mask_padding:
+                frames = input_frames_from_fraction(input_sizes, int(inputs.shape[1]))
+                frames = frames if torch.is_tensor(frames) else torch.from_numpy(frames)
+                out = model(inputs, input_lengths=frames)
+            else:
+                out = model(inputs)
             out_len, batch_size, _ = out.size()
-            if torch.is_tensor(input_sizes) and input_sizes.is_cuda:
+            if mask_padding:
+                in_len = model.output_lengths(frames).to(device, non_blocking=True)
+            elif torch.is_tensor(input_sizes) and input_sizes.is_cuda:
                 # DevicePrefetcher staged the fractions: the float32 product and truncation of train_ctc.py:46 on the device
                 # (same IEEE multiply, same integers), no blocking pageable H2D in the middle of the step
                 in_len = (input_sizes.float() * float(out_len)).long()
@@ -143,6 +163,12 @@ def optimizer_options(opts):
     absent (or null / false) keys leave both features off: the run is then the unclipped, unguarded one."""
     mg = getattr(opts, "max_grad_norm", None)
     return {"max_grad_norm": None if mg is None else float(mg), "skip_nonfinite": bool(getattr(opts, "skip_nonfinite_steps", False))}
+
+
+def epoch_options(opts):
+    """run_epoch's keywords from the driver options: `mask_padding: true` passes the utterance lengths to the model; an absent (or false)
+    key passes nothing -- run_epoch then calls the model exactly as the reference's loop does."""
+    return {"mask_padding": True} if bool(getattr(opts, "mask_padding", False)) else {}
 
 
 class Config(object):
@@ -270,11 +296,11 @@ def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print):
             ctl.begin_epoch(optimizer)
             log("Start training epoch: %d, learning_rate: %.5f" % (count, optimizer.param_groups[0]["lr"]))
             _, loss = run_epoch(count, model, train_loader, loss_fn, device, optimizer=optimizer, print_every=opts.verbose_step,
-                                is_training=True, log=log)
+                                is_training=True, log=log, **epoch_options(opts))
             # per-shard BatchNorm: one set of running statistics for the evaluation below and for rank 0's checkpoint
             parallel.sync_bn_buffers(model)
             acc, dev_loss = run_epoch(count, model, dev_loader, loss_fn, device, optimizer=None, print_every=opts.verbose_step,
-                                      is_training=False, log=log)
+                                      is_training=False, log=log, **epoch_options(opts))
             loss_results.append(loss)
             dev_loss_results.append(dev_loss)
             dev_cer_results.append(acc)
@@ -305,8 +331,11 @@ if __name__ == "__main__":
     ap.add_argument("--conf", default="conf/ctc_config.yaml")
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm to this value (default: the YAML's max_grad_norm, else off)")
     ap.add_argument("--skip-nonfinite-steps", action="store_true", help="drop optimiser steps whose gradient holds NaN / Inf (default: the YAML's skip_nonfinite_steps, else off)")
+    ap.add_argument("--mask-padding", action="store_true", help="tell the model every utterance's real frames: padding reaches no BatchNorm statistic and no recurrence (default: the YAML's mask_padding, else off)")
     a = ap.parse_args()
     conf = yaml.safe_load(open(a.conf, "r"))
+    if a.mask_padding:
+        conf["mask_padding"] = True
     if a.max_grad_norm is not None:
         conf["max_grad_norm"] = a.max_grad_norm
     if a.skip_nonfinite_steps:

@@ -314,6 +314,27 @@ int ctcn_bn_bwd_dropout(const float *x, const float *dy_drop, const float *gamma
                         float *dx, float *dgamma, float *dbeta, int outer, int C, int inner, int relu, float beta_acc, void *ws, size_t ws_bytes,
                         void *stream, float p, uint64_t seed, uint64_t offset);
 
+/* Length-aware BatchNorm and frame mask: padding never reaches the statistics, the outputs or the gradients.
+ * lens[b] (device int32) = real frames of utterance b; the geometry names the two layouts of the model:
+ *   inner == 1 (rows = T * batch, time-major; frame must be 1): row r is valid iff r / batch < lens[r % batch]
+ *   inner  > 1 (NCHW; batch must equal outer, inner = T' * frame): element i of plane (o, c) is valid iff i / frame < lens[o]
+ * (lens are clamped to [0, T] on the device.)  The statistics, dgamma / dbeta and the dx reduction terms run over the valid elements with
+ * n = sum(lens) * frame taken on the device (no host sync); running statistics use that n (unbiased variance: n - 1).  y and dx are 0 at
+ * invalid elements by select, and no pass reads x / y / dy there.  Otherwise the contract of ctcn_bn_fwd_train / _eval / ctcn_bn_bwd
+ * (relu, num_batches_tracked, beta_acc, deterministic float64 partials).  ws: >= ctcn_bn_masked_ws_bytes(outer, C, inner).
+ * ctcn_mask_frames: y = valid ? x : 0 (its own backward); y may alias x. */
+size_t ctcn_bn_masked_ws_bytes(int outer, int C, int inner);
+int ctcn_mask_frames(const float *x, float *y, const int *lens, int batch, int frame, int outer, int C, int inner, void *stream);
+int ctcn_bn_fwd_train_masked(const float *x, float *y, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                             float *save_mean, float *save_rstd, const int *lens, int batch, int frame, int outer, int C, int inner,
+                             float eps, float momentum, int relu, void *ws, size_t ws_bytes, void *stream, long long *num_batches_tracked);
+int ctcn_bn_fwd_eval_masked(const float *x, float *y, const float *gamma, const float *beta, const float *running_mean,
+                            const float *running_var, const int *lens, int batch, int frame, int outer, int C, int inner, float eps,
+                            int relu, void *stream);
+int ctcn_bn_bwd_masked(const float *x, const float *y, const float *dy, const float *gamma, const float *save_mean, const float *save_rstd,
+                       float *dx, float *dgamma, float *dbeta, const int *lens, int batch, int frame, int outer, int C, int inner, int relu,
+                       float beta_acc, void *ws, size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Dropout (inverted, Philox4x32-10 counter RNG keyed by (seed, offset + element index)).
  * replaces: nn.Dropout (model_ctc.py:26,34,58,67).  bwd regenerates the mask from (seed, offset). */
