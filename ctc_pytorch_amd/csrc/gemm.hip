@@ -1879,6 +1879,9 @@ static int gemm_core(int transA, int transB, int M, int N, int K, const float *A
   CTCN_REQUIRE(M > 0 && N > 0 && K >= 0, "ctcn_gemm: bad dims M=%d N=%d K=%d", M, N, K);
   CTCN_REQUIRE(A && B && C, "ctcn_gemm: null pointer");
   CTCN_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "ctcn_gemm: leading dim too small");
+  // A, B and C may start on any 4 bytes (every 16-byte access to them is chosen from the pointer: vecA / vecB, split_transpose_tile, the inline
+  // A split, the TN tile, the split-K reduce); the workspace may not: bf16 planes, partials and queue words are carved from it by offset alone
+  CTCN_REQUIRE(!ws || (uintptr_t)ws % 16 == 0, "ctcn_gemm: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int tiles_m = ceil_div(M, BM), tiles_n = ceil_div(N, BN);
   const int nt = tiles_m * tiles_n;

@@ -2603,7 +2603,7 @@ struct FwdCall {
 };
 
 static int fwd_validate(int cell, int T, int B, int I, int H, int dirs, const float *x, const float *w_ih0, const float *w_hh0, const float *w_ih1,
-                        const float *w_hh1, const float *y, const float *gates, const float *aux) {
+                        const float *w_hh1, const float *y, const float *gates, const float *aux, const void *ws) {
   CTCN_REQUIRE(cell >= 0 && cell <= 2, "ctcn_rnn_fwd: unknown cell %d", cell);
   CTCN_REQUIRE(T > 0 && B > 0 && I > 0 && H > 0 && (dirs == 1 || dirs == 2), "ctcn_rnn_fwd: bad dims");
   if (H % 4 != 0) { ctcn_set_error("ctcn_rnn_fwd: hidden size %d must be a multiple of 4", H); return CTCN_EUNSUPPORTED; }
@@ -2611,6 +2611,8 @@ static int fwd_validate(int cell, int T, int B, int I, int H, int dirs, const fl
   CTCN_REQUIRE(cell == CTCN_CELL_TANH || aux, "ctcn_rnn_fwd: aux reserve required for LSTM/GRU");
   CTCN_REQUIRE(((uintptr_t)w_hh0 % 16 == 0) && ((uintptr_t)y % 16 == 0) && (dirs == 1 || (uintptr_t)w_hh1 % 16 == 0),
                "ctcn_rnn_fwd: w_hh / y must be 16-byte aligned");
+  // (x, w_ih: the GEMM's operands, any 4 bytes; gates / aux / y_drop: dword accesses, 16-byte ones only where fwd_try_tagged has looked)
+  CTCN_REQUIRE((uintptr_t)ws % 16 == 0, "ctcn_rnn_fwd: the workspace must be 16-byte aligned (hand-off tiles)");
   return CTCN_OK;
 }
 
@@ -2844,7 +2846,7 @@ static int fwd_per_timestep(FwdCall &c) {
 static int rnn_fwd_impl(int cell, int T, int B, int I, int H, int dirs, const float *x, const float *w_ih0,
                         const float *w_hh0, const float *w_ih1, const float *w_hh1, float *y, float *gates,
                         float *aux, int precision, void *ws, size_t ws_bytes, void *stream, const ctcn_rnn_call &call, bool &drop_pending) {
-  if (int rc = fwd_validate(cell, T, B, I, H, dirs, x, w_ih0, w_hh0, w_ih1, w_hh1, y, gates, aux)) return rc;
+  if (int rc = fwd_validate(cell, T, B, I, H, dirs, x, w_ih0, w_hh0, w_ih1, w_hh1, y, gates, aux, ws)) return rc;
   FwdCall c = {cell, T, B, I, H, dirs, precision, x, {w_ih0, w_ih1}, gates, ws, ws_bytes, stream, call};
   fwd_begin(c, w_hh0, w_hh1, y, aux);
   const PipePlan plan = decide_pipeline(c);
@@ -3099,6 +3101,7 @@ extern "C" int ctcn_rnn_bwd_ex(int cell, int T, int B, int I, int H, int dirs, c
   CTCN_REQUIRE(cell == CTCN_CELL_TANH || aux, "ctcn_rnn_bwd: aux reserve required for LSTM/GRU");
   CTCN_REQUIRE((uintptr_t)gates % 16 == 0 && (uintptr_t)scratch % 16 == 0 && (cell == CTCN_CELL_TANH || (uintptr_t)aux % 16 == 0),
                "ctcn_rnn_bwd: gates / aux / scratch must be 16-byte aligned");
+  CTCN_REQUIRE((uintptr_t)ws % 16 == 0, "ctcn_rnn_bwd: the workspace must be 16-byte aligned (hand-off tiles)");
   BwdCall c = {cell, T, B, I, H, dirs, precision, dy, ws, ws_bytes, stream, call};
   c.G = gates_of(cell); c.GH = c.G * H;
   const int GH = c.GH;

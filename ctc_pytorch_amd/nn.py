@@ -12,6 +12,7 @@ import torch
 import torch.nn as _tnn
 
 from . import ops
+from .optim import ALIGN
 
 Module = _tnn.Module
 Sequential = _tnn.Sequential
@@ -23,7 +24,8 @@ def __getattr__(name):          # everything else (init, functional, ...) is pla
 
 
 def _flat_grad_of(params):
-    """The flat gradient buffer of optim.FlatAdam if `params` are all homed in it and together cover it exactly once, else None."""
+    """The flat gradient buffer of optim.FlatAdam if `params` are all homed in it and together cover it exactly once, else None.  Between two
+    views there may lie optim.flat_layout's alignment padding (fewer than optim.ALIGN elements, which hold zero and add nothing to a norm)."""
     grads = [getattr(p, "_ctcn_grad", None) for p in params]
     if not grads or any(g is None for g in grads):
         return None
@@ -36,9 +38,9 @@ def _flat_grad_of(params):
         return None
     cur = flat.data_ptr()
     for ptr, n in spans:
-        if ptr != cur:
+        if not 0 <= ptr - cur < 4 * ALIGN:
             return None
-        cur += 4 * n
+        cur = ptr + 4 * n
     return flat if cur == flat.data_ptr() + 4 * flat.numel() else None
 
 

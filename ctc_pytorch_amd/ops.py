@@ -566,6 +566,11 @@ class _RNNLayer(torch.autograd.Function):
         ctx.gviews = [_gview(w) for w in (w_ih0, w_hh0, w_ih1, w_hh1)]
         x = _f32c(x)
         ws = [_f32c(w) if w is not None else None for w in (w_ih0, w_hh0, w_ih1, w_hh1)]
+        # W_hh is the one operand the recurrent kernels read with unconditional 16-byte loads (ctcn_rnn_fwd refuses another): a caller's
+        # misaligned view is copied (G*H*H floats) -- optim.FlatAdam's parameters never are.  Gradients still go to the caller's view.
+        for k in (1, 3):
+            if ws[k] is not None and ws[k].data_ptr() % 16:
+                ws[k] = ws[k].clone()
         T, B, I = x.shape
         G = GATES[cell]
         H = ws[1].shape[1]

@@ -4,7 +4,7 @@ replaces: torch.optim.Adam(model.parameters(), lr, weight_decay) as used at the 
 timit/steps/train_ctc.py:145,62-65 (L2-coupled weight decay, betas (0.9,0.999), eps 1e-8).
 
 All parameters of the model are re-homed into ONE contiguous float32 buffer and all gradients into a second
-one (288 GB of HBM: no reason to scatter 25 tensors).  The backward kernels of ops.py accumulate weight
+one (288 GB of HBM: no reason to scatter 25 tensors), each parameter starting on 16 bytes (flat_layout).  The backward kernels of ops.py accumulate weight
 gradients straight into views of the flat gradient buffer (`param._ctcn_grad`), so a training step needs
   1 memset (zero_grad) + 1 RCCL all-reduce over the flat gradient (data parallel) + 1 fused Adam launch.
 BatchNorm running statistics stay ordinary buffers.
@@ -22,6 +22,22 @@ def placement_order(names):
     for i, n in enumerate(names):
         first.setdefault(n.rsplit(".", 1)[0], i)
     return sorted(range(len(names)), key=lambda i: (first[names[i].rsplit(".", 1)[0]], rank.get(names[i].rsplit(".", 1)[-1], 4), i))
+
+
+ALIGN = 4      # floats: every parameter starts on 16 bytes inside the (allocator-aligned) flat buffers
+
+
+def flat_layout(sizes):
+    """(offsets, total) of tensors of `sizes` elements placed in that order in a flat buffer: back to back, each start rounded up to a
+    multiple of ALIGN elements -- the operand alignment the recurrent kernels require of W_hh (DESIGN, "Operand alignment contract") and
+    the vector paths of all the others take.  Sizes that are all multiples of ALIGN (every shipped configuration) give the plain prefix
+    sums; the padding elements belong to no parameter and hold zero in every buffer.  Device-free."""
+    offsets, off = [], 0
+    for n in sizes:
+        off = -(-off // ALIGN) * ALIGN
+        offsets.append(off)
+        off += int(n)
+    return offsets, off
 
 
 class FlatAdam:
@@ -59,20 +75,20 @@ class FlatAdam:
             raise RuntimeError("FlatAdam: move the model to the ROCm device first (no CPU path)")
         self.params = [p for _, p in named]
         sizes = [p.numel() for p in params]
-        total = sum(sizes)
-        self.flat = torch.empty(total, dtype=torch.float32, device=dev)
+        self.offsets, total = flat_layout(sizes)
+        # zeros, not empty: a padding element is 0 in all four buffers and stays 0 (Adam of p = g = m = v = 0 is 0, with weight decay and
+        # any clip coefficient; no backward kernel writes outside a parameter's view; the gradient norm does not see a zero)
+        self.flat = torch.zeros(total, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(total, dtype=torch.float32, device=dev)
         self.m = torch.zeros(total, dtype=torch.float32, device=dev)
         self.v = torch.zeros(total, dtype=torch.float32, device=dev)
-        off = 0
         with torch.no_grad():
-            for p, n in zip(params, sizes):
+            for p, n, off in zip(params, sizes, self.offsets):
                 self.flat[off:off + n].copy_(p.data.reshape(-1))
                 p.data = self.flat[off:off + n].view(p.shape)
                 g = self.grad[off:off + n].view(p.shape)
                 p._ctcn_grad = g          # ops.py backward kernels accumulate here and return None to autograd
                 p.grad = g
-                off += n
         self.step_count = 0
         self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, params=self.params)]
 
@@ -156,12 +172,8 @@ class FlatAdam:
         """(index in model.parameters() order, offset, numel, shape) of every parameter inside the flat buffers."""
         order = {id(p): i for i, p in enumerate(self.params)}
         by_name = dict((n, p) for n, p in self.model.named_parameters() if p.requires_grad)
-        out, off = [], 0
-        for name in self.layout:
-            p = by_name[name]
-            out.append((order[id(p)], off, p.numel(), tuple(p.shape)))
-            off += p.numel()
-        return out
+        ps = [by_name[name] for name in self.layout]
+        return [(order[id(p)], off, p.numel(), tuple(p.shape)) for p, off in zip(ps, self.offsets)]
 
     def state_dict(self):
         """{'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]} exactly as torch.optim.Adam writes it
