@@ -125,8 +125,62 @@ struct BwdVal {    // (dy', dy' * xhat), dy' = dy masked by relu (and, with a Dr
 };
 static const DropSpec k_no_drop = {0.0f, 1.0f, 0, 0, nullptr, nullptr};
 
-template <class F>
-__global__ __launch_bounds__(256) void colreduce_rows_kernel(F f, int rows, int C, int rows_per_chunk, double *__restrict__ part) {
+// validity policies -------------------------------------------------------------------------------
+// Every utterance b of a padded batch has lens[b] real frames; the rest of its time axis is padding.  Validity is a function of the frame:
+//   inner == 1 (rows = T * batch, time-major):  row r is valid iff r / batch < lens[r % batch]
+//   inner  > 1 (NCHW, outer = batch, inner = T' * frame):  element i of a plane (o, c) is valid iff i / frame < lens[o]
+// The length-aware entry points (*_masked) take the statistics, dgamma / dbeta and the two dx reduction terms over the valid elements
+// only, with the count n = sum(lens) * frame taken on the device (no host sync); y and dx are 0 at invalid elements BY SELECT, and no pass
+// reads x / y / dy there -- a NaN in the padding cannot reach anything, and a padded row costs no read.
+// Every kernel below takes one of two policies by value: AllFrames (the dense entry points: every test folds away at compile time) or
+// Frames.  The chunking, the float64 partials, their fixed-order sums and the per-element expressions (bn_value, bn_dx_value) are one
+// piece of code for both: with full lengths the length-aware calls sum the same values in the same order as the dense ones.
+struct AllFrames {     // n and 1 / n come from the host (the synchronised finish calls: of the global batch)
+  double count_; float inv_n_;
+  static constexpr bool kAll = true;
+  __device__ __forceinline__ bool row_valid(int) const { return true; }
+  __device__ __forceinline__ int prefix(int, int inner) const { return inner; }       // valid elements at the head of a plane
+  __device__ __forceinline__ double count(int) const { return count_; }
+  __device__ __forceinline__ float inv_n(const float *, int) const { return inv_n_; }
+  // first element i0 of a group of V (in one row / one plane) -> its channel c0 and the bits of the valid elements
+  template <int V>
+  __device__ __forceinline__ unsigned valid_mask(size_t i0, int C, int inner, int &c0) const {
+    c0 = (int)((i0 / inner) % C);
+    return (1u << V) - 1u;
+  }
+};
+static AllFrames all_frames(double count) { return {count, (float)(1.0 / count)}; }
+
+struct Frames {        // tmax: frames on the time axis (lens are clamped to [0, tmax])
+  const int *lens; int batch, frame, tmax;
+  static constexpr bool kAll = false;
+  __device__ __forceinline__ int len(int b) const { return min(max(lens[b], 0), tmax); }
+  __device__ __forceinline__ bool row_valid(int r) const { return r / batch < lens[r % batch]; }
+  __device__ __forceinline__ int prefix(int o, int) const { return len(o) * frame; }
+  // n = sum(lens) * frame, by one whole wave (every lane receives it; integers below 2^53: exact in any order)
+  __device__ __forceinline__ double count(int lane) const {
+    double n = 0.0;
+    for (int b = lane; b < batch; b += 64) n += (double)len(b);
+    return wave_sum_d(n) * (double)frame;
+  }
+  __device__ __forceinline__ float inv_n(const float *sums, int C) const { return sums[2 * C]; }     // (left there by bn_finalize_bwd_kernel)
+  template <int V>
+  __device__ __forceinline__ unsigned valid_mask(size_t i0, int C, int inner, int &c0) const {
+    if (inner == 1) {
+      const size_t r = i0 / (unsigned)C;
+      c0 = (int)(i0 - r * (unsigned)C);
+      return row_valid((int)r) ? (1u << V) - 1u : 0u;
+    }
+    const size_t pl = i0 / (unsigned)inner;              // plane o * C + c
+    const int in = (int)(i0 - pl * (unsigned)inner);
+    c0 = (int)(pl % (unsigned)C);
+    const int left = prefix((int)(pl / (unsigned)C), inner) - in;
+    return left >= V ? (1u << V) - 1u : left > 0 ? (1u << left) - 1u : 0u;
+  }
+};
+
+template <class F, class G>
+__global__ __launch_bounds__(256) void colreduce_rows_kernel(F f, G g, int rows, int C, int rows_per_chunk, double *__restrict__ part) {
   __shared__ double sa[4][64], sb[4][64];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + cx;
@@ -139,11 +193,12 @@ __global__ __launch_bounds__(256) void colreduce_rows_kernel(F f, int rows, int 
     for (; r + 28 < r1; r += 32) {
       Pair p[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) p[u] = f((size_t)(r + 4 * u) * C + c, c);
+      for (int u = 0; u < 8; ++u) p[u] = g.row_valid(r + 4 * u) ? f((size_t)(r + 4 * u) * C + c, c) : Pair{0.0, 0.0};
 #pragma unroll
       for (int u = 0; u < 8; ++u) { a += p[u].a; b += p[u].b; }
     }
     for (; r < r1; r += 4) {
+      if (!g.row_valid(r)) continue;
       const Pair p = f((size_t)r * C + c, c);
       a += p.a; b += p.b;
     }
@@ -165,8 +220,8 @@ __global__ __launch_bounds__(256) void colreduce_rows_kernel(F f, int rows, int 
 // Steps: cfg2 13.33 -> 13.25 ms, cfg4 53.2 -> 52.8 (A/B in one session, option "bn_rows4"), losses bit-identical.
 // Same chunks (grid, rows_per_chunk) and the same per-element values as colreduce_rows_kernel; a column's rows are grouped into sixteen
 // phases instead of four before the (fixed-order) float64 sums, so the two kernels agree to float64 rounding, not bit for bit.
-template <class F>
-__global__ __launch_bounds__(256) void colreduce_rows4_kernel(F f, int rows, int C, int rows_per_chunk, double *__restrict__ part) {
+template <class F, class G>
+__global__ __launch_bounds__(256) void colreduce_rows4_kernel(F f, G g, int rows, int C, int rows_per_chunk, double *__restrict__ part) {
   __shared__ double sa[16][65], sb[16][65];
   const int l16 = threadIdx.x & 15, rp = threadIdx.x >> 4;
   const int c0 = blockIdx.x * 64 + 4 * l16;
@@ -176,12 +231,21 @@ __global__ __launch_bounds__(256) void colreduce_rows4_kernel(F f, int rows, int
     const typename F::ColK k = f.colk(c0);
     constexpr int U = F::ROWS_IN_FLIGHT;
     for (int r = r0 + rp; r < r1; r += 16 * U) {
-      typename F::Quad q[U];
+      typename F::Quad q[U] = {};
+      bool v[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) q[u] = f.load4((size_t)min(r + 16 * u, r1 - 1) * C + c0);     // (clamped address; the row test is on the addition)
+      for (int u = 0; u < U; ++u) {
+        const int rr = r + 16 * u;
+        if constexpr (G::kAll) {      // unconditional loads from a clamped address; the row test is on the addition
+          q[u] = f.load4((size_t)min(rr, r1 - 1) * C + c0);
+        } else {                      // an invalid row is neither requested nor added
+          v[u] = rr < r1 && g.row_valid(rr);
+          if (v[u]) q[u] = f.load4((size_t)rr * C + c0);
+        }
+      }
 #pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (r + 16 * u < r1) f.cols4(q[u], k, a, b);
+      for (int u = 0; u < U; ++u)     // (all frames: the row test is formed here, not kept in v[] -- kept there, the loads are scheduled differently)
+        if (G::kAll ? r + 16 * u < r1 : v[u]) f.cols4(q[u], k, a, b);
     }
   }
 #pragma unroll
@@ -201,28 +265,37 @@ __global__ __launch_bounds__(256) void colreduce_rows4_kernel(F f, int rows, int
 // shipped-YAML shape, 8 x 32 x 400 x 122: one workgroup per (channel, image) walked 195 KB with one dword load in flight per lane: 100 /
 // 163 us for the backward sums against a ~30 us HBM floor): the planes are cut along the inner dimension as well (`ich` pieces of <= 64 KB),
 // lanes take 16-B pieces, four of them in flight per operand; the partials stay float64, one per chunk, added by the finalize pass in chunk
-// order (deterministic).
-template <class F>
-__global__ __launch_bounds__(256) void colreduce_nchw_kernel(F f, int outer, int C, int inner, int opc, int ich, int ilen, int vec, double *__restrict__ part) {
+// order (deterministic).  A plane is read up to its valid prefix only.
+template <class F, class G>
+__global__ __launch_bounds__(256) void colreduce_nchw_kernel(F f, G g, int outer, int C, int inner, int opc, int ich, int ilen, int vec,
+                                                             double *__restrict__ part) {
   __shared__ double sa[4], sb[4];
   const int c = blockIdx.x;
   // chunk -> planes [o0, o1) (opc of them; 1 when the planes are cut into ich pieces) and the inner range [i0, i1)
   const int oc = blockIdx.y / ich, ic = blockIdx.y - oc * ich;
   const int o0 = oc * opc, o1 = min(outer, o0 + opc);
-  const int i0 = ic * ilen, i1 = min(inner, i0 + ilen);
+  const int i0 = ic * ilen;
   double a = 0.0, b = 0.0;
   for (int o = o0; o < o1; ++o) {
     const size_t base = ((size_t)o * C + c) * inner;
+    const int i1 = min(min(inner, i0 + ilen), g.prefix(o, inner));
     if (vec) {                      // inner % 4 == 0, ilen % 1024 == 0, 16-B aligned operands
+      const int i1v = G::kAll ? i1 : i1 & ~3;           // (all frames: i1 is a multiple of 4 as it is)
       int i = i0 + threadIdx.x * 4;
-      for (; i + 3 * 1024 < i1; i += 4096) {
+      for (; i + 3 * 1024 < i1v; i += 4096) {
         typename F::Quad q[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) q[u] = f.load4(base + i + 1024 * u);
 #pragma unroll
         for (int u = 0; u < 4; ++u) f.add4(q[u], c, a, b);
       }
-      for (; i < i1; i += 1024) f.add4(f.load4(base + i), c, a, b);
+      for (; i < i1v; i += 1024) f.add4(f.load4(base + i), c, a, b);
+      if constexpr (!G::kAll) {     // a prefix may end inside a quad: its (at most three) last elements are added one by one behind the 16-B pieces
+        if (i1v >= i0 && (int)threadIdx.x < i1 - i1v) {
+          const Pair p = f(base + i1v + threadIdx.x, c);
+          a += p.a; b += p.b;
+        }
+      }
     } else {
       for (int i = i0 + threadIdx.x; i < i1; i += 256) {
         const Pair p = f(base + i, c);
@@ -240,19 +313,21 @@ __global__ __launch_bounds__(256) void colreduce_nchw_kernel(F f, int outer, int
   }
 }
 
-__global__ void bn_finalize_stats_kernel(const double *__restrict__ part, int nchunks, int C, double count, float eps,
+template <class G>
+__global__ void bn_finalize_stats_kernel(const double *__restrict__ part, int nchunks, int C, G g, float eps,
                                          float momentum, float *__restrict__ mean_out, float *__restrict__ rstd_out,
                                          float *__restrict__ rm, float *__restrict__ rv, long long *__restrict__ batches) {
   // one wave per channel: lanes take the chunk partials k = lane, lane+64, ... in order, then a fixed shuffle tree
   const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (batches && blockIdx.x == 0 && threadIdx.x == 0) *batches += 1;          // nn.BatchNorm's num_batches_tracked: no launch of its own
   if (c >= C) return;
+  const double count = g.count(lane);
   double s = 0.0, ss = 0.0;
   for (int k = lane; k < nchunks; k += 64) { s += part[((size_t)k * C + c) * 2]; ss += part[((size_t)k * C + c) * 2 + 1]; }
   s = wave_sum_d(s); ss = wave_sum_d(ss);
   if (lane != 0) return;
-  const double mean = s / count;
-  double var = ss / count - mean * mean;
+  const double mean = count > 0.0 ? s / count : 0.0;                          // (a batch of empty utterances; never with AllFrames)
+  double var = count > 0.0 ? ss / count - mean * mean : 0.0;
   if (var < 0.0) var = 0.0;
   mean_out[c] = (float)mean;
   rstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -273,30 +348,58 @@ __global__ void bn_sum_chunks_kernel(const double *__restrict__ part, int nchunk
   if (lane == 0) { sums[c * 2] = s; sums[c * 2 + 1] = ss; }
 }
 
-__global__ void bn_finalize_bwd_kernel(const double *__restrict__ part, int nchunks, int C, float *__restrict__ dgamma,
+template <class G>
+__global__ void bn_finalize_bwd_kernel(const double *__restrict__ part, int nchunks, int C, G g, float *__restrict__ dgamma,
                                        float *__restrict__ dbeta, float *__restrict__ sums /*[2*C]: sum dy, sum dy*xhat*/,
                                        float beta_acc) {
   const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= C) return;
+  const double count = g.count(lane);
   double s = 0.0, ss = 0.0;
   for (int k = lane; k < nchunks; k += 64) { s += part[((size_t)k * C + c) * 2]; ss += part[((size_t)k * C + c) * 2 + 1]; }
   s = wave_sum_d(s); ss = wave_sum_d(ss);
   if (lane != 0) return;
+  // 1 / n for the dx pass goes behind the sums where n is known on the device only; the dense workspace (ctcn_bn_ws_bytes) has no such
+  // word, and the dense dx pass takes 1 / n from the host
+  if constexpr (!G::kAll) { if (c == 0) sums[2 * C] = count > 0.0 ? (float)(1.0 / count) : 0.0f; }
   sums[c] = (float)s; sums[C + c] = (float)ss;
   if (dbeta) dbeta[c] = (float)s + (beta_acc != 0.0f ? beta_acc * dbeta[c] : 0.0f);
   if (dgamma) dgamma[c] = (float)ss + (beta_acc != 0.0f ? beta_acc * dgamma[c] : 0.0f);
 }
 
-// y = (x - mean)*rstd*gamma + beta  [relu]
-__global__ void bn_apply_kernel(const float *__restrict__ x, float *__restrict__ y, const float *__restrict__ gamma,
-                                const float *__restrict__ beta, const float *__restrict__ mean, const float *__restrict__ rstd_or_var,
-                                float eps, int var_is_variance, size_t total, int C, int inner, int relu) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int c = (int)((i / inner) % C);
-    const float rs = var_is_variance ? 1.0f / sqrtf(rstd_or_var[c] + eps) : rstd_or_var[c];
-    float v = bn_value(x[i], mean[c], rs, gamma[c], beta[c]);
-    if (relu) v = fmaxf(v, 0.0f);
-    y[i] = v;
+// The streaming passes: a thread takes V (4 or 1) consecutive elements.  V == 4 needs 16-B aligned tensors and C % 4 == 0 (inner == 1) or
+// inner % 4 == 0 (NCHW), so that a group lies in one row / one plane.  G::valid_mask: bit e set iff element i0 + e is valid.
+template <int V>
+__device__ __forceinline__ void load_valid(const float *__restrict__ p, size_t i0, unsigned m, float (&v)[V]) {
+  if (V == 4 && m == 15u) { const f32x4 q = *reinterpret_cast<const f32x4 *>(p + i0); v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3]; return; }
+#pragma unroll
+  for (int e = 0; e < V; ++e) v[e] = (m >> e & 1u) ? p[i0 + e] : 0.0f;
+}
+template <int V>
+__device__ __forceinline__ void store_all(float *__restrict__ p, size_t i0, const float (&v)[V]) {
+  if (V == 4) { f32x4 q; q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; q[3] = v[3]; *reinterpret_cast<f32x4 *>(p + i0) = q; }
+  else p[i0] = v[0];
+}
+
+// y = (x - mean)*rstd*gamma + beta  [relu]; 0 at invalid elements
+template <int V, class G>
+__global__ void bn_apply_kernel(const float *__restrict__ x, float *__restrict__ y, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                const float *__restrict__ mean, const float *__restrict__ rstd_or_var, float eps, int var_is_variance, G g,
+                                size_t ngroups, int C, int inner, int relu) {
+  for (size_t gi = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gi < ngroups; gi += (size_t)gridDim.x * blockDim.x) {
+    int c0;
+    const unsigned m = g.template valid_mask<V>(gi * V, C, inner, c0);
+    float xv[V], o[V];
+    load_valid<V>(x, gi * V, m, xv);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int c = inner == 1 ? c0 + e : c0;
+      const float rs = var_is_variance ? 1.0f / sqrtf(rstd_or_var[c] + eps) : rstd_or_var[c];
+      float v = bn_value(xv[e], mean[c], rs, gamma[c], beta[c]);
+      if (relu) v = fmaxf(v, 0.0f);
+      o[e] = (m >> e & 1u) ? v : 0.0f;
+    }
+    store_all<V>(y, gi * V, o);
   }
 }
 
@@ -380,30 +483,52 @@ __global__ void bn_dx_drop_kernel(const float *__restrict__ x, const float *__re
   }
 }
 
-static void launch_bn_apply(hipStream_t st, const float *x, float *y, const float *gamma, const float *beta, const float *mean, const float *rstd_or_var,
-                            float eps, int var_is_variance, size_t total, int C, int inner, int relu) {
-  const bool al = ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)mean | (uintptr_t)rstd_or_var) & 15) == 0);
-  if (inner == 1 && C % 4 == 0 && al) {
-    const size_t total4 = total / 4;
-    const int blocks = (int)std::min((size_t)4096, ceil_div_z(total4, 256));
-    hipLaunchKernelGGL(bn_apply_rows4_kernel, dim3(blocks), dim3(256), 0, st, x, y, gamma, beta, mean, rstd_or_var, eps, var_is_variance, total4, C / 4, relu);
+// 4: the 16-B form of the streaming passes applies
+int stream_vec(int C, int inner, uintptr_t ptrs) { return (ptrs & 15) == 0 && (inner == 1 ? C % 4 == 0 : inner % 4 == 0) ? 4 : 1; }
+int stream_blocks(size_t ngroups) { return (int)std::min((size_t)4096, std::max((size_t)1, ceil_div_z(ngroups, 256))); }
+
+// Which 16-B form, if any: all frames -- the rows4 kernel, which wants rows (NCHW stays on V = 1) and the per-channel vectors aligned as well;
+// with lengths -- V = 4 in either layout, x and y aligned.
+template <class G>
+void launch_bn_apply(hipStream_t st, const G &g, const float *x, float *y, const float *gamma, const float *beta, const float *mean,
+                     const float *rstd_or_var, float eps, int var_is_variance, size_t total, int C, int inner, int relu) {
+  const uintptr_t io = (uintptr_t)x | (uintptr_t)y, ch = (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)mean | (uintptr_t)rstd_or_var;
+  if (G::kAll ? inner == 1 && stream_vec(C, 1, io | ch) == 4 : stream_vec(C, inner, io) == 4) {
+    if constexpr (G::kAll)
+      hipLaunchKernelGGL(bn_apply_rows4_kernel, dim3(stream_blocks(total / 4)), dim3(256), 0, st, x, y, gamma, beta, mean, rstd_or_var, eps, var_is_variance,
+                         total / 4, C / 4, relu);
+    else
+      hipLaunchKernelGGL((bn_apply_kernel<4, G>), dim3(stream_blocks(total / 4)), dim3(256), 0, st, x, y, gamma, beta, mean, rstd_or_var, eps,
+                         var_is_variance, g, total / 4, C, inner, relu);
   } else {
-    const int blocks = (int)std::min((size_t)4096, ceil_div_z(total, 256));
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, st, x, y, gamma, beta, mean, rstd_or_var, eps, var_is_variance, total, C, inner, relu);
+    hipLaunchKernelGGL((bn_apply_kernel<1, G>), dim3(stream_blocks(total)), dim3(256), 0, st, x, y, gamma, beta, mean, rstd_or_var, eps, var_is_variance, g,
+                       total, C, inner, relu);
   }
 }
 
-// dx = gamma*rstd*(dy' - sum(dy')/N - xhat*sum(dy' xhat)/N)
-__global__ void bn_dx_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ dy,
-                             const float *__restrict__ gamma, const float *__restrict__ mean, const float *__restrict__ rstd,
-                             const float *__restrict__ sums, float *__restrict__ dx, size_t total, int C, int inner, float inv_n,
-                             int relu) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int c = (int)((i / inner) % C);
-    float g = dy[i];
-    if (relu && !(y[i] > 0.0f)) g = 0.0f;
-    const float xh = (x[i] - mean[c]) * rstd[c];
-    dx[i] = bn_dx_value(g, xh, gamma[c], rstd[c], sums[c], sums[C + c], inv_n);
+// dx = gamma*rstd*(dy' - sum(dy')/N - xhat*sum(dy' xhat)/N); 0 at invalid elements
+template <int V, class G>
+__global__ void bn_dx_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *dy, const float *__restrict__ gamma,
+                             const float *__restrict__ mean, const float *__restrict__ rstd, const float *__restrict__ sums, float *dx, G g,
+                             size_t ngroups, int C, int inner, int relu) {
+  const float inv_n = g.inv_n(sums, C);
+  for (size_t gi = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gi < ngroups; gi += (size_t)gridDim.x * blockDim.x) {
+    int c0;
+    const unsigned m = g.template valid_mask<V>(gi * V, C, inner, c0);
+    float xv[V], gv[V], yv[V], o[V];
+    load_valid<V>(x, gi * V, m, xv);
+    load_valid<V>(dy, gi * V, m, gv);
+    if (relu) load_valid<V>(y, gi * V, m, yv);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int c = inner == 1 ? c0 + e : c0;
+      float gr = gv[e];
+      if (relu && !(yv[e] > 0.0f)) gr = 0.0f;
+      const float xh = (xv[e] - mean[c]) * rstd[c];
+      const float d = bn_dx_value(gr, xh, gamma[c], rstd[c], sums[c], sums[C + c], inv_n);
+      o[e] = (m >> e & 1u) ? d : 0.0f;
+    }
+    store_all<V>(dx, gi * V, o);
   }
 }
 
@@ -434,17 +559,21 @@ __global__ void bn_dx_rows4_kernel(const float *__restrict__ x, const float *__r
     reinterpret_cast<float4 *>(dx)[i] = make_float4(o[0], o[1], o[2], o[3]);
   }
 }
-static void launch_bn_dx(hipStream_t st, const float *x, const float *y, const float *dy, const float *gamma, const float *mean, const float *rstd,
-                         const float *sums, float *dx, size_t total, int C, int inner, float inv_n, int relu) {
-  const bool al = ((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)gamma | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)sums |
-                     (relu ? (uintptr_t)y : 0)) & 15) == 0);
-  if (inner == 1 && C % 4 == 0 && al) {
-    const size_t total4 = total / 4;
-    hipLaunchKernelGGL(bn_dx_rows4_kernel, dim3((int)std::min((size_t)4096, ceil_div_z(total4, 256))), dim3(256), 0, st, x, y, dy, gamma, mean, rstd, sums, dx,
-                       total4, C / 4, inv_n, relu);
+// (launch_bn_apply's rule; the rows4 kernel loads sums as vectors too, and y is read only for the relu mask)
+template <class G>
+void launch_bn_dx(hipStream_t st, const G &g, const float *x, const float *y, const float *dy, const float *gamma, const float *mean, const float *rstd,
+                  const float *sums, float *dx, size_t total, int C, int inner, int relu) {
+  const uintptr_t io = (uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (relu ? (uintptr_t)y : 0);
+  const uintptr_t ch = (uintptr_t)gamma | (uintptr_t)mean | (uintptr_t)rstd | (uintptr_t)sums;
+  if (G::kAll ? inner == 1 && stream_vec(C, 1, io | ch) == 4 : stream_vec(C, inner, io) == 4) {
+    if constexpr (G::kAll)
+      hipLaunchKernelGGL(bn_dx_rows4_kernel, dim3(stream_blocks(total / 4)), dim3(256), 0, st, x, y, dy, gamma, mean, rstd, sums, dx, total / 4, C / 4,
+                         g.inv_n_, relu);
+    else
+      hipLaunchKernelGGL((bn_dx_kernel<4, G>), dim3(stream_blocks(total / 4)), dim3(256), 0, st, x, y, dy, gamma, mean, rstd, sums, dx, g, total / 4, C,
+                         inner, relu);
   } else {
-    hipLaunchKernelGGL(bn_dx_kernel, dim3((int)std::min((size_t)4096, ceil_div_z(total, 256))), dim3(256), 0, st, x, y, dy, gamma, mean, rstd, sums, dx, total, C,
-                       inner, inv_n, relu);
+    hipLaunchKernelGGL((bn_dx_kernel<1, G>), dim3(stream_blocks(total)), dim3(256), 0, st, x, y, dy, gamma, mean, rstd, sums, dx, g, total, C, inner, relu);
   }
 }
 
@@ -473,54 +602,141 @@ NchwChunks chunks_nchw(int outer, int C, int inner) {
   return k;
 }
 
-template <class F>
-int launch_reduce(F f, int outer, int C, int inner, double *part, int *nchunks_out, hipStream_t st) {
+template <class F, class G>
+void launch_reduce(F f, const G &g, int outer, int C, int inner, double *part, int *nchunks_out, hipStream_t st) {
   if (inner == 1) {
     const int n = chunks_rows(outer, C);
     const int rpc = ceil_div(outer, n);
     const int nn = ceil_div(outer, rpc);
     if (C % 4 == 0 && f.aligned16() && ctcn_get_option("bn_rows4") != 0)
-      hipLaunchKernelGGL((colreduce_rows4_kernel<F>), dim3(ceil_div(C, 64), nn), dim3(256), 0, st, f, outer, C, rpc, part);
+      hipLaunchKernelGGL((colreduce_rows4_kernel<F, G>), dim3(ceil_div(C, 64), nn), dim3(256), 0, st, f, g, outer, C, rpc, part);
     else
-      hipLaunchKernelGGL((colreduce_rows_kernel<F>), dim3(ceil_div(C, 64), nn), dim3(256), 0, st, f, outer, C, rpc, part);
+      hipLaunchKernelGGL((colreduce_rows_kernel<F, G>), dim3(ceil_div(C, 64), nn), dim3(256), 0, st, f, g, outer, C, rpc, part);
     *nchunks_out = nn;
   } else {
     const NchwChunks k = chunks_nchw(outer, C, inner);
-    const int nn = k.n;
     const int vec = inner % 4 == 0 && f.aligned16() ? 1 : 0;
-    hipLaunchKernelGGL((colreduce_nchw_kernel<F>), dim3(C, nn), dim3(256), 0, st, f, outer, C, inner, k.opc, k.ich, k.ilen, vec, part);
-    *nchunks_out = nn;
+    hipLaunchKernelGGL((colreduce_nchw_kernel<F, G>), dim3(C, k.n), dim3(256), 0, st, f, g, outer, C, inner, k.opc, k.ich, k.ilen, vec, part);
+    *nchunks_out = k.n;
   }
-  return 0;
 }
+
+template <int V>
+__global__ void mask_frames_kernel(const float *x, float *y, Frames g, size_t ngroups, int C, int inner) {
+  for (size_t gi = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gi < ngroups; gi += (size_t)gridDim.x * blockDim.x) {
+    int c0;
+    const unsigned m = g.valid_mask<V>(gi * V, C, inner, c0);
+    float v[V];
+    load_valid<V>(x, gi * V, m, v);
+    store_all<V>(y, gi * V, v);
+  }
+}
+
+bool dims_ok(int outer, int C, int inner) { return outer > 0 && C > 0 && inner > 0; }
+bool geom_ok(int outer, int C, int inner, const int *lens, int batch, int frame, Frames *g) {
+  if (!lens || !dims_ok(outer, C, inner) || batch <= 0 || frame <= 0) return false;
+  if (inner == 1 ? (frame != 1 || outer % batch != 0) : (batch != outer || inner % frame != 0)) return false;
+  *g = Frames{lens, batch, frame, inner == 1 ? outer / batch : inner / frame};
+  return true;
+}
+
+// The workspace: [(nmax + 1) x C chunk partials of two doubles | pad to 256 B | float sums[2 * C] | with lengths: the 1 / n word].  Offset of `sums`:
+size_t ws_part_bytes(int outer, int C, int inner) {
+  const int nmax = inner == 1 ? chunks_rows(outer, C) : chunks_nchw(outer, C, inner).n;
+  return align_up((size_t)(nmax + 1) * C * 2 * sizeof(double), 256);
+}
+template <class G>
+size_t ws_need(int outer, int C, int inner) { return G::kAll ? ctcn_bn_ws_bytes(outer, C, inner) : ctcn_bn_masked_ws_bytes(outer, C, inner); }
+
+// The drivers behind the extern "C" entry points.  `who` is the public function that was called (users and tests read the error strings);
+// `geom`: what the caller found about its dims (and, with lengths, the geometry) while it built the policy.
+
+// partials -> mean / rstd / running statistics, then y (with a DropSpec: the dropped y)
+template <class G>
+int bn_stats_apply(const G &g, const double *part, int nchunks, const float *x, float *y, const float *gamma, const float *beta, float *running_mean,
+                   float *running_var, float *save_mean, float *save_rstd, int outer, int C, int inner, float eps, float momentum, int relu,
+                   hipStream_t st, long long *num_batches_tracked, const DropSpec *drop) {
+  hipLaunchKernelGGL(bn_finalize_stats_kernel<G>, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, g, eps, momentum, save_mean, save_rstd,
+                     running_mean, running_var, num_batches_tracked);
+  CTCN_LAUNCH_CHECK();
+  const size_t total = (size_t)outer * C * inner;
+  if (drop)
+    hipLaunchKernelGGL(bn_apply_drop_kernel, dim3(stream_blocks((total + 3) / 4)), dim3(256), 0, st, x, y, gamma, beta, save_mean, save_rstd, total, C, inner,
+                       relu, *drop);
+  else
+    launch_bn_apply(st, g, x, y, gamma, beta, save_mean, save_rstd, eps, 0, total, C, inner, relu);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+template <class G>
+int bn_forward(const char *who, const G &g, bool geom, const float *x, float *y, const float *gamma, const float *beta, float *running_mean,
+               float *running_var, float *save_mean, float *save_rstd, int outer, int C, int inner, float eps, float momentum, int relu, void *ws,
+               size_t ws_bytes, void *stream, long long *num_batches_tracked, const DropSpec *drop) {
+  CTCN_REQUIRE(x && y && gamma && beta && save_mean && save_rstd && ws, "%s: null pointer", who);
+  CTCN_REQUIRE(geom, "%s: bad dims%s", who, G::kAll ? "" : " / geometry");
+  CTCN_REQUIRE(!drop || (drop->p > 0.0f && drop->p < 1.0f), "%s: p=%f outside (0,1)", who, (double)drop->p);
+  if (ws_bytes < ws_need<G>(outer, C, inner)) { ctcn_set_error("%s: workspace too small", who); return CTCN_EWORKSPACE; }
+  hipStream_t st = (hipStream_t)stream;
+  double *part = (double *)ws;
+  int nchunks = 0;
+  launch_reduce(StatVal{x}, g, outer, C, inner, part, &nchunks, st);
+  CTCN_LAUNCH_CHECK();
+  return bn_stats_apply(g, part, nchunks, x, y, gamma, beta, running_mean, running_var, save_mean, save_rstd, outer, C, inner, eps, momentum, relu, st,
+                        num_batches_tracked, drop);
+}
+
+// with a DropSpec: dy is the gradient of the dropped output, y is not read
+template <class G>
+int bn_backward(const char *who, const G &g, bool geom, const float *x, const float *y, const float *dy, const float *gamma, const float *save_mean,
+                const float *save_rstd, float *dx, float *dgamma, float *dbeta, int outer, int C, int inner, int relu, float beta_acc, void *ws,
+                size_t ws_bytes, void *stream, const DropSpec *drop) {
+  CTCN_REQUIRE(x && dy && gamma && save_mean && save_rstd && dx && ws && (!drop || drop->beta), "%s: null pointer", who);
+  CTCN_REQUIRE(!relu || y || drop, "%s: y required for the fused relu mask", who);
+  CTCN_REQUIRE(geom, "%s: bad dims%s", who, G::kAll ? "" : " / geometry");
+  CTCN_REQUIRE(!drop || (drop->p > 0.0f && drop->p < 1.0f), "%s: p=%f outside (0,1)", who, (double)drop->p);
+  if (ws_bytes < ws_need<G>(outer, C, inner)) { ctcn_set_error("%s: workspace too small", who); return CTCN_EWORKSPACE; }
+  hipStream_t st = (hipStream_t)stream;
+  double *part = (double *)ws;
+  float *sums = (float *)((char *)ws + ws_part_bytes(outer, C, inner));
+  int nchunks = 0;
+  launch_reduce(BwdVal{x, y, dy, save_mean, save_rstd, relu, drop ? *drop : k_no_drop}, g, outer, C, inner, part, &nchunks, st);
+  CTCN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(bn_finalize_bwd_kernel<G>, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, g, dgamma, dbeta, sums, beta_acc);
+  CTCN_LAUNCH_CHECK();
+  const size_t total = (size_t)outer * C * inner;
+  if constexpr (G::kAll) {          // (the fused dropout pair has no length-aware form)
+    if (drop) {
+      hipLaunchKernelGGL(bn_dx_drop_kernel, dim3(stream_blocks((total + 3) / 4)), dim3(256), 0, st, x, dy, gamma, drop->beta, save_mean, save_rstd, sums, dx,
+                         total, C, inner, g.inv_n_, relu, *drop);
+      CTCN_LAUNCH_CHECK();
+      return CTCN_OK;
+    }
+  }
+  launch_bn_dx(st, g, x, y, dy, gamma, save_mean, save_rstd, sums, dx, total, C, inner, relu);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+DropSpec drop_spec(float p, uint64_t seed, uint64_t offset, const float *gamma, const float *beta) { return {p, 1.0f / (1.0f - p), seed, offset, gamma, beta}; }
 
 }  // namespace
 
 extern "C" size_t ctcn_bn_ws_bytes(int outer, int C, int inner) {
-  if (outer <= 0 || C <= 0 || inner <= 0) return 0;                  // (as the other *_ws_bytes queries answer bad dims; the chunk planners divide by them)
-  const int n = inner == 1 ? chunks_rows(outer, C) : chunks_nchw(outer, C, inner).n;
-  return align_up((size_t)(n + 1) * C * 2 * sizeof(double), 256) + (size_t)2 * C * sizeof(float);
+  if (!dims_ok(outer, C, inner)) return 0;                  // (as the other *_ws_bytes queries answer bad dims; the chunk planners divide by them)
+  return ws_part_bytes(outer, C, inner) + (size_t)2 * C * sizeof(float);
+}
+
+extern "C" size_t ctcn_bn_masked_ws_bytes(int outer, int C, int inner) {
+  const size_t n = ctcn_bn_ws_bytes(outer, C, inner);
+  return n ? n + 256 : 0;                       // (+ the 1 / n word behind the two float sums)
 }
 
 extern "C" int ctcn_bn_fwd_train(const float *x, float *y, const float *gamma, const float *beta, float *running_mean,
                                  float *running_var, float *save_mean, float *save_rstd, int outer, int C, int inner,
                                  float eps, float momentum, int relu, void *ws, size_t ws_bytes, void *stream, long long *num_batches_tracked) {
-  CTCN_REQUIRE(x && y && gamma && beta && save_mean && save_rstd && ws, "ctcn_bn_fwd_train: null pointer");
-  CTCN_REQUIRE(outer > 0 && C > 0 && inner > 0, "ctcn_bn_fwd_train: bad dims");
-  if (ws_bytes < ctcn_bn_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_fwd_train: workspace too small"); return CTCN_EWORKSPACE; }
-  hipStream_t st = (hipStream_t)stream;
-  double *part = (double *)ws;
-  int nchunks = 0;
-  launch_reduce(StatVal{x}, outer, C, inner, part, &nchunks, st);
-  CTCN_LAUNCH_CHECK();
-  const double count = (double)outer * inner;
-  hipLaunchKernelGGL(bn_finalize_stats_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, count, eps, momentum,
-                     save_mean, save_rstd, running_mean, running_var, num_batches_tracked);
-  CTCN_LAUNCH_CHECK();
-  const size_t total = (size_t)outer * C * inner;
-  launch_bn_apply(st, x, y, gamma, beta, save_mean, save_rstd, eps, 0, total, C, inner, relu);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
+  return bn_forward("ctcn_bn_fwd_train", all_frames((double)outer * inner), dims_ok(outer, C, inner), x, y, gamma, beta, running_mean, running_var,
+                    save_mean, save_rstd, outer, C, inner, eps, momentum, relu, ws, ws_bytes, stream, num_batches_tracked, nullptr);
 }
 
 // BatchNorm (training statistics) + ReLU + dropout in one apply pass (LayerCNN: conv -> BN -> ReLU -> Dropout).  y_drop receives
@@ -528,46 +744,74 @@ extern "C" int ctcn_bn_fwd_train(const float *x, float *y, const float *gamma, c
 extern "C" int ctcn_bn_fwd_train_dropout(const float *x, float *y_drop, const float *gamma, const float *beta, float *running_mean, float *running_var,
                                          float *save_mean, float *save_rstd, int outer, int C, int inner, float eps, float momentum, int relu, void *ws,
                                          size_t ws_bytes, void *stream, long long *num_batches_tracked, float p, uint64_t seed, uint64_t offset) {
-  CTCN_REQUIRE(x && y_drop && gamma && beta && save_mean && save_rstd && ws, "ctcn_bn_fwd_train_dropout: null pointer");
-  CTCN_REQUIRE(outer > 0 && C > 0 && inner > 0, "ctcn_bn_fwd_train_dropout: bad dims");
-  CTCN_REQUIRE(p > 0.0f && p < 1.0f, "ctcn_bn_fwd_train_dropout: p=%f outside (0,1)", (double)p);
-  if (ws_bytes < ctcn_bn_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_fwd_train_dropout: workspace too small"); return CTCN_EWORKSPACE; }
-  hipStream_t st = (hipStream_t)stream;
-  double *part = (double *)ws;
-  int nchunks = 0;
-  launch_reduce(StatVal{x}, outer, C, inner, part, &nchunks, st);
-  CTCN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_finalize_stats_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, (double)outer * inner, eps, momentum,
-                     save_mean, save_rstd, running_mean, running_var, num_batches_tracked);
-  CTCN_LAUNCH_CHECK();
-  const size_t total = (size_t)outer * C * inner;
-  const DropSpec d = {p, 1.0f / (1.0f - p), seed, offset, gamma, beta};
-  hipLaunchKernelGGL(bn_apply_drop_kernel, dim3((int)std::min((size_t)4096, ceil_div_z((total + 3) / 4, 256))), dim3(256), 0, st, x, y_drop, gamma, beta,
-                     save_mean, save_rstd, total, C, inner, relu, d);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
+  const DropSpec d = drop_spec(p, seed, offset, gamma, beta);
+  return bn_forward("ctcn_bn_fwd_train_dropout", all_frames((double)outer * inner), dims_ok(outer, C, inner), x, y_drop, gamma, beta, running_mean,
+                    running_var, save_mean, save_rstd, outer, C, inner, eps, momentum, relu, ws, ws_bytes, stream, num_batches_tracked, &d);
+}
+
+extern "C" int ctcn_bn_fwd_train_masked(const float *x, float *y, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                                        float *save_mean, float *save_rstd, const int *lens, int batch, int frame, int outer, int C, int inner,
+                                        float eps, float momentum, int relu, void *ws, size_t ws_bytes, void *stream, long long *num_batches_tracked) {
+  Frames g = {};
+  const bool geom = geom_ok(outer, C, inner, lens, batch, frame, &g);
+  return bn_forward("ctcn_bn_fwd_train_masked", g, geom, x, y, gamma, beta, running_mean, running_var, save_mean, save_rstd, outer, C, inner, eps,
+                    momentum, relu, ws, ws_bytes, stream, num_batches_tracked, nullptr);
+}
+
+extern "C" int ctcn_bn_bwd(const float *x, const float *y, const float *dy, const float *gamma, const float *save_mean,
+                           const float *save_rstd, float *dx, float *dgamma, float *dbeta, int outer, int C, int inner,
+                           int relu, float beta_acc, void *ws, size_t ws_bytes, void *stream) {
+  return bn_backward("ctcn_bn_bwd", all_frames((double)outer * inner), dims_ok(outer, C, inner), x, y, dy, gamma, save_mean, save_rstd, dx, dgamma, dbeta,
+                     outer, C, inner, relu, beta_acc, ws, ws_bytes, stream, nullptr);
 }
 
 extern "C" int ctcn_bn_bwd_dropout(const float *x, const float *dy_drop, const float *gamma, const float *beta, const float *save_mean,
                                    const float *save_rstd, float *dx, float *dgamma, float *dbeta, int outer, int C, int inner, int relu, float beta_acc,
                                    void *ws, size_t ws_bytes, void *stream, float p, uint64_t seed, uint64_t offset) {
-  CTCN_REQUIRE(x && dy_drop && gamma && beta && save_mean && save_rstd && dx && ws, "ctcn_bn_bwd_dropout: null pointer");
-  CTCN_REQUIRE(outer > 0 && C > 0 && inner > 0, "ctcn_bn_bwd_dropout: bad dims");
-  CTCN_REQUIRE(p > 0.0f && p < 1.0f, "ctcn_bn_bwd_dropout: p=%f outside (0,1)", (double)p);
-  if (ws_bytes < ctcn_bn_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_bwd_dropout: workspace too small"); return CTCN_EWORKSPACE; }
-  hipStream_t st = (hipStream_t)stream;
-  double *part = (double *)ws;
-  const int nmax = inner == 1 ? chunks_rows(outer, C) : chunks_nchw(outer, C, inner).n;
-  float *sums = (float *)((char *)ws + align_up((size_t)(nmax + 1) * C * 2 * sizeof(double), 256));
-  const DropSpec d = {p, 1.0f / (1.0f - p), seed, offset, gamma, beta};
-  int nchunks = 0;
-  launch_reduce(BwdVal{x, nullptr, dy_drop, save_mean, save_rstd, relu, d}, outer, C, inner, part, &nchunks, st);
+  const DropSpec d = drop_spec(p, seed, offset, gamma, beta);
+  return bn_backward("ctcn_bn_bwd_dropout", all_frames((double)outer * inner), dims_ok(outer, C, inner), x, nullptr, dy_drop, gamma, save_mean, save_rstd,
+                     dx, dgamma, dbeta, outer, C, inner, relu, beta_acc, ws, ws_bytes, stream, &d);
+}
+
+extern "C" int ctcn_bn_bwd_masked(const float *x, const float *y, const float *dy, const float *gamma, const float *save_mean, const float *save_rstd,
+                                  float *dx, float *dgamma, float *dbeta, const int *lens, int batch, int frame, int outer, int C, int inner, int relu,
+                                  float beta_acc, void *ws, size_t ws_bytes, void *stream) {
+  Frames g = {};
+  const bool geom = geom_ok(outer, C, inner, lens, batch, frame, &g);
+  return bn_backward("ctcn_bn_bwd_masked", g, geom, x, y, dy, gamma, save_mean, save_rstd, dx, dgamma, dbeta, outer, C, inner, relu, beta_acc, ws,
+                     ws_bytes, stream, nullptr);
+}
+
+extern "C" int ctcn_bn_fwd_eval(const float *x, float *y, const float *gamma, const float *beta, const float *running_mean,
+                                const float *running_var, int outer, int C, int inner, float eps, int relu, void *stream) {
+  CTCN_REQUIRE(x && y && gamma && beta && running_mean && running_var, "ctcn_bn_fwd_eval: null pointer");
+  CTCN_REQUIRE(dims_ok(outer, C, inner), "ctcn_bn_fwd_eval: bad dims");
+  launch_bn_apply((hipStream_t)stream, all_frames((double)outer * inner), x, y, gamma, beta, running_mean, running_var, eps, 1, (size_t)outer * C * inner, C,
+                  inner, relu);
   CTCN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, dgamma, dbeta, sums, beta_acc);
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_bn_fwd_eval_masked(const float *x, float *y, const float *gamma, const float *beta, const float *running_mean,
+                                       const float *running_var, const int *lens, int batch, int frame, int outer, int C, int inner, float eps,
+                                       int relu, void *stream) {
+  CTCN_REQUIRE(x && y && gamma && beta && running_mean && running_var, "ctcn_bn_fwd_eval_masked: null pointer");
+  Frames g;
+  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_bn_fwd_eval_masked: bad dims / geometry");
+  launch_bn_apply((hipStream_t)stream, g, x, y, gamma, beta, running_mean, running_var, eps, 1, (size_t)outer * C * inner, C, inner, relu);
   CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_mask_frames(const float *x, float *y, const int *lens, int batch, int frame, int outer, int C, int inner, void *stream) {
+  CTCN_REQUIRE(x && y, "ctcn_mask_frames: null pointer");
+  Frames g;
+  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_mask_frames: bad dims / geometry");
   const size_t total = (size_t)outer * C * inner;
-  hipLaunchKernelGGL(bn_dx_drop_kernel, dim3((int)std::min((size_t)4096, ceil_div_z((total + 3) / 4, 256))), dim3(256), 0, st, x, dy_drop, gamma, beta,
-                     save_mean, save_rstd, sums, dx, total, C, inner, (float)(1.0 / ((double)outer * inner)), relu, d);
+  if (stream_vec(C, inner, (uintptr_t)x | (uintptr_t)y) == 4)
+    hipLaunchKernelGGL(mask_frames_kernel<4>, dim3(stream_blocks(total / 4)), dim3(256), 0, (hipStream_t)stream, x, y, g, total / 4, C, inner);
+  else
+    hipLaunchKernelGGL(mask_frames_kernel<1>, dim3(stream_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, g, total, C, inner);
   CTCN_LAUNCH_CHECK();
   return CTCN_OK;
 }
@@ -577,11 +821,11 @@ extern "C" int ctcn_bn_bwd_dropout(const float *x, const float *dy_drop, const f
 // normalises with the global count.  With one rank the result equals ctcn_bn_fwd_train / ctcn_bn_bwd exactly.
 extern "C" int ctcn_bn_fwd_sums(const float *x, double *sums, int outer, int C, int inner, void *ws, size_t ws_bytes, void *stream) {
   CTCN_REQUIRE(x && sums && ws, "ctcn_bn_fwd_sums: null pointer");
-  CTCN_REQUIRE(outer > 0 && C > 0 && inner > 0, "ctcn_bn_fwd_sums: bad dims");
+  CTCN_REQUIRE(dims_ok(outer, C, inner), "ctcn_bn_fwd_sums: bad dims");
   if (ws_bytes < ctcn_bn_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_fwd_sums: workspace too small"); return CTCN_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   int nchunks = 0;
-  launch_reduce(StatVal{x}, outer, C, inner, (double *)ws, &nchunks, st);
+  launch_reduce(StatVal{x}, all_frames((double)outer * inner), outer, C, inner, (double *)ws, &nchunks, st);
   CTCN_LAUNCH_CHECK();
   hipLaunchKernelGGL(bn_sum_chunks_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, (const double *)ws, nchunks, C, sums);
   CTCN_LAUNCH_CHECK();
@@ -592,26 +836,20 @@ extern "C" int ctcn_bn_fwd_finish(const float *x, float *y, const float *gamma, 
                                   float *save_mean, float *save_rstd, const double *sums, double count_total, int outer, int C, int inner,
                                   float eps, float momentum, int relu, void *stream, long long *num_batches_tracked) {
   CTCN_REQUIRE(x && y && gamma && beta && save_mean && save_rstd && sums, "ctcn_bn_fwd_finish: null pointer");
-  CTCN_REQUIRE(outer > 0 && C > 0 && inner > 0 && count_total >= (double)outer * inner, "ctcn_bn_fwd_finish: bad dims / count");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_finalize_stats_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, sums, 1, C, count_total, eps, momentum, save_mean,
-                     save_rstd, running_mean, running_var, num_batches_tracked);
-  CTCN_LAUNCH_CHECK();
-  const size_t total = (size_t)outer * C * inner;
-  launch_bn_apply(st, x, y, gamma, beta, save_mean, save_rstd, eps, 0, total, C, inner, relu);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
+  CTCN_REQUIRE(dims_ok(outer, C, inner) && count_total >= (double)outer * inner, "ctcn_bn_fwd_finish: bad dims / count");
+  return bn_stats_apply(all_frames(count_total), sums, 1, x, y, gamma, beta, running_mean, running_var, save_mean, save_rstd, outer, C, inner, eps, momentum,
+                        relu, (hipStream_t)stream, num_batches_tracked, nullptr);
 }
 
 extern "C" int ctcn_bn_bwd_sums(const float *x, const float *y, const float *dy, const float *save_mean, const float *save_rstd, double *sums,
                                 int outer, int C, int inner, int relu, void *ws, size_t ws_bytes, void *stream) {
   CTCN_REQUIRE(x && dy && save_mean && save_rstd && sums && ws, "ctcn_bn_bwd_sums: null pointer");
   CTCN_REQUIRE(!relu || y, "ctcn_bn_bwd_sums: y required for the fused relu mask");
-  CTCN_REQUIRE(outer > 0 && C > 0 && inner > 0, "ctcn_bn_bwd_sums: bad dims");
+  CTCN_REQUIRE(dims_ok(outer, C, inner), "ctcn_bn_bwd_sums: bad dims");
   if (ws_bytes < ctcn_bn_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_bwd_sums: workspace too small"); return CTCN_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   int nchunks = 0;
-  launch_reduce(BwdVal{x, y, dy, save_mean, save_rstd, relu, k_no_drop}, outer, C, inner, (double *)ws, &nchunks, st);
+  launch_reduce(BwdVal{x, y, dy, save_mean, save_rstd, relu, k_no_drop}, all_frames((double)outer * inner), outer, C, inner, (double *)ws, &nchunks, st);
   CTCN_LAUNCH_CHECK();
   hipLaunchKernelGGL(bn_sum_chunks_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, (const double *)ws, nchunks, C, sums);
   CTCN_LAUNCH_CHECK();
@@ -625,427 +863,17 @@ extern "C" int ctcn_bn_bwd_finish(const float *x, const float *y, const float *d
                                   void *ws, size_t ws_bytes, void *stream) {
   CTCN_REQUIRE(x && dy && gamma && save_mean && save_rstd && dx && local_sums && global_sums && ws, "ctcn_bn_bwd_finish: null pointer");
   CTCN_REQUIRE(!relu || y, "ctcn_bn_bwd_finish: y required for the fused relu mask");
-  CTCN_REQUIRE(outer > 0 && C > 0 && inner > 0 && count_total >= (double)outer * inner, "ctcn_bn_bwd_finish: bad dims / count");
+  CTCN_REQUIRE(dims_ok(outer, C, inner) && count_total >= (double)outer * inner, "ctcn_bn_bwd_finish: bad dims / count");
   if (ws_bytes < (size_t)4 * C * sizeof(float)) { ctcn_set_error("ctcn_bn_bwd_finish: workspace too small"); return CTCN_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
+  const AllFrames g = all_frames(count_total);
   float *scratch = (float *)ws, *sums = scratch + 2 * C;
-  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, local_sums, 1, C, dgamma, dbeta, scratch, beta_acc);
-  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, global_sums, 1, C, (float *)nullptr, (float *)nullptr, sums, 0.0f);
+  hipLaunchKernelGGL(bn_finalize_bwd_kernel<AllFrames>, dim3(ceil_div(C, 4)), dim3(256), 0, st, local_sums, 1, C, g, dgamma, dbeta, scratch, beta_acc);
   CTCN_LAUNCH_CHECK();
-  const size_t total = (size_t)outer * C * inner;
-  launch_bn_dx(st, x, y, dy, gamma, save_mean, save_rstd, sums, dx, total, C, inner, (float)(1.0 / count_total), relu);
+  hipLaunchKernelGGL(bn_finalize_bwd_kernel<AllFrames>, dim3(ceil_div(C, 4)), dim3(256), 0, st, global_sums, 1, C, g, (float *)nullptr, (float *)nullptr, sums,
+                     0.0f);
   CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-extern "C" int ctcn_bn_fwd_eval(const float *x, float *y, const float *gamma, const float *beta, const float *running_mean,
-                                const float *running_var, int outer, int C, int inner, float eps, int relu, void *stream) {
-  CTCN_REQUIRE(x && y && gamma && beta && running_mean && running_var, "ctcn_bn_fwd_eval: null pointer");
-  CTCN_REQUIRE(outer > 0 && C > 0 && inner > 0, "ctcn_bn_fwd_eval: bad dims");
-  const size_t total = (size_t)outer * C * inner;
-  launch_bn_apply((hipStream_t)stream, x, y, gamma, beta, running_mean, running_var, eps, 1, total, C, inner, relu);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-extern "C" int ctcn_bn_bwd(const float *x, const float *y, const float *dy, const float *gamma, const float *save_mean,
-                           const float *save_rstd, float *dx, float *dgamma, float *dbeta, int outer, int C, int inner,
-                           int relu, float beta_acc, void *ws, size_t ws_bytes, void *stream) {
-  CTCN_REQUIRE(x && dy && gamma && save_mean && save_rstd && dx && ws, "ctcn_bn_bwd: null pointer");
-  CTCN_REQUIRE(!relu || y, "ctcn_bn_bwd: y required for the fused relu mask");
-  CTCN_REQUIRE(outer > 0 && C > 0 && inner > 0, "ctcn_bn_bwd: bad dims");
-  if (ws_bytes < ctcn_bn_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_bwd: workspace too small"); return CTCN_EWORKSPACE; }
-  hipStream_t st = (hipStream_t)stream;
-  double *part = (double *)ws;
-  const int nmax = inner == 1 ? chunks_rows(outer, C) : chunks_nchw(outer, C, inner).n;
-  float *sums = (float *)((char *)ws + align_up((size_t)(nmax + 1) * C * 2 * sizeof(double), 256));
-  int nchunks = 0;
-  launch_reduce(BwdVal{x, y, dy, save_mean, save_rstd, relu, k_no_drop}, outer, C, inner, part, &nchunks, st);
-  CTCN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, dgamma, dbeta, sums, beta_acc);
-  CTCN_LAUNCH_CHECK();
-  const size_t total = (size_t)outer * C * inner;
-  launch_bn_dx(st, x, y, dy, gamma, save_mean, save_rstd, sums, dx, total, C, inner, (float)(1.0 / ((double)outer * inner)), relu);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-// ---- length-aware BatchNorm and frame mask ---------------------------------------------------------------------------
-// Every utterance b of a padded batch has lens[b] real frames; the rest of its time axis is padding.  Validity is a function of the frame:
-//   inner == 1 (rows = T * batch, time-major):  row r is valid iff r / batch < lens[r % batch]
-//   inner  > 1 (NCHW, outer = batch, inner = T' * frame):  element i of a plane (o, c) is valid iff i / frame < lens[o]
-// The statistics, dgamma / dbeta and the two dx reduction terms run over the valid elements only, with the count n = sum(lens) * frame taken
-// on the device (no host sync); y and dx are 0 at invalid elements BY SELECT, and no pass reads x / y / dy there -- a NaN in the padding
-// cannot reach anything, and a padded row costs no read.  The chunking, the float64 partials, their fixed-order sums and the per-element
-// expressions (bn_value, bn_dx_value) are those of the kernels above: with full lengths the sums are taken over the same values in the same order.
-namespace {
-
-struct FrameGeom { const int *lens; int batch, frame, tmax; };     // tmax: frames on the time axis (lens are clamped to [0, tmax])
-
-__device__ __forceinline__ int geom_len(const FrameGeom &g, int b) { return min(max(g.lens[b], 0), g.tmax); }
-__device__ __forceinline__ bool row_valid(const FrameGeom &g, int r) { return r / g.batch < g.lens[r % g.batch]; }
-// n = sum(lens) * frame, by one whole wave (every lane receives it; integers below 2^53: exact in any order)
-__device__ __forceinline__ double geom_count(const FrameGeom &g, int lane) {
-  double n = 0.0;
-  for (int b = lane; b < g.batch; b += 64) n += (double)geom_len(g, b);
-  return wave_sum_d(n) * (double)g.frame;
-}
-
-// colreduce_rows_kernel over the valid rows
-template <class F>
-__global__ __launch_bounds__(256) void mreduce_rows_kernel(F f, FrameGeom g, int rows, int C, int rows_per_chunk, double *__restrict__ part) {
-  __shared__ double sa[4][64], sb[4][64];
-  const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cx;
-  const int r0 = blockIdx.y * rows_per_chunk, r1 = min(rows, r0 + rows_per_chunk);
-  double a = 0.0, b = 0.0;
-  if (c < C) {
-    int r = r0 + ry;
-    for (; r + 28 < r1; r += 32) {
-      Pair p[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) p[u] = row_valid(g, r + 4 * u) ? f((size_t)(r + 4 * u) * C + c, c) : Pair{0.0, 0.0};
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { a += p[u].a; b += p[u].b; }
-    }
-    for (; r < r1; r += 4) {
-      if (!row_valid(g, r)) continue;
-      const Pair p = f((size_t)r * C + c, c);
-      a += p.a; b += p.b;
-    }
-  }
-  sa[ry][cx] = a; sb[ry][cx] = b;
-  __syncthreads();
-  if (ry == 0 && c < C) {
-    a = sa[0][cx] + sa[1][cx] + sa[2][cx] + sa[3][cx];
-    b = sb[0][cx] + sb[1][cx] + sb[2][cx] + sb[3][cx];
-    part[((size_t)blockIdx.y * C + c) * 2 + 0] = a;
-    part[((size_t)blockIdx.y * C + c) * 2 + 1] = b;
-  }
-}
-
-// colreduce_rows4_kernel over the valid rows (C % 4 == 0, 16-B aligned operands): an invalid row is neither requested nor added
-template <class F>
-__global__ __launch_bounds__(256) void mreduce_rows4_kernel(F f, FrameGeom g, int rows, int C, int rows_per_chunk, double *__restrict__ part) {
-  __shared__ double sa[16][65], sb[16][65];
-  const int l16 = threadIdx.x & 15, rp = threadIdx.x >> 4;
-  const int c0 = blockIdx.x * 64 + 4 * l16;
-  const int r0 = blockIdx.y * rows_per_chunk, r1 = min(rows, r0 + rows_per_chunk);
-  double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
-  if (c0 < C && r0 < r1) {
-    const typename F::ColK k = f.colk(c0);
-    constexpr int U = F::ROWS_IN_FLIGHT;
-    for (int r = r0 + rp; r < r1; r += 16 * U) {
-      typename F::Quad q[U] = {};
-      bool v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int rr = r + 16 * u;
-        v[u] = rr < r1 && row_valid(g, rr);
-        if (v[u]) q[u] = f.load4((size_t)rr * C + c0);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (v[u]) f.cols4(q[u], k, a, b);
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { sa[rp][4 * l16 + e] = a[e]; sb[rp][4 * l16 + e] = b[e]; }
-  __syncthreads();
-  const int c = blockIdx.x * 64 + threadIdx.x;
-  if (threadIdx.x < 64 && c < C) {
-    double ta = sa[0][threadIdx.x], tb = sb[0][threadIdx.x];
-#pragma unroll
-    for (int p = 1; p < 16; ++p) { ta += sa[p][threadIdx.x]; tb += sb[p][threadIdx.x]; }
-    part[((size_t)blockIdx.y * C + c) * 2 + 0] = ta;
-    part[((size_t)blockIdx.y * C + c) * 2 + 1] = tb;
-  }
-}
-
-// colreduce_nchw_kernel over the valid prefix [0, lens[o] * frame) of every plane; the (at most three) elements behind the last whole
-// quad of the prefix are added one by one after the 16-B pieces
-template <class F>
-__global__ __launch_bounds__(256) void mreduce_nchw_kernel(F f, FrameGeom g, int outer, int C, int inner, int opc, int ich, int ilen, int vec,
-                                                           double *__restrict__ part) {
-  __shared__ double sa[4], sb[4];
-  const int c = blockIdx.x;
-  const int oc = blockIdx.y / ich, ic = blockIdx.y - oc * ich;
-  const int o0 = oc * opc, o1 = min(outer, o0 + opc);
-  const int i0 = ic * ilen;
-  double a = 0.0, b = 0.0;
-  for (int o = o0; o < o1; ++o) {
-    const size_t base = ((size_t)o * C + c) * inner;
-    const int i1 = min(min(inner, i0 + ilen), geom_len(g, o) * g.frame);
-    if (vec) {
-      const int i1v = i1 & ~3;
-      int i = i0 + threadIdx.x * 4;
-      for (; i + 3 * 1024 < i1v; i += 4096) {
-        typename F::Quad q[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) q[u] = f.load4(base + i + 1024 * u);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) f.add4(q[u], c, a, b);
-      }
-      for (; i < i1v; i += 1024) f.add4(f.load4(base + i), c, a, b);
-      if (i1v >= i0 && (int)threadIdx.x < i1 - i1v) {
-        const Pair p = f(base + i1v + threadIdx.x, c);
-        a += p.a; b += p.b;
-      }
-    } else {
-      for (int i = i0 + threadIdx.x; i < i1; i += 256) {
-        const Pair p = f(base + i, c);
-        a += p.a; b += p.b;
-      }
-    }
-  }
-  a = wave_sum_d(a); b = wave_sum_d(b);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { sa[w] = a; sb[w] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[((size_t)blockIdx.y * C + c) * 2 + 0] = sa[0] + sa[1] + sa[2] + sa[3];
-    part[((size_t)blockIdx.y * C + c) * 2 + 1] = sb[0] + sb[1] + sb[2] + sb[3];
-  }
-}
-
-// bn_finalize_stats_kernel with the count taken from the lengths
-__global__ void bn_finalize_stats_masked_kernel(const double *__restrict__ part, int nchunks, int C, FrameGeom g, float eps, float momentum,
-                                                float *__restrict__ mean_out, float *__restrict__ rstd_out, float *__restrict__ rm,
-                                                float *__restrict__ rv, long long *__restrict__ batches) {
-  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (batches && blockIdx.x == 0 && threadIdx.x == 0) *batches += 1;
-  if (c >= C) return;
-  const double count = geom_count(g, lane);
-  double s = 0.0, ss = 0.0;
-  for (int k = lane; k < nchunks; k += 64) { s += part[((size_t)k * C + c) * 2]; ss += part[((size_t)k * C + c) * 2 + 1]; }
-  s = wave_sum_d(s); ss = wave_sum_d(ss);
-  if (lane != 0) return;
-  const double mean = count > 0.0 ? s / count : 0.0;
-  double var = count > 0.0 ? ss / count - mean * mean : 0.0;
-  if (var < 0.0) var = 0.0;
-  mean_out[c] = (float)mean;
-  rstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (rm) rm[c] = (float)((1.0 - (double)momentum) * (double)rm[c] + (double)momentum * mean);
-  if (rv) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    rv[c] = (float)((1.0 - (double)momentum) * (double)rv[c] + (double)momentum * unbiased);
-  }
-}
-
-// bn_finalize_bwd_kernel; sums[2 * C] receives 1 / n for the dx pass
-__global__ void bn_finalize_bwd_masked_kernel(const double *__restrict__ part, int nchunks, int C, FrameGeom g, float *__restrict__ dgamma,
-                                              float *__restrict__ dbeta, float *__restrict__ sums, float beta_acc) {
-  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (c >= C) return;
-  const double count = geom_count(g, lane);
-  double s = 0.0, ss = 0.0;
-  for (int k = lane; k < nchunks; k += 64) { s += part[((size_t)k * C + c) * 2]; ss += part[((size_t)k * C + c) * 2 + 1]; }
-  s = wave_sum_d(s); ss = wave_sum_d(ss);
-  if (lane != 0) return;
-  if (c == 0) sums[2 * C] = count > 0.0 ? (float)(1.0 / count) : 0.0f;
-  sums[c] = (float)s; sums[C + c] = (float)ss;
-  if (dbeta) dbeta[c] = (float)s + (beta_acc != 0.0f ? beta_acc * dbeta[c] : 0.0f);
-  if (dgamma) dgamma[c] = (float)ss + (beta_acc != 0.0f ? beta_acc * dgamma[c] : 0.0f);
-}
-
-// The streaming passes: a thread takes V (4 or 1) consecutive elements.  V == 4 needs 16-B aligned tensors and C % 4 == 0 (inner == 1) or
-// inner % 4 == 0 (NCHW), so that a group lies in one row / one plane.  valid_mask: bit e set iff element i0 + e is valid.
-template <int V>
-__device__ __forceinline__ unsigned valid_mask(const FrameGeom &g, size_t i0, int C, int inner, int &c0) {
-  if (inner == 1) {
-    const size_t r = i0 / (unsigned)C;
-    c0 = (int)(i0 - r * (unsigned)C);
-    return row_valid(g, (int)r) ? (1u << V) - 1u : 0u;
-  }
-  const size_t pl = i0 / (unsigned)inner;              // plane o * C + c
-  const int in = (int)(i0 - pl * (unsigned)inner);
-  c0 = (int)(pl % (unsigned)C);
-  const int left = geom_len(g, (int)(pl / (unsigned)C)) * g.frame - in;
-  return left >= V ? (1u << V) - 1u : left > 0 ? (1u << left) - 1u : 0u;
-}
-template <int V>
-__device__ __forceinline__ void load_valid(const float *__restrict__ p, size_t i0, unsigned m, float (&v)[V]) {
-  if (V == 4 && m == 15u) { const f32x4 q = *reinterpret_cast<const f32x4 *>(p + i0); v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3]; return; }
-#pragma unroll
-  for (int e = 0; e < V; ++e) v[e] = (m >> e & 1u) ? p[i0 + e] : 0.0f;
-}
-template <int V>
-__device__ __forceinline__ void store_all(float *__restrict__ p, size_t i0, const float (&v)[V]) {
-  if (V == 4) { f32x4 q; q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; q[3] = v[3]; *reinterpret_cast<f32x4 *>(p + i0) = q; }
-  else p[i0] = v[0];
-}
-
-template <int V>
-__global__ void mask_frames_kernel(const float *x, float *y, FrameGeom g, size_t ngroups, int C, int inner) {
-  for (size_t gi = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gi < ngroups; gi += (size_t)gridDim.x * blockDim.x) {
-    int c0;
-    const unsigned m = valid_mask<V>(g, gi * V, C, inner, c0);
-    float v[V];
-    load_valid<V>(x, gi * V, m, v);
-    store_all<V>(y, gi * V, v);
-  }
-}
-
-template <int V>
-__global__ void bn_apply_masked_kernel(const float *__restrict__ x, float *__restrict__ y, const float *__restrict__ gamma, const float *__restrict__ beta,
-                                       const float *__restrict__ mean, const float *__restrict__ rstd_or_var, float eps, int var_is_variance,
-                                       FrameGeom g, size_t ngroups, int C, int inner, int relu) {
-  for (size_t gi = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gi < ngroups; gi += (size_t)gridDim.x * blockDim.x) {
-    int c0;
-    const unsigned m = valid_mask<V>(g, gi * V, C, inner, c0);
-    float xv[V], o[V];
-    load_valid<V>(x, gi * V, m, xv);
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const int c = inner == 1 ? c0 + e : c0;
-      const float rs = var_is_variance ? 1.0f / sqrtf(rstd_or_var[c] + eps) : rstd_or_var[c];
-      float v = bn_value(xv[e], mean[c], rs, gamma[c], beta[c]);
-      if (relu) v = fmaxf(v, 0.0f);
-      o[e] = (m >> e & 1u) ? v : 0.0f;
-    }
-    store_all<V>(y, gi * V, o);
-  }
-}
-
-template <int V>
-__global__ void bn_dx_masked_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *dy, const float *__restrict__ gamma,
-                                    const float *__restrict__ mean, const float *__restrict__ rstd, const float *__restrict__ sums, float *dx,
-                                    FrameGeom g, size_t ngroups, int C, int inner, int relu) {
-  const float inv_n = sums[2 * C];
-  for (size_t gi = blockIdx.x * (size_t)blockDim.x + threadIdx.x; gi < ngroups; gi += (size_t)gridDim.x * blockDim.x) {
-    int c0;
-    const unsigned m = valid_mask<V>(g, gi * V, C, inner, c0);
-    float xv[V], gv[V], yv[V], o[V];
-    load_valid<V>(x, gi * V, m, xv);
-    load_valid<V>(dy, gi * V, m, gv);
-    if (relu) load_valid<V>(y, gi * V, m, yv);
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const int c = inner == 1 ? c0 + e : c0;
-      float gr = gv[e];
-      if (relu && !(yv[e] > 0.0f)) gr = 0.0f;
-      const float xh = (xv[e] - mean[c]) * rstd[c];
-      const float d = bn_dx_value(gr, xh, gamma[c], rstd[c], sums[c], sums[C + c], inv_n);
-      o[e] = (m >> e & 1u) ? d : 0.0f;
-    }
-    store_all<V>(dx, gi * V, o);
-  }
-}
-
-bool geom_ok(int outer, int C, int inner, const int *lens, int batch, int frame, FrameGeom *g) {
-  if (!lens || outer <= 0 || C <= 0 || inner <= 0 || batch <= 0 || frame <= 0) return false;
-  if (inner == 1 ? (frame != 1 || outer % batch != 0) : (batch != outer || inner % frame != 0)) return false;
-  *g = FrameGeom{lens, batch, frame, inner == 1 ? outer / batch : inner / frame};
-  return true;
-}
-// 4: the 16-B form of the streaming passes applies
-int stream_vec(int C, int inner, uintptr_t ptrs) { return (ptrs & 15) == 0 && (inner == 1 ? C % 4 == 0 : inner % 4 == 0) ? 4 : 1; }
-int stream_blocks(size_t ngroups) { return (int)std::min((size_t)4096, std::max((size_t)1, ceil_div_z(ngroups, 256))); }
-
-template <class F>
-void launch_reduce_masked(F f, const FrameGeom &g, int outer, int C, int inner, double *part, int *nchunks_out, hipStream_t st) {
-  if (inner == 1) {
-    const int n = chunks_rows(outer, C);
-    const int rpc = ceil_div(outer, n);
-    const int nn = ceil_div(outer, rpc);
-    if (C % 4 == 0 && f.aligned16() && ctcn_get_option("bn_rows4") != 0)
-      hipLaunchKernelGGL((mreduce_rows4_kernel<F>), dim3(ceil_div(C, 64), nn), dim3(256), 0, st, f, g, outer, C, rpc, part);
-    else
-      hipLaunchKernelGGL((mreduce_rows_kernel<F>), dim3(ceil_div(C, 64), nn), dim3(256), 0, st, f, g, outer, C, rpc, part);
-    *nchunks_out = nn;
-  } else {
-    const NchwChunks k = chunks_nchw(outer, C, inner);
-    const int vec = inner % 4 == 0 && f.aligned16() ? 1 : 0;
-    hipLaunchKernelGGL((mreduce_nchw_kernel<F>), dim3(C, k.n), dim3(256), 0, st, f, g, outer, C, inner, k.opc, k.ich, k.ilen, vec, part);
-    *nchunks_out = k.n;
-  }
-}
-
-void launch_bn_apply_masked(hipStream_t st, const float *x, float *y, const float *gamma, const float *beta, const float *mean, const float *rstd_or_var,
-                            float eps, int var_is_variance, const FrameGeom &g, size_t total, int C, int inner, int relu) {
-  if (stream_vec(C, inner, (uintptr_t)x | (uintptr_t)y) == 4)
-    hipLaunchKernelGGL(bn_apply_masked_kernel<4>, dim3(stream_blocks(total / 4)), dim3(256), 0, st, x, y, gamma, beta, mean, rstd_or_var, eps,
-                       var_is_variance, g, total / 4, C, inner, relu);
-  else
-    hipLaunchKernelGGL(bn_apply_masked_kernel<1>, dim3(stream_blocks(total)), dim3(256), 0, st, x, y, gamma, beta, mean, rstd_or_var, eps,
-                       var_is_variance, g, total, C, inner, relu);
-}
-
-}  // namespace
-
-extern "C" size_t ctcn_bn_masked_ws_bytes(int outer, int C, int inner) {
-  const size_t n = ctcn_bn_ws_bytes(outer, C, inner);
-  return n ? n + 256 : 0;                       // (+ the 1 / n word behind the two float sums)
-}
-
-extern "C" int ctcn_mask_frames(const float *x, float *y, const int *lens, int batch, int frame, int outer, int C, int inner, void *stream) {
-  CTCN_REQUIRE(x && y, "ctcn_mask_frames: null pointer");
-  FrameGeom g;
-  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_mask_frames: bad dims / geometry");
-  const size_t total = (size_t)outer * C * inner;
-  if (stream_vec(C, inner, (uintptr_t)x | (uintptr_t)y) == 4)
-    hipLaunchKernelGGL(mask_frames_kernel<4>, dim3(stream_blocks(total / 4)), dim3(256), 0, (hipStream_t)stream, x, y, g, total / 4, C, inner);
-  else
-    hipLaunchKernelGGL(mask_frames_kernel<1>, dim3(stream_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, g, total, C, inner);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-extern "C" int ctcn_bn_fwd_train_masked(const float *x, float *y, const float *gamma, const float *beta, float *running_mean, float *running_var,
-                                        float *save_mean, float *save_rstd, const int *lens, int batch, int frame, int outer, int C, int inner,
-                                        float eps, float momentum, int relu, void *ws, size_t ws_bytes, void *stream, long long *num_batches_tracked) {
-  CTCN_REQUIRE(x && y && gamma && beta && save_mean && save_rstd && ws, "ctcn_bn_fwd_train_masked: null pointer");
-  FrameGeom g;
-  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_bn_fwd_train_masked: bad dims / geometry");
-  if (ws_bytes < ctcn_bn_masked_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_fwd_train_masked: workspace too small"); return CTCN_EWORKSPACE; }
-  hipStream_t st = (hipStream_t)stream;
-  double *part = (double *)ws;
-  int nchunks = 0;
-  launch_reduce_masked(StatVal{x}, g, outer, C, inner, part, &nchunks, st);
-  CTCN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_finalize_stats_masked_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, g, eps, momentum, save_mean, save_rstd,
-                     running_mean, running_var, num_batches_tracked);
-  CTCN_LAUNCH_CHECK();
-  launch_bn_apply_masked(st, x, y, gamma, beta, save_mean, save_rstd, eps, 0, g, (size_t)outer * C * inner, C, inner, relu);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-extern "C" int ctcn_bn_fwd_eval_masked(const float *x, float *y, const float *gamma, const float *beta, const float *running_mean,
-                                       const float *running_var, const int *lens, int batch, int frame, int outer, int C, int inner, float eps,
-                                       int relu, void *stream) {
-  CTCN_REQUIRE(x && y && gamma && beta && running_mean && running_var, "ctcn_bn_fwd_eval_masked: null pointer");
-  FrameGeom g;
-  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_bn_fwd_eval_masked: bad dims / geometry");
-  launch_bn_apply_masked((hipStream_t)stream, x, y, gamma, beta, running_mean, running_var, eps, 1, g, (size_t)outer * C * inner, C, inner, relu);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-extern "C" int ctcn_bn_bwd_masked(const float *x, const float *y, const float *dy, const float *gamma, const float *save_mean, const float *save_rstd,
-                                  float *dx, float *dgamma, float *dbeta, const int *lens, int batch, int frame, int outer, int C, int inner, int relu,
-                                  float beta_acc, void *ws, size_t ws_bytes, void *stream) {
-  CTCN_REQUIRE(x && dy && gamma && save_mean && save_rstd && dx && ws, "ctcn_bn_bwd_masked: null pointer");
-  CTCN_REQUIRE(!relu || y, "ctcn_bn_bwd_masked: y required for the fused relu mask");
-  FrameGeom g;
-  CTCN_REQUIRE(geom_ok(outer, C, inner, lens, batch, frame, &g), "ctcn_bn_bwd_masked: bad dims / geometry");
-  if (ws_bytes < ctcn_bn_masked_ws_bytes(outer, C, inner)) { ctcn_set_error("ctcn_bn_bwd_masked: workspace too small"); return CTCN_EWORKSPACE; }
-  hipStream_t st = (hipStream_t)stream;
-  double *part = (double *)ws;
-  const int nmax = inner == 1 ? chunks_rows(outer, C) : chunks_nchw(outer, C, inner).n;
-  float *sums = (float *)((char *)ws + align_up((size_t)(nmax + 1) * C * 2 * sizeof(double), 256));
-  int nchunks = 0;
-  launch_reduce_masked(BwdVal{x, y, dy, save_mean, save_rstd, relu, k_no_drop}, g, outer, C, inner, part, &nchunks, st);
-  CTCN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_finalize_bwd_masked_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, part, nchunks, C, g, dgamma, dbeta, sums, beta_acc);
-  CTCN_LAUNCH_CHECK();
-  const size_t total = (size_t)outer * C * inner;
-  if (stream_vec(C, inner, (uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (relu ? (uintptr_t)y : 0)) == 4)
-    hipLaunchKernelGGL(bn_dx_masked_kernel<4>, dim3(stream_blocks(total / 4)), dim3(256), 0, st, x, y, dy, gamma, save_mean, save_rstd, sums, dx, g,
-                       total / 4, C, inner, relu);
-  else
-    hipLaunchKernelGGL(bn_dx_masked_kernel<1>, dim3(stream_blocks(total)), dim3(256), 0, st, x, y, dy, gamma, save_mean, save_rstd, sums, dx, g, total, C,
-                       inner, relu);
+  launch_bn_dx(st, g, x, y, dy, gamma, save_mean, save_rstd, sums, dx, (size_t)outer * C * inner, C, inner, relu);
   CTCN_LAUNCH_CHECK();
   return CTCN_OK;
 }

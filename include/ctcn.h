@@ -100,7 +100,7 @@ int ctcn_device_xcds(void);
  * the SLOW instantiations of rnn_bwd_scatter / rnn_bwd_scatter2 (item waves sleep before they read the parked tiles / start their gather, exchange waves
  * behind the barrier before they read the staged operand): test_rnn_bwd_with_slow_waves.
  * "bn_rows4" = 1 (default, round 5): BatchNorm over (rows, C) with C % 4 == 0 forms its column sums with 16-B loads, sixteen row phases per
- * workgroup (colreduce_rows4_kernel); 0: the dword kernel.  Same chunks, same element values, float64 partials grouped differently: the float32
+ * workgroup (colreduce_rows4_kernel, behind the dense and the length-aware entry points alike); 0: the dword kernel (colreduce_rows_kernel).  Same chunks, same element values, float64 partials grouped differently: the float32
  * results agreed bit for bit wherever compared (tools/bn_rows_probe.py).  cfg2 13.33 -> 13.25 ms per step, cfg4 53.2 -> 52.8.
  * "tn_splits_force" = 0 (default; development): n > 0 forces the split-K count of the TN tile (tools/gemm_tn_splits_probe.py: the rule's own
  * choice -- one round of (tile, split) items on the CUs the launch may use -- is where the time is shortest on the cfg2 / cfg4 products).

@@ -773,7 +773,7 @@ def test_batchnorm_large_rows_vs_torch(dev):
 
 # name: (outer, C, inner, variant)   variant: None | "rows4_off" (option bn_rows4 = 0, held bit for bit to = 1) | "offset" (x at storage offset 1)
 BN_BRANCH_CASES = {
-    "rows_c14": (1000, 14, 1, None),            # C % 4 != 0: dword column sums, bn_apply_kernel / bn_dx_kernel on rows
+    "rows_c14": (1000, 14, 1, None),            # C % 4 != 0: dword column sums, bn_apply_kernel / bn_dx_kernel (V = 1) on rows
     "rows_c62": (2001, 62, 1, None),
     "rows_c321": (777, 321, 1, None),           # ragged 64-column blocks
     "rows_c640_dword": (3000, 640, 1, "rows4_off"),

@@ -447,6 +447,70 @@ def test_masked_kernels_against_float64(dev, case, relu, into_flat):
     assert np.array_equal(xd.cpu().numpy(), want)
 
 
+FULL_LENGTH_CASES = [  # layout, outer, C, inner, batch, frame, storage offset of x (floats), option bn_rows4
+    ("rows", 200, 24, 1, 4, 1, 0, 1),                         # 16-B path
+    ("rows", 400, 64, 1, 4, 1, 0, 1),
+    ("rows", 27, 7, 1, 3, 1, 0, 1),                           # C % 4 != 0: scalar path
+    ("rows", 1500, 64, 1, 4, 1, 1, 1),                        # x 4-B aligned only: the dword kernels although C % 4 == 0
+    ("rows", 400, 64, 1, 4, 1, 0, 0),                         # the dword reductions by option
+    ("nchw", 3, 5, 200, 3, 8, 0, 1),                          # inner % 4 == 0: vector path
+    ("nchw", 2, 4, 33, 2, 3, 0, 1),                           # scalar path
+    ("nchw", 3, 2, 28000, 3, 40, 0, 1),                       # planes cut into several chunks (ich > 1)
+    ("nchw", 200, 64, 37, 200, 1, 0, 1),                      # several planes per chunk (opc > 1)
+]
+
+
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("case", FULL_LENGTH_CASES, ids=lambda c: "%s_%dx%dx%d_off%d_rows4_%d" % (c[0], c[1], c[2], c[3], c[6], c[7]))
+def test_full_length_masked_kernels_equal_dense_bit_for_bit(dev, case, relu):
+    """With lens = [tmax] * batch the length-aware entry points sum the same values in the same order as the dense ones and evaluate the
+    same per-element expressions: ctcn_bn_fwd_train / _masked, ctcn_bn_bwd / _masked and ctcn_bn_fwd_eval / _masked agree bit for bit
+    (the counts are the same doubles, 1 / n the same correctly rounded division)."""
+    from ctc_pytorch_amd import _lib
+    L = _lib.lib()
+    layout, outer, C, inner, batch_n, frame, xoff, rows4 = case
+    tmax = outer // batch_n if layout == "rows" else inner // frame
+    rs = np.random.RandomState(outer + C + inner)
+    shape = (outer, C, inner)
+    buf = torch.empty(outer * C * inner + xoff, device=dev)
+    xd = buf[xoff:].view(shape)
+    xd.copy_(torch.from_numpy((2.0 * rs.standard_normal(shape) + 0.5).astype(np.float32)))
+    assert xd.data_ptr() % 16 == 4 * xoff
+    dyd = torch.from_numpy(rs.standard_normal(shape).astype(np.float32)).to(dev)
+    gd = torch.from_numpy((1.0 + 0.3 * rs.standard_normal(C)).astype(np.float32)).to(dev)
+    bd = torch.from_numpy((0.2 * rs.standard_normal(C)).astype(np.float32)).to(dev)
+    rm0, rv0 = torch.from_numpy(rs.standard_normal(C).astype(np.float32)).to(dev), torch.from_numpy((0.5 + rs.random_sample(C)).astype(np.float32)).to(dev)
+    lens_d = torch.tensor([tmax] * batch_n, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(L.ctcn_bn_masked_ws_bytes(outer, C, inner)), dtype=torch.uint8, device=dev)
+    assert ws.numel() >= int(L.ctcn_bn_ws_bytes(outer, C, inner)) > 0
+    st, eps, mom = _lib.stream_ptr(), 1e-5, 0.1
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    nan = lambda *s: torch.full(s, float("nan"), device=dev)
+
+    def run(masked):
+        geom = (P(lens_d), batch_n, frame) if masked else ()
+        sfx = "_masked" if masked else ""
+        o = {"y": nan(*shape), "save_mean": nan(C), "save_rstd": nan(C), "running_mean": rm0.clone(), "running_var": rv0.clone(),
+             "dx": nan(*shape), "dgamma": nan(C), "dbeta": nan(C), "eval_y": nan(*shape)}
+        _lib.check(getattr(L, "ctcn_bn_fwd_train" + sfx)(P(xd), P(o["y"]), P(gd), P(bd), P(o["running_mean"]), P(o["running_var"]), P(o["save_mean"]),
+                                                         P(o["save_rstd"]), *geom, outer, C, inner, eps, mom, relu, P(ws), ws.numel(), st, None), "fwd" + sfx)
+        _lib.check(getattr(L, "ctcn_bn_bwd" + sfx)(P(xd), P(o["y"]) if relu else None, P(dyd), P(gd), P(o["save_mean"]), P(o["save_rstd"]), P(o["dx"]),
+                                                   P(o["dgamma"]), P(o["dbeta"]), *geom, outer, C, inner, relu, 0.0, P(ws), ws.numel(), st), "bwd" + sfx)
+        _lib.check(getattr(L, "ctcn_bn_fwd_eval" + sfx)(P(xd), P(o["eval_y"]), P(gd), P(bd), P(rm0), P(rv0), *geom, outer, C, inner, eps, relu, st), "eval" + sfx)
+        torch.cuda.synchronize()
+        return o
+
+    before = L.ctcn_get_option(b"bn_rows4")
+    try:
+        _lib.check(L.ctcn_set_option(b"bn_rows4", rows4), "set_option")
+        dense, masked = run(False), run(True)
+    finally:
+        L.ctcn_set_option(b"bn_rows4", before)
+    for k in dense:
+        assert bool(torch.isfinite(dense[k]).all()), k
+        assert torch.equal(masked[k], dense[k]), (k, maxabs(masked[k], dense[k]))
+
+
 def test_mask_frames_autograd_and_layouts(dev):
     from ctc_pytorch_amd import ops
     lens = [5, 1, 3]

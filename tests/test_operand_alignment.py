@@ -307,8 +307,8 @@ def test_rnn_layer_misaligned_w_hh_is_not_refused(dev):
 # ---------------------------------------------------------------------------------------------------------
 # BatchNorm (plain, length-aware, fused dropout).  ops allocates y and dx itself (always on 16 bytes), so through ops the operands that can be
 # misaligned are x, gamma, beta, the running statistics, dy and the dgamma / dbeta views.  One misaligned pointer among x / y / gamma / beta /
-# mean / rstd sends launch_bn_apply and the backward (`al`), the column sums (aligned16()) and the masked streams (stream_vec, load_valid /
-# store_all) to their dword side.
+# mean / rstd sends launch_bn_apply and launch_bn_dx (`io | ch`: the dense rows4 kernels; `io`: the length-aware V = 4 streams, stream_vec,
+# load_valid / store_all) and the column sums (aligned16()) to their dword side.
 #   plain:  oracle/np_ref.py in float64 at the gates of test_gpu_kernels.test_batchnorm_branch_matrix_vs_oracle (y, dx, eval 2e-5 scaled by
 #           magnitude; dgamma / dbeta rel-L2 1e-5; running statistics 1e-5 scaled)
 #   masked: the float64 restatement and gates of test_length_mask.test_masked_kernels_against_float64 (y, dx, eval 2e-5 scaled; running
