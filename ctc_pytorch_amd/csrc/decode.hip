@@ -37,6 +37,15 @@ __device__ __forceinline__ double log_add_prob(double log_x, double log_y) {   /
   return log_x + log(1 + exp(log_y - log_x));
 }
 
+// ln P_LM * alpha rounded on its own before it joins a sum -- as the fast kernel's LDS table holds it and as the reference computes it.  Without
+// the pragma the compiler fuses the product into the sum (v_fma_f64) wherever it is formed per use: the fast kernel's global-memory LM variant
+// then differed from its LDS variant in the last bits (beam_occ2 = 1 / 2 where the LM does not fit beside the trie, V > 70 at any setting), and
+// the generic kernel from both (tests/test_beam_edges.py holds every path to the same bits).
+__device__ __forceinline__ double lm_scaled(double lm, double alpha) {
+#pragma clang fp contract(off)
+  return lm * alpha;
+}
+
 struct Fields { double nb, b, t; };
 __device__ __forceinline__ void apply_stay(Fields &e, double s_nb, double s_b) {   // BeamSearch.py:108-113
   e.nb = log_add_prob(e.nb, s_nb);
@@ -181,7 +190,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
   double *const sv_v = selv + wcap;                            // selection: survivors of the pruning bound (value | candidate index)
   int *const mfrom = ibase + 8 * wcap, *const sel = mfrom + wcap, *const sv_i = sel + wcap;
   // (round 6) the LM table in LDS when the launch has room for it: one LDS read instead of a global gather per candidate and frame; the raw
-  // ln-probs are copied, the product with alpha is formed per use exactly as before
+  // ln-probs are copied, the product with alpha is formed per use by lm_scaled() (rounded on its own: never re-inline the multiply, the compiler fuses it into the sum)
   const double *lmt = a.lm;
   if (a.lm_in_lds) {
     double *lml = reinterpret_cast<double *>(reinterpret_cast<char *>(sv_i + SEL_SMAX) + ((8 - ((size_t)(10 * wcap + SEL_SMAX) * 4) % 8) % 8));
@@ -290,7 +299,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
         const int c = c0 + u * NT;
         if (c < ncand && ck[u] >= 0) {
           const int i = ci[u], k = ck[u];
-          const double bigram = lmv[u] * a.alpha;
+          const double bigram = lm_scaled(lmv[u], a.alpha);
           const double base = (cln[u] > 0 && cl[u] == k && rep_ok) ? L.pB[i] : L.pT[i];
           cand[c] = lg[k] + bigram + base;
         }
@@ -631,7 +640,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
       // normalised scores (BeamSearch.py:147: prTotal / labelling length), then `last.sort()[0:nbest]` (:150, the reference keeps [0]): a stable
       // descending sort -- among equal scores the earlier entry (the order of BHat) comes first.  L.pT is reused for the scores, L.par as "taken"
       for (int r = 0; r < nb; ++r) {
-        const double pr = L.pT[r] + lmt[(size_t)L.last[r] * (V + 1) + V] * a.alpha;
+        const double pr = L.pT[r] + lm_scaled(lmt[(size_t)L.last[r] * (V + 1) + V], a.alpha);
         const double tot = log_add_prob(LOG_ZERO, pr);
         const int ln = L.len[r];
         L.pT[r] = tot * (1.0 / (ln ? ln : 1));
@@ -775,14 +784,6 @@ constexpr int SURV_MAX = 256;
 constexpr int FAST_NCT = 1024 - 192;                           // candidate threads: waves 3..15
 constexpr int FAST_NTH = 1024, FAST_NWV = FAST_NTH / 64;      // 16 waves: the parallel phases are instruction-issue bound (~10 cycles per
                                                                // dependent instruction and wave), so more waves per SIMD is what shortens them
-// ln P_LM * alpha rounded on its own before it joins a sum -- as the LDS table holds it (LM_LDS) and as the reference computes it.  Without
-// the pragma the compiler fuses the product into the sum (v_fma_f64) in the global-memory variant only, and its scores then differed from the
-// LDS variant's in the last bits (beam_occ2 = 1 / 2 where the LM does not fit beside the trie, and V > 70 at any setting).
-__device__ __forceinline__ double lm_scaled(double lm, double alpha) {
-#pragma clang fp contract(off)
-  return lm * alpha;
-}
-
 template <int NPT, bool LM_LDS>
 __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   constexpr int NTH = FAST_NTH, NWV = FAST_NWV;
@@ -829,7 +830,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   constexpr int TMASK = (1 << 29) - 1;
 
   if (LM_LDS)
-    for (int i = tid; i < V1 * V1; i += NTH) lmA[i] = a.lm[i] * a.alpha;        // the same product the generic kernel forms per use
+    for (int i = tid; i < V1 * V1; i += NTH) lmA[i] = a.lm[i] * a.alpha;        // rounded by the store: the same product lm_scaled() gives the generic kernel and the global-memory variant per use
   for (int i = tid; i < W * V; i += NTH) mslot[i] = -1;
   for (int i = tid; i < TS; i += NTH) trie[i] = 0u;
   const int nframes = min(max(a.lens[b], 0), T);
@@ -1463,7 +1464,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
     if (st == 0) {
       // as in beam_kernel: normalised scores, then the first `nbest` of a stable descending sort (f_pT is reused for the scores, f_last as "taken")
       for (int r = 0; r < nb; ++r) {
-        const double pr = f_pT[r] + a.lm[(size_t)f_last[r] * V1 + V] * a.alpha;
+        const double pr = f_pT[r] + lm_scaled(a.lm[(size_t)f_last[r] * V1 + V], a.alpha);
         const double tot = pr;                      // == log_add_prob(LOG_ZERO, pr): its first test returns the second argument (BeamSearch.py:44-45)
         const int ln = f_len[r];
         f_pT[r] = tot * (1.0 / (ln ? ln : 1));
