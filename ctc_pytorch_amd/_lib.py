@@ -93,6 +93,8 @@ _SIGS = {
     "ctcn_scale_by_device_scalar": (I, [P, Z, P, P]),
     "ctcn_greedy_collapse": (I, [P, Z, Z, P, P, P, I, I, I, P]),
     "ctcn_edit_distance": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "ctcn_edit_ops_ws_bytes": (Z, [I, I, I]),
+    "ctcn_edit_ops": (I, [P, P, P, P, P, I, P, P, P, P, I, I, I, I, P, Z, P]),
     "ctcn_step_stats": (I, [P, P, P, I, P, P, P]),
     "ctcn_comm_unique_id": (I, [P]),
     "ctcn_comm_init": (I, [P, I, I, ctypes.POINTER(ctypes.c_void_p)]),
@@ -102,6 +104,7 @@ _SIGS = {
     "ctcn_diag_pipeline_chunks": (I, [I, I, I, I, I, I, I, I, ctypes.c_uint]),
     "ctcn_rnn_last_kernel": (ctypes.c_char_p, [I]),
     "ctcn_levenshtein": (ctypes.c_longlong, [P, ctypes.c_longlong, P, ctypes.c_longlong]),
+    "ctcn_levenshtein_ops": (ctypes.c_longlong, [P, ctypes.c_longlong, P, ctypes.c_longlong, P, P]),
     "ctcn_join_tokens": (ctypes.c_longlong, [P, ctypes.c_longlong, P, I, P, P, P, I, I, P, ctypes.c_longlong, P]),
     "ctcn_beam_ws_bytes": (Z, [I, I, I, I]),
     "ctcn_beam_decode": (I, [P, I, P, P, D, I, I, P, P, P, P, I, I, I, P, Z, P]),

@@ -73,3 +73,56 @@ extern "C" long long ctcn_levenshtein(const int32_t *a, long long na, const int3
   free(row);
   return d;
 }
+
+// ctcn_levenshtein_ops: the alignment behind that distance -- the host twin of ctcn_edit_ops (editops.hip), for word- and string-level
+// scoring and for the decode driver, whose hypotheses are on the host already.  The move of cell (i, j) is the first of diagonal (a correct
+// pair or a substitution), deletion (reference symbol j - 1 without a partner), insertion (hypothesis symbol i - 1 without one) that attains
+// the minimum; row 0 holds deletions only, column 0 insertions only.  One byte per cell for the moves, a rolling row for the values.
+// counts4 = (sub, del, ins, cor); ali (nh + nr, 2), if given, takes the (ref, hyp) pairs in forward order, -1 = none, and -1 past the last
+// pair.  Returns the number of pairs, CTCN_EINVAL on bad arguments.
+extern "C" long long ctcn_levenshtein_ops(const int32_t *hyp, long long nh, const int32_t *ref, long long nr, long long *counts4, int32_t *ali) {
+  if (nh < 0 || nr < 0 || (nh > 0 && !hyp) || (nr > 0 && !ref) || !counts4) return CTCN_EINVAL;
+  uint8_t *mv = nullptr;
+  if (nh > 0 && nr > 0) {
+    mv = static_cast<uint8_t *>(malloc((size_t)nh * (size_t)nr));
+    int32_t *row = static_cast<int32_t *>(malloc(sizeof(int32_t) * (size_t)(nr + 1)));
+    if (!mv || !row) { free(mv); free(row); return CTCN_EINVAL; }
+    for (long long j = 0; j <= nr; ++j) row[j] = (int32_t)j;
+    for (long long i = 1; i <= nh; ++i) {
+      const int32_t x = hyp[i - 1];
+      int32_t diag = row[0];                                // D[i-1][j-1]
+      int32_t left = row[0] = (int32_t)i;                   // D[i][j-1]
+      uint8_t *m = mv + (size_t)(i - 1) * (size_t)nr;
+      for (long long j = 1; j <= nr; ++j) {
+        const int32_t up = row[j];                          // D[i-1][j]
+        const int32_t dg = diag + (x != ref[j - 1] ? 1 : 0), de = left + 1, in = up + 1;
+        const int32_t best = dg <= de ? (dg <= in ? dg : in) : (de <= in ? de : in);
+        m[j - 1] = dg == best ? 0 : de == best ? 1 : 2;
+        diag = up;
+        row[j] = left = best;
+      }
+    }
+    free(row);
+  }
+  long long i = nh, j = nr, n = 0, c[4] = {0, 0, 0, 0};
+  while (i > 0 || j > 0) {
+    const int m = i == 0 ? 1 : j == 0 ? 2 : mv[(size_t)(i - 1) * (size_t)nr + (size_t)(j - 1)];
+    int32_t r = -1, h = -1;
+    if (m != 2) r = ref[--j];
+    if (m != 1) h = hyp[--i];
+    ++c[m == 0 ? (r == h ? 3 : 0) : m];
+    if (ali) { ali[2 * n] = r; ali[2 * n + 1] = h; }        // backwards for now
+    ++n;
+  }
+  free(mv);
+  for (int k = 0; k < 4; ++k) counts4[k] = c[k];
+  if (ali) {
+    for (long long lo = 0, hi = n - 1; lo < hi; ++lo, --hi) {
+      const int32_t r = ali[2 * lo], h = ali[2 * lo + 1];
+      ali[2 * lo] = ali[2 * hi]; ali[2 * lo + 1] = ali[2 * hi + 1];
+      ali[2 * hi] = r; ali[2 * hi + 1] = h;
+    }
+    for (long long k = 2 * n; k < 2 * (nh + nr); ++k) ali[k] = -1;
+  }
+  return n;
+}

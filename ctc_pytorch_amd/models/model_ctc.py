@@ -320,6 +320,19 @@ class CTC_Model(nn.Module):
         dist = ops.edit_distance(ids, ids_len, tg, tl)
         return int(dist.sum().item()), int(tl.sum().item())
 
+    def compute_error_ops(self, index, input_sizes, targets, target_sizes, class_map=None):
+        """compute_wer's arguments -> the error breakdown of the batch (ops.edit_ops): the six python ints (sub, del, ins, cor, hyp_len,
+        ref_len), lengths taken after class_map (utils.scoring.load_phone_map; None: the classes as they are, and sub + del + ins is
+        compute_wer's error count).  One device-to-host copy."""
+        dev = next(self.parameters()).device
+        idx = torch.as_tensor(np.asarray(index) if not torch.is_tensor(index) else index).to(dev).to(torch.int32)
+        lens = torch.as_tensor(np.asarray(input_sizes) if not torch.is_tensor(input_sizes) else input_sizes).to(dev)
+        tg = torch.as_tensor(np.asarray(targets) if not torch.is_tensor(targets) else targets).to(dev)
+        tl = torch.as_tensor(np.asarray(target_sizes) if not torch.is_tensor(target_sizes) else target_sizes).to(dev)
+        ids, ids_len = ops.greedy_collapse(idx, lens, blank=0, batch_major=True)
+        counts = ops.edit_ops(ids, ids_len, tg, tl, class_map=class_map, num_classes=None if class_map is None else len(class_map)).counts
+        return tuple(int(v) for v in counts.sum(0, dtype=torch.int64).cpu())
+
     def add_weights_noise(self):
         # dead code in the reference as well (model_ctc.py:204-207 rebinds a local and changes nothing)
         return None

@@ -1452,6 +1452,53 @@ def edit_distance(ids, ids_len, targets, tgt_len):
     return out
 
 
+EditOps = collections.namedtuple("EditOps", "counts ali ali_len")
+
+
+def edit_ops(ids, ids_len, targets, tgt_len, class_map=None, num_classes=None, confusion=None, alignment=False):
+    """The error breakdown behind edit_distance (ctcn_edit_ops; definition and tie rule in include/ctcn.h): per utterance
+    counts (B,6) int32 = (sub, del, ins, cor, hyp_len', ref_len') with the lengths taken after the class map, and with alignment=True
+    ali (B, T + Lmax, 2) int32 = the (reference id, hypothesis id) pairs in forward order, -1 = none, plus ali_len (B) int32 (both None
+    otherwise).  class_map: V int32 entries applied to both sequences (a value in [0, V) replaces the id, -1 removes the symbol; ids outside
+    [0, V) pass through); confusion: a caller-owned (V+1, V+1) int64 device tensor that is ACCUMULATED into (row V insertions, column V
+    deletions).  V = num_classes, else the length of class_map, else confusion.shape[0] - 1.  Takes what edit_distance takes; everything
+    stays on the device, no host sync."""
+    _need_gpu(ids)
+    dev = ids.device
+    if ids.dtype != torch.int32 or not ids.is_contiguous():
+        ids = ids.to(torch.int32).contiguous()
+    ids_len = ids_len.to(device=dev, dtype=torch.int32).contiguous()
+    targets = targets.to(device=dev, dtype=torch.int64).contiguous()
+    tgt_len = tgt_len.to(device=dev, dtype=torch.int64).contiguous()
+    B = ids.shape[0]
+    if ids.dim() != 2 or targets.dim() != 2 or targets.shape[0] != B or tgt_len.numel() != B or ids_len.numel() != B:
+        raise ValueError("ctc_pytorch_amd.edit_ops: expected ids (B,T), ids_len (B), targets (B,Lmax), tgt_len (B)")
+    V = num_classes
+    if class_map is not None:
+        class_map = torch.as_tensor(class_map).to(device=dev, dtype=torch.int32).contiguous()
+        V = class_map.numel() if V is None else V
+        if class_map.dim() != 1 or class_map.numel() != V:
+            raise ValueError("ctc_pytorch_amd.edit_ops: class_map must hold num_classes = %s entries, got %s" % (V, tuple(class_map.shape)))
+    if confusion is not None:
+        V = confusion.shape[0] - 1 if V is None else V
+        if confusion.dtype != torch.int64 or confusion.device != dev or not confusion.is_contiguous() or tuple(confusion.shape) != (V + 1, V + 1):
+            raise ValueError("ctc_pytorch_amd.edit_ops: confusion must be a contiguous int64 (V+1, V+1) tensor on %s with V = %s" % (dev, V))
+    V = 0 if V is None else int(V)
+    if (class_map is not None or confusion is not None) and V <= 0:
+        raise ValueError("ctc_pytorch_amd.edit_ops: num_classes must be positive, got %d" % V)
+    L = _lib.lib()
+    lda, ldb = ids.shape[1], targets.shape[1]
+    counts = torch.empty((B, 6), dtype=torch.int32, device=dev)
+    ali = torch.empty((B, lda + ldb, 2), dtype=torch.int32, device=dev) if alignment else None
+    ali_len = torch.empty(B, dtype=torch.int32, device=dev) if alignment else None
+    need = L.ctcn_edit_ops_ws_bytes(B, lda, max(ldb, 1))
+    # move bits that do not fit in LDS: a buffer of this call's own (stream-ordered, as in ctc_forced_align)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    _lib.check(L.ctcn_edit_ops(_ptr(ids), _ptr(ids_len), _ptr(targets), _ptr(tgt_len), _ptr(class_map), V, _ptr(counts), _ptr(ali),
+                               _ptr(ali_len), _ptr(confusion), B, lda, ldb, max(ldb, 1), _ptr(ws), need, _lib.stream_ptr()), "edit_ops")
+    return EditOps(counts, ali, ali_len)
+
+
 def step_stats(loss, dist, tgt_len):
     """(loss, sum(dist), sum(tgt_len), hand-off status word) as a float64 device tensor of 4 -- one launch (ctcn_step_stats)."""
     _need_gpu(loss, dist, tgt_len)

@@ -51,8 +51,13 @@ def input_frames_from_fraction(input_sizes, T):
 
 
 def run_epoch(epoch_id, model, data_iter, loss_fn, device, optimizer=None, print_every=20, is_training=True,
-              global_batch=None, log=print, mask_padding=False):
-    """mask_padding (YAML key `mask_padding`, default off = the reference's behaviour): the model is told every utterance's real frames
+              global_batch=None, log=print, mask_padding=False, error_report=False, score_map=None, index2word=None):
+    """error_report (YAML key `error_report`, default off): VALIDATION passes take the error breakdown behind total_wer -- ops.edit_ops in
+    place of ops.edit_distance, the six totals and the confusion table accumulated on the device in a utils.scoring.ErrorStats, read once
+    after the loop and logged as one extra line (`%PER x.xx [ e / n, i ins, d del, s sub ]` plus the top confusions; index2word names
+    them).  score_map (YAML keys `score_map`, `score_map_cols`: utils.scoring.load_phone_map): the class map the breakdown is scored
+    under; total_wer and the return value stay those of the unmapped classes.  Training passes are untouched by either.
+    mask_padding (YAML key `mask_padding`, default off = the reference's behaviour): the model is told every utterance's real frames
     (CTC_Model.forward(input_lengths=)), so padding reaches no BatchNorm statistic and no recurrence, and the CTC loss takes
     model.output_lengths(...) instead of floor(fraction * T_out)."""
     model.train() if is_training else model.eval()
@@ -86,6 +91,9 @@ def run_epoch(epoch_id, model, data_iter, loss_fn, device, optimizer=None, print
                 epoch_id, step + 1, acc["cur_loss"] / print_every, acc["total_loss"] / (step + 1), acc["total_errs"] / acc["total_tokens"]))
             acc["cur_loss"] = 0.0
 
+    report = bool(error_report) and not is_training
+    estats = cmap = None
+    count_rows = []
     pending = None
     for i, data in enumerate(data_iter):
         inputs, input_sizes, targets, target_sizes, utt_list = data[:5]
@@ -117,7 +125,17 @@ def run_epoch(epoch_id, model, data_iter, loss_fn, device, optimizer=None, print
         # greedy error count on the pre-update model, all on device
         idx = ops.argmax_last(out)                                        # (T,B) int32
         ids, ids_len = ops.greedy_collapse(idx, in_len, blank=0)
-        dist = ops.edit_distance(ids, ids_len, targets_d, target_sizes_d)
+        if report:
+            if estats is None:
+                from ctc_pytorch_amd.utils.scoring import ErrorStats
+                estats = ErrorStats(index2word if index2word is not None else [str(k) for k in range(int(out.shape[2]))], device=out.device)
+                cmap = None if score_map is None else torch.as_tensor(np.asarray(score_map, dtype=np.int32)).to(out.device)
+            counts = ops.edit_ops(ids, ids_len, targets_d, target_sizes_d, class_map=cmap, num_classes=estats.V, confusion=estats.confusion).counts
+            count_rows.append(counts)                        # summed once after the loop: no launch per step for the totals
+            # without a map sub + del + ins IS the distance; with one, total_wer still reports the distance of the unmapped classes
+            dist = counts[:, :3].sum(1, dtype=torch.int32) if cmap is None else ops.edit_distance(ids, ids_len, targets_d, target_sizes_d)
+        else:
+            dist = ops.edit_distance(ids, ids_len, targets_d, target_sizes_d)
         if is_training:
             optimizer.zero_grad()
             loss.backward()
@@ -155,6 +173,12 @@ def run_epoch(epoch_id, model, data_iter, loss_fn, device, optimizer=None, print
         clip_note = ", dropped_steps: %d, last_grad_norm: %.4g" % (optimizer.skipped_steps, float(optimizer.last_grad_norm))
     log("Epoch %d %s done, total_loss: %.4f, total_wer: %.4f%s" % (epoch_id, "Train" if is_training else "Valid", average_loss,
                                                                   total_errs / max(total_tokens, 1), clip_note))
+    if estats is not None:
+        # read once per pass, here, where the last step's statistics have been waited for; data parallel: one all-reduce of the flat state
+        estats.add(torch.cat(count_rows))
+        if step_global:
+            estats = estats.from_state(estats.names, parallel.allreduce_stats(estats.state()))
+        log("Epoch %d Valid error breakdown%s: %s" % (epoch_id, "" if cmap is None else " (mapped classes)", estats.report().replace("\n", "; ")))
     return 1 - total_errs / max(total_tokens, 1), average_loss
 
 
@@ -169,6 +193,21 @@ def epoch_options(opts):
     """run_epoch's keywords from the driver options: `mask_padding: true` passes the utterance lengths to the model; an absent (or false)
     key passes nothing -- run_epoch then calls the model exactly as the reference's loop does."""
     return {"mask_padding": True} if bool(getattr(opts, "mask_padding", False)) else {}
+
+
+def report_options(opts, index2word=None):
+    """run_epoch's error-breakdown keywords from the driver options `error_report` (bool), `score_map` (path of a three-column phone table)
+    and `score_map_cols` ("60-48", "60-39" or "48-39"); absent (or false) keys pass nothing.  A score map needs the vocabulary's names."""
+    if not bool(getattr(opts, "error_report", False)):
+        return {}
+    kw = {"error_report": True, "index2word": index2word}
+    path = getattr(opts, "score_map", None)
+    if path:
+        if index2word is None:
+            raise ValueError("score_map needs the vocabulary (index2word) to resolve the phone names of %s" % path)
+        from ctc_pytorch_amd.utils.scoring import load_phone_map
+        kw["score_map"] = load_phone_map(path, str(getattr(opts, "score_map_cols", "48-39")), index2word)
+    return kw
 
 
 class Config(object):
@@ -242,7 +281,7 @@ class LRController:
             self.stop = True
 
 
-def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print):
+def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print, index2word=None):
     opts = Config()
     for k, v in conf.items():
         setattr(opts, k, v)
@@ -259,6 +298,7 @@ def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print):
         from ctc_pytorch_amd.utils.data_loader import Vocab, SpeechDataset, SpeechDataLoader
         vocab = Vocab(opts.vocab_file)
         num_class = vocab.n_words
+        index2word = vocab.index2word
         train_loader = SpeechDataLoader(SpeechDataset(vocab, opts.train_scp_path, opts.train_lab_path, opts),
                                         batch_size=opts.batch_size, shuffle=opts.shuffle_train, num_workers=opts.num_workers)
         dev_loader = SpeechDataLoader(SpeechDataset(vocab, opts.valid_scp_path, opts.valid_lab_path, opts),
@@ -282,6 +322,7 @@ def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print):
     parallel.broadcast_params(optimizer.flat)
     ctl = LRController(opts.end_adjust_acc, opts.lr_decay)
     loss_results, dev_loss_results, dev_cer_results = [], [], []
+    report_kw = report_options(opts, index2word)          # (validation passes only; empty with the keys off)
     count = 0
     # the long-lived objects built so far (module tree, optimizer, loaders) leave the interpreter's cyclic collector: its generation-2
     # passes over them took ~50 ms each -- three or four whole training steps -- and the loop only stays two steps ahead of the device
@@ -300,7 +341,7 @@ def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print):
             # per-shard BatchNorm: one set of running statistics for the evaluation below and for rank 0's checkpoint
             parallel.sync_bn_buffers(model)
             acc, dev_loss = run_epoch(count, model, dev_loader, loss_fn, device, optimizer=None, print_every=opts.verbose_step,
-                                      is_training=False, log=log, **epoch_options(opts))
+                                      is_training=False, log=log, **epoch_options(opts), **report_kw)
             loss_results.append(loss)
             dev_loss_results.append(dev_loss)
             dev_cer_results.append(acc)
@@ -332,8 +373,17 @@ if __name__ == "__main__":
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm to this value (default: the YAML's max_grad_norm, else off)")
     ap.add_argument("--skip-nonfinite-steps", action="store_true", help="drop optimiser steps whose gradient holds NaN / Inf (default: the YAML's skip_nonfinite_steps, else off)")
     ap.add_argument("--mask-padding", action="store_true", help="tell the model every utterance's real frames: padding reaches no BatchNorm statistic and no recurrence (default: the YAML's mask_padding, else off)")
+    ap.add_argument("--error-report", action="store_true", help="log the error breakdown (sub / del / ins, top confusions) of every validation pass (default: the YAML's error_report, else off)")
+    ap.add_argument("--score-map", default=None, help="three-column phone table the breakdown is scored under (default: the YAML's score_map, else none)")
+    ap.add_argument("--score-map-cols", default=None, choices=["60-48", "60-39", "48-39"], help="which fold of the table (default: the YAML's score_map_cols, else 48-39)")
     a = ap.parse_args()
     conf = yaml.safe_load(open(a.conf, "r"))
+    if a.error_report:
+        conf["error_report"] = True
+    if a.score_map is not None:
+        conf["score_map"] = a.score_map
+    if a.score_map_cols is not None:
+        conf["score_map_cols"] = a.score_map_cols
     if a.mask_padding:
         conf["mask_padding"] = True
     if a.max_grad_norm is not None:

@@ -68,6 +68,47 @@ class Decoder(object):
             self.num_char += len(ref)
         return char_errs, word_errs
 
+    # ---- error breakdown -------------------------------------------------------------------------------
+    def _device_ids(self, prob_tensor, frame_seq_len):
+        """The decoder's label ids where it produces them: (ids (B, T) int32, lengths (B) int32, status (B) int32 or None), on the device."""
+        raise NotImplementedError
+
+    def error_ops(self, prob_tensor, frame_seq_len, targets, target_sizes, class_map=None, stats=None):
+        """The error breakdown of one batch (ops.edit_ops on the label ids the decoder leaves on the device; the reference has no counterpart):
+        prob_tensor / frame_seq_len as `decode` takes them, targets the padded (B, Lmax) labels of the loader or the concatenated labels
+        `phone_word_error` takes (those on the host), class_map the fold of utils.scoring.load_phone_map, stats a utils.scoring.ErrorStats
+        that takes the totals and the confusion table.  Returns the six totals (sub, del, ins, cor, hyp_len, ref_len) of the batch: a list
+        of ints after ONE device-to-host copy (totals, table and the search's status words in one buffer) -- or, when `stats` accumulates
+        on the device, a device tensor and no copy at all (a beam search's status words are then not looked at: an utterance whose search
+        failed counts as an empty hypothesis)."""
+        ids, ids_len, status = self._device_ids(prob_tensor, frame_seq_len)
+        dev = ids.device
+        sizes = torch.as_tensor(np.asarray([int(n) for n in target_sizes], dtype=np.int64)) if not torch.is_tensor(target_sizes) else target_sizes
+        tg = targets if torch.is_tensor(targets) else torch.as_tensor(np.asarray(targets, dtype=np.int64))
+        if tg.dim() != 2:
+            rows = self._unflatten_targets(tg.reshape(-1).numpy(), sizes.tolist())
+            tg = torch.zeros((len(rows), max([len(r) for r in rows] + [1])), dtype=torch.int64)
+            for b, r in enumerate(rows):
+                tg[b, :len(r)] = torch.as_tensor(np.asarray(r, dtype=np.int64))
+        V = stats.V if stats is not None else None
+        on_device = stats is not None and stats.confusion.is_cuda
+        table = None
+        if stats is not None:
+            table = stats.confusion if on_device else torch.zeros((V + 1, V + 1), dtype=torch.int64, device=dev)
+        counts = ops.edit_ops(ids, ids_len, tg, sizes, class_map=class_map, num_classes=V, confusion=table).counts
+        if on_device:
+            tot = counts.sum(0, dtype=torch.int64)
+            stats.add(tot)
+            return tot
+        parts = [counts.sum(0, dtype=torch.int64)] + ([table.reshape(-1)] if table is not None else []) + ([status.to(torch.int64)] if status is not None else [])
+        blob = torch.cat(parts).cpu().numpy()
+        if status is not None:
+            from ctc_pytorch_amd.utils.BeamSearch import ctcBeamSearch
+            ctcBeamSearch._checked(None, None, blob[len(blob) - status.numel():])
+        if stats is not None:
+            stats.add(blob[:6], blob[6:6 + (V + 1) ** 2].reshape(V + 1, V + 1))
+        return [int(v) for v in blob[:6]]
+
     # ---- forced alignment ------------------------------------------------------------------------------
     def align(self, prob_tensor, frame_seq_len, targets, target_sizes, frame_stride=1):
         """Where each label of the KNOWN transcript sits in time (ops.ctc_forced_align: the best CTC path of the transcript; the reference
@@ -159,6 +200,10 @@ class GreedyDecoder(Decoder):
             voc = self._voc = (snap, self.space_idx, words)
         return ops.join_tokens(ids_c, len_c, voc[2], "")
 
+    def _device_ids(self, prob_tensor, frame_seq_len):
+        ids, out_len = ops.greedy_collapse(ops.argmax_last(_to_device(prob_tensor)), frame_seq_len, blank=self.blank_index)
+        return ids, out_len, None
+
     def decode(self, prob_tensor, frame_seq_len):
         """Same strings as the reference: each kept frame contributes ' '+phone when space_idx == -1."""
         lp = _to_device(prob_tensor)
@@ -182,6 +227,14 @@ class BeamDecoder(Decoder):
         if frame_seq_len is None:
             frame_seq_len = [lp.shape[0]] * lp.shape[1]
         return self._decoder.decode_strings_async(lp, frame_seq_len, input_is_prob=False)()
+
+    def _device_ids(self, prob_tensor, frame_seq_len=None):
+        lp = _to_device(prob_tensor)
+        if frame_seq_len is None:
+            frame_seq_len = [lp.shape[0]] * lp.shape[1]
+        d = self._decoder
+        ids, out_len, _, status = ops.beam_decode_device(lp, frame_seq_len, d._lm_table_on(lp.device), d.lm_alpha, d.beamWidth, d.blank_index, False)
+        return ids, out_len, status
 
     def decode_async(self, prob_tensor, frame_seq_len=None):
         """decode() enqueued on the current stream: returns a callable that waits for this batch alone and returns its strings

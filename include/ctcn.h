@@ -513,6 +513,32 @@ int ctcn_greedy_collapse(const int32_t *idx, size_t stride_t, size_t stride_b, c
  * (model_ctc.py:200).  max_b_len >= max(b_len). */
 int ctcn_edit_distance(const int32_t *a, const int32_t *a_len, const int64_t *b, const int64_t *b_len, int32_t *out, int B,
                        int lda, int ldb, int max_b_len, void *stream);
+/* ---------------------------------------------------------------------------------------------------
+ * Error breakdown (editops.hip): what lies behind that distance -- substitutions, deletions, insertions, the alignment, the confusion table.
+ * Definition.  h[0..nh) is the hypothesis and r[0..nr) the reference, both AFTER the class map:
+ *   D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j-1] + (h[i-1] != r[j-1]), D[i][j-1] + 1, D[i-1][j] + 1)
+ * The move of cell (i, j) is the first candidate, in this order, that attains the minimum: diagonal (a correct pair or a substitution),
+ * deletion (from (i, j-1): reference symbol j-1 has no partner), insertion (from (i-1, j): hypothesis symbol i-1 has none).  Row 0 has only
+ * deletions, column 0 only insertions.  The alignment is the chain of moves from (nh, nr) back to (0, 0), emitted in forward order: a
+ * function of the two sequences alone (h = [1], r = [1, 1]: del r0, cor;  h = [a, b], r = [b, a]: sub, sub).
+ * Class map: map (V int32, or NULL) is applied to both sequences before the recursion -- a value in [0, V) replaces the id, -1 removes the
+ * symbol (the sequence gets shorter), an id outside [0, V) passes through unchanged and never indexes anything.
+ *   a (B,lda) int32 / a_len (B) int32, b (B,ldb) int64 / b_len (B) int64: the operands and the length clamps of ctcn_edit_distance
+ *   (a_len to [0, lda], b_len to [0, min(max_b_len, ldb)]); nothing is read past the clamped lengths
+ *   counts (B,6) int32: sub, del, ins, cor, nh, nr (lengths after the map); sub + del + cor == nr, sub + ins + cor == nh, sub + del + ins ==
+ *   the Levenshtein distance of the mapped sequences
+ *   ali (B, lda + ldb, 2) int32 or NULL: the (reference id, hypothesis id) pairs, -1 = none, and (-1, -1) past the last pair;
+ *   ali_len (B) int32 or NULL: the number of pairs
+ *   conf ((V+1)*(V+1)) int64 or NULL, zeroed by the caller, ACCUMULATED into across calls (integer atomic adds: exact, independent of
+ *   order): [r][h] counts an aligned pair (correct pairs on the diagonal), row V the insertions by hypothesis class, column V the deletions
+ *   by reference class, [V][V] stays 0; pairs with a member outside [0, V) are counted in `counts` but not entered
+ * One wavefront per utterance; the 2-bit moves live in LDS where hypothesis, reference and moves fit in 64 KB (32 x (800 x <= 64): 17 KB),
+ * else in ws (ctcn_edit_ops_ws_bytes, 0 in the LDS case; 4-byte aligned).  max_b_len > 512: CTCN_EUNSUPPORTED (the range of the
+ * wavefront distance kernel).  map or conf given: V > 0. */
+size_t ctcn_edit_ops_ws_bytes(int B, int lda, int max_b_len);
+int ctcn_edit_ops(const int32_t *a, const int32_t *a_len, const int64_t *b, const int64_t *b_len, const int32_t *map, int V,
+                  int32_t *counts, int32_t *ali, int32_t *ali_len, long long *conf, int B, int lda, int ldb, int max_b_len, void *ws,
+                  size_t ws_bytes, void *stream);
 /* (loss, sum of dist[0..B), sum of tgt_len[0..B), *status or 0) as four doubles in out4 (device memory): the per-step statistics of the
  * reference's run_epoch (loss.item(), total_wer's numerator and denominator, timit/steps/train_ctc.py:55-60) plus the sticky hand-off
  * status, gathered in one launch so that the host can fetch them with one small copy a step later. */
@@ -573,6 +599,11 @@ long long ctcn_join_tokens(const int32_t *ids, long long row_stride, const int32
  * replaces: Decoder._edit_distance (ctcDecoder.py:131-150; cer :127-129 and wer :118-125 call it once per decoded utterance).  -1 on bad
  * arguments. */
 long long ctcn_levenshtein(const int32_t *a, long long na, const int32_t *b, long long nb);
+/* ctcn_levenshtein_ops: the alignment behind ctcn_levenshtein, by the move rule of ctcn_edit_ops (diagonal, then deletion, then insertion), host
+ * code: word- and string-level scoring, and the decode driver, whose hypotheses are on the host already.  counts4 = (sub, del, ins, cor);
+ * ali (nh + nr, 2) int32 or NULL: the (reference, hypothesis) pairs in forward order, -1 = none, (-1, -1) past the last pair.  Returns the
+ * number of pairs; CTCN_EINVAL on bad arguments (a NULL counts4 is one). */
+long long ctcn_levenshtein_ops(const int32_t *hyp, long long nh, const int32_t *ref, long long nr, long long *counts4, int32_t *ali);
 
 #ifdef __cplusplus
 }
