@@ -102,6 +102,8 @@ _SIGS = {
     "ctcn_comm_destroy": (I, [P]),
     "ctcn_diag_squat": (I, [I, I, I, ctypes.c_uint, P]),
     "ctcn_diag_pipeline_chunks": (I, [I, I, I, I, I, I, I, I, ctypes.c_uint]),
+    "ctcn_diag_gemm_plan": (I, [I] * 13 + [Z, ctypes.c_uint, I, I, I, I, P]),
+    "ctcn_diag_gemm_on_xcds": (I, [I, I, I, I, I, P, I, P, I, P, I, F, I, P, Z, P, ctypes.c_uint]),
     "ctcn_rnn_last_kernel": (ctypes.c_char_p, [I]),
     "ctcn_levenshtein": (ctypes.c_longlong, [P, ctypes.c_longlong, P, ctypes.c_longlong]),
     "ctcn_levenshtein_ops": (ctypes.c_longlong, [P, ctypes.c_longlong, P, ctypes.c_longlong, P, P]),

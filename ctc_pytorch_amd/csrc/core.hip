@@ -35,7 +35,6 @@ static int g_opt_gemm_tile256 = 1;      // 1: 256-row plane-GEMM tiles (global_l
 static int g_opt_gemm_dbg = 0;          // development: bit 0 = 256-tile GEMM skips its stores, bit 1 = skips its DMA loads (results invalid)
 static int g_opt_gemm_a_inline = 1;     // 1: 256-row tiles split a row-major float32 A operand while staging it (no plane pass over A)
 static int g_opt_conv_mfma = 1;         // 1: Conv2d forward / dgrad / wgrad as MFMA implicit GEMMs; 0: the direct kernels
-static int g_opt_gemm_pingpong = 1;     // 1: 256-row plane tiles run the ping-pong schedule (wave halves half a k-step apart)
 static int g_opt_rnn_mixed_slices = 0;  // forward recurrence: one workgroup per CU with mixed 12- / 4-unit slices (experiment)
 static int g_opt_rnn_fwd_tagged = 1;    // forward persistent recurrence: 1 = tagged gather (rnn_fwd_tagged) where it applies
 static int g_opt_rnn_fused_dropout = 1; // 1: ctcn_rnn_fwd_dropout stores the dropped output from inside rnn_fwd_tagged; 0: dropout kernel behind the recurrence
@@ -52,7 +51,7 @@ static int g_opt_rnn_rsv_nt = 0;        // rnn_bwd_scatter2: non-temporal hint o
 static int g_opt_gemm_bf16_single = 0;  // 256-row GEMM tiles: one bf16 product (ah*bh) instead of the three bf16x3 products (north_star's bf16 tolerance; gemm.hip)
 static int g_opt_xcd_interleave = 1;    // which physical XCD hosts group g of a persistent recurrence that leaves XCDs idle (eight XCDs; 0: XCD g, 1 (default): the even XCDs first, 2-5: other orders; the host's xcd_allow masks follow: ops._idle_xcd_mask)
 static int g_opt_bn_rows4 = 1;          // BatchNorm over (T*B, C) rows: column sums with 16-B loads (colreduce_rows4_kernel); 0: the dword kernel (colreduce_rows_kernel); dense and length-aware calls alike
-static int g_opt_tn_splits_force = 0;   // development (tools/gemm_tn_bench.py): split-K count of the TN tile, 0 = the rule of gemm.hip:tn_splits
+static int g_opt_tn_splits_force = 0;   // development (tools/gemm_tn_bench.py): split-K count of the TN tile, 0 = the rule of gemm.hip:plan_gemm
 static int g_opt_tn_splits_xcd = 1;     // TN weight-gradient tile: split count sized for the CUs of xcd_allow (one round of items there), not for the whole device
 static int g_opt_beam_generic_threads = 0;  // generic beam kernel: 0 = 256 threads per utterance up to W = 64 and 1 024 beyond; 256 / 512 / 1024 = forced
 static int g_opt_beam_bitonic = 1;      // generic beam kernel: 1 = up to 256 survivors of the pruning bound are ranked by a bitonic sort; 0 = by counting pairs (rounds 5-6)
@@ -100,7 +99,6 @@ static const OptionRow k_options[] = {
   {"tag_poll_delay", &g_opt_tag_poll_delay, [](int value) -> int { return value < 0 ? 0 : (value > 64 ? 64 : value); }},
   {"rnn_fwd_tagged", &g_opt_rnn_fwd_tagged, [](int value) -> int { return value ? 1 : 0; }},
   {"rnn_mixed_slices", &g_opt_rnn_mixed_slices, [](int value) -> int { return value ? 1 : 0; }},
-  {"gemm_pingpong", &g_opt_gemm_pingpong, [](int value) -> int { return value ? 1 : 0; }},
   {"gemm_a_inline", &g_opt_gemm_a_inline, [](int value) -> int { return value ? 1 : 0; }},
   {"gemm_dbg", &g_opt_gemm_dbg, [](int value) -> int { return value; }},
   {"gemm_tile256", &g_opt_gemm_tile256, [](int value) -> int { return value ? 1 : 0; }},

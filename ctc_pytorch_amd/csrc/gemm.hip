@@ -25,6 +25,11 @@ namespace {
 
 constexpr int BM = 128, BN = 128, BK = 16, PAD = 4;
 
+// XCD-aware tile order (bijective for any tile count): blocks b, b + 8, b + 16, ... share an XCD / L2; each XCD gets a contiguous band of tiles
+__device__ __forceinline__ int xcd_band_tile(int bid, int nt) {
+  const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
 // ---- global -> registers (8 floats per thread per operand slab) --------------------------------
 // KC: operand element (r, k) at src[(r0+r)*ld + k0+k]  (k contiguous)
 __device__ __forceinline__ void g2r_kc(const float *__restrict__ src, int ld, int r0, int R, int k0, int Kend,
@@ -162,13 +167,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(int M, int N, int K, cons
                                                        int tiles_m, int tiles_n, bool vecA, bool vecB) {
   __shared__ __attribute__((aligned(16))) float sA[BK][BM + PAD];
   __shared__ __attribute__((aligned(16))) float sB[BK][BN + PAD];
-  // XCD-aware remap (bijective for any tile count): blocks b, b+8, b+16.. share an XCD/L2.
-  const int nt = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = xcd_band_tile(blockIdx.x, tiles_m * tiles_n);
   f32_tile<TA, TB>(sA, sB, bid, blockIdx.y, M, N, K, A, lda, B, ldb, C, ldc, beta, kchunk, ws, tiles_n, vecA, vecB);
 }
 
@@ -284,12 +283,7 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(int M, int N, int K, c
   __shared__ __attribute__((aligned(16))) unsigned short sAh[BM][XLD], sAl[BM][XLD], sBh[BN][XLD], sBl[BN][XLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  const int nt = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = xcd_band_tile(blockIdx.x, tiles_m * tiles_n);
   const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
   const int kbeg = blockIdx.y * kchunk;
@@ -590,12 +584,7 @@ __global__ __launch_bounds__(256) void gemm_planes_nt_kernel(int M, int N, int K
                                                              const unsigned short *__restrict__ Bl, float *__restrict__ C, int ldc, float beta,
                                                              int kchunk, float *__restrict__ ws, int tiles_m, int tiles_n) {
   extern __shared__ __attribute__((aligned(16))) unsigned char psm[];       // Ah | Al | Bh | Bl tiles
-  const int nt = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = xcd_band_tile(blockIdx.x, tiles_m * tiles_n);
   plane_tile<TI, TJ>(psm, bid, blockIdx.y, M, N, Kp, Ah, Al, Bh, Bl, C, ldc, beta, kchunk, ws, tiles_n);
 }
 
@@ -632,149 +621,26 @@ __global__ __launch_bounds__(256) void gemm_planes_nt_queue_kernel(int M, int N,
 //   * 512 threads = 8 waves as 2 (M) x 4 (N); a wave owns 128 x 64 (or 128 x 32) outputs = 4 x WNT MFMA tiles of 32 x 32: 128 / 64
 //     accumulator VGPRs; per 16-k step 8 + 4 (or 8 + 2) ds_read_b128 feed 24 (12) v_mfma_f32_32x32x16_bf16;
 //   * 32-k stages, two LDS buffers (2 x 64 KB / 2 x 48 KB): the next stage is copied global -> LDS by the DMA path
-//     (global_load_lds_dwordx4: no staging VGPRs, no ds_write pass) while the current one is multiplied; ONE barrier per stage;
+//     (global_load_lds_dwordx4: no staging VGPRs, no ds_write pass) while the current one is multiplied;
 //   * LDS image: rows of 64 B (4 chunks of 16 B = 8 bf16), chunk' = chunk ^ ((row >> 2) & 3): the 16 lanes of every ds_read_b128
 //     group hit 16 distinct bank slots.  The DMA writes LDS lane-linearly, so the swizzle is applied to the SOURCE address;
 //   * same products, same k order inside a 16-k step and across steps as the 128 x 128 tile: bit-identical results.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool v_is_magic(float v) { return v == 1.2345678e33f; }   // (debug switch of tools/gemm_bench.py: keeps the accumulators live)
-__device__ __forceinline__ int qswz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
-template <int WNT>      // 32-column MFMA tiles per wave: 2 -> 256 x 256 workgroup tile, 1 -> 256 x 128
-__global__ __launch_bounds__(512) void gemm_planes_nt256_kernel(int M, int N, int Kp, const unsigned short *__restrict__ Ah,
-                                                                const unsigned short *__restrict__ Al, const unsigned short *__restrict__ Bh,
-                                                                const unsigned short *__restrict__ Bl, float *__restrict__ C, int ldc, float beta,
-                                                                int tiles_m, int tiles_n, int dbg) {
-  constexpr int TBM = 256, TBN = 128 * WNT;
-  constexpr int A_BYTES = TBM * 64, B_BYTES = TBN * 64;              // one plane of one stage
-  constexpr int STAGE = 2 * A_BYTES + 2 * B_BYTES;                   // Ah | Al | Bh | Bl
-  constexpr int IA = TBM * 4 / 512, IB = TBN * 4 / 512;              // DMA instructions per thread and plane
-  extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const int nt = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {   // XCD-aware remap: blocks b, b + 8, ... share an XCD / L2; give each XCD a contiguous band of tiles (N fastest: shared A panel)
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
-  const int m0 = tm * TBM, n0 = tn * TBN;
-
-  f32x16 acc[4][WNT];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < WNT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-
-  // DMA source offsets (elements) of this lane: LDS position p = (inst * 8 + wave) * 64 + lane -> row p >> 2, swizzled chunk p & 3
-  unsigned offA[IA], offB[IB];
-#pragma unroll
-  for (int i = 0; i < IA; ++i) {
-    const int p = (i * 8 + wave) * 64 + lane, row = p >> 2, chunk = (p & 3) ^ ((row >> 2) & 3);
-    offA[i] = (unsigned)min(m0 + row, M - 1) * (unsigned)Kp + chunk * 8;
-  }
-#pragma unroll
-  for (int i = 0; i < IB; ++i) {
-    const int p = (i * 8 + wave) * 64 + lane, row = p >> 2, chunk = (p & 3) ^ ((row >> 2) & 3);
-    offB[i] = (unsigned)min(n0 + row, N - 1) * (unsigned)Kp + chunk * 8;
-  }
-  typedef const __attribute__((address_space(1))) void *gptr_t;
-  typedef __attribute__((address_space(3))) void *lptr_t;
-  auto issue = [&](int k0, int buf) {
-    unsigned char *sb = qsm + buf * STAGE;
-#pragma unroll
-    for (int i = 0; i < IA; ++i) {
-      const int dst = (i * 8 + wave) * 1024;
-      __builtin_amdgcn_global_load_lds((gptr_t)(Ah + offA[i] + k0), (lptr_t)(sb + dst), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gptr_t)(Al + offA[i] + k0), (lptr_t)(sb + A_BYTES + dst), 16, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < IB; ++i) {
-      const int dst = (i * 8 + wave) * 1024;
-      __builtin_amdgcn_global_load_lds((gptr_t)(Bh + offB[i] + k0), (lptr_t)(sb + 2 * A_BYTES + dst), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gptr_t)(Bl + offB[i] + k0), (lptr_t)(sb + 2 * A_BYTES + B_BYTES + dst), 16, 0, 0);
-    }
-  };
-  const int nst = Kp / 32;
-  const int ml = lane & 31, g = lane >> 5;
-  // fragment loads of one 16-k half: 8 + 2*WNT ds_read_b128
-  auto load_frags = [&](const unsigned char *sb, int ks, bf16x8_t (&ah)[4], bf16x8_t (&al)[4], bf16x8_t (&bh)[WNT], bf16x8_t (&bl)[WNT]) {
-    const int cq = ks * 2 + g;
-#pragma unroll
-    for (int j = 0; j < WNT; ++j) {
-      const int o = qswz(wn * 32 * WNT + j * 32 + ml, cq);
-      bh[j] = *reinterpret_cast<const bf16x8_t *>(sb + 2 * A_BYTES + o);
-      bl[j] = *reinterpret_cast<const bf16x8_t *>(sb + 2 * A_BYTES + B_BYTES + o);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int o = qswz(wm * 128 + i * 32 + ml, cq);
-      ah[i] = *reinterpret_cast<const bf16x8_t *>(sb + o);
-      al[i] = *reinterpret_cast<const bf16x8_t *>(sb + A_BYTES + o);
-    }
-  };
-  auto multiply = [&](const bf16x8_t (&ah)[4], const bf16x8_t (&al)[4], const bf16x8_t (&bh)[WNT], const bf16x8_t (&bl)[WNT]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < WNT; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);   // small terms first
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-      }
-  };
-  issue(0, 0);
-  for (int s = 0; s < nst; ++s) {
-    __syncthreads();                       // stage s has landed (the DMA is waited for here), everybody is done with stage s - 1
-    const unsigned char *sb = qsm + (s & 1) * STAGE;
-    // Both 16-k halves of the stage are requested from LDS up front (two register sets): the second half's reads return behind
-    // the first half's 24 MFMAs instead of behind an s_waitcnt in front of every second MFMA group (the compiler's own
-    // schedule waited nine times per stage with 2-4 reads in flight)
-    bf16x8_t ah0[4], al0[4], bh0[WNT], bl0[WNT], ah1[4], al1[4], bh1[WNT], bl1[WNT];
-    load_frags(sb, 0, ah0, al0, bh0, bl0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (s + 1 < nst && !(dbg & 2)) issue((s + 1) * 32, (s + 1) & 1);
-    __builtin_amdgcn_sched_barrier(0);
-    load_frags(sb, 1, ah1, al1, bh1, bl1);
-    __builtin_amdgcn_sched_barrier(0);
-    multiply(ah0, al0, bh0, bl0);
-    __builtin_amdgcn_sched_barrier(0);
-    multiply(ah1, al1, bh1, bl1);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < WNT; ++j) {
-      const int col = n0 + wn * 32 * WNT + j * 32 + (lane & 31);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = m0 + wm * 128 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        if (row < M && col < N && (!(dbg & 1) || v_is_magic(acc[i][j][e]))) {
-          float v = acc[i][j][e];
-          float *p = C + (size_t)row * ldc + col;
-          if (beta != 0.0f) v += beta * *p;
-          if (dbg & 4) __builtin_nontemporal_store(v, p); else *p = v;
-        }
-      }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Ping-pong schedule of the same tile (MI355X_MICROARCH.md "Two waves per SIMD"): the workgroup's two waves on a SIMD share that
-// SIMD's matrix pipe, so when all eight waves run the same phase (barrier -> LDS reads -> 48 MFMAs) the pipe idles through every
-// read / DMA-issue phase.  Here the wave halves (waves 0-3 = rows 0-127, waves 4-7 = rows 128-255; one of each per SIMD) run
-// half a 16-k step apart: while one half issues its 24 MFMAs the other fetches its next fragments from LDS and issues its share
-// of the next stage's DMA; an s_barrier separates the phases (4 per 32-k stage).  Per stage s:
+// Ping-pong schedule (MI355X_MICROARCH.md "Two waves per SIMD"): the workgroup's two waves on a SIMD share that SIMD's matrix pipe,
+// so if all eight waves ran the same phase (barrier -> LDS reads -> 48 MFMAs) the pipe would idle through every read / DMA-issue
+// phase (the lock-step form this tile replaced: DESIGN_HISTORY.md).  The wave halves (waves 0-3 = rows 0-127, waves 4-7 = rows
+// 128-255; one of each per SIMD) run half a 16-k step apart: while one half issues its 24 MFMAs the other fetches its next
+// fragments from LDS and issues its share of the next stage's DMA; an s_barrier separates the phases (4 per 32-k stage).  Per stage s:
 //     phase 4s     A: read fragments (s, k-half 0)                              B: multiply (s-1, 1)
 //     phase 4s+1   A: multiply (s, 0) + DMA share of stage s+1                  B: read (s, 0)
 //     phase 4s+2   A: read (s, 1), own DMA pieces landed                        B: multiply (s, 0) + DMA share of s+1
 //     phase 4s+3   A: multiply (s, 1)                                           B: read (s, 1), own DMA pieces landed
 // Buffer (s+1)&1 is rewritten from phase 4s+1 on: its last readers were phases 4s-2 (A) and 4s-1 (B); it is first read in 4s+4.
-// Same products in the same order per accumulator: bit-identical to the other plane tiles.
+// (The accumulator clear, the DMA source offsets, the C-store epilogue and the queue loop of the XCD-filtered forms are spelled out in
+// every kernel that has them: as shared inline helpers each of them changed the register allocation or the instruction count of a tile.)
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool v_is_magic(float v) { return v == 1.2345678e33f; }   // (debug switch of tools/gemm_bench.py: keeps the accumulators live)
+__device__ __forceinline__ int qswz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
+
 // (sched_barrier: MFMAs are register-only instructions, a "memory" clobber alone lets the scheduler carry them across the barrier
 // into the other phase -- which is exactly what the phases exist to prevent)
 __device__ __forceinline__ void pp_barrier() {
@@ -835,6 +701,7 @@ __device__ __forceinline__ void planes256pp_tile(unsigned char *qsm, int bid, in
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
 
+  // DMA source offsets (elements) of this lane: LDS position p = (inst * 8 + wave) * 64 + lane -> row p >> 2, swizzled chunk p & 3
   unsigned offA[IA], offB[IB];
 #pragma unroll
   for (int i = 0; i < IA; ++i) {
@@ -996,12 +863,7 @@ __global__ __launch_bounds__(512) void gemm_planes_nt256pp_kernel(int M, int N, 
                                                                   const unsigned short *__restrict__ Bl, float *__restrict__ C, int ldc, float beta,
                                                                   int tiles_m, int tiles_n, int dbg) {
   extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
-  const int nt = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = xcd_band_tile(blockIdx.x, tiles_m * tiles_n);
   planes256pp_tile<WNT, NP>(qsm, bid, M, N, Kp, Ah, Al, Bh, Bl, C, ldc, beta, tiles_n, dbg);
 }
 
@@ -1028,145 +890,10 @@ __global__ __launch_bounds__(512) void gemm_planes_nt256pp_queue_kernel(int M, i
   }
 }
 
-// The same tile with the A operand taken straight from the float32 matrix (row-major, k contiguous) and split into hi / lo bf16
-// while it is staged: no plane pass over A (for da = 25 600 x 2 560 that pass moves 524 MB, 91 us -- a third of the product's
-// own time).  Per stage a thread loads its 16 floats (64 B of one row) a stage ahead into registers, and after the stage's
-// MFMAs converts them (the same split_bf16 as the plane pass: identical planes, bit-identical results) and writes four 16-B
-// chunks into the other LDS buffer; the conversion is VALU work next to the other wave's MFMAs.  B (the weights) still comes
-// pre-split through the DMA path.
-template <int WNT>
-__global__ __launch_bounds__(512) void gemm_planes_nt256_af32_kernel(int M, int N, int K, int Kp, const float *__restrict__ A, int lda,
-                                                                     const unsigned short *__restrict__ Bh, const unsigned short *__restrict__ Bl,
-                                                                     float *__restrict__ C, int ldc, float beta, int tiles_m, int tiles_n) {
-  constexpr int TBM = 256, TBN = 128 * WNT;
-  constexpr int A_BYTES = TBM * 64, B_BYTES = TBN * 64;
-  constexpr int STAGE = 2 * A_BYTES + 2 * B_BYTES;
-  constexpr int IB = TBN * 4 / 512;
-  extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const int nt = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
-  const int m0 = tm * TBM, n0 = tn * TBN;
-
-  f32x16 acc[4][WNT];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < WNT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-
-  unsigned offB[IB];
-#pragma unroll
-  for (int i = 0; i < IB; ++i) {
-    const int p = (i * 8 + wave) * 64 + lane, row = p >> 2, chunk = (p & 3) ^ ((row >> 2) & 3);
-    offB[i] = (unsigned)min(n0 + row, N - 1) * (unsigned)Kp + chunk * 8;
-  }
-  typedef const __attribute__((address_space(1))) void *gptr_t;
-  typedef __attribute__((address_space(3))) void *lptr_t;
-  auto issue_b = [&](int k0, int buf) {
-    unsigned char *sb = qsm + buf * STAGE + 2 * A_BYTES;
-#pragma unroll
-    for (int i = 0; i < IB; ++i) {
-      const int dst = (i * 8 + wave) * 1024;
-      __builtin_amdgcn_global_load_lds((gptr_t)(Bh + offB[i] + k0), (lptr_t)(sb + dst), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gptr_t)(Bl + offB[i] + k0), (lptr_t)(sb + B_BYTES + dst), 16, 0, 0);
-    }
-  };
-  // A staging of this thread: row tid >> 1 of the tile, 16 consecutive k (two 16-B bf16 chunks per plane)
-  const int arow = tid >> 1, akh = (tid & 1) * 16;
-  const float *aptr = A + (size_t)min(m0 + arow, M - 1) * lda + akh;
-  f32x4 av[4];
-  // (bare loads from clamped addresses: a select on the loaded value would make the wave wait for the load where it is issued;
-  // K % 4 == 0, so a 16-B piece is inside the matrix or outside it as a whole, and the ones outside are zeroed when they are split)
-  auto load_a = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) av[q] = *reinterpret_cast<const f32x4 *>(aptr + min(k0 + 4 * q, max(K - akh - 4, 0)));
-  };
-  auto store_a = [&](int buf, int k0) {
-    unsigned char *sb = qsm + buf * STAGE;
-    if (k0 + 32 > K) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (k0 + akh + 4 * q >= K) av[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      unsigned hw[4], lw[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        unsigned short h0, l0, h1, l1;
-        split_bf16(av[2 * h + (e >> 1)][(e & 1) * 2], h0, l0);
-        split_bf16(av[2 * h + (e >> 1)][(e & 1) * 2 + 1], h1, l1);
-        hw[e] = (unsigned)h0 | ((unsigned)h1 << 16);
-        lw[e] = (unsigned)l0 | ((unsigned)l1 << 16);
-      }
-      const int o = qswz(arow, (tid & 1) * 2 + h);
-      *reinterpret_cast<u32x4 *>(sb + o) = (u32x4){hw[0], hw[1], hw[2], hw[3]};
-      *reinterpret_cast<u32x4 *>(sb + A_BYTES + o) = (u32x4){lw[0], lw[1], lw[2], lw[3]};
-    }
-  };
-  const int nst = Kp / 32;
-  const int ml = lane & 31, g = lane >> 5;
-  load_a(0);
-  issue_b(0, 0);
-  store_a(0, 0);
-  for (int s = 0; s < nst; ++s) {
-    __syncthreads();                       // stage s is in LDS (A written by the waves, B landed), everybody is done with stage s - 1
-    if (s + 1 < nst) { load_a((s + 1) * 32); issue_b((s + 1) * 32, (s + 1) & 1); }
-    const unsigned char *sb = qsm + (s & 1) * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int cq = ks * 2 + g;
-      bf16x8_t ah[4], al[4], bh[WNT], bl[WNT];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int o = qswz(wm * 128 + i * 32 + ml, cq);
-        ah[i] = *reinterpret_cast<const bf16x8_t *>(sb + o);
-        al[i] = *reinterpret_cast<const bf16x8_t *>(sb + A_BYTES + o);
-      }
-#pragma unroll
-      for (int j = 0; j < WNT; ++j) {
-        const int o = qswz(wn * 32 * WNT + j * 32 + ml, cq);
-        bh[j] = *reinterpret_cast<const bf16x8_t *>(sb + 2 * A_BYTES + o);
-        bl[j] = *reinterpret_cast<const bf16x8_t *>(sb + 2 * A_BYTES + B_BYTES + o);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < WNT; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);   // small terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
-    if (s + 1 < nst) store_a((s + 1) & 1, (s + 1) * 32);  // (the other buffer: last read in stage s - 1, released by the barrier above)
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < WNT; ++j) {
-      const int col = n0 + wn * 32 * WNT + j * 32 + (lane & 31);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = m0 + wm * 128 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        if (row < M && col < N) {
-          float v = acc[i][j][e];
-          float *p = C + (size_t)row * ldc + col;
-          if (beta != 0.0f) v += beta * *p;
-          *p = v;
-        }
-      }
-    }
-}
-
-// The float32-A tile in the ping-pong schedule of gemm_planes_nt256pp_kernel (one instruction stream, half B one barrier behind):
+// The float32-A tile: the same tile with the A operand taken straight from the float32 matrix (row-major, k contiguous) and split
+// into hi / lo bf16 while it is staged: no plane pass over A (for da = 25 600 x 2 560 that pass moves 524 MB, 91 us -- a third of the
+// product's own time).  B (the weights) still comes pre-split through the DMA path.  The ping-pong schedule of
+// gemm_planes_nt256pp_kernel (one instruction stream, half B one barrier behind):
 //     read (s, k-half 0) | multiply + the wave's DMA pieces of B(s+1) | read (s, 1), convert + store A(s+1), own DMA landed |
 //     multiply + global loads of A(s+2)
 // A thread stages its own 16 floats of a row of A: loaded during the second multiply of stage s-1, split into hi / lo (the same
@@ -1184,12 +911,7 @@ __global__ __launch_bounds__(512) void gemm_planes_nt256pp_af32_kernel(int M, in
   extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
-  const int nt = tiles_m * tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid & 7, q = nt >> 3, r = nt & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int bid = xcd_band_tile(blockIdx.x, tiles_m * tiles_n);
   const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
   const int m0 = tm * TBM, n0 = tn * TBN;
 
@@ -1442,8 +1164,6 @@ __global__ __launch_bounds__(512) void gemm_planes_nt256pp_af32_kernel(int M, in
     }
 }
 
-
-__global__ void splitk_reduce_kernel(const float *__restrict__ ws, float *__restrict__ C, int M, int N, int ldc, int splits, float beta);
 
 // ------------------------------------------------------------------------------------------------
 // TN tile: C = A^T B for two CONTRACTION-MAJOR float32 operands (A: K x M, B: K x N, k the slow index) -- the weight gradients
@@ -1705,101 +1425,6 @@ __global__ __launch_bounds__(512) void gemm_tn_f32_pp_kernel(int M, int N, int K
   }
 }
 
-// split count and launch of the TN tile; `part` must hold splits * M * N floats when splits > 1
-static int tn_splits(int M, int N, int K, int wnt, size_t part_bytes, int cus) {
-  const int tiles = ceil_div(M, 256) * ceil_div(N, 128 * wnt);
-  // `cus`: the CUs the launch may run on -- 256, or (round 5, option "tn_splits_xcd") the CUs of the XCDs of xcd_allow: one round of items there
-  // instead of two rounds of half-length items (each item pays a prologue, a 128-KB partial store and its share of the reduce pass)
-  int s = std::min(std::max(cus / tiles, 1), std::max(K / 512, 1));      // <= 256 items: one round on a whole device
-  s = std::min(s, 32);                                                    // (a handful of tiles: the reduce pass over the partials would take over)
-  if (const int f = ctcn_get_option("tn_splits_force")) s = std::min(f, std::max(K / 64, 1));       // (development)
-  s = std::min(s, (int)(part_bytes / ((size_t)M * N * sizeof(float))));
-  return s < 2 ? 1 : s;
-}
-// option "gemm_bf16_single" (default 0): 1 = the 256-row tiles (plane, float32-A and TN forms: every product of T*B rows) multiply the bf16 roundings of
-// their operands ONCE (ah*bh, f32 accumulate) instead of the three bf16x3 products -- the "bf16 tolerance" BASELINE.json's north_star states
-// (loss / activations within 1e-3), against the default's f32-equivalent 1e-5.  The recurrent matmul and the small tiles keep bf16x3.
-static bool bf16_single() { return ctcn_get_option("gemm_bf16_single") != 0; }
-
-template <int WNT>
-static int launch_tn(hipStream_t st, int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc, float beta, int splits,
-                     float *part, unsigned xcd_allow, unsigned *queue) {
-  const int tiles_m = ceil_div(M, 256), tiles_n = ceil_div(N, 128 * WNT);
-  int kchunk = ceil_div(ceil_div(K, splits), 32) * 32;
-  splits = ceil_div(K, kchunk);
-  const size_t lds = (size_t)2 * (2 * 256 * 64 + 2 * 128 * WNT * 64);
-  auto kern = bf16_single() ? gemm_tn_f32_pp_kernel<WNT, 1> : gemm_tn_f32_pp_kernel<WNT, 3>;
-  CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  CTCN_HIP(hipMemsetAsync(queue, 0, 128, st));              // the queue word, and at +64 the 16 zero bytes pieces outside the operands are loaded from
-  const int nx = std::min(ctcn_device_xcds(), 16);
-  const unsigned xcd_mask = xcd_allow ? xcd_allow : (nx > 1 ? (1u << nx) - 1u : 0xffffu);
-  hipLaunchKernelGGL(kern, dim3(ctcn_device_cus()), dim3(512), lds, st, M, N, K, A, lda, B, ldb, C, ldc, beta, kchunk, splits, part, tiles_m, tiles_n, xcd_mask,
-                     queue);
-  CTCN_LAUNCH_CHECK();
-  if (splits > 1) {
-    const size_t total = (size_t)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)std::min((size_t)2048, ceil_div_z(total, 256))), dim3(256), 0, st, (const float *)part, C, M, N, ldc,
-                       splits, beta);
-    CTCN_LAUNCH_CHECK();
-  }
-  return CTCN_OK;
-}
-
-template <int WNT>
-static int launch_planes256_af32(hipStream_t st, int M, int N, int K, int Kp, const float *A, int lda, const unsigned short *bh, const unsigned short *bl,
-                                 float *C, int ldc, float beta) {
-  const int tiles_m = ceil_div(M, 256), tiles_n = ceil_div(N, 128 * WNT);
-  const size_t lds = (size_t)2 * (2 * 256 * 64 + 2 * 128 * WNT * 64);
-  auto kern = ctcn_get_option("gemm_pingpong") ? (bf16_single() ? gemm_planes_nt256pp_af32_kernel<WNT, 1> : gemm_planes_nt256pp_af32_kernel<WNT, 3>)
-                                               : gemm_planes_nt256_af32_kernel<WNT>;
-  CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, st, M, N, K, Kp, A, lda, bh, bl, C, ldc, beta, tiles_m, tiles_n);
-  return CTCN_OK;
-}
-
-template <int WNT>
-static int launch_planes256(hipStream_t st, int M, int N, int Kp, const unsigned short *ah, const unsigned short *al, const unsigned short *bh,
-                            const unsigned short *bl, float *C, int ldc, float beta) {
-  const int tiles_m = ceil_div(M, 256), tiles_n = ceil_div(N, 128 * WNT);
-  const size_t lds = (size_t)2 * (2 * 256 * 64 + 2 * 128 * WNT * 64);
-  const int dbg = ctcn_get_option("gemm_dbg");
-  auto kern = ctcn_get_option("gemm_pingpong") ? (bf16_single() ? gemm_planes_nt256pp_kernel<WNT, 1> : gemm_planes_nt256pp_kernel<WNT, 3>)
-                                               : gemm_planes_nt256_kernel<WNT>;
-  CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(512), lds, st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, tiles_m, tiles_n, dbg);
-  return CTCN_OK;
-}
-
-template <int WNT>
-static int launch_planes256_queue(hipStream_t st, int M, int N, int Kp, const unsigned short *ah, const unsigned short *al, const unsigned short *bh,
-                                  const unsigned short *bl, float *C, int ldc, float beta, unsigned xcd_allow, unsigned *queue) {
-  const int tiles_m = ceil_div(M, 256), tiles_n = ceil_div(N, 128 * WNT);
-  const size_t lds = (size_t)2 * (2 * 256 * 64 + 2 * 128 * WNT * 64);
-  auto kern = bf16_single() ? gemm_planes_nt256pp_queue_kernel<WNT, 1> : gemm_planes_nt256pp_queue_kernel<WNT, 3>;
-  CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(ctcn_device_cus()), dim3(512), lds, st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, tiles_m, tiles_n, xcd_allow, queue);
-  return CTCN_OK;
-}
-
-// launch one of the three tile shapes (dynamic LDS = 2 planes x (BM + BN) rows x 128 B)
-template <int TI, int TJ>
-static int launch_planes(bool queued, int nt, int psplits, hipStream_t st, int M, int N, int Kp, const unsigned short *ah, const unsigned short *al,
-                         const unsigned short *bh, const unsigned short *bl, float *C, int ldc, float beta, int pchunk, float *part, int tiles_m,
-                         int tiles_n, unsigned xcd_allow, unsigned *queue) {
-  const size_t lds = (size_t)2 * (64 * TI + 64 * TJ) * 128;
-  if (queued) {
-    auto kern = gemm_planes_nt_queue_kernel<TI, TJ>;
-    if (lds > 64 * 1024) CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(2 * ctcn_device_cus()), dim3(256), lds, st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, pchunk, part, tiles_m, tiles_n,
-                       psplits, xcd_allow, queue);
-  } else {
-    auto kern = gemm_planes_nt_kernel<TI, TJ>;
-    if (lds > 64 * 1024) CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nt, psplits), dim3(256), lds, st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, pchunk, part, tiles_m, tiles_n);
-  }
-  return CTCN_OK;
-}
-
 __global__ void splitk_reduce_kernel(const float *__restrict__ ws, float *__restrict__ C, int M, int N, int ldc,
                                      int splits, float beta) {
   const size_t total = (size_t)M * N;
@@ -1859,15 +1484,225 @@ __global__ void transpose01_kernel(const float *__restrict__ in, float *__restri
 
 }  // namespace
 
+// ================================================================================================
+// Host side.  plan_gemm decides -- which of the nine kernel families, its tiling, the split-K count, the operand split passes, the
+// workspace layout, the grid -- by arithmetic alone; gemm_core carries a plan out.  ctcn_diag_gemm_plan shows the plan to the CPU tests.
+// ================================================================================================
+enum GemmPath { GP_F32 = 0, GP_F32_QUEUE, GP_BF16X3, GP_PLANES128, GP_PLANES128_QUEUE, GP_PLANES256, GP_PLANES256_AF32, GP_PLANES256_QUEUE, GP_TN };
+enum SplitPass { SP_NONE = 0, SP_ROWS, SP_TRANSPOSE, SP_TRANSPOSE_QUEUE };      // how an operand becomes bf16 planes in the workspace
+struct GemmShape { int transA, transB, M, N, K, lda, ldb, ldc, precision, b_shift; };
+struct GemmOptions { int tile256, a_inline, tn, big_tiles, tn_splits_xcd, tn_splits_force; };
+struct GemmEnv {
+  int a_mod16, b_mod16;          // A and B modulo 16 bytes
+  bool has_ws;
+  size_t ws_bytes;
+  unsigned xcd_allow;            // 0 = whole device; otherwise the XCDs the workgroups may run on (side stream next to a recurrence)
+  bool same_a, same_b;           // the workspace still holds this call's A / B planes (GemmPlanes)
+  int cus, xcds;
+  GemmOptions opt;
+};
+struct GemmPlan {
+  GemmPath path;
+  int ti, tj;                    // workgroup tile = 64 ti x 64 tj
+  int wnt;                       // 256-row tiles: 32-column MFMA tiles per wave
+  int splits, kchunk;            // split-K
+  SplitPass split_a, split_b;
+  int Kp;                        // plane paths: K rounded up to the planes' 64-k slabs
+  size_t off_al, off_bh, off_bl, off_part, off_queue;      // workspace layout (bytes): [Ah | Al | Bh | Bl | split-K partials ... queue words]
+  int tiles_m, tiles_n;
+  unsigned grid_x, grid_y;
+  bool vecA, vecB;               // direct kernels: 16-B loads of the operand
+  unsigned xcd_mask;             // TN tile: the XCDs its queue runs on
+};
+static bool uses_planes(GemmPath p) { return p >= GP_PLANES128 && p <= GP_PLANES256_QUEUE; }
+static GemmOptions gemm_options() {
+  return {ctcn_get_option("gemm_tile256"), ctcn_get_option("gemm_a_inline"), ctcn_get_option("gemm_tn"), ctcn_opt_gemm_big_tiles(),
+          ctcn_get_option("tn_splits_xcd"), ctcn_get_option("tn_splits_force")};
+}
+static int check_gemm_shape(const GemmShape &g) {
+  CTCN_REQUIRE(g.precision == 0 || g.precision == 1, "ctcn_gemm: precision %d (0 = f32 MFMA, 1 = bf16x3 split MFMA)", g.precision);
+  CTCN_REQUIRE(g.M > 0 && g.N > 0 && g.K >= 0, "ctcn_gemm: bad dims M=%d N=%d K=%d", g.M, g.N, g.K);
+  CTCN_REQUIRE(g.lda >= (g.transA ? g.M : g.K) && g.ldb >= (g.transB ? g.K : g.N) && g.ldc >= g.N, "ctcn_gemm: leading dim too small");
+  return CTCN_OK;
+}
+// pre-split planes in the workspace: Ah | Al (M x Kp each) | Bh | Bl (N x Kp each), then the split-K partials
+struct PlaneLayout { int Kp; size_t a_el, b_el, bytes; };
+static PlaneLayout plane_layout(int M, int N, int K) {
+  const int Kp = ceil_div(K, PBK) * PBK;
+  const size_t a_el = (size_t)M * Kp, b_el = (size_t)N * Kp;
+  return {Kp, a_el, b_el, align_up(2 * (a_el + b_el) * sizeof(unsigned short), 256)};
+}
 // the TN tile (gemm_tn_f32_pp_kernel) takes C = A^T B with 16-B aligned rows of whole float4 pieces, large K, and a workspace for its
 // queue word (+ the split-K partials)
-static bool tn_eligible(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B, int ldb, int precision, const void *ws,
-                        size_t ws_bytes) {
-  return precision == 1 && transA && !transB && ws && ws_bytes >= 1024 && ctcn_get_option("gemm_tn") != 0 && M >= 128 && N >= 32 && K >= 1024 &&
-         M % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
-         lda < (1 << 24) && ldb < (1 << 24);                     // (eight rows of a piece behind one 32-bit buffer offset)
+static bool tn_eligible(const GemmShape &g, const GemmEnv &e) {
+  return g.precision == 1 && g.transA && !g.transB && e.has_ws && e.ws_bytes >= 1024 && e.opt.tn != 0 && g.M >= 128 && g.N >= 32 && g.K >= 1024 &&
+         g.M % 4 == 0 && g.N % 4 == 0 && g.lda % 4 == 0 && g.ldb % 4 == 0 && e.a_mod16 == 0 && e.b_mod16 == 0 &&
+         g.lda < (1 << 24) && g.ldb < (1 << 24);                 // (eight rows of a piece behind one 32-bit buffer offset)
 }
-// xcd_allow: 0 = whole device; otherwise (precision 1 plane path only) the XCDs the GEMM workgroups may run on
+
+static GemmPlan plan_gemm(const GemmShape &g, const GemmEnv &e) {
+  const int M = g.M, N = g.N, K = g.K;
+  const size_t mn_bytes = (size_t)M * N * sizeof(float);
+  GemmPlan p = {};
+  p.splits = 1;
+  // the last 256 bytes of the workspace hold the work queue of the XCD-filtered variants and of the TN tile
+  p.off_queue = e.ws_bytes >= 256 ? (e.ws_bytes - 256) & ~(size_t)255 : 0;
+  if (tn_eligible(g, e) && g.b_shift == 0) {
+    // both operands contraction-major (weight gradients): the TN tile reads the float32 rows as they are -- no plane pass
+    p.path = GP_TN;
+    p.wnt = ceil_div(N, 256) * 256 == ceil_div(N, 128) * 128 ? 2 : 1;     // (N = 640 as 3 x 256 or 5 x 128: the same time)
+    p.ti = 4; p.tj = 2 * p.wnt;
+    p.tiles_m = ceil_div(M, 256); p.tiles_n = ceil_div(N, 128 * p.wnt);
+    // the CUs the launch may run on -- 256, or (round 5, option "tn_splits_xcd") the CUs of the XCDs of xcd_allow: one round of items there
+    // instead of two rounds of half-length items (each item pays a prologue, a 128-KB partial store and its share of the reduce pass)
+    int cus = 256;
+    if (e.xcd_allow && e.opt.tn_splits_xcd != 0) {
+      const int nx = std::max(1, std::min(e.xcds, 16));
+      cus = std::max(e.cus / nx * __builtin_popcount(e.xcd_allow & ((1u << nx) - 1u)), 32);
+    }
+    const int tiles = p.tiles_m * p.tiles_n;
+    int s = std::min(std::max(cus / tiles, 1), std::max(K / 512, 1));      // <= 256 items: one round on a whole device
+    s = std::min(s, 32);                                                    // (a handful of tiles: the reduce pass over the partials would take over)
+    if (const int f = e.opt.tn_splits_force) s = std::min(f, std::max(K / 64, 1));       // (development)
+    s = std::min(s, (int)((e.ws_bytes - 512) / mn_bytes));                  // the partials: splits * M * N floats at the workspace's start
+    if (s < 2) s = 1;
+    p.kchunk = ceil_div(ceil_div(K, s), 32) * 32;
+    p.splits = ceil_div(K, p.kchunk);
+    const int nx = std::min(e.xcds, 16);
+    p.xcd_mask = e.xcd_allow ? e.xcd_allow : (nx > 1 ? (1u << nx) - 1u : 0xffffu);
+    p.grid_x = e.cus; p.grid_y = 1;
+    return p;
+  }
+  const PlaneLayout lay = plane_layout(M, N, K);
+  if (g.precision == 1 && K >= 64 && e.has_ws && e.ws_bytes >= lay.bytes + 1024) {
+    const int Kp = p.Kp = lay.Kp;
+    p.off_al = lay.a_el * sizeof(unsigned short); p.off_bh = 2 * p.off_al; p.off_bl = p.off_bh + lay.b_el * sizeof(unsigned short);
+    p.off_part = lay.bytes;
+    const size_t part_bytes = e.ws_bytes - lay.bytes - 512;
+    p.kchunk = Kp;
+    const SplitPass pass_a = g.transA == 0 ? SP_ROWS : (e.xcd_allow ? SP_TRANSPOSE_QUEUE : SP_TRANSPOSE);
+    const SplitPass pass_b = g.transB != 0 ? SP_ROWS : (e.xcd_allow ? SP_TRANSPOSE_QUEUE : SP_TRANSPOSE);
+    p.split_b = e.same_b ? SP_NONE : pass_b;
+    // activation-sized products (M = T*B): the 256-row tiles, when they give the device at least ~0.75 workgroups per CU; a
+    // row-major A (k contiguous) is then split while it is staged, without a plane pass of its own
+    const int wnt256 = (N % 256 == 0 || (N > 512 && ceil_div(N, 256) * 256 - N <= N / 8)) ? 2 : 1;
+    const int t256_m = ceil_div(M, 256), t256_n = ceil_div(N, 128 * wnt256);
+    const bool use256 = !e.xcd_allow && e.opt.tile256 != 0 && M >= 1024 && N >= 96 && (long)t256_m * t256_n * 4 >= (long)e.cus * 3;
+    // (every N-tile converts its A rows again.  Stand-alone the inline split now wins at every shape of the bench configurations --
+    // 25 600 x 1 280 x 640: 134 vs 150 us, 25 600 x 640 x 2 560: 278 vs 354 us, 25 600 x 2 560 x 640 (10 N-tiles): 253 vs 262 us,
+    // 76 800 x 3 072 x 1 024 (12 N-tiles): 1 333 vs 1 351 us -- but with a limit of 16 N-tiles instead of 5 no step got faster (cfg2
+    // 13.74 / 13.75 ms in an A/B inside one session, cfg4 58.2 vs 57.6-58.3), so the limit stays where it was tested longest)
+    const bool a_inline = use256 && !e.same_a && !g.transA && e.opt.a_inline != 0 && K >= 32 && K % 4 == 0 && g.lda % 4 == 0 && e.a_mod16 == 0 &&
+                          t256_n <= 5;
+    p.split_a = (a_inline || e.same_a) ? SP_NONE : pass_a;
+    // side stream: the 256-row tiles from a queue when they fill the allowed XCDs' CUs at least 3/4 in whole rounds of one tile per CU
+    // (the chunk GEMMs of the pipelined input projection are sized for that: rnn.hip)
+    bool queue256 = false;
+    if (e.xcd_allow && e.opt.tile256 != 0 && M >= 1024 && N >= 96) {
+      const int cus = e.cus / std::max(1, std::min(e.xcds, 16)) * __builtin_popcount(e.xcd_allow);
+      const int t256 = t256_m * t256_n, rounds = ceil_div(t256, std::max(cus, 1));
+      queue256 = cus > 0 && t256 * 4 >= rounds * cus * 3;
+    }
+    if (use256 || queue256) {
+      p.path = a_inline ? GP_PLANES256_AF32 : (use256 ? GP_PLANES256 : GP_PLANES256_QUEUE);
+      p.wnt = wnt256; p.ti = 4; p.tj = 2 * wnt256;
+      p.tiles_m = t256_m; p.tiles_n = t256_n;
+      p.grid_x = queue256 ? e.cus : t256_m * t256_n; p.grid_y = 1;
+      return p;
+    }
+    // tile shape: 128x128 (two workgroups per CU).  Option gemm_big_tiles: 256x128 / 128x256 tiles (one per CU, 96 KB of LDS)
+    // when they fill the device at least once without more padding -- 25 % fewer LDS fragment reads per MFMA, yet measured
+    // 7 % SLOWER at cfg2 / 4 % at cfg4 (the second resident workgroup hides the staging barriers better), so off by default
+    p.ti = p.tj = 2; p.tiles_m = ceil_div(M, BM); p.tiles_n = ceil_div(N, BN);
+    {
+      const long t22 = (long)p.tiles_m * p.tiles_n * 128 * 128;
+      const int m42 = ceil_div(M, 256), n42 = ceil_div(N, 128), m24 = ceil_div(M, 128), n24 = ceil_div(N, 256);
+      const long t42 = (long)m42 * n42 * 256 * 128, t24 = (long)m24 * n24 * 128 * 256;
+      const bool ok42 = m42 * n42 >= e.cus && t42 <= t22 + t22 / 32, ok24 = m24 * n24 >= e.cus && t24 <= t22 + t22 / 32;
+      if (e.opt.big_tiles && (ok42 || ok24)) {
+        if (ok24 && (!ok42 || t24 <= t42)) { p.tj = 4; p.tiles_m = m24; p.tiles_n = n24; }
+        else { p.ti = 4; p.tiles_m = m42; p.tiles_n = n42; }
+      }
+    }
+    const int pnt = p.tiles_m * p.tiles_n;
+    if (pnt < 256 && Kp >= 1024 && part_bytes >= 2 * mn_bytes) {
+      p.splits = std::min(std::min(ceil_div(512, pnt), Kp / 512), (int)(part_bytes / mn_bytes));
+      if (p.splits < 2) p.splits = 1;
+    }
+    if (p.splits > 1) {
+      p.kchunk = ceil_div(ceil_div(Kp, p.splits), PBK) * PBK;
+      p.splits = ceil_div(Kp, p.kchunk);
+    }
+    p.path = e.xcd_allow ? GP_PLANES128_QUEUE : GP_PLANES128;
+    p.grid_x = e.xcd_allow ? 2 * e.cus : pnt; p.grid_y = e.xcd_allow ? 1 : p.splits;
+    return p;
+  }
+  // the direct kernels: 128 x 128 tiles, operands staged (and, precision 1, split) from the float32 matrices
+  p.ti = p.tj = 2; p.tiles_m = ceil_div(M, BM); p.tiles_n = ceil_div(N, BN);
+  const int nt = p.tiles_m * p.tiles_n;
+  if (nt < 256 && K >= 512 && e.has_ws && e.ws_bytes >= 2 * mn_bytes) {
+    p.splits = std::min(std::min(ceil_div(512, nt), K / 256), (int)(e.ws_bytes / mn_bytes));
+    if (p.splits < 2) p.splits = 1;
+  }
+  p.kchunk = K;
+  if (p.splits > 1) {
+    p.kchunk = ceil_div(ceil_div(K, p.splits), XBK) * XBK;
+    p.splits = ceil_div(K, p.kchunk);
+  }
+  p.vecA = e.a_mod16 == 0 && g.lda % 4 == 0;
+  p.vecB = e.b_mod16 == 0 && g.ldb % 4 == 0;
+  // precision 0 on a side stream next to a persistent recurrence: tiles from an atomic queue, workgroups off the allowed XCDs exit
+  const bool queued = g.precision == 0 && e.xcd_allow && e.has_ws && e.ws_bytes >= (p.splits > 1 ? p.splits * mn_bytes : 0) + 512;
+  p.path = g.precision == 1 ? GP_BF16X3 : (queued ? GP_F32_QUEUE : GP_F32);
+  p.grid_x = queued ? 2 * e.cus : nt; p.grid_y = queued ? 1 : p.splits;
+  return p;
+}
+
+extern "C" int ctcn_diag_gemm_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, int ldc, int precision, int b_shift, int a_mod16,
+                                   int b_mod16, int has_ws, size_t ws_bytes, unsigned xcd_allow, int same_a, int same_b, int cus, int xcds, int *out) {
+  const GemmShape g = {transA, transB, M, N, K, lda, ldb, ldc, precision, b_shift};
+  if (const int rc = check_gemm_shape(g)) return rc;
+  CTCN_REQUIRE(out && cus > 0 && xcds > 0 && a_mod16 >= 0 && a_mod16 < 16 && b_mod16 >= 0 && b_mod16 < 16, "ctcn_diag_gemm_plan: bad args");
+  const GemmPlan p = plan_gemm(g, {a_mod16, b_mod16, has_ws != 0, ws_bytes, xcd_allow, same_a != 0, same_b != 0, cus, xcds, gemm_options()});
+  const int v[CTCN_GEMM_PLAN_INTS] = {p.path, p.ti, p.tj, p.wnt, p.splits, p.kchunk, p.split_a, p.split_b, (int)p.grid_x, (int)p.grid_y, p.vecA, p.vecB};
+  memcpy(out, v, sizeof(v));
+  return CTCN_OK;
+}
+
+// option "gemm_bf16_single" (default 0): 1 = the 256-row tiles (plane, float32-A and TN forms: every product of T*B rows) multiply the bf16 roundings of
+// their operands ONCE (ah*bh, f32 accumulate) instead of the three bf16x3 products -- the "bf16 tolerance" BASELINE.json's north_star states
+// (loss / activations within 1e-3), against the default's f32-equivalent 1e-5.  The recurrent matmul and the small tiles keep bf16x3.
+static bool bf16_single() { return ctcn_get_option("gemm_bf16_single") != 0; }
+
+// f(integral_constant) for a runtime value that takes one of two / three forms
+template <class F> static int with_wnt(int wnt, F f) { return wnt == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 1>{}); }
+template <class F> static void with_trans(int ta, int tb, F f) {
+  if (ta) { if (tb) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+  else    { if (tb) f(std::false_type{}, std::true_type{}); else f(std::false_type{}, std::false_type{}); }
+}
+// one of the 256-row kernels: 512 threads, two stages of (256 + 128 wnt) rows x 64 B x 2 planes of dynamic LDS
+template <class Kern, class... Args>
+static int launch_tile256(Kern kern, unsigned grid, int wnt, hipStream_t st, Args... args) {
+  const size_t lds = (size_t)2 * (2 * 256 * 64 + 2 * 128 * wnt * 64);
+  CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, args...);
+  return CTCN_OK;
+}
+// one operand -> its hi / lo bf16 planes (rows x Kp, k contiguous); `queue`: the next free queue word of an XCD-filtered pass
+static void launch_split(SplitPass pass, hipStream_t st, const float *src, int ld, int rows, int K, int Kp, unsigned short *hi, unsigned short *lo, int shift,
+                         unsigned xcd_allow, unsigned *queue) {
+  if (pass == SP_ROWS) {                      // src[row*ld + k]
+    const size_t total = (size_t)rows * (Kp / 4);
+    hipLaunchKernelGGL(split_rows_kernel, dim3((unsigned)std::min((size_t)8192, ceil_div_z(total, 256))), dim3(256), 0, st, src, ld, rows, K, Kp, hi, lo);
+  } else if (pass == SP_TRANSPOSE_QUEUE) {    // src[k*ld + row] -> transpose
+    hipLaunchKernelGGL(split_transpose_queue_kernel, dim3(ctcn_opt_side_split_wgs() * ctcn_device_cus()), dim3(256), 0, st, src, ld, K, rows, Kp, hi, lo,
+                       ceil_div(rows, 64), ceil_div(Kp, 64), xcd_allow, queue, shift);
+  } else if (pass == SP_TRANSPOSE) {
+    hipLaunchKernelGGL(split_transpose_kernel, dim3(ceil_div(rows, 64), ceil_div(Kp, 64)), dim3(256), 0, st, src, ld, K, rows, Kp, hi, lo, shift);
+  }
+}
+
+// xcd_allow: 0 = whole device; otherwise the XCDs the GEMM workgroups may run on
 // b_shift: ctcn_gemm_shift_b's shift of B along k, applied while B is split (plane path only)
 static int gemm_core(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C,
                      int ldc, float beta, int precision, void *ws, size_t ws_bytes, void *stream, unsigned xcd_allow, GemmPlanes *planes, int b_shift) {
@@ -1875,215 +1710,151 @@ static int gemm_core(int transA, int transB, int M, int N, int K, const float *A
   GemmPlanes &pl = planes ? *planes : scratch_planes;
   const bool want_same_a = pl.same_a, want_same_b = pl.same_b;
   pl.same_a = pl.same_b = false;              // one-shot
-  CTCN_REQUIRE(precision == 0 || precision == 1, "ctcn_gemm: precision %d (0 = f32 MFMA, 1 = bf16x3 split MFMA)", precision);
-  CTCN_REQUIRE(M > 0 && N > 0 && K >= 0, "ctcn_gemm: bad dims M=%d N=%d K=%d", M, N, K);
+  const GemmShape g = {transA, transB, M, N, K, lda, ldb, ldc, precision, b_shift};
+  if (const int rc = check_gemm_shape(g)) return rc;
   CTCN_REQUIRE(A && B && C, "ctcn_gemm: null pointer");
-  CTCN_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "ctcn_gemm: leading dim too small");
   // A, B and C may start on any 4 bytes (every 16-byte access to them is chosen from the pointer: vecA / vecB, split_transpose_tile, the inline
   // A split, the TN tile, the split-K reduce); the workspace may not: bf16 planes, partials and queue words are carved from it by offset alone
   CTCN_REQUIRE(!ws || (uintptr_t)ws % 16 == 0, "ctcn_gemm: the workspace must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const int tiles_m = ceil_div(M, BM), tiles_n = ceil_div(N, BN);
-  const int nt = tiles_m * tiles_n;
-  int splits = 1;
-  if (nt < 256 && K >= 512 && ws && ws_bytes >= (size_t)2 * M * N * sizeof(float)) {
-    splits = ceil_div(512, nt);
-    splits = min(splits, K / 256);
-    splits = min(splits, (int)(ws_bytes / ((size_t)M * N * sizeof(float))));
-    if (splits < 2) splits = 1;
-  }
-  int kchunk = K;
-  if (splits > 1) {
-    kchunk = ceil_div(ceil_div(K, splits), XBK) * XBK;
-    splits = ceil_div(K, kchunk);
-  }
-  if (tn_eligible(transA, transB, M, N, K, A, lda, B, ldb, precision, ws, ws_bytes) && b_shift == 0) {
-    // both operands contraction-major (weight gradients): the TN tile reads the float32 rows as they are -- no plane pass
-    pl.a_valid = false; pl.b_valid = false;
-    const int wnt = ceil_div(N, 256) * 256 == ceil_div(N, 128) * 128 ? 2 : 1;     // (N = 640 as 3 x 256 or 5 x 128: the same time)
-    unsigned *queue = (unsigned *)((char *)ws + ((ws_bytes - 256) & ~(size_t)255));
-    int tn_cus = 256;
-    if (xcd_allow && ctcn_get_option("tn_splits_xcd") != 0) {
-      const int nx = std::max(1, std::min(ctcn_device_xcds(), 16));
-      tn_cus = std::max(ctcn_device_cus() / nx * __builtin_popcount(xcd_allow & ((1u << nx) - 1u)), 32);
-    }
-    const int tsplits = tn_splits(M, N, K, wnt, ws_bytes - 512, tn_cus);
-    return wnt == 2 ? launch_tn<2>(st, M, N, K, A, lda, B, ldb, C, ldc, beta, tsplits, (float *)ws, xcd_allow, queue)
-                    : launch_tn<1>(st, M, N, K, A, lda, B, ldb, C, ldc, beta, tsplits, (float *)ws, xcd_allow, queue);
-  }
-  if (precision == 1 && K >= 64 && ws) {
-    // pre-split planes in the workspace: [Ah | Al | Bh | Bl | split-K partials]
-    const int Kp = ceil_div(K, PBK) * PBK;
-    const size_t a_el = (size_t)M * Kp, b_el = (size_t)N * Kp;
-    const size_t plane_bytes = align_up(2 * (a_el + b_el) * sizeof(unsigned short), 256);
-    if (ws_bytes >= plane_bytes + 1024) {
-      unsigned short *ah = (unsigned short *)ws, *al = ah + a_el, *bh = al + a_el, *bl = bh + b_el;
-      float *part = (float *)((char *)ws + plane_bytes);
-      // the last 256 bytes of the workspace hold the work queue of the XCD-filtered variant
-      unsigned *queue = (unsigned *)((char *)ws + ((ws_bytes - 256) & ~(size_t)255));
-      const size_t part_bytes = ws_bytes - plane_bytes - 512;
-      if (xcd_allow) CTCN_HIP(hipMemsetAsync(queue, 0, 16, st));
-      int nq = 0;      // queue words 1, 2: the operand splits
-      auto split = [&](const float *src, int ld, bool contraction_major, int rows, unsigned short *hi, unsigned short *lo, int shift) {
-        if (!contraction_major) {   // src[row*ld + k]
-          const size_t total = (size_t)rows * (Kp / 4);
-          hipLaunchKernelGGL(split_rows_kernel, dim3((unsigned)std::min((size_t)8192, ceil_div_z(total, 256))), dim3(256), 0, st, src, ld, rows, K, Kp, hi, lo);
-        } else {                    // src[k*ld + row] -> transpose
-          if (xcd_allow)
-            hipLaunchKernelGGL(split_transpose_queue_kernel, dim3(ctcn_opt_side_split_wgs() * ctcn_device_cus()), dim3(256), 0, st, src, ld, K, rows, Kp, hi, lo, ceil_div(rows, 64),
-                               ceil_div(Kp, 64), xcd_allow, queue + (++nq), shift);
-          else
-            hipLaunchKernelGGL(split_transpose_kernel, dim3(ceil_div(rows, 64), ceil_div(Kp, 64)), dim3(256), 0, st, src, ld, K, rows, Kp, hi, lo, shift);
-        }
-      };
-      const bool same_a = want_same_a && pl.a_valid && pl.A == A && pl.lda == lda && pl.M == M && pl.Ka == K && pl.transA == transA && pl.ws_a == ws &&
-                          pl.st_a == (void *)st;
-      const bool same_b = want_same_b && pl.b_valid && pl.B == B && pl.ldb == ldb && pl.N == N && pl.Kb == K && pl.transB == transB && pl.shift == b_shift &&
-                          pl.ws_b == ws && pl.st_b == (void *)st && pl.bh == (const void *)bh;
-      pl.B = B; pl.ldb = ldb; pl.N = N; pl.Kb = K; pl.transB = transB; pl.shift = b_shift; pl.ws_b = ws;
-      pl.st_b = (void *)st; pl.bh = (const void *)bh; pl.b_valid = true;     // (every branch below leaves B's planes at bh / bl)
-      // activation-sized products (M = T*B): the 256-row tiles, when they give the device at least ~0.75 workgroups per CU; a
-      // row-major A (k contiguous) is then split while it is staged, without a plane pass of its own
-      const int wnt256 = (N % 256 == 0 || (N > 512 && ceil_div(N, 256) * 256 - N <= N / 8)) ? 2 : 1;
-      const bool use256 = !xcd_allow && ctcn_get_option("gemm_tile256") != 0 && M >= 1024 && N >= 96 &&
-                          (long)ceil_div(M, 256) * ceil_div(N, 128 * wnt256) * 4 >= (long)ctcn_device_cus() * 3;
-      // (every N-tile converts its A rows again.  Stand-alone the inline split now wins at every shape of the bench configurations --
-      // 25 600 x 1 280 x 640: 134 vs 150 us, 25 600 x 640 x 2 560: 278 vs 354 us, 25 600 x 2 560 x 640 (10 N-tiles): 253 vs 262 us,
-      // 76 800 x 3 072 x 1 024 (12 N-tiles): 1 333 vs 1 351 us -- but with a limit of 16 N-tiles instead of 5 no step got faster (cfg2
-      // 13.74 / 13.75 ms in an A/B inside one session, cfg4 58.2 vs 57.6-58.3), so the limit stays where it was tested longest)
-      const bool a_inline = use256 && !same_a && !transA && ctcn_get_option("gemm_a_inline") != 0 && K >= 32 && K % 4 == 0 && lda % 4 == 0 &&
-                            ((uintptr_t)A & 15) == 0 && ceil_div(N, 128 * wnt256) <= 5;
-      if (a_inline) {
-        pl.a_valid = false;                         // no A planes in the workspace after this call
-        if (!same_b) split(B, ldb, transB == 0, N, bh, bl, b_shift);
-        CTCN_LAUNCH_CHECK();
-        const int lrc = wnt256 == 2 ? launch_planes256_af32<2>(st, M, N, K, Kp, A, lda, bh, bl, C, ldc, beta)
-                                    : launch_planes256_af32<1>(st, M, N, K, Kp, A, lda, bh, bl, C, ldc, beta);
-        if (lrc) return lrc;
-        CTCN_LAUNCH_CHECK();
-        return CTCN_OK;
-      }
-      if (!same_a) split(A, lda, transA != 0, M, ah, al, 0);
+  char *const wsb = (char *)ws;
+  const void *bh_here = wsb + 2 * plane_layout(M, N, K).a_el * sizeof(unsigned short);       // where this call's B planes would lie
+  GemmEnv e = {(int)((uintptr_t)A & 15), (int)((uintptr_t)B & 15), ws != nullptr, ws_bytes, xcd_allow, false, false, ctcn_device_cus(), 0, gemm_options()};
+  e.same_a = want_same_a && pl.a_valid && pl.A == A && pl.lda == lda && pl.M == M && pl.Ka == K && pl.transA == transA && pl.ws_a == ws && pl.st_a == (void *)st;
+  e.same_b = want_same_b && pl.b_valid && pl.B == B && pl.ldb == ldb && pl.N == N && pl.Kb == K && pl.transB == transB && pl.shift == b_shift &&
+             pl.ws_b == ws && pl.st_b == (void *)st && pl.bh == bh_here;
+  // (the XCD count is read by the side-stream rules and the TN tile only, and its first query probes the device: calls that cannot need it do not ask)
+  if (xcd_allow || tn_eligible(g, e)) e.xcds = ctcn_device_xcds();
+  const GemmPlan p = plan_gemm(g, e);
+
+  unsigned short *ah = (unsigned short *)wsb, *al = (unsigned short *)(wsb + p.off_al), *bh = (unsigned short *)(wsb + p.off_bh),
+                 *bl = (unsigned short *)(wsb + p.off_bl);
+  float *part = p.splits > 1 ? (float *)(wsb + p.off_part) : nullptr;
+  unsigned *queue = (unsigned *)(wsb + p.off_queue);
+  pl.a_valid = pl.b_valid = false;            // what the workspace holds after this call
+  if (uses_planes(p.path)) {
+    pl.B = B; pl.ldb = ldb; pl.N = N; pl.Kb = K; pl.transB = transB; pl.shift = b_shift; pl.ws_b = ws;
+    pl.st_b = (void *)st; pl.bh = (const void *)bh; pl.b_valid = true;
+    if (p.path != GP_PLANES256_AF32) {
       pl.A = A; pl.lda = lda; pl.M = M; pl.Ka = K; pl.transA = transA; pl.ws_a = ws; pl.st_a = (void *)st;
       pl.a_valid = true;
-      if (!same_b) split(B, ldb, transB == 0, N, bh, bl, b_shift);
-      CTCN_LAUNCH_CHECK();
-      // tile shape: 128x128 (two workgroups per CU).  Option gemm_big_tiles: 256x128 / 128x256 tiles (one per CU, 96 KB of LDS)
-      // when they fill the device at least once without more padding -- 25 % fewer LDS fragment reads per MFMA, yet measured
-      // 7 % SLOWER at cfg2 / 4 % at cfg4 (the second resident workgroup hides the staging barriers better), so off by default
-      int shape = 0, ptm = tiles_m, ptn = tiles_n;
-      {
-        const long t22 = (long)tiles_m * tiles_n * 128 * 128;
-        const int m42 = ceil_div(M, 256), n42 = ceil_div(N, 128), m24 = ceil_div(M, 128), n24 = ceil_div(N, 256);
-        const long t42 = (long)m42 * n42 * 256 * 128, t24 = (long)m24 * n24 * 128 * 256;
-        const int min_tiles = ctcn_device_cus();
-        const bool ok42 = m42 * n42 >= min_tiles && t42 <= t22 + t22 / 32, ok24 = m24 * n24 >= min_tiles && t24 <= t22 + t22 / 32;
-        if (ctcn_opt_gemm_big_tiles() && (ok42 || ok24)) {
-          if (ok24 && (!ok42 || t24 <= t42)) { shape = 2; ptm = m24; ptn = n24; }
-          else { shape = 1; ptm = m42; ptn = n42; }
-        }
-      }
-      if (use256) {
-        const int lrc256 = wnt256 == 2 ? launch_planes256<2>(st, M, N, Kp, ah, al, bh, bl, C, ldc, beta)
-                                       : launch_planes256<1>(st, M, N, Kp, ah, al, bh, bl, C, ldc, beta);
-        if (lrc256) return lrc256;
-        CTCN_LAUNCH_CHECK();
-        return CTCN_OK;
-      }
-      // side stream: the 256-row tiles from a queue when they fill the allowed XCDs' CUs at least 3/4 in whole rounds of one tile per CU
-      // (the chunk GEMMs of the pipelined input projection are sized for that: rnn.hip)
-      if (xcd_allow && ctcn_get_option("gemm_tile256") != 0 && ctcn_get_option("gemm_pingpong") != 0 && M >= 1024 && N >= 96) {
-        const int cus = ctcn_device_cus() / std::max(1, std::min(ctcn_device_xcds(), 16)) * __builtin_popcount(xcd_allow);
-        const int t256 = ceil_div(M, 256) * ceil_div(N, 128 * wnt256), rounds = ceil_div(t256, std::max(cus, 1));
-        if (cus > 0 && t256 * 4 >= rounds * cus * 3) {
-          const int lrc = wnt256 == 2 ? launch_planes256_queue<2>(st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, xcd_allow, queue)
-                                      : launch_planes256_queue<1>(st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, xcd_allow, queue);
-          if (lrc) return lrc;
-          CTCN_LAUNCH_CHECK();
-          return CTCN_OK;
-        }
-      }
-      const int pnt = ptm * ptn;
-      int psplits = 1;
-      if (pnt < 256 && Kp >= 1024 && part_bytes >= (size_t)2 * M * N * sizeof(float)) {
-        psplits = std::min(std::min(ceil_div(512, pnt), Kp / 512), (int)(part_bytes / ((size_t)M * N * sizeof(float))));
-        if (psplits < 2) psplits = 1;
-      }
-      int pchunk = Kp;
-      if (psplits > 1) {
-        pchunk = ceil_div(ceil_div(Kp, psplits), PBK) * PBK;
-        psplits = ceil_div(Kp, pchunk);
-      }
-      float *pp = psplits > 1 ? part : (float *)nullptr;
-      int lrc;
-      if (shape == 1) lrc = launch_planes<4, 2>(xcd_allow != 0, pnt, psplits, st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, pchunk, pp, ptm, ptn, xcd_allow, queue);
-      else if (shape == 2) lrc = launch_planes<2, 4>(xcd_allow != 0, pnt, psplits, st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, pchunk, pp, ptm, ptn, xcd_allow, queue);
-      else lrc = launch_planes<2, 2>(xcd_allow != 0, pnt, psplits, st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, pchunk, pp, ptm, ptn, xcd_allow, queue);
-      if (lrc) return lrc;
-      CTCN_LAUNCH_CHECK();
-      if (psplits > 1) {
-        const size_t total = (size_t)M * N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)std::min((size_t)2048, ceil_div_z(total, 256))), dim3(256), 0, st, (const float *)part, C, M,
-                           N, ldc, psplits, beta);
-        CTCN_LAUNCH_CHECK();
-      }
-      return CTCN_OK;
     }
+    if (xcd_allow) CTCN_HIP(hipMemsetAsync(queue, 0, 16, st));
+    int nq = 0;      // queue words 1, 2: the operand splits
+    launch_split(p.split_a, st, A, lda, M, K, p.Kp, ah, al, 0, xcd_allow, queue + (p.split_a == SP_TRANSPOSE_QUEUE ? ++nq : 0));
+    launch_split(p.split_b, st, B, ldb, N, K, p.Kp, bh, bl, b_shift, xcd_allow, queue + (p.split_b == SP_TRANSPOSE_QUEUE ? ++nq : 0));
+    CTCN_LAUNCH_CHECK();
   }
-  pl.a_valid = false; pl.b_valid = false;                        // not the plane path: nothing to reuse
-  const bool vecA = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0);
-  const bool vecB = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0);
-  float *wsp = splits > 1 ? (float *)ws : nullptr;
-  dim3 grid(nt, splits), block(256);
-#define LAUNCH(KERN, TA, TB)                                                                             \
-  hipLaunchKernelGGL((KERN<TA, TB>), grid, block, 0, st, M, N, K, A, lda, B, ldb, C, ldc, beta, kchunk, wsp, \
-                     tiles_m, tiles_n, vecA, vecB)
-  if (precision == 0 && xcd_allow && ws && ws_bytes >= (size_t)splits * M * N * sizeof(float) * (splits > 1 ? 1 : 0) + 512) {
-    // side stream next to a persistent recurrence: tiles from an atomic queue, workgroups off the allowed XCDs exit
-    unsigned *queue = (unsigned *)((char *)ws + ((ws_bytes - 256) & ~(size_t)255));
-    CTCN_HIP(hipMemsetAsync(queue, 0, 4, st));
-    const dim3 qgrid(2 * ctcn_device_cus());
-#define QLAUNCH(TA, TB)                                                                                              \
-  hipLaunchKernelGGL((gemm_f32_queue_kernel<TA, TB>), qgrid, block, 0, st, M, N, K, A, lda, B, ldb, C, ldc, beta, kchunk, wsp, \
-                     tiles_m, tiles_n, vecA, vecB, splits, xcd_allow, queue)
-    if (transA) { if (transB) QLAUNCH(true, true); else QLAUNCH(true, false); }
-    else        { if (transB) QLAUNCH(false, true); else QLAUNCH(false, false); }
-#undef QLAUNCH
-  } else if (precision == 0) {
-    if (transA) { if (transB) LAUNCH(gemm_f32_kernel, true, true); else LAUNCH(gemm_f32_kernel, true, false); }
-    else        { if (transB) LAUNCH(gemm_f32_kernel, false, true); else LAUNCH(gemm_f32_kernel, false, false); }
-  } else {
-    if (transA) { if (transB) LAUNCH(gemm_bf16x3_kernel, true, true); else LAUNCH(gemm_bf16x3_kernel, true, false); }
-    else        { if (transB) LAUNCH(gemm_bf16x3_kernel, false, true); else LAUNCH(gemm_bf16x3_kernel, false, false); }
+  const int tiles_m = p.tiles_m, tiles_n = p.tiles_n, Kp = p.Kp, kchunk = p.kchunk, splits = p.splits;
+  const dim3 grid(p.grid_x, p.grid_y);
+  int rc = CTCN_OK;
+  switch (p.path) {
+    case GP_TN:
+      CTCN_HIP(hipMemsetAsync(queue, 0, 128, st));              // the queue word, and at +64 the 16 zero bytes pieces outside the operands are loaded from
+      rc = with_wnt(p.wnt, [&](auto W) {
+        constexpr int WNT = decltype(W)::value;
+        return launch_tile256(bf16_single() ? gemm_tn_f32_pp_kernel<WNT, 1> : gemm_tn_f32_pp_kernel<WNT, 3>, p.grid_x, WNT, st, M, N, K, A, lda, B, ldb, C, ldc,
+                              beta, kchunk, splits, part, tiles_m, tiles_n, p.xcd_mask, queue);
+      });
+      break;
+    case GP_PLANES256_AF32:
+      rc = with_wnt(p.wnt, [&](auto W) {
+        constexpr int WNT = decltype(W)::value;
+        return launch_tile256(bf16_single() ? gemm_planes_nt256pp_af32_kernel<WNT, 1> : gemm_planes_nt256pp_af32_kernel<WNT, 3>, p.grid_x, WNT, st, M, N, K, Kp,
+                              A, lda, (const unsigned short *)bh, (const unsigned short *)bl, C, ldc, beta, tiles_m, tiles_n);
+      });
+      break;
+    case GP_PLANES256:
+      rc = with_wnt(p.wnt, [&](auto W) {
+        constexpr int WNT = decltype(W)::value;
+        return launch_tile256(bf16_single() ? gemm_planes_nt256pp_kernel<WNT, 1> : gemm_planes_nt256pp_kernel<WNT, 3>, p.grid_x, WNT, st, M, N, Kp,
+                              (const unsigned short *)ah, (const unsigned short *)al, (const unsigned short *)bh, (const unsigned short *)bl, C, ldc, beta,
+                              tiles_m, tiles_n, ctcn_get_option("gemm_dbg"));
+      });
+      break;
+    case GP_PLANES256_QUEUE:
+      rc = with_wnt(p.wnt, [&](auto W) {
+        constexpr int WNT = decltype(W)::value;
+        return launch_tile256(bf16_single() ? gemm_planes_nt256pp_queue_kernel<WNT, 1> : gemm_planes_nt256pp_queue_kernel<WNT, 3>, p.grid_x, WNT, st, M, N, Kp,
+                              (const unsigned short *)ah, (const unsigned short *)al, (const unsigned short *)bh, (const unsigned short *)bl, C, ldc, beta,
+                              tiles_m, tiles_n, xcd_allow, queue);
+      });
+      break;
+    case GP_PLANES128:
+    case GP_PLANES128_QUEUE: {
+      // one of the three tile shapes (dynamic LDS = 2 planes x (BM + BN) rows x 128 B)
+      auto launch = [&](auto TI_, auto TJ_) {
+        constexpr int TI = decltype(TI_)::value, TJ = decltype(TJ_)::value;
+        const size_t lds = (size_t)2 * (64 * TI + 64 * TJ) * 128;
+        if (p.path == GP_PLANES128_QUEUE) {
+          auto kern = gemm_planes_nt_queue_kernel<TI, TJ>;
+          if (lds > 64 * 1024) CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+          hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, kchunk, part, tiles_m, tiles_n, splits, xcd_allow, queue);
+        } else {
+          auto kern = gemm_planes_nt_kernel<TI, TJ>;
+          if (lds > 64 * 1024) CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+          hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, M, N, Kp, ah, al, bh, bl, C, ldc, beta, kchunk, part, tiles_m, tiles_n);
+        }
+        return (int)CTCN_OK;
+      };
+      constexpr std::integral_constant<int, 2> two{};
+      constexpr std::integral_constant<int, 4> four{};
+      rc = p.ti == 4 ? launch(four, two) : (p.tj == 4 ? launch(two, four) : launch(two, two));
+      break;
+    }
+    case GP_F32_QUEUE:
+      CTCN_HIP(hipMemsetAsync(queue, 0, 4, st));
+      with_trans(transA, transB, [&](auto TA, auto TB) {
+        hipLaunchKernelGGL((gemm_f32_queue_kernel<decltype(TA)::value, decltype(TB)::value>), grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C, ldc, beta, kchunk,
+                           part, tiles_m, tiles_n, p.vecA, p.vecB, splits, xcd_allow, queue);
+      });
+      break;
+    case GP_F32:
+      with_trans(transA, transB, [&](auto TA, auto TB) {
+        hipLaunchKernelGGL((gemm_f32_kernel<decltype(TA)::value, decltype(TB)::value>), grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C, ldc, beta, kchunk, part,
+                           tiles_m, tiles_n, p.vecA, p.vecB);
+      });
+      break;
+    case GP_BF16X3:
+      with_trans(transA, transB, [&](auto TA, auto TB) {
+        hipLaunchKernelGGL((gemm_bf16x3_kernel<decltype(TA)::value, decltype(TB)::value>), grid, dim3(256), 0, st, M, N, K, A, lda, B, ldb, C, ldc, beta, kchunk,
+                           part, tiles_m, tiles_n, p.vecA, p.vecB);
+      });
+      break;
   }
-#undef LAUNCH
+  if (rc) return rc;
   CTCN_LAUNCH_CHECK();
-  if (splits > 1) {
+  if (splits > 1) {                           // the partials are summed in split order, whichever workgroup made them
     const size_t total = (size_t)M * N;
-    const int blocks = (int)min((size_t)2048, ceil_div_z(total, 256));
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float *)ws, C, M, N, ldc, splits, beta);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)std::min((size_t)2048, ceil_div_z(total, 256))), dim3(256), 0, st, (const float *)part, C, M, N, ldc,
+                       splits, beta);
     CTCN_LAUNCH_CHECK();
   }
   return CTCN_OK;
+}
+
+int ctcn_gemm_on_xcds(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C,
+                      int ldc, float beta, int precision, void *ws, size_t ws_bytes, void *stream, unsigned xcd_allow, GemmPlanes *planes) {
+  return gemm_core(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, beta, precision, ws, ws_bytes, stream, xcd_allow, planes, 0);
+}
+extern "C" int ctcn_diag_gemm_on_xcds(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc,
+                                      float beta, int precision, void *ws, size_t ws_bytes, void *stream, unsigned xcd_allow) {
+  return gemm_core(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, beta, precision, ws, ws_bytes, stream, xcd_allow, nullptr, 0);
 }
 
 // C = A^T * shift_k(B) for contraction-major A (K x M) and B (K x N): B_eff[k] = B[k - shift] when 0 <= k - shift < K, else 0 --
 // the recurrent weight gradient dW_hh = da^T h_prev with h_prev = y delayed (forward direction) or advanced (reverse) by one
 // timestep.  On the bf16x3 plane path the shift is applied while B is split, so that A = da^T keeps the SAME K window as in
 // dW_ih = da^T x and its planes can be reused (GemmPlanes::same_a); elsewhere the window is narrowed instead.
-int ctcn_gemm_on_xcds(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C,
-                      int ldc, float beta, int precision, void *ws, size_t ws_bytes, void *stream, unsigned xcd_allow, GemmPlanes *planes) {
-  return gemm_core(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, beta, precision, ws, ws_bytes, stream, xcd_allow, planes, 0);
-}
-
 int ctcn_gemm_shift_b(int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc, float beta, int precision,
                       void *ws, size_t ws_bytes, void *stream, unsigned xcd_allow, int shift, GemmPlanes *planes) {
   const int as = shift < 0 ? -shift : shift;
   CTCN_REQUIRE(as < K, "ctcn_gemm_shift_b: |shift| %d >= K %d", as, K);
-  const int Kp = ceil_div(K, PBK) * PBK;
-  const size_t plane_bytes = align_up(2 * ((size_t)M * Kp + (size_t)N * Kp) * sizeof(unsigned short), 256);
-  const bool plane = precision == 1 && K >= 64 && ws && ws_bytes >= plane_bytes + 1024 &&
-                     !tn_eligible(1, 0, M, N, K - as, A, lda, B, ldb, precision, ws, ws_bytes);   // (the TN tile narrows the window: no planes to share)
+  // the plane path with the whole window, unless the narrowed window would go to the TN tile, which has no planes to share (both answers
+  // are the same on any device: the XCD count only sizes things inside a path)
+  const GemmEnv e = {(int)((uintptr_t)A & 15), (int)((uintptr_t)B & 15), ws != nullptr, ws_bytes, xcd_allow, false, false, ctcn_device_cus(), 0, gemm_options()};
+  const bool plane = uses_planes(plan_gemm({1, 0, M, N, K, lda, ldb, ldc, precision, shift}, e).path) &&
+                     plan_gemm({1, 0, M, N, K - as, lda, ldb, ldc, precision, 0}, e).path != GP_TN;
   if (!plane) {
     if (planes) planes->same_a = false;
     const float *A2 = shift > 0 ? A + (size_t)as * lda : A, *B2 = shift < 0 ? B + (size_t)as * ldb : B;

@@ -470,11 +470,12 @@ def bctf_to_tbcf(x):
 # --------------------------------------------------------------------------------------------------
 # linear (GEMM)
 # --------------------------------------------------------------------------------------------------
-def gemm(transA, transB, M, N, K, A, lda, Bm, ldb, C, ldc, beta=0.0):
+def gemm(transA, transB, M, N, K, A, lda, Bm, ldb, C, ldc, beta=0.0, xcd_allow=0):
+    """xcd_allow != 0: the side-stream form, workgroups confined to those XCDs (ctcn_diag_gemm_on_xcds; tests)."""
     _need_gpu(A, Bm, C)
     w, wp, wn = _ws(C)
-    _lib.check(_lib.lib().ctcn_gemm(int(transA), int(transB), M, N, K, _ptr(A), lda, _ptr(Bm), ldb, _ptr(C), ldc, float(beta),
-                                    get_precision(), wp, wn, _lib.stream_ptr()), "gemm")
+    args = (int(transA), int(transB), M, N, K, _ptr(A), lda, _ptr(Bm), ldb, _ptr(C), ldc, float(beta), get_precision(), wp, wn, _lib.stream_ptr())
+    _lib.check(_lib.lib().ctcn_diag_gemm_on_xcds(*args, int(xcd_allow)) if xcd_allow else _lib.lib().ctcn_gemm(*args), "gemm")
     return C
 
 

@@ -66,9 +66,6 @@ int ctcn_device_xcds(void);
  * it (no separate plane pass over A; same planes, same results); 0: A is pre-split like B.
  * "conv_mfma" = 1 (default): ctcn_conv2d_fwd / _bwd run as implicit GEMMs on v_mfma_f32_16x16x4_f32 (im2col tile of 64 positions and
  * the filter matrix staged in LDS; exact float32 in both matmul precisions); 0: the direct (lane-per-position) kernels.
- * "gemm_pingpong" = 1 (default): the 256-row bf16x3 plane tiles run the ping-pong schedule (the two waves of a SIMD half a
- * 16-k step apart: one multiplies while the other reads its fragments; DMA pieces issued between MFMAs); 0: all waves in phase.
- * Bit-identical results either way.
  * "gemm_tn" = 1 (default): bf16x3 products C = A^T B with BOTH operands contraction-major (transA = 1, transB = 0: the weight
  * gradients dW = da^T x; M >= 128, N >= 32, K >= 1024, 16-B aligned rows) run on the TN tile -- float32 rows split into hi / lo while
  * they are staged, ds_read_b64_tr_b16 fragments, split-K queue -- instead of a transposing plane pass + the NT plane tiles; the same
@@ -584,6 +581,20 @@ int ctcn_diag_squat(int wgs_per_xcd, int threads, int lds_bytes, unsigned usec, 
  * of `xcds` XCDs and `cus` CUs with the idle XCDs `xcd_allow`: the number of time chunks (even, 8..24) it would be pipelined with, 0 = not
  * pipelined (the one-round / 72-steps / throughput / free-CU rules of rnn.hip), -1 = bad arguments.  Pure arithmetic, no device needed. */
 int ctcn_diag_pipeline_chunks(int cell, int T, int B, int I, int H, int dirs, int xcds, int cus, unsigned xcd_allow);
+/* ctcn_diag_gemm_plan: what ctcn_gemm (and the internal side-stream / shifted forms: xcd_allow, b_shift, same_a / same_b = the operand's bf16
+ * planes of the previous call are still in the workspace) would do with a product on a device of `xcds` XCDs and `cus` CUs, given A and B
+ * modulo 16 bytes and the workspace's size -- the plan of gemm.hip's plan_gemm under the current options.  out[CTCN_GEMM_PLAN_INTS] =
+ * path (0 f32, 1 f32 queued, 2 bf16x3 direct, 3 planes 128-row tile, 4 the same queued, 5 planes 256-row tile, 6 256-row tile with float32 A,
+ * 7 256-row tile queued, 8 TN tile), workgroup tile rows / 64, columns / 64, wnt, split-K count, k-chunk, split pass of A, of B (0 none,
+ * 1 rows, 2 transposing, 3 transposing queued), grid x, grid y, 16-B loads of A, of B (direct kernels).  CTCN_EINVAL on the arguments
+ * ctcn_gemm refuses.  Pure arithmetic, no device needed.
+ * ctcn_diag_gemm_on_xcds: ctcn_gemm with its workgroups confined to the XCDs of `xcd_allow` (0: ctcn_gemm itself) -- the side-stream forms
+ * the recurrent layer uses, for tests. */
+#define CTCN_GEMM_PLAN_INTS 12
+int ctcn_diag_gemm_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, int ldc, int precision, int b_shift, int a_mod16,
+                        int b_mod16, int has_ws, size_t ws_bytes, unsigned xcd_allow, int same_a, int same_b, int cus, int xcds, int *out);
+int ctcn_diag_gemm_on_xcds(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc,
+                           float beta, int precision, void *ws, size_t ws_bytes, void *stream, unsigned xcd_allow);
 const char *ctcn_rnn_last_kernel(int which);
 
 /* ---- host end of the decoders (hostjoin.hip; no kernel, no HIP call: works without a GPU) -------------------------------------------------

@@ -242,6 +242,59 @@ def test_gemm_bf16_single_is_the_product_of_the_rounded_operands(dev, ta, tb, M,
     assert float((outs[1][rows, :N].double() - exact).abs().max()) > 1e-3 * scale          # bf16 operands: the third digit moves
 
 
+def test_gemm_side_stream_forms_equal_the_whole_device_forms(dev):
+    """ops.gemm(..., xcd_allow=mask) = ctcn_diag_gemm_on_xcds: the queued forms a side stream next to a persistent recurrence runs (workgroups
+    off the XCDs of `mask` exit, the others pull tiles from an atomic queue) -- gemm_f32_queue_kernel, gemm_planes_nt_queue_kernel (+
+    split_transpose_queue_kernel for a contraction-major operand), gemm_planes_nt256pp_queue_kernel and the TN tile with an XCD mask --
+    against mask 0, bit for bit (the same tile code; the plane tiles are bit-identical across tile sizes by design, and the TN partials are
+    summed in split order: tn_splits_force = 2 gives every mask the same two k windows), with beta = 0 and 1 and columns beyond N that must
+    stay untouched.  The plan of every call is asserted first, so that a rule that moved cannot turn the test into mask 0 against mask 0."""
+    from ctc_pytorch_amd import ops, _lib
+    from test_host_logic import _gemm_plan
+    L = _lib.lib()
+    cus, xcds = L.ctcn_device_cus(), L.ctcn_device_xcds()
+    if xcds < 8:
+        pytest.skip("needs a device of 8 XCDs (masks 0x01 and 0xF0)")
+    cases = [   # prec, ta, tb, M, N, K, options, {mask: path}
+        (0, 0, 0, 200, 62, 40, {}, {0: "f32", 0x01: "f32_queue", 0xF0: "f32_queue"}),
+        (1, 0, 0, 300, 257, 130, {}, {0: "planes128", 0x01: "planes128_queue", 0xF0: "planes128_queue"}),
+        (1, 0, 1, 300, 257, 130, {}, {0: "planes128", 0x01: "planes128_queue", 0xF0: "planes128_queue"}),
+        (1, 1, 1, 300, 257, 130, {}, {0: "planes128", 0x01: "planes128_queue", 0xF0: "planes128_queue"}),
+        (1, 0, 1, 6144, 128, 64, {}, {0: "planes128", 0x01: "planes256_queue", 0xF0: "planes128_queue"}),
+        (1, 1, 0, 388, 132, 1100, {"tn_splits_force": 2}, {0: "tn", 0x01: "tn", 0xF0: "tn"}),
+        (1, 1, 0, 128, 64, 1024, {"tn_splits_force": 2}, {0: "tn", 0x01: "tn", 0xF0: "tn"}),
+    ]
+    try:
+        for prec, ta, tb, M, N, K, opts, paths in cases:
+            ops.set_precision(prec)
+            for n, v in opts.items():
+                ops.set_option(n, v)
+            rs = np.random.RandomState(M + 3 * N + K + ta * 2 + tb)
+            A = gpu(rs.standard_normal((K, M) if ta else (M, K)).astype(np.float32), dev)
+            Bm = gpu(rs.standard_normal((N, K) if tb else (K, N)).astype(np.float32), dev)
+            C0 = gpu(rs.standard_normal((M, N + 3)).astype(np.float32), dev)
+            ref = (A.t() if ta else A).double() @ (Bm.t() if tb else Bm).double()
+            for mask, path in paths.items():
+                got = _gemm_plan(ta, tb, M, N, K, prec=prec, amod=A.data_ptr() % 16, bmod=Bm.data_ptr() % 16, xcd=mask, cus=cus, xcds=xcds)
+                assert got["path"] == path and (path != "tn" or got["splits"] == 2), (M, N, K, mask, got)
+            for beta in (0.0, 1.0):
+                outs = {}
+                for mask in paths:
+                    C = C0.clone()
+                    ops.gemm(ta, tb, M, N, K, A, A.shape[1], Bm, Bm.shape[1], C, N + 3, beta=beta, xcd_allow=mask)
+                    outs[mask] = C
+                tol = (2e-6 if prec == 0 else 4e-5) * 4 * float(A.abs().max() * Bm.abs().max()) * K ** 0.5 + 1e-6
+                assert float((outs[0][:, :N].double() - (ref + beta * C0[:, :N].double())).abs().max()) < tol
+                for mask in (0x01, 0xF0):
+                    assert torch.equal(outs[mask], outs[0]), (prec, ta, tb, M, N, K, beta, mask)
+                    assert torch.equal(outs[mask][:, N:], C0[:, N:]), "wrote outside the ldc window"
+            for n in opts:
+                ops.set_option(n, 0)
+    finally:
+        ops.set_option("tn_splits_force", 0)
+        ops.set_precision(0)
+
+
 @pytest.mark.parametrize("kind", ["lstm", "gru", "rnn"])
 def test_rnn_layer_golden(dev, kind):
     from ctc_pytorch_amd import ops

@@ -870,6 +870,178 @@ def test_weight_gradient_plan_table():
     assert fwd(60, 8, 128, 2, off) == 0 and fwd(800, 32, 320, 2, dict(base, fwd_overlap=False)) == 0 and fwd(800, 32, 320, 2, nx=1) == 0   # (last two: r)
 
 
+_GEMM_PATHS = ("f32", "f32_queue", "bf16x3", "planes128", "planes128_queue", "planes256", "planes256_af32", "planes256_queue", "tn")
+
+
+def _gemm_plan(ta, tb, M, N, K, prec=1, lda=None, ldb=None, amod=0, bmod=0, ws=1 << 30, xcd=0, same_a=0, same_b=0, shift=0, cus=256, xcds=8):
+    """ctcn_diag_gemm_plan for contiguous operands unless lda / ldb say otherwise; ws = workspace bytes (None: no workspace)."""
+    import ctypes
+    from ctc_pytorch_amd import _lib
+    out = (ctypes.c_int * 12)()
+    lda = (M if ta else K) if lda is None else lda
+    ldb = (K if tb else N) if ldb is None else ldb
+    rc = _lib.lib().ctcn_diag_gemm_plan(ta, tb, M, N, K, lda, ldb, N, prec, shift, amod, bmod, 0 if ws is None else 1, ws or 0, xcd, same_a, same_b,
+                                        cus, xcds, ctypes.cast(out, ctypes.c_void_p))
+    assert rc == 0, (rc, _lib.lib().ctcn_last_error())
+    keys = ("path", "ti", "tj", "wnt", "splits", "kchunk", "split_a", "split_b", "grid_x", "grid_y", "vec_a", "vec_b")
+    d = dict(zip(keys, out))
+    d["path"] = _GEMM_PATHS[d["path"]]
+    return d
+
+
+def test_gemm_plan_table():
+    """ctcn_diag_gemm_plan = gemm.hip's plan_gemm, the pure decision behind ctcn_gemm and its internal side-stream / shifted forms: WHICH of the
+    nine kernel families a product takes (with its tile, wnt, split-K count and operand split passes) on a device of 8 XCDs x 32 CUs.  The
+    GPU tests pass just as well when a shape silently falls from the 256-row tile to the 128-row one (the tiles are bit-identical by design);
+    this one does not.
+
+    Where the expected values come from: NOT from the function under test.  Rows marked `t`, and every line of
+    profiles/gemm_plan_trace_parent.txt (replayed first), are a trace of the commit BEFORE the decision was separated from the launches (its
+    gemm_core, 200 lines with the rules braided in), recorded on an MI355X with one fprintf per call: the five GEMM tests of
+    tests/test_gpu_kernels.py and two training steps of cfg1-cfg4 and the shipped YAML shape as bench.py runs them.  Rows marked `r` (the two
+    sides of each rule's edge, misaligned operands, workspaces that are missing or too small, the side-stream masks, the option switches)
+    were not in that run and are derived by reading the same commit's gemm_core."""
+    from ctc_pytorch_amd import ops
+    names = ("gemm_tile256", "gemm_a_inline", "gemm_tn", "gemm_big_tiles", "tn_splits_xcd", "tn_splits_force")
+    defaults = {n: ops.get_option(n) for n in names}
+    assert defaults == dict(gemm_tile256=1, gemm_a_inline=1, gemm_tn=1, gemm_big_tiles=0, tn_splits_xcd=1, tn_splits_force=0)
+
+    def plan_with(opts, *a, **k):
+        try:
+            for n, v in opts.items():
+                ops.set_option(n, v)
+            return _gemm_plan(*a, **k)
+        finally:
+            for n, v in defaults.items():
+                ops.set_option(n, v)
+
+    # ---- the recorded trace, every line
+    shapes = {0: (2, 2), 1: (4, 2), 2: (2, 4)}
+    lines = [l for l in open(os.path.join(ROOT, "profiles", "gemm_plan_trace_parent.txt")) if not l.startswith("#")]
+    assert len(lines) >= 150
+    for l in lines:
+        head, want = l.split(" -> ")
+        f = {k: int(v, 0) for k, v in re.findall(r"(\w+)=(-?\w+)", head.split(" ", 2)[2])}
+        w = dict(re.findall(r"(\w+)=(\w+)", want))
+        o = re.search(r"opts=(\S+)", head).group(1)
+        opts = {} if o == "-" else {k: int(v) for k, v in (kv.split("=") for kv in o.split(","))}
+        got = plan_with(opts, f["ta"], f["tb"], f["M"], f["N"], f["K"], prec=f["prec"], lda=f["lda"], ldb=f["ldb"], amod=f["amod"], bmod=f["bmod"],
+                        ws=f["ws_bytes"] if f["ws"] else None, xcd=f["xcd"], same_a=f["same_a"], same_b=f["same_b"], shift=f["shift"])
+        tile = (4, 2 * int(w["wnt"])) if w["path"].startswith("planes256") or w["path"] == "tn" else shapes[int(w["shape"])]
+        assert (got["path"], (got["ti"], got["tj"]), got["wnt"], got["splits"], got["kchunk"], got["split_a"], got["split_b"]) == \
+               (w["path"], tile, int(w["wnt"]), int(w["splits"]), int(w["kchunk"]), int(w["split_a"]), int(w["split_b"])), l
+
+    # ---- the table: (ta, tb, M, N, K), keywords of _gemm_plan, options moved -> path, tile / 64, wnt, splits, split pass of A, of B
+    NONE, ROWS, TR, TRQ = 0, 1, 2, 3
+    D = {}
+    AF32_BYTES = 2 * (1280 + 640) * 25600 * 2          # the planes of 1 280 x 640 x 25 600
+    rows = [
+        # the products of cfg1-cfg4 and the shipped YAML shape
+        ((0, 1, 25600, 1280, 640), {}, D, "planes256_af32", (4, 4), 2, 1, NONE, ROWS),              # t input projection
+        ((0, 0, 25600, 640, 2560), {}, D, "planes256_af32", (4, 2), 1, 1, NONE, TR),                # t dx
+        ((0, 1, 25600, 2560, 640), {}, D, "planes256", (4, 4), 2, 1, ROWS, ROWS),                   # t 10 N-tiles: A pre-split
+        ((0, 1, 76800, 3072, 1024), {}, D, "planes256", (4, 4), 2, 1, ROWS, ROWS),                  # t cfg4
+        ((0, 1, 2560, 2560, 640), dict(xcd=0xAA), D, "planes256_queue", (4, 4), 2, 1, ROWS, ROWS),  # t a chunk of cfg2's pipelined projection
+        ((0, 1, 2560, 2560, 640), dict(xcd=0xAA, same_b=1), D, "planes256_queue", (4, 4), 2, 1, ROWS, NONE),   # t ... W_ih's planes reused
+        ((0, 1, 1600, 3072, 768), {}, D, "planes128", (2, 2), 0, 1, ROWS, ROWS),                    # t shipped YAML shape
+        ((1, 0, 1280, 640, 25600), {}, D, "tn", (4, 2), 1, 10, NONE, NONE),                         # t dW_ih
+        ((1, 0, 1280, 640, 25600), dict(lda=2560, xcd=0xAA), D, "tn", (4, 2), 1, 5, NONE, NONE),    # t ... on the side stream: one round on four XCDs
+        ((1, 0, 1280, 320, 25568), dict(lda=2560, ldb=640), D, "tn", (4, 2), 1, 17, NONE, NONE),    # t dW_hh, window narrowed by the shift
+        ((1, 0, 1280, 320, 25568), dict(lda=2560, ldb=640, xcd=0xAA), D, "tn", (4, 2), 1, 8, NONE, NONE),   # t
+        ((1, 0, 1536, 768, 1600), dict(lda=3072, xcd=0xFA), D, "tn", (4, 4), 2, 3, NONE, NONE),     # t TN wnt: N = 768 as 3 x 256
+        ((1, 0, 62, 640, 25600), {}, D, "planes128", (2, 2), 0, 50, TR, TR),                        # t the head's weight gradient (M < 128)
+        # the shifted dW_hh product on the plane path (gemm_tn off, or b_shift given): B shifted while it is split, A's planes shared
+        ((1, 0, 1280, 320, 25600), dict(shift=1), dict(gemm_tn=0), "planes128", (2, 2), 0, 18, TR, TR),             # r
+        ((1, 0, 1280, 320, 25600), dict(shift=1, same_a=1), dict(gemm_tn=0), "planes128", (2, 2), 0, 18, NONE, TR), # r
+        ((1, 0, 1280, 320, 25600), dict(shift=-1, same_a=1), D, "planes128", (2, 2), 0, 18, NONE, TR),              # r a shift keeps the call off the TN tile
+        ((1, 0, 1280, 320, 25600), dict(shift=1, xcd=0xAA), dict(gemm_tn=0), "planes128_queue", (2, 2), 0, 18, TRQ, TRQ),   # r
+        # plane path: M 1 023 / 1 024, N 95 / 96, K 63 / 64
+        ((0, 1, 1024, 16384, 128), {}, D, "planes256", (4, 4), 2, 1, ROWS, ROWS),                   # r
+        ((0, 1, 1023, 16384, 128), {}, D, "planes128", (2, 2), 0, 1, ROWS, ROWS),                   # r
+        ((0, 0, 49152, 96, 128), {}, D, "planes256_af32", (4, 2), 1, 1, NONE, TR),                  # r
+        ((0, 0, 49152, 95, 128), {}, D, "planes128", (2, 2), 0, 1, ROWS, TR),                       # r
+        ((0, 1, 2048, 256, 64), {}, D, "planes128", (2, 2), 0, 1, ROWS, ROWS),                      # r
+        ((0, 1, 2048, 256, 63), {}, D, "bf16x3", (2, 2), 0, 1, NONE, NONE),                         # r
+        # TN: K 1 023 / 1 024, M 124 / 127 / 128, N 28 / 31 / 32
+        ((1, 0, 128, 64, 1024), {}, D, "tn", (4, 2), 1, 2, NONE, NONE),                             # t
+        ((1, 0, 128, 64, 1023), {}, D, "planes128", (2, 2), 0, 2, TR, TR),                          # r
+        ((1, 0, 124, 64, 1024), {}, D, "planes128", (2, 2), 0, 2, TR, TR),                          # r
+        ((1, 0, 127, 64, 1024), dict(lda=128), D, "planes128", (2, 2), 0, 2, TR, TR),               # r
+        ((1, 0, 128, 32, 1024), {}, D, "tn", (4, 2), 1, 2, NONE, NONE),                             # r
+        ((1, 0, 128, 28, 1024), {}, D, "planes128", (2, 2), 0, 2, TR, TR),                          # r
+        ((1, 0, 128, 31, 1024), dict(ldb=32), D, "planes128", (2, 2), 0, 2, TR, TR),                # r
+        # use256: at least 3/4 of a workgroup per CU (192 tiles of 256 CUs)
+        ((0, 1, 49152, 256, 128), {}, D, "planes256_af32", (4, 4), 2, 1, NONE, ROWS),               # r 192 tiles
+        ((0, 1, 48896, 256, 128), {}, D, "planes128", (2, 2), 0, 1, ROWS, ROWS),                    # r 191 tiles
+        # the float32-A tile up to 5 N-tiles
+        ((0, 0, 25600, 650, 2560), {}, D, "planes256", (4, 2), 1, 1, ROWS, TR),                     # r 6 N-tiles of 128
+        ((0, 1, 76800, 1536, 1024), {}, D, "planes256", (4, 4), 2, 1, ROWS, ROWS),                  # t 6 N-tiles of 256
+        # wnt of the 256-row plane tiles at N = 512, 640 (above), 1 030, 2 560 (above)
+        ((0, 0, 25001, 512, 204), {}, D, "planes256_af32", (4, 4), 2, 1, NONE, TR),                 # t
+        ((0, 1, 16390, 1030, 200), {}, D, "planes256", (4, 2), 1, 1, ROWS, ROWS),                   # t
+        # A or B at 4 (mod 16) bytes, lda or ldb no multiple of 4: no float32-A tile, no TN tile
+        ((0, 0, 25600, 640, 2560), dict(amod=4), D, "planes256", (4, 2), 1, 1, ROWS, TR),           # r
+        ((0, 0, 25600, 640, 2560), dict(lda=2561), D, "planes256", (4, 2), 1, 1, ROWS, TR),         # r
+        ((0, 0, 25600, 640, 2560), dict(bmod=4, ldb=641), D, "planes256_af32", (4, 2), 1, 1, NONE, TR),   # r (B goes through its split pass either way)
+        ((1, 0, 1280, 640, 25600), dict(amod=4), D, "planes128", (2, 2), 0, 11, TR, TR),            # r
+        ((1, 0, 1280, 640, 25600), dict(bmod=4), D, "planes128", (2, 2), 0, 11, TR, TR),            # r
+        ((1, 0, 1280, 640, 25600), dict(lda=1281), D, "planes128", (2, 2), 0, 11, TR, TR),          # r
+        ((1, 0, 1280, 640, 25600), dict(ldb=642), D, "planes128", (2, 2), 0, 11, TR, TR),           # r
+        # no workspace; one too small for the planes; one too small for the partials
+        ((0, 1, 25600, 1280, 640), dict(ws=None), D, "bf16x3", (2, 2), 0, 1, NONE, NONE),           # r
+        ((1, 0, 1280, 640, 25600), dict(ws=None), D, "bf16x3", (2, 2), 0, 1, NONE, NONE),           # r
+        ((1, 0, 1280, 640, 25600), dict(ws=AF32_BYTES + 1023), dict(gemm_tn=0), "bf16x3", (2, 2), 0, 11, NONE, NONE),   # r
+        ((1, 0, 1280, 640, 25600), dict(ws=AF32_BYTES + 1024), dict(gemm_tn=0), "planes128", (2, 2), 0, 1, TR, TR),     # r
+        ((1, 0, 1280, 640, 25600), dict(ws=1024), D, "tn", (4, 2), 1, 1, NONE, NONE),               # r
+        ((1, 0, 1280, 640, 25600), dict(ws=1023), D, "bf16x3", (2, 2), 0, 1, NONE, NONE),           # r
+        ((1, 0, 62, 640, 6400), dict(prec=0), D, "f32", (2, 2), 0, 25, NONE, NONE),                 # t
+        ((1, 0, 62, 640, 6400), dict(prec=0, ws=2 * 62 * 640 * 4 - 1), D, "f32", (2, 2), 0, 1, NONE, NONE),   # r
+        # the side stream: 256-row tiles from the queue only in whole rounds that fill 3/4 of the allowed XCDs' CUs
+        ((0, 1, 6144, 128, 64), dict(xcd=0x01), D, "planes256_queue", (4, 2), 1, 1, ROWS, ROWS),    # r 24 tiles on 32 CUs
+        ((0, 1, 5888, 128, 64), dict(xcd=0x01), D, "planes128_queue", (2, 2), 0, 1, ROWS, ROWS),    # r 23 tiles
+        ((0, 1, 6144, 128, 64), dict(xcd=0x03), D, "planes128_queue", (2, 2), 0, 1, ROWS, ROWS),    # r 24 tiles on 64 CUs
+        ((0, 1, 6144, 128, 64), {}, D, "planes128", (2, 2), 0, 1, ROWS, ROWS),                      # r the whole device: too few tiles
+        ((1, 1, 300, 257, 130), dict(xcd=0xF0), D, "planes128_queue", (2, 2), 0, 1, TRQ, ROWS),     # r
+        ((0, 0, 300, 257, 130), dict(xcd=0xF0), D, "planes128_queue", (2, 2), 0, 1, ROWS, TRQ),     # r
+        ((0, 0, 200, 62, 40), dict(prec=0, xcd=0x01), D, "f32_queue", (2, 2), 0, 1, NONE, NONE),    # r
+        ((0, 0, 200, 62, 40), dict(prec=0, xcd=0x01, ws=None), D, "f32", (2, 2), 0, 1, NONE, NONE), # r
+        ((0, 0, 200, 62, 40), dict(prec=1, xcd=0x01), D, "bf16x3", (2, 2), 0, 1, NONE, NONE),       # r K < 64: the direct kernel, on every XCD
+        ((1, 0, 388, 132, 1100), dict(lda=396, ldb=140, xcd=0x01), D, "tn", (4, 4), 2, 2, NONE, NONE),   # r
+        # each option moved from its default
+        ((0, 1, 25600, 1280, 640), {}, dict(gemm_tile256=0), "planes128", (2, 2), 0, 1, ROWS, ROWS),        # t
+        ((0, 1, 25600, 1280, 640), {}, dict(gemm_a_inline=0), "planes256", (4, 4), 2, 1, ROWS, ROWS),       # t
+        ((0, 1, 2560, 2560, 640), dict(xcd=0xAA), dict(gemm_tile256=0), "planes128_queue", (2, 2), 0, 1, ROWS, ROWS),   # r
+        ((1, 0, 1280, 640, 25600), {}, dict(gemm_tn=0), "planes128", (2, 2), 0, 11, TR, TR),                # t
+        ((0, 1, 8192, 1024, 200), {}, dict(gemm_big_tiles=1), "planes128", (2, 4), 0, 1, ROWS, ROWS),       # t
+        ((0, 1, 8192, 1024, 200), {}, D, "planes128", (2, 2), 0, 1, ROWS, ROWS),                            # t
+        ((1, 0, 1280, 640, 25600), dict(xcd=0xAA), dict(tn_splits_xcd=0), "tn", (4, 2), 1, 10, NONE, NONE), # r
+        ((1, 0, 1280, 640, 25600), {}, dict(tn_splits_force=2), "tn", (4, 2), 1, 2, NONE, NONE),            # r
+        ((1, 0, 388, 132, 1100), dict(lda=396, ldb=140), dict(tn_splits_force=3), "tn", (4, 4), 2, 3, NONE, NONE),   # r
+    ]
+    for shape, kw, opts, path, tile, wnt, splits, sa, sb in rows:
+        got = plan_with(opts, *shape, **kw)
+        assert (got["path"], (got["ti"], got["tj"]), got["wnt"], got["splits"], got["split_a"], got["split_b"]) == (path, tile, wnt, splits, sa, sb), \
+               (shape, kw, opts, got)
+    # r: the direct kernels load 16 bytes at a time only from 16-byte aligned rows
+    vec = lambda **k: (lambda d: (d["vec_a"], d["vec_b"]))(_gemm_plan(0, 1, 128, 128, 64, prec=0, **k))
+    assert vec() == (1, 1) and vec(amod=4) == (0, 1) and vec(bmod=4) == (1, 0) and vec(lda=65) == (0, 1) and vec(ldb=66) == (1, 0)
+    # r: grids -- one workgroup per tile (and split), or a queue's worth of workgroups per CU
+    g = lambda d: (d["grid_x"], d["grid_y"])
+    assert g(_gemm_plan(0, 1, 25600, 1280, 640)) == (500, 1) and g(_gemm_plan(0, 1, 2560, 2560, 640, xcd=0xAA)) == (256, 1)
+    assert g(_gemm_plan(1, 0, 62, 640, 25600)) == (5, 50) and g(_gemm_plan(1, 1, 300, 257, 130, xcd=0xF0)) == (512, 1)
+    assert g(_gemm_plan(1, 0, 1280, 640, 25600)) == (256, 1) and g(_gemm_plan(1, 0, 62, 640, 6400, prec=0)) == (5, 25)
+    # the arguments ctcn_gemm refuses
+    import ctypes
+    from ctc_pytorch_amd import _lib
+    out = (ctypes.c_int * 12)()
+    bad = lambda *a: _lib.lib().ctcn_diag_gemm_plan(*a, 0, 0, 0, 1, 1 << 30, 0, 0, 0, 256, 8, ctypes.cast(out, ctypes.c_void_p))
+    assert bad(0, 1, 128, 128, 64, 64, 64, 128, 1) == 0
+    assert bad(0, 1, 128, 128, 64, 64, 64, 128, 2) == -1 and bad(0, 1, 0, 128, 64, 64, 64, 128, 1) == -1 and bad(0, 1, 128, 128, -1, 64, 64, 128, 1) == -1
+    assert bad(0, 1, 128, 128, 64, 63, 64, 128, 1) == -1 and bad(0, 1, 128, 128, 64, 64, 63, 128, 1) == -1 and bad(0, 1, 128, 128, 64, 64, 64, 127, 1) == -1
+    assert bad(1, 0, 128, 128, 64, 127, 128, 128, 1) == -1
+    assert _lib.lib().ctcn_diag_gemm_plan(0, 1, 128, 128, 64, 64, 64, 128, 1, 0, 0, 0, 1, 1 << 30, 0, 0, 0, 256, 8, None) == -1
+
+
 def test_projection_pipeline_plan_on_the_measured_shapes():
     """ctcn_diag_pipeline_chunks = the pure plan behind ctcn_rnn_fwd_ex's projection pipeline (rnn.hip, round 4): chunk counts at the shapes
     whose A/B runs set its rules (8 XCDs x 32 CUs; `allow` = the XCDs a bidirectional recurrence of B rows leaves idle)."""

@@ -1,4 +1,4 @@
-"""Time the bf16x3 plane GEMM on the shapes of a cfg2 step with both workgroup tilings (development aid)."""
+"""Time the 256-row bf16x3 plane GEMM on the shapes of a cfg2 step, with A pre-split and split while it is staged (development aid)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -10,10 +10,8 @@ for M, N, K, ta, tb in shapes:
     A = torch.randn((K, M) if ta else (M, K), device=dev)
     B = torch.randn((N, K) if tb else (K, N), device=dev)
     C = torch.empty(M, N, device=dev)
-    for t256, dbg in ((1, 1), (1, 4), (1, 5)):
-        ops.set_option("gemm_tile256", t256)
-        ops.set_option("gemm_pingpong", 1 if dbg in (1, 5) else 0)
-        ops.set_option("gemm_a_inline", 1 if dbg in (4, 5) else 0)
+    for inline in (0, 1):
+        ops.set_option("gemm_a_inline", inline)
         for _ in range(3):
             ops.gemm(ta, tb, M, N, K, A, A.shape[1], B, B.shape[1], C, N)
         torch.cuda.synchronize()
@@ -24,7 +22,5 @@ for M, N, K, ta, tb in shapes:
         e1.record()
         torch.cuda.synchronize()
         us = e0.elapsed_time(e1) / 20 * 1e3
-        print("%6d x %5d x %5d  tile256=%d variant=%d (1: ping-pong planes, 4: inline-A, 5: inline-A ping-pong)  %8.1f us  %7.1f TFLOP/s (incl. split passes)" % (M, N, K, t256, dbg, us, 2.0 * M * N * K / us / 1e6))
-ops.set_option("gemm_tile256", 1)
-ops.set_option("gemm_pingpong", 1)
+        print("%6d x %5d x %5d  gemm_a_inline=%d  %8.1f us  %7.1f TFLOP/s (incl. split passes)" % (M, N, K, inline, us, 2.0 * M * N * K / us / 1e6))
 ops.set_option("gemm_a_inline", 1)

@@ -1,5 +1,5 @@
 """The TN weight-gradient tile on cfg4's / cfg2's products with the split-K count forced (development option "tn_splits_force"): is the
-rule of gemm.hip:tn_splits (one round of items on the device) where the time is shortest?  (development aid; run on the GPU box)"""
+rule of gemm.hip:plan_gemm (one round of items on the device) where the time is shortest?  (development aid; run on the GPU box)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
