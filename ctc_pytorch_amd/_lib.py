@@ -92,6 +92,7 @@ _SIGS = {
     "ctcn_adam_step_ex": (I, [P, P, P, P, Z, F, F, F, F, P, P]),
     "ctcn_scale_by_device_scalar": (I, [P, Z, P, P]),
     "ctcn_greedy_collapse": (I, [P, Z, Z, P, P, P, I, I, I, P]),
+    "ctcn_path_tokens": (I, [P, Z, Z, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "ctcn_edit_distance": (I, [P, P, P, P, P, I, I, I, I, P]),
     "ctcn_edit_ops_ws_bytes": (Z, [I, I, I]),
     "ctcn_edit_ops": (I, [P, P, P, P, P, I, P, P, P, P, I, I, I, I, P, Z, P]),

@@ -1437,6 +1437,48 @@ def greedy_collapse(idx, lens, blank=0, batch_major=False):
     return ids, out_len
 
 
+PathTokens = collections.namedtuple("PathTokens", "ids lengths starts ends mean_lp min_lp mean_margin path_score")
+
+
+def path_tokens(path, lens, log_probs, blank=0, batch_major=False):
+    """The tokens of a per-frame class path with their frames and scores (ctcn_path_tokens; definition in include/ctcn.h): path int32,
+    (T,B) time-major or (B,T) if batch_major (any strides) -- the arg-max path of argmax_last or the `paths` of ctc_forced_align; lens (B);
+    log_probs (T,B,V) float32.  Returns PathTokens of device tensors: ids, starts, ends (B,T) int32 (-1 past lengths[b]), lengths (B) int32,
+    mean_lp, min_lp, mean_margin (B,T) float32 (0 past lengths[b]): per token the mean and the minimum of its class's log-prob over its
+    frames [start, end) and the mean lead over the best other class; path_score (B) float32: the log-probability of the whole path.  ids
+    and lengths are greedy_collapse's.  A class id outside [0, V) counts as blank.  Raises ValueError, before it looks at the device, for
+    a blank outside [0, V), empty tensors, shapes that do not match and lens of the wrong length.  No autograd; float32 on the device
+    only (no CPU fallback)."""
+    if log_probs.dim() != 3 or path.dim() != 2:
+        raise ValueError("ctc_pytorch_amd.path_tokens: expected log_probs (T, B, V) and a 2-D path, got %s and %s" % (tuple(log_probs.shape), tuple(path.shape)))
+    T, B, V = log_probs.shape
+    if T == 0 or B == 0 or V == 0:
+        raise ValueError("ctc_pytorch_amd.path_tokens: empty log_probs %s" % (tuple(log_probs.shape),))
+    if tuple(path.shape) != ((B, T) if batch_major else (T, B)):
+        raise ValueError("ctc_pytorch_amd.path_tokens: path %s does not match log_probs %s (batch_major=%s)"
+                         % (tuple(path.shape), tuple(log_probs.shape), bool(batch_major)))
+    if not 0 <= int(blank) < V:
+        raise ValueError("ctc_pytorch_amd.path_tokens: blank must lie in [0, %d), got %d" % (V, int(blank)))
+    lens = lens if torch.is_tensor(lens) else torch.as_tensor(lens)
+    if lens.numel() != B:
+        raise ValueError("ctc_pytorch_amd.path_tokens: %d lengths for a batch of %d" % (lens.numel(), B))
+    _need_gpu(path, log_probs)
+    lp = _f32c(log_probs.detach())
+    dev = lp.device
+    if path.dtype != torch.int32:
+        path = path.to(torch.int32)
+    st_b, st_t = path.stride() if batch_major else path.stride()[::-1]
+    lens = lens.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    ints = torch.empty((3, B, T), dtype=torch.int32, device=dev)
+    vals = torch.empty((3, B, T), dtype=torch.float32, device=dev)
+    out_len = torch.empty(B, dtype=torch.int32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().ctcn_path_tokens(_ptr(path), st_t, st_b, _ptr(lp), _ptr(lens), _ptr(ints[0]), _ptr(out_len), _ptr(ints[1]),
+                                           _ptr(ints[2]), _ptr(vals[0]), _ptr(vals[1]), _ptr(vals[2]), _ptr(score), T, B, V, int(blank),
+                                           _lib.stream_ptr()), "path_tokens")
+    return PathTokens(ints[0], out_len, ints[1], ints[2], vals[0], vals[1], vals[2], score)
+
+
 def edit_distance(ids, ids_len, targets, tgt_len):
     """per-utterance Levenshtein distance (B,) int32 on device (editdistance.eval, model_ctc.py:200)."""
     _need_gpu(ids)

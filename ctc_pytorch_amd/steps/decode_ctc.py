@@ -17,6 +17,14 @@ Keys `error_report`, `score_map`, `score_map_cols` (--error-report, --score-map,
 word error rate.  The loop is still test_ctc's: it is handed `_ScoringDecoder`, a proxy of the decoder whose `wer` returns what the decoder's
 own returns and, on the side, aligns the two strings' word ids (folded by the score map) in the library's host code and tallies the
 alignment into a utils.scoring.ErrorStats.  The CER / WER lines and the return value do not change; the report is logged after them.
+
+Keys `ctm` (--ctm PATH; default off) and `ctm_frame_shift` (--ctm-frame-shift; seconds per model INPUT frame as the feature extraction made
+them, default 0.01): a NIST CTM file of what was recognised -- per token its start, duration and confidence (Decoder.decode_timed,
+utils/ctm.py).  The loop is still test_ctc's: it is handed `_CtmDecoder`, a proxy that decodes every batch once, through `decode_timed`,
+keeps the entries and hands the loop the strings put together from their tokens (the decoder's own join: the strings `decode` returns);
+`_recorded` notes the loader's utterance ids in loader order, which is decode order.  A token's frames are output frames times `input_frames_per_output_frame(model)` (the front-end geometry
+CTC_Model.output_lengths uses) times the loader's frame skip (`n_skip_frame`).  Under torchrun rank r writes PATH.r (its own minibatches).
+The CER / WER lines and the return value do not change.
 """
 import argparse
 import os
@@ -105,17 +113,93 @@ class _ScoringDecoder(object):
         return self._decoder.wer(s1, s2)
 
 
+def input_frames_per_output_frame(model):
+    """Input frames one output frame of `model` advances by: the product of the time strides and time poolings of its convolutional
+    front-end -- the numbers LayerCNN.out_lengths divides by -- and 1 without one."""
+    stride = 1
+    if getattr(model, "add_cnn", False):
+        for block in model.conv:
+            conv_s = block.conv.stride
+            stride *= int(conv_s[0] if isinstance(conv_s, (tuple, list)) else conv_s)
+            if block.pooling is not None:
+                pool = block.pooling.kernel_size
+                stride *= int(pool[0] if isinstance(pool, (tuple, list)) else pool)
+    return stride
+
+
+def _recorded(loader, seen):
+    """The loader, with the utterance ids of every minibatch appended to `seen` as it goes by."""
+    for batch in loader:
+        seen.append(list(batch[4]))
+        yield batch
+
+
+class _CtmDecoder(object):
+    """The decoder, as test_ctc.decode_and_score sees it, decoding every batch ONCE, through `decode_timed`: the entries go into `timed`
+    (one list per call) and the strings the loop scores are put together from their tokens (Decoder.timed_strings: the decoder's own join),
+    so a beam search does not run twice.  A batch with an utterance that has no entry (a search that ended with a status) is handed to
+    the decoder's own `decode`, which raises what it raises without `ctm`.  `decode_async` is kept for the loop that asks for it; its
+    result is ready when it returns (decode_timed ends with the copy to the host), so the batches are not overlapped while `ctm` is on.
+    Everything else -- cer, wer, the num_word / num_char counters -- is the wrapped decoder's, read and written through."""
+
+    def __init__(self, decoder, timed, frame_stride):
+        object.__setattr__(self, "_decoder", decoder)
+        object.__setattr__(self, "_ctm", (timed, frame_stride))
+
+    def __getattr__(self, name):
+        inner = getattr(self._decoder, name)
+        if name != "decode_async":
+            return inner
+
+        def decode_async(probs, lens):
+            strings = self.decode(probs, lens)
+            return lambda: strings
+        return decode_async
+
+    def __setattr__(self, name, value):
+        setattr(self._decoder, name, value)
+
+    def decode(self, probs, lens):
+        timed, frame_stride = self._ctm
+        entries = self._decoder.decode_timed(probs, lens, frame_stride=frame_stride)
+        timed.append(entries)
+        if any(e is None for e in entries):
+            return self._decoder.decode(probs, lens)
+        return self._decoder.timed_strings(entries)
+
+
+def write_ctm_file(path, seen, timed, frame_shift, rank=0, world=1):
+    """The CTM file of one rank: call k of the decoder was minibatch rank + k * world of the loader (test_ctc.decode_and_score_sharded's
+    deal).  PATH for one process, PATH.<rank> under torchrun.  Returns the file's name."""
+    from ctc_pytorch_amd.utils.ctm import write_ctm
+    name = path if world <= 1 else "%s.%d" % (path, rank)
+    with open(name, "w") as fh:
+        for k, entries in enumerate(timed):
+            write_ctm(fh, seen[rank + k * world if world > 1 else k], entries, frame_shift=frame_shift)
+    return name
+
+
 def decode_and_score(model, loader, decoder, index2word, device, verbose=False, log=print, mask_padding=True, rank=0, world=1,
-                     stats=None, class_map=None):
+                     stats=None, class_map=None, ctm=None, ctm_frame_shift=0.01, n_skip_frame=1):
     """steps/test_ctc.decode_and_score_sharded (one process: decode_and_score) over the length-aware pair; mask_padding=False: over the
     plain one.  stats (a host utils.scoring.ErrorStats): the loop scores through _ScoringDecoder, the stats are summed over the ranks
-    beside the four totals, and rank 0 logs the report after the CER / WER lines."""
+    beside the four totals, and rank 0 logs the report after the CER / WER lines.  ctm (a file name): the timed tokens of every utterance
+    go to that file (module docstring), in seconds of ctm_frame_shift per input frame; n_skip_frame: the loader's frame skip."""
+    seen, timed = [], []
+    if ctm:
+        stride = input_frames_per_output_frame(model) * max(int(n_skip_frame or 1), 1)
+        loader, decoder = _recorded(loader, seen), _CtmDecoder(decoder, timed, stride)
     if mask_padding:
         model, loader = length_aware(model, loader)
     if stats is None:
-        return test_ctc.decode_and_score_sharded(model, loader, decoder, index2word, device, rank, world, verbose=verbose, log=log)
+        out = test_ctc.decode_and_score_sharded(model, loader, decoder, index2word, device, rank, world, verbose=verbose, log=log)
+        if ctm:
+            write_ctm_file(ctm, seen, timed, float(ctm_frame_shift), rank, world)
+        return out
     out = test_ctc.decode_and_score_sharded(model, loader, _ScoringDecoder(decoder, stats, index2word, class_map), index2word, device, rank,
                                             world, verbose=verbose, log=log)
+    if ctm:
+        write_ctm_file(ctm, seen, timed, float(ctm_frame_shift), rank, world)
     if world > 1:
         import torch.distributed as dist
         t = stats.state().to(device if dist.get_backend() == "nccl" else "cpu")
@@ -126,6 +210,43 @@ def decode_and_score(model, loader, decoder, index2word, device, verbose=False, 
     return out
 
 
+def ctm_options(opts):
+    """The keys `ctm` / `ctm_frame_shift` of a Config as decode_and_score's keyword arguments; {} while `ctm` is off (the default)."""
+    path = getattr(opts, "ctm", None)
+    if not path:
+        return {}
+    return {"ctm": str(path), "ctm_frame_shift": float(getattr(opts, "ctm_frame_shift", 0.01))}
+
+
+def apply_argv(conf, a):
+    """The command line's switches laid over the YAML's keys; a switch that was not given leaves its key alone."""
+    if a.error_report:
+        conf["error_report"] = True
+    if a.score_map is not None:
+        conf["score_map"] = a.score_map
+    if a.score_map_cols is not None:
+        conf["score_map_cols"] = a.score_map_cols
+    if a.mask_padding:
+        conf["mask_padding"] = True
+    if a.ctm is not None:
+        conf["ctm"] = a.ctm
+    if a.ctm_frame_shift is not None:
+        conf["ctm_frame_shift"] = a.ctm_frame_shift
+    return conf
+
+
+def arg_parser():
+    ap = argparse.ArgumentParser(description="decode + score a ctc_best_model.pkl on MI355X, optionally with the utterance lengths passed to the model")
+    ap.add_argument("--conf", help="conf file (same keys as timit/conf/ctc_config.yaml, plus mask_padding)")
+    ap.add_argument("--mask-padding", action="store_true", help="tell the model every utterance's real frames (default: the YAML's mask_padding, else off)")
+    ap.add_argument("--error-report", action="store_true", help="log the error breakdown (sub / del / ins, top confusions) after the CER / WER lines (default: the YAML's error_report, else off)")
+    ap.add_argument("--score-map", default=None, help="three-column phone table the breakdown is scored under (default: the YAML's score_map, else none)")
+    ap.add_argument("--score-map-cols", default=None, choices=["60-48", "60-39", "48-39"], help="which fold of the table (default: the YAML's score_map_cols, else 48-39)")
+    ap.add_argument("--ctm", default=None, metavar="PATH", help="write the recognised tokens with start, duration and confidence to this NIST CTM file (default: the YAML's ctm, else off)")
+    ap.add_argument("--ctm-frame-shift", default=None, type=float, help="seconds per model input frame (default: the YAML's ctm_frame_shift, else 0.01)")
+    return ap
+
+
 def main(conf, test_loader=None, index2word=None, log=print):
     """steps/test_ctc.main for the same YAML plus `mask_padding`.  Returns (CER, WER)."""
     from ctc_pytorch_amd import parallel
@@ -134,7 +255,8 @@ def main(conf, test_loader=None, index2word=None, log=print):
     for k, v in conf.items():
         setattr(opts, k, v)
     report = bool(getattr(opts, "error_report", False))
-    if not epoch_options(opts) and not report:
+    ctm = ctm_options(opts)
+    if not epoch_options(opts) and not report and not ctm:
         return test_ctc.main(conf, test_loader=test_loader, index2word=index2word, log=log)
     if not getattr(opts, "use_gpu", True):
         raise RuntimeError("ctc_pytorch_amd: use_gpu must be True -- the HIP path has no CPU fallback")
@@ -155,7 +277,8 @@ def main(conf, test_loader=None, index2word=None, log=print):
         class_map = report_options(opts, index2word).get("score_map")
     start = time.time()
     cer, wer = decode_and_score(model, test_loader, decoder, index2word, device, verbose=bool(getattr(opts, "verbose", False)), log=log,
-                                mask_padding=bool(epoch_options(opts)), rank=rank, world=world, stats=stats, class_map=class_map)
+                                mask_padding=bool(epoch_options(opts)), rank=rank, world=world, stats=stats, class_map=class_map,
+                                n_skip_frame=getattr(opts, "n_skip_frame", 1), **ctm)
     if rank == 0:
         log("time used for decode: %.4f minutes." % ((time.time() - start) / 60.0))
     return cer, wer
@@ -163,20 +286,5 @@ def main(conf, test_loader=None, index2word=None, log=print):
 
 if __name__ == "__main__":
     import yaml
-    ap = argparse.ArgumentParser(description="decode + score a ctc_best_model.pkl on MI355X, optionally with the utterance lengths passed to the model")
-    ap.add_argument("--conf", help="conf file (same keys as timit/conf/ctc_config.yaml, plus mask_padding)")
-    ap.add_argument("--mask-padding", action="store_true", help="tell the model every utterance's real frames (default: the YAML's mask_padding, else off)")
-    ap.add_argument("--error-report", action="store_true", help="log the error breakdown (sub / del / ins, top confusions) after the CER / WER lines (default: the YAML's error_report, else off)")
-    ap.add_argument("--score-map", default=None, help="three-column phone table the breakdown is scored under (default: the YAML's score_map, else none)")
-    ap.add_argument("--score-map-cols", default=None, choices=["60-48", "60-39", "48-39"], help="which fold of the table (default: the YAML's score_map_cols, else 48-39)")
-    a = ap.parse_args()
-    conf = yaml.safe_load(open(a.conf, "r"))
-    if a.error_report:
-        conf["error_report"] = True
-    if a.score_map is not None:
-        conf["score_map"] = a.score_map
-    if a.score_map_cols is not None:
-        conf["score_map_cols"] = a.score_map_cols
-    if a.mask_padding:
-        conf["mask_padding"] = True
-    main(conf)
+    a = arg_parser().parse_args()
+    main(apply_argv(yaml.safe_load(open(a.conf, "r")), a))

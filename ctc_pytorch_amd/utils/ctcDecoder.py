@@ -147,6 +147,50 @@ class Decoder(object):
             out.append((spans, float(scores[b])))
         return out
 
+    # ---- timed, scored output ----------------------------------------------------------------------------
+    def decode_timed(self, prob_tensor, frame_seq_len, frame_stride=1, detail=False):
+        """What `decode` recognises, with where and how sure (ops.path_tokens; the reference has no counterpart): one entry per utterance,
+        (tokens, score) with tokens = [(phone, start * frame_stride, end * frame_stride, confidence), ...] in time order, start / end = the
+        token's first and one-past-last frame, confidence = exp(mean log-prob of the phone over its frames) in (0, 1], score = the
+        log-probability of the path the tokens were read from.  detail=True: tokens are (phone, start, end, confidence, min_lp, mean_margin)
+        -- the phone's lowest frame log-prob and its mean lead over the best other class.  frame_stride is a plain multiplier, as in
+        `align`.  One device-to-host copy per batch."""
+        raise NotImplementedError
+
+    def timed_strings(self, timed):
+        """The strings `decode` returns for the same batch, from the entries of `decode_timed` (all of them present): each token
+        contributes ' ' + phone when space_idx == -1, else the space symbol becomes ' ' (GreedyDecoder.decode's rule; BeamDecoder joins
+        the phones with ' ', as its search does)."""
+        if self.space_idx == -1:
+            return ["".join([" " + tok[0] for tok in entry[0]]) for entry in timed]
+        space = self.int_to_char[self.space_idx]
+        return ["".join([" " if tok[0] == space else tok[0] for tok in entry[0]]) for entry in timed]
+
+    def _timed(self, pt, frame_stride=1, detail=False, ok=None):
+        """Host half of `decode_timed`: an ops.PathTokens (on the device) and, optionally, a (B) int32 device vector `ok` (0: the utterance
+        has no entry) -> the list `decode_timed` returns, after one copy of everything to the host."""
+        B, T = pt.ids.shape
+        f = lambda t: t.reshape(-1).view(torch.float32)
+        parts = [f(pt.ids), f(pt.starts), f(pt.ends), f(pt.lengths), pt.mean_lp.reshape(-1), pt.min_lp.reshape(-1), pt.mean_margin.reshape(-1),
+                 pt.path_score.reshape(-1)] + ([f(ok.to(torch.int32))] if ok is not None else [])
+        blob = torch.cat(parts).cpu().numpy()
+        cuts = np.cumsum([p.numel() for p in parts])[:-1]
+        ids, st, en, n, mean, mn, mg, sc, *rest = np.split(blob, cuts)
+        ids, st, en = (a.view(np.int32).reshape(B, T) for a in (ids, st, en))
+        n, mean, mn, mg = n.view(np.int32), mean.reshape(B, T), mn.reshape(B, T), mg.reshape(B, T)
+        good = rest[0].view(np.int32) if rest else np.ones(B, dtype=np.int32)
+        conf = np.exp(mean.astype(np.float64))
+        out = []
+        for b in range(B):                                             # (whole rows through tolist(): no per-token numpy scalar)
+            if not good[b]:
+                out.append(None)
+                continue
+            k = int(n[b])
+            cols = [[self.int_to_char[i] for i in ids[b, :k].tolist()], (st[b, :k] * frame_stride).tolist(), (en[b, :k] * frame_stride).tolist(),
+                    conf[b, :k].tolist()] + ([mn[b, :k].tolist(), mg[b, :k].tolist()] if detail else [])
+            out.append((list(zip(*cols)), float(sc[b])))
+        return out
+
     # ---- id / string plumbing ----------------------------------------------------------------------------
     @staticmethod
     def _unflatten_targets(targets, target_sizes):
@@ -204,6 +248,11 @@ class GreedyDecoder(Decoder):
         ids, out_len = ops.greedy_collapse(ops.argmax_last(_to_device(prob_tensor)), frame_seq_len, blank=self.blank_index)
         return ids, out_len, None
 
+    def decode_timed(self, prob_tensor, frame_seq_len, frame_stride=1, detail=False):
+        """Decoder.decode_timed on the arg-max path: the tokens are `decode`'s, a token's frames the run of arg-max frames it was collapsed from."""
+        lp = _to_device(prob_tensor)
+        return self._timed(ops.path_tokens(ops.argmax_last(lp), frame_seq_len, lp, blank=self.blank_index), frame_stride, detail)
+
     def decode(self, prob_tensor, frame_seq_len):
         """Same strings as the reference: each kept frame contributes ' '+phone when space_idx == -1."""
         lp = _to_device(prob_tensor)
@@ -235,6 +284,29 @@ class BeamDecoder(Decoder):
         d = self._decoder
         ids, out_len, _, status = ops.beam_decode_device(lp, frame_seq_len, d._lm_table_on(lp.device), d.lm_alpha, d.beamWidth, d.blank_index, False)
         return ids, out_len, status
+
+    def decode_timed(self, prob_tensor, frame_seq_len=None, frame_stride=1, detail=False):
+        """Decoder.decode_timed for the search's hypothesis: the hypothesis (the ids the search leaves on the device) is force-aligned to the
+        log-probs (ops.ctc_forced_align) and the tokens are read from the alignment's path, so a token's frames are those of its best CTC
+        path and `score` is that path's log-probability (not the search's LM-weighted score).  One small read of the hypothesis lengths
+        sizes the alignment's lattice (Lmax = the longest hypothesis, not T).  None for an utterance whose search did not end with status 0
+        or whose hypothesis has no alignment; a hypothesis beyond the aligner's 2 047 labels raises ValueError."""
+        lp = _to_device(prob_tensor)
+        if frame_seq_len is None:
+            frame_seq_len = [lp.shape[0]] * lp.shape[1]
+        ids, out_len, status = self._device_ids(lp, frame_seq_len)
+        done = status == 0
+        hyp_len = torch.where(done, out_len, torch.zeros_like(out_len)).to(torch.int64)
+        Lmax = int(hyp_len.max())                                       # (the one small read)
+        if Lmax > 2047:
+            raise ValueError("BeamDecoder.decode_timed: a hypothesis of %d labels is beyond the aligner's 2047" % Lmax)
+        lens = frame_seq_len if torch.is_tensor(frame_seq_len) else [int(n) for n in frame_seq_len]
+        a = ops.ctc_forced_align(lp, ids[:, :Lmax].to(torch.int64), lens, hyp_len, blank=self.blank_index)
+        pt = ops.path_tokens(a.paths, lens, lp, blank=self.blank_index, batch_major=True)
+        return self._timed(pt, frame_stride, detail, ok=a.ok * done.to(torch.int32))
+
+    def timed_strings(self, timed):
+        return [" ".join([tok[0] for tok in entry[0]]) for entry in timed]
 
     def decode_async(self, prob_tensor, frame_seq_len=None):
         """decode() enqueued on the current stream: returns a callable that waits for this batch alone and returns its strings

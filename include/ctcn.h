@@ -505,6 +505,27 @@ int ctcn_comm_destroy(void *comm);
 int ctcn_greedy_collapse(const int32_t *idx, size_t stride_t, size_t stride_b, const int32_t *lens, int32_t *out_ids,
                          int32_t *out_len, int T, int B, int blank, void *stream);
 
+/* Tokens of a per-frame class path with their frames and scores: what ctcn_greedy_collapse throws away.  The path is the arg-max
+ * path (ctcn_argmax) or the `paths` of ctcn_ctc_align; the reference has no counterpart (its decoders return strings).
+ * path int32, element (t,b) at path[t*stride_t+b*stride_b] as for ctcn_greedy_collapse; lp (T,B,V) float32 contiguous; lens (B) int32;
+ * any blank in [0, V).  For utterance b, n = clamp(lens[b], 0, T), k_t = path[t, b]:
+ *   a class id outside [0, V) counts as blank; its frame never indexes lp and adds 0 to every sum (ctcn_ctc_align writes -1 for
+ *   utterances without an alignment);
+ *   frame t < n starts token j when k_t is not blank and (t == 0 or k_t != k_{t-1}) -- ctcn_greedy_collapse's rule, the same integers for
+ *   a path of valid ids; start_j = t; end_j = the first t' > t with t' == n or k_t' != k_t;
+ *   over the frames t of [start_j, end_j), k the token's class:
+ *     tok_mean_j = mean of lp[t, b, k]; tok_min_j = their minimum (exact);
+ *     tok_margin_j = mean of lp[t, b, k] - max_{c != k} lp[t, b, c] (the max exact, the difference taken in double);
+ *   path_score[b] = sum over all t < n of lp[t, b, k_t], blank frames included.
+ *   Sums accumulate in double and are rounded once to float32.
+ * Outputs (every element is written, the caller need not clear them): out_ids, starts, ends (B,T) int32, -1 from out_len[b] on;
+ *   out_len (B) int32; tok_mean, tok_min, tok_margin (B,T) float32, 0 from out_len[b] on; path_score (B) float32, 0 for n == 0.
+ * One workgroup per utterance; the row of a frame inside a token is read once (for the best competitor), a blank frame's one element,
+ * nothing at or past n.  No workspace, no learnt state, no option. */
+int ctcn_path_tokens(const int32_t *path, size_t stride_t, size_t stride_b, const float *lp, const int32_t *lens, int32_t *out_ids,
+                     int32_t *out_len, int32_t *starts, int32_t *ends, float *tok_mean, float *tok_min, float *tok_margin,
+                     float *path_score, int T, int B, int V, int blank, void *stream);
+
 /* Levenshtein distance per utterance between collapsed predictions a (B,lda) int32 / a_len (B) int32 and labels
  * b (B,ldb) int64 / b_len (B) int64 -> out (B) int32; replaces editdistance.eval in CTC_Model.compute_wer
  * (model_ctc.py:200).  max_b_len >= max(b_len). */
