@@ -97,6 +97,12 @@ _SIGS = {
     "ctcn_edit_ops_ws_bytes": (Z, [I, I, I]),
     "ctcn_edit_ops": (I, [P, P, P, P, P, I, P, P, P, P, I, I, I, I, P, Z, P]),
     "ctcn_step_stats": (I, [P, P, P, I, P, P, P]),
+    "ctcn_fbank_frames": (I, [ctypes.c_longlong, I, I, I]),
+    "ctcn_fbank_plan_bytes": (Z, [P]),
+    "ctcn_fbank_plan": (I, [P, P, Z]),
+    "ctcn_fbank": (I, [P, I, P, P, P, P, P, P, P, I, I, I, F, U, U, P]),
+    "ctcn_cmvn_accumulate_ws_bytes": (Z, [I, I, I]),
+    "ctcn_cmvn_accumulate": (I, [P, P, P, I, I, I, P, Z, P]),
     "ctcn_comm_unique_id": (I, [P]),
     "ctcn_comm_init": (I, [P, I, I, ctypes.POINTER(ctypes.c_void_p)]),
     "ctcn_comm_allreduce_sum_f32": (I, [P, P, Z, P]),
@@ -121,6 +127,14 @@ class RnnCall(ctypes.Structure):
                 ("dy_tmp", ctypes.c_void_p), ("side_stream", ctypes.c_void_p), ("side_event", ctypes.c_void_p), ("side_ws", ctypes.c_void_p),
                 ("side_ws_bytes", ctypes.c_size_t), ("xcd_allow", ctypes.c_uint), ("prelaunch_event", ctypes.c_void_p), ("status", ctypes.c_void_p),
                 ("launched", ctypes.POINTER(ctypes.c_char_p))]
+
+
+class FbankOpts(ctypes.Structure):
+    """ctcn_fbank_opts of include/ctcn.h: Kaldi's filterbank options (utils/features.FbankConfig fills it)."""
+    _fields_ = [(k, ctypes.c_float) for k in ("samp_freq", "frame_shift_ms", "frame_length_ms", "preemph_coeff", "blackman_coeff", "low_freq",
+                                              "high_freq", "energy_floor")] + \
+               [(k, ctypes.c_int32) for k in ("window_type", "num_mel_bins", "remove_dc_offset", "round_to_power_of_two", "snip_edges",
+                                              "use_energy", "raw_energy", "htk_compat", "use_log_fbank", "use_power")]
 
 
 def sources():

@@ -1,0 +1,313 @@
+// fbank.hip -- the filterbank front-end: waveform -> (normalised) log-mel features, and the statistics of the global mean / variance
+// normalisation (ctcn_fbank_frames, ctcn_fbank_plan, ctcn_fbank, ctcn_cmvn_accumulate; contract and plan layout in include/ctcn.h).
+//
+// fbank_kernel<NPAD>: grid (frame blocks, utterances), four waves per workgroup.
+//   1. The workgroup stages the plan (float64 twiddles, window, filter table, weights: 6 NPAD + 384 words) and the sample span of its `fpw` (<= 8)
+//      consecutive frames in LDS once: neighbouring frames share all but `shift` of their samples.  int16 input is converted here;
+//      snip_edges == 0 reflects indices outside the signal here.
+//   2. One wave owns one frame at a time, lane l holding samples l, l + 64, ... (NPAD / 64 of them: conflict-free LDS rows).  Dither, DC
+//      removal, raw energy, pre-emphasis (the left neighbour is the previous lane's value: one rotation per register) and the window run
+//      in registers, with wave_sum for the two reductions.
+//   3. Real FFT as the half-length complex transform of z[m] = x[2m] + i x[2m+1] plus a split step, in float64 (fbank_core.h says why):
+//      the windowed frame goes to the wave's LDS buffer, where pairs ARE z; three Stockham passes of radix 8, 8 and NPAD / 128 ping-pong between the wave's two buffers
+//      (fbank_core.h), twiddles from the plan's table; the split step writes the power spectrum of bins 0 .. NPAD/2 - 1.
+//   4. Lanes take mel filters (lane, lane + 64): a filter is a contiguous bin range, a dot product of <= ~30 terms; log, energy column,
+//      (x - mean) * scale, one coalesced row store.
+//   Rows of the block at or beyond the utterance's frame count are zero-filled by the whole workgroup first.
+//   Waves of a workgroup never wait for each other after the staging barrier: the FFT buffers are per wave, ordered by wave_lds_sync.
+// cmvn_partial_kernel / cmvn_finish_kernel: float64 column sums of 64-row blocks into the workspace, then one thread per statistic adds the
+//   partials in index order into the caller's block (norm.hip's scheme: no atomics, a function of the input bits).
+#include <algorithm>
+
+#include "common.h"
+#include "fbank_core.h"
+
+namespace {
+
+constexpr size_t FBANK_LDS_LIMIT = 160 * 1024;     // a CU's LDS; launches beyond 64 KB opt in (Npad = 1024: 99 KB)
+constexpr int CMVN_ROWS = 64;
+
+struct FbankArgs {
+  const void *wave;
+  const int32_t *lens;
+  const float *plan;
+  const float *mean, *scale;
+  float *feats;
+  int32_t *frames;
+  uint64_t seed, utt_offset;
+  int is_i16, Nmax, Tmax, L, shift, nbins, F, fpw;
+  int snip, remove_dc, use_energy, raw_energy, htk, use_log, use_power, has_floor;
+  float preemph, log_floor, dither;
+};
+
+static inline size_t fbank_lds_words(int npad, int L, int shift, int fpw) {
+  return (size_t)22 * npad + 3 * FBANK_MAX_BINS + (size_t)(fpw - 1) * shift + L;      // 4-byte words: twiddles 4, wave buffers 16, window 1, weights 1 (x npad)
+}
+
+// LDS traffic between the lanes of ONE wave: drain the wave's own LDS operations and keep the compiler from moving accesses across.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// N(0, 1) for sample i of frame `frame` of utterance `utt`: one Philox call per sample pair, Box-Muller's cosine for the even, sine for the odd one
+__device__ __forceinline__ float fbank_gauss(uint64_t seed, uint64_t utt, int frame, int i) {
+  uint32_t w[4];
+  philox4(seed, (utt << 38) | ((uint64_t)(uint32_t)frame << 10) | (uint64_t)(i >> 1), w);
+  const float u1 = ((float)(w[0] >> 8) + 1.0f) * 5.9604644775390625e-08f;      // (0, 1]
+  const float th = 6.28318530717958647692f * ((float)(w[1] >> 8) * 5.9604644775390625e-08f);
+  const float r = sqrtf(-2.0f * logf(u1));
+  return r * ((i & 1) ? sinf(th) : cosf(th));
+}
+
+template <int NPAD>
+__global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
+  constexpr int P = NPAD / 64, M = NPAD / 2;
+  extern __shared__ __align__(16) double smem_d[];
+  fbc *tw = reinterpret_cast<fbc *>(smem_d);                        // NPAD complex doubles
+  double *wbuf = smem_d + 2 * NPAD;                                 // 4 waves x 2 x NPAD doubles (M complex each)
+  float *win = reinterpret_cast<float *>(wbuf + 8 * NPAD);          // NPAD
+  float *wts = win + NPAD;                                          // NPAD
+  int *ftab = reinterpret_cast<int *>(wts + NPAD);                  // first | count | weight offset, 128 each
+  float *span = wts + NPAD + 3 * FBANK_MAX_BINS;
+
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int L = a.L, shift = a.shift, F = a.F;
+  const int n = min(max(a.lens[b], 0), a.Nmax);
+  const int Tb = min(fbank_num_frames(n, L, shift, a.snip), a.Tmax);
+  if (blockIdx.x == 0 && tid == 0) a.frames[b] = Tb;
+  const int f0 = blockIdx.x * a.fpw;
+  float *out = a.feats + (size_t)b * a.Tmax * F;
+  {
+    const size_t zend = (size_t)min(f0 + a.fpw, a.Tmax) * F;
+    for (size_t i = (size_t)max(f0, Tb) * F + tid; i < zend; i += 256) out[i] = 0.f;
+  }
+  const int nf = min(a.fpw, Tb - f0);
+  if (nf <= 0) return;                                               // (the whole workgroup: nothing below is reached by a part of it)
+
+  // ---- 1. stage the plan and the samples ---------------------------------------------------------------------------------------------
+  {
+    const double *p_tw = reinterpret_cast<const double *>(a.plan + NPAD);
+    const float *p_tab = a.plan + 5 * NPAD;
+    for (int i = tid; i < 2 * NPAD; i += 256) smem_d[i] = p_tw[i];
+    for (int i = tid; i < NPAD; i += 256) win[i] = a.plan[i];
+    for (int i = tid; i < 3 * FBANK_MAX_BINS; i += 256) ftab[i] = reinterpret_cast<const int *>(p_tab)[i];
+    for (int i = tid; i < NPAD; i += 256) wts[i] = p_tab[3 * FBANK_MAX_BINS + i];
+    const long long s0 = (long long)f0 * shift + (a.snip ? 0 : shift / 2 - L / 2);
+    const int span_len = (nf - 1) * shift + L;
+    const size_t base = (size_t)b * a.Nmax;
+    for (int i = tid; i < span_len; i += 256) {
+      long long s = s0 + i;
+      while (s < 0 || s >= n) s = s < 0 ? -s - 1 : 2LL * n - 1 - s;    // Kaldi's reflection; n >= 1 here (Tb > 0), and with snip_edges s is inside already
+      span[i] = a.is_i16 ? (float)static_cast<const int16_t *>(a.wave)[base + s] : static_cast<const float *>(a.wave)[base + s];
+    }
+  }
+  __syncthreads();
+
+  double *bufA = wbuf + wv * 2 * NPAD, *bufB = bufA + NPAD;
+  fbc *zA = reinterpret_cast<fbc *>(bufA), *zB = reinterpret_cast<fbc *>(bufB);
+  float *pw = reinterpret_cast<float *>(bufA);                      // the power spectrum, once the transform has left bufA
+  const int mel_off = (a.use_energy && !a.htk) ? 1 : 0;
+  const bool norm = a.mean != nullptr;
+
+  for (int fi = wv; fi < nf; fi += 4) {
+    const int frame = f0 + fi;
+    const float *fr = span + fi * shift;
+    // ---- 2. the frame in registers ------------------------------------------------------------------------------------------------------
+    float x[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      const int i = lane + 64 * j;
+      x[j] = i < L ? fr[i] : 0.f;
+    }
+    if (a.dither > 0.f) {
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        const int i = lane + 64 * j;
+        if (i < L) x[j] += a.dither * fbank_gauss(a.seed, (uint64_t)b + a.utt_offset, frame, i);
+      }
+    }
+    if (a.remove_dc) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < P; ++j) s += x[j];
+      const float mean = wave_sum(s) / (float)L;
+#pragma unroll
+      for (int j = 0; j < P; ++j)
+        if (lane + 64 * j < L) x[j] -= mean;
+    }
+    float energy = 0.f;
+    if (a.use_energy && a.raw_energy) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < P; ++j) s += x[j] * x[j];
+      energy = wave_sum(s);
+    }
+    if (a.preemph != 0.f) {
+      float rot[P];                                                   // sample i - 1 lives in the previous lane; lane 0 takes lane 63's previous register
+#pragma unroll
+      for (int j = 0; j < P; ++j) rot[j] = __shfl(x[j], (lane + 63) & 63, 64);
+      const float x0 = x[0];
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        const float prev = lane != 0 ? rot[j] : (j == 0 ? x0 : rot[j > 0 ? j - 1 : 0]);
+        x[j] -= a.preemph * prev;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < P; ++j) x[j] *= win[lane + 64 * j];           // 0 from L on: the zero padding
+    if (a.use_energy && !a.raw_energy) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < P; ++j) s += x[j] * x[j];
+      energy = wave_sum(s);
+    }
+    // ---- 3. real FFT -> power spectrum ------------------------------------------------------------------------------------------------------
+#pragma unroll
+    for (int j = 0; j < P; ++j) bufA[lane + 64 * j] = (double)x[j];
+    wave_lds_sync();
+    fbank_fft_pass<M, 8>(lane, 1, zA, zB, tw);
+    wave_lds_sync();
+    fbank_fft_pass<M, 8>(lane, 8, zB, zA, tw);
+    wave_lds_sync();
+    fbank_fft_pass<M, M / 64>(lane, 64, zA, zB, tw);
+    wave_lds_sync();
+    for (int k = lane; k < M; k += 64) {
+      const double p = fbank_split_power<M>(k, zB, tw);
+      pw[k] = (float)(a.use_power ? p : sqrt(p));
+    }
+    wave_lds_sync();
+    // ---- 4. mel bank, log, energy, normalisation -------------------------------------------------------------------------------------------
+    float *row = out + (size_t)frame * F;
+    for (int m = lane; m < a.nbins; m += 64) {
+      const int first = ftab[m], cnt = ftab[FBANK_MAX_BINS + m];
+      const float *w = wts + ftab[2 * FBANK_MAX_BINS + m];
+      float e = 0.f;
+      for (int i = 0; i < cnt; ++i) e += w[i] * pw[first + i];
+      if (a.use_log) e = logf(fmaxf(e, FLT_EPSILON));
+      const int col = m + mel_off;
+      if (norm) e = (e - a.mean[col]) * a.scale[col];
+      row[col] = e;
+    }
+    if (a.use_energy && lane == 0) {
+      float le = logf(fmaxf(energy, FLT_EPSILON));
+      if (a.has_floor && le < a.log_floor) le = a.log_floor;
+      const int col = a.htk ? a.nbins : 0;
+      if (norm) le = (le - a.mean[col]) * a.scale[col];
+      row[col] = le;
+    }
+    wave_lds_sync();                                                  // the next frame overwrites bufA (pw)
+  }
+}
+
+// Partial sums of rows [c * 64, c * 64 + 64) below frames[b] of utterance b: ws[(b * chunks + c)][2][F] doubles (zeros for an empty block).
+__global__ __launch_bounds__(256) void cmvn_partial_kernel(const float *__restrict__ feats, const int32_t *__restrict__ frames, double *__restrict__ ws,
+                                                           int Tmax, int F) {
+  const int b = blockIdx.y, c = blockIdx.x, chunks = gridDim.x;
+  const int Tb = min(max(frames[b], 0), Tmax);
+  const int t0 = c * CMVN_ROWS, t1 = min(t0 + CMVN_ROWS, Tb);
+  double *o = ws + ((size_t)b * chunks + c) * 2 * F;
+  const float *x = feats + (size_t)b * Tmax * F;
+  for (int f = threadIdx.x; f < F; f += 256) {
+    double s = 0.0, q = 0.0;
+    for (int t = t0; t < t1; ++t) {
+      const double v = (double)x[(size_t)t * F + f];
+      s += v;
+      q += v * v;
+    }
+    o[f] = s;
+    o[F + f] = q;
+  }
+}
+
+// thread i < 2F adds its column of the partials in index order into stats; thread 2F adds the frame count
+__global__ __launch_bounds__(256) void cmvn_finish_kernel(const double *__restrict__ ws, const int32_t *__restrict__ frames, double *__restrict__ stats,
+                                                          int B, int Tmax, int F, int chunks) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < 2 * F) {
+    double s = 0.0;
+    for (size_t p = 0; p < (size_t)B * chunks; ++p) s += ws[p * 2 * F + i];
+    stats[i < F ? i : i + 1] += s;                                    // row 1 starts at F + 1
+  } else if (i == 2 * F) {
+    double cnt = 0.0;
+    for (int b = 0; b < B; ++b) cnt += (double)min(max(frames[b], 0), Tmax);
+    stats[F] += cnt;
+  }
+}
+
+}  // namespace
+
+extern "C" int ctcn_fbank_frames(long long num_samples, int frame_length, int frame_shift, int snip_edges) {
+  CTCN_REQUIRE(num_samples >= 0 && frame_length > 0 && frame_shift > 0, "ctcn_fbank_frames: bad args (samples %lld, frame length %d, shift %d)",
+               num_samples, frame_length, frame_shift);
+  CTCN_REQUIRE((num_samples + frame_shift / 2) / frame_shift < 0x7fffffffLL, "ctcn_fbank_frames: frame count beyond int");
+  return fbank_num_frames(num_samples, frame_length, frame_shift, snip_edges);
+}
+
+extern "C" size_t ctcn_fbank_plan_bytes(const ctcn_fbank_opts *opts) {
+  FbankGeom g;
+  const char *why;
+  return fbank_geom(opts, &g, &why) == CTCN_OK ? g.words * 4 : 0;
+}
+
+extern "C" int ctcn_fbank_plan(const ctcn_fbank_opts *opts, void *plan, size_t plan_bytes) {
+  FbankGeom g;
+  const char *why;
+  int rc = fbank_geom(opts, &g, &why);
+  if (rc != CTCN_OK) { ctcn_set_error("ctcn_fbank_plan: %s", why); return rc; }
+  CTCN_REQUIRE(plan && plan_bytes >= g.words * 4, "ctcn_fbank_plan: buffer of %zu bytes needed", g.words * 4);
+  rc = fbank_build_plan(opts, g, plan, &why);
+  if (rc != CTCN_OK) ctcn_set_error("ctcn_fbank_plan: %s", why);
+  return rc;
+}
+
+extern "C" int ctcn_fbank(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_fbank_opts *opts, const void *plan, const float *mean,
+                          const float *scale, float *feats, int32_t *frames, int B, int Nmax, int Tmax, float dither, uint64_t seed,
+                          uint64_t utt_offset, void *stream) {
+  FbankGeom g;
+  const char *why;
+  const int rc = fbank_geom(opts, &g, &why);
+  if (rc != CTCN_OK) { ctcn_set_error("ctcn_fbank: %s", why); return rc; }
+  CTCN_REQUIRE(lens && plan && frames && B > 0 && Nmax >= 0 && Tmax >= 0 && (wave || Nmax == 0) && (feats || Tmax == 0), "ctcn_fbank: bad args");
+  CTCN_REQUIRE((mean == nullptr) == (scale == nullptr), "ctcn_fbank: mean and scale come together");
+  CTCN_REQUIRE(dither >= 0.f && B <= 65535, "ctcn_fbank: dither must not be negative, B at most 65 535 per call (B %d)", B);
+  int fpw = 8;
+  while (fpw > 1 && fbank_lds_words(g.npad, g.L, g.shift, fpw) * 4 > FBANK_LDS_LIMIT) fpw >>= 1;
+  const size_t lds = fbank_lds_words(g.npad, g.L, g.shift, fpw) * 4;
+  if (lds > FBANK_LDS_LIMIT) { ctcn_set_error("ctcn_fbank: frame shift %d too long for the LDS staging", g.shift); return CTCN_EUNSUPPORTED; }
+  FbankArgs a;
+  a.wave = wave; a.lens = lens; a.plan = static_cast<const float *>(plan); a.mean = mean; a.scale = scale; a.feats = feats; a.frames = frames;
+  a.seed = seed; a.utt_offset = utt_offset;
+  a.is_i16 = wave_is_int16 != 0; a.Nmax = Nmax; a.Tmax = Tmax; a.L = g.L; a.shift = g.shift; a.nbins = g.nbins; a.F = g.F; a.fpw = fpw;
+  a.snip = opts->snip_edges != 0; a.remove_dc = opts->remove_dc_offset != 0; a.use_energy = opts->use_energy != 0; a.raw_energy = opts->raw_energy != 0;
+  a.htk = opts->htk_compat != 0; a.use_log = opts->use_log_fbank != 0; a.use_power = opts->use_power != 0;
+  a.has_floor = opts->energy_floor > 0.f; a.log_floor = a.has_floor ? logf(opts->energy_floor) : 0.f;
+  a.preemph = opts->preemph_coeff; a.dither = dither;
+  const dim3 grid(std::max(ceil_div(Tmax, fpw), 1), B);
+  hipStream_t st = (hipStream_t)stream;
+  void (*kern)(FbankArgs) = g.npad == 256 ? fbank_kernel<256> : g.npad == 512 ? fbank_kernel<512> : fbank_kernel<1024>;
+  if (lds > 64 * 1024) CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" size_t ctcn_cmvn_accumulate_ws_bytes(int B, int Tmax, int F) {
+  if (B <= 0 || Tmax <= 0 || F <= 0) return 0;
+  return (size_t)B * ceil_div(Tmax, CMVN_ROWS) * 2 * F * sizeof(double);
+}
+
+extern "C" int ctcn_cmvn_accumulate(const float *feats, const int32_t *frames, double *stats, int B, int Tmax, int F, void *ws, size_t ws_bytes,
+                                    void *stream) {
+  CTCN_REQUIRE(feats && frames && stats && B > 0 && Tmax > 0 && F > 0 && B <= 65535, "ctcn_cmvn_accumulate: bad args");
+  const size_t need = ctcn_cmvn_accumulate_ws_bytes(B, Tmax, F);
+  CTCN_REQUIRE(ws && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)stats & 7) == 0, "ctcn_cmvn_accumulate: workspace of ctcn_cmvn_accumulate_ws_bytes needed, 8-byte aligned");
+  if (ws_bytes < need) { ctcn_set_error("ctcn_cmvn_accumulate: workspace %zu < %zu bytes", ws_bytes, need); return CTCN_EWORKSPACE; }
+  const int chunks = ceil_div(Tmax, CMVN_ROWS);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(cmvn_partial_kernel, dim3(chunks, B), dim3(256), 0, st, feats, frames, static_cast<double *>(ws), Tmax, F);
+  CTCN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cmvn_finish_kernel, dim3(ceil_div(2 * F + 1, 256)), dim3(256), 0, st, static_cast<const double *>(ws), frames, stats, B, Tmax, F, chunks);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}

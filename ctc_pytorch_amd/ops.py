@@ -1845,3 +1845,102 @@ def adam_step_ex(p, g, m, v, beta1, beta2, eps, weight_decay, ctl):
     _need_gpu(p, g, m, v, ctl)
     _lib.check(_lib.lib().ctcn_adam_step_ex(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(beta1), float(beta2), float(eps),
                                             float(weight_decay), _ptr(ctl), _lib.stream_ptr()), "adam_step_ex")
+
+
+# --------------------------------------------------------------------------------------------------
+# filterbank front-end (fbank.hip): waveform -> normalised log-mel features, CMVN statistics
+# --------------------------------------------------------------------------------------------------
+def fbank_frames(num_samples, frame_length, frame_shift, snip_edges=True):
+    """Frames of a signal of num_samples samples (ctcn_fbank_frames; lengths in samples): Kaldi's two rules.  Host arithmetic, no device."""
+    r = _lib.lib().ctcn_fbank_frames(int(num_samples), int(frame_length), int(frame_shift), int(bool(snip_edges)))
+    if r < 0:
+        raise ValueError("ctc_pytorch_amd.fbank_frames: bad arguments (samples %r, frame length %r, shift %r)" % (num_samples, frame_length, frame_shift))
+    return r
+
+
+class FbankPlan(object):
+    """The plan of one filterbank configuration (ctcn_fbank_plan: window, twiddles, mel filters): built on the host from an _lib.FbankOpts when
+    the object is made -- a RuntimeError here, before any launch, for a configuration the kernel does not take -- and uploaded once per
+    device on first use.  `host` is the block as uint32 words (layout in include/ctcn.h)."""
+
+    def __init__(self, opts):
+        L = _lib.lib()
+        self.opts = opts
+        nbytes = L.ctcn_fbank_plan_bytes(ctypes.byref(opts))
+        buf = np.zeros(max(nbytes // 4, 1), dtype=np.uint32)
+        _lib.check(L.ctcn_fbank_plan(ctypes.byref(opts), buf.ctypes.data_as(ctypes.c_void_p), nbytes), "fbank_plan")
+        self.host = buf
+        self.frame_length = int(float(opts.samp_freq) * 0.001 * float(opts.frame_length_ms))
+        self.frame_shift = int(float(opts.samp_freq) * 0.001 * float(opts.frame_shift_ms))
+        self.padded_length = 1 << (self.frame_length - 1).bit_length()
+        self.num_mel_bins = int(opts.num_mel_bins)
+        self.feat_dim = self.num_mel_bins + (1 if opts.use_energy else 0)
+        self.snip_edges = bool(opts.snip_edges)
+        self._dev = {}
+
+    def num_frames(self, num_samples):
+        return fbank_frames(num_samples, self.frame_length, self.frame_shift, self.snip_edges)
+
+    def on(self, device):
+        key = (device.type, device.index)
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.host.view(np.int32)).to(device)
+        return t
+
+
+def fbank(wave, lengths, plan, mean=None, scale=None, dither=0.0, seed=0, utt_offset=0):
+    """Filterbank features of a padded batch of waveforms (ctcn_fbank; the computation, step by step, in include/ctcn.h): wave (B, Nmax)
+    float32 on Kaldi's scale (the int16 range) or int16; lengths (B) samples, a list or a tensor (read on the host: the frame counts size
+    the output); plan a FbankPlan; mean / scale (F) float32 device vectors or None: (x - mean) * scale applied by the same kernel.
+    Returns (feats (B, Tmax, F) float32, frames (B) int32) with Tmax = the largest frame count; rows from frames[b] on are zero.  dither > 0
+    adds dither * N(0, 1) per extracted sample, a function of (seed, b + utt_offset, frame, sample) alone.  No autograd; device tensors only
+    (no CPU fallback)."""
+    if wave.dim() != 2:
+        raise ValueError("ctc_pytorch_amd.fbank: expected wave (B, Nmax), got %s" % (tuple(wave.shape),))
+    _need_gpu(wave, mean, scale)
+    if wave.dtype not in (torch.float32, torch.int16):
+        raise TypeError("ctc_pytorch_amd.fbank: expected float32 or int16 samples, got %s" % wave.dtype)
+    if (mean is None) != (scale is None):
+        raise ValueError("ctc_pytorch_amd.fbank: mean and scale come together")
+    B, Nmax = wave.shape
+    host_lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(host_lens) != B or B == 0:
+        raise ValueError("ctc_pytorch_amd.fbank: %d lengths for a batch of %d" % (len(host_lens), B))
+    if not float(dither) >= 0.0:
+        raise ValueError("ctc_pytorch_amd.fbank: dither must not be negative, got %r" % (dither,))
+    dev, F = wave.device, plan.feat_dim
+    wave = wave.contiguous()
+    for v in (mean, scale):
+        if v is not None and (v.dtype != torch.float32 or v.numel() != F):
+            raise ValueError("ctc_pytorch_amd.fbank: mean / scale must hold %d float32 values" % F)
+    mean, scale = (None, None) if mean is None else (mean.contiguous(), scale.contiguous())
+    Tmax = max(plan.num_frames(min(max(n, 0), Nmax)) for n in host_lens)
+    lens = torch.as_tensor(host_lens, dtype=torch.int32).to(dev)
+    feats = torch.empty((B, Tmax, F), dtype=torch.float32, device=dev)
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().ctcn_fbank(_ptr(wave), int(wave.dtype == torch.int16), _ptr(lens), ctypes.byref(plan.opts), _ptr(plan.on(dev)),
+                                     _ptr(mean), _ptr(scale), _ptr(feats) if Tmax else None, _ptr(frames), B, Nmax, Tmax, float(dither),
+                                     int(seed) & (2 ** 64 - 1), int(utt_offset), _lib.stream_ptr()), "fbank")
+    return feats, frames
+
+
+def cmvn_accumulate(feats, frames, stats):
+    """Adds the rows t < frames[b] of feats (B, Tmax, F) float32 to stats (2, F + 1) float64 on the device, Kaldi's CMVN statistics layout
+    (sums | count; sums of squares | 0): ctcn_cmvn_accumulate.  Rows at or beyond frames[b] are never read; float64 partial sums combined
+    in a fixed order.  Returns stats."""
+    _need_gpu(feats, frames, stats)
+    if feats.dim() != 3 or feats.dtype != torch.float32:
+        raise ValueError("ctc_pytorch_amd.cmvn_accumulate: expected feats (B, Tmax, F) float32, got %s %s" % (tuple(feats.shape), feats.dtype))
+    B, Tmax, F = feats.shape
+    if frames.numel() != B or stats.dtype != torch.float64 or tuple(stats.shape) != (2, F + 1) or not stats.is_contiguous():
+        raise ValueError("ctc_pytorch_amd.cmvn_accumulate: expected frames (%d) and contiguous float64 stats (2, %d)" % (B, F + 1))
+    if B == 0 or Tmax == 0:
+        return stats
+    feats = feats.contiguous()
+    frames = frames.to(device=feats.device, dtype=torch.int32).contiguous()
+    need = _lib.lib().ctcn_cmvn_accumulate_ws_bytes(B, Tmax, F)
+    ws = _lib.workspace(feats.device, nbytes=need, tag="cmvn")
+    _lib.check(_lib.lib().ctcn_cmvn_accumulate(_ptr(feats), _ptr(frames), _ptr(stats), B, Tmax, F, _ptr(ws), ws.numel(), _lib.stream_ptr()),
+               "cmvn_accumulate")
+    return stats

@@ -1,0 +1,120 @@
+"""Audio -> feature archive on the device: the counterpart of the reference's timit/steps/make_feat.sh, whose three Kaldi binaries
+(compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true with one global mean and variance) become
+utils/features.Fbank and GlobalCMVN.
+
+    make_feat.py --conf fbank.conf --wav-scp train/wav.scp --out-dir DIR [--cmvn-stats FILE] [--compute-cmvn]
+
+wav.scp: one `<utterance> <path>` per line (RIFF PCM-16 mono or uncompressed SPHERE; piped commands are not run).  Writes DIR/feats.ark and
+DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDataset and both drivers read them unchanged.
+  --compute-cmvn   two passes: the first accumulates the global statistics on the device and writes them as Kaldi's text matrix
+                   (--cmvn-stats, default DIR/global_fbank_cmvn.txt), the second writes features normalised with them (in the kernel)
+  --cmvn-stats     without --compute-cmvn: statistics to apply (the training set's, for dev and test data); none: raw features
+Utterances are sorted by length and batched under --max-samples padded samples per launch.  Dither is the conf file's (Kaldi's default is
+1.0; `--dither=0` in the conf switches it off), keyed by --seed and the utterance's place in the length-sorted list."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
+
+from ctc_pytorch_amd.utils.data_loader import write_kaldi_ark  # noqa: E402
+from ctc_pytorch_amd.utils.features import Fbank, FbankConfig, GlobalCMVN, read_wave  # noqa: E402
+
+
+def read_wav_scp(path):
+    out = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            parts = line.split(None, 1)
+            if not parts:
+                continue
+            if len(parts) != 2 or parts[1].rstrip().endswith("|"):
+                raise ValueError("%s:%d: expected '<utterance> <path>' (piped commands are not supported)" % (path, ln))
+            out.append((parts[0], parts[1].strip()))
+    return out
+
+
+def length_batches(lengths, max_samples):
+    """Index lists over the length-sorted utterances, each with B * max(length) <= max_samples (a single longer utterance stands alone)."""
+    order = sorted(range(len(lengths)), key=lambda i: (lengths[i], i))
+    batches, cur = [], []
+    for i in order:                                                    # ascending: the newcomer is the batch's longest
+        if cur and (len(cur) + 1) * max(lengths[i], 1) > max_samples:
+            batches.append(cur)
+            cur = []
+        cur.append(i)
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=None):
+    """Features of `waves` (list of int16 arrays), batch by batch: {index: (T, F) float32 ndarray}, or -- with `cmvn` -- nothing kept, the raw
+    features accumulated into it."""
+    mats, place = {}, 0
+    for idx in batches:
+        feats, frames = fbank([waves[i] for i in idx], mean=mean, scale=scale, seed=seed, utt_offset=place)
+        place += len(idx)
+        if cmvn is not None:
+            cmvn.accumulate(feats, frames)
+            continue
+        host, n = feats.cpu().numpy(), frames.cpu().numpy()
+        for b, i in enumerate(idx):
+            mats[i] = host[b, :n[b]].copy()
+    return mats
+
+
+def main(argv=None, log=print):
+    ap = argparse.ArgumentParser(description="waveforms -> (normalised) filterbank features as a Kaldi archive, computed on the MI355X")
+    ap.add_argument("--conf", required=True, help="Kaldi fbank config file (--key=value lines), e.g. the reference's conf/fbank.conf")
+    ap.add_argument("--wav-scp", required=True, help="list of '<utterance> <wav or sphere path>'")
+    ap.add_argument("--out-dir", required=True, help="where feats.ark / feats.scp go")
+    ap.add_argument("--cmvn-stats", default=None, help="Kaldi text CMVN statistics to apply (with --compute-cmvn: where to write them)")
+    ap.add_argument("--compute-cmvn", action="store_true", help="accumulate global statistics over this list first, then normalise with them")
+    ap.add_argument("--max-samples", type=int, default=32 * 8 * 16000, help="cap on padded samples per launch (default: 32 utterances of 8 s at 16 kHz)")
+    ap.add_argument("--seed", type=int, default=0, help="dither seed")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+
+    config = FbankConfig.from_kaldi_conf(args.conf)
+    device = torch.device(args.device)
+    fbank = Fbank(config, device)
+    entries = read_wav_scp(args.wav_scp)
+    if not entries:
+        raise ValueError("%s: no utterances" % args.wav_scp)
+    waves = []
+    for utt, path in entries:
+        samples, rate = read_wave(path)
+        if float(rate) != float(config.sample_frequency):
+            raise ValueError("%s: %s is sampled at %d Hz, the configuration says %g (no resampling here)" % (utt, path, rate, config.sample_frequency))
+        waves.append(samples)
+    batches = length_batches([w.shape[0] for w in waves], args.max_samples)
+    os.makedirs(args.out_dir, exist_ok=True)
+
+    mean = scale = None
+    if args.compute_cmvn:
+        cmvn = GlobalCMVN(fbank.feat_dim, device)
+        make_features(fbank, waves, batches, seed=args.seed, cmvn=cmvn)
+        stats_path = args.cmvn_stats or os.path.join(args.out_dir, "global_fbank_cmvn.txt")
+        cmvn.save_kaldi_text(stats_path)
+        log("wrote CMVN statistics of %d frames to %s" % (int(cmvn.stats[0, -1].item()), stats_path))
+        mean, scale = cmvn.mean_scale(device)
+    elif args.cmvn_stats:
+        cmvn = GlobalCMVN.load_kaldi_text(args.cmvn_stats)
+        if cmvn.feat_dim != fbank.feat_dim:
+            raise ValueError("%s holds statistics of %d dimensions, the configuration gives %d" % (args.cmvn_stats, cmvn.feat_dim, fbank.feat_dim))
+        mean, scale = cmvn.mean_scale(device)
+    mats = make_features(fbank, waves, batches, mean=mean, scale=scale, seed=args.seed)
+    ark, scp = os.path.join(args.out_dir, "feats.ark"), os.path.join(args.out_dir, "feats.scp")
+    write_kaldi_ark(ark, scp, {utt: mats[i] for i, (utt, _) in enumerate(entries)})
+    log("wrote %d utterances, %d frames of %d dimensions to %s" % (len(entries), sum(m.shape[0] for m in mats.values()), fbank.feat_dim, ark))
+    return ark, scp
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,225 @@
+"""Waveform -> normalised filterbank features on the device: the stage in front of utils/data_loader.py.  Counterpart of the three Kaldi
+binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn
+--norm-vars=true with one global mean and variance); steps/make_feat.py is the driver.
+
+  FbankConfig   Kaldi's option names and defaults; from_kaldi_conf reads a `--key=value` file such as the reference's conf/fbank.conf
+  Fbank         the configured front-end on one device (ops.fbank behind it; holds the uploaded plan)
+  GlobalCMVN    Kaldi's 2 x (F + 1) statistics, accumulated on the device (ops.cmvn_accumulate), its text file, mean and 1 / stddev
+  read_wave     RIFF PCM-16 mono and uncompressed NIST SPHERE (TIMIT's) -> int16 samples
+
+Not here: MFCC, pitch, VTLN, deltas, resampling, per-speaker CMVN, compressed SPHERE."""
+import struct
+
+import numpy as np
+import torch
+
+from .. import _lib, ops
+
+WINDOW_TYPES = ("hamming", "hanning", "povey", "rectangular", "blackman")     # the order of ctcn_fbank_opts.window_type
+
+
+class FbankConfig(object):
+    """The options of Kaldi's compute-fbank-feats that the kernel implements, under Kaldi's names (dashes as underscores) and with Kaldi's
+    defaults -- dither = 1.0 among them: pass dither=0 for a deterministic front-end."""
+    DEFAULTS = dict(sample_frequency=16000.0, frame_shift=10.0, frame_length=25.0, dither=1.0, preemphasis_coefficient=0.97,
+                    remove_dc_offset=True, window_type="povey", round_to_power_of_two=True, blackman_coeff=0.42, snip_edges=True,
+                    num_mel_bins=23, low_freq=20.0, high_freq=0.0, use_energy=False, energy_floor=0.0, raw_energy=True, htk_compat=False,
+                    use_log_fbank=True, use_power=True)
+
+    def __init__(self, **kw):
+        for k in kw:
+            if k not in self.DEFAULTS:
+                raise ValueError("FbankConfig: unknown option %r" % k)
+        for k, d in self.DEFAULTS.items():
+            setattr(self, k, self._convert(k, kw.get(k, d)))
+        if self.window_type not in WINDOW_TYPES:
+            raise ValueError("FbankConfig: unknown window type %r (one of %s)" % (self.window_type, ", ".join(WINDOW_TYPES)))
+
+    @classmethod
+    def _convert(cls, key, value):
+        d = cls.DEFAULTS[key]
+        if isinstance(d, bool):
+            if isinstance(value, str):
+                if value.lower() not in ("true", "false", "t", "f", "1", "0"):
+                    raise ValueError("FbankConfig: %s expects true or false, got %r" % (key, value))
+                return value.lower() in ("true", "t", "1")
+            return bool(value)
+        return type(d)(value)
+
+    @classmethod
+    def from_kaldi_conf(cls, path):
+        """A Kaldi config file: one `--key=value` per line, a bare `--flag` means true, `#` starts a comment, blank lines are skipped.
+        A key this front-end does not implement raises ValueError (a silently ignored option would change the features)."""
+        kw = {}
+        with open(path) as f:
+            for ln, line in enumerate(f, 1):
+                line = line.split("#", 1)[0].strip()
+                if not line:
+                    continue
+                if not line.startswith("--"):
+                    raise ValueError("%s:%d: expected --key=value, got %r" % (path, ln, line))
+                key, _, value = line[2:].partition("=")
+                key = key.strip().replace("-", "_")
+                if key not in cls.DEFAULTS:
+                    raise ValueError("%s:%d: unknown or unsupported option --%s" % (path, ln, key.replace("_", "-")))
+                kw[key] = value.strip() if _ else "true"
+        return cls(**kw)
+
+    @property
+    def feat_dim(self):
+        return self.num_mel_bins + (1 if self.use_energy else 0)
+
+    def c_opts(self):
+        return _lib.FbankOpts(samp_freq=self.sample_frequency, frame_shift_ms=self.frame_shift, frame_length_ms=self.frame_length,
+                              preemph_coeff=self.preemphasis_coefficient, blackman_coeff=self.blackman_coeff, low_freq=self.low_freq,
+                              high_freq=self.high_freq, energy_floor=self.energy_floor, window_type=WINDOW_TYPES.index(self.window_type),
+                              num_mel_bins=self.num_mel_bins, remove_dc_offset=self.remove_dc_offset,
+                              round_to_power_of_two=self.round_to_power_of_two, snip_edges=self.snip_edges, use_energy=self.use_energy,
+                              raw_energy=self.raw_energy, htk_compat=self.htk_compat, use_log_fbank=self.use_log_fbank, use_power=self.use_power)
+
+
+class Fbank(object):
+    """The front-end of one configuration on one device.  Building it builds the plan: a configuration outside the kernel's range (a padded
+    frame other than 256 / 512 / 1024 samples, more than 128 mel bins, round_to_power_of_two=false) raises RuntimeError here."""
+
+    def __init__(self, config, device):
+        self.config = config
+        self.device = torch.device(device)
+        self.plan = ops.FbankPlan(config.c_opts())
+        self.feat_dim = self.plan.feat_dim
+
+    def num_frames(self, num_samples):
+        return self.plan.num_frames(num_samples)
+
+    def __call__(self, waves, lengths=None, mean=None, scale=None, seed=0, utt_offset=0):
+        """waves: a list of 1-D waveforms (int16 or float arrays / tensors on Kaldi's scale: int16 range), or a padded (B, Nmax) batch with
+        `lengths`.  mean / scale: the (F) vectors of GlobalCMVN.mean_scale, applied by the same kernel.  Returns (feats (B, Tmax, F) float32
+        zero-padded, frames (B) int32) on the device: the loader's layout.  Dither is config.dither, keyed by (seed, b + utt_offset)."""
+        if lengths is None:
+            arrs = [w.cpu().numpy() if torch.is_tensor(w) else np.asarray(w) for w in waves]
+            if not arrs or any(a.ndim != 1 for a in arrs):
+                raise ValueError("Fbank: expected a non-empty list of 1-D waveforms")
+            lengths = [a.shape[0] for a in arrs]
+            batch = np.zeros((len(arrs), max(max(lengths), 1)), dtype=np.int16 if all(a.dtype == np.int16 for a in arrs) else np.float32)
+            for b, a in enumerate(arrs):
+                batch[b, :a.shape[0]] = a
+            waves = torch.from_numpy(batch)
+        elif not torch.is_tensor(waves):
+            waves = torch.from_numpy(np.ascontiguousarray(waves))
+        if waves.dtype not in (torch.int16, torch.float32):
+            waves = waves.to(torch.float32)
+        vec = lambda v: None if v is None else torch.as_tensor(v, dtype=torch.float32).to(self.device)
+        return ops.fbank(waves.to(self.device), lengths, self.plan, mean=vec(mean), scale=vec(scale), dither=self.config.dither, seed=seed,
+                         utt_offset=utt_offset)
+
+
+class GlobalCMVN(object):
+    """One global mean / variance normalisation: Kaldi's CMVN statistics matrix, (2, F + 1) doubles -- row 0 the sums and the frame count,
+    row 1 the sums of squares and 0 -- kept on `device`.  A CPU device serves loading, saving and mean_scale; accumulate needs the GPU."""
+
+    def __init__(self, feat_dim, device="cpu"):
+        self.feat_dim = int(feat_dim)
+        self.stats = torch.zeros((2, self.feat_dim + 1), dtype=torch.float64, device=device)
+
+    def accumulate(self, feats, frames):
+        ops.cmvn_accumulate(feats, frames, self.stats)
+        return self
+
+    def mean_scale(self, device=None):
+        """(mean, scale) float32: mean = sum / n, var = max(sumsq / n - mean^2, 1e-20), scale = 1 / sqrt(var) (apply-cmvn --norm-vars=true),
+        computed in double and rounded once.  numpy arrays, or tensors on `device`."""
+        s = self.stats.cpu().numpy()
+        n = s[0, -1]
+        if not n > 0:
+            raise ValueError("GlobalCMVN: no frames accumulated")
+        mean = s[0, :-1] / n
+        var = np.maximum(s[1, :-1] / n - mean * mean, 1e-20)
+        mean, scale = mean.astype(np.float32), (1.0 / np.sqrt(var)).astype(np.float32)
+        if device is None:
+            return mean, scale
+        return torch.from_numpy(mean).to(device), torch.from_numpy(scale).to(device)
+
+    def save_kaldi_text(self, path):
+        """The text form of `compute-cmvn-stats --binary=false`: ` [`, one indented row per line, `]`.  Values carry 17 significant digits
+        (Kaldi's own writer keeps fewer; its reader takes either)."""
+        s = self.stats.cpu().numpy()
+        with open(path, "w") as f:
+            f.write(" [")
+            for row in s:
+                f.write("\n  " + "".join("%.17g " % v for v in row))
+            f.write("]\n")
+
+    @classmethod
+    def load_kaldi_text(cls, path, device="cpu"):
+        """Reads save_kaldi_text's layout, and the same matrix behind an archive key (`global [ ...`)."""
+        text = open(path).read()
+        lo, hi = text.find("["), text.rfind("]")
+        if lo < 0 or hi < lo:
+            raise ValueError("%s: not a Kaldi text matrix" % path)
+        rows = [[float(v) for v in line.split()] for line in text[lo + 1:hi].strip().splitlines() if line.strip()]
+        if len(rows) != 2 or len(rows[0]) != len(rows[1]) or len(rows[0]) < 2:
+            raise ValueError("%s: expected a 2 x (F + 1) CMVN statistics matrix" % path)
+        out = cls(len(rows[0]) - 1, device)
+        out.stats.copy_(torch.tensor(rows, dtype=torch.float64))
+        return out
+
+
+def _riff(path, data):
+    if data[8:12] != b"WAVE":
+        raise NotImplementedError("%s: RIFF file of type %r, not WAVE" % (path, data[8:12]))
+    pos, fmt = 12, None
+    while pos + 8 <= len(data):
+        tag, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
+        body = data[pos + 8:pos + 8 + size]
+        if tag == b"fmt ":
+            fmt = struct.unpack("<HHIIHH", body[:16])
+            if fmt[0] == 0xFFFE and len(body) >= 26:                   # WAVE_FORMAT_EXTENSIBLE: the real tag opens the sub-format
+                fmt = (struct.unpack("<H", body[24:26])[0],) + fmt[1:]
+        elif tag == b"data":
+            if fmt is None:
+                raise ValueError("%s: data chunk before fmt chunk" % path)
+            code, channels, rate, _, _, bits = fmt
+            if code != 1 or bits != 16 or channels != 1:
+                raise NotImplementedError("%s: WAVE format tag %d, %d bit, %d channel(s); only PCM (1), 16 bit, mono is read" % (path, code, bits, channels))
+            return np.frombuffer(body[:len(body) // 2 * 2], dtype="<i2").astype(np.int16), rate
+        pos += 8 + size + (size & 1)
+    raise ValueError("%s: no data chunk" % path)
+
+
+def _sphere(path, data):
+    try:
+        head_bytes = int(data[8:16].split()[0])
+    except (ValueError, IndexError):
+        raise ValueError("%s: malformed SPHERE header" % path)
+    fields = {}
+    for line in data[16:head_bytes].decode("latin-1").splitlines():
+        parts = line.split(None, 2)
+        if parts and parts[0] == "end_head":
+            break
+        if len(parts) == 3:
+            fields[parts[0]] = parts[2].strip()
+    coding = fields.get("sample_coding", "pcm")
+    channels, nbytes = int(fields.get("channel_count", 1)), int(fields.get("sample_n_bytes", 2))
+    if coding != "pcm" or channels != 1 or nbytes != 2:
+        raise NotImplementedError("%s: SPHERE sample_coding %r, %d byte(s) per sample, %d channel(s); only uncompressed pcm, 2 bytes, mono is read"
+                                  % (path, coding, nbytes, channels))
+    order = fields.get("sample_byte_format", "01")
+    if order not in ("01", "10"):
+        raise NotImplementedError("%s: SPHERE sample_byte_format %r" % (path, order))
+    body = data[head_bytes:]
+    if "sample_count" in fields:
+        body = body[:2 * int(fields["sample_count"])]
+    return np.frombuffer(body[:len(body) // 2 * 2], dtype="<i2" if order == "01" else ">i2").astype(np.int16), int(fields["sample_rate"])
+
+
+def read_wave(path):
+    """(int16 samples, sample rate) of a RIFF WAVE file (PCM, 16 bit, mono) or an uncompressed NIST SPHERE file such as TIMIT's (the 1024-byte
+    text header, sample_coding pcm, 2 bytes per sample, either byte order, one channel).  Anything else raises NotImplementedError naming
+    what the file holds."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:4] == b"RIFF":
+        return _riff(path, data)
+    if data[:7] == b"NIST_1A":
+        return _sphere(path, data)
+    raise NotImplementedError("%s: neither a RIFF nor a NIST SPHERE file (starts with %r)" % (path, data[:8]))

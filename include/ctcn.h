@@ -563,6 +563,59 @@ int ctcn_edit_ops(const int32_t *a, const int32_t *a_len, const int64_t *b, cons
 int ctcn_step_stats(const float *loss, const int32_t *dist, const int64_t *tgt_len, int B, const int32_t *status, double *out4, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Filterbank front-end (fbank.hip): waveform -> log-mel features with one global mean / variance normalisation; replaces the three Kaldi
+ * binaries of timit/steps/make_feat.sh (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true).
+ * The computation is Kaldi's, as its feature-window, feature-fbank and mel-computations sources document it; option names and defaults are
+ * Kaldi's.  window_type: 0 hamming, 1 hanning, 2 povey (Kaldi's default), 3 rectangular, 4 blackman.  high_freq <= 0 is an offset from Nyquist.
+ * Not here: MFCC, VTLN, deltas, resampling.  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
+ * defaults). */
+typedef struct ctcn_fbank_opts {
+  float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff, blackman_coeff, low_freq, high_freq, energy_floor;
+  int32_t window_type, num_mel_bins, remove_dc_offset, round_to_power_of_two, snip_edges, use_energy, raw_energy, htk_compat, use_log_fbank,
+      use_power;
+} ctcn_fbank_opts;
+/* Frames of a signal of num_samples samples: snip_edges != 0: 0 if num_samples < frame_length, else 1 + (num_samples - frame_length) /
+ * frame_shift; snip_edges == 0: (num_samples + frame_shift / 2) / frame_shift.  Lengths in samples.  CTCN_EINVAL for a negative sample
+ * count, a frame length or shift that is not positive, or a count beyond int. */
+int ctcn_fbank_frames(long long num_samples, int frame_length, int frame_shift, int snip_edges);
+/* The plan of a configuration, built on the HOST into the caller's buffer (no HIP call) and uploaded by the caller once: 4-byte words,
+ * Npad = the frame length rounded up to a power of two,
+ *   [0, Npad)            float  the window (feature-window's formulas in double, rounded once), 0 from the frame length on
+ *   [Npad, 5 Npad)       float64 (cos, -sin)(2 pi k / Npad), k < Npad: the transform runs in float64 (a float32 one leaves ~1e-7 of the
+ *                               frame's RMS in every bin, 1e-4 .. 1e-3 of the log of the weakest filters)
+ *   [5 Npad, +128)       int32  first FFT bin of every mel filter; [+128, +256) its number of bins; [+256, +384) the offset of its weights
+ *   [5 Npad + 384, +Npad) float the triangular weights of mel-computations, filter after filter (every bin feeds at most two filters, so
+ *                               Npad words hold them); computed in double and rounded once -- Kaldi forms the same expressions in float32,
+ *                               whose mel scale carries ~1e-7 relative noise that the 34-mel filter spacing turns into ~1e-5 of a weight
+ * plan_bytes: the size of that block, 0 for options the kernel does not take.  Supported: round_to_power_of_two, Npad in {256, 512, 1024},
+ * 3 <= num_mel_bins <= 128; anything else CTCN_EUNSUPPORTED.  CTCN_EINVAL: NULL, frequencies outside (0, Nyquist], an empty filter (Kaldi's
+ * "num-mel-bins too large"), a buffer smaller than plan_bytes. */
+size_t ctcn_fbank_plan_bytes(const ctcn_fbank_opts *opts);
+int ctcn_fbank_plan(const ctcn_fbank_opts *opts, void *plan, size_t plan_bytes);
+/* wave (B, Nmax): float32 on Kaldi's scale (the int16 range, not +-1) or, with wave_is_int16, int16 converted on load (the same values give
+ * the same bits); lens (B) int32 samples, clamped to [0, Nmax]; opts on the host, plan = the block above in DEVICE memory; mean / scale: F
+ * device floats each or both NULL, F = num_mel_bins + (use_energy ? 1 : 0).
+ * feats (B, Tmax, F): rows below frames[b] hold the features -- per frame, in Kaldi's order: window extraction (snip_edges == 0 reflects the
+ * signal at both ends), dither, DC removal, raw log-energy, pre-emphasis, window, zero padding, real FFT, power (or magnitude) spectrum over
+ * bins 0 .. Npad/2 - 1, mel bank, log(max(e, FLT_EPSILON)), energy in column 0 (last column under htk_compat), then (x - mean) * scale as a
+ * float32 subtraction followed by a float32 multiplication; rows from frames[b] on are written as zeros.  frames (B) int32 = the frame
+ * count of the utterance, at most Tmax.  The rows of an utterance depend on its own samples alone, not on B, Nmax, Tmax or its neighbours.
+ * dither > 0 adds dither * N(0, 1) to every sample of every extracted window: Philox4x32-10 keyed by seed, counter (utterance index b +
+ * utt_offset, frame, sample pair), Box-Muller -- a function of those alone (not Kaldi's generator); b + utt_offset < 2^26, frames < 2^28.
+ * One wave per frame (Npad / 64 points per lane), four waves per workgroup sharing the staged samples of up to eight neighbouring frames;
+ * a half-length complex FFT in float64 (radix 8, 8, Npad / 128 through LDS) and a split step; everything else is float32. */
+int ctcn_fbank(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_fbank_opts *opts, const void *plan, const float *mean,
+               const float *scale, float *feats, int32_t *frames, int B, int Nmax, int Tmax, float dither, uint64_t seed, uint64_t utt_offset,
+               void *stream);
+/* stats (2, F + 1) DEVICE doubles, Kaldi's CMVN statistics matrix: row 0 the per-column sums with the frame count in the last column, row 1
+ * the sums of squares with 0 there.  ADDS the rows t < frames[b] (clamped to [0, Tmax]) of feats (B, Tmax, F) to it; nothing at or beyond
+ * frames[b] is read.  Every workgroup leaves float64 partial sums of its 64 rows in ws, one launch adds them up in index order: a function
+ * of the input bits, not of scheduling.  ws: ctcn_cmvn_accumulate_ws_bytes(B, Tmax, F) bytes, 8-byte aligned. */
+size_t ctcn_cmvn_accumulate_ws_bytes(int B, int Tmax, int F);
+int ctcn_cmvn_accumulate(const float *feats, const int32_t *frames, double *stats, int B, int Tmax, int F, void *ws, size_t ws_bytes,
+                         void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * CTC prefix beam search with bigram LM; replaces BeamDecoder.decode -> ctcBeamSearch.decode
  * (ctcDecoder.py:181-192; BeamSearch.py:73-153).  One workgroup per utterance.
  *   x (T,B,V) float32: log-probs (input_is_prob==0, exp taken on device) or probabilities exp(lp)

@@ -1,0 +1,103 @@
+"""Time of the filterbank front-end (ctcn_fbank) on a cfg2-like batch -- 32 utterances x 8 s of 16 kHz audio, the reference's shipped
+fbank.conf (hamming, 80 bins, energy: 81 dimensions) -- by HIP events, with and without the fused normalisation, and of
+ctcn_cmvn_accumulate on its output; beside it the float32 numpy restatement (tests/fbank_ref.py) on the host's threads.
+
+    python tools/fbank_bench.py [--reps 50] [--rounds 5] [--batch 32] [--seconds 8] [--cpu-threads 16]
+
+Per round, alternating: `--reps` back-to-back launches of each variant after a warm-up of all; prints one JSON line with the median and
+the spread of the per-call time over the rounds, the bytes the algorithm has to move (bytes(wave) + 4 F T B) and the rate that makes of
+the median, and the host figure (wall clock, one pass over the same batch, utterances dealt to a thread pool).  GPU only: no device, no
+number.  """
+import argparse
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import fbank_ref                                                   # noqa: E402
+from ctc_pytorch_amd import ops                                    # noqa: E402
+from ctc_pytorch_amd.utils import features                         # noqa: E402
+
+
+def timed(fn, reps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps                          # us per call
+
+
+def spread(xs):
+    return {"median": round(float(np.median(xs)), 2), "min": round(float(min(xs)), 2), "max": round(float(max(xs)), 2)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--seconds", type=float, default=8.0)
+    ap.add_argument("--cpu-threads", type=int, default=16)
+    ap.add_argument("--no-cpu", action="store_true")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "fbank_bench.py measures on the GPU only"
+    dev = torch.device("cuda:0")
+    kw = dict(window_type="hamming", num_mel_bins=80, use_energy=True, dither=0.0)
+    fb = features.Fbank(features.FbankConfig(**kw), dev)
+    B, N = args.batch, int(args.seconds * 16000)
+    rs = np.random.RandomState(0)
+    host = np.clip(np.round(3000.0 * rs.standard_normal((B, N))), -32768, 32767).astype(np.int16)
+    lens = [N - 160 * (b % 7) for b in range(B)]                   # ragged by a few frames, as a length-sorted batch is
+    w16 = torch.from_numpy(host).to(dev)
+    w32 = w16.to(torch.float32)
+    F, T = fb.feat_dim, fb.num_frames(N)
+    mean = torch.full((F,), 15.0, device=dev)
+    scale = torch.full((F,), 0.25, device=dev)
+    feats, frames = ops.fbank(w16, lens, fb.plan)
+    stats = torch.zeros((2, F + 1), dtype=torch.float64, device=dev)
+    fns = {
+        "fbank_int16": lambda: ops.fbank(w16, lens, fb.plan),
+        "fbank_int16_normalised": lambda: ops.fbank(w16, lens, fb.plan, mean=mean, scale=scale),
+        "fbank_float32": lambda: ops.fbank(w32, lens, fb.plan),
+        "cmvn_accumulate": lambda: ops.cmvn_accumulate(feats, frames, stats),
+    }
+    for fn in fns.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for k, fn in fns.items():
+            times[k].append(timed(fn, args.reps))
+    out = {"batch": B, "samples": N, "frames": T, "feat_dim": F, "reps": args.reps, "rounds": args.rounds,
+           "us_per_call": {k: spread(v) for k, v in times.items()}}
+    # what the algorithm has to move: the samples once, the features once (ops.fbank also uploads B lengths and allocates its outputs: part of the call)
+    algo = {"fbank_int16": 2 * B * N + 4 * F * T * B, "fbank_int16_normalised": 2 * B * N + 4 * F * T * B, "fbank_float32": 4 * B * N + 4 * F * T * B,
+            "cmvn_accumulate": 4 * F * T * B}
+    out["algorithmic_bytes"] = algo
+    out["algorithmic_GBps_at_median"] = {k: round(algo[k] / (out["us_per_call"][k]["median"] * 1e-6) / 1e9, 1) for k in algo}
+    if not args.no_cpu:
+        o = fbank_ref.options(**kw)
+        waves = [host[b, :lens[b]].astype(np.float32) for b in range(B)]
+        cpu = []
+        with ThreadPoolExecutor(max_workers=args.cpu_threads) as pool:
+            list(pool.map(lambda w: fbank_ref.fbank(w, o, np.float32), waves[:args.cpu_threads]))      # warm-up
+            for _ in range(3):
+                t0 = time.perf_counter()
+                list(pool.map(lambda w: fbank_ref.fbank(w, o, np.float32), waves))
+                cpu.append((time.perf_counter() - t0) * 1e6)
+        out["cpu_float32_restatement_us"] = dict(spread(cpu), threads=args.cpu_threads)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
