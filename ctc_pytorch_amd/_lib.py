@@ -36,6 +36,7 @@ _SIGS = {
     "ctcn_option_name": (ctypes.c_char_p, [I]),
     "ctcn_set_status_buffer": (I, [P]),
     "ctcn_gemm": (I, [I, I, I, I, I, P, I, P, I, P, I, F, I, P, Z, P]),
+    "ctcn_gemm_dx": (I, [I, I, I, P, I, P, I, P, I, F, I, P, Z, P]),
     "ctcn_transpose01": (I, [P, P, I, I, I, P]),
     "ctcn_copy_strided4": (I, [P, P, I, I, I, I, Z, Z, Z, Z, P]),
     "ctcn_relu_fwd": (I, [P, P, Z, P]),
@@ -110,6 +111,7 @@ _SIGS = {
     "ctcn_diag_squat": (I, [I, I, I, ctypes.c_uint, P]),
     "ctcn_diag_pipeline_chunks": (I, [I, I, I, I, I, I, I, I, ctypes.c_uint]),
     "ctcn_diag_gemm_plan": (I, [I] * 13 + [Z, ctypes.c_uint, I, I, I, I, P]),
+    "ctcn_diag_dx_plan": (I, [I, I, I, I, I, I, I, Z, I, P]),
     "ctcn_diag_gemm_on_xcds": (I, [I, I, I, I, I, P, I, P, I, P, I, F, I, P, Z, P, ctypes.c_uint]),
     "ctcn_rnn_last_kernel": (ctypes.c_char_p, [I]),
     "ctcn_levenshtein": (ctypes.c_longlong, [P, ctypes.c_longlong, P, ctypes.c_longlong]),

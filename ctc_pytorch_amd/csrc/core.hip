@@ -49,6 +49,7 @@ static int g_opt_fwd_pipe_min_input = 0;       // smallest layer input width who
 static int g_opt_conv_dbg = 0;          // development: conv_mfma_kernel skips phases (1 window load, 2 MFMA loop, 4 output phase); results invalid
 static int g_opt_rnn_rsv_nt = 0;        // rnn_bwd_scatter2: non-temporal hint on the reserve traffic (experiment: keep the exchange tiles in L2 at H = 512)
 static int g_opt_gemm_bf16_single = 0;  // 256-row GEMM tiles: one bf16 product (ah*bh) instead of the three bf16x3 products (north_star's bf16 tolerance; gemm.hip)
+static int g_opt_gemm_dx_wide = 1;      // ctcn_gemm_dx's 256 x 320 tile: 0 never, 1 by the rounds rule (gemm.hip: plan_dx), 2 wherever eligible (tests)
 static int g_opt_xcd_interleave = 1;    // which physical XCD hosts group g of a persistent recurrence that leaves XCDs idle (eight XCDs; 0: XCD g, 1 (default): the even XCDs first, 2-5: other orders; the host's xcd_allow masks follow: ops._idle_xcd_mask)
 static int g_opt_bn_rows4 = 1;          // BatchNorm over (T*B, C) rows: column sums with 16-B loads (colreduce_rows4_kernel); 0: the dword kernel (colreduce_rows_kernel); dense and length-aware calls alike
 static int g_opt_tn_splits_force = 0;   // development (tools/gemm_tn_bench.py): split-K count of the TN tile, 0 = the rule of gemm.hip:plan_gemm
@@ -83,6 +84,7 @@ static const OptionRow k_options[] = {
   {"bn_rows4", &g_opt_bn_rows4, [](int value) -> int { return value ? 1 : 0; }},
   {"tn_splits_force", &g_opt_tn_splits_force, [](int value) -> int { return value < 0 ? 0 : value; }},
   {"gemm_bf16_single", &g_opt_gemm_bf16_single, [](int value) -> int { return value ? 1 : 0; }},
+  {"gemm_dx_wide", &g_opt_gemm_dx_wide, [](int value) -> int { return value < 0 ? 0 : (value > 2 ? 2 : value); }},
   {"beam_generic_threads", &g_opt_beam_generic_threads, [](int value) -> int { return (value == 256 || value == 512 || value == 1024) ? value : 0; }},
   {"beam_cand_global", &g_opt_beam_cand_global, [](int value) -> int { return value ? 1 : 0; }},
   {"beam_bitonic", &g_opt_beam_bitonic, [](int value) -> int { return value ? 1 : 0; }},

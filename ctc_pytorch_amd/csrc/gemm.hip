@@ -1164,6 +1164,245 @@ __global__ __launch_bounds__(512) void gemm_planes_nt256pp_af32_kernel(int M, in
     }
 }
 
+// The float32-A tile at 256 x 320, for the dx product of a 320-unit bidirectional layer (N = 640 = 2 x 320: 200 tiles, one round on 256 CUs,
+// where the 256 x 128 tile above takes 500 tiles in two rounds and its 12-MFMA multiply phases cannot cover the other half's read phase).
+// The schedule, the A staging and the LDS image of gemm_planes_nt256pp_af32_kernel, a kernel of its own so that that one's code stays as it is:
+//   * the eight waves as 4 (M) x 2 (N): a wave owns 64 x 160 outputs = 2 x 5 MFMA tiles (160 accumulator registers); per 16-k half-stage
+//     4 + 10 ds_read_b128 feed 30 MFMAs.  Waves 0-3 hold rows 0-127 and waves 4-7 rows 128-255: the ping-pong halves, one of each per SIMD;
+//   * a stage is A hi / lo 2 x 16 KB + B hi / lo 2 x 20 KB = 72 KB, two buffers 144 KB;
+//   * B by DMA: 2 planes x 20 sixteen-row pieces of 1 KB per stage, five per wave -- piece n of wave w is number 8 n + w: plane w & 1,
+//     rows 16 (4 n + (w >> 1)) onwards.  N % 320 == 0 (the host's condition): no row of B is clamped.
+// Per accumulator and 16-k step the products al*bh, ah*bl, ah*bh in that order, on the split_bf16 planes, k ascending: bit-identical to the
+// other plane tiles.  bf16x3 only (option "gemm_bf16_single" keeps the 256 x 128 tile).
+// gfx950, hipcc -O3 (-Rpass-analysis=kernel-resource-usage): 256 VGPRs of the unified file (160 of them accumulators, no AGPRs), 50 SGPRs, no
+// scratch, 147 456 B of dynamic LDS.  Every register is taken: the B pieces are issued by hand from a scalar base and the epilogue recomputes
+// its lane number for that reason (each cost 1-3 spilled registers otherwise); check the remark after any edit.
+__global__ __launch_bounds__(512) void gemm_af32_n320pp_kernel(int M, int N, int K, int Kp, const float *__restrict__ A, int lda,
+                                                               const unsigned short *__restrict__ Bh, const unsigned short *__restrict__ Bl,
+                                                               float *__restrict__ C, int ldc, float beta, int tiles_m, int tiles_n) {
+  constexpr int TBM = 256, TBN = 320, WI = 2, WJ = 5;
+  constexpr int A_BYTES = TBM * 64, B_BYTES = TBN * 64;
+  constexpr int STAGE = 2 * A_BYTES + 2 * B_BYTES;
+  constexpr int NBP = 2 * TBN / 16 / 8;                        // DMA pieces of B per wave and stage: 5
+  extern __shared__ __attribute__((aligned(16))) unsigned char qsm[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int bid = xcd_band_tile(blockIdx.x, tiles_m * tiles_n);
+  const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
+  const int m0 = tm * TBM, n0 = tn * TBN;
+
+  f32x16 acc[WI][WJ];
+#pragma unroll
+  for (int i = 0; i < WI; ++i)
+#pragma unroll
+    for (int j = 0; j < WJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+
+  // DMA source of this lane in the wave's first piece: LDS position lane -> row lane >> 2 of the piece, swizzled chunk (the piece's first row is
+  // a multiple of 16: the swizzle term is the lane's own); the wave's further pieces lie 64 rows apart
+  const unsigned short *const bplane = (wave & 1) ? Bl : Bh;
+  const int bdst = 2 * A_BYTES + (wave & 1) * B_BYTES + (wave >> 1) * 1024;
+  const unsigned offB = ((unsigned)(n0 + (wave >> 1) * 16 + (lane >> 2)) * (unsigned)Kp + (unsigned)(((lane & 3) ^ ((lane >> 4) & 3)) * 8)) * 2u;   // bytes
+  typedef __attribute__((address_space(3))) unsigned char *lds_u8_t;
+  auto issue_b_piece = [&](int n, int k0, int buf) {            // n = 0 .. NBP-1
+    // issued by hand: the piece's base in a scalar pair + the lane's 32-bit offset, the LDS address in M0, written in the statement that reads
+    // it (the kernel has no other user of M0).  The builtin on a pointer forms per-lane 64-bit addresses that advance with k0: four more
+    // registers than the kernel has.  The waits for the pieces are the kernel's own (WAIT_A, the vmcnt in front of the third barrier)
+    const unsigned short *sbase = bplane + (size_t)n * 64 * Kp + k0;
+    const unsigned dst = (unsigned)(uintptr_t)(lds_u8_t)(qsm + buf * STAGE + bdst + n * 4096);
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(dst), "v"(offB), "s"(sbase) : "memory");
+  };
+  // A staging: as in gemm_planes_nt256pp_af32_kernel (the comments there) -- the 16-B bf16 chunk `ach` of rows arow0 and 128 + arow0 of the tile
+  const int arow0 = tid >> 2, ach = tid & 3;
+  u32x4 aw[4];
+  const float *atile = A + (size_t)m0 * lda;
+  const unsigned arel[2] = {(unsigned)min(arow0, M - 1 - m0) * (unsigned)lda, (unsigned)min(128 + arow0, M - 1 - m0) * (unsigned)lda};
+  auto load_a_piece = [&](int q, int k0) {                     // q = 2 * row + half
+    const int c = 8 * ach + 4 * (q & 1);
+    const bool whole = k0 + 32 <= K;
+    const float *sbase = atile + (whole ? k0 : 0);
+    const unsigned voff = (arel[q >> 1] + (unsigned)(whole ? c : min(k0 + c, K - 4))) * 4u;
+    asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(aw[q]) : "v"(voff), "s"(sbase) : "memory");
+  };
+  auto split_pair = [](float a, float b, unsigned &hw, unsigned &lw) {
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    hw = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
+    const f32x2_t r = {a - __uint_as_float(hw << 16), b - __uint_as_float(hw & 0xffff0000u)};
+    lw = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_t));
+  };
+  auto convert_half = [&](int r, int h, int k0) {
+    u32x4 w = aw[2 * r + h];
+    if (k0 + 32 > K && k0 + 8 * ach + 4 * h >= K) w = (u32x4){0u, 0u, 0u, 0u};          // (K % 4 == 0: a 16-B piece is inside or outside as a whole)
+    unsigned h0, l0, h1, l1;
+    split_pair(__uint_as_float(w[0]), __uint_as_float(w[1]), h0, l0);
+    split_pair(__uint_as_float(w[2]), __uint_as_float(w[3]), h1, l1);
+    aw[2 * r + h] = (u32x4){h0, h1, l0, l1};
+  };
+  auto store_a_row = [&](int r, int buf) {
+    unsigned char *sb = qsm + buf * STAGE + qswz(arow0 + 128 * r, ach);
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      *reinterpret_cast<u32x2 *>(sb + 8 * h) = (u32x2){aw[2 * r + h][0], aw[2 * r + h][1]};
+      *reinterpret_cast<u32x2 *>(sb + A_BYTES + 8 * h) = (u32x2){aw[2 * r + h][2], aw[2 * r + h][3]};
+    }
+  };
+  const int nst = Kp / 32;
+  const int ml = lane & 31, g = lane >> 5;
+  bf16x8_t ah[WI], al[WI], bh[WJ], bl[WJ];
+  // LDS offsets of this lane's fragments per 16-k half: the first MFMA tile's; the others lie 32 rows = 2 KB further each (the wave's first
+  // row and 32 j are multiples of 16 rows, so the swizzle term is the lane's own)
+  int oa[2], ob[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    oa[ks] = qswz(wm * 64 + ml, ks * 2 + g);
+    ob[ks] = 2 * A_BYTES + qswz(wn * 160 + ml, ks * 2 + g);
+  }
+  auto load_frags = [&](int stage, int ks) {
+    const unsigned char *sb = qsm + (stage & 1) * STAGE;
+#pragma unroll
+    for (int j = 0; j < WJ; ++j) {
+      bh[j] = *reinterpret_cast<const bf16x8_t *>(sb + ob[ks] + j * 2048);
+      bl[j] = *reinterpret_cast<const bf16x8_t *>(sb + B_BYTES + ob[ks] + j * 2048);
+    }
+#pragma unroll
+    for (int i = 0; i < WI; ++i) {
+      ah[i] = *reinterpret_cast<const bf16x8_t *>(sb + oa[ks] + i * 2048);
+      al[i] = *reinterpret_cast<const bf16x8_t *>(sb + A_BYTES + oa[ks] + i * 2048);
+    }
+  };
+  constexpr int NMM = WI * WJ;
+  // One multiply phase: 30 MFMAs, the wave's other work of the stage one item behind an MFMA (WHICH, HAS1, HAS2 and the loads in flight: as in
+  // gemm_planes_nt256pp_af32_kernel, with five DMA pieces)
+  auto multiply = [&](auto which, auto has1, auto has2, int s) {
+    constexpr int WHICH = decltype(which)::value;
+    constexpr bool HAS1 = decltype(has1)::value, HAS2 = decltype(has2)::value;
+    constexpr int CV0 = 3 * NMM - 3;
+    static_assert(NBP <= CV0, "DMA slots and split slots of a multiply phase overlap");
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int i = 0; i < WI; ++i)
+#pragma unroll
+        for (int j = 0; j < WJ; ++j) {
+          if (t == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);   // small terms first
+          else if (t == 1) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+          else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+          const int n = t * NMM + i * WJ + j;
+          if (n < NBP || n == CV0 || n == CV0 + 1) {
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (WHICH == 1) {
+              if (HAS1 && n < NBP) issue_b_piece(n, (s + 1) * 32, (s + 1) & 1);
+              if (HAS1 && n == CV0) {          // A(s+1) row 1 has landed: what may stay in flight is A(s+2) row 0 (2 loads, HAS2) + this phase's 5 pieces
+                static_assert(NBP == 5, "vmcnt literals");
+                if constexpr (HAS2) WAIT_A(7, 1); else WAIT_A(5, 1);
+              }
+              if (HAS1 && n >= CV0) convert_half(1, n - CV0, (s + 1) * 32);
+            } else {
+              if (HAS2 && n == CV0) WAIT_A(2, 0);
+              if (HAS2 && n >= CV0) convert_half(0, n - CV0, (s + 2) * 32);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+  };
+  constexpr std::integral_constant<int, 1> first{};
+  constexpr std::integral_constant<int, 2> second{};
+  constexpr std::integral_constant<bool, true> yes{};
+  constexpr std::integral_constant<bool, false> no{};
+  // prologue: stage 0 into buffer 0 (A through the registers, B by DMA), all of A(1) into the registers
+#pragma unroll
+  for (int q = 0; q < 4; ++q) aw[q] = (u32x4){0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) load_a_piece(q, 0);
+#pragma unroll
+  for (int n = 0; n < NBP; ++n) issue_b_piece(n, 0, 0);
+  WAIT_A(0, 0); WAIT_A(0, 1);
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    convert_half(r, 0, 0); convert_half(r, 1, 0);
+    store_a_row(r, 0);
+  }
+  if (nst > 1) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // (the ds_writes have read aw)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) load_a_piece(q, 32);
+    WAIT_A(2, 0);
+    convert_half(0, 0, 32); convert_half(0, 1, 32);           // row 0 of A(1): the first read phase stores it; row 1 is split in the first multiply
+  }
+  pp_barrier_vm();
+  if (wave >= 4) pp_barrier();                                // half B runs one barrier behind
+#ifdef CTCN_GEMM_STATS
+  long long gs_work[4] = {0, 0, 0, 0}, gs_wait[4] = {0, 0, 0, 0};
+  const long long gs_t0 = clock64();
+  long long gs_prev = gs_t0;
+#endif
+  auto stage = [&](int s, auto has1, auto has2) {
+    constexpr bool HAS1 = decltype(has1)::value, HAS2 = decltype(has2)::value;
+    load_frags(s, 0);
+    if constexpr (HAS1) store_a_row(0, (s + 1) & 1);
+    if constexpr (HAS2) {
+      __builtin_amdgcn_sched_barrier(0);
+      load_a_piece(0, (s + 2) * 32); load_a_piece(1, (s + 2) * 32);
+    }
+    PPB(0);
+    multiply(first, has1, has2, s);
+    PPB(1);
+    load_frags(s, 1);
+    if constexpr (HAS1) store_a_row(1, (s + 1) & 1);
+    if constexpr (HAS2) {
+      __builtin_amdgcn_sched_barrier(0);
+      load_a_piece(2, (s + 2) * 32); load_a_piece(3, (s + 2) * 32);
+    }
+    // this wave's DMA pieces of B(s+1) have landed (and A(s+2) row 0, older; the two loads of row 1, just issued, stay in flight)
+#ifdef CTCN_GEMM_STATS
+    PPB_VM(2);
+#else
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (HAS2) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+    multiply(second, has1, has2, s);
+    PPB(3);
+  };
+  int s = 0;
+  for (; s + 2 < nst; ++s) stage(s, yes, yes);
+#ifdef CTCN_GEMM_STATS
+  if (lane == 0 && (wave & 3) == 0 && (blockIdx.x == 0 || blockIdx.x == 1000) && g_gemm_stats) {
+    long long *o = g_gemm_stats + ((blockIdx.x ? 2 : 0) + (wave >> 2)) * 16;
+    for (int i = 0; i < 4; ++i) { o[i] = gs_work[i]; o[4 + i] = gs_wait[i]; }
+    o[8] = clock64() - gs_t0; o[9] = nst - 2; o[10] = 0;
+  }
+#endif
+  if (s + 1 < nst) { stage(s, yes, no); ++s; }
+  stage(s, no, no);
+  if (wave < 4) pp_barrier();
+  // (the lane number afresh, behind an asm the compiler cannot look through: computed in front of the main loop, the epilogue's row / column
+  // values stay in registers the loop has none to spare for -- three of them were spilled)
+  int zero = 0;
+  asm volatile("" : "+v"(zero));
+  const int elane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero));
+#pragma unroll
+  for (int i = 0; i < WI; ++i)
+#pragma unroll
+    for (int j = 0; j < WJ; ++j) {
+      const int col = n0 + wn * 160 + j * 32 + (elane & 31);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = m0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (elane >> 5);
+        if (row < M) {
+          float v = acc[i][j][e];
+          float *p = C + (size_t)row * ldc + col;
+          if (beta != 0.0f) v += beta * *p;
+          *p = v;
+        }
+      }
+    }
+}
+
 
 // ------------------------------------------------------------------------------------------------
 // TN tile: C = A^T B for two CONTRACTION-MAJOR float32 operands (A: K x M, B: K x N, k the slow index) -- the weight gradients
@@ -1867,6 +2106,54 @@ extern "C" int ctcn_gemm(int transA, int transB, int M, int N, int K, const floa
                          int ldb, float *C, int ldc, float beta, int precision, void *ws, size_t ws_bytes,
                          void *stream) {
   return gemm_core(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, beta, precision, ws, ws_bytes, stream, 0u, nullptr, 0);
+}
+
+// ---- the dx product: C = A B, A row-major float32 (M x K), B row-major K x N -------------------------------------------------------------
+// ctcn_gemm(0, 0, ...) with one more tile to choose from: gemm_af32_n320pp_kernel (256 x 320) where N is a multiple of 320 and the tile count
+// says it wins.  A planner of its own: plan_gemm's answers stay what they are for every caller.  Same bits either way.
+// DX_WIDE_COST: time of one round of 256 x 320 tiles over one round of 256 x 128 float32-A tiles at N = 640, K = 2 560 on an MI355X: 216 us
+// (200 tiles, M = 25 600) against 115.5 us (250 tiles, M = 12 800) -- tools/mb_gemm_pp.hip modes 4 and 1, profiles/dx_tile_ab.txt.
+constexpr double DX_WIDE_COST = 1.87;
+struct DxPlan { bool eligible, wide; int tiles_wide, tiles_128; };
+static DxPlan plan_dx(int M, int N, int K, int lda, int precision, int a_mod16, bool has_ws, size_t ws_bytes, int cus, int opt_wide, bool single) {
+  DxPlan p = {};
+  p.tiles_128 = ceil_div(M, 256) * ceil_div(N, 128);
+  p.eligible = precision == 1 && !single && N % 320 == 0 && K >= 64 && K % 4 == 0 && lda % 4 == 0 && a_mod16 == 0 && has_ws &&
+               ws_bytes >= plane_layout(0, N, K).bytes;
+  if (!p.eligible) return p;
+  p.tiles_wide = ceil_div(M, 256) * (N / 320);
+  // by rounds of one tile per CU: the wide tile where its rounds, each DX_WIDE_COST times as long, take less time than the 256 x 128 tile's
+  const int c = std::max(cus, 1);
+  p.wide = opt_wide == 2 || (opt_wide == 1 && ceil_div(p.tiles_wide, c) * DX_WIDE_COST < (double)ceil_div(p.tiles_128, c));
+  return p;
+}
+extern "C" int ctcn_diag_dx_plan(int M, int N, int K, int lda, int precision, int a_mod16, int has_ws, size_t ws_bytes, int cus, int *out) {
+  CTCN_REQUIRE(out && M > 0 && N > 0 && K >= 0 && cus > 0 && a_mod16 >= 0 && a_mod16 < 16, "ctcn_diag_dx_plan: bad args");
+  const DxPlan p = plan_dx(M, N, K, lda, precision, a_mod16, has_ws != 0, ws_bytes, cus, ctcn_get_option("gemm_dx_wide"), bf16_single());
+  const int v[CTCN_DX_PLAN_INTS] = {p.eligible, p.wide, p.tiles_wide, p.tiles_128};
+  memcpy(out, v, sizeof(v));
+  return CTCN_OK;
+}
+extern "C" int ctcn_gemm_dx(int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc, float beta, int precision, void *ws,
+                            size_t ws_bytes, void *stream) {
+  const GemmShape g = {0, 0, M, N, K, lda, ldb, ldc, precision, 0};
+  if (const int rc = check_gemm_shape(g)) return rc;
+  CTCN_REQUIRE(A && B && C, "ctcn_gemm_dx: null pointer");
+  CTCN_REQUIRE(!ws || (uintptr_t)ws % 16 == 0, "ctcn_gemm_dx: the workspace must be 16-byte aligned");
+  const DxPlan p = plan_dx(M, N, K, lda, precision, (int)((uintptr_t)A & 15), ws != nullptr, ws_bytes, ctcn_device_cus(), ctcn_get_option("gemm_dx_wide"),
+                           bf16_single());
+  if (!p.wide) return gemm_core(0, 0, M, N, K, A, lda, B, ldb, C, ldc, beta, precision, ws, ws_bytes, stream, 0u, nullptr, 0);
+  hipStream_t st = (hipStream_t)stream;
+  const PlaneLayout lay = plane_layout(0, N, K);               // B's planes alone: Bh | Bl at the workspace's start
+  unsigned short *bh = (unsigned short *)ws, *bl = bh + lay.b_el;
+  launch_split(SP_TRANSPOSE, st, B, ldb, N, K, lay.Kp, bh, bl, 0, 0u, nullptr);
+  CTCN_LAUNCH_CHECK();
+  const size_t lds = (size_t)2 * (2 * 256 * 64 + 2 * 320 * 64);
+  CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_af32_n320pp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(gemm_af32_n320pp_kernel, dim3(p.tiles_wide), dim3(512), lds, st, M, N, K, lay.Kp, A, lda, (const unsigned short *)bh,
+                     (const unsigned short *)bl, C, ldc, beta, ceil_div(M, 256), N / 320);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
 }
 
 // the same transposition of two equally shaped tensors in ONE launch (W_hh of the two directions before a backward recurrence)

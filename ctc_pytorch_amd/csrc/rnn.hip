@@ -2925,7 +2925,9 @@ static int rnn_bwd_gemms(int cell, int T, int B, int I, int H, int dirs, const f
     StackedWih s;
     if (int rc = stack_w_ih(w_ih0, w_ih1, GH, I, ws, ws_bytes, (hipStream_t)stream, s)) return rc;
     if (s.w) {
-      if (int rc = ctcn_gemm_on_xcds(0, 0, TB, I, 2 * GH, gates, 2 * GH, s.w, I, dx, I, 0.0f, precision, s.ws, s.ws_bytes, stream, xcd_allow)) return rc;
+      // (main stream: ctcn_gemm_dx, which has a 256 x 320 tile for I = 640 -- one round of 200 tiles at cfg2 instead of two of 250; same bits)
+      if (int rc = xcd_allow ? ctcn_gemm_on_xcds(0, 0, TB, I, 2 * GH, gates, 2 * GH, s.w, I, dx, I, 0.0f, precision, s.ws, s.ws_bytes, stream, xcd_allow)
+                             : ctcn_gemm_dx(TB, I, 2 * GH, gates, 2 * GH, s.w, I, dx, I, 0.0f, precision, s.ws, s.ws_bytes, stream)) return rc;
       dx_done = true;
     }
   }

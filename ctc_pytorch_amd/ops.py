@@ -479,6 +479,15 @@ def gemm(transA, transB, M, N, K, A, lda, Bm, ldb, C, ldc, beta=0.0, xcd_allow=0
     return C
 
 
+def gemm_dx(M, N, K, A, lda, Bm, ldb, C, ldc, beta=0.0):
+    """C = A B for a row-major A (M x K) and a row-major B (K x N) through ctcn_gemm_dx, the entry of a recurrent layer's dx product (tests)."""
+    _need_gpu(A, Bm, C)
+    w, wp, wn = _ws(C)
+    _lib.check(_lib.lib().ctcn_gemm_dx(M, N, K, _ptr(A), lda, _ptr(Bm), ldb, _ptr(C), ldc, float(beta), get_precision(), wp, wn, _lib.stream_ptr()),
+               "gemm_dx")
+    return C
+
+
 class _Linear(torch.autograd.Function):
     """y = x @ W^T, W (N,K), no bias  (nn.Linear(bias=False), model_ctc.py:137,166)."""
 

@@ -109,6 +109,8 @@ int ctcn_device_xcds(void);
  * full-size cfg2 / cfg3 / cfg4 loss within 1e-5 .. 3e-5 of the REFERENCE's, gradient norms within 6e-4 .. 4e-3, log-probs 2-3e-3 mean (1.8e-2 max)
  * next to the default mode's (test_bf16_single_mode_against_reference_checksums).  Tile time 1.27-1.84x shorter; cfg2 13.21 -> 12.69 ms per
  * step, cfg3 7.71 -> 7.42, cfg4 52.6 -> 45.5.  The default (0) keeps every parity statement of this header (1e-5 against the reference).
+ * "gemm_dx_wide" = 1 (default): ctcn_gemm_dx takes its 256 x 320 float32-A tile (gemm_af32_n320pp_kernel) where the tile counts say it wins
+ * (the rule at ctcn_gemm_dx below); 0: never (ctcn_gemm_dx is ctcn_gemm(0, 0, ...)); 2: wherever the tile is eligible (tests).  0 and 1 give the same bits.
  * "beam_occ2" = 0 (default, round 5): 1 / 2 launch the fast beam search compiled for eight waves per SIMD (<= 64 VGPRs, 43 spilled dwords)
  * with <= 68 KB of dynamic LDS (4 096-slot trie; 2: LM in global memory, 8 192 slots) so that two utterances share a CU.  Same results;
  * measured SLOWER (cfg5, three searches in flight: 279 k -> 248 k utt/s peaky, 128 k -> 97 k flat; profiles/r05_beam_occ2_ab.txt) and kept
@@ -164,6 +166,17 @@ int ctcn_set_status_buffer(int *dev_word);
  * (hi*hi + hi*lo + lo*hi), f32 accumulate: ~2^-16 relative operand error instead of bf16's 2^-8. */
 int ctcn_gemm(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B, int ldb,
               float *C, int ldc, float beta, int precision, void *ws, size_t ws_bytes, void *stream);
+
+/* ctcn_gemm_dx: C[M,N] = A[M,K] * B[K,N] + beta*C for a row-major float32 A (k contiguous) and a row-major K x N B: ctcn_gemm(0, 0, ...)
+ * with one more tile, 256 x 320, for the dx product of a recurrent layer (dx = da W_ih: N = the layer's input width).  The tile is eligible
+ * with precision 1, option "gemm_bf16_single" off, N % 320 == 0, K >= 64, K % 4 == 0, lda % 4 == 0, A 16-byte aligned and a workspace that
+ * holds B's bf16 planes; it is taken when ceil(tiles_wide / CUs) * r < ceil(tiles_128 / CUs), tiles_wide = ceil(M / 256) * N / 320,
+ * tiles_128 = ceil(M / 256) * ceil(N / 128), r = the measured cost of a wide tile in 256 x 128 tiles (1 < r < 2): fewer rounds of one tile
+ * per CU.  Every other call is ctcn_gemm(0, 0, ...) itself.  Where the rule takes the tile ctcn_gemm runs a 256-row tile (more than one
+ * tile per CU), which adds the same products in the same k order: bit-identical results.  (Forced by option "gemm_dx_wide" = 2 onto a
+ * product small enough for ctcn_gemm to split over K, the tile differs from it by the order of the partial sums.) */
+int ctcn_gemm_dx(int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc, float beta, int precision, void *ws,
+                 size_t ws_bytes, void *stream);
 
 /* out[b,a,c] = in[a,b,c]  (x.transpose(0,1), model_ctc.py:175) */
 int ctcn_transpose01(const float *in, float *out, int A, int B, int C, void *stream);
@@ -669,6 +682,11 @@ int ctcn_diag_gemm_plan(int transA, int transB, int M, int N, int K, int lda, in
                         int b_mod16, int has_ws, size_t ws_bytes, unsigned xcd_allow, int same_a, int same_b, int cus, int xcds, int *out);
 int ctcn_diag_gemm_on_xcds(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc,
                            float beta, int precision, void *ws, size_t ws_bytes, void *stream, unsigned xcd_allow);
+/* ctcn_diag_dx_plan: what ctcn_gemm_dx would do on a device of `cus` CUs under the current options, given A modulo 16 bytes and the
+ * workspace's size: out[CTCN_DX_PLAN_INTS] = eligible for the 256 x 320 tile, takes it, tiles_wide (0 when not eligible), tiles_128.
+ * Pure arithmetic, no device needed. */
+#define CTCN_DX_PLAN_INTS 4
+int ctcn_diag_dx_plan(int M, int N, int K, int lda, int precision, int a_mod16, int has_ws, size_t ws_bytes, int cus, int *out);
 const char *ctcn_rnn_last_kernel(int which);
 
 /* ---- host end of the decoders (hostjoin.hip; no kernel, no HIP call: works without a GPU) -------------------------------------------------

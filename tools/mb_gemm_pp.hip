@@ -1,7 +1,10 @@
-// tools/mb_gemm_pp.hip -- phase accounting of the 256 x 256 ping-pong plane tile (gemm_planes_nt256pp_kernel<2>): in-kernel clock64 sums of the
+// tools/mb_gemm_pp.hip -- phase accounting of the 256-row ping-pong tiles (gemm_planes_nt256pp_kernel<2> and the float32-A / TN forms: `mode`): in-kernel clock64 sums of the
 // cycles waves 0 (half A) and 4 (half B) spend working before each of the four barriers of a stage and waiting inside it (development aid).
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/mb_gemm_pp.bin tools/mb_gemm_pp.hip ctc_pytorch_amd/csrc/core.hip
+// -DMB_NO_STATS: the kernels as the library builds them (no clocks in the loop): times only, no phase table
+#ifndef MB_NO_STATS
 #define CTCN_GEMM_STATS 1
+#endif
 #include "../ctc_pytorch_amd/csrc/gemm.hip"
 #include <vector>
 extern "C" int ctcn_device_xcds(void) { return 8; }
@@ -18,11 +21,14 @@ int main(int argc, char **argv) {
     auto fill = [&](unsigned short *d, size_t n) { for (size_t i = 0; i < n; ++i) { x = x * 1664525u + 1013904223u; v[i] = (unsigned short)(((x >> 16) & 0x807f) | ((120 + ((x >> 8) & 7)) << 7)); } return hipMemcpy(d, v.data(), n * 2, hipMemcpyHostToDevice); };
     CK(fill(ah, (size_t)M * Kp)); CK(fill(al, (size_t)M * Kp)); CK(fill(bh, (size_t)N * Kp)); CK(fill(bl, (size_t)N * Kp));
   }
+#ifdef CTCN_GEMM_STATS
   CK(hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_stats), &stats, sizeof(stats)));
+#endif
   hipStream_t st; CK(hipStreamCreate(&st));
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   const int tiles_m = (M + 255) / 256;
-  const int mode = argc > 4 ? atoi(argv[4]) : 0;        // 0: plane tile <2>; 1: float32-A tile <1>; 2: float32-A tile <2>; 3: TN tile <2> (M, N = the output, Kp = the contraction)
+  const int mode = argc > 4 ? atoi(argv[4]) : 0;        // 0: plane tile <2>; 1: float32-A tile <1>; 2: float32-A tile <2>; 3: TN tile <2> (M, N = the output, Kp = the contraction); 4: float32-A 256 x 320 tile (N % 320 == 0)
+  const int reps = argc > 5 ? atoi(argv[5]) : 1;        // timed launches, each printed (after two warm-up launches)
   float *Af = nullptr;
   if (mode) {
     CK(hipMalloc(&Af, (size_t)M * Kp * 4));
@@ -43,10 +49,11 @@ int main(int argc, char **argv) {
   for (int dbg : {0, 1}) {
     if (mode && dbg) break;
     const int wnt = mode == 1 ? 1 : 2;
-    const int tiles_nn = (N + 128 * wnt - 1) / (128 * wnt);
-    const size_t ldsb = (size_t)2 * (2 * 256 * 64 + 2 * 128 * wnt * 64);
-    for (int it = 0; it < 3; ++it) {
-      if (it == 2) CK(hipEventRecord(e0, st));
+    const int tiles_nn = mode == 4 ? N / 320 : (N + 128 * wnt - 1) / (128 * wnt);
+    const size_t ldsb = mode == 4 ? (size_t)2 * (2 * 256 * 64 + 2 * 320 * 64) : (size_t)2 * (2 * 256 * 64 + 2 * 128 * wnt * 64);
+    if (mode == 4 && N % 320) { printf("mode 4 needs N %% 320 == 0\n"); return 1; }
+    for (int it = 0; it < 2 + reps; ++it) {
+      if (it >= 2) CK(hipEventRecord(e0, st));
       if (mode == 3) {
         auto kern = gemm_tn_f32_pp_kernel<2>;
         CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
@@ -61,10 +68,19 @@ int main(int argc, char **argv) {
         auto kern = gemm_planes_nt256pp_af32_kernel<1>;
         CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
         hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_nn), dim3(512), ldsb, st, M, N, Kp, Kp, (const float *)Af, Kp, bh, bl, C, N, 0.0f, tiles_m, tiles_nn);
+      } else if (mode == 4) {
+        auto kern = gemm_af32_n320pp_kernel;
+        CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
+        hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_nn), dim3(512), ldsb, st, M, N, Kp, Kp, (const float *)Af, Kp, bh, bl, C, N, 0.0f, tiles_m, tiles_nn);
       } else {
         auto kern = gemm_planes_nt256pp_af32_kernel<2>;
         CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb));
         hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_nn), dim3(512), ldsb, st, M, N, Kp, Kp, (const float *)Af, Kp, bh, bl, C, N, 0.0f, tiles_m, tiles_nn);
+      }
+      if (it >= 2 && it + 1 < 2 + reps) {
+        CK(hipEventRecord(e1, st)); CK(hipStreamSynchronize(st));
+        float ms_; CK(hipEventElapsedTime(&ms_, e0, e1));
+        printf("mode %d M %d N %d Kp %d rep %d: %.1f us\n", mode, M, N, Kp, it - 2, ms_ * 1e3);
       }
     }
     CK(hipEventRecord(e1, st)); CK(hipStreamSynchronize(st));
