@@ -35,7 +35,6 @@ static int g_opt_gemm_tile256 = 1;      // 1: 256-row plane-GEMM tiles (global_l
 static int g_opt_gemm_dbg = 0;          // development: bit 0 = 256-tile GEMM skips its stores, bit 1 = skips its DMA loads (results invalid)
 static int g_opt_gemm_a_inline = 1;     // 1: 256-row tiles split a row-major float32 A operand while staging it (no plane pass over A)
 static int g_opt_conv_mfma = 1;         // 1: Conv2d forward / dgrad / wgrad as MFMA implicit GEMMs; 0: the direct kernels
-static int g_opt_rnn_mixed_slices = 0;  // forward recurrence: one workgroup per CU with mixed 12- / 4-unit slices (experiment)
 static int g_opt_rnn_fwd_tagged = 1;    // forward persistent recurrence: 1 = tagged gather (rnn_fwd_tagged) where it applies
 static int g_opt_rnn_fused_dropout = 1; // 1: ctcn_rnn_fwd_dropout stores the dropped output from inside rnn_fwd_tagged; 0: dropout kernel behind the recurrence
 static int g_opt_gemm_tn = 1;           // 1: weight-gradient products (both operands contraction-major) on the TN tile, no plane pass
@@ -47,7 +46,6 @@ static int g_opt_fwd_rsv_lds = 2;       // rnn_fwd_tagged: reserve traffic throu
 static int g_opt_fwd_pipe_any_chunking = 0;  // 1: pipeline the input projection with the forward recurrence even when no chunk count fits the side stream's one-round criterion (tests)
 static int g_opt_fwd_pipe_min_input = 0;       // smallest layer input width whose projection is pipelined with the forward recurrence
 static int g_opt_conv_dbg = 0;          // development: conv_mfma_kernel skips phases (1 window load, 2 MFMA loop, 4 output phase); results invalid
-static int g_opt_rnn_rsv_nt = 0;        // rnn_bwd_scatter2: non-temporal hint on the reserve traffic (experiment: keep the exchange tiles in L2 at H = 512)
 static int g_opt_gemm_bf16_single = 0;  // 256-row GEMM tiles: one bf16 product (ah*bh) instead of the three bf16x3 products (north_star's bf16 tolerance; gemm.hip)
 static int g_opt_gemm_dx_wide = 1;      // ctcn_gemm_dx's 256 x 320 tile: 0 never, 1 by the rounds rule (gemm.hip: plan_dx), 2 wherever eligible (tests)
 static int g_opt_xcd_interleave = 1;    // which physical XCD hosts group g of a persistent recurrence that leaves XCDs idle (eight XCDs; 0: XCD g, 1 (default): the even XCDs first, 2-5: other orders; the host's xcd_allow masks follow: ops._idle_xcd_mask)
@@ -78,7 +76,6 @@ static const OptionRow k_options[] = {
   {"gemm_big_tiles", &g_opt_gemm_big_tiles, [](int value) -> int { return value ? 1 : 0; }},
   {"beam_fast", &g_opt_beam_fast, [](int value) -> int { return value ? 1 : 0; }},
   {"conv_dbg", &g_opt_conv_dbg, [](int value) -> int { return value & 7; }},
-  {"rnn_rsv_nt", &g_opt_rnn_rsv_nt, [](int value) -> int { return value ? 1 : 0; }},
   {"tn_splits_xcd", &g_opt_tn_splits_xcd, [](int value) -> int { return value ? 1 : 0; }},
   {"xcd_interleave", &g_opt_xcd_interleave, [](int value) -> int { return value < 0 ? 0 : (value > 5 ? 5 : value); }},
   {"bn_rows4", &g_opt_bn_rows4, [](int value) -> int { return value ? 1 : 0; }},
@@ -100,7 +97,6 @@ static const OptionRow k_options[] = {
   {"rnn_fused_dropout", &g_opt_rnn_fused_dropout, [](int value) -> int { return value != 0; }},
   {"tag_poll_delay", &g_opt_tag_poll_delay, [](int value) -> int { return value < 0 ? 0 : (value > 64 ? 64 : value); }},
   {"rnn_fwd_tagged", &g_opt_rnn_fwd_tagged, [](int value) -> int { return value ? 1 : 0; }},
-  {"rnn_mixed_slices", &g_opt_rnn_mixed_slices, [](int value) -> int { return value ? 1 : 0; }},
   {"gemm_a_inline", &g_opt_gemm_a_inline, [](int value) -> int { return value ? 1 : 0; }},
   {"gemm_dbg", &g_opt_gemm_dbg, [](int value) -> int { return value; }},
   {"gemm_tile256", &g_opt_gemm_tile256, [](int value) -> int { return value ? 1 : 0; }},

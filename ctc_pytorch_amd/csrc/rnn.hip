@@ -46,13 +46,15 @@ __device__ __forceinline__ float act_tanh(float x) {
 // cycles for the same k on the f32 MFMA): the matmul leaves the serial path of the timestep almost entirely.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 union Bf16Pack { u32x4 u; bf16x8_t v; };
+__device__ __forceinline__ void split_bf16(float x, unsigned &hi, unsigned &lo) {
+  hi = f2bf(x);
+  lo = f2bf(x - __uint_as_float(hi << 16));
+}
 __device__ __forceinline__ void split8(const f32x4 &a, const f32x4 &b, bf16x8_t &hi, bf16x8_t &lo) {
   unsigned h[8], l[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const float x = e < 4 ? a[e] : b[e - 4];
-    h[e] = f2bf(x);
-    l[e] = f2bf(x - __uint_as_float(h[e] << 16));
+    split_bf16(e < 4 ? a[e] : b[e - 4], h[e], l[e]);
   }
   Bf16Pack ph, pl;
   ph.u = (u32x4){h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16)};
@@ -71,6 +73,74 @@ __device__ __forceinline__ void load_w8(const float *brow, int k0, int K, bf16x8
     b = k0 + 4 < K ? vb : zero;
   }
   split8(a, b, hi, lo);
+}
+
+// The cell equations, once for all seven recurrence kernels.  The expressions are kept as written: hipcc contracts a * b + c
+// into FMAs by their shape, and a reshaped expression changes bits.
+// Forward: o = the recurrent sums W_hh h_{t-1} per gate, pre = the input projection's pre-activations, state = c_{t-1} (LSTM) / h_{t-1} (GRU), carried.
+// Out: h = h_t; what the backward pass needs: sv = the gates in reserve order (LSTM i f g o, GRU r z n), sx = c_t (LSTM) / W_hn h_{t-1} (GRU).
+template <int CELL>
+__device__ __forceinline__ void cell_fwd(const float (&o)[4], const float (&pre)[4], float &state, float &h, float (&sv)[4], float &sx) {
+  if constexpr (CELL == CTCN_CELL_LSTM) {
+    const float i_ = act_sigmoid(o[0] + pre[0]);
+    const float f_ = act_sigmoid(o[1] + pre[1]);
+    const float g_ = act_tanh(o[2] + pre[2]);
+    const float o_ = act_sigmoid(o[3] + pre[3]);
+    const float c = f_ * state + i_ * g_;
+    h = o_ * act_tanh(c);
+    state = c;
+    sv[0] = i_; sv[1] = f_; sv[2] = g_; sv[3] = o_; sx = c;
+  } else if constexpr (CELL == CTCN_CELL_GRU) {
+    const float hn = o[2];
+    const float r_ = act_sigmoid(o[0] + pre[0]);
+    const float z_ = act_sigmoid(o[1] + pre[1]);
+    const float n_ = act_tanh(pre[2] + r_ * hn);
+    h = (1.0f - z_) * n_ + z_ * state;
+    state = h;
+    sv[0] = r_; sv[1] = z_; sv[2] = n_; sx = hn;
+  } else {
+    h = act_tanh(o[0] + pre[0]);
+  }
+}
+// Backward: dh = dy_t + (d(pre-act)_{next} W_hh), sv = the saved gates, e0 = c_t (LSTM) / W_hn h_{t-1} (GRU) / y_t (tanh), e1 = c_{t-1} (LSTM) / h_{t-1} (GRU),
+// 0 at the sequence start, state = dc (LSTM) / dh * z (GRU), carried.  Out: out = what the next step multiplies by W_hh, per gate block (GRU: out[2] =
+// dan * r, the gradient of W_hn h), and dan, the GRU's gradient of n's pre-activation -- the caller decides which of the two it publishes and stores where.
+template <int CELL>
+__device__ __forceinline__ void cell_bwd(float dh, const float (&sv)[4], float e0, float e1, float &state, float (&out)[4], float &dan) {
+  if constexpr (CELL == CTCN_CELL_LSTM) {
+    const float i_ = sv[0], f_ = sv[1], g_ = sv[2], o_ = sv[3];
+    const float tc = act_tanh(e0);
+    const float do_ = dh * tc;
+    const float dc = dh * o_ * (1.0f - tc * tc) + state;
+    out[0] = dc * g_ * i_ * (1.0f - i_);
+    out[1] = dc * e1 * f_ * (1.0f - f_);
+    out[2] = dc * i_ * (1.0f - g_ * g_);
+    out[3] = do_ * o_ * (1.0f - o_);
+    state = dc * f_;
+  } else if constexpr (CELL == CTCN_CELL_GRU) {
+    dh += state;
+    const float r_ = sv[0], z_ = sv[1], n_ = sv[2], hn = e0, hp = e1;
+    const float dn = dh * (1.0f - z_);
+    const float dz = dh * (hp - n_);
+    dan = dn * (1.0f - n_ * n_);
+    out[0] = dan * hn * r_ * (1.0f - r_);
+    out[1] = dz * z_ * (1.0f - z_);
+    out[2] = dan * r_;
+    state = dh * z_;
+  } else {
+    out[0] = dh * (1.0f - e0 * e0);
+  }
+}
+// ... and for the kernels that read the cell type from their arguments
+__device__ __forceinline__ void cell_fwd(int cell, const float (&o)[4], const float (&pre)[4], float &state, float &h, float (&sv)[4], float &sx) {
+  if (cell == CTCN_CELL_LSTM) cell_fwd<CTCN_CELL_LSTM>(o, pre, state, h, sv, sx);
+  else if (cell == CTCN_CELL_GRU) cell_fwd<CTCN_CELL_GRU>(o, pre, state, h, sv, sx);
+  else cell_fwd<CTCN_CELL_TANH>(o, pre, state, h, sv, sx);
+}
+__device__ __forceinline__ void cell_bwd(int cell, float dh, const float (&sv)[4], float e0, float e1, float &state, float (&out)[4], float &dan) {
+  if (cell == CTCN_CELL_LSTM) cell_bwd<CTCN_CELL_LSTM>(dh, sv, e0, e1, state, out, dan);
+  else if (cell == CTCN_CELL_GRU) cell_bwd<CTCN_CELL_GRU>(dh, sv, e0, e1, state, out, dan);
+  else cell_bwd<CTCN_CELL_TANH>(dh, sv, e0, e1, state, out, dan);
 }
 
 struct RnnArgs {
@@ -217,24 +287,18 @@ __global__ __launch_bounds__(256) void rnn_fwd_step(RnnArgs p) {
   if (item) {
     float *gt = p.gates + (row_t * D + d) * (size_t)(G * H);
     float *yt = p.y + row_t * D * H + d * H;
+    float sv[4], sx, h;
     if (p.cell == CTCN_CELL_LSTM) {
-      const float i_ = act_sigmoid(outs[bl][0 * 4 + jl] + pre[0]);
-      const float f_ = act_sigmoid(outs[bl][1 * 4 + jl] + pre[1]);
-      const float g_ = act_tanh(outs[bl][2 * 4 + jl] + pre[2]);
-      const float o_ = act_sigmoid(outs[bl][3 * 4 + jl] + pre[3]);
-      const float c = f_ * prev + i_ * g_;
-      gt[0 * H + j] = i_; gt[1 * H + j] = f_; gt[2 * H + j] = g_; gt[3 * H + j] = o_;
-      p.aux[(row_t * D + d) * H + j] = c;
-      yt[j] = o_ * act_tanh(c);
+      const float o[4] = {outs[bl][0 * 4 + jl], outs[bl][1 * 4 + jl], outs[bl][2 * 4 + jl], outs[bl][3 * 4 + jl]};
+      cell_fwd<CTCN_CELL_LSTM>(o, pre, prev, h, sv, sx);
+      gt[0 * H + j] = sv[0]; gt[1 * H + j] = sv[1]; gt[2 * H + j] = sv[2]; gt[3 * H + j] = sv[3];
     } else {
-      const float hn = outs[bl][2 * 4 + jl];
-      const float r_ = act_sigmoid(outs[bl][0 * 4 + jl] + pre[0]);
-      const float z_ = act_sigmoid(outs[bl][1 * 4 + jl] + pre[1]);
-      const float n_ = act_tanh(pre[2] + r_ * hn);
-      gt[0 * H + j] = r_; gt[1 * H + j] = z_; gt[2 * H + j] = n_;
-      p.aux[(row_t * D + d) * H + j] = hn;
-      yt[j] = (1.0f - z_) * n_ + z_ * prev;
+      const float o[4] = {outs[bl][0 * 4 + jl], outs[bl][1 * 4 + jl], outs[bl][2 * 4 + jl], 0.f};
+      cell_fwd<CTCN_CELL_GRU>(o, pre, prev, h, sv, sx);
+      gt[0 * H + j] = sv[0]; gt[1 * H + j] = sv[1]; gt[2 * H + j] = sv[2];
     }
+    p.aux[(row_t * D + d) * H + j] = sx;
+    yt[j] = h;
   }
   if (tanh_cell) {
     for (int it = tid; it < Bc * 16; it += 256) {
@@ -309,30 +373,23 @@ __global__ __launch_bounds__(1024) void rnn_bwd_step(RnnArgs p) {
 
   if (item) {
     float *gt = p.gates + (row_t * D + d) * (size_t)GH;
-    float dh = dyv + outs[bl][jl];
+    const float dh = dyv + outs[bl][jl];
+    // (cell_bwd works on copies: handed the prefetched values themselves, hipcc allocates two more VGPRs for the same instructions)
+    const float svc[4] = {sv[0], sv[1], sv[2], sv[3]};
+    float stc = stv;
+    float out[4] = {0.f, 0.f, 0.f, 0.f}, dan = 0.f;
     if (p.cell == CTCN_CELL_LSTM) {
-      const float i_ = sv[0], f_ = sv[1], g_ = sv[2], o_ = sv[3];
-      const float tc = act_tanh(e0);
-      const float do_ = dh * tc;
-      const float dc = dh * o_ * (1.0f - tc * tc) + stv;
-      gt[0 * H + j] = dc * g_ * i_ * (1.0f - i_);
-      gt[1 * H + j] = dc * e1 * f_ * (1.0f - f_);
-      gt[2 * H + j] = dc * i_ * (1.0f - g_ * g_);
-      gt[3 * H + j] = do_ * o_ * (1.0f - o_);
-      p.state[((size_t)b * D + d) * H + j] = dc * f_;
-    } else if (p.cell == CTCN_CELL_GRU) {
-      dh += stv;
-      const float r_ = sv[0], z_ = sv[1], n_ = sv[2], hn = e0, hp = e1;
-      const float dn = dh * (1.0f - z_);
-      const float dz = dh * (hp - n_);
-      const float dan = dn * (1.0f - n_ * n_);
-      gt[0 * H + j] = dan * hn * r_ * (1.0f - r_);
-      gt[1 * H + j] = dz * z_ * (1.0f - z_);
-      gt[2 * H + j] = dan;
-      p.aux[(row_t * D + d) * H + j] = dan * r_;
-      p.state[((size_t)b * D + d) * H + j] = dh * z_;
+      cell_bwd<CTCN_CELL_LSTM>(dh, svc, e0, e1, stc, out, dan);
+      gt[0 * H + j] = out[0]; gt[1 * H + j] = out[1]; gt[2 * H + j] = out[2]; gt[3 * H + j] = out[3];
+      p.state[((size_t)b * D + d) * H + j] = stc;
+    } else if (p.cell == CTCN_CELL_GRU) {          // dan stays here, dan * r (what W_hn h receives) goes to aux
+      cell_bwd<CTCN_CELL_GRU>(dh, svc, e0, e1, stc, out, dan);
+      gt[0 * H + j] = out[0]; gt[1 * H + j] = out[1]; gt[2 * H + j] = dan;
+      p.aux[(row_t * D + d) * H + j] = out[2];
+      p.state[((size_t)b * D + d) * H + j] = stc;
     } else {
-      gt[j] = dh * (1.0f - e0 * e0);
+      cell_bwd<CTCN_CELL_TANH>(dh, svc, e0, e1, stc, out, dan);
+      gt[j] = out[0];
     }
   }
 }
@@ -399,9 +456,10 @@ struct PersistArgs {
   unsigned *chunk_ready; //   ... and the counter the side stream raises after each chunk PAIR (p covers chunks p and nchunk-1-p)
   int slow, slow_x;      // options "rnn_slow_items" / "rnn_slow_exchange" (parity harness): the SLOW instantiations of the persistent kernels -- item / exchange waves sleep this many x 64 cycles at the start of their phase of every step
   int xperm;             // option "xcd_interleave" (eight XCDs): which physical XCD is logical XCD g, i.e. hosts group g (persist_role)
-  int nbig, hsu_small;  // forward, mixed slices (nbig > 0): slices 0 .. nbig-1 own `hsu` units each, the others `hsu_small`
+  int rsv_lds;          // rnn_fwd_tagged: 1 = the RSV instantiation (reserve traffic through LDS; fwd_try_tagged decides)
+  int spare;            // unused (take it for the next int): with it poll_depth, ydrop and the dropout fields sit at the offsets they had before nbig / hsu_small /
+                        // rsv_nt left, so that removal changed no kernel but the two that read them (moved fields regroup the scalar loads of every kernel)
   int poll_depth;       // XCD-local mode: flag polls kept in flight (1..4)
-  int rsv_nt;           // rnn_bwd_scatter2: reserve loads / stores carry the non-temporal hint (streaming data must not evict the exchange tiles from L2)
   int tagmode;          // rnn_bwd_scatter: 1 = no flags, every float of a partial block carries the step tag in its LSB and the
                         // gathering wave polls the block itself; 0 = stores drained, then a flag per block
   float *ydrop;         // rnn_fwd_tagged: when set, the inverted dropout of y (Philox4x32-10, the dropout kernel's counters) is stored here as well
@@ -409,7 +467,60 @@ struct PersistArgs {
   float drop_p, drop_scale;
   unsigned long long drop_seed, drop_off;
 #ifdef CTCN_PERSIST_STATS
-  long long *stats;   // development instrumentation (tools/mb_step.hip only)
+  long long *stats;   // development instrumentation (tools/mb_step.hip, tools/mb_bwd2.hip)
+  int debug;          // ... rnn_bwd_persist: 1 = the item waves skip their reserve loads, 2 = their reserve stores
+#endif
+};
+
+// Inverted dropout of one element of the fused-dropout launches from its Philox word w (the dropout kernel's test): x * scale as a multiply of its own, as
+// the dropout pass rounds it, or 0
+__device__ __forceinline__ float drop_keep(const PersistArgs &pa, uint32_t w, float x) {
+  return ((w >> 8) * (1.0f / 16777216.0f) >= pa.drop_p) ? __fmul_rn(x, pa.drop_scale) : 0.0f;
+}
+
+// rnn_bwd_persist's debug switches (tools): the item waves skip their reserve loads (bit 1) / stores (bit 2); never in the product build
+#ifdef CTCN_PERSIST_STATS
+__device__ __forceinline__ bool debug_skip(const PersistArgs &pa, int bit) { return (pa.debug & bit) != 0; }
+#else
+__device__ __forceinline__ constexpr bool debug_skip(const PersistArgs &, int) { return false; }
+#endif
+
+// Phase accounting of the persistent kernels (development instrumentation: tools/mb_step.hip and tools/mb_bwd2.hip define
+// CTCN_PERSIST_STATS).  Every thread keeps N accumulators in decode.hip's BSTAMP idiom: a stamp adds the cycles since the
+// thread's previous stamp to one of them, so a stamp that a thread skips leaves its phase at 0 and the phases of a step add up
+// to the step.  In the product build the struct is empty, its members do nothing and the kernels compile as if it were not there.
+template <int N>
+struct Stamps {
+#ifdef CTCN_PERSIST_STATS
+  long long acc[N] = {}, t0, last;
+  __device__ __forceinline__ Stamps() { t0 = last = clock64(); }
+  __device__ __forceinline__ void at(int i) { const long long now = clock64(); acc[i] += now - last; last = now; }
+  // ... once the LDS accesses issued so far have completed
+  __device__ __forceinline__ void at_lds(int i) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0); at(i); __builtin_amdgcn_sched_barrier(0);
+  }
+  // ... once x has been computed: the comparison consumes it in front of the stamp
+  __device__ __forceinline__ void at_used(int i, float x) { if (x == 12345.678f) acc[i] += 1; at(i); }
+  // ... once the loads into a and b have returned
+  __device__ __forceinline__ void at_loaded(int i, u32x4 &a, u32x4 &b) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(a), "+v"(b)::"memory"); at(i); }
+  __device__ __forceinline__ void count(int i) { acc[i] += 1; }      // an accumulator used as an event counter
+  // at the end of the kernel: the thread for which `who` holds writes its record to pa.stats[base ..]: the N accumulators, the cycles since
+  // the struct was created, the HW_ID register (the CU it ran on)
+  __device__ __forceinline__ void report(const PersistArgs &pa, bool who, int base) const {
+    if (!pa.stats || !who) return;
+    unsigned hw;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    for (int i = 0; i < N; ++i) pa.stats[base + i] = acc[i];
+    pa.stats[base + N] = clock64() - t0; pa.stats[base + N + 1] = hw;
+  }
+#else
+  __device__ __forceinline__ void at(int) {}
+  __device__ __forceinline__ void at_lds(int) {}
+  __device__ __forceinline__ void at_used(int, float) {}
+  __device__ __forceinline__ void at_loaded(int, u32x4 &, u32x4 &) {}
+  __device__ __forceinline__ void count(int) {}
+  __device__ __forceinline__ void report(const PersistArgs &, bool, int) const {}
 #endif
 };
 
@@ -478,9 +589,9 @@ __device__ __forceinline__ bool poll_flags_pipelined(const unsigned *flags, int 
 }
 __device__ __forceinline__ bool poll_group(const unsigned *flags, int n, unsigned want, int lane, const PersistArgs &pa) {
   if (pa.local && n <= 64) {
-    if ((pa.poll_depth & 255) == 2) return poll_flags_pipelined<2>(flags, n, want, lane, pa.spin_limit, pa.status);
-    if ((pa.poll_depth & 255) == 3) return poll_flags_pipelined<3>(flags, n, want, lane, pa.spin_limit, pa.status);
-    if ((pa.poll_depth & 255) >= 4) return poll_flags_pipelined<4>(flags, n, want, lane, pa.spin_limit, pa.status);
+    if (pa.poll_depth == 2) return poll_flags_pipelined<2>(flags, n, want, lane, pa.spin_limit, pa.status);
+    if (pa.poll_depth == 3) return poll_flags_pipelined<3>(flags, n, want, lane, pa.spin_limit, pa.status);
+    if (pa.poll_depth >= 4) return poll_flags_pipelined<4>(flags, n, want, lane, pa.spin_limit, pa.status);
   }
   return poll_flags(flags, n, want, lane, pa.spin_limit, pa.status);
 }
@@ -584,11 +695,7 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
   const int b0 = bt * 16;
   const int Bc = min(16, B - b0);
   const bool tanh_cell = cell == CTCN_CELL_TANH;
-  // hidden units owned by this workgroup (<= 4*NT; 16 for tanh).  Mixed slices: one workgroup per CU of the XCD with a few light
-  // ones (e.g. H = 320 on 32 CUs: 24 x 12 + 8 x 4 units) instead of 40 equal slices of which 16 share 8 CUs and set the period
-  const bool small_slice = pa.nbig > 0 && slice >= pa.nbig;
-  const int HSU = small_slice ? pa.hsu_small : pa.hsu;
-  const int j0 = small_slice ? pa.nbig * pa.hsu + (slice - pa.nbig) * pa.hsu_small : slice * pa.hsu;
+  const int HSU = pa.hsu, j0 = slice * HSU;                  // hidden units owned by this workgroup (<= 4*NT; 16 for tanh)
   const float *W = d == 0 ? p.w0 : p.w1;
   const int kb = wave * 16 * KQ4 + q * 4;
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -658,17 +765,12 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
     pre[0] = ld_slab(rg, vg0, o); pre[1] = ld_slab(rg, vg1, o); pre[2] = ld_slab(rg, vg2, o); pre[3] = ld_slab(rg, vg3, o);
   }
   __syncthreads();
-#ifdef CTCN_PERSIST_STATS
-  long long st_poll = 0, st_fill = 0, st_mm = 0, st_red = 0, st_epi = 0, st_t0 = clock64();
-  long long st_e1 = 0, st_e2 = 0, st_e3 = 0, st_e4 = 0;   // gate math (to hpub barrier) | publish stores issued | drained | flag + reserve issue
-  long long st_i0 = 0, st_i1 = 0, st_i2 = 0;             // item wave: partial sums | gate math + split + hpub writes
-#endif
+  // phases of a step: flag poll + barrier | operand loads | MFMAs | park + barrier | partial sums | gate math + split + hpub writes | hpub barrier |
+  // publish stores issued | drained | flag + reserve issue
+  enum { S_POLL, S_FILL, S_MM, S_RED, S_SUM, S_MATH, S_HPUB, S_PUB, S_DRAIN, S_TAIL, S_N };
+  Stamps<S_N> st;
 
   for (int s = 0; s < T; ++s) {
-#ifdef CTCN_PERSIST_STATS
-    const long long c_a = clock64();
-    long long c_p = c_a, c_f = c_a;
-#endif
     const int t = d == 0 ? s : T - 1 - s;
     const size_t row_t = (size_t)t * B + b;
     f32x4 acc[NT];
@@ -686,9 +788,7 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
       }
       lds_barrier();
       if (s_abort) break;
-#ifdef CTCN_PERSIST_STATS
-      c_p = clock64();
-#endif
+      st.at(S_POLL);
       const unsigned tbase = tile_b[par];
       if constexpr (PREC == 0) {
         f32x4 av[KQ4];
@@ -698,9 +798,7 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
           const f32x4 v = ld_sc1_f4(rs, tbase + (unsigned)((c * 64 + lane) * 16));
           av[si] = (k < H && r < Bc) ? v : zero;
         }
-#ifdef CTCN_PERSIST_STATS
-        c_f = clock64();
-#endif
+        st.at(S_FILL);
 #pragma unroll
         for (int si = 0; si < KQ4; ++si)
 #pragma unroll
@@ -717,9 +815,7 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
           al[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 1024, 0, 16);
         }
         __builtin_amdgcn_sched_barrier(0);        // all operand loads in flight before the first MFMA (hipcc otherwise reuses two register sets and serialises them)
-#ifdef CTCN_PERSIST_STATS
-        c_f = clock64();
-#endif
+        st.at(S_FILL);
 #pragma unroll
         for (int i = 0; i < KB; ++i) {
           const bf16x8_t ahv = __builtin_bit_cast(bf16x8_t, ah[i]), alv = __builtin_bit_cast(bf16x8_t, al[i]);
@@ -732,22 +828,14 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
         }
       }
     }
-#ifdef CTCN_PERSIST_STATS
-    const long long c_b = clock64();
-#endif
+    st.at(S_MM);
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt)      // park [wave][tile][unit q][row]: one 16-B slot = the four gates (tanh cell: four units) of a row
       *reinterpret_cast<f32x4 *>(red + (((wave * NT + nt) * PK_T + q * PK_Q + r) << 2)) = acc[nt];
     lds_barrier();
-#ifdef CTCN_PERSIST_STATS
-    const long long c_c = clock64();
-    st_poll += c_p - c_a; st_fill += c_f - c_p; st_mm += c_b - c_f; st_red += c_c - c_b;
-#endif
+    st.at(S_RED);
 
-    float sv0 = 0.f, sv1 = 0.f, sv2 = 0.f, sv3 = 0.f, sv4 = 0.f, hval = 0.f;     // values this item stores after the hand-off
-#ifdef CTCN_PERSIST_STATS
-    long long c_i0 = c_c;
-#endif
+    float sv0 = 0.f, sv1 = 0.f, sv2 = 0.f, sv3 = 0.f, sx = 0.f, hval = 0.f;     // values this item stores after the hand-off
     if (item) {
       // recurrent pre-activations of this item: gate g sits in column g*4 + ojl of tile ont (tanh cell: column jl)
       float o[4] = {0.f, 0.f, 0.f, 0.f};
@@ -763,49 +851,24 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
           o[0] += v[0]; o[1] += v[1]; o[2] += v[2]; o[3] += v[3];
         }
       }
-#ifdef CTCN_PERSIST_STATS
-      if (o[0] + o[1] + o[2] + o[3] == 12345.678f) st_i2 += 1;                  // consume the sums before the stamp
-      c_i0 = clock64();
-#endif
-      if (cell == CTCN_CELL_LSTM) {
-        const float i_ = act_sigmoid(o[0] + pre[0]);
-        const float f_ = act_sigmoid(o[1] + pre[1]);
-        const float g_ = act_tanh(o[2] + pre[2]);
-        const float o_ = act_sigmoid(o[3] + pre[3]);
-        const float c = f_ * state + i_ * g_;
-        hval = o_ * act_tanh(c);
-        state = c;
-        sv0 = i_; sv1 = f_; sv2 = g_; sv3 = o_; sv4 = c;
-      } else if (cell == CTCN_CELL_GRU) {
-        const float hn = o[2];
-        const float r_ = act_sigmoid(o[0] + pre[0]);
-        const float z_ = act_sigmoid(o[1] + pre[1]);
-        const float n_ = act_tanh(pre[2] + r_ * hn);
-        hval = (1.0f - z_) * n_ + z_ * state;
-        state = hval;
-        sv0 = r_; sv1 = z_; sv2 = n_; sv4 = hn;
-      } else {
-        hval = act_tanh(o[0] + pre[0]);
-      }
+      st.at_used(S_SUM, o[0] + o[1] + o[2] + o[3]);
+      float sv[4] = {0.f, 0.f, 0.f, 0.f};        // (copied to the scalars above, as in rnn_fwd_tagged: kept in this array across the hand-off the kernels grow)
+      if constexpr (CELL >= 0) cell_fwd<CELL>(o, pre, state, hval, sv, sx);
+      else cell_fwd(cell, o, pre, state, hval, sv, sx);
+      sv0 = sv[0]; sv1 = sv[1]; sv2 = sv[2]; sv3 = sv[3];
       if constexpr (PREC == 0) {
         hpub[bl][jl] = hval;
       } else {
         unsigned short *hp = reinterpret_cast<unsigned short *>(&hpub[0][0]);
-        const unsigned hi = f2bf(hval);
+        unsigned hi, lo;
+        split_bf16(hval, hi, lo);
         hp[bl * 16 + jl] = (unsigned short)hi;
-        hp[256 + bl * 16 + jl] = f2bf(hval - __uint_as_float(hi << 16));
+        hp[256 + bl * 16 + jl] = (unsigned short)lo;
       }
     }
-#ifdef CTCN_PERSIST_STATS
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const long long c_d0 = clock64();
-    st_i0 += c_i0 - c_c; st_i1 += c_d0 - c_i0;
-#endif
+    st.at_lds(S_MATH);
     lds_barrier();
-#ifdef CTCN_PERSIST_STATS
-    const long long c_d = clock64();
-    long long c_e = c_d, c_g = c_d;
-#endif
+    st.at(S_HPUB);
     // publish this workgroup's 16 x HSU block of h_t: 16-B stores by the communication wave, drained, then the flag
     if (s + 1 < T && wave == cw) {
       const int par = s & 1;
@@ -841,13 +904,9 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
           st_f4(rs, tbase + (unsigned)(((col >> 4) * 256 + (((col >> 2) & 3) * 16 + row) * 4) * 4), v, local);
         }
       }
-#ifdef CTCN_PERSIST_STATS
-      c_e = clock64();
-#endif
+      st.at(S_PUB);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the storing wave drains its stores (to L2 / to memory)
-#ifdef CTCN_PERSIST_STATS
-      c_g = clock64();
-#endif
+      st.at(S_DRAIN);
       if (lane == 0) st_u1(rf, (flg_el[par] + (unsigned)slice) * 4, (unsigned)(s + 1), local);
     }
     // The item waves' reserve stores (6 scattered dword stores per item) must not enter this CU's memory pipeline ahead of
@@ -866,34 +925,20 @@ __global__ __launch_bounds__(256) void rnn_fwd_persist(PersistArgs pa) {
       if (item) {
         if (cell == CTCN_CELL_LSTM) {
           st_slab(rg, vg0, og, sv0); st_slab(rg, vg1, og, sv1); st_slab(rg, vg2, og, sv2); st_slab(rg, vg3, og, sv3);
-          st_slab(ra, vh, oh, sv4);
+          st_slab(ra, vh, oh, sx);
         } else if (cell == CTCN_CELL_GRU) {
           st_slab(rg, vg0, og, sv0); st_slab(rg, vg1, og, sv1); st_slab(rg, vg2, og, sv2);
-          st_slab(ra, vh, oh, sv4);
+          st_slab(ra, vh, oh, sx);
         }
         st_slab(ry, vh, oh, hval);
         pre[0] = ld_slab(rg, vg0, on); pre[1] = ld_slab(rg, vg1, on); pre[2] = ld_slab(rg, vg2, on); pre[3] = ld_slab(rg, vg3, on);
       }
     }
-#ifdef CTCN_PERSIST_STATS
-    const long long c_h = clock64();
-    st_epi += c_h - c_c; st_e1 += c_d - c_c; st_e2 += c_e - c_d; st_e3 += c_g - c_e; st_e4 += c_h - c_g;
-    if (tid == 0) st_e1 += 0;
-    (void)c_d0;
-#endif
+    st.at(S_TAIL);
   }
-#ifdef CTCN_PERSIST_STATS
-  if (pa.stats && slice == 7 && d == 0 && bt == 0 && tid == cw * 64) {
-    pa.stats[0] = st_poll; pa.stats[1] = st_fill; pa.stats[2] = st_mm; pa.stats[3] = st_red; pa.stats[4] = st_epi; pa.stats[5] = clock64() - st_t0;
-    pa.stats[6] = st_e1; pa.stats[7] = st_e2; pa.stats[8] = st_e3; pa.stats[9] = st_e4;
-  }
-  if (pa.stats && slice == 7 && d == 0 && bt == 0 && tid == 0) { pa.stats[10] = st_i0; pa.stats[11] = st_i1; pa.stats[12] = st_i2; }
-  if (pa.stats && d == 0 && bt == 0 && tid == cw * 64 && slice < 64) {      // per-slice poll / rest split + the CU it ran on
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    pa.stats[16 + slice * 3] = st_poll; pa.stats[17 + slice * 3] = st_fill + st_mm + st_red + st_epi; pa.stats[18 + slice * 3] = hw;
-  }
-#endif
+  // item wave 0 of slice 7 at slot 0, the communication wave of slice k at 16 + 12 k
+  st.report(pa, slice == 7 && d == 0 && bt == 0 && tid == 0, 0);
+  st.report(pa, d == 0 && bt == 0 && tid == cw * 64 && slice < 64, 16 + 12 * slice);
   // a hand-off timed out: nothing this launch produced can be trusted.  Every (row, unit) item poisons its WHOLE output
   // column with NaN (all T frames -- a single poisoned frame can sit in the padding of every shorter utterance and be masked
   // out of the CTC loss), so the loss of this step is NaN for every model configuration, besides the sticky status word.
@@ -1090,9 +1135,10 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
   // to their publish and 0 for their reserve traffic, here and in rnn_bwd_scatter: 13.36 ms per cfg2 step without, 13.38-13.43 with; the
   // phases of the two wave kinds barely overlap, so there is nothing to arbitrate)
   __syncthreads();
-#ifdef CTCN_PERSIST_STATS
-  long long zx[4] = {0, 0, 0, 0}, zi[6] = {0, 0, 0, 0, 0, 0}, zt0 = clock64(), z_prev = zt0, zq = 0;
-#endif
+  // phases of a step.  Exchange waves: pause, validity checks and MFMAs between polls | polls in flight | perm + MFMAs + park | barrier wait (item
+  // waves: from the end of their previous step); item waves: partial sums | gate math | split + publish | reserve issue.  S_POLLS counts the polls.
+  enum { S_IDLE, S_POLL, S_MM, S_BARRIER, S_SUM, S_MATH, S_PUB, S_RSV, S_POLLS, S_N };
+  Stamps<S_N> st;
 
   for (int s = 0; s < T; ++s) {
     const int t = d == 0 ? s : T - 1 - s;
@@ -1100,10 +1146,6 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
     float *const red = red2 + (s & 1) * RED_N;                // the parked tiles of this step
 #else
     float *const red = red2;                                  // (tools: the single buffer of rounds 2-5, to show that the SLOW test catches it)
-#endif
-#ifdef CTCN_PERSIST_STATS
-    const long long z_a = clock64();
-    long long z_p = z_a, z_m = z_a;
 #endif
     if (wave >= 4) {
       if constexpr (SLOW) { for (int i = 0; i < pa.slow_x; ++i) __builtin_amdgcn_s_sleep(1); }
@@ -1132,15 +1174,10 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
               return __builtin_amdgcn_ballot_w64(okl) == ~0ull;
             };
             for (int spins = 0;; ++spins) {
-#ifdef CTCN_PERSIST_STATS
-              const long long z_q0 = clock64();
-#endif
+              st.at(S_IDLE);
               v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, boff, 0, 16);
               v1 = __builtin_amdgcn_raw_buffer_load_b128(rs, boff + 1024, 0, 16);
-#ifdef CTCN_PERSIST_STATS
-              asm volatile("s_waitcnt vmcnt(0)" : "+v"(v0), "+v"(v1)::"memory");
-              zx[3] += clock64() - z_q0; zq += 1;
-#endif
+              st.at_loaded(S_POLL, v0, v1); st.count(S_POLLS);
               if (valid(v0, v1)) break;
               if (spins > pa.spin_limit || ((spins & 63) == 63 && pa.status && __hip_atomic_load(pa.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
                 if (pa.status) atomicCAS(pa.status, 0, 111);             // give up: the launch finishes with a poisoned output
@@ -1148,9 +1185,7 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
               }
               __builtin_amdgcn_s_sleep(1);
             }
-#ifdef CTCN_PERSIST_STATS
-            z_p = clock64();
-#endif
+            st.at(S_IDLE);
             // split the {hi | lo << 16} dwords into the two MFMA fragments (8 consecutive k per lane), tag bits cleared
             Bf16Pack fh, fl;
             fh.u = (u32x4){__builtin_amdgcn_perm(v0.y, v0.x, 0x05040100u), __builtin_amdgcn_perm(v0.w, v0.z, 0x05040100u),
@@ -1169,18 +1204,11 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
       // park: slot (wave, tile, unit q, row r) = the four gates of unit mt*4 + q for batch row r
 #pragma unroll
       for (int mt = 0; mt < NMT; ++mt) *reinterpret_cast<f32x4 *>(red + ((((gw * NMT + mt) * 4 + q) * PQ + r) << 2)) = acc[mt];
-#ifdef CTCN_PERSIST_STATS
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      z_m = clock64();
-#endif
+      st.at_lds(S_MM);
     }
     if constexpr (RSV) { if (wave < G) asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); }   // this wave's pre-activation DMA of step s has landed (the youngest, s + 1, may be in flight)
     lds_barrier();
-#ifdef CTCN_PERSIST_STATS
-    const long long z_b = clock64();
-    if (wave >= 4) { zx[0] += z_p - z_a; zx[1] += z_m - z_p; zx[2] += z_b - z_m; }
-    long long z_i1 = z_b, z_i2 = z_b, z_i3 = z_b;
-#endif
+    st.at(S_BARRIER);
     if (wave < 4) {
       if constexpr (SLOW) { for (int i = 0; i < pa.slow; ++i) __builtin_amdgcn_s_sleep(1); }
       if constexpr (RSV) {
@@ -1194,47 +1222,27 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
         const f32x4 v = *reinterpret_cast<const f32x4 *>(rp + ((w * NMT * 4 * PQ) << 2));
         o[0] += v[0]; o[1] += v[1]; o[2] += v[2]; o[3] += v[3];
       }
-#ifdef CTCN_PERSIST_STATS
-      if (o[0] + o[1] + o[2] + o[3] == 12345.678f) zi[5] += 1;
-      z_i1 = clock64();
-#endif
-      float sv0 = 0.f, sv1 = 0.f, sv2 = 0.f, sv3 = 0.f, sv4 = 0.f, hval = 0.f;
+      st.at_used(S_SUM, o[0] + o[1] + o[2] + o[3]);
+      // (the saved gates live in scalars of this scope, not in cell_fwd's array: whether hipcc contracts c = f * state + i * g into an FMA or packs the two
+      // products depends on how they are kept -- it differs between the RSV and the plain instantiation -- and the results stay what they were)
+      float sv0 = 0.f, sv1 = 0.f, sv2 = 0.f, sv3 = 0.f, sx = 0.f, hval = 0.f;
       if (item) {
-        if constexpr (CELL == CTCN_CELL_LSTM) {
-          const float i_ = act_sigmoid(o[0] + pre[0]);
-          const float f_ = act_sigmoid(o[1] + pre[1]);
-          const float g_ = act_tanh(o[2] + pre[2]);
-          const float o_ = act_sigmoid(o[3] + pre[3]);
-          const float c = f_ * state + i_ * g_;
-          hval = o_ * act_tanh(c);
-          state = c;
-          sv0 = i_; sv1 = f_; sv2 = g_; sv3 = o_; sv4 = c;
-        } else {
-          const float hn = o[2];
-          const float r_ = act_sigmoid(o[0] + pre[0]);
-          const float z_ = act_sigmoid(o[1] + pre[1]);
-          const float n_ = act_tanh(pre[2] + r_ * hn);
-          hval = (1.0f - z_) * n_ + z_ * state;
-          state = hval;
-          sv0 = r_; sv1 = z_; sv2 = n_; sv4 = hn;
-        }
+        float sv[4];
+        cell_fwd<CELL>(o, pre, state, hval, sv, sx);
+        sv0 = sv[0]; sv1 = sv[1]; sv2 = sv[2];
+        if constexpr (CELL == CTCN_CELL_LSTM) sv3 = sv[3];
       }
-#ifdef CTCN_PERSIST_STATS
-      if (hval == 12345.678f) zi[5] += 1;
-      z_i2 = clock64();
-#endif
+      st.at_used(S_MATH, hval);
       if (s + 1 < T) {             // publish (every lane of the item waves: rows / units nobody owns publish a tagged 0)
-        const unsigned hi = f2bf(hval);
-        const unsigned lo = f2bf(hval - __uint_as_float(hi << 16));
+        unsigned hi, lo;
+        split_bf16(hval, hi, lo);
         const unsigned tbit = ((((unsigned)s) >> 1) & 1u) ^ 1u;
         const unsigned word = hi | (((lo & ~1u) | tbit) << 16);
         // (16-B publishes -- the four dwords of a lane quad gathered with DPP broadcasts, one store from 16 lanes per wave, 64 write requests
         // per workgroup instead of 256 -- measured in round 3: 1.66-1.67 vs 1.60-1.64 us per step: not kept)
         __builtin_amdgcn_raw_buffer_store_b32(word, rs, tile_b[s & 1] + pub_off, 0, 0);   // write-back into this XCD's L2
       }
-#ifdef CTCN_PERSIST_STATS
-      z_i3 = clock64();
-#endif
+      st.at(S_PUB);
       // reserve traffic, behind the publish in this wave's queue: saved activations, c / hn, y out; next step's pre-activations in
       const unsigned og = (unsigned)t * sg_b, oh = (unsigned)t * sh_b;
       const unsigned on = (unsigned)(s + 1 < T ? (d == 0 ? t + 1 : t - 1) : t) * sg_b;
@@ -1259,13 +1267,13 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
           float *oq = &outq[s & 1][0][tid];
           oq[0] = sv0; oq[256] = sv1; oq[512] = sv2;
           if constexpr (CELL == CTCN_CELL_LSTM) oq[768] = sv3;
-          oq[1024] = sv4; oq[1280] = hval;
+          oq[1024] = sx; oq[1280] = hval;
         }
         if (wave < G) pre_dma(s + 2, pset == 0 ? 2 : pset - 1);        // ring set (s + 2) % 3
       } else if (item) {
         st_slab(rg, vg0, og, sv0); st_slab(rg, vg1, og, sv1); st_slab(rg, vg2, og, sv2);
         if constexpr (CELL == CTCN_CELL_LSTM) st_slab(rg, vg3, og, sv3);
-        st_slab(ra, vh, oh, sv4);
+        st_slab(ra, vh, oh, sx);
         st_slab(ry, vh, oh, hval);
         pre[0] = ld_slab(rg, vg0, on); pre[1] = ld_slab(rg, vg1, on); pre[2] = ld_slab(rg, vg2, on);
         if constexpr (CELL == CTCN_CELL_LSTM) pre[3] = ld_slab(rg, vg3, on);
@@ -1285,23 +1293,20 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
           dropw[tid >> 6][lane] = make_uint4(rr[0], rr[1], rr[2], rr[3]);
         }
         const uint32_t w = reinterpret_cast<const uint32_t *>(&dropw[tid >> 6][(s & 3) * 16 + (lane >> 4) * 4 + ((lane & 15) >> 2)])[lane & 3];
-        if constexpr (RSV) { if (item) outq[s & 1][RSV ? 6 : 0][tid] = ((w >> 8) * (1.0f / 16777216.0f) >= pa.drop_p) ? hval * pa.drop_scale : 0.0f; }
-        else if (item) st_slab(ryd, vh, oh, ((w >> 8) * (1.0f / 16777216.0f) >= pa.drop_p) ? hval * pa.drop_scale : 0.0f);
+        if constexpr (RSV) { if (item) outq[s & 1][RSV ? 6 : 0][tid] = drop_keep(pa, w, hval); }
+        else if (item) st_slab(ryd, vh, oh, drop_keep(pa, w, hval));
       }
       if constexpr (RSV) pset = pset == 2 ? 0 : pset + 1;
-#ifdef CTCN_PERSIST_STATS
-      { const long long z_e = clock64(); zi[0] += z_b - z_prev; zi[1] += z_i1 - z_b; zi[2] += z_i2 - z_i1; zi[3] += z_i3 - z_i2; zi[4] += z_e - z_i3; z_prev = z_e; }
-#endif
+      st.at(S_RSV);
     }
   }
   if constexpr (RSV) {
     lds_barrier();
     if (wave >= 4) { if (T > 1) service_store(T - 2); service_store(T - 1); }
   }
-#ifdef CTCN_PERSIST_STATS
-  if (pa.stats && slice == 3 && d == 0 && bt == 0 && tid == 4 * 64) { pa.stats[0] = zx[0]; pa.stats[1] = zx[1]; pa.stats[2] = zx[2]; pa.stats[3] = clock64() - zt0; pa.stats[4] = zx[3]; pa.stats[5] = zq; }
-  if (pa.stats && slice == 3 && d == 0 && bt == 0 && tid == 0) for (int i = 0; i < 5; ++i) pa.stats[8 + i] = zi[i];
-#endif
+  // slice 3: exchange wave 4 at slot 0, item wave 0 at 16
+  st.report(pa, slice == 3 && d == 0 && bt == 0 && tid == 4 * 64, 0);
+  st.report(pa, slice == 3 && d == 0 && bt == 0 && tid == 0, 16);
   const bool bad = pa.status && __hip_atomic_load(pa.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
   if (bad && item)             // a hand-off timed out: poison the whole output column (see rnn_fwd_persist)
     for (int tt = 0; tt < T; ++tt) {
@@ -1314,7 +1319,7 @@ __global__ __launch_bounds__(1024) void rnn_fwd_tagged(PersistArgs pa) {
 bool launch_fwd_tagged(int nbw, dim3 grid, hipStream_t st, const PersistArgs &a, int wpx) {
   return pick_int<CTCN_CELL_LSTM, CTCN_CELL_GRU>(a.a.cell, [&](auto CELL) {
     return pick_int<0, 1>(a.slow > 0 || a.slow_x > 0, [&](auto SLOW) {
-      return pick_int<0, 1>((a.poll_depth & 256) != 0, [&](auto RSV) {
+      return pick_int<0, 1>(a.rsv_lds != 0, [&](auto RSV) {
         return pick_int<1, 2>(nbw, [&](auto NBW) {
           return launch_resident(rnn_fwd_tagged<decltype(NBW)::value, decltype(CELL)::value, decltype(RSV)::value != 0, decltype(SLOW)::value != 0>, grid, 1024, 0, st, a, wpx);
         });
@@ -1409,14 +1414,10 @@ __global__ __launch_bounds__(1024) void rnn_bwd_persist(PersistArgs pa) {
   }
   __syncthreads();
 
-#ifdef CTCN_PERSIST_STATS
-  long long bt_poll = 0, bt_mm = 0, bt_red = 0, bt_math = 0, bt_copy = 0, bt_tail = 0, bt_t0 = clock64();
-#endif
+  // phases of a step: flag poll + barrier | operand loads + MFMAs | park + barrier | item sum + gate math + stage + barrier | copy-out + drain + barrier | flag + reserve traffic
+  enum { S_POLL, S_MM, S_RED, S_MATH, S_COPY, S_TAIL, S_N };
+  Stamps<S_N> st;
   for (int s = 0; s < T; ++s) {
-#ifdef CTCN_PERSIST_STATS
-    const long long q_a = clock64();
-    long long q_p = q_a;
-#endif
     const int t = d == 0 ? T - 1 - s : s;
     const size_t row_t = (size_t)t * B + b;
     f32x4 acc[1];
@@ -1432,9 +1433,7 @@ __global__ __launch_bounds__(1024) void rnn_bwd_persist(PersistArgs pa) {
       }
       lds_barrier();
       if (s_abort) break;
-#ifdef CTCN_PERSIST_STATS
-      q_p = clock64();
-#endif
+      st.at(S_POLL);
       const unsigned tbase = tile_b[par];
       f32x4 acc1 = zero;      // two independent accumulator chains hide the dependent MFMA latency
       if constexpr (PREC == 0) {
@@ -1471,15 +1470,10 @@ __global__ __launch_bounds__(1024) void rnn_bwd_persist(PersistArgs pa) {
       }
       acc[0] += acc1;
     }
-#ifdef CTCN_PERSIST_STATS
-    const long long q_m = clock64();
-#endif
+    st.at(S_MM);
     park_tile(red, wave, lane, acc[0]);
     lds_barrier();
-#ifdef CTCN_PERSIST_STATS
-    const long long q_r = clock64();
-    long long q_e = q_r, q_c = q_r;
-#endif
+    st.at(S_RED);
 
     const int par = s & 1;
     const unsigned px = tile_b[par];                                                                // published tile (bytes)
@@ -1492,31 +1486,9 @@ __global__ __launch_bounds__(1024) void rnn_bwd_persist(PersistArgs pa) {
       for (int w = 0; w < NW; ++w) rec += rp[w * RT_T];
     }
     if (item) {
-      float dh = dyv + rec;
+      const float dh = dyv + rec;
       const float e1u = e1_valid ? e1 : 0.0f;                 // c / h of a step before the sequence start is 0
-      if (p.cell == CTCN_CELL_LSTM) {
-        const float i_ = sv[0], f_ = sv[1], g_ = sv[2], o_ = sv[3];
-        const float tc = act_tanh(e0);
-        const float do_ = dh * tc;
-        const float dc = dh * o_ * (1.0f - tc * tc) + state;
-        out[0] = dc * g_ * i_ * (1.0f - i_);
-        out[1] = dc * e1u * f_ * (1.0f - f_);
-        out[2] = dc * i_ * (1.0f - g_ * g_);
-        out[3] = do_ * o_ * (1.0f - o_);
-        state = dc * f_;
-      } else if (p.cell == CTCN_CELL_GRU) {
-        dh += state;
-        const float r_ = sv[0], z_ = sv[1], n_ = sv[2], hn = e0, hp = e1u;
-        const float dn = dh * (1.0f - z_);
-        const float dz = dh * (hp - n_);
-        dan = dn * (1.0f - n_ * n_);
-        out[0] = dan * hn * r_ * (1.0f - r_);
-        out[1] = dz * z_ * (1.0f - z_);
-        out[2] = dan * r_;
-        state = dh * z_;
-      } else {
-        out[0] = dh * (1.0f - e0 * e0);
-      }
+      cell_bwd(p.cell, dh, sv, e0, e1u, state, out, dan);
       // stage this workgroup's 16 x 16 x G block in LDS in the granule order of the tile
       if (s + 1 < T) {
 #pragma unroll
@@ -1526,18 +1498,17 @@ __global__ __launch_bounds__(1024) void rnn_bwd_persist(PersistArgs pa) {
               stage[((k * 4 + (jl >> 2)) * 16 + bl) * 4 + (jl & 3)] = out[k];
             } else {
               unsigned short *sp = reinterpret_cast<unsigned short *>(stage);
-              const unsigned hi = f2bf(out[k]);
+              unsigned hi, lo;
+              split_bf16(out[k], hi, lo);
               sp[((k * 2 + (jl >> 3)) * 16 + bl) * 8 + (jl & 7)] = (unsigned short)hi;
-              sp[(((4 + k) * 2 + (jl >> 3)) * 16 + bl) * 8 + (jl & 7)] = f2bf(out[k] - __uint_as_float(hi << 16));
+              sp[(((4 + k) * 2 + (jl >> 3)) * 16 + bl) * 8 + (jl & 7)] = (unsigned short)lo;
             }
           }
       }
     }
     if (s + 1 < T) {
       lds_barrier();
-#ifdef CTCN_PERSIST_STATS
-      q_e = clock64();
-#endif
+      st.at(S_MATH);
       // copy-out by waves 0..3: every lane one 16-B granule, 16 consecutive rows = 256 contiguous bytes of the tile
       if (tid < 256) {
         const int row = tid & 15;
@@ -1561,9 +1532,7 @@ __global__ __launch_bounds__(1024) void rnn_bwd_persist(PersistArgs pa) {
     if (s + 1 < T) {
       if (wave < 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its stores (to L2 / to memory)
       lds_barrier();
-#ifdef CTCN_PERSIST_STATS
-      q_c = clock64();
-#endif
+      st.at(S_COPY);
       if (tid == 0) st_u1(rf, (flg_el[par] + (unsigned)slice) * 4, (unsigned)(s + 1), local);
     }
     // off the critical path (item waves): d(pre-activation) for the deferred dW / dX GEMMs leaves after the hand-off,
@@ -1572,12 +1541,7 @@ __global__ __launch_bounds__(1024) void rnn_bwd_persist(PersistArgs pa) {
       const unsigned og = (unsigned)t * sg_b, oh = (unsigned)t * sh_b;
       const int tn = s + 1 < T ? t + tdir : t, tp = s + 2 < T ? tn + tdir : tn;             // past the end: re-read (unused)
       const unsigned ogn = (unsigned)tn * sg_b, ohn = (unsigned)tn * sh_b, ohp = (unsigned)tp * sh_b;
-#ifdef CTCN_PERSIST_STATS
-      const bool dbg_no_st = (pa.poll_depth & 512) != 0, dbg_no_ld = (pa.poll_depth & 256) != 0;
-#else
-      constexpr bool dbg_no_st = false, dbg_no_ld = false;
-#endif
-      if (item && !dbg_no_st) {
+      if (item && !debug_skip(pa, 2)) {
         if (is_lstm) {
           st_slab(rg, vg0, og, out[0]); st_slab(rg, vg1, og, out[1]); st_slab(rg, vg2, og, out[2]); st_slab(rg, vg3, og, out[3]);
         } else if (p.cell == CTCN_CELL_GRU) {
@@ -1587,22 +1551,17 @@ __global__ __launch_bounds__(1024) void rnn_bwd_persist(PersistArgs pa) {
           st_slab(rg, vg0, og, out[0]);
         }
       }
-      if (item && !dbg_no_ld) {
+      if (item && !debug_skip(pa, 1)) {
         sv[0] = ld_slab(rg, vg0, ogn); sv[1] = ld_slab(rg, vg1, ogn); sv[2] = ld_slab(rg, vg2, ogn); sv[3] = ld_slab(rg, vg3, ogn);
         dyv = ld_slab(rdy, vh, ohn); e0 = ld_slab(r0, vh, ohn); e1 = ld_slab(r1, vh, ohp);
       }
       e1_valid = s + 2 < T && !is_tanh;
     }
-#ifdef CTCN_PERSIST_STATS
-    { const long long q_z = clock64(); bt_poll += q_p - q_a; bt_mm += q_m - q_p; bt_red += q_r - q_m; bt_math += q_e - q_r; bt_copy += q_c - q_e; bt_tail += q_z - q_c; }
-#endif
+    st.at(S_TAIL);
   }
-#ifdef CTCN_PERSIST_STATS
-  if (pa.stats && slice == 3 && d == 0 && bt == 0 && (tid == 0 || tid == 960)) {
-    long long *o = pa.stats + (tid == 0 ? 0 : 8);
-    o[0] = bt_poll; o[1] = bt_mm; o[2] = bt_red; o[3] = bt_math; o[4] = bt_copy; o[5] = bt_tail; o[6] = clock64() - bt_t0;
-  }
-#endif
+  // slice 3: item wave 0 at slot 0, the polling wave at 8
+  st.report(pa, slice == 3 && d == 0 && bt == 0 && tid == 0, 0);
+  st.report(pa, slice == 3 && d == 0 && bt == 0 && tid == 960, 8);
   if (s_abort && item)       // poison d(pre-activation) of every frame: dx and both weight gradients of the layer become NaN
     for (int tt = 0; tt < T; ++tt) st_slab(rg, vg0, (unsigned)tt * sg_b, __uint_as_float(0x7fc00000u));
 }
@@ -1742,15 +1701,11 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
   }
   __syncthreads();
 
-#ifdef CTCN_PERSIST_STATS
-  long long zt[6] = {0, 0, 0, 0, 0, 0}, zi[4] = {0, 0, 0, 0}, zt0 = clock64();
-#endif
+  // phases of a step: gather + park + barrier | item sum | gate math + stage writes | barrier wait | LDS reads + MFMAs + scatter issue | drain + flags | reserve traffic
+  enum { S_GATHER, S_SUM, S_MATH, S_STAGED, S_SCATTER, S_DRAIN, S_TAIL, S_N };
+  Stamps<S_N> st;
   auto step = [&](const int s, auto PSC) {
     constexpr int ps = decltype(PSC)::value;
-#ifdef CTCN_PERSIST_STATS
-    const long long z_a = clock64();
-    long long z_p = z_a, z_g = z_a, z_m = z_a, z_s = z_a, z_d = z_a;
-#endif
     const int t = d == 0 ? T - 1 - s : s;
     uint32_t dropword = 0;
     if (pa.drop_bwd && tid < 256)
@@ -1809,9 +1764,7 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
         park_tile(red, gw, lane, sum);
       }
       lds_barrier();
-#ifdef CTCN_PERSIST_STATS
-      z_p = z_g = clock64();
-#endif
+      st.at(S_GATHER);
       if (tid < 256) {
         if constexpr (SLOW) { for (int i = 0; i < pa.slow; ++i) __builtin_amdgcn_s_sleep(1); }
         const float *rp = red + parked_at(bl, jl);
@@ -1819,10 +1772,7 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
         for (int w = 0; w < NGW; ++w) rec += rp[w * RT_T];
       }
     }
-#ifdef CTCN_PERSIST_STATS
-    if (rec == 12345.678f) zi[3] += 1;         // consume the sum before the stamp
-    const long long z_i0 = clock64();
-#endif
+    st.at_used(S_SUM, rec);
 
     float out[4] = {0.f, 0.f, 0.f, 0.f};      // d(pre-activation) the next step multiplies by W_hh, per gate block
     float dan = 0.f;
@@ -1831,43 +1781,21 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
     asm volatile("s_waitcnt vmcnt(7)" : "+v"(sv[ps][0]), "+v"(sv[ps][1]), "+v"(sv[ps][2]), "+v"(sv[ps][3]), "+v"(dyv[ps]), "+v"(e0[ps]), "+v"(e1[ps])::"memory");
     if (item) {
       float dyd = dyv[ps];
-      if (pa.drop_bwd)            // (a separate multiply, as the dropout pass would round it, then the add)
-        dyd = ((dropword >> 8) * (1.0f / 16777216.0f) >= pa.drop_p) ? __fmul_rn(dyd, pa.drop_scale) : 0.0f;
-      float dh = dyd + rec;
+      if (pa.drop_bwd) dyd = drop_keep(pa, dropword, dyd);
+      const float dh = dyd + rec;
       const float e1u = (s + 1 < T && !is_tanh) ? e1[ps] : 0.0f;   // c / h of a step before the sequence start is 0
-      if constexpr (CELL == CTCN_CELL_LSTM) {
-        const float i_ = sv[ps][0], f_ = sv[ps][1], g_ = sv[ps][2], o_ = sv[ps][3];
-        const float tc = act_tanh(e0[ps]);
-        const float do_ = dh * tc;
-        const float dc = dh * o_ * (1.0f - tc * tc) + state;
-        out[0] = dc * g_ * i_ * (1.0f - i_);
-        out[1] = dc * e1u * f_ * (1.0f - f_);
-        out[2] = dc * i_ * (1.0f - g_ * g_);
-        out[3] = do_ * o_ * (1.0f - o_);
-        state = dc * f_;
-      } else if constexpr (CELL == CTCN_CELL_GRU) {
-        dh += state;
-        const float r_ = sv[ps][0], z_ = sv[ps][1], n_ = sv[ps][2], hn = e0[ps], hp = e1u;
-        const float dn = dh * (1.0f - z_);
-        const float dz = dh * (hp - n_);
-        dan = dn * (1.0f - n_ * n_);
-        out[0] = dan * hn * r_ * (1.0f - r_);
-        out[1] = dz * z_ * (1.0f - z_);
-        out[2] = dan * r_;
-        state = dh * z_;
-      } else {
-        out[0] = dh * (1.0f - e0[ps] * e0[ps]);
-      }
+      cell_bwd<CELL>(dh, sv[ps], e0[ps], e1u, state, out, dan);
       if (s + 1 < T) {                                        // A operand of this workgroup's product, in MFMA order
 #pragma unroll
         for (int k = 0; k < 4; ++k)
           if (k < G) {
             if constexpr (PREC == 1) {
               unsigned short *sp = reinterpret_cast<unsigned short *>(stage);
-              const unsigned hi = f2bf(out[k]);
+              unsigned hi, lo;
+              split_bf16(out[k], hi, lo);
               const int o = ((((k >> 1) * 4) + (k & 1) * 2 + (jl >> 3)) * 16 + bl) * 8 + (jl & 7);     // [blk][q][row][8]
               sp[o] = (unsigned short)hi;
-              sp[1024 + o] = f2bf(out[k] - __uint_as_float(hi << 16));
+              sp[1024 + o] = (unsigned short)lo;
             } else {
               const int kk = k * 16 + jl;                                                              // [m][kq][row]
               stage[((kk >> 2) * 4 + (kk & 3)) * 16 + bl] = out[k];
@@ -1875,16 +1803,10 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
           }
       }
     }
-#ifdef CTCN_PERSIST_STATS
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const long long z_i1 = clock64();
-#endif
+    st.at_lds(S_MATH);
     if (s + 1 < T) {
       lds_barrier();
-#ifdef CTCN_PERSIST_STATS
-      z_m = clock64();
-      zi[0] += z_i0 - z_g; zi[1] += z_i1 - z_i0; zi[2] += z_m - z_i1;
-#endif
+      st.at(S_STAGED);
       const int par = s & 1;
       if (wave >= 4) {
       if constexpr (SLOW) { for (int i = 0; i < pa.slow_x; ++i) __builtin_amdgcn_s_sleep(1); }
@@ -1945,9 +1867,7 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
         }
       }
       }
-#ifdef CTCN_PERSIST_STATS
-      z_s = clock64();
-#endif
+      st.at(S_SCATTER);
       if constexpr (!TAGGED) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's block stores have landed (L2 / memory) ...
       if (lane == 0) {
@@ -1959,9 +1879,7 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
       }
       }
       }
-#ifdef CTCN_PERSIST_STATS
-      z_d = clock64();
-#endif
+      st.at(S_DRAIN);
     }
     // off the critical path (item waves): d(pre-activation) for the deferred dW / dX GEMMs, next step's saved values
     {
@@ -1979,22 +1897,15 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
       }
       if (pa.drop_bwd && tid < 256 && (s & 3) == 3) drop_block(s + 1);
     }
-#ifdef CTCN_PERSIST_STATS
-    { const long long z_z = clock64(); zt[0] += z_p - z_a; zt[1] += z_g - z_p; zt[2] += z_m - z_g; zt[3] += z_s - z_m; zt[4] += z_d - z_s; zt[5] += z_z - z_d; }
-#endif
+    st.at(S_TAIL);
   };
   for (int s = 0; s < T; s += 2) {                            // unrolled by two: the reserve set of a step is a compile-time index
     step(s, std::integral_constant<int, 0>{});
     if (s + 1 < T) step(s + 1, std::integral_constant<int, 1>{});
   }
-#ifdef CTCN_PERSIST_STATS
-  if (pa.stats && slice == 3 && d == 0 && bt == 0 && (tid == 0 || tid == 960)) {
-    long long *o = pa.stats + (tid == 0 ? 0 : 8);
-    for (int i = 0; i < 6; ++i) o[i] = zt[i];
-    o[6] = clock64() - zt0;
-    if (tid == 0) for (int i = 0; i < 3; ++i) pa.stats[16 + i] = zi[i];
-  }
-#endif
+  // slice 3: item wave 0 at slot 0, exchange wave 15 at 16
+  st.report(pa, slice == 3 && d == 0 && bt == 0 && tid == 0, 0);
+  st.report(pa, slice == 3 && d == 0 && bt == 0 && tid == 960, 16);
   const bool bad = pa.status && __hip_atomic_load(pa.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
   if (bad && item)           // poison d(pre-activation) of every frame: dx and both weight gradients of the layer become NaN
     for (int tt = 0; tt < T; ++tt) st_slab(rg, vg0, (unsigned)tt * sg_b, __uint_as_float(0x7fc00000u));
@@ -2093,8 +2004,7 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
     else if (a == 4) src = p.dy + (size_t)tx * slab_h + xh;
     else if (a == 5) src = (is_tanh ? p.y : p.aux) + (size_t)tx * slab_h + xh;
     else src = (is_lstm ? p.aux : p.y) + (size_t)tx1 * slab_h + xh;
-    if (pa.rsv_nt) __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)&resv[set][a][0], 16, 0, 2);      // aux 2 = nt
-    else __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)&resv[set][a][0], 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)&resv[set][a][0], 16, 0, 0);
   };
   auto dma = [&](int x, int set) {
     if (needed(ew)) dma1(ew, x, set);
@@ -2118,23 +2028,20 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
   // byte offset of this item lane's float inside a partial block (MFMA C layout: float ((row >> 2) * 16 + unit) * 4 + (row & 3))
   const unsigned poll_off = (unsigned)(slice * nsl) * 1024u + (unsigned)(wave & 3) * 256u + (unsigned)((lane & 15) * 16 + (lane >> 4) * 4);
   int set = 0;                                     // s % 3
-#ifdef CTCN_PERSIST_STATS
-  long long zs[6] = {0, 0, 0, 0, 0, 0}, zq[3] = {0, 0, 0}, z0 = clock64();
-#endif
+  // phases of a step: item waves: delay + poll + sum (exchange waves: vmcnt wait) | gate math + stage (LDS drained) | barrier wait | exchange waves: A fragments in
+  // registers | chains + tags + block stores issued | after that (item waves: after the barrier).  S_ROUNDS counts the poll rounds.
+  enum { S_GATHER, S_MATH, S_BARRIER, S_FRAG, S_CHAINS, S_TAIL, S_ROUNDS, S_N };
+  Stamps<S_N> st;
   for (int s = 0; s < T; ++s) {
     const int t = d == 0 ? T - 1 - s : s;
     const int sb = s & 1;
-#ifdef CTCN_PERSIST_STATS
-    const long long z_a = clock64();
-    long long z_b = z_a, z_c = z_a;
-#endif
     if (wave < 4) {
       // ---------------- item waves: gather, gate math, stage ------------------------------------------------------------------
       if constexpr (SLOW) { for (int i = 0; i < pa.slow; ++i) __builtin_amdgcn_s_sleep(1); }
       uint32_t dropword = 0;
       if (pa.drop_bwd) dropword = reinterpret_cast<const uint32_t *>(&dropw[wave][(s & 3) * 16 + (lane >> 4) * 4 + ((lane & 15) >> 2)])[lane & 3];
       const float *rv = &resv[set][0][0] + tid;
-      const float sv0 = rv[0], sv1 = rv[256], sv2 = rv[512], sv3 = rv[768], dyv = rv[1024], e0 = rv[1280], e1 = rv[1536];
+      const float sv[4] = {rv[0], rv[256], rv[512], rv[768]}, dyv = rv[1024], e0 = rv[1280], e1 = rv[1536];
       float rec = 0.0f;
       if (s > 0) {
         const int par = (s - 1) & 1;
@@ -2155,9 +2062,7 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
 #pragma unroll
           for (int i = 1; i < NPL; ++i) { va &= v[i].x & v[i].y & v[i].z & v[i].w; vo |= v[i].x | v[i].y | v[i].z | v[i].w; }
           const bool okl = ((tb ? va : ~vo) & 1u) != 0;
-#ifdef CTCN_PERSIST_STATS
-          zs[4] += 1;
-#endif
+          st.count(S_ROUNDS);
           if (__builtin_amdgcn_ballot_w64(okl) == ~0ull) break;
           if (spins > pa.spin_limit || ((spins & 63) == 63 && pa.status && __hip_atomic_load(pa.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
             if (pa.status) atomicCAS(pa.status, 0, 203);
@@ -2182,49 +2087,25 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
         const auto sf = __builtin_amdgcn_permlane16_swap(__float_as_uint(h0), __float_as_uint(h1), false, false);
         rec = __uint_as_float(sf[0]) + __uint_as_float(sf[1]);
       }
-#ifdef CTCN_PERSIST_STATS
-      if (rec == 12345.678f) zs[5] += 1;
-      z_b = clock64();
-#endif
+      st.at_used(S_GATHER, rec);
       float out[4] = {0.f, 0.f, 0.f, 0.f};
       float dan = 0.f;
       if (item) {
         float dyd = dyv;
-        if (pa.drop_bwd) dyd = ((dropword >> 8) * (1.0f / 16777216.0f) >= pa.drop_p) ? __fmul_rn(dyd, pa.drop_scale) : 0.0f;
-        float dh = dyd + rec;
+        if (pa.drop_bwd) dyd = drop_keep(pa, dropword, dyd);
+        const float dh = dyd + rec;
         const float e1u = (s + 1 < T && !is_tanh) ? e1 : 0.0f;
-        if constexpr (is_lstm) {
-          const float i_ = sv0, f_ = sv1, g_ = sv2, o_ = sv3;
-          const float tc = act_tanh(e0);
-          const float do_ = dh * tc;
-          const float dc = dh * o_ * (1.0f - tc * tc) + state;
-          out[0] = dc * g_ * i_ * (1.0f - i_);
-          out[1] = dc * e1u * f_ * (1.0f - f_);
-          out[2] = dc * i_ * (1.0f - g_ * g_);
-          out[3] = do_ * o_ * (1.0f - o_);
-          state = dc * f_;
-        } else if constexpr (is_gru) {
-          dh += state;
-          const float r_ = sv0, z_ = sv1, n_ = sv2, hn = e0, hp = e1u;
-          const float dn = dh * (1.0f - z_);
-          const float dz = dh * (hp - n_);
-          dan = dn * (1.0f - n_ * n_);
-          out[0] = dan * hn * r_ * (1.0f - r_);
-          out[1] = dz * z_ * (1.0f - z_);
-          out[2] = dan * r_;
-          state = dh * z_;
-        } else {
-          out[0] = dh * (1.0f - e0 * e0);
-        }
+        cell_bwd<CELL>(dh, sv, e0, e1u, state, out, dan);
         if (s + 1 < T) {
           unsigned short *sp = reinterpret_cast<unsigned short *>(&stage[sb][0]);
 #pragma unroll
           for (int k = 0; k < 4; ++k)
             if (k < G) {
-              const unsigned hi = f2bf(out[k]);
+              unsigned hi, lo;
+              split_bf16(out[k], hi, lo);
               const int o = ((((k >> 1) * 4) + (k & 1) * 2 + (jl >> 3)) * 16 + bl) * 8 + (jl & 7);     // [blk][q][row][8]
               sp[o] = (unsigned short)hi;
-              sp[1024 + o] = f2bf(out[k] - __uint_as_float(hi << 16));
+              sp[1024 + o] = (unsigned short)lo;
             }
         }
         // float32 copy for the reserve: LSTM 4 gates; GRU r, z, dan | dan * r (-> aux); tanh 1
@@ -2235,19 +2116,11 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
       // every reserve load but this wave's youngest `ndma` has landed (see header)
       if (ndma == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       else if (ndma == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-#ifdef CTCN_PERSIST_STATS
-      z_b = clock64();
-#endif
+      st.at(S_GATHER);
     }
-#ifdef CTCN_PERSIST_STATS
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    z_c = clock64();
-#endif
+    st.at_lds(S_MATH);
     lds_barrier();
-#ifdef CTCN_PERSIST_STATS
-    const long long z_d = clock64();
-    long long z_e = z_d;
-#endif
+    st.at(S_BARRIER);
     if (wave >= 4) {
       // ---------------- exchange waves: multiply, scatter, reserve traffic ----------------------------------------------------
       if constexpr (SLOW) { for (int i = 0; i < pa.slow_x; ++i) __builtin_amdgcn_s_sleep(1); }
@@ -2261,13 +2134,7 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
           al[blk] = *reinterpret_cast<const bf16x8_t *>(sp + 1024 + ((blk * 4 + q) * 16 + r) * 8);
         }
         const unsigned tbs = ((((unsigned)s) >> 1) & 1u) ^ 1u;
-#ifdef CTCN_PERSIST_STATS
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        const long long z_x0 = clock64();
-        zq[0] += z_x0 - z_d;
-        __builtin_amdgcn_sched_barrier(0);
-#endif
+        st.at_lds(S_FRAG);
         // one chain after the other (a dependent chain issues at the same 16 cycles per MFMA as independent ones, tools/mb_mfma16.hip),
         // each tile's block stored as soon as its chain ends: the CU's store path (20 x 1 KB per step, ~200 cycles per block when all
         // exchange waves store together) then works WHILE the matrix pipes do, instead of after them
@@ -2287,22 +2154,12 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
             st_f4(rs, tile_b[par] + (unsigned)(((owner * nsl + slice) * 64 + lane) * 16), acc, local);
           }
         }
-#ifdef CTCN_PERSIST_STATS
-        __builtin_amdgcn_sched_barrier(0);
-        { const long long z_x3 = clock64(); zq[2] += z_x3 - z_x0; }
-        __builtin_amdgcn_sched_barrier(0);
-#endif
       }
-#ifdef CTCN_PERSIST_STATS
-      z_e = clock64();
-#endif
+      st.at(S_CHAINS);
       if (ew < (is_tanh ? 1 : 4)) {
         const f32x4 vst = *reinterpret_cast<const f32x4 *>(&outf[sb][ew][lane * 4]);
         float *dst = (is_gru && ew == 3) ? p.aux + (size_t)t * slab_h + xh : p.gates + (size_t)t * slab_g + xg + (size_t)ew * H;
-        if (xvalid) {
-          if (pa.rsv_nt) __builtin_nontemporal_store(vst, reinterpret_cast<f32x4 *>(dst));
-          else *reinterpret_cast<f32x4 *>(dst) = vst;
-        }
+        if (xvalid) *reinterpret_cast<f32x4 *>(dst) = vst;
       }
       // LAST in program order: the vmcnt(ndma) wait before the next barrier then lets exactly these loads stay in flight, whatever the
       // order in which the counter retires loads against stores
@@ -2311,18 +2168,11 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
       if (pa.drop_bwd && (s & 3) == 3) drop_block(s + 1);
     }
     set = set == 2 ? 0 : set + 1;
-#ifdef CTCN_PERSIST_STATS
-    { const long long z_f = clock64(); zs[0] += z_b - z_a; zs[1] += z_c - z_b; zs[2] += z_d - z_c; zs[3] += z_e - z_d; zs[5] += z_f - z_e; }
-#endif
+    st.at(S_TAIL);
   }
-#ifdef CTCN_PERSIST_STATS
-  if (pa.stats && slice == 3 && d == 0 && bt == 0 && (tid == 0 || tid == 256)) {
-    long long *o = pa.stats + (tid == 0 ? 0 : 8);
-    for (int i = 0; i < 6; ++i) o[i] = zs[i];
-    o[6] = clock64() - z0;
-    if (tid == 256) { pa.stats[16] = zq[0]; pa.stats[17] = zq[1]; pa.stats[18] = zq[2]; }
-  }
-#endif
+  // slice 3: item wave 0 at slot 0, exchange wave 4 at 16
+  st.report(pa, slice == 3 && d == 0 && bt == 0 && tid == 0, 0);
+  st.report(pa, slice == 3 && d == 0 && bt == 0 && tid == 256, 16);
   const bool bad = pa.status && __hip_atomic_load(pa.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
   if (bad && item)           // poison d(pre-activation) of every frame: dx and both weight gradients of the layer become NaN
     for (int tt = 0; tt < T; ++tt) p.gates[(size_t)tt * slab_g + ((size_t)b * D + d) * K + j] = __uint_as_float(0x7fc00000u);
@@ -2557,9 +2407,6 @@ static PersistArgs persist_args(const RnnArgs &a, const Handoff &h, int *status,
   pa.local = g.mode; pa.nx = g.nx; pa.xperm = g.mode ? xcd_order_for(g.nx, g.groups) : 0;
   pa.nsl = g.nsl; pa.nbt = g.nbt; pa.hsu = g.hsu; pa.wpx = g.wpx;
   pa.poll_depth = ctcn_opt_poll_depth(); pa.tagmode = 0;                 // (the tagged launches set their own)
-#ifdef CTCN_PERSIST_STATS
-  pa.stats = nullptr;
-#endif
   return pa;
 }
 
@@ -2597,7 +2444,7 @@ struct FwdCall {
   int *status;
   bool fits32;                // the persistent kernels address each tensor through one 32-bit-offset buffer resource
   int nxd, cus;               // XCDs the XCD-local hand-off can use (1: none, or option "handoff" off); CUs of the device
-  bool recurrence_only, persistent, tagged, mixed_slices, any_chunking, fused_dropout;
+  bool recurrence_only, persistent, tagged, any_chunking, fused_dropout;
   int min_input, rsv_lds, tag_poll_delay, slow_items, slow_exchange;
   hipStream_t st() const { return (hipStream_t)stream; }
 };
@@ -2628,7 +2475,6 @@ static void fwd_begin(FwdCall &c, const float *w_hh0, const float *w_hh1, float 
   c.recurrence_only = ctcn_opt_recurrence_only() != 0;
   c.persistent = ctcn_opt_rnn_persistent() != 0;
   c.tagged = ctcn_get_option("rnn_fwd_tagged") != 0;
-  c.mixed_slices = ctcn_get_option("rnn_mixed_slices") != 0;
   c.any_chunking = ctcn_get_option("fwd_pipe_any_chunking") != 0;
   c.fused_dropout = ctcn_get_option("rnn_fused_dropout") != 0;
   c.min_input = ctcn_get_option("fwd_pipe_min_input");
@@ -2752,7 +2598,7 @@ static int fwd_try_tagged(const FwdCall &c, const PipePlan &p, GemmPlanes &pl_ma
     // the polls)
     const bool rsv = (c.rsv_lds == 1 || (c.rsv_lds == 2 && nsl > 24)) &&
                      ((uintptr_t)c.a.gates | (uintptr_t)c.a.aux | (uintptr_t)c.a.y | (uintptr_t)(drop_pending ? c.call.y_drop : nullptr)) % 16 == 0;
-    pa.poll_depth = 1 | (rsv ? 256 : 0); pa.tagmode = 1; pa.poll_delay = c.tag_poll_delay;
+    pa.poll_depth = 1; pa.rsv_lds = rsv; pa.tagmode = 1; pa.poll_delay = c.tag_poll_delay;
     pa.chunk_T = p.on ? p.chunk_T : 0; pa.nchunk = p.nchunk; pa.chunk_ready = pa.flags;       // (first word of the flag area; tickets sit 256 B further)
     const bool fuse_drop = drop_pending && c.fused_dropout;
     if (fuse_drop) {
@@ -2783,29 +2629,25 @@ static int fwd_try_persist(const FwdCall &c, bool &launched, const char *&why) {
   const int H = c.H;
   int kq = ceil_div(H, 64);
   if (kq == 7) kq = 8;
-  struct Cand { int mode, hsu, nbig, hsu_small; };
+  struct Cand { int mode, hsu; };
   Cand cands[8];
   int nc = 0;
   if (c.cell == CTCN_CELL_TANH) {
-    if (c.nxd > 1) cands[nc++] = {1, 16, 0, 0};
-    cands[nc++] = {0, 16, 0, 0};
+    if (c.nxd > 1) cands[nc++] = {1, 16};
+    cands[nc++] = {0, 16};
   } else {
     if (c.nxd > 1) {
-      // mixed slices: a 12-unit and b 4-unit workgroups, a + b = CUs of one XCD, 12 a + 4 b = H
-      const int cpx = c.cus / c.nxd, nbig = (H - 4 * cpx) / 8;
-      if (c.mixed_slices && H % 8 == 0 && (H - 4 * cpx) % 8 == 0 && nbig > 0 && nbig <= cpx && ceil_div(c.groups, c.nxd) == 1)
-        cands[nc++] = {1, 12, nbig, 4};
-      if (H % 8 == 0) cands[nc++] = {1, 8, 0, 0};
-      cands[nc++] = {1, 12, 0, 0}; cands[nc++] = {1, 16, 0, 0}; cands[nc++] = {1, 4, 0, 0};
+      if (H % 8 == 0) cands[nc++] = {1, 8};
+      cands[nc++] = {1, 12}; cands[nc++] = {1, 16}; cands[nc++] = {1, 4};
     }
-    cands[nc++] = {0, H % 8 == 0 ? 8 : 4, 0, 0};
+    cands[nc++] = {0, H % 8 == 0 ? 8 : 4};
   }
   why = kq > 8 ? "hidden size above 512" : "no candidate geometry is co-resident on this device";
   for (int ci = 0; ci < nc && kq <= 8; ++ci) {
-    const int mode = cands[ci].mode, HSU = cands[ci].hsu, nbig = cands[ci].nbig, hsu_small = cands[ci].hsu_small;
+    const int mode = cands[ci].mode, HSU = cands[ci].hsu;
     const int nx = mode ? c.nxd : 1;
     const int NT = c.cell == CTCN_CELL_TANH ? 1 : ceil_div(HSU, 4);
-    const int nsl = nbig ? nbig + (H - nbig * HSU) / hsu_small : ceil_div(H, HSU);
+    const int nsl = ceil_div(H, HSU);
     const int wpx = ceil_div(c.groups, nx) * nsl;
     const int prec = c.precision == 1 && HSU % 4 == 0 && H % 8 == 0 ? 1 : 0;       // bf16x3 recurrent matmul
     const size_t hx_bytes = align_up((size_t)2 * c.groups * (prec ? ceil_div(H, 32) * 512 : ceil_div(H, 16) * 256) * sizeof(float), 256);
@@ -2813,7 +2655,6 @@ static int fwd_try_persist(const FwdCall &c, bool &launched, const char *&why) {
     Handoff h;
     if (!carve_handoff(c.ws, c.ws_bytes, hx_bytes, fl_bytes, h)) { why = "workspace too small for the hand-off tiles"; break; }
     PersistArgs pa = persist_args(c.a, h, c.status, {mode, nx, c.groups, nsl, c.nbt, HSU, wpx});
-    pa.nbig = nbig; pa.hsu_small = hsu_small;
     CTCN_HIP(clear_handoff(h, prec != 0, c.st()));
     launched = launch_fwd_persist(prec, NT, kq, mode ? xcd_local_grid(nx, wpx) : dim3(nsl, c.dirs, c.nbt), 0, c.st(), pa, wpx);
     if (launched) {
@@ -2988,7 +2829,7 @@ struct BwdCall {
   void *prelaunch_event;      // NULL once recorded
   int nxd;                    // XCDs the XCD-local hand-off can use (1: none, or option "handoff" off)
   bool persistent, bwd_scatter, fused_dropout;
-  int handoff_tags, item_gather, rsv_nt, poll_delay, slow_items, slow_exchange;
+  int handoff_tags, item_gather, poll_delay, slow_items, slow_exchange;
   hipStream_t st() const { return (hipStream_t)stream; }
 };
 
@@ -3063,7 +2904,6 @@ static int bwd_try_persistent(BwdCall &c, const BwdPlan &p, const Handoff &h, in
   }
   record_prelaunch(c);
   if (p.gather2) {
-    pa.rsv_nt = c.rsv_nt;
     pa.poll_delay = c.poll_delay < 0 ? (nsl <= 24 ? 16 : 24) : c.poll_delay;     // auto: the exchange phase grows with the tiles per wave (cfg4: 2.69 -> 2.55 us per step)
     done = launch_bwd_scatter2(nsl, pgrid, st, pa, wpx);
     if (done) note_kernel(1, "rnn_bwd_scatter2", c.call);
@@ -3114,7 +2954,7 @@ extern "C" int ctcn_rnn_bwd_ex(int cell, int T, int B, int I, int H, int dirs, c
   c.prelaunch_event = call.prelaunch_event;
   c.nxd = ctcn_opt_handoff() ? ctcn_device_xcds() : 1;
   c.persistent = ctcn_opt_rnn_persistent() != 0; c.bwd_scatter = ctcn_opt_bwd_scatter() != 0; c.fused_dropout = ctcn_get_option("rnn_fused_dropout") != 0;
-  c.handoff_tags = ctcn_opt_handoff_tags(); c.item_gather = ctcn_get_option("bwd_item_gather"); c.rsv_nt = ctcn_get_option("rnn_rsv_nt");
+  c.handoff_tags = ctcn_opt_handoff_tags(); c.item_gather = ctcn_get_option("bwd_item_gather");
   c.poll_delay = ctcn_get_option("bwd_poll_delay"); c.slow_items = ctcn_get_option("rnn_slow_items"); c.slow_exchange = ctcn_get_option("rnn_slow_exchange");
 
   // W_hh^T of both directions, then the carried state of the per-timestep kernels, in `scratch` (ctcn_rnn_scratch_bytes)

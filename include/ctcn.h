@@ -74,8 +74,6 @@ int ctcn_device_xcds(void);
  * h_t dwords carry the step tag and the gathering waves poll the data itself) where it applies -- precision 1, LSTM / GRU, H % 32 == 0,
  * XCD-local placement; 0: the flag + data kernel (rnn_fwd_persist) everywhere.  "tag_poll_delay" = 8: 64-cycle sleeps between the
  * step barrier and a gathering wave's first poll.
- * "rnn_mixed_slices" = 0 (default): 1 = forward persistent recurrence with one workgroup per CU of an XCD and mixed 12- / 4-unit
- * slices (measured slower than 40 equal slices at H = 320; kept as an experiment switch).
  * "edit_wave" = 1 (default): ctcn_edit_distance runs one wavefront per utterance along anti-diagonals (labels up to 512 symbols);
  * 0: one lane per utterance with its DP row in LDS (also the path for longer labels).
  * "gemm_big_tiles" = 0 (default): 1 lets the bf16x3 GEMM use 256x128 / 128x256 workgroup tiles (same results, measured slower).
@@ -125,8 +123,6 @@ int ctcn_device_xcds(void);
  * LDS each).  Same results bit for bit (test_beam_generic_kernel_occupancy_options).  Measured on the kernel as it stood at the start of the
  * round's last session (cfg5, W = 200, profiles/r06_wide_beam_probe.txt): +13 % / +22 % utterances/s (peaky / flat) with twelve searches in
  * flight, -13 % with three, one batch 14 % slower -- an opt-in for offline decoding with many batches in flight, not the default.
- * "rnn_rsv_nt" = 0 (default): 1 puts the non-temporal hint on rnn_bwd_scatter2's reserve loads / stores (experiment: -15 % L2 write-backs at H = 512, no
- * change of the step).
  * "conv_dbg" = 0 (default): development only (tools/conv_phase_probe.py) -- conv_mfma_kernel skips its window load (1), MFMA loop (2) and /
  * or output phase (4); results are invalid.
  * "fwd_pipe_any_chunking" = 0 (default): the input projection is pipelined with the forward recurrence (ctcn_rnn_call.side_stream) only

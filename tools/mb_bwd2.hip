@@ -11,6 +11,7 @@ int ctcn_transpose01_pair(const float *, const float *, float *, float *, int, i
 extern "C" int ctcn_dropout(const float *, float *, size_t, float, uint64_t, uint64_t, void *) { return 0; }
 int ctcn_gemm_on_xcds(int, int, int, int, int, const float *, int, const float *, int, float *, int, float, int, void *, size_t, void *, unsigned, GemmPlanes *) { return 0; }
 int ctcn_gemm_shift_b(int, int, int, const float *, int, const float *, int, float *, int, float, int, void *, size_t, void *, unsigned, int, GemmPlanes *) { return 0; }
+extern "C" int ctcn_gemm_dx(int, int, int, const float *, int, const float *, int, float *, int, float, int, void *, size_t, void *) { return 0; }
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); return 1; } } while (0)
 
@@ -84,10 +85,12 @@ int main(int argc, char **argv) {
     }
     printf("rnn_bwd_scatter2 %d exchange waves, poll delay %2d       %6.3f us/step (status %d)\n", NEWV, delay, ms * 1e3 / T, hs);
     printf("   item wave 0   (cycles/step): delay + poll + sum %6.0f | gate math + stage %5.0f | barrier wait %5.0f | after barrier %5.0f | total %6.0f   [%.2f poll rounds per step]\n",
-           (double)h[0] / T, (double)h[1] / T, (double)h[2] / T, (double)(h[3] + h[5]) / T, (double)h[6] / T, (double)h[4] / T);
-    printf("   exchange wave, inside 'lds + mfma + scatter issue': barrier -> A fragments in registers %5.0f | chains + tags + block stores issued %5.0f\n", (double)h[16] / T, (double)h[18] / T);
+           (double)h[0] / T, (double)h[1] / T, (double)h[2] / T, (double)(h[3] + h[4] + h[5]) / T, (double)h[7] / T, (double)h[6] / T);
+    // (records of rnn.hip's Stamps::report for rnn_bwd_scatter2: gather, math, barrier, frag, chains, tail, rounds | total; item wave 0 at 0, exchange wave 4 at 16)
+    const long long *x = h + 16;
+    printf("   exchange wave, inside 'lds + mfma + scatter issue': barrier -> A fragments in registers %5.0f | chains + tags + block stores issued %5.0f\n", (double)x[3] / T, (double)x[4] / T);
     printf("   exchange wave (cycles/step): vmcnt wait %6.0f | lgkm %5.0f | barrier wait %5.0f | lds + mfma + scatter issue %5.0f | reserve store + dma issue %5.0f | total %6.0f\n",
-           (double)h[8] / T, (double)h[9] / T, (double)h[10] / T, (double)h[11] / T, (double)h[13] / T, (double)h[14] / T);
+           (double)x[0] / T, (double)x[1] / T, (double)x[2] / T, (double)(x[3] + x[4]) / T, (double)x[5] / T, (double)x[7] / T);
   }
   return 0;
 }

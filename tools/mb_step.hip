@@ -10,6 +10,7 @@ int ctcn_transpose01_pair(const float *, const float *, float *, float *, int, i
 extern "C" int ctcn_dropout(const float *, float *, size_t, float, uint64_t, uint64_t, void *) { return 0; }
 int ctcn_gemm_on_xcds(int, int, int, int, int, const float *, int, const float *, int, float *, int, float, int, void *, size_t, void *, unsigned, GemmPlanes *) { return 0; }
 int ctcn_gemm_shift_b(int, int, int, const float *, int, const float *, int, float *, int, float, int, void *, size_t, void *, unsigned, int, GemmPlanes *) { return 0; }
+extern "C" int ctcn_gemm_dx(int, int, int, const float *, int, const float *, int, float *, int, float, int, void *, size_t, void *) { return 0; }
 
 namespace {
 __global__ void empty_kernel(RnnArgs p) { if (p.T < 0) p.y[0] = 1.f; }
@@ -155,15 +156,15 @@ int main() {
     // persistent forward / backward recurrences with in-kernel phase accounting (forward), device-scope vs XCD-local
     const int nbt = 2, K = G * H;
     const size_t hx_bytes = (size_t)2 * D * nbt * 32 * 32 * 1024, fl_bytes = (size_t)2 * D * nbt * 32 * 32 * 4 + 256;
-    float *hx; unsigned *flags; int *status; long long *stats, h[16 + 64 * 3];
-    CK(hipMalloc(&hx, hx_bytes)); CK(hipMalloc(&flags, fl_bytes)); CK(hipMalloc(&status, 4)); CK(hipMalloc(&stats, sizeof(long long) * (16 + 64 * 3))); CK(hipMemset(stats, 0, sizeof(long long) * (16 + 64 * 3)));
+    float *hx; unsigned *flags; int *status; long long *stats, h[16 + 64 * 12];   // records of rnn.hip's Stamps::report: the kernel's phases in the order of its enum, total cycles, HW_ID
+    CK(hipMalloc(&hx, hx_bytes)); CK(hipMalloc(&flags, fl_bytes)); CK(hipMalloc(&status, 4)); CK(hipMalloc(&stats, sizeof(h))); CK(hipMemset(stats, 0, sizeof(h)));
     const int nx = ctcn_device_xcds();
     printf("device XCDs (even deal verified): %d\n", nx);
     struct Cfg { int local, hsu, nt, prec, pd; } cfgs[] = {{1, 8, 2, 1, 2}, {1, 12, 3, 1, 2}, {1, 16, 4, 1, 2}};   // measured besides: HSU 4 -> 2.55, HSU 10 (4-B publish pieces) -> 2.37, polls 1 / 3 / 4 -> 2.08 / 2.09 / 2.15 us
     for (auto &c : cfgs) {
       if (c.local && nx <= 1) continue;
       PersistArgs pa = {}; pa.a = a; pa.a.w0 = w; pa.a.w1 = w + (size_t)G * H * H; pa.hx = hx; pa.flags = flags; pa.status = status; pa.spin_limit = 1 << 20; pa.stats = stats;
-      pa.nbig = 0; pa.hsu_small = 0; pa.poll_delay = 0; pa.poll_depth = c.pd; pa.local = c.local; pa.nx = c.local ? nx : 1; pa.nbt = nbt; pa.hsu = c.hsu; pa.nsl = (H + c.hsu - 1) / c.hsu;
+      pa.poll_delay = 0; pa.poll_depth = c.pd; pa.local = c.local; pa.nx = c.local ? nx : 1; pa.nbt = nbt; pa.hsu = c.hsu; pa.nsl = (H + c.hsu - 1) / c.hsu;
       const int wpx = (D * nbt + pa.nx - 1) / pa.nx * pa.nsl;
       pa.wpx = wpx; pa.tickets = flags + (fl_bytes - 256) / 4;
       dim3 gp = c.local ? dim3(pa.nx * (wpx + 4), 1, 1) : dim3(pa.nsl, D, nbt);
@@ -183,24 +184,30 @@ int main() {
       float ms; hipEventElapsedTime(&ms, e0, e1);
       int hs = -1; CK(hipMemcpy(&hs, status, 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(h, stats, sizeof(h), hipMemcpyDeviceToHost));
       printf("fwd PERSISTENT local=%d HSU=%2d NT=%d precision=%d polls=%d  %3d slices/group   %8.2f us/step   (status %d)\n", c.local, c.hsu, c.nt, c.prec, c.pd, pa.nsl, ms * 1e3 / T, hs);
+      // rnn_fwd_persist: poll, fill, mm, red, sum, math, hpub, pub, drain, tail | total | HW_ID; item wave 0 of slice 7 at 0, the communication wave of slice k at 16 + 12 k
+      const long long *cw = h + 16 + 12 * 7;
+      const long long wait_math = cw[4] + cw[5] + cw[6];
       printf("  per step (cycles), slice 7, communication wave: flag poll+barrier %.0f | operand loads %.0f | mfma %.0f | reduce %.0f | gate math+publish %.0f | total %.0f\n",
-             (double)h[0] / T, (double)h[1] / T, (double)h[2] / T, (double)h[3] / T, (double)h[4] / T, (double)h[5] / T);
+             (double)cw[0] / T, (double)cw[1] / T, (double)cw[2] / T, (double)cw[3] / T, (double)(wait_math + cw[7] + cw[8] + cw[9]) / T, (double)cw[10] / T);
       if (c.local) {
         printf("    per slice: poll / rest cycles per step [se.sh.cu]:");
         for (int i = 0; i < pa.nsl; ++i) {
-          const unsigned hw = (unsigned)h[18 + i * 3];
-          printf(" %d:%.0f/%.0f[%u.%u.%u]", i, (double)h[16 + i * 3] / T, (double)h[17 + i * 3] / T, (hw >> 13) & 7, (hw >> 12) & 1, (hw >> 8) & 15);
+          const long long *r = h + 16 + 12 * i;
+          const unsigned hw = (unsigned)r[11];
+          long long rest = 0;
+          for (int k = 1; k < 10; ++k) rest += r[k];
+          printf(" %d:%.0f/%.0f[%u.%u.%u]", i, (double)r[0] / T, (double)rest / T, (hw >> 13) & 7, (hw >> 12) & 1, (hw >> 8) & 15);
         }
         printf("\n");
       }
       printf("    gate math+publish split: wait for gate math (hpub barrier) %.0f | convert + issue stores %.0f | drain %.0f | flag + tail %.0f\n",
-             (double)h[6] / T, (double)h[7] / T, (double)h[8] / T, (double)h[9] / T);
-      printf("    item wave 0: partial sums (4 x 16-B LDS reads) %.0f | gate math + split + hpub writes %.0f\n", (double)h[10] / T, (double)h[11] / T);
+             (double)wait_math / T, (double)cw[7] / T, (double)cw[8] / T, (double)cw[9] / T);
+      printf("    item wave 0: partial sums (4 x 16-B LDS reads) %.0f | gate math + split + hpub writes %.0f\n", (double)h[4] / T, (double)h[5] / T);
     }
     for (int pd : {0, 8}) {   // tagged-gather forward (round 2): 64-cycle sleeps before the first poll of a step
       if (nx <= 1) break;
       PersistArgs pa = {}; pa.a = a; pa.a.w0 = w; pa.a.w1 = w + (size_t)G * H * H; pa.hx = hx; pa.flags = flags; pa.status = status; pa.spin_limit = 1 << 20; pa.stats = stats;
-      pa.poll_depth = 1; pa.poll_delay = pd; pa.local = 1; pa.nx = nx; pa.nbt = nbt; pa.hsu = 16; pa.nbig = 0; pa.hsu_small = 0; pa.nsl = H / 16; pa.tagmode = 1;
+      pa.poll_depth = 1; pa.poll_delay = pd; pa.local = 1; pa.nx = nx; pa.nbt = nbt; pa.hsu = 16; pa.nsl = H / 16; pa.tagmode = 1;
       const int wpx = (D * nbt + pa.nx - 1) / pa.nx * pa.nsl;
       pa.wpx = wpx; pa.tickets = flags + (fl_bytes - 256) / 4;
       dim3 gp = dim3(pa.nx * (wpx + 4), 1, 1);
@@ -214,15 +221,16 @@ int main() {
       int hs = -1; CK(hipMemcpy(&hs, status, 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(h, stats, sizeof(h), hipMemcpyDeviceToHost));
       printf("fwd TAGGED GATHER poll delay=%d  %3d slices/group   %8.2f us/step   (status %d)\n", pd, pa.nsl, ms * 1e3 / T, hs);
       printf("  per step (cycles), slice 3, exchange wave 4: poll until the block is valid %.0f | perm + 12 mfma + park %.0f | barrier wait %.0f | total %.0f   [%.2f full polls per step, %.0f cycles per poll round trip]\n",
-             (double)h[0] / T, (double)h[1] / T, (double)h[2] / T, (double)h[3] / T, (double)h[5] / T, (double)h[4] / (double)(h[5] ? h[5] : 1));
+             (double)(h[0] + h[1]) / T, (double)h[2] / T, (double)h[3] / T, (double)h[9] / T, (double)h[8] / T, (double)h[1] / (double)(h[8] ? h[8] : 1));
+      // (rnn_fwd_tagged: idle, poll, mm, barrier, sum, math, pub, rsv, polls | total; exchange wave 4 of slice 3 at 0, item wave 0 at 16)
       printf("  item wave 0: wait for the barrier %.0f | 12 partial reads + sums %.0f | gate math %.0f | split + publish issue %.0f | reserve issue %.0f\n",
-             (double)h[8] / T, (double)h[9] / T, (double)h[10] / T, (double)h[11] / T, (double)h[12] / T);
+             (double)h[16 + 3] / T, (double)h[16 + 4] / T, (double)h[16 + 5] / T, (double)h[16 + 6] / T, (double)h[16 + 7] / T);
     }
     for (int lp = 0; lp < 3; ++lp) {
       const int local = 1, prec = 1, pd = 2, scatter = lp, bdelay = 0;
       if (nx <= 1) continue;
       PersistArgs pa = {}; pa.a = a; pa.a.w0 = wT; pa.a.w1 = wT + (size_t)G * H * H; pa.hx = hx; pa.flags = flags; pa.status = status; pa.spin_limit = 1 << 20; pa.stats = stats;
-      pa.poll_depth = pd; pa.poll_delay = bdelay; pa.nbig = 0; pa.hsu_small = 0; pa.local = local; pa.nx = nx; pa.nbt = nbt; pa.hsu = 16; pa.nsl = (H + 15) / 16;
+      pa.poll_depth = pd; pa.poll_delay = bdelay; pa.local = local; pa.nx = nx; pa.nbt = nbt; pa.hsu = 16; pa.nsl = (H + 15) / 16;
       const int wpx = (D * nbt + pa.nx - 1) / pa.nx * pa.nsl;
       pa.wpx = wpx; pa.tickets = flags + (fl_bytes - 256) / 4;
       dim3 gp = dim3(pa.nx * (wpx + 4), 1, 1);
@@ -238,13 +246,16 @@ int main() {
       float ms; hipEventElapsedTime(&ms, e0, e1);
       int hs = -1; CK(hipMemcpy(&hs, status, 4, hipMemcpyDeviceToHost));
       CK(hipMemcpy(h, stats, sizeof(h), hipMemcpyDeviceToHost));
-      for (int wv = 0; wv < 2; ++wv)
+      // rnn_bwd_persist: poll, mm, red, math, copy, tail | total, wave 0 at 0, wave 15 at 8;  rnn_bwd_scatter: gather, sum, math, staged, scatter, drain, tail | total, at 0 and 16
+      for (int wv = 0; wv < 2; ++wv) {
+        const long long *r = h + wv * (scatter ? 16 : 8);
+        const long long col[7] = {r[0], scatter ? 0 : r[1], scatter ? r[1] + r[2] + r[3] : r[2], scatter ? r[4] : r[3], scatter ? r[5] : r[4], scatter ? r[6] : r[5], scatter ? r[7] : r[6]};
         printf("  bwd %s per step (cycles), slice 3, %s: %s %.0f | %.0f | %.0f | %.0f | %.0f | %.0f | total %.0f\n", scatter == 2 ? "SCATTER tagged" : scatter ? "SCATTER flags" : "gather",
                wv ? "wave 15 (exchange)" : "wave 0 (items)", scatter ? "gather+park+barrier | - | item sum+math+stage+barrier | lds+mfma+scatter issue | drain+flags | reserve traffic:" : "phases:",
-               (double)h[wv * 8 + 0] / T, (double)h[wv * 8 + 1] / T, (double)h[wv * 8 + 2] / T, (double)h[wv * 8 + 3] / T,
-               (double)h[wv * 8 + 4] / T, (double)h[wv * 8 + 5] / T, (double)h[wv * 8 + 6] / T);
+               (double)col[0] / T, (double)col[1] / T, (double)col[2] / T, (double)col[3] / T, (double)col[4] / T, (double)col[5] / T, (double)col[6] / T);
+      }
       if (scatter) printf("    item wave, inside 'item sum+math+stage+barrier': partial sum (12 LDS reads) %.0f | gate math + stage writes %.0f | barrier wait %.0f\n",
-                          (double)h[16] / T, (double)h[17] / T, (double)h[18] / T);
+                          (double)h[1] / T, (double)h[2] / T, (double)h[3] / T);
       printf("bwd PERSISTENT %s delay %d  %8.2f us/step   (status %d)\n", scatter == 2 ? "scatter tagged" : scatter ? "scatter flags" : "gather", bdelay, ms * 1e3 / T, hs);
     }
   }
