@@ -102,6 +102,9 @@ _SIGS = {
     "ctcn_fbank_plan_bytes": (Z, [P]),
     "ctcn_fbank_plan": (I, [P, P, Z]),
     "ctcn_fbank": (I, [P, I, P, P, P, P, P, P, P, I, I, I, F, U, U, P]),
+    "ctcn_mfcc_plan_bytes": (Z, [P]),
+    "ctcn_mfcc_plan": (I, [P, P, Z]),
+    "ctcn_mfcc": (I, [P, I, P, P, P, P, P, P, P, I, I, I, F, U, U, P]),
     "ctcn_cmvn_accumulate_ws_bytes": (Z, [I, I, I]),
     "ctcn_cmvn_accumulate": (I, [P, P, P, I, I, I, P, Z, P]),
     "ctcn_comm_unique_id": (I, [P]),
@@ -137,6 +140,14 @@ class FbankOpts(ctypes.Structure):
                                               "high_freq", "energy_floor")] + \
                [(k, ctypes.c_int32) for k in ("window_type", "num_mel_bins", "remove_dc_offset", "round_to_power_of_two", "snip_edges",
                                               "use_energy", "raw_energy", "htk_compat", "use_log_fbank", "use_power")]
+
+
+class MfccOpts(ctypes.Structure):
+    """ctcn_mfcc_opts of include/ctcn.h: Kaldi's MFCC options (utils/features.MfccConfig fills it)."""
+    _fields_ = [(k, ctypes.c_float) for k in ("samp_freq", "frame_shift_ms", "frame_length_ms", "preemph_coeff", "blackman_coeff", "low_freq",
+                                              "high_freq", "energy_floor", "cepstral_lifter")] + \
+               [(k, ctypes.c_int32) for k in ("window_type", "num_mel_bins", "num_ceps", "remove_dc_offset", "round_to_power_of_two", "snip_edges",
+                                              "use_energy", "raw_energy", "htk_compat")]
 
 
 def sources():

@@ -1,7 +1,8 @@
 // fbank.hip -- the filterbank front-end: waveform -> (normalised) log-mel features, and the statistics of the global mean / variance
-// normalisation (ctcn_fbank_frames, ctcn_fbank_plan, ctcn_fbank, ctcn_cmvn_accumulate; contract and plan layout in include/ctcn.h).
+// normalisation (ctcn_fbank_frames, ctcn_fbank_plan, ctcn_fbank, ctcn_mfcc_plan, ctcn_mfcc, ctcn_cmvn_accumulate; contract and plan layouts in
+// include/ctcn.h).
 //
-// fbank_kernel<NPAD>: grid (frame blocks, utterances), four waves per workgroup.
+// fbank_kernel<NPAD, KIND>: grid (frame blocks, utterances), four waves per workgroup.
 //   1. The workgroup stages the plan (float64 twiddles, window, filter table, weights: 6 NPAD + 384 words) and the sample span of its `fpw` (<= 8)
 //      consecutive frames in LDS once: neighbouring frames share all but `shift` of their samples.  int16 input is converted here;
 //      snip_edges == 0 reflects indices outside the signal here.
@@ -13,6 +14,10 @@
 //      (fbank_core.h), twiddles from the plan's table; the split step writes the power spectrum of bins 0 .. NPAD/2 - 1.
 //   4. Lanes take mel filters (lane, lane + 64): a filter is a contiguous bin range, a dot product of <= ~30 terms; log, energy column,
 //      (x - mean) * scale, one coalesced row store.
+//   5. KIND_MFCC only (ctcn_mfcc; fbank_kernel<NPAD, KIND> is one body for both feature types): stage 4 leaves the log-mel vector in the wave's
+//      idle FFT buffer instead of global memory; lane k < num_ceps takes row k of the DCT (table staged bin-major behind the filter table, so
+//      consecutive lanes read consecutive words and the log-mel value is a broadcast) in ascending bin order, multiplies by the lifter,
+//      applies the energy and HTK column rules and the normalisation, and the wave stores one coalesced row of num_ceps floats.
 //   Rows of the block at or beyond the utterance's frame count are zero-filled by the whole workgroup first.
 //   Waves of a workgroup never wait for each other after the staging barrier: the FFT buffers are per wave, ordered by wave_lds_sync.
 // cmvn_partial_kernel / cmvn_finish_kernel: float64 column sums of 64-row blocks into the workspace, then one thread per statistic adds the
@@ -35,13 +40,14 @@ struct FbankArgs {
   float *feats;
   int32_t *frames;
   uint64_t seed, utt_offset;
-  int is_i16, Nmax, Tmax, L, shift, nbins, F, fpw;
+  int is_i16, Nmax, Tmax, L, shift, nbins, F, fpw;                  // F: columns of an output row (MFCC: the number of cepstra)
   int snip, remove_dc, use_energy, raw_energy, htk, use_log, use_power, has_floor;
   float preemph, log_floor, dither;
 };
 
-static inline size_t fbank_lds_words(int npad, int L, int shift, int fpw) {
-  return (size_t)22 * npad + 3 * FBANK_MAX_BINS + (size_t)(fpw - 1) * shift + L;      // 4-byte words: twiddles 4, wave buffers 16, window 1, weights 1 (x npad)
+// `extra`: the words of the plan behind the filterbank block (MFCC: DCT table and lifter), staged between the filter table and the samples
+static inline size_t fbank_lds_words(int npad, int L, int shift, int fpw, int extra) {
+  return (size_t)22 * npad + 3 * FBANK_MAX_BINS + extra + (size_t)(fpw - 1) * shift + L;      // 4-byte words: twiddles 4, wave buffers 16, window 1, weights 1 (x npad)
 }
 
 // LDS traffic between the lanes of ONE wave: drain the wave's own LDS operations and keep the compiler from moving accesses across.
@@ -60,16 +66,20 @@ __device__ __forceinline__ float fbank_gauss(uint64_t seed, uint64_t utt, int fr
   return r * ((i & 1) ? sinf(th) : cosf(th));
 }
 
-template <int NPAD>
+enum { KIND_FBANK = 0, KIND_MFCC = 1 };
+
+template <int NPAD, int KIND>
 __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
   constexpr int P = NPAD / 64, M = NPAD / 2;
+  constexpr bool MFCC = KIND == KIND_MFCC;
   extern __shared__ __align__(16) double smem_d[];
   fbc *tw = reinterpret_cast<fbc *>(smem_d);                        // NPAD complex doubles
   double *wbuf = smem_d + 2 * NPAD;                                 // 4 waves x 2 x NPAD doubles (M complex each)
   float *win = reinterpret_cast<float *>(wbuf + 8 * NPAD);          // NPAD
   float *wts = win + NPAD;                                          // NPAD
   int *ftab = reinterpret_cast<int *>(wts + NPAD);                  // first | count | weight offset, 128 each
-  float *span = wts + NPAD + 3 * FBANK_MAX_BINS;
+  float *dct = wts + NPAD + 3 * FBANK_MAX_BINS;                     // MFCC: nbins x F bin-major, then the lifter (F)
+  float *span = dct + (MFCC ? a.nbins * a.F + a.F : 0);
 
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int L = a.L, shift = a.shift, F = a.F;
@@ -93,6 +103,8 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     for (int i = tid; i < NPAD; i += 256) win[i] = a.plan[i];
     for (int i = tid; i < 3 * FBANK_MAX_BINS; i += 256) ftab[i] = reinterpret_cast<const int *>(p_tab)[i];
     for (int i = tid; i < NPAD; i += 256) wts[i] = p_tab[3 * FBANK_MAX_BINS + i];
+    if (MFCC)
+      for (int i = tid; i < a.nbins * a.F + a.F; i += 256) dct[i] = p_tab[3 * FBANK_MAX_BINS + NPAD + i];
     const long long s0 = (long long)f0 * shift + (a.snip ? 0 : shift / 2 - L / 2);
     const int span_len = (nf - 1) * shift + L;
     const size_t base = (size_t)b * a.Nmax;
@@ -107,6 +119,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
   double *bufA = wbuf + wv * 2 * NPAD, *bufB = bufA + NPAD;
   fbc *zA = reinterpret_cast<fbc *>(bufA), *zB = reinterpret_cast<fbc *>(bufB);
   float *pw = reinterpret_cast<float *>(bufA);                      // the power spectrum, once the transform has left bufA
+  float *lm = reinterpret_cast<float *>(bufB);                      // MFCC: the log-mel vector, once the split step has read bufB
   const int mel_off = (a.use_energy && !a.htk) ? 1 : 0;
   const bool norm = a.mean != nullptr;
 
@@ -185,11 +198,31 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
       float e = 0.f;
       for (int i = 0; i < cnt; ++i) e += w[i] * pw[first + i];
       if (a.use_log) e = logf(fmaxf(e, FLT_EPSILON));
+      if (MFCC) { lm[m] = e; continue; }
       const int col = m + mel_off;
       if (norm) e = (e - a.mean[col]) * a.scale[col];
       row[col] = e;
     }
-    if (a.use_energy && lane == 0) {
+    if (MFCC) {
+      // ---- 5. DCT, lifter, energy and HTK column rules: lane k owns cepstrum k ----------------------------------------------------------------
+      wave_lds_sync();                                                // stage 4's own sync above sits behind the split step's reads of bufB
+      if (lane < F) {
+        float c = 0.f;
+        for (int i = 0; i < a.nbins; ++i) c = fmaf(dct[i * F + lane], lm[i], c);      // ascending bins: a function of the frame alone
+        c = __fmul_rn(c, dct[a.nbins * F + lane]);                    // (never contracted into the normalisation's subtraction)
+        int col = lane;
+        if (lane == 0 && a.use_energy) {
+          c = logf(fmaxf(energy, FLT_EPSILON));
+          if (a.has_floor && c < a.log_floor) c = a.log_floor;
+        }
+        if (a.htk) {
+          if (lane == 0 && !a.use_energy) c = (float)((double)c * 1.41421356237309504880);
+          col = lane == 0 ? F - 1 : lane - 1;
+        }
+        if (norm) c = (c - a.mean[col]) * a.scale[col];
+        row[col] = c;
+      }
+    } else if (a.use_energy && lane == 0) {
       float le = logf(fmaxf(energy, FLT_EPSILON));
       if (a.has_floor && le < a.log_floor) le = a.log_floor;
       const int col = a.htk ? a.nbins : 0;
@@ -261,6 +294,37 @@ extern "C" int ctcn_fbank_plan(const ctcn_fbank_opts *opts, void *plan, size_t p
   return rc;
 }
 
+// The launch of either feature type: `o` are the filterbank options stages 1-4 run with, F the columns of an output row, `extra` the words of
+// the plan behind the filterbank block (KIND_MFCC: table and lifter).
+static int fbank_launch(const char *who, int kind, const ctcn_fbank_opts *o, const FbankGeom &g, int F, int extra, const void *wave, int wave_is_int16,
+                        const int32_t *lens, const void *plan, const float *mean, const float *scale, float *feats, int32_t *frames, int B, int Nmax,
+                        int Tmax, float dither, uint64_t seed, uint64_t utt_offset, void *stream) {
+  CTCN_REQUIRE(lens && plan && frames && B > 0 && Nmax >= 0 && Tmax >= 0 && (wave || Nmax == 0) && (feats || Tmax == 0), "%s: bad args", who);
+  CTCN_REQUIRE((mean == nullptr) == (scale == nullptr), "%s: mean and scale come together", who);
+  CTCN_REQUIRE(dither >= 0.f && B <= 65535, "%s: dither must not be negative, B at most 65 535 per call (B %d)", who, B);
+  int fpw = 8;
+  while (fpw > 1 && fbank_lds_words(g.npad, g.L, g.shift, fpw, extra) * 4 > FBANK_LDS_LIMIT) fpw >>= 1;
+  const size_t lds = fbank_lds_words(g.npad, g.L, g.shift, fpw, extra) * 4;
+  if (lds > FBANK_LDS_LIMIT) { ctcn_set_error("%s: frame shift %d too long for the LDS staging", who, g.shift); return CTCN_EUNSUPPORTED; }
+  FbankArgs a;
+  a.wave = wave; a.lens = lens; a.plan = static_cast<const float *>(plan); a.mean = mean; a.scale = scale; a.feats = feats; a.frames = frames;
+  a.seed = seed; a.utt_offset = utt_offset;
+  a.is_i16 = wave_is_int16 != 0; a.Nmax = Nmax; a.Tmax = Tmax; a.L = g.L; a.shift = g.shift; a.nbins = g.nbins; a.F = F; a.fpw = fpw;
+  a.snip = o->snip_edges != 0; a.remove_dc = o->remove_dc_offset != 0; a.use_energy = o->use_energy != 0; a.raw_energy = o->raw_energy != 0;
+  a.htk = o->htk_compat != 0; a.use_log = o->use_log_fbank != 0; a.use_power = o->use_power != 0;
+  a.has_floor = o->energy_floor > 0.f; a.log_floor = a.has_floor ? logf(o->energy_floor) : 0.f;
+  a.preemph = o->preemph_coeff; a.dither = dither;
+  const dim3 grid(std::max(ceil_div(Tmax, fpw), 1), B);
+  hipStream_t st = (hipStream_t)stream;
+  void (*kern)(FbankArgs);
+  if (kind == KIND_MFCC) kern = g.npad == 256 ? fbank_kernel<256, KIND_MFCC> : g.npad == 512 ? fbank_kernel<512, KIND_MFCC> : fbank_kernel<1024, KIND_MFCC>;
+  else kern = g.npad == 256 ? fbank_kernel<256, KIND_FBANK> : g.npad == 512 ? fbank_kernel<512, KIND_FBANK> : fbank_kernel<1024, KIND_FBANK>;
+  if (lds > 64 * 1024) CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
 extern "C" int ctcn_fbank(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_fbank_opts *opts, const void *plan, const float *mean,
                           const float *scale, float *feats, int32_t *frames, int B, int Nmax, int Tmax, float dither, uint64_t seed,
                           uint64_t utt_offset, void *stream) {
@@ -268,28 +332,37 @@ extern "C" int ctcn_fbank(const void *wave, int wave_is_int16, const int32_t *le
   const char *why;
   const int rc = fbank_geom(opts, &g, &why);
   if (rc != CTCN_OK) { ctcn_set_error("ctcn_fbank: %s", why); return rc; }
-  CTCN_REQUIRE(lens && plan && frames && B > 0 && Nmax >= 0 && Tmax >= 0 && (wave || Nmax == 0) && (feats || Tmax == 0), "ctcn_fbank: bad args");
-  CTCN_REQUIRE((mean == nullptr) == (scale == nullptr), "ctcn_fbank: mean and scale come together");
-  CTCN_REQUIRE(dither >= 0.f && B <= 65535, "ctcn_fbank: dither must not be negative, B at most 65 535 per call (B %d)", B);
-  int fpw = 8;
-  while (fpw > 1 && fbank_lds_words(g.npad, g.L, g.shift, fpw) * 4 > FBANK_LDS_LIMIT) fpw >>= 1;
-  const size_t lds = fbank_lds_words(g.npad, g.L, g.shift, fpw) * 4;
-  if (lds > FBANK_LDS_LIMIT) { ctcn_set_error("ctcn_fbank: frame shift %d too long for the LDS staging", g.shift); return CTCN_EUNSUPPORTED; }
-  FbankArgs a;
-  a.wave = wave; a.lens = lens; a.plan = static_cast<const float *>(plan); a.mean = mean; a.scale = scale; a.feats = feats; a.frames = frames;
-  a.seed = seed; a.utt_offset = utt_offset;
-  a.is_i16 = wave_is_int16 != 0; a.Nmax = Nmax; a.Tmax = Tmax; a.L = g.L; a.shift = g.shift; a.nbins = g.nbins; a.F = g.F; a.fpw = fpw;
-  a.snip = opts->snip_edges != 0; a.remove_dc = opts->remove_dc_offset != 0; a.use_energy = opts->use_energy != 0; a.raw_energy = opts->raw_energy != 0;
-  a.htk = opts->htk_compat != 0; a.use_log = opts->use_log_fbank != 0; a.use_power = opts->use_power != 0;
-  a.has_floor = opts->energy_floor > 0.f; a.log_floor = a.has_floor ? logf(opts->energy_floor) : 0.f;
-  a.preemph = opts->preemph_coeff; a.dither = dither;
-  const dim3 grid(std::max(ceil_div(Tmax, fpw), 1), B);
-  hipStream_t st = (hipStream_t)stream;
-  void (*kern)(FbankArgs) = g.npad == 256 ? fbank_kernel<256> : g.npad == 512 ? fbank_kernel<512> : fbank_kernel<1024>;
-  if (lds > 64 * 1024) CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
+  return fbank_launch("ctcn_fbank", KIND_FBANK, opts, g, g.F, 0, wave, wave_is_int16, lens, plan, mean, scale, feats, frames, B, Nmax, Tmax, dither, seed,
+                      utt_offset, stream);
+}
+
+extern "C" size_t ctcn_mfcc_plan_bytes(const ctcn_mfcc_opts *opts) {
+  MfccGeom g;
+  const char *why;
+  return mfcc_geom(opts, &g, &why) == CTCN_OK ? g.words * 4 : 0;
+}
+
+extern "C" int ctcn_mfcc_plan(const ctcn_mfcc_opts *opts, void *plan, size_t plan_bytes) {
+  MfccGeom g;
+  const char *why;
+  int rc = mfcc_geom(opts, &g, &why);
+  if (rc != CTCN_OK) { ctcn_set_error("ctcn_mfcc_plan: %s", why); return rc; }
+  CTCN_REQUIRE(plan && plan_bytes >= g.words * 4, "ctcn_mfcc_plan: buffer of %zu bytes needed", g.words * 4);
+  rc = mfcc_build_plan(opts, g, plan, &why);
+  if (rc != CTCN_OK) ctcn_set_error("ctcn_mfcc_plan: %s", why);
+  return rc;
+}
+
+extern "C" int ctcn_mfcc(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_mfcc_opts *opts, const void *plan, const float *mean,
+                         const float *scale, float *feats, int32_t *frames, int B, int Nmax, int Tmax, float dither, uint64_t seed,
+                         uint64_t utt_offset, void *stream) {
+  MfccGeom g;
+  const char *why;
+  const int rc = mfcc_geom(opts, &g, &why);
+  if (rc != CTCN_OK) { ctcn_set_error("ctcn_mfcc: %s", why); return rc; }
+  const ctcn_fbank_opts f = mfcc_fbank_opts(opts);
+  return fbank_launch("ctcn_mfcc", KIND_MFCC, &f, g.fb, g.nceps, g.fb.nbins * g.nceps + g.nceps, wave, wave_is_int16, lens, plan, mean, scale, feats, frames,
+                      B, Nmax, Tmax, dither, seed, utt_offset, stream);
 }
 
 extern "C" size_t ctcn_cmvn_accumulate_ws_bytes(int B, int Tmax, int F) {

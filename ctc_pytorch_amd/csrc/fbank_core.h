@@ -1,5 +1,6 @@
 // fbank_core.h -- the parts of the filterbank front-end (fbank.hip) that are plain arithmetic on the options or on one frame: the geometry of a
-// configuration, the host-side plan builder and the FFT butterflies.  Everything here compiles for the host too, so the plan builder and the
+// configuration, the host-side plan builder (filterbank, and the MFCC's DCT table and lifter behind it) and the FFT butterflies.  Everything here
+// compiles for the host too, so the plan builders and the
 // FFT passes can be exercised by a stand-alone host program (one loop over the 64 "lanes" per pass stands in for the wave).
 #pragma once
 #include <float.h>
@@ -117,6 +118,62 @@ inline int fbank_build_plan(const ctcn_fbank_opts *o, const FbankGeom &g, void *
     iw[g.off_woff + b] = used - (last - first + 1);
     if (o->htk_compat && b == 0 && low != 0.0) w[g.off_wts + iw[g.off_woff + b]] = 0.f;    // HTK's first-bin quirk, as Kaldi's htk_mode replicates it
   }
+  return CTCN_OK;
+}
+
+// ---- MFCC: the filterbank plan of the same frame and mel options, then the DCT table and the lifter ------------------------------------------------
+constexpr int MFCC_MAX_CEPS = 64;                      // one lane per coefficient; a 128 x 64 table is 32 KB of LDS
+
+struct MfccGeom {
+  FbankGeom fb;                                        // fb.F is the filterbank's; the MFCC row has nceps columns
+  int nceps, off_dct, off_lift;
+  size_t words;
+};
+
+// The filterbank options an MFCC configuration runs stages 1-4 with: log of the mel-filtered power spectrum, always.
+inline ctcn_fbank_opts mfcc_fbank_opts(const ctcn_mfcc_opts *o) {
+  ctcn_fbank_opts f;
+  memset(&f, 0, sizeof f);
+  f.samp_freq = o->samp_freq; f.frame_shift_ms = o->frame_shift_ms; f.frame_length_ms = o->frame_length_ms; f.preemph_coeff = o->preemph_coeff;
+  f.blackman_coeff = o->blackman_coeff; f.low_freq = o->low_freq; f.high_freq = o->high_freq; f.energy_floor = o->energy_floor;
+  f.window_type = o->window_type; f.num_mel_bins = o->num_mel_bins; f.remove_dc_offset = o->remove_dc_offset;
+  f.round_to_power_of_two = o->round_to_power_of_two; f.snip_edges = o->snip_edges; f.use_energy = o->use_energy; f.raw_energy = o->raw_energy;
+  f.htk_compat = o->htk_compat; f.use_log_fbank = 1; f.use_power = 1;
+  return f;
+}
+
+// As fbank_geom: every refusal of the filterbank geometry first, then the MFCC's own.
+inline int mfcc_geom(const ctcn_mfcc_opts *o, MfccGeom *g, const char **why) {
+  *why = "";
+  if (!o) { *why = "null options"; return CTCN_EINVAL; }
+  const ctcn_fbank_opts f = mfcc_fbank_opts(o);
+  const int rc = fbank_geom(&f, &g->fb, why);
+  if (rc != CTCN_OK) return rc;
+  if (o->num_ceps < 1 || o->num_ceps > o->num_mel_bins) { *why = "num_ceps outside [1, num_mel_bins]"; return CTCN_EINVAL; }
+  if (!(o->cepstral_lifter >= 0.f)) { *why = "negative cepstral lifter"; return CTCN_EINVAL; }
+  if (o->num_ceps > MFCC_MAX_CEPS) { *why = "more than 64 cepstral coefficients are not supported"; return CTCN_EUNSUPPORTED; }
+  g->nceps = o->num_ceps;
+  g->off_dct = (int)g->fb.words;
+  g->off_lift = g->off_dct + g->fb.nbins * g->nceps;
+  g->words = (size_t)g->off_lift + g->nceps;
+  return CTCN_OK;
+}
+
+// Fills `plan` (g.words words): the filterbank block, then the first nceps rows of Kaldi's ComputeDctMatrix stored bin-major (D[n * nceps + k]:
+// lanes that own consecutive cepstra read consecutive words), then the lifter 1 + Q/2 sin(pi k / Q) (ones for Q = 0).  Double, rounded once.
+inline int mfcc_build_plan(const ctcn_mfcc_opts *o, const MfccGeom &g, void *plan, const char **why) {
+  const double pi = 3.14159265358979323846;
+  const ctcn_fbank_opts f = mfcc_fbank_opts(o);
+  const int rc = fbank_build_plan(&f, g.fb, plan, why);
+  if (rc != CTCN_OK) return rc;
+  float *w = (float *)plan;
+  const int N = g.fb.nbins, C = g.nceps;
+  for (int n = 0; n < N; ++n) {
+    w[g.off_dct + n * C] = (float)sqrt(1.0 / N);
+    for (int k = 1; k < C; ++k) w[g.off_dct + n * C + k] = (float)(sqrt(2.0 / N) * cos(pi / N * (n + 0.5) * k));
+  }
+  const double Q = (double)o->cepstral_lifter;
+  for (int k = 0; k < C; ++k) w[g.off_lift + k] = Q != 0.0 ? (float)(1.0 + 0.5 * Q * sin(pi * k / Q)) : 1.f;
   return CTCN_OK;
 }
 

@@ -1871,21 +1871,25 @@ class FbankPlan(object):
     """The plan of one filterbank configuration (ctcn_fbank_plan: window, twiddles, mel filters): built on the host from an _lib.FbankOpts when
     the object is made -- a RuntimeError here, before any launch, for a configuration the kernel does not take -- and uploaded once per
     device on first use.  `host` is the block as uint32 words (layout in include/ctcn.h)."""
+    _name = "fbank"                                                    # ctcn_<name>_plan_bytes, ctcn_<name>_plan, ctcn_<name>
 
     def __init__(self, opts):
         L = _lib.lib()
         self.opts = opts
-        nbytes = L.ctcn_fbank_plan_bytes(ctypes.byref(opts))
+        nbytes = getattr(L, "ctcn_%s_plan_bytes" % self._name)(ctypes.byref(opts))
         buf = np.zeros(max(nbytes // 4, 1), dtype=np.uint32)
-        _lib.check(L.ctcn_fbank_plan(ctypes.byref(opts), buf.ctypes.data_as(ctypes.c_void_p), nbytes), "fbank_plan")
+        _lib.check(getattr(L, "ctcn_%s_plan" % self._name)(ctypes.byref(opts), buf.ctypes.data_as(ctypes.c_void_p), nbytes), "%s_plan" % self._name)
         self.host = buf
         self.frame_length = int(float(opts.samp_freq) * 0.001 * float(opts.frame_length_ms))
         self.frame_shift = int(float(opts.samp_freq) * 0.001 * float(opts.frame_shift_ms))
         self.padded_length = 1 << (self.frame_length - 1).bit_length()
         self.num_mel_bins = int(opts.num_mel_bins)
-        self.feat_dim = self.num_mel_bins + (1 if opts.use_energy else 0)
+        self.feat_dim = self._feat_dim(opts)
         self.snip_edges = bool(opts.snip_edges)
         self._dev = {}
+
+    def _feat_dim(self, opts):
+        return int(opts.num_mel_bins) + (1 if opts.use_energy else 0)
 
     def num_frames(self, num_samples):
         return fbank_frames(num_samples, self.frame_length, self.frame_shift, self.snip_edges)
@@ -1898,6 +1902,48 @@ class FbankPlan(object):
         return t
 
 
+class MfccPlan(FbankPlan):
+    """The plan of one MFCC configuration (ctcn_mfcc_plan, from an _lib.MfccOpts): the filterbank plan of the same frame and mel options,
+    then the DCT table (bin-major) and the lifter.  feat_dim = num_ceps."""
+    _name = "mfcc"
+
+    def _feat_dim(self, opts):
+        self.num_ceps = int(opts.num_ceps)
+        return self.num_ceps
+
+
+def _frontend(name, wave, lengths, plan, mean, scale, dither, seed, utt_offset):
+    """The body of fbank and mfcc: validation, output allocation, ctcn_<name>."""
+    if wave.dim() != 2:
+        raise ValueError("ctc_pytorch_amd.%s: expected wave (B, Nmax), got %s" % (name, tuple(wave.shape)))
+    _need_gpu(wave, mean, scale)
+    if wave.dtype not in (torch.float32, torch.int16):
+        raise TypeError("ctc_pytorch_amd.%s: expected float32 or int16 samples, got %s" % (name, wave.dtype))
+    if (mean is None) != (scale is None):
+        raise ValueError("ctc_pytorch_amd.%s: mean and scale come together" % name)
+    B, Nmax = wave.shape
+    host_lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(host_lens) != B or B == 0:
+        raise ValueError("ctc_pytorch_amd.%s: %d lengths for a batch of %d" % (name, len(host_lens), B))
+    if not float(dither) >= 0.0:
+        raise ValueError("ctc_pytorch_amd.%s: dither must not be negative, got %r" % (name, dither))
+    dev, F = wave.device, plan.feat_dim
+    wave = wave.contiguous()
+    for v in (mean, scale):
+        if v is not None and (v.dtype != torch.float32 or v.numel() != F):
+            raise ValueError("ctc_pytorch_amd.%s: mean / scale must hold %d float32 values" % (name, F))
+    mean, scale = (None, None) if mean is None else (mean.contiguous(), scale.contiguous())
+    Tmax = max(plan.num_frames(min(max(n, 0), Nmax)) for n in host_lens)
+    lens = torch.as_tensor(host_lens, dtype=torch.int32).to(dev)
+    feats = torch.empty((B, Tmax, F), dtype=torch.float32, device=dev)
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    entry = getattr(_lib.lib(), "ctcn_" + name)
+    _lib.check(entry(_ptr(wave), int(wave.dtype == torch.int16), _ptr(lens), ctypes.byref(plan.opts), _ptr(plan.on(dev)), _ptr(mean), _ptr(scale),
+                     _ptr(feats) if Tmax else None, _ptr(frames), B, Nmax, Tmax, float(dither), int(seed) & (2 ** 64 - 1), int(utt_offset),
+                     _lib.stream_ptr()), name)
+    return feats, frames
+
+
 def fbank(wave, lengths, plan, mean=None, scale=None, dither=0.0, seed=0, utt_offset=0):
     """Filterbank features of a padded batch of waveforms (ctcn_fbank; the computation, step by step, in include/ctcn.h): wave (B, Nmax)
     float32 on Kaldi's scale (the int16 range) or int16; lengths (B) samples, a list or a tensor (read on the host: the frame counts size
@@ -1905,33 +1951,17 @@ def fbank(wave, lengths, plan, mean=None, scale=None, dither=0.0, seed=0, utt_of
     Returns (feats (B, Tmax, F) float32, frames (B) int32) with Tmax = the largest frame count; rows from frames[b] on are zero.  dither > 0
     adds dither * N(0, 1) per extracted sample, a function of (seed, b + utt_offset, frame, sample) alone.  No autograd; device tensors only
     (no CPU fallback)."""
-    if wave.dim() != 2:
-        raise ValueError("ctc_pytorch_amd.fbank: expected wave (B, Nmax), got %s" % (tuple(wave.shape),))
-    _need_gpu(wave, mean, scale)
-    if wave.dtype not in (torch.float32, torch.int16):
-        raise TypeError("ctc_pytorch_amd.fbank: expected float32 or int16 samples, got %s" % wave.dtype)
-    if (mean is None) != (scale is None):
-        raise ValueError("ctc_pytorch_amd.fbank: mean and scale come together")
-    B, Nmax = wave.shape
-    host_lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-    if len(host_lens) != B or B == 0:
-        raise ValueError("ctc_pytorch_amd.fbank: %d lengths for a batch of %d" % (len(host_lens), B))
-    if not float(dither) >= 0.0:
-        raise ValueError("ctc_pytorch_amd.fbank: dither must not be negative, got %r" % (dither,))
-    dev, F = wave.device, plan.feat_dim
-    wave = wave.contiguous()
-    for v in (mean, scale):
-        if v is not None and (v.dtype != torch.float32 or v.numel() != F):
-            raise ValueError("ctc_pytorch_amd.fbank: mean / scale must hold %d float32 values" % F)
-    mean, scale = (None, None) if mean is None else (mean.contiguous(), scale.contiguous())
-    Tmax = max(plan.num_frames(min(max(n, 0), Nmax)) for n in host_lens)
-    lens = torch.as_tensor(host_lens, dtype=torch.int32).to(dev)
-    feats = torch.empty((B, Tmax, F), dtype=torch.float32, device=dev)
-    frames = torch.empty(B, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().ctcn_fbank(_ptr(wave), int(wave.dtype == torch.int16), _ptr(lens), ctypes.byref(plan.opts), _ptr(plan.on(dev)),
-                                     _ptr(mean), _ptr(scale), _ptr(feats) if Tmax else None, _ptr(frames), B, Nmax, Tmax, float(dither),
-                                     int(seed) & (2 ** 64 - 1), int(utt_offset), _lib.stream_ptr()), "fbank")
-    return feats, frames
+    if not isinstance(plan, FbankPlan) or isinstance(plan, MfccPlan):
+        raise TypeError("ctc_pytorch_amd.fbank: expected a FbankPlan, got %s" % type(plan).__name__)
+    return _frontend("fbank", wave, lengths, plan, mean, scale, dither, seed, utt_offset)
+
+
+def mfcc(wave, lengths, plan, mean=None, scale=None, dither=0.0, seed=0, utt_offset=0):
+    """MFCCs of a padded batch of waveforms (ctcn_mfcc: the filterbank kernel with the DCT, the lifter and Kaldi's column rules behind its
+    log-mel stage; include/ctcn.h).  The contract of fbank with plan a MfccPlan and F = num_ceps."""
+    if not isinstance(plan, MfccPlan):
+        raise TypeError("ctc_pytorch_amd.mfcc: expected a MfccPlan, got %s" % type(plan).__name__)
+    return _frontend("mfcc", wave, lengths, plan, mean, scale, dither, seed, utt_offset)
 
 
 def cmvn_accumulate(feats, frames, stats):

@@ -1,13 +1,14 @@
 """Audio -> feature archive on the device: the counterpart of the reference's timit/steps/make_feat.sh, whose three Kaldi binaries
 (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true with one global mean and variance) become
-utils/features.Fbank and GlobalCMVN.
+utils/features.Fbank and GlobalCMVN.  --feat-type mfcc is the recipe's feat_type=mfcc: compute-mfcc-feats --config=conf/mfcc.conf becomes
+utils/features.Mfcc.
 
-    make_feat.py --conf fbank.conf --wav-scp train/wav.scp --out-dir DIR [--cmvn-stats FILE] [--compute-cmvn]
+    make_feat.py --conf fbank.conf --wav-scp train/wav.scp --out-dir DIR [--cmvn-stats FILE] [--compute-cmvn] [--feat-type {fbank,mfcc}]
 
 wav.scp: one `<utterance> <path>` per line (RIFF PCM-16 mono or uncompressed SPHERE; piped commands are not run).  Writes DIR/feats.ark and
 DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDataset and both drivers read them unchanged.
   --compute-cmvn   two passes: the first accumulates the global statistics on the device and writes them as Kaldi's text matrix
-                   (--cmvn-stats, default DIR/global_fbank_cmvn.txt), the second writes features normalised with them (in the kernel)
+                   (--cmvn-stats, default DIR/global_<feat type>_cmvn.txt), the second writes features normalised with them (in the kernel)
   --cmvn-stats     without --compute-cmvn: statistics to apply (the training set's, for dev and test data); none: raw features
 Utterances are sorted by length and batched under --max-samples padded samples per launch.  Dither is the conf file's (Kaldi's default is
 1.0; `--dither=0` in the conf switches it off), keyed by --seed and the utterance's place in the length-sorted list."""
@@ -23,7 +24,9 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from ctc_pytorch_amd.utils.data_loader import write_kaldi_ark  # noqa: E402
-from ctc_pytorch_amd.utils.features import Fbank, FbankConfig, GlobalCMVN, read_wave  # noqa: E402
+from ctc_pytorch_amd.utils.features import Fbank, FbankConfig, GlobalCMVN, Mfcc, MfccConfig, read_wave  # noqa: E402
+
+FEAT_TYPES = {"fbank": (FbankConfig, Fbank), "mfcc": (MfccConfig, Mfcc)}
 
 
 def read_wav_scp(path):
@@ -72,6 +75,7 @@ def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=Non
 def main(argv=None, log=print):
     ap = argparse.ArgumentParser(description="waveforms -> (normalised) filterbank features as a Kaldi archive, computed on the MI355X")
     ap.add_argument("--conf", required=True, help="Kaldi fbank config file (--key=value lines), e.g. the reference's conf/fbank.conf")
+    ap.add_argument("--feat-type", choices=sorted(FEAT_TYPES), default="fbank", help="mfcc: --conf is read as an MFCC config (conf/mfcc.conf)")
     ap.add_argument("--wav-scp", required=True, help="list of '<utterance> <wav or sphere path>'")
     ap.add_argument("--out-dir", required=True, help="where feats.ark / feats.scp go")
     ap.add_argument("--cmvn-stats", default=None, help="Kaldi text CMVN statistics to apply (with --compute-cmvn: where to write them)")
@@ -81,9 +85,10 @@ def main(argv=None, log=print):
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
 
-    config = FbankConfig.from_kaldi_conf(args.conf)
+    config_type, frontend_type = FEAT_TYPES[args.feat_type]
+    config = config_type.from_kaldi_conf(args.conf)
     device = torch.device(args.device)
-    fbank = Fbank(config, device)
+    fbank = frontend_type(config, device)
     entries = read_wav_scp(args.wav_scp)
     if not entries:
         raise ValueError("%s: no utterances" % args.wav_scp)
@@ -100,7 +105,7 @@ def main(argv=None, log=print):
     if args.compute_cmvn:
         cmvn = GlobalCMVN(fbank.feat_dim, device)
         make_features(fbank, waves, batches, seed=args.seed, cmvn=cmvn)
-        stats_path = args.cmvn_stats or os.path.join(args.out_dir, "global_fbank_cmvn.txt")
+        stats_path = args.cmvn_stats or os.path.join(args.out_dir, "global_%s_cmvn.txt" % args.feat_type)
         cmvn.save_kaldi_text(stats_path)
         log("wrote CMVN statistics of %d frames to %s" % (int(cmvn.stats[0, -1].item()), stats_path))
         mean, scale = cmvn.mean_scale(device)

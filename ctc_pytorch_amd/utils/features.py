@@ -4,10 +4,12 @@ binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --conf
 
   FbankConfig   Kaldi's option names and defaults; from_kaldi_conf reads a `--key=value` file such as the reference's conf/fbank.conf
   Fbank         the configured front-end on one device (ops.fbank behind it; holds the uploaded plan)
+  MfccConfig    the same for compute-mfcc-feats (the recipe's feat_type=mfcc, conf/mfcc.conf): Kaldi's MFCC defaults, use_energy = true
+  Mfcc          the MFCC front-end (ops.mfcc: the same kernel with the DCT, the lifter and Kaldi's column rules behind its log-mel stage)
   GlobalCMVN    Kaldi's 2 x (F + 1) statistics, accumulated on the device (ops.cmvn_accumulate), its text file, mean and 1 / stddev
   read_wave     RIFF PCM-16 mono and uncompressed NIST SPHERE (TIMIT's) -> int16 samples
 
-Not here: MFCC, pitch, VTLN, deltas, resampling, per-speaker CMVN, compressed SPHERE."""
+Not here: pitch, VTLN, deltas, resampling, per-speaker CMVN, compressed SPHERE."""
 import struct
 
 import numpy as np
@@ -18,22 +20,20 @@ from .. import _lib, ops
 WINDOW_TYPES = ("hamming", "hanning", "povey", "rectangular", "blackman")     # the order of ctcn_fbank_opts.window_type
 
 
-class FbankConfig(object):
-    """The options of Kaldi's compute-fbank-feats that the kernel implements, under Kaldi's names (dashes as underscores) and with Kaldi's
-    defaults -- dither = 1.0 among them: pass dither=0 for a deterministic front-end."""
-    DEFAULTS = dict(sample_frequency=16000.0, frame_shift=10.0, frame_length=25.0, dither=1.0, preemphasis_coefficient=0.97,
-                    remove_dc_offset=True, window_type="povey", round_to_power_of_two=True, blackman_coeff=0.42, snip_edges=True,
-                    num_mel_bins=23, low_freq=20.0, high_freq=0.0, use_energy=False, energy_floor=0.0, raw_energy=True, htk_compat=False,
-                    use_log_fbank=True, use_power=True)
+class _KaldiConfig(object):
+    """What FbankConfig and MfccConfig share: options under Kaldi's names (dashes as underscores) held as attributes, converted to the types
+    of the class's DEFAULTS, and the reader of Kaldi's `--key=value` files."""
+    DEFAULTS = {}
 
     def __init__(self, **kw):
+        name = type(self).__name__
         for k in kw:
             if k not in self.DEFAULTS:
-                raise ValueError("FbankConfig: unknown option %r" % k)
+                raise ValueError("%s: unknown option %r" % (name, k))
         for k, d in self.DEFAULTS.items():
             setattr(self, k, self._convert(k, kw.get(k, d)))
         if self.window_type not in WINDOW_TYPES:
-            raise ValueError("FbankConfig: unknown window type %r (one of %s)" % (self.window_type, ", ".join(WINDOW_TYPES)))
+            raise ValueError("%s: unknown window type %r (one of %s)" % (name, self.window_type, ", ".join(WINDOW_TYPES)))
 
     @classmethod
     def _convert(cls, key, value):
@@ -41,7 +41,7 @@ class FbankConfig(object):
         if isinstance(d, bool):
             if isinstance(value, str):
                 if value.lower() not in ("true", "false", "t", "f", "1", "0"):
-                    raise ValueError("FbankConfig: %s expects true or false, got %r" % (key, value))
+                    raise ValueError("%s: %s expects true or false, got %r" % (cls.__name__, key, value))
                 return value.lower() in ("true", "t", "1")
             return bool(value)
         return type(d)(value)
@@ -65,27 +65,59 @@ class FbankConfig(object):
                 kw[key] = value.strip() if _ else "true"
         return cls(**kw)
 
+    def _frame_mel_opts(self):
+        """The fields ctcn_fbank_opts and ctcn_mfcc_opts have in common."""
+        return dict(samp_freq=self.sample_frequency, frame_shift_ms=self.frame_shift, frame_length_ms=self.frame_length,
+                    preemph_coeff=self.preemphasis_coefficient, blackman_coeff=self.blackman_coeff, low_freq=self.low_freq,
+                    high_freq=self.high_freq, energy_floor=self.energy_floor, window_type=WINDOW_TYPES.index(self.window_type),
+                    num_mel_bins=self.num_mel_bins, remove_dc_offset=self.remove_dc_offset,
+                    round_to_power_of_two=self.round_to_power_of_two, snip_edges=self.snip_edges, use_energy=self.use_energy,
+                    raw_energy=self.raw_energy, htk_compat=self.htk_compat)
+
+
+class FbankConfig(_KaldiConfig):
+    """The options of Kaldi's compute-fbank-feats that the kernel implements, under Kaldi's names (dashes as underscores) and with Kaldi's
+    defaults -- dither = 1.0 among them: pass dither=0 for a deterministic front-end."""
+    DEFAULTS = dict(sample_frequency=16000.0, frame_shift=10.0, frame_length=25.0, dither=1.0, preemphasis_coefficient=0.97,
+                    remove_dc_offset=True, window_type="povey", round_to_power_of_two=True, blackman_coeff=0.42, snip_edges=True,
+                    num_mel_bins=23, low_freq=20.0, high_freq=0.0, use_energy=False, energy_floor=0.0, raw_energy=True, htk_compat=False,
+                    use_log_fbank=True, use_power=True)
+
     @property
     def feat_dim(self):
         return self.num_mel_bins + (1 if self.use_energy else 0)
 
     def c_opts(self):
-        return _lib.FbankOpts(samp_freq=self.sample_frequency, frame_shift_ms=self.frame_shift, frame_length_ms=self.frame_length,
-                              preemph_coeff=self.preemphasis_coefficient, blackman_coeff=self.blackman_coeff, low_freq=self.low_freq,
-                              high_freq=self.high_freq, energy_floor=self.energy_floor, window_type=WINDOW_TYPES.index(self.window_type),
-                              num_mel_bins=self.num_mel_bins, remove_dc_offset=self.remove_dc_offset,
-                              round_to_power_of_two=self.round_to_power_of_two, snip_edges=self.snip_edges, use_energy=self.use_energy,
-                              raw_energy=self.raw_energy, htk_compat=self.htk_compat, use_log_fbank=self.use_log_fbank, use_power=self.use_power)
+        return _lib.FbankOpts(use_log_fbank=self.use_log_fbank, use_power=self.use_power, **self._frame_mel_opts())
 
 
-class Fbank(object):
-    """The front-end of one configuration on one device.  Building it builds the plan: a configuration outside the kernel's range (a padded
-    frame other than 256 / 512 / 1024 samples, more than 128 mel bins, round_to_power_of_two=false) raises RuntimeError here."""
+class MfccConfig(_KaldiConfig):
+    """The options of Kaldi's compute-mfcc-feats, under Kaldi's names and with Kaldi's MFCC defaults: use_energy is TRUE here (the
+    reference's conf/mfcc.conf switches it off), and there is no use_log_fbank / use_power -- an MFCC is always taken from the log of the
+    mel-filtered power spectrum, and those keys are unknown options."""
+    DEFAULTS = dict(sample_frequency=16000.0, frame_shift=10.0, frame_length=25.0, dither=1.0, preemphasis_coefficient=0.97,
+                    remove_dc_offset=True, window_type="povey", round_to_power_of_two=True, blackman_coeff=0.42, snip_edges=True,
+                    num_mel_bins=23, low_freq=20.0, high_freq=0.0, num_ceps=13, use_energy=True, energy_floor=0.0, raw_energy=True,
+                    cepstral_lifter=22.0, htk_compat=False)
+
+    @property
+    def feat_dim(self):
+        return self.num_ceps
+
+    def c_opts(self):
+        return _lib.MfccOpts(num_ceps=self.num_ceps, cepstral_lifter=self.cepstral_lifter, **self._frame_mel_opts())
+
+
+class _FrontEnd(object):
+    """A configured front-end on one device: the plan (built here, so a configuration outside the kernel's range raises RuntimeError here)
+    and the call that batches waveforms for the kernel.  Subclasses name the plan type and the op."""
+    _plan_type = None
+    _op = None
 
     def __init__(self, config, device):
         self.config = config
         self.device = torch.device(device)
-        self.plan = ops.FbankPlan(config.c_opts())
+        self.plan = self._plan_type(config.c_opts())
         self.feat_dim = self.plan.feat_dim
 
     def num_frames(self, num_samples):
@@ -98,7 +130,7 @@ class Fbank(object):
         if lengths is None:
             arrs = [w.cpu().numpy() if torch.is_tensor(w) else np.asarray(w) for w in waves]
             if not arrs or any(a.ndim != 1 for a in arrs):
-                raise ValueError("Fbank: expected a non-empty list of 1-D waveforms")
+                raise ValueError("%s: expected a non-empty list of 1-D waveforms" % type(self).__name__)
             lengths = [a.shape[0] for a in arrs]
             batch = np.zeros((len(arrs), max(max(lengths), 1)), dtype=np.int16 if all(a.dtype == np.int16 for a in arrs) else np.float32)
             for b, a in enumerate(arrs):
@@ -109,8 +141,22 @@ class Fbank(object):
         if waves.dtype not in (torch.int16, torch.float32):
             waves = waves.to(torch.float32)
         vec = lambda v: None if v is None else torch.as_tensor(v, dtype=torch.float32).to(self.device)
-        return ops.fbank(waves.to(self.device), lengths, self.plan, mean=vec(mean), scale=vec(scale), dither=self.config.dither, seed=seed,
-                         utt_offset=utt_offset)
+        return type(self)._op(waves.to(self.device), lengths, self.plan, mean=vec(mean), scale=vec(scale), dither=self.config.dither, seed=seed,
+                              utt_offset=utt_offset)
+
+
+class Fbank(_FrontEnd):
+    """The filterbank front-end of one FbankConfig on one device.  Building it builds the plan: a configuration outside the kernel's range (a
+    padded frame other than 256 / 512 / 1024 samples, more than 128 mel bins, round_to_power_of_two=false) raises RuntimeError here."""
+    _plan_type = ops.FbankPlan
+    _op = staticmethod(ops.fbank)
+
+
+class Mfcc(_FrontEnd):
+    """The MFCC front-end of one MfccConfig on one device: Fbank's call signature and return layout with F = num_ceps.  Beyond Fbank's
+    limits, num_ceps outside [1, num_mel_bins], more than 64 cepstra or a negative lifter raise RuntimeError here."""
+    _plan_type = ops.MfccPlan
+    _op = staticmethod(ops.mfcc)
 
 
 class GlobalCMVN(object):

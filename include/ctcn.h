@@ -576,7 +576,7 @@ int ctcn_step_stats(const float *loss, const int32_t *dist, const int64_t *tgt_l
  * binaries of timit/steps/make_feat.sh (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true).
  * The computation is Kaldi's, as its feature-window, feature-fbank and mel-computations sources document it; option names and defaults are
  * Kaldi's.  window_type: 0 hamming, 1 hanning, 2 povey (Kaldi's default), 3 rectangular, 4 blackman.  high_freq <= 0 is an offset from Nyquist.
- * Not here: MFCC, VTLN, deltas, resampling.  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
+ * Not here: VTLN, deltas, resampling (MFCC: ctcn_mfcc below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
  * defaults). */
 typedef struct ctcn_fbank_opts {
   float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff, blackman_coeff, low_freq, high_freq, energy_floor;
@@ -623,6 +623,34 @@ int ctcn_fbank(const void *wave, int wave_is_int16, const int32_t *lens, const c
 size_t ctcn_cmvn_accumulate_ws_bytes(int B, int Tmax, int F);
 int ctcn_cmvn_accumulate(const float *feats, const int32_t *frames, double *stats, int B, int Tmax, int F, void *ws, size_t ws_bytes,
                          void *stream);
+/* MFCC, the recipe's second feature type (feat_type=mfcc: compute-mfcc-feats --config=conf/mfcc.conf), by the same kernel: Kaldi's
+ * feature-mfcc.  The options are Kaldi's MfccOptions under the filterbank's field names plus num_ceps and cepstral_lifter; Kaldi's MFCC
+ * defaults differ from the filterbank's in use_energy = true (and num_mel_bins = 23, num_ceps = 13, cepstral_lifter = 22).  There is no
+ * use_log_fbank / use_power: an MFCC is always taken from the log of the mel-filtered power spectrum.  Zero-initialise and fill every field
+ * (utils/features.MfccConfig holds the defaults).  Per frame, N = num_mel_bins, C = num_ceps, Q = cepstral_lifter:
+ *   1. log-mel energies m[0..N) and the log energy e exactly as ctcn_fbank computes them with use_power, use_log_fbank (the same code);
+ *   2. c[k] = sum_n D[k][n] m[n], k < C, summed in ascending n with one fused multiply-add per term: D[0][n] = sqrt(1 / N),
+ *      D[k][n] = sqrt(2 / N) cos(pi / N (n + 0.5) k) -- the first C rows of Kaldi's ComputeDctMatrix;
+ *   3. c[k] *= 1 + Q / 2 sin(pi k / Q), a float32 multiplication of its own (Q = 0: no lifter);
+ *   4. use_energy: e is raised to log(energy_floor) where energy_floor > 0, and c[0] = e;
+ *   5. htk_compat: c[0] goes to column C - 1 and the others move down by one; without use_energy it is multiplied by sqrt(2) first (in
+ *      double, rounded once, as Kaldi's `*= M_SQRT2` does);
+ *   6. (x - mean[col]) * scale[col] on the final columns, as ctcn_fbank.
+ * The plan: the filterbank plan of the same frame and mel options, bit for bit, in words [0, 6 Npad + 384); then
+ *   [6 Npad + 384, + N C)  float  the DCT table, bin-major: D[k][n] at word n C + k (lanes owning consecutive cepstra read consecutive words)
+ *   [.. + N C, + C)        float  the lifter (ones for Q = 0)
+ * both computed in double and rounded once.  Limits beyond the filterbank's (which all carry over): 1 <= num_ceps <= num_mel_bins and
+ * cepstral_lifter >= 0, else CTCN_EINVAL; num_ceps <= 64, else CTCN_EUNSUPPORTED (one lane per coefficient; the table stays within 32 KB
+ * of LDS).  ctcn_mfcc takes ctcn_fbank's arguments with feats (B, Tmax, C) and mean / scale of C floats; frame counts: ctcn_fbank_frames. */
+typedef struct ctcn_mfcc_opts {
+  float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff, blackman_coeff, low_freq, high_freq, energy_floor, cepstral_lifter;
+  int32_t window_type, num_mel_bins, num_ceps, remove_dc_offset, round_to_power_of_two, snip_edges, use_energy, raw_energy, htk_compat;
+} ctcn_mfcc_opts;
+size_t ctcn_mfcc_plan_bytes(const ctcn_mfcc_opts *opts);
+int ctcn_mfcc_plan(const ctcn_mfcc_opts *opts, void *plan, size_t plan_bytes);
+int ctcn_mfcc(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_mfcc_opts *opts, const void *plan, const float *mean,
+              const float *scale, float *feats, int32_t *frames, int B, int Nmax, int Tmax, float dither, uint64_t seed, uint64_t utt_offset,
+              void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * CTC prefix beam search with bigram LM; replaces BeamDecoder.decode -> ctcBeamSearch.decode

@@ -2,7 +2,10 @@
 fbank.conf (hamming, 80 bins, energy: 81 dimensions) -- by HIP events, with and without the fused normalisation, and of
 ctcn_cmvn_accumulate on its output; beside it the float32 numpy restatement (tests/fbank_ref.py) on the host's threads.
 
-    python tools/fbank_bench.py [--reps 50] [--rounds 5] [--batch 32] [--seconds 8] [--cpu-threads 16]
+    python tools/fbank_bench.py [--reps 50] [--rounds 5] [--batch 32] [--seconds 8] [--cpu-threads 16] [--mfcc]
+
+--mfcc adds ctcn_mfcc on the same batch to the alternating rounds of the same process: Kaldi's MFCC defaults (23 bins, 13 cepstra) and 80
+bins / 64 cepstra under the filterbank leg's frame options, and ctcn_fbank with the MFCC defaults' 23 bins.
 
 Per round, alternating: `--reps` back-to-back launches of each variant after a warm-up of all; prints one JSON line with the median and
 the spread of the per-call time over the rounds, the bytes the algorithm has to move (bytes(wave) + 4 F T B) and the rate that makes of
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--seconds", type=float, default=8.0)
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--mfcc", action="store_true", help="time ops.mfcc next to ops.fbank in the same rounds")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "fbank_bench.py measures on the GPU only"
     dev = torch.device("cuda:0")
@@ -70,6 +74,16 @@ def main():
         "fbank_float32": lambda: ops.fbank(w32, lens, fb.plan),
         "cmvn_accumulate": lambda: ops.cmvn_accumulate(feats, frames, stats),
     }
+    algo_extra = {}
+    if args.mfcc:
+        for key, mkw in (("mfcc_int16_defaults", dict()), ("mfcc_int16_80bins_64ceps", dict(window_type="hamming", num_mel_bins=80, num_ceps=64))):
+            mf = features.Mfcc(features.MfccConfig(dither=0.0, **mkw), dev)
+            fns[key] = lambda plan=mf.plan: ops.mfcc(w16, lens, plan)
+            algo_extra[key] = 2 * B * N + 4 * mf.feat_dim * T * B
+        # the filterbank of the MFCC defaults' frame and mel options (povey, 23 bins, energy): what stages 1-4 cost there
+        fb23 = features.Fbank(features.FbankConfig(dither=0.0, use_energy=True), dev)
+        fns["fbank_int16_23bins"] = lambda: ops.fbank(w16, lens, fb23.plan)
+        algo_extra["fbank_int16_23bins"] = 2 * B * N + 4 * fb23.feat_dim * T * B
     for fn in fns.values():
         for _ in range(3):
             fn()
@@ -83,6 +97,7 @@ def main():
     # what the algorithm has to move: the samples once, the features once (ops.fbank also uploads B lengths and allocates its outputs: part of the call)
     algo = {"fbank_int16": 2 * B * N + 4 * F * T * B, "fbank_int16_normalised": 2 * B * N + 4 * F * T * B, "fbank_float32": 4 * B * N + 4 * F * T * B,
             "cmvn_accumulate": 4 * F * T * B}
+    algo.update(algo_extra)
     out["algorithmic_bytes"] = algo
     out["algorithmic_GBps_at_median"] = {k: round(algo[k] / (out["us_per_call"][k]["median"] * 1e-6) / 1e9, 1) for k in algo}
     if not args.no_cpu:
