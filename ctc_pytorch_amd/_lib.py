@@ -105,6 +105,15 @@ _SIGS = {
     "ctcn_mfcc_plan_bytes": (Z, [P]),
     "ctcn_mfcc_plan": (I, [P, P, Z]),
     "ctcn_mfcc": (I, [P, I, P, P, P, P, P, P, P, I, I, I, F, U, U, P]),
+    "ctcn_spectrogram_plan_bytes": (Z, [P]),
+    "ctcn_spectrogram_plan": (I, [P, P, Z]),
+    "ctcn_spectrogram": (I, [P, I, P, P, P, P, P, P, P, I, I, I, F, U, U, P]),
+    "ctcn_logspec_frames": (I, [ctypes.c_longlong, I]),
+    "ctcn_logspec_plan_bytes": (Z, [P]),
+    "ctcn_logspec_plan": (I, [P, P, Z]),
+    "ctcn_logspec_ws_bytes": (Z, [P, I, I]),
+    "ctcn_logspec": (I, [P, I, P, P, P, P, P, P, I, I, I, P, Z, P]),
+    "ctcn_fbank_power_host": (I, [P, I, P]),
     "ctcn_cmvn_accumulate_ws_bytes": (Z, [I, I, I]),
     "ctcn_cmvn_accumulate": (I, [P, P, P, I, I, I, P, Z, P]),
     "ctcn_comm_unique_id": (I, [P]),
@@ -148,6 +157,18 @@ class MfccOpts(ctypes.Structure):
                                               "high_freq", "energy_floor", "cepstral_lifter")] + \
                [(k, ctypes.c_int32) for k in ("window_type", "num_mel_bins", "num_ceps", "remove_dc_offset", "round_to_power_of_two", "snip_edges",
                                               "use_energy", "raw_energy", "htk_compat")]
+
+
+class SpectrogramOpts(ctypes.Structure):
+    """ctcn_spectrogram_opts of include/ctcn.h: Kaldi's spectrogram options (utils/features.SpectrogramConfig fills it)."""
+    _fields_ = [(k, ctypes.c_float) for k in ("samp_freq", "frame_shift_ms", "frame_length_ms", "preemph_coeff", "blackman_coeff", "energy_floor")] + \
+               [(k, ctypes.c_int32) for k in ("window_type", "remove_dc_offset", "round_to_power_of_two", "snip_edges", "raw_energy", "return_raw_fft")]
+
+
+class LogSpecOpts(ctypes.Structure):
+    """ctcn_logspec_opts of include/ctcn.h: the audio_conf of the recipe's make_spectrum.py (utils/features.LogSpecConfig fills it)."""
+    _fields_ = [(k, ctypes.c_double) for k in ("sample_rate", "window_size", "window_stride")] + [("input_scale", ctypes.c_float)] + \
+               [(k, ctypes.c_int32) for k in ("window", "normalize")]
 
 
 def sources():

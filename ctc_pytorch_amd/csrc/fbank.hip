@@ -1,6 +1,7 @@
 // fbank.hip -- the filterbank front-end: waveform -> (normalised) log-mel features, and the statistics of the global mean / variance
 // normalisation (ctcn_fbank_frames, ctcn_fbank_plan, ctcn_fbank, ctcn_mfcc_plan, ctcn_mfcc, ctcn_cmvn_accumulate; contract and plan layouts in
-// include/ctcn.h).
+// include/ctcn.h); Kaldi's spectrogram by the same kernel (ctcn_spectrogram) and the recipe's log-magnitude STFT with its per-utterance
+// normalisation (ctcn_logspec: logspec_kernel / logspec_finish_kernel below); ctcn_fbank_power_host, the transform on the host.
 //
 // fbank_kernel<NPAD, KIND>: grid (frame blocks, utterances), four waves per workgroup.
 //   1. The workgroup stages the plan (float64 twiddles, window, filter table, weights: 6 NPAD + 384 words) and the sample span of its `fpw` (<= 8)
@@ -10,7 +11,7 @@
 //      removal, raw energy, pre-emphasis (the left neighbour is the previous lane's value: one rotation per register) and the window run
 //      in registers, with wave_sum for the two reductions.
 //   3. Real FFT as the half-length complex transform of z[m] = x[2m] + i x[2m+1] plus a split step, in float64 (fbank_core.h says why):
-//      the windowed frame goes to the wave's LDS buffer, where pairs ARE z; three Stockham passes of radix 8, 8 and NPAD / 128 ping-pong between the wave's two buffers
+//      the windowed frame goes to the wave's LDS buffer, where pairs ARE z; three Stockham passes (FbRadix<NPAD>: radix 8, 8 and NPAD / 128) ping-pong between the wave's two buffers
 //      (fbank_core.h), twiddles from the plan's table; the split step writes the power spectrum of bins 0 .. NPAD/2 - 1.
 //   4. Lanes take mel filters (lane, lane + 64): a filter is a contiguous bin range, a dot product of <= ~30 terms; log, energy column,
 //      (x - mean) * scale, one coalesced row store.
@@ -18,11 +19,14 @@
 //      idle FFT buffer instead of global memory; lane k < num_ceps takes row k of the DCT (table staged bin-major behind the filter table, so
 //      consecutive lanes read consecutive words and the log-mel value is a broadcast) in ascending bin order, multiplies by the lifter,
 //      applies the energy and HTK column rules and the normalisation, and the wave stores one coalesced row of num_ceps floats.
+//   KIND_SPEC (ctcn_spectrogram; the same body): no mel bank; the split step also leaves the Nyquist bin, stage 4 is the log of bins
+//      0 .. NPAD/2 with the energy in place of bin 0, lanes storing columns lane, lane + 64, ... of the row of NPAD/2 + 1 floats.
 //   Rows of the block at or beyond the utterance's frame count are zero-filled by the whole workgroup first.
 //   Waves of a workgroup never wait for each other after the staging barrier: the FFT buffers are per wave, ordered by wave_lds_sync.
 // cmvn_partial_kernel / cmvn_finish_kernel: float64 column sums of 64-row blocks into the workspace, then one thread per statistic adds the
 //   partials in index order into the caller's block (norm.hip's scheme: no atomics, a function of the input bits).
 #include <algorithm>
+#include <vector>
 
 #include "common.h"
 #include "fbank_core.h"
@@ -66,12 +70,13 @@ __device__ __forceinline__ float fbank_gauss(uint64_t seed, uint64_t utt, int fr
   return r * ((i & 1) ? sinf(th) : cosf(th));
 }
 
-enum { KIND_FBANK = 0, KIND_MFCC = 1 };
+enum { KIND_FBANK = 0, KIND_MFCC = 1, KIND_SPEC = 2 };
 
 template <int NPAD, int KIND>
 __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
   constexpr int P = NPAD / 64, M = NPAD / 2;
-  constexpr bool MFCC = KIND == KIND_MFCC;
+  constexpr bool MFCC = KIND == KIND_MFCC, SPEC = KIND == KIND_SPEC;
+  using Radix = FbRadix<NPAD>;
   extern __shared__ __align__(16) double smem_d[];
   fbc *tw = reinterpret_cast<fbc *>(smem_d);                        // NPAD complex doubles
   double *wbuf = smem_d + 2 * NPAD;                                 // 4 waves x 2 x NPAD doubles (M complex each)
@@ -101,8 +106,10 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
     const float *p_tab = a.plan + 5 * NPAD;
     for (int i = tid; i < 2 * NPAD; i += 256) smem_d[i] = p_tw[i];
     for (int i = tid; i < NPAD; i += 256) win[i] = a.plan[i];
-    for (int i = tid; i < 3 * FBANK_MAX_BINS; i += 256) ftab[i] = reinterpret_cast<const int *>(p_tab)[i];
-    for (int i = tid; i < NPAD; i += 256) wts[i] = p_tab[3 * FBANK_MAX_BINS + i];
+    if (!SPEC) {                                                      // (the spectrogram's plan ends behind the twiddles)
+      for (int i = tid; i < 3 * FBANK_MAX_BINS; i += 256) ftab[i] = reinterpret_cast<const int *>(p_tab)[i];
+      for (int i = tid; i < NPAD; i += 256) wts[i] = p_tab[3 * FBANK_MAX_BINS + i];
+    }
     if (MFCC)
       for (int i = tid; i < a.nbins * a.F + a.F; i += 256) dct[i] = p_tab[3 * FBANK_MAX_BINS + NPAD + i];
     const long long s0 = (long long)f0 * shift + (a.snip ? 0 : shift / 2 - L / 2);
@@ -179,19 +186,31 @@ __global__ __launch_bounds__(256) void fbank_kernel(FbankArgs a) {
 #pragma unroll
     for (int j = 0; j < P; ++j) bufA[lane + 64 * j] = (double)x[j];
     wave_lds_sync();
-    fbank_fft_pass<M, 8>(lane, 1, zA, zB, tw);
+    fbank_fft_pass<M, Radix::r0>(lane, 1, zA, zB, tw);
     wave_lds_sync();
-    fbank_fft_pass<M, 8>(lane, 8, zB, zA, tw);
+    fbank_fft_pass<M, Radix::r1>(lane, Radix::r0, zB, zA, tw);
     wave_lds_sync();
-    fbank_fft_pass<M, M / 64>(lane, 64, zA, zB, tw);
+    fbank_fft_pass<M, Radix::r2>(lane, Radix::r0 * Radix::r1, zA, zB, tw);
     wave_lds_sync();
     for (int k = lane; k < M; k += 64) {
       const double p = fbank_split_power<M>(k, zB, tw);
       pw[k] = (float)(a.use_power ? p : sqrt(p));
     }
+    if (SPEC && lane == 0) pw[M] = (float)fbank_nyquist_power(zB);   // the bin no mel filter reads
     wave_lds_sync();
     // ---- 4. mel bank, log, energy, normalisation -------------------------------------------------------------------------------------------
     float *row = out + (size_t)frame * F;
+    if (SPEC) {
+      // ---- 4'. the spectrogram: the log of every bin, the energy in place of the DC bin; lanes store lane, lane + 64, ... of the row ----------
+      for (int c = lane; c < F; c += 64) {
+        float e = logf(fmaxf(c ? pw[c] : energy, FLT_EPSILON));
+        if (c == 0 && a.has_floor && e < a.log_floor) e = a.log_floor;
+        if (norm) e = (e - a.mean[c]) * a.scale[c];
+        row[c] = e;
+      }
+      wave_lds_sync();                                                // the next frame overwrites bufA (pw)
+      continue;
+    }
     for (int m = lane; m < a.nbins; m += 64) {
       const int first = ftab[m], cnt = ftab[FBANK_MAX_BINS + m];
       const float *w = wts + ftab[2 * FBANK_MAX_BINS + m];
@@ -268,6 +287,129 @@ __global__ __launch_bounds__(256) void cmvn_finish_kernel(const double *__restri
   }
 }
 
+// ---- the recipe's log-magnitude STFT (ctcn_logspec) -------------------------------------------------------------------------------------------
+// logspec_kernel<N>: the filterbank kernel's shape -- grid (frame blocks, utterances), four waves, one wave per frame, the plan and the sample
+//   span of `fpw` (<= 8) neighbouring frames staged once (numpy's reflection and input_scale applied there) -- with P = ceil(N / 64) registers
+//   per lane (N = 400: seven, the float64 window padded with zeros to 448), the passes of FbRadix<N>, and the split step's magnitudes going through
+//   log1pf straight to the row.  Every lane keeps float64 sums of its values and their squares; wave_sum_d, then wave 0 .. 3 in order: one
+//   (sum, sum of squares) per workgroup in ws.
+// logspec_finish_kernel: the same grid; every workgroup of an utterance adds the utterance's partials in index order (the same bits in each),
+//   forms mean and standard deviation in double, rounds each once; block 0 writes stats, all normalise their own rows in place.
+struct LogSpecArgs {
+  const void *wave;
+  const int32_t *lens;
+  const float *plan;
+  float *feats;
+  int32_t *frames;
+  float *stats;
+  double *ws;
+  int is_i16, Nmax, Tmax, hop, fpw, normalize;
+  float in_scale;
+};
+
+static inline size_t logspec_lds_words(int nfft, int wpad, int hop, int fpw) {
+  return (size_t)20 * nfft + 16 + 2 * wpad + (size_t)(fpw - 1) * hop + nfft;     // 4-byte words: twiddles 4, wave buffers 16 (x nfft), 8 doubles of partial sums, float64 window, samples
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void logspec_kernel(LogSpecArgs a) {
+  constexpr int P = (N + 63) / 64, M = N / 2, F = M + 1;
+  using Radix = FbRadix<N>;
+  extern __shared__ __align__(16) double smem_d[];
+  fbc *tw = reinterpret_cast<fbc *>(smem_d);                        // N complex doubles
+  double *wbuf = smem_d + 2 * N;                                    // 4 waves x 2 x N doubles (M complex each)
+  double *red = wbuf + 8 * N;                                       // 4 waves x (sum, sum of squares)
+  double *win = red + 8;                                            // 64 P
+  float *span = reinterpret_cast<float *>(win + 64 * P);
+
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int hop = a.hop;
+  const int n = min(max(a.lens[b], 0), a.Nmax);
+  const int Tb = min(logspec_num_frames(n, hop), a.Tmax);
+  if (blockIdx.x == 0 && tid == 0) a.frames[b] = Tb;
+  const int f0 = blockIdx.x * a.fpw;
+  float *out = a.feats + (size_t)b * a.Tmax * F;
+  {
+    const size_t zend = (size_t)min(f0 + a.fpw, a.Tmax) * F;
+    for (size_t i = (size_t)max(f0, Tb) * F + tid; i < zend; i += 256) out[i] = 0.f;
+  }
+  const int nf = min(a.fpw, Tb - f0);
+  if (nf <= 0) return;                                               // (the whole workgroup; the finish kernel reads the partials of blocks with frames only)
+
+  {
+    const double *p_win = reinterpret_cast<const double *>(a.plan), *p_tw = p_win + 64 * P;
+    for (int i = tid; i < 2 * N; i += 256) smem_d[i] = p_tw[i];
+    for (int i = tid; i < 64 * P; i += 256) win[i] = p_win[i];
+    const long long s0 = (long long)f0 * hop - N / 2;
+    const int span_len = (nf - 1) * hop + N;
+    const size_t base = (size_t)b * a.Nmax;
+    for (int i = tid; i < span_len; i += 256) {
+      const long long s = logspec_reflect(s0 + i, n);                // n >= 1 here (Tb > 0)
+      const float v = a.is_i16 ? (float)static_cast<const int16_t *>(a.wave)[base + s] : static_cast<const float *>(a.wave)[base + s];
+      span[i] = __fmul_rn(v, a.in_scale);
+    }
+  }
+  __syncthreads();
+
+  double *bufA = wbuf + wv * 2 * N, *bufB = bufA + N;
+  fbc *zA = reinterpret_cast<fbc *>(bufA), *zB = reinterpret_cast<fbc *>(bufB);
+  double sum = 0.0, sq = 0.0;
+  for (int fi = wv; fi < nf; fi += 4) {
+    const float *fr = span + fi * hop;
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      const int i = lane + 64 * j;
+      if (i < N) bufA[i] = (double)fr[i] * win[i];                    // exact: 24 x 53 bits round once
+    }
+    wave_lds_sync();
+    fbank_fft_pass<M, Radix::r0>(lane, 1, zA, zB, tw);
+    wave_lds_sync();
+    fbank_fft_pass<M, Radix::r1>(lane, Radix::r0, zB, zA, tw);
+    wave_lds_sync();
+    fbank_fft_pass<M, Radix::r2>(lane, Radix::r0 * Radix::r1, zA, zB, tw);
+    wave_lds_sync();
+    float *row = out + (size_t)(f0 + fi) * F;
+    for (int k = lane; k < F; k += 64) {
+      const double p = k < M ? fbank_split_power<M>(k, zB, tw) : fbank_nyquist_power(zB);
+      const float v = log1pf((float)sqrt(p));
+      row[k] = v;
+      sum += (double)v;
+      sq += (double)v * (double)v;
+    }
+    wave_lds_sync();                                                  // the next frame overwrites bufA and bufB
+  }
+  sum = wave_sum_d(sum);
+  sq = wave_sum_d(sq);
+  if (lane == 0) { red[2 * wv] = sum; red[2 * wv + 1] = sq; }
+  __syncthreads();
+  if (tid < 2) a.ws[((size_t)b * gridDim.x + blockIdx.x) * 2 + tid] = ((red[tid] + red[2 + tid]) + red[4 + tid]) + red[6 + tid];
+}
+
+__global__ __launch_bounds__(256) void logspec_finish_kernel(LogSpecArgs a, int F) {
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int n = min(max(a.lens[b], 0), a.Nmax);
+  const int Tb = min(logspec_num_frames(n, a.hop), a.Tmax);
+  const int nb = (Tb + a.fpw - 1) / a.fpw;                           // the blocks that left partials
+  if ((int)blockIdx.x >= nb && blockIdx.x != 0) return;
+  double s = 0.0, q = 0.0;
+  for (int p = 0; p < nb; ++p) {                                      // every thread of every block of the utterance: the same sum
+    s += a.ws[((size_t)b * gridDim.x + p) * 2];
+    q += a.ws[((size_t)b * gridDim.x + p) * 2 + 1];
+  }
+  float m = 0.f, sd = 0.f;
+  if (Tb > 0) {
+    const double cnt = (double)Tb * (double)F, mean = s / cnt;
+    m = (float)mean;
+    sd = (float)sqrt(fmax(q / cnt - mean * mean, 0.0));
+  }
+  if (blockIdx.x == 0 && tid == 0) { a.stats[2 * b] = m; a.stats[2 * b + 1] = sd; }
+  if (!a.normalize || (int)blockIdx.x >= nb) return;
+  const int f0 = blockIdx.x * a.fpw;
+  float *x = a.feats + ((size_t)b * a.Tmax + f0) * F;
+  const int cnt = (min(f0 + a.fpw, Tb) - f0) * F;
+  for (int i = tid; i < cnt; i += 256) x[i] = sd > 0.f ? __fdiv_rn(__fsub_rn(x[i], m), sd) : 0.f;
+}
+
 }  // namespace
 
 extern "C" int ctcn_fbank_frames(long long num_samples, int frame_length, int frame_shift, int snip_edges) {
@@ -317,7 +459,8 @@ static int fbank_launch(const char *who, int kind, const ctcn_fbank_opts *o, con
   const dim3 grid(std::max(ceil_div(Tmax, fpw), 1), B);
   hipStream_t st = (hipStream_t)stream;
   void (*kern)(FbankArgs);
-  if (kind == KIND_MFCC) kern = g.npad == 256 ? fbank_kernel<256, KIND_MFCC> : g.npad == 512 ? fbank_kernel<512, KIND_MFCC> : fbank_kernel<1024, KIND_MFCC>;
+  if (kind == KIND_SPEC) kern = g.npad == 256 ? fbank_kernel<256, KIND_SPEC> : g.npad == 512 ? fbank_kernel<512, KIND_SPEC> : fbank_kernel<1024, KIND_SPEC>;
+  else if (kind == KIND_MFCC) kern = g.npad == 256 ? fbank_kernel<256, KIND_MFCC> : g.npad == 512 ? fbank_kernel<512, KIND_MFCC> : fbank_kernel<1024, KIND_MFCC>;
   else kern = g.npad == 256 ? fbank_kernel<256, KIND_FBANK> : g.npad == 512 ? fbank_kernel<512, KIND_FBANK> : fbank_kernel<1024, KIND_FBANK>;
   if (lds > 64 * 1024) CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
@@ -382,5 +525,118 @@ extern "C" int ctcn_cmvn_accumulate(const float *feats, const int32_t *frames, d
   CTCN_LAUNCH_CHECK();
   hipLaunchKernelGGL(cmvn_finish_kernel, dim3(ceil_div(2 * F + 1, 256)), dim3(256), 0, st, static_cast<const double *>(ws), frames, stats, B, Tmax, F, chunks);
   CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" size_t ctcn_spectrogram_plan_bytes(const ctcn_spectrogram_opts *opts) {
+  FbankGeom g;
+  const char *why;
+  return spectrogram_geom(opts, &g, &why) == CTCN_OK ? g.words * 4 : 0;
+}
+
+extern "C" int ctcn_spectrogram_plan(const ctcn_spectrogram_opts *opts, void *plan, size_t plan_bytes) {
+  FbankGeom g;
+  const char *why;
+  const int rc = spectrogram_geom(opts, &g, &why);
+  if (rc != CTCN_OK) { ctcn_set_error("ctcn_spectrogram_plan: %s", why); return rc; }
+  CTCN_REQUIRE(plan && plan_bytes >= g.words * 4, "ctcn_spectrogram_plan: buffer of %zu bytes needed", g.words * 4);
+  const ctcn_fbank_opts f = spectrogram_fbank_opts(opts);
+  fbank_build_window(&f, g, plan);
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_spectrogram(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_spectrogram_opts *opts, const void *plan,
+                                const float *mean, const float *scale, float *feats, int32_t *frames, int B, int Nmax, int Tmax, float dither,
+                                uint64_t seed, uint64_t utt_offset, void *stream) {
+  FbankGeom g;
+  const char *why;
+  const int rc = spectrogram_geom(opts, &g, &why);
+  if (rc != CTCN_OK) { ctcn_set_error("ctcn_spectrogram: %s", why); return rc; }
+  const ctcn_fbank_opts f = spectrogram_fbank_opts(opts);
+  return fbank_launch("ctcn_spectrogram", KIND_SPEC, &f, g, g.F, 0, wave, wave_is_int16, lens, plan, mean, scale, feats, frames, B, Nmax, Tmax, dither,
+                      seed, utt_offset, stream);
+}
+
+extern "C" int ctcn_logspec_frames(long long num_samples, int hop) {
+  CTCN_REQUIRE(num_samples >= 0 && hop > 0, "ctcn_logspec_frames: bad args (samples %lld, hop %d)", num_samples, hop);
+  CTCN_REQUIRE(num_samples / hop < 0x7ffffffeLL, "ctcn_logspec_frames: frame count beyond int");
+  return logspec_num_frames(num_samples, hop);
+}
+
+extern "C" size_t ctcn_logspec_plan_bytes(const ctcn_logspec_opts *opts) {
+  LogSpecGeom g;
+  const char *why;
+  return logspec_geom(opts, &g, &why) == CTCN_OK ? g.words * 4 : 0;
+}
+
+extern "C" int ctcn_logspec_plan(const ctcn_logspec_opts *opts, void *plan, size_t plan_bytes) {
+  LogSpecGeom g;
+  const char *why;
+  const int rc = logspec_geom(opts, &g, &why);
+  if (rc != CTCN_OK) { ctcn_set_error("ctcn_logspec_plan: %s", why); return rc; }
+  CTCN_REQUIRE(plan && plan_bytes >= g.words * 4, "ctcn_logspec_plan: buffer of %zu bytes needed", g.words * 4);
+  logspec_build_plan(opts, g, plan);
+  return CTCN_OK;
+}
+
+// frames per workgroup: eight where the staged samples fit in LDS, else fewer; 0: not even one frame does
+static int logspec_fpw(const LogSpecGeom &g) {
+  int fpw = 8;
+  while (fpw > 1 && logspec_lds_words(g.nfft, g.wpad, g.hop, fpw) * 4 > FBANK_LDS_LIMIT) fpw >>= 1;
+  return logspec_lds_words(g.nfft, g.wpad, g.hop, fpw) * 4 > FBANK_LDS_LIMIT ? 0 : fpw;
+}
+
+extern "C" size_t ctcn_logspec_ws_bytes(const ctcn_logspec_opts *opts, int B, int Tmax) {
+  LogSpecGeom g;
+  const char *why;
+  if (logspec_geom(opts, &g, &why) != CTCN_OK || B <= 0 || Tmax < 0) return 0;
+  const int fpw = logspec_fpw(g);
+  return fpw ? (size_t)B * std::max(ceil_div(Tmax, fpw), 1) * 2 * sizeof(double) : 0;
+}
+
+extern "C" int ctcn_logspec(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_logspec_opts *opts, const void *plan, float *feats,
+                            int32_t *frames, float *stats, int B, int Nmax, int Tmax, void *ws, size_t ws_bytes, void *stream) {
+  LogSpecGeom g;
+  const char *why;
+  const int rc = logspec_geom(opts, &g, &why);
+  if (rc != CTCN_OK) { ctcn_set_error("ctcn_logspec: %s", why); return rc; }
+  CTCN_REQUIRE(lens && plan && frames && stats && B > 0 && B <= 65535 && Nmax >= 0 && Tmax >= 0 && (wave || Nmax == 0) && (feats || Tmax == 0),
+               "ctcn_logspec: bad args (B %d at most 65 535)", B);
+  const int fpw = logspec_fpw(g);
+  if (!fpw) { ctcn_set_error("ctcn_logspec: window stride of %d samples too long for the LDS staging", g.hop); return CTCN_EUNSUPPORTED; }
+  const size_t need = ctcn_logspec_ws_bytes(opts, B, Tmax);
+  CTCN_REQUIRE(ws && ((uintptr_t)ws & 7) == 0, "ctcn_logspec: workspace of ctcn_logspec_ws_bytes needed, 8-byte aligned");
+  if (ws_bytes < need) { ctcn_set_error("ctcn_logspec: workspace %zu < %zu bytes", ws_bytes, need); return CTCN_EWORKSPACE; }
+  const size_t lds = logspec_lds_words(g.nfft, g.wpad, g.hop, fpw) * 4;
+  LogSpecArgs a;
+  a.wave = wave; a.lens = lens; a.plan = static_cast<const float *>(plan); a.feats = feats; a.frames = frames; a.stats = stats;
+  a.ws = static_cast<double *>(ws);
+  a.is_i16 = wave_is_int16 != 0; a.Nmax = Nmax; a.Tmax = Tmax; a.hop = g.hop; a.fpw = fpw; a.normalize = opts->normalize != 0;
+  a.in_scale = opts->input_scale;
+  const dim3 grid(std::max(ceil_div(Tmax, fpw), 1), B);
+  hipStream_t st = (hipStream_t)stream;
+  void (*kern)(LogSpecArgs) = g.nfft == 256 ? logspec_kernel<256> : g.nfft == 400 ? logspec_kernel<400> : g.nfft == 512 ? logspec_kernel<512> : logspec_kernel<1024>;
+  if (lds > 64 * 1024) CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
+  CTCN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(logspec_finish_kernel, grid, dim3(256), 0, st, a, g.F);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_fbank_power_host(const double *frame, int n, double *power) {
+  CTCN_REQUIRE(frame && power, "ctcn_fbank_power_host: null argument");
+  if (n != 256 && n != 400 && n != 512 && n != 1024) { ctcn_set_error("ctcn_fbank_power_host: n must be 256, 400, 512 or 1024, got %d", n); return CTCN_EUNSUPPORTED; }
+  const double two_pi = 6.283185307179586476925286766559;
+  std::vector<fbc> buf(n), tw(n);                                      // a | b of n / 2 complex each
+  for (int k = 0; k < n; ++k) tw[k] = fb_c(cos(two_pi * k / n), -sin(two_pi * k / n));
+  memcpy(buf.data(), frame, sizeof(double) * n);                      // pairs ARE z[m] = x[2m] + i x[2m+1]
+  fbc *za = buf.data(), *zb = za + n / 2;
+  switch (n) {
+    case 256: fbank_power_host<256>(za, zb, tw.data(), power); break;
+    case 400: fbank_power_host<400>(za, zb, tw.data(), power); break;
+    case 512: fbank_power_host<512>(za, zb, tw.data(), power); break;
+    default: fbank_power_host<1024>(za, zb, tw.data(), power); break;
+  }
   return CTCN_OK;
 }

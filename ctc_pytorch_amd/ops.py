@@ -1883,7 +1883,7 @@ class FbankPlan(object):
         self.frame_length = int(float(opts.samp_freq) * 0.001 * float(opts.frame_length_ms))
         self.frame_shift = int(float(opts.samp_freq) * 0.001 * float(opts.frame_shift_ms))
         self.padded_length = 1 << (self.frame_length - 1).bit_length()
-        self.num_mel_bins = int(opts.num_mel_bins)
+        self.num_mel_bins = int(getattr(opts, "num_mel_bins", 0))      # (the spectrogram has no mel bank)
         self.feat_dim = self._feat_dim(opts)
         self.snip_edges = bool(opts.snip_edges)
         self._dev = {}
@@ -1912,8 +1912,17 @@ class MfccPlan(FbankPlan):
         return self.num_ceps
 
 
+class SpectrogramPlan(FbankPlan):
+    """The plan of one spectrogram configuration (ctcn_spectrogram_plan, from an _lib.SpectrogramOpts): the window and the twiddles of the
+    filterbank plan of the same frame options.  feat_dim = padded_length / 2 + 1; there is no mel bank (num_mel_bins is 0)."""
+    _name = "spectrogram"
+
+    def _feat_dim(self, opts):
+        return self.padded_length // 2 + 1
+
+
 def _frontend(name, wave, lengths, plan, mean, scale, dither, seed, utt_offset):
-    """The body of fbank and mfcc: validation, output allocation, ctcn_<name>."""
+    """The body of fbank, mfcc and spectrogram: validation, output allocation, ctcn_<name>."""
     if wave.dim() != 2:
         raise ValueError("ctc_pytorch_amd.%s: expected wave (B, Nmax), got %s" % (name, tuple(wave.shape)))
     _need_gpu(wave, mean, scale)
@@ -1951,7 +1960,7 @@ def fbank(wave, lengths, plan, mean=None, scale=None, dither=0.0, seed=0, utt_of
     Returns (feats (B, Tmax, F) float32, frames (B) int32) with Tmax = the largest frame count; rows from frames[b] on are zero.  dither > 0
     adds dither * N(0, 1) per extracted sample, a function of (seed, b + utt_offset, frame, sample) alone.  No autograd; device tensors only
     (no CPU fallback)."""
-    if not isinstance(plan, FbankPlan) or isinstance(plan, MfccPlan):
+    if type(plan) is not FbankPlan:                                     # (MfccPlan and SpectrogramPlan carry other option structs)
         raise TypeError("ctc_pytorch_amd.fbank: expected a FbankPlan, got %s" % type(plan).__name__)
     return _frontend("fbank", wave, lengths, plan, mean, scale, dither, seed, utt_offset)
 
@@ -1962,6 +1971,74 @@ def mfcc(wave, lengths, plan, mean=None, scale=None, dither=0.0, seed=0, utt_off
     if not isinstance(plan, MfccPlan):
         raise TypeError("ctc_pytorch_amd.mfcc: expected a MfccPlan, got %s" % type(plan).__name__)
     return _frontend("mfcc", wave, lengths, plan, mean, scale, dither, seed, utt_offset)
+
+
+def spectrogram(wave, lengths, plan, mean=None, scale=None, dither=0.0, seed=0, utt_offset=0):
+    """Kaldi's spectrogram features of a padded batch of waveforms (ctcn_spectrogram: the filterbank kernel without the mel bank -- the log
+    power of bins 0 .. Npad / 2 with the log energy in column 0; include/ctcn.h).  The contract of fbank with plan a SpectrogramPlan and
+    F = Npad / 2 + 1."""
+    if not isinstance(plan, SpectrogramPlan):
+        raise TypeError("ctc_pytorch_amd.spectrogram: expected a SpectrogramPlan, got %s" % type(plan).__name__)
+    return _frontend("spectrogram", wave, lengths, plan, mean, scale, dither, seed, utt_offset)
+
+
+class LogSpecPlan(object):
+    """The plan of one configuration of the recipe's log-magnitude STFT (ctcn_logspec_plan, from an _lib.LogSpecOpts: symmetric window,
+    twiddles): built on the host when the object is made -- a RuntimeError here, before any launch, for a configuration the kernel does not
+    take (n_fft other than 256, 400, 512, 1024) -- and uploaded once per device on first use.  `host`: the block as uint32 words."""
+
+    def __init__(self, opts):
+        L = _lib.lib()
+        self.opts = opts
+        nbytes = L.ctcn_logspec_plan_bytes(ctypes.byref(opts))
+        buf = np.zeros(max(nbytes // 4, 1), dtype=np.uint32)
+        _lib.check(L.ctcn_logspec_plan(ctypes.byref(opts), buf.ctypes.data_as(ctypes.c_void_p), nbytes), "logspec_plan")
+        self.host = buf
+        self.n_fft = int(float(opts.sample_rate) * float(opts.window_size))
+        self.hop = int(float(opts.sample_rate) * float(opts.window_stride))
+        self.feat_dim = self.n_fft // 2 + 1
+        self.normalize = bool(opts.normalize)
+        self._dev = {}
+
+    def num_frames(self, num_samples):
+        r = _lib.lib().ctcn_logspec_frames(int(num_samples), self.hop)
+        if r < 0:
+            raise ValueError("ctc_pytorch_amd.LogSpecPlan.num_frames: bad sample count %r" % (num_samples,))
+        return r
+
+    on = FbankPlan.on
+
+
+def log_spectrum(wave, lengths, plan):
+    """The recipe's spectrogram (make_spectrum.py: centred STFT over the reflected signal, symmetric window, log1p of the magnitude, one mean
+    and standard deviation per utterance; ctcn_logspec, step by step in include/ctcn.h) of a padded batch: wave (B, Nmax) float32 or int16,
+    lengths (B) samples (read on the host), plan a LogSpecPlan.  Returns (feats (B, Tmax, n_fft / 2 + 1) float32 with rows from frames[b] on
+    zero, frames (B) int32, stats (B, 2) float32: the mean and standard deviation applied -- or, with normalize off, that would have been).
+    No autograd; device tensors only (no CPU fallback)."""
+    if not isinstance(plan, LogSpecPlan):
+        raise TypeError("ctc_pytorch_amd.log_spectrum: expected a LogSpecPlan, got %s" % type(plan).__name__)
+    if wave.dim() != 2:
+        raise ValueError("ctc_pytorch_amd.log_spectrum: expected wave (B, Nmax), got %s" % (tuple(wave.shape),))
+    _need_gpu(wave)
+    if wave.dtype not in (torch.float32, torch.int16):
+        raise TypeError("ctc_pytorch_amd.log_spectrum: expected float32 or int16 samples, got %s" % wave.dtype)
+    B, Nmax = wave.shape
+    host_lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(host_lens) != B or B == 0:
+        raise ValueError("ctc_pytorch_amd.log_spectrum: %d lengths for a batch of %d" % (len(host_lens), B))
+    dev, F = wave.device, plan.feat_dim
+    wave = wave.contiguous()
+    Tmax = max(plan.num_frames(min(max(n, 0), Nmax)) for n in host_lens)
+    lens = torch.as_tensor(host_lens, dtype=torch.int32).to(dev)
+    feats = torch.empty((B, Tmax, F), dtype=torch.float32, device=dev)
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    stats = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    need = _lib.lib().ctcn_logspec_ws_bytes(ctypes.byref(plan.opts), B, Tmax)
+    ws = _lib.workspace(dev, nbytes=need, tag="logspec")
+    _lib.check(_lib.lib().ctcn_logspec(_ptr(wave), int(wave.dtype == torch.int16), _ptr(lens), ctypes.byref(plan.opts), _ptr(plan.on(dev)),
+                                       _ptr(feats) if Tmax else None, _ptr(frames), _ptr(stats), B, Nmax, Tmax, _ptr(ws), ws.numel(),
+                                       _lib.stream_ptr()), "logspec")
+    return feats, frames, stats
 
 
 def cmvn_accumulate(feats, frames, stats):

@@ -1,9 +1,14 @@
 """Audio -> feature archive on the device: the counterpart of the reference's timit/steps/make_feat.sh, whose three Kaldi binaries
 (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true with one global mean and variance) become
 utils/features.Fbank and GlobalCMVN.  --feat-type mfcc is the recipe's feat_type=mfcc: compute-mfcc-feats --config=conf/mfcc.conf becomes
-utils/features.Mfcc.
+utils/features.Mfcc, --feat-type spectrogram is feat_type=spectrogram: compute-spectrogram-feats becomes utils/features.Spectrogram (257
+columns under Kaldi's defaults), with the same global CMVN.  --feat-type logspec is the recipe's own local/make_spectrum.py
+(utils/features.LogSpectrum): --conf holds `--key=value` lines after its audio_conf (sample-rate, window-size, window-stride, window,
+normalize, input-scale; an empty file gives its defaults: 201 columns); it normalises every utterance by its own mean and standard
+deviation, so --compute-cmvn and --cmvn-stats are refused.
 
-    make_feat.py --conf fbank.conf --wav-scp train/wav.scp --out-dir DIR [--cmvn-stats FILE] [--compute-cmvn] [--feat-type {fbank,mfcc}]
+    make_feat.py --conf fbank.conf --wav-scp train/wav.scp --out-dir DIR [--cmvn-stats FILE] [--compute-cmvn]
+                 [--feat-type {fbank,mfcc,spectrogram,logspec}]
 
 wav.scp: one `<utterance> <path>` per line (RIFF PCM-16 mono or uncompressed SPHERE; piped commands are not run).  Writes DIR/feats.ark and
 DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDataset and both drivers read them unchanged.
@@ -24,9 +29,11 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from ctc_pytorch_amd.utils.data_loader import write_kaldi_ark  # noqa: E402
-from ctc_pytorch_amd.utils.features import Fbank, FbankConfig, GlobalCMVN, Mfcc, MfccConfig, read_wave  # noqa: E402
+from ctc_pytorch_amd.utils.features import (Fbank, FbankConfig, GlobalCMVN, LogSpecConfig, LogSpectrum, Mfcc, MfccConfig, Spectrogram,  # noqa: E402
+                                            SpectrogramConfig, read_wave)
 
-FEAT_TYPES = {"fbank": (FbankConfig, Fbank), "mfcc": (MfccConfig, Mfcc)}
+FEAT_TYPES = {"fbank": (FbankConfig, Fbank), "mfcc": (MfccConfig, Mfcc), "spectrogram": (SpectrogramConfig, Spectrogram),
+              "logspec": (LogSpecConfig, LogSpectrum)}
 
 
 def read_wav_scp(path):
@@ -61,7 +68,10 @@ def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=Non
     features accumulated into it."""
     mats, place = {}, 0
     for idx in batches:
-        feats, frames = fbank([waves[i] for i in idx], mean=mean, scale=scale, seed=seed, utt_offset=place)
+        if isinstance(fbank, LogSpectrum):                             # normalised per utterance by the call itself; no dither
+            feats, frames, _ = fbank([waves[i] for i in idx])
+        else:
+            feats, frames = fbank([waves[i] for i in idx], mean=mean, scale=scale, seed=seed, utt_offset=place)
         place += len(idx)
         if cmvn is not None:
             cmvn.accumulate(feats, frames)
@@ -75,7 +85,8 @@ def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=Non
 def main(argv=None, log=print):
     ap = argparse.ArgumentParser(description="waveforms -> (normalised) filterbank features as a Kaldi archive, computed on the MI355X")
     ap.add_argument("--conf", required=True, help="Kaldi fbank config file (--key=value lines), e.g. the reference's conf/fbank.conf")
-    ap.add_argument("--feat-type", choices=sorted(FEAT_TYPES), default="fbank", help="mfcc: --conf is read as an MFCC config (conf/mfcc.conf)")
+    ap.add_argument("--feat-type", choices=sorted(FEAT_TYPES), default="fbank", help="mfcc, spectrogram: --conf is read as that Kaldi config (conf/mfcc.conf, conf/spectrogram.conf); "
+                    "logspec: the recipe's make_spectrum.py, --conf holds its audio_conf as --key=value lines, normalisation is per utterance")
     ap.add_argument("--wav-scp", required=True, help="list of '<utterance> <wav or sphere path>'")
     ap.add_argument("--out-dir", required=True, help="where feats.ark / feats.scp go")
     ap.add_argument("--cmvn-stats", default=None, help="Kaldi text CMVN statistics to apply (with --compute-cmvn: where to write them)")
@@ -85,6 +96,9 @@ def main(argv=None, log=print):
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
 
+    if args.feat_type == "logspec" and (args.compute_cmvn or args.cmvn_stats):
+        raise ValueError("--feat-type logspec normalises every utterance by its own mean and standard deviation (normalize in --conf): "
+                         "--compute-cmvn and --cmvn-stats do not apply to it")
     config_type, frontend_type = FEAT_TYPES[args.feat_type]
     config = config_type.from_kaldi_conf(args.conf)
     device = torch.device(args.device)

@@ -6,6 +6,10 @@ binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --conf
   Fbank         the configured front-end on one device (ops.fbank behind it; holds the uploaded plan)
   MfccConfig    the same for compute-mfcc-feats (the recipe's feat_type=mfcc, conf/mfcc.conf): Kaldi's MFCC defaults, use_energy = true
   Mfcc          the MFCC front-end (ops.mfcc: the same kernel with the DCT, the lifter and Kaldi's column rules behind its log-mel stage)
+  SpectrogramConfig / Spectrogram   compute-spectrogram-feats (the recipe's feat_type=spectrogram): the log power of every FFT bin, the log
+                energy in column 0 (ops.spectrogram: the same kernel without the mel bank)
+  LogSpecConfig / LogSpectrum       the recipe's own spectrogram (local/make_spectrum.py: a centred STFT of 400 points, log1p of the magnitude,
+                one mean and standard deviation per utterance; ops.log_spectrum)
   GlobalCMVN    Kaldi's 2 x (F + 1) statistics, accumulated on the device (ops.cmvn_accumulate), its text file, mean and 1 / stddev
   read_wave     RIFF PCM-16 mono and uncompressed NIST SPHERE (TIMIT's) -> int16 samples
 
@@ -18,10 +22,11 @@ import torch
 from .. import _lib, ops
 
 WINDOW_TYPES = ("hamming", "hanning", "povey", "rectangular", "blackman")     # the order of ctcn_fbank_opts.window_type
+LOGSPEC_WINDOWS = ("hamming", "hann", "blackman", "bartlett")                  # the order of ctcn_logspec_opts.window
 
 
 class _KaldiConfig(object):
-    """What FbankConfig and MfccConfig share: options under Kaldi's names (dashes as underscores) held as attributes, converted to the types
+    """What the config classes share: options under Kaldi's names (dashes as underscores) held as attributes, converted to the types
     of the class's DEFAULTS, and the reader of Kaldi's `--key=value` files."""
     DEFAULTS = {}
 
@@ -32,8 +37,11 @@ class _KaldiConfig(object):
                 raise ValueError("%s: unknown option %r" % (name, k))
         for k, d in self.DEFAULTS.items():
             setattr(self, k, self._convert(k, kw.get(k, d)))
+        self._check_window()
+
+    def _check_window(self):
         if self.window_type not in WINDOW_TYPES:
-            raise ValueError("%s: unknown window type %r (one of %s)" % (name, self.window_type, ", ".join(WINDOW_TYPES)))
+            raise ValueError("%s: unknown window type %r (one of %s)" % (type(self).__name__, self.window_type, ", ".join(WINDOW_TYPES)))
 
     @classmethod
     def _convert(cls, key, value):
@@ -108,6 +116,77 @@ class MfccConfig(_KaldiConfig):
         return _lib.MfccOpts(num_ceps=self.num_ceps, cepstral_lifter=self.cepstral_lifter, **self._frame_mel_opts())
 
 
+class SpectrogramConfig(_KaldiConfig):
+    """The options of Kaldi's compute-spectrogram-feats, under Kaldi's names and with Kaldi's defaults: the frame options, energy_floor,
+    raw_energy and return_raw_fft -- read and kept, but true is refused when the plan is built (Kaldi's complex output is not built).
+    There is no mel bank: num_mel_bins and the frequency limits are unknown options."""
+    DEFAULTS = dict(sample_frequency=16000.0, frame_shift=10.0, frame_length=25.0, dither=1.0, preemphasis_coefficient=0.97,
+                    remove_dc_offset=True, window_type="povey", round_to_power_of_two=True, blackman_coeff=0.42, snip_edges=True,
+                    energy_floor=0.0, raw_energy=True, return_raw_fft=False)
+
+    @property
+    def feat_dim(self):
+        L = int(float(np.float32(self.sample_frequency)) * 0.001 * float(np.float32(self.frame_length)))
+        return (1 << (L - 1).bit_length()) // 2 + 1
+
+    def c_opts(self):
+        return _lib.SpectrogramOpts(samp_freq=self.sample_frequency, frame_shift_ms=self.frame_shift, frame_length_ms=self.frame_length,
+                                    preemph_coeff=self.preemphasis_coefficient, blackman_coeff=self.blackman_coeff,
+                                    energy_floor=self.energy_floor, window_type=WINDOW_TYPES.index(self.window_type),
+                                    remove_dc_offset=self.remove_dc_offset, round_to_power_of_two=self.round_to_power_of_two,
+                                    snip_edges=self.snip_edges, raw_energy=self.raw_energy, return_raw_fft=self.return_raw_fft)
+
+
+class LogSpecConfig(_KaldiConfig):
+    """The audio_conf of the recipe's local/make_spectrum.py under its own names and defaults, plus normalize (its parse_audio argument) and
+    input_scale (multiplied onto the samples first: log1p is not scale-free, and the reference's loader may hand floats in +-1 where
+    read_wave hands the int16 range).  n_fft = int(sample_rate * window_size), hop = int(sample_rate * window_stride).  from_kaldi_conf
+    reads the same `--key=value` lines (`--window-size=0.032`); an empty file gives the defaults."""
+    DEFAULTS = dict(sample_rate=16000.0, window_size=0.025, window_stride=0.01, window="hamming", normalize=True, input_scale=1.0)
+
+    def _check_window(self):
+        if self.window not in LOGSPEC_WINDOWS:
+            raise ValueError("LogSpecConfig: unknown window %r (one of %s)" % (self.window, ", ".join(LOGSPEC_WINDOWS)))
+
+    @property
+    def sample_frequency(self):
+        return self.sample_rate
+
+    @property
+    def n_fft(self):
+        return int(self.sample_rate * self.window_size)
+
+    @property
+    def hop(self):
+        return int(self.sample_rate * self.window_stride)
+
+    @property
+    def feat_dim(self):
+        return self.n_fft // 2 + 1
+
+    def c_opts(self):
+        return _lib.LogSpecOpts(sample_rate=self.sample_rate, window_size=self.window_size, window_stride=self.window_stride,
+                                input_scale=self.input_scale, window=LOGSPEC_WINDOWS.index(self.window), normalize=self.normalize)
+
+
+def _batch(name, waves, lengths):
+    """(padded (B, Nmax) int16 / float32 tensor, lengths) of a list of 1-D waveforms, or of a padded batch with `lengths`."""
+    if lengths is None:
+        arrs = [w.cpu().numpy() if torch.is_tensor(w) else np.asarray(w) for w in waves]
+        if not arrs or any(a.ndim != 1 for a in arrs):
+            raise ValueError("%s: expected a non-empty list of 1-D waveforms" % name)
+        lengths = [a.shape[0] for a in arrs]
+        batch = np.zeros((len(arrs), max(max(lengths), 1)), dtype=np.int16 if all(a.dtype == np.int16 for a in arrs) else np.float32)
+        for b, a in enumerate(arrs):
+            batch[b, :a.shape[0]] = a
+        waves = torch.from_numpy(batch)
+    elif not torch.is_tensor(waves):
+        waves = torch.from_numpy(np.ascontiguousarray(waves))
+    if waves.dtype not in (torch.int16, torch.float32):
+        waves = waves.to(torch.float32)
+    return waves, lengths
+
+
 class _FrontEnd(object):
     """A configured front-end on one device: the plan (built here, so a configuration outside the kernel's range raises RuntimeError here)
     and the call that batches waveforms for the kernel.  Subclasses name the plan type and the op."""
@@ -127,19 +206,7 @@ class _FrontEnd(object):
         """waves: a list of 1-D waveforms (int16 or float arrays / tensors on Kaldi's scale: int16 range), or a padded (B, Nmax) batch with
         `lengths`.  mean / scale: the (F) vectors of GlobalCMVN.mean_scale, applied by the same kernel.  Returns (feats (B, Tmax, F) float32
         zero-padded, frames (B) int32) on the device: the loader's layout.  Dither is config.dither, keyed by (seed, b + utt_offset)."""
-        if lengths is None:
-            arrs = [w.cpu().numpy() if torch.is_tensor(w) else np.asarray(w) for w in waves]
-            if not arrs or any(a.ndim != 1 for a in arrs):
-                raise ValueError("%s: expected a non-empty list of 1-D waveforms" % type(self).__name__)
-            lengths = [a.shape[0] for a in arrs]
-            batch = np.zeros((len(arrs), max(max(lengths), 1)), dtype=np.int16 if all(a.dtype == np.int16 for a in arrs) else np.float32)
-            for b, a in enumerate(arrs):
-                batch[b, :a.shape[0]] = a
-            waves = torch.from_numpy(batch)
-        elif not torch.is_tensor(waves):
-            waves = torch.from_numpy(np.ascontiguousarray(waves))
-        if waves.dtype not in (torch.int16, torch.float32):
-            waves = waves.to(torch.float32)
+        waves, lengths = _batch(type(self).__name__, waves, lengths)
         vec = lambda v: None if v is None else torch.as_tensor(v, dtype=torch.float32).to(self.device)
         return type(self)._op(waves.to(self.device), lengths, self.plan, mean=vec(mean), scale=vec(scale), dither=self.config.dither, seed=seed,
                               utt_offset=utt_offset)
@@ -157,6 +224,34 @@ class Mfcc(_FrontEnd):
     limits, num_ceps outside [1, num_mel_bins], more than 64 cepstra or a negative lifter raise RuntimeError here."""
     _plan_type = ops.MfccPlan
     _op = staticmethod(ops.mfcc)
+
+
+class Spectrogram(_FrontEnd):
+    """The spectrogram front-end of one SpectrogramConfig on one device: Fbank's call signature and return layout with F = Npad / 2 + 1
+    (257 under the defaults).  A padded frame other than 256 / 512 / 1024 samples, round_to_power_of_two=false or return_raw_fft=true raise
+    RuntimeError here."""
+    _plan_type = ops.SpectrogramPlan
+    _op = staticmethod(ops.spectrogram)
+
+
+class LogSpectrum(object):
+    """The recipe's own spectrogram of one LogSpecConfig on one device (ops.log_spectrum).  Building it builds the plan: an n_fft other than
+    256, 400, 512 or 1024 raises RuntimeError here.  Normalisation is per utterance and part of the call; there is no mean / scale."""
+
+    def __init__(self, config, device):
+        self.config = config
+        self.device = torch.device(device)
+        self.plan = ops.LogSpecPlan(config.c_opts())
+        self.feat_dim = self.plan.feat_dim
+
+    def num_frames(self, num_samples):
+        return self.plan.num_frames(num_samples)
+
+    def __call__(self, waves, lengths=None):
+        """waves as Fbank takes them.  Returns (feats (B, Tmax, F) float32 zero-padded, frames (B) int32, stats (B, 2) float32: the mean and
+        standard deviation of each utterance) on the device."""
+        waves, lengths = _batch("LogSpectrum", waves, lengths)
+        return ops.log_spectrum(waves.to(self.device), lengths, self.plan)
 
 
 class GlobalCMVN(object):

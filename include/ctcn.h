@@ -576,7 +576,7 @@ int ctcn_step_stats(const float *loss, const int32_t *dist, const int64_t *tgt_l
  * binaries of timit/steps/make_feat.sh (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true).
  * The computation is Kaldi's, as its feature-window, feature-fbank and mel-computations sources document it; option names and defaults are
  * Kaldi's.  window_type: 0 hamming, 1 hanning, 2 povey (Kaldi's default), 3 rectangular, 4 blackman.  high_freq <= 0 is an offset from Nyquist.
- * Not here: VTLN, deltas, resampling (MFCC: ctcn_mfcc below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
+ * Not here: VTLN, deltas, resampling (MFCC: ctcn_mfcc below; the spectrogram types: ctcn_spectrogram, ctcn_logspec below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
  * defaults). */
 typedef struct ctcn_fbank_opts {
   float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff, blackman_coeff, low_freq, high_freq, energy_floor;
@@ -651,6 +651,74 @@ int ctcn_mfcc_plan(const ctcn_mfcc_opts *opts, void *plan, size_t plan_bytes);
 int ctcn_mfcc(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_mfcc_opts *opts, const void *plan, const float *mean,
               const float *scale, float *feats, int32_t *frames, int B, int Nmax, int Tmax, float dither, uint64_t seed, uint64_t utt_offset,
               void *stream);
+/* Spectrogram, the recipe's third feature type (feat_type=spectrogram: compute-spectrogram-feats --config=conf/spectrogram.conf), by the
+ * same kernel: Kaldi's feature-spectrogram.  The options are Kaldi's SpectrogramOptions under the filterbank's field names: the frame
+ * options, energy_floor (0), raw_energy (true) and return_raw_fft (false; true is Kaldi's complex output and not built).  Zero-initialise
+ * and fill every field (utils/features.SpectrogramConfig holds the defaults).  Per frame, F = Npad / 2 + 1:
+ *   1. extraction (both snip_edges rules), dither, DC removal, raw log-energy, pre-emphasis, window, zero padding and the float64 real
+ *      transform exactly as ctcn_fbank runs them (the same code);
+ *   2. the power of bins 0 .. Npad / 2 INCLUSIVE, rounded once to float32; the Nyquist bin, which the filterbank never reads, comes from
+ *      the split step's first element: (Re Z[0] - Im Z[0])^2;
+ *   3. log(max(p, FLT_EPSILON));
+ *   4. column 0 (the DC bin) is replaced by the log energy e -- log(max(sum x^2, FLT_EPSILON)) before pre-emphasis and window (raw_energy)
+ *      or behind the window -- raised to log(energy_floor) where energy_floor > 0;
+ *   5. (x - mean[col]) * scale[col], as ctcn_fbank.
+ * The plan: words [0, 5 Npad) of the filterbank plan of the same frame options, bit for bit (window, float64 twiddles); nothing behind them.
+ * Limits: the filterbank's frame limits (round_to_power_of_two, Npad in {256, 512, 1024}; else CTCN_EUNSUPPORTED) and return_raw_fft = false
+ * (true: CTCN_EUNSUPPORTED); every refusal comes from ctcn_spectrogram_plan (and again from ctcn_spectrogram before any launch).
+ * ctcn_spectrogram takes ctcn_fbank's arguments with feats (B, Tmax, F) and mean / scale of F floats; lanes store columns lane, lane + 64,
+ * ... of a row; frame counts: ctcn_fbank_frames.  ctcn_cmvn_accumulate takes F = 257 or 513 as it is. */
+typedef struct ctcn_spectrogram_opts {
+  float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff, blackman_coeff, energy_floor;
+  int32_t window_type, remove_dc_offset, round_to_power_of_two, snip_edges, raw_energy, return_raw_fft;
+} ctcn_spectrogram_opts;
+size_t ctcn_spectrogram_plan_bytes(const ctcn_spectrogram_opts *opts);
+int ctcn_spectrogram_plan(const ctcn_spectrogram_opts *opts, void *plan, size_t plan_bytes);
+int ctcn_spectrogram(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_spectrogram_opts *opts, const void *plan,
+                     const float *mean, const float *scale, float *feats, int32_t *frames, int B, int Nmax, int Tmax, float dither, uint64_t seed,
+                     uint64_t utt_offset, void *stream);
+/* The recipe's own spectrogram (timit/local/make_spectrum.py: librosa.stft, magphase, log1p, one mean and one standard deviation per
+ * utterance), as numpy states it.  Options after its audio_conf: sample_rate (16000), window_size (0.025 s), window_stride (0.01 s) --
+ * doubles, because n_fft = int(sample_rate * window_size) and hop = int(sample_rate * window_stride) are Python's double products (a
+ * float32 0.01 gives a hop of 159) --, window: 0 hamming, 1 hann, 2 blackman, 3 bartlett (scipy.signal.windows' SYMMETRIC forms of length
+ * n_fft, which is what librosa gets from the callable), normalize (true), input_scale (1.0): multiplied onto every sample in float32
+ * first (log1p is not scale-free; the reference's loader may hand floats in +-1).  Per utterance of n samples, F = n_fft / 2 + 1:
+ *   1. T = 0 for n = 0, else 1 + n / hop (ctcn_logspec_frames);
+ *   2. frame t = samples t hop - n_fft / 2 .. + n_fft of the signal extended as numpy.pad(mode="reflect") extends it: the edge sample
+ *      is not repeated, the period is 2 (n - 1), folded as often as needed, n = 1 is constant;
+ *   3. the window, kept in float64 and multiplied in float64, an n_fft-point real transform in float64 (half-length complex passes of the radices fbank_core.h lists: 8, 5, 5
+ *      for 400), the magnitude of bins 0 .. n_fft / 2 rounded once to float32, log1pf;
+ *   4. m = the mean and s = the standard deviation (ddof = 0) of all T F values of the utterance, from float64 sums and sums of squares,
+ *      each rounded once to float32; with normalize the output is (x - m) / s, a float32 subtraction and a correctly rounded float32
+ *      division (numpy's np.add(x, -m), np.divide(., s)).  s == 0 (silence, or one value) gives ZEROS: the reference divides 0 by 0 there
+ *      and stores NaN.
+ * feats (B, Tmax, F): rows from frames[b] on are zero; frames (B) int32, at most Tmax; stats (B, 2) float32 = the (m, s) that were applied
+ * or, without normalize, would have been ((0, 0) for an utterance without frames).  An utterance's rows and stats depend on its own samples
+ * alone.  No atomics: the feature kernel leaves one float64 (sum, sum of squares) per workgroup in ws, a second kernel adds an utterance's
+ * partials in index order in every one of its workgroups (the same bits in each), writes stats and normalises in place.
+ * The plan (host, 4-byte words, W = n_fft rounded up to a multiple of 64): [0, 2 W) float64 the window, zeros from n_fft on (so lane-strided
+ * loads of W / 64 registers stay in bounds) -- float64 because a float32 window or product leaves ~1e-3 of absolute noise in every bin, which
+ * log1p shows as 1e-5 in a valley 500 times below the spectrum's level; [2 W, 2 W + 4 n_fft) float64 (cos, -sin)(2 pi k / n_fft), k < n_fft.
+ * Limits: n_fft in {256, 400, 512, 1024}, else CTCN_EUNSUPPORTED; CTCN_EINVAL: NULL, a rate, size, stride or scale that is not positive,
+ * an unknown window, a hop below 1, a buffer smaller than plan_bytes; all from ctcn_logspec_plan, before any launch.  A stride too long
+ * for the LDS staging of one frame is CTCN_EUNSUPPORTED from ctcn_logspec.  wave, wave_is_int16, lens, B, Nmax, Tmax as ctcn_fbank takes
+ * them; there is no dither.
+ * ws: ctcn_logspec_ws_bytes(opts, B, Tmax) bytes, 8-byte aligned. */
+typedef struct ctcn_logspec_opts {
+  double sample_rate, window_size, window_stride;
+  float input_scale;
+  int32_t window, normalize;
+} ctcn_logspec_opts;
+int ctcn_logspec_frames(long long num_samples, int hop);
+size_t ctcn_logspec_plan_bytes(const ctcn_logspec_opts *opts);
+int ctcn_logspec_plan(const ctcn_logspec_opts *opts, void *plan, size_t plan_bytes);
+size_t ctcn_logspec_ws_bytes(const ctcn_logspec_opts *opts, int B, int Tmax);
+int ctcn_logspec(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_logspec_opts *opts, const void *plan, float *feats,
+                 int32_t *frames, float *stats, int B, int Nmax, int Tmax, void *ws, size_t ws_bytes, void *stream);
+/* The transform of both front-ends on the HOST (no HIP call; works without a GPU): power[0 .. n / 2] = |X[k]|^2 of the n real values of
+ * `frame`, n in {256, 400, 512, 1024}, by the kernels' own passes and split step (fbank_core.h) with a loop over the 64 lanes standing in
+ * for the wave.  CTCN_EINVAL for NULL, CTCN_EUNSUPPORTED for another n. */
+int ctcn_fbank_power_host(const double *frame, int n, double *power);
 
 /* ---------------------------------------------------------------------------------------------------
  * CTC prefix beam search with bigram LM; replaces BeamDecoder.decode -> ctcBeamSearch.decode

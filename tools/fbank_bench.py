@@ -2,10 +2,14 @@
 fbank.conf (hamming, 80 bins, energy: 81 dimensions) -- by HIP events, with and without the fused normalisation, and of
 ctcn_cmvn_accumulate on its output; beside it the float32 numpy restatement (tests/fbank_ref.py) on the host's threads.
 
-    python tools/fbank_bench.py [--reps 50] [--rounds 5] [--batch 32] [--seconds 8] [--cpu-threads 16] [--mfcc]
+    python tools/fbank_bench.py [--reps 50] [--rounds 5] [--batch 32] [--seconds 8] [--cpu-threads 16] [--mfcc] [--spectrogram] [--logspec]
 
 --mfcc adds ctcn_mfcc on the same batch to the alternating rounds of the same process: Kaldi's MFCC defaults (23 bins, 13 cepstra) and 80
 bins / 64 cepstra under the filterbank leg's frame options, and ctcn_fbank with the MFCC defaults' 23 bins.
+
+--spectrogram adds ctcn_spectrogram (Kaldi's defaults: 257 columns, three times the filterbank's output) with and without the fused
+normalisation; --logspec adds ctcn_logspec (the recipe's 400-point STFT, 201 columns) raw and normalised -- the normalisation reads and
+writes its output once more, which its algorithmic bytes count.
 
 Per round, alternating: `--reps` back-to-back launches of each variant after a warm-up of all; prints one JSON line with the median and
 the spread of the per-call time over the rounds, the bytes the algorithm has to move (bytes(wave) + 4 F T B) and the rate that makes of
@@ -52,6 +56,8 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--mfcc", action="store_true", help="time ops.mfcc next to ops.fbank in the same rounds")
+    ap.add_argument("--spectrogram", action="store_true", help="time ops.spectrogram (Kaldi's defaults) in the same rounds")
+    ap.add_argument("--logspec", action="store_true", help="time ops.log_spectrum (the recipe's defaults), raw and normalised, in the same rounds")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "fbank_bench.py measures on the GPU only"
     dev = torch.device("cuda:0")
@@ -84,6 +90,18 @@ def main():
         fb23 = features.Fbank(features.FbankConfig(dither=0.0, use_energy=True), dev)
         fns["fbank_int16_23bins"] = lambda: ops.fbank(w16, lens, fb23.plan)
         algo_extra["fbank_int16_23bins"] = 2 * B * N + 4 * fb23.feat_dim * T * B
+    if args.spectrogram:
+        sp = features.Spectrogram(features.SpectrogramConfig(dither=0.0), dev)
+        smean, sscale = torch.full((sp.feat_dim,), 15.0, device=dev), torch.full((sp.feat_dim,), 0.25, device=dev)
+        fns["spectrogram_int16"] = lambda: ops.spectrogram(w16, lens, sp.plan)
+        fns["spectrogram_int16_normalised"] = lambda: ops.spectrogram(w16, lens, sp.plan, mean=smean, scale=sscale)
+        algo_extra["spectrogram_int16"] = algo_extra["spectrogram_int16_normalised"] = 2 * B * N + 4 * sp.feat_dim * sp.num_frames(N) * B
+    if args.logspec:
+        for key, normalize in (("logspec_int16_raw", False), ("logspec_int16_normalised", True)):
+            ls = features.LogSpectrum(features.LogSpecConfig(normalize=normalize), dev)
+            fns[key] = lambda plan=ls.plan: ops.log_spectrum(w16, lens, plan)
+            out_bytes = 4 * ls.feat_dim * ls.num_frames(N) * B
+            algo_extra[key] = 2 * B * N + out_bytes * (3 if normalize else 1)       # normalised: written, read and written again
     for fn in fns.values():
         for _ in range(3):
             fn()
