@@ -114,6 +114,11 @@ _SIGS = {
     "ctcn_logspec_ws_bytes": (Z, [P, I, I]),
     "ctcn_logspec": (I, [P, I, P, P, P, P, P, P, I, I, I, P, Z, P]),
     "ctcn_fbank_power_host": (I, [P, I, P]),
+    "ctcn_resample_samples": (I, [ctypes.c_longlong, I, I]),
+    "ctcn_resample_plan_bytes": (Z, [P]),
+    "ctcn_resample_plan": (I, [P, P, Z]),
+    "ctcn_resample": (I, [P, I, P, P, P, P, I, I, I, P]),
+    "ctcn_resample_host": (I, [P, I, I, P, P, P, I]),
     "ctcn_cmvn_accumulate_ws_bytes": (Z, [I, I, I]),
     "ctcn_cmvn_accumulate": (I, [P, P, P, I, I, I, P, Z, P]),
     "ctcn_comm_unique_id": (I, [P]),
@@ -169,6 +174,11 @@ class LogSpecOpts(ctypes.Structure):
     """ctcn_logspec_opts of include/ctcn.h: the audio_conf of the recipe's make_spectrum.py (utils/features.LogSpecConfig fills it)."""
     _fields_ = [(k, ctypes.c_double) for k in ("sample_rate", "window_size", "window_stride")] + [("input_scale", ctypes.c_float)] + \
                [(k, ctypes.c_int32) for k in ("window", "normalize")]
+
+
+class ResampleOpts(ctypes.Structure):
+    """ctcn_resample_opts of include/ctcn.h: the rates, cutoff and zero crossings of Kaldi's LinearResample (utils/features.Resampler fills it)."""
+    _fields_ = [("cutoff", ctypes.c_double)] + [(k, ctypes.c_int32) for k in ("orig_freq", "new_freq", "num_zeros")]
 
 
 def sources():

@@ -2041,6 +2041,75 @@ def log_spectrum(wave, lengths, plan):
     return feats, frames, stats
 
 
+# resampling in front of the feature kernels (resample.hip): another sample rate, speed perturbation
+def resample_samples(num_samples, orig_freq, new_freq):
+    """Samples a signal of num_samples samples has after resampling from orig_freq to new_freq Hz (ctcn_resample_samples: ceil(n new / orig),
+    Kaldi's count with flush).  Host arithmetic, no device.  ValueError for bad arguments, RuntimeError for a length beyond int32."""
+    r = _lib.lib().ctcn_resample_samples(int(num_samples), int(orig_freq), int(new_freq))
+    if r == -3:
+        _lib.check(r, "resample_samples")
+    if r < 0:
+        raise ValueError("ctc_pytorch_amd.resample_samples: bad arguments (samples %r, rates %r -> %r)" % (num_samples, orig_freq, new_freq))
+    return r
+
+
+class ResamplePlan(object):
+    """The plan of one pair of rates (ctcn_resample_plan: Kaldi's LinearResample filter, one row of float32 weights per output phase): built on
+    the host when the object is made -- a RuntimeError here, before any launch, for what the kernel does not take (a table beyond its LDS
+    budget, a cutoff above the lower Nyquist frequency, num_zeros or a rate that is not positive) -- and uploaded once per device on first
+    use.  cutoff (Hz) defaults to Kaldi's 0.99 * 0.5 * min(rates).  `host` is the block as uint32 words (layout in include/ctcn.h); `first`,
+    `ntaps` (ou) and `weights` (ou, row stride) are numpy views of it: the table the kernel reads.  `tile`: outputs per workgroup."""
+
+    def __init__(self, orig_freq, new_freq, num_zeros=6, cutoff=None):
+        L = _lib.lib()
+        if cutoff is None:
+            cutoff = 0.99 * 0.5 * min(int(orig_freq), int(new_freq))
+        self.opts = opts = _lib.ResampleOpts(cutoff=float(cutoff), orig_freq=int(orig_freq), new_freq=int(new_freq), num_zeros=int(num_zeros))
+        nbytes = L.ctcn_resample_plan_bytes(ctypes.byref(opts))
+        buf = np.zeros(max(nbytes // 4, 8), dtype=np.uint32)
+        _lib.check(L.ctcn_resample_plan(ctypes.byref(opts), buf.ctypes.data_as(ctypes.c_void_p), nbytes), "resample_plan")
+        self.host = buf
+        self.orig_freq, self.new_freq, self.num_zeros, self.cutoff = int(orig_freq), int(new_freq), int(num_zeros), float(cutoff)
+        hdr = buf[:8].view(np.int32)
+        self.ou, self.iu, self.stride, self.max_taps, self.tile = (int(v) for v in hdr[:5])
+        self.first = buf[8:8 + self.ou].view(np.int32)
+        self.ntaps = buf[8 + self.ou:8 + 2 * self.ou].view(np.int32)
+        self.weights = buf[8 + 2 * self.ou:8 + 2 * self.ou + self.ou * self.stride].view(np.float32).reshape(self.ou, self.stride)
+        self._dev = {}
+
+    def num_samples(self, num_samples):
+        return resample_samples(num_samples, self.orig_freq, self.new_freq)
+
+    on = FbankPlan.on
+
+
+def resample(wave, lengths, plan):
+    """A padded batch of waveforms at plan.new_freq (ctcn_resample; the computation, step by step, in include/ctcn.h): wave (B, Nmax) float32
+    or int16 at plan.orig_freq, lengths (B) samples, a list or a tensor (read on the host: the output lengths are host arithmetic), plan a
+    ResamplePlan.  Returns (out (B, Mmax) float32 on the input's scale with zeros from the utterance's length on, out_lengths list of ints),
+    Mmax the largest output length.  No autograd; device tensors only (no CPU fallback)."""
+    if not isinstance(plan, ResamplePlan):
+        raise TypeError("ctc_pytorch_amd.resample: expected a ResamplePlan, got %s" % type(plan).__name__)
+    if wave.dim() != 2:
+        raise ValueError("ctc_pytorch_amd.resample: expected wave (B, Nmax), got %s" % (tuple(wave.shape),))
+    _need_gpu(wave)
+    if wave.dtype not in (torch.float32, torch.int16):
+        raise TypeError("ctc_pytorch_amd.resample: expected float32 or int16 samples, got %s" % wave.dtype)
+    B, Nmax = wave.shape
+    host_lens = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+    if len(host_lens) != B or B == 0:
+        raise ValueError("ctc_pytorch_amd.resample: %d lengths for a batch of %d" % (len(host_lens), B))
+    dev = wave.device
+    wave = wave.contiguous()
+    out_lens = [plan.num_samples(min(max(n, 0), Nmax)) for n in host_lens]
+    Mmax = max(out_lens)
+    lens = torch.as_tensor(host_lens, dtype=torch.int32).to(dev)
+    out = torch.empty((B, Mmax), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().ctcn_resample(_ptr(wave), int(wave.dtype == torch.int16), _ptr(lens), ctypes.byref(plan.opts), _ptr(plan.on(dev)),
+                                        _ptr(out) if Mmax else None, B, Nmax, Mmax, _lib.stream_ptr()), "resample")
+    return out, out_lens
+
+
 def cmvn_accumulate(feats, frames, stats):
     """Adds the rows t < frames[b] of feats (B, Tmax, F) float32 to stats (2, F + 1) float64 on the device, Kaldi's CMVN statistics layout
     (sums | count; sums of squares | 0): ctcn_cmvn_accumulate.  Rows at or beyond frames[b] are never read; float64 partial sums combined

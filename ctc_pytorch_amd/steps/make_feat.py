@@ -8,13 +8,21 @@ normalize, input-scale; an empty file gives its defaults: 201 columns); it norma
 deviation, so --compute-cmvn and --cmvn-stats are refused.
 
     make_feat.py --conf fbank.conf --wav-scp train/wav.scp --out-dir DIR [--cmvn-stats FILE] [--compute-cmvn]
-                 [--feat-type {fbank,mfcc,spectrogram,logspec}]
+                 [--feat-type {fbank,mfcc,spectrogram,logspec}] [--speed-perturb 0.9,1.0,1.1] [--text FILE]
 
 wav.scp: one `<utterance> <path>` per line (RIFF PCM-16 mono or uncompressed SPHERE; piped commands are not run).  Writes DIR/feats.ark and
 DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDataset and both drivers read them unchanged.
   --compute-cmvn   two passes: the first accumulates the global statistics on the device and writes them as Kaldi's text matrix
                    (--cmvn-stats, default DIR/global_<feat type>_cmvn.txt), the second writes features normalised with them (in the kernel)
   --cmvn-stats     without --compute-cmvn: statistics to apply (the training set's, for dev and test data); none: raw features
+  --speed-perturb  Kaldi's speed perturbation (utils/perturb_data_dir_speed.sh): every utterance is written once per factor, under the key
+                   sp<factor as typed>-<utterance>, in wav.scp order with the factors in the order given; factor f resamples on the device
+                   from round(rate * f) to the configured rate (utils/features.SpeedPerturb), 1.0 resamples nothing; --compute-cmvn
+                   accumulates over all copies
+  --text           with --speed-perturb: the label file the loader reads (`<utterance> <labels>` lines), rewritten to DIR/text with the same
+                   key prefixes -- SpeechDataset looks labels up by key, so a perturbed archive needs it
+A file whose sample rate differs from the configuration's is resampled on the device first (utils/features.Resampler, one plan per rate) when
+the conf file holds Kaldi's --allow-downsample (file rate above the configured one) / --allow-upsample (below); otherwise it is an error.
 Utterances are sorted by length and batched under --max-samples padded samples per launch.  Dither is the conf file's (Kaldi's default is
 1.0; `--dither=0` in the conf switches it off), keyed by --seed and the utterance's place in the length-sorted list."""
 import argparse
@@ -30,7 +38,7 @@ if _ROOT not in sys.path:
 
 from ctc_pytorch_amd.utils.data_loader import write_kaldi_ark  # noqa: E402
 from ctc_pytorch_amd.utils.features import (Fbank, FbankConfig, GlobalCMVN, LogSpecConfig, LogSpectrum, Mfcc, MfccConfig, Spectrogram,  # noqa: E402
-                                            SpectrogramConfig, read_wave)
+                                            Resampler, SpectrogramConfig, read_wave)
 
 FEAT_TYPES = {"fbank": (FbankConfig, Fbank), "mfcc": (MfccConfig, Mfcc), "spectrogram": (SpectrogramConfig, Spectrogram),
               "logspec": (LogSpecConfig, LogSpectrum)}
@@ -63,6 +71,76 @@ def length_batches(lengths, max_samples):
     return batches
 
 
+def parse_factors(text):
+    """--speed-perturb's value: [(the factor as typed, its value)], in the order given."""
+    out = []
+    for part in text.split(","):
+        part = part.strip()
+        try:
+            value = float(part)
+        except ValueError:
+            value = 0.0
+        if not (value > 0.0 and value < float("inf")):
+            raise ValueError("--speed-perturb: expected positive factors separated by commas (0.9,1.0,1.1), got %r" % text)
+        out.append((part, value))
+    if len(set(p for p, _ in out)) != len(out):
+        raise ValueError("--speed-perturb: a factor is given twice in %r" % text)
+    return out
+
+
+def perturbed_keys(utts, factors):
+    """The keys of a speed-perturbed list: every utterance once per factor as sp<factor as typed>-<utterance> (Kaldi's prefix), utterances in
+    their order, the factors of one utterance in the order given.  `factors`: parse_factors' list, or None for the list as it is."""
+    if factors is None:
+        return list(utts)
+    return ["sp%s-%s" % (typed, utt) for utt in utts for typed, _ in factors]
+
+
+def perturb_text(lines, factors):
+    """The lines of a label file (`<utterance> <labels>`) for perturbed_keys' list: every line once per factor, the key prefixed, the labels as
+    they are.  Blank lines are dropped."""
+    out = []
+    for line in lines:
+        parts = line.rstrip("\n").split(None, 1)
+        if not parts:
+            continue
+        for key in perturbed_keys([parts[0]], factors):
+            out.append(key + (" " + parts[1] if len(parts) > 1 else "") + "\n")
+    return out
+
+
+def source_rate(utt, path, rate, config):
+    """The rate a file is to be read at: its own, after the check of Kaldi's binaries -- a rate other than the configuration's needs
+    allow_downsample (file rate higher) or allow_upsample (lower) in the configuration, else ValueError."""
+    target = float(config.sample_frequency)
+    if float(rate) == target:
+        return int(rate)
+    option = "allow_downsample" if rate > target else "allow_upsample"
+    if not hasattr(config, option):
+        raise ValueError("%s: %s is sampled at %d Hz, the configuration says %g (no resampling here)" % (utt, path, rate, config.sample_frequency))
+    if not getattr(config, option):
+        raise ValueError("%s: %s is sampled at %d Hz, the configuration says %g (no resampling here: --%s in --conf would allow it)"
+                         % (utt, path, rate, config.sample_frequency, option.replace("_", "-")))
+    if target != int(target):
+        raise ValueError("%s: resampling needs a whole number of Hz as the configured rate, got %g" % (utt, config.sample_frequency))
+    return int(rate)
+
+
+def resample_waves(waves, source_rates, target, device, max_samples):
+    """`waves` (int16 arrays) read at `source_rates` as waveforms at `target` Hz: those already there stay as they are, the others become
+    float32 arrays, resampled on the device with one plan per source rate in length-sorted batches."""
+    out = list(waves)
+    for rate in sorted(set(source_rates) - {target}):
+        idx = [i for i, r in enumerate(source_rates) if r == rate]
+        resampler = Resampler(rate, target, device)
+        for batch in length_batches([waves[i].shape[0] for i in idx], max_samples):
+            res, lens = resampler([waves[idx[j]] for j in batch])
+            host = res.cpu().numpy()
+            for b, j in enumerate(batch):
+                out[idx[j]] = host[b, :lens[b]].copy()
+    return out
+
+
 def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=None):
     """Features of `waves` (list of int16 arrays), batch by batch: {index: (T, F) float32 ndarray}, or -- with `cmvn` -- nothing kept, the raw
     features accumulated into it."""
@@ -93,12 +171,18 @@ def main(argv=None, log=print):
     ap.add_argument("--compute-cmvn", action="store_true", help="accumulate global statistics over this list first, then normalise with them")
     ap.add_argument("--max-samples", type=int, default=32 * 8 * 16000, help="cap on padded samples per launch (default: 32 utterances of 8 s at 16 kHz)")
     ap.add_argument("--seed", type=int, default=0, help="dither seed")
+    ap.add_argument("--speed-perturb", default=None, metavar="FACTORS", help="comma-separated speed factors (Kaldi's 0.9,1.0,1.1): every utterance "
+                    "once per factor under the key sp<factor>-<utterance>")
+    ap.add_argument("--text", default=None, help="with --speed-perturb: label file to rewrite to OUT_DIR/text with the perturbed keys")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
 
     if args.feat_type == "logspec" and (args.compute_cmvn or args.cmvn_stats):
         raise ValueError("--feat-type logspec normalises every utterance by its own mean and standard deviation (normalize in --conf): "
                          "--compute-cmvn and --cmvn-stats do not apply to it")
+    if args.text and not args.speed_perturb:
+        raise ValueError("--text rewrites the label file for --speed-perturb's keys: it needs --speed-perturb")
+    factors = parse_factors(args.speed_perturb) if args.speed_perturb else None
     config_type, frontend_type = FEAT_TYPES[args.feat_type]
     config = config_type.from_kaldi_conf(args.conf)
     device = torch.device(args.device)
@@ -106,12 +190,19 @@ def main(argv=None, log=print):
     entries = read_wav_scp(args.wav_scp)
     if not entries:
         raise ValueError("%s: no utterances" % args.wav_scp)
-    waves = []
+    waves, rates = [], []
     for utt, path in entries:
         samples, rate = read_wave(path)
-        if float(rate) != float(config.sample_frequency):
-            raise ValueError("%s: %s is sampled at %d Hz, the configuration says %g (no resampling here)" % (utt, path, rate, config.sample_frequency))
         waves.append(samples)
+        rates.append(source_rate(utt, path, rate, config))
+    if factors is not None:                                            # every utterance once per factor: the copies stand side by side
+        if float(config.sample_frequency) != int(config.sample_frequency):
+            raise ValueError("--speed-perturb needs a whole number of Hz as the configured rate, got %g" % config.sample_frequency)
+        waves = [w for w in waves for _ in factors]
+        rates = [int(round(r * f)) for r in rates for _, f in factors]
+        entries = [(key, path) for utt, path in entries for key in perturbed_keys([utt], factors)]
+    if any(float(r) != float(config.sample_frequency) for r in rates):
+        waves = resample_waves(waves, rates, int(config.sample_frequency), device, args.max_samples)
     batches = length_batches([w.shape[0] for w in waves], args.max_samples)
     os.makedirs(args.out_dir, exist_ok=True)
 
@@ -132,6 +223,12 @@ def main(argv=None, log=print):
     ark, scp = os.path.join(args.out_dir, "feats.ark"), os.path.join(args.out_dir, "feats.scp")
     write_kaldi_ark(ark, scp, {utt: mats[i] for i, (utt, _) in enumerate(entries)})
     log("wrote %d utterances, %d frames of %d dimensions to %s" % (len(entries), sum(m.shape[0] for m in mats.values()), fbank.feat_dim, ark))
+    if args.text:
+        with open(args.text) as f:
+            lines = perturb_text(f.readlines(), factors)
+        with open(os.path.join(args.out_dir, "text"), "w") as f:
+            f.writelines(lines)
+        log("wrote %d label lines to %s" % (len(lines), os.path.join(args.out_dir, "text")))
     return ark, scp
 
 

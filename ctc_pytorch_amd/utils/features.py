@@ -11,9 +11,11 @@ binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --conf
   LogSpecConfig / LogSpectrum       the recipe's own spectrogram (local/make_spectrum.py: a centred STFT of 400 points, log1p of the magnitude,
                 one mean and standard deviation per utterance; ops.log_spectrum)
   GlobalCMVN    Kaldi's 2 x (F + 1) statistics, accumulated on the device (ops.cmvn_accumulate), its text file, mean and 1 / stddev
+  Resampler     a waveform batch at another sample rate (ops.resample: Kaldi's LinearResample, what its binaries run under --allow-downsample /
+                --allow-upsample); SpeedPerturb: the recipe's three-way speed perturbation (perturb_data_dir_speed.sh) as one Resampler per factor
   read_wave     RIFF PCM-16 mono and uncompressed NIST SPHERE (TIMIT's) -> int16 samples
 
-Not here: pitch, VTLN, deltas, resampling, per-speaker CMVN, compressed SPHERE."""
+Not here: pitch, VTLN, deltas, per-speaker CMVN, compressed SPHERE."""
 import struct
 
 import numpy as np
@@ -27,15 +29,23 @@ LOGSPEC_WINDOWS = ("hamming", "hann", "blackman", "bartlett")                  #
 
 class _KaldiConfig(object):
     """What the config classes share: options under Kaldi's names (dashes as underscores) held as attributes, converted to the types
-    of the class's DEFAULTS, and the reader of Kaldi's `--key=value` files."""
+    of the class's DEFAULTS, and the reader of Kaldi's `--key=value` files.  DEFAULTS holds the options of the feature computation itself;
+    DRIVER_OPTIONS those of Kaldi's binaries around it (allow_downsample, allow_upsample: what to do with a file at another sample rate),
+    read and kept the same way, acted on by steps/make_feat.py and absent from the C structs."""
     DEFAULTS = {}
+    DRIVER_OPTIONS = dict(allow_downsample=False, allow_upsample=False)
+
+    @classmethod
+    def _options(cls):
+        return dict(cls.DEFAULTS, **cls.DRIVER_OPTIONS)
 
     def __init__(self, **kw):
         name = type(self).__name__
+        options = self._options()
         for k in kw:
-            if k not in self.DEFAULTS:
+            if k not in options:
                 raise ValueError("%s: unknown option %r" % (name, k))
-        for k, d in self.DEFAULTS.items():
+        for k, d in options.items():
             setattr(self, k, self._convert(k, kw.get(k, d)))
         self._check_window()
 
@@ -45,7 +55,7 @@ class _KaldiConfig(object):
 
     @classmethod
     def _convert(cls, key, value):
-        d = cls.DEFAULTS[key]
+        d = cls._options()[key]
         if isinstance(d, bool):
             if isinstance(value, str):
                 if value.lower() not in ("true", "false", "t", "f", "1", "0"):
@@ -68,7 +78,7 @@ class _KaldiConfig(object):
                     raise ValueError("%s:%d: expected --key=value, got %r" % (path, ln, line))
                 key, _, value = line[2:].partition("=")
                 key = key.strip().replace("-", "_")
-                if key not in cls.DEFAULTS:
+                if key not in cls._options():
                     raise ValueError("%s:%d: unknown or unsupported option --%s" % (path, ln, key.replace("_", "-")))
                 kw[key] = value.strip() if _ else "true"
         return cls(**kw)
@@ -85,7 +95,9 @@ class _KaldiConfig(object):
 
 class FbankConfig(_KaldiConfig):
     """The options of Kaldi's compute-fbank-feats that the kernel implements, under Kaldi's names (dashes as underscores) and with Kaldi's
-    defaults -- dither = 1.0 among them: pass dither=0 for a deterministic front-end."""
+    defaults -- dither = 1.0 among them: pass dither=0 for a deterministic front-end.  allow_downsample / allow_upsample (Kaldi's, here
+    and in MfccConfig and SpectrogramConfig; both false, in DRIVER_OPTIONS) let steps/make_feat.py resample a file recorded at a higher /
+    lower rate to sample_frequency first (Resampler); they are not options of the kernel and do not enter the C struct."""
     DEFAULTS = dict(sample_frequency=16000.0, frame_shift=10.0, frame_length=25.0, dither=1.0, preemphasis_coefficient=0.97,
                     remove_dc_offset=True, window_type="povey", round_to_power_of_two=True, blackman_coeff=0.42, snip_edges=True,
                     num_mel_bins=23, low_freq=20.0, high_freq=0.0, use_energy=False, energy_floor=0.0, raw_energy=True, htk_compat=False,
@@ -143,6 +155,7 @@ class LogSpecConfig(_KaldiConfig):
     read_wave hands the int16 range).  n_fft = int(sample_rate * window_size), hop = int(sample_rate * window_stride).  from_kaldi_conf
     reads the same `--key=value` lines (`--window-size=0.032`); an empty file gives the defaults."""
     DEFAULTS = dict(sample_rate=16000.0, window_size=0.025, window_stride=0.01, window="hamming", normalize=True, input_scale=1.0)
+    DRIVER_OPTIONS = {}                                                # (make_spectrum.py has no rate options: a mismatch stays an error)
 
     def _check_window(self):
         if self.window not in LOGSPEC_WINDOWS:
@@ -252,6 +265,57 @@ class LogSpectrum(object):
         standard deviation of each utterance) on the device."""
         waves, lengths = _batch("LogSpectrum", waves, lengths)
         return ops.log_spectrum(waves.to(self.device), lengths, self.plan)
+
+
+class Resampler(object):
+    """Waveforms at orig_freq Hz -> new_freq Hz on one device (ops.resample: Kaldi's LinearResample with ResampleWaveform's parameters: a
+    Hann-windowed sinc of lowpass_filter_width zero crossings, cutoff = cutoff_ratio * 0.5 * min(rates)).  Building it builds the plan: a
+    pair of rates whose filter table does not fit the kernel's LDS budget raises RuntimeError here.  Equal rates build nothing and pass the
+    batch through."""
+
+    def __init__(self, orig_freq, new_freq, device, lowpass_filter_width=6, cutoff_ratio=0.99):
+        if int(orig_freq) != orig_freq or int(new_freq) != new_freq:
+            raise ValueError("Resampler: sample rates must be whole numbers of Hz, got %r -> %r" % (orig_freq, new_freq))
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.device = torch.device(device)
+        self.plan = None
+        if self.orig_freq != self.new_freq:
+            self.plan = ops.ResamplePlan(self.orig_freq, self.new_freq, num_zeros=lowpass_filter_width,
+                                         cutoff=cutoff_ratio * 0.5 * min(self.orig_freq, self.new_freq))
+
+    def num_samples(self, num_samples):
+        return int(num_samples) if self.plan is None else self.plan.num_samples(num_samples)
+
+    def __call__(self, waves, lengths=None):
+        """waves as Fbank takes them.  Returns (out (B, Mmax) float32 zero-padded on the device, lengths list): any front-end's (waves, lengths)
+        form.  Samples stay on the input's scale.  Equal rates: the batch as it came (int16 stays int16), moved to the device."""
+        waves, lengths = _batch("Resampler", waves, lengths)
+        waves = waves.to(self.device)
+        if self.plan is None:
+            return waves, [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        return ops.resample(waves, lengths, self.plan)
+
+
+class SpeedPerturb(object):
+    """Kaldi's speed perturbation (utils/perturb_data_dir_speed.sh: sox `speed f`, factors 0.9 / 1.0 / 1.1) at one sample rate: perturbing by
+    f is resampling from round(sample_frequency * f) to sample_frequency and reading the result at sample_frequency -- ceil(n / f) samples,
+    pitch and tempo both scaled by f.  One Resampler per factor, built here; factor 1.0 is the identity."""
+
+    def __init__(self, sample_frequency, factors=(0.9, 1.0, 1.1), device="cuda:0"):
+        if int(sample_frequency) != sample_frequency:
+            raise ValueError("SpeedPerturb: the sample rate must be a whole number of Hz, got %r" % (sample_frequency,))
+        self.sample_frequency = int(sample_frequency)
+        self.factors = tuple(float(f) for f in factors)
+        if not self.factors or any(not f > 0 for f in self.factors):
+            raise ValueError("SpeedPerturb: factors must be positive, got %r" % (factors,))
+        self.resamplers = {f: Resampler(int(round(self.sample_frequency * f)), self.sample_frequency, device) for f in self.factors}
+
+    def __call__(self, waves, factor, lengths=None):
+        """The batch perturbed by `factor`, one of self.factors: Resampler's call and return."""
+        r = self.resamplers.get(float(factor))
+        if r is None:
+            raise ValueError("SpeedPerturb: factor %r is not one of %r" % (factor, self.factors))
+        return r(waves, lengths)
 
 
 class GlobalCMVN(object):

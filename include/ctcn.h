@@ -576,7 +576,7 @@ int ctcn_step_stats(const float *loss, const int32_t *dist, const int64_t *tgt_l
  * binaries of timit/steps/make_feat.sh (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true).
  * The computation is Kaldi's, as its feature-window, feature-fbank and mel-computations sources document it; option names and defaults are
  * Kaldi's.  window_type: 0 hamming, 1 hanning, 2 povey (Kaldi's default), 3 rectangular, 4 blackman.  high_freq <= 0 is an offset from Nyquist.
- * Not here: VTLN, deltas, resampling (MFCC: ctcn_mfcc below; the spectrogram types: ctcn_spectrogram, ctcn_logspec below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
+ * Not here: VTLN, deltas (MFCC: ctcn_mfcc below; the spectrogram types: ctcn_spectrogram, ctcn_logspec below; resampling in front of them: ctcn_resample below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
  * defaults). */
 typedef struct ctcn_fbank_opts {
   float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff, blackman_coeff, low_freq, high_freq, energy_floor;
@@ -719,6 +719,46 @@ int ctcn_logspec(const void *wave, int wave_is_int16, const int32_t *lens, const
  * `frame`, n in {256, 400, 512, 1024}, by the kernels' own passes and split step (fbank_core.h) with a loop over the 64 lanes standing in
  * for the wave.  CTCN_EINVAL for NULL, CTCN_EUNSUPPORTED for another n. */
 int ctcn_fbank_power_host(const double *frame, int n, double *power);
+/* Waveform resampling in front of the feature kernels (resample.hip): Kaldi's LinearResample as its ResampleWaveform configures it -- what
+ * the Kaldi binaries run under --allow-downsample / --allow-upsample -- and, read at the original rate, the recipe's speed perturbation:
+ * perturbing by factor f at rate sr is orig_freq = round(sr f), new_freq = sr (ceil(n / f) samples; sox `speed f` with this filter).
+ * Options: integer rates fin = orig_freq and fout = new_freq in Hz, cutoff in Hz (ResampleWaveform: 0.99 * 0.5 * min(fin, fout)), num_zeros
+ * (ResampleWaveform: 6); utils/features.Resampler holds those defaults.  With g = gcd(fin, fout), iu = fin / g input and ou = fout / g output
+ * samples per unit (ou = the number of filter phases) and ww = num_zeros / (2 cutoff):
+ *   1. the plan, on the host in double, for every phase i < ou: t = i / fout; lo = ceil((t - ww) fin), hi = floor((t + ww) fin);
+ *      first[i] = lo (may be negative), ntaps[i] = hi - lo + 1; for j < ntaps[i]: dt = (lo + j) / fin - t,
+ *      w[i][j] = filt(dt) win(dt) / fin rounded once to float32 (Kaldi's storage type), with
+ *      win(dt) = 0.5 (1 + cos(2 pi cutoff / num_zeros dt)) for |dt| < ww, else 0, and filt(dt) = sin(2 pi cutoff dt) / (pi dt), 2 cutoff at 0;
+ *   2. the output length (Kaldi's flush = true): ceil(n fout / fin) in integer arithmetic, 0 for n = 0 (ctcn_resample_samples;
+ *      CTCN_EINVAL for a negative count or a rate that is not positive, CTCN_EUNSUPPORTED for a length beyond int);
+ *   3. output sample k, u = k / ou, p = k % ou: y[k] = sum_j w[p][j] x[first[p] + u iu + j], j ascending, samples outside [0, n) counting
+ *      as zero and never read; accumulated in float64 from the float32 weights and float32 samples (int16 converted exactly) and rounded
+ *      once to float32.  A float32 product is exact in double, so the sum is one number with or without fused multiply-adds: numpy's
+ *      ascending double sum over the plan's weights gives the same bits.  Output stays on the input's scale; nothing is rounded to int16.
+ * The plan block (host, 4-byte words): [0, 8) int32 ou, iu, the weight row stride S (the longest tap count made odd: lanes on neighbouring
+ * phases meet different LDS banks), the longest tap count, outputs per workgroup tile (a multiple of ou, at most 2048 unless ou is larger),
+ * the smallest first[], staged input samples per tile, 0; [8, 8 + ou) int32 first; [8 + ou, 8 + 2 ou) int32 ntaps; [8 + 2 ou, + ou S) float
+ * the weights, row p at p S, zeros behind ntaps[p].
+ * ctcn_resample: wave (B, Nmax) float32 or, with wave_is_int16, int16; lens (B) int32 samples clamped to [0, Nmax]; opts on the host, plan
+ * the block in DEVICE memory; out (B, Mmax) float32: the first min(ceil(lens[b] fout / fin), Mmax) values of row b are the samples, the
+ * rest of the row zeros.  One launch, grid (tiles of Mmax, B): the workgroup stages the table and the tile's input span in LDS, every lane
+ * computes whole outputs.  A row depends on its own samples alone, not on B, Nmax, Mmax or its neighbours.
+ * Limits, all CTCN_EUNSUPPORTED from ctcn_resample_plan (plan_bytes: 0) and again from ctcn_resample before any launch: rates that are not
+ * positive or beyond 2^24, num_zeros <= 0, a cutoff that is not positive or with 2 cutoff > min(fin, fout), a table of ou S floats beyond
+ * 24 576 (96 KB of LDS) or one unit's reach of input samples beyond 8192.  CTCN_EINVAL: NULL, B outside [1, 65 535], a small buffer.
+ * ctcn_resample_host: the same sum for ONE utterance on the HOST (no HIP call; works without a GPU), `plan` the host block of the same
+ * options; returns the number of samples written (out_cap must hold them) or an error code. */
+typedef struct ctcn_resample_opts {
+  double cutoff;
+  int32_t orig_freq, new_freq, num_zeros;
+} ctcn_resample_opts;
+int ctcn_resample_samples(long long num_samples, int orig_freq, int new_freq);
+size_t ctcn_resample_plan_bytes(const ctcn_resample_opts *opts);
+int ctcn_resample_plan(const ctcn_resample_opts *opts, void *plan, size_t plan_bytes);
+int ctcn_resample(const void *wave, int wave_is_int16, const int32_t *lens, const ctcn_resample_opts *opts, const void *plan, float *out, int B,
+                  int Nmax, int Mmax, void *stream);
+int ctcn_resample_host(const void *wave, int wave_is_int16, int num_samples, const ctcn_resample_opts *opts, const void *plan, float *out,
+                       int out_cap);
 
 /* ---------------------------------------------------------------------------------------------------
  * CTC prefix beam search with bigram LM; replaces BeamDecoder.decode -> ctcBeamSearch.decode

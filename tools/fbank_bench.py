@@ -3,6 +3,7 @@ fbank.conf (hamming, 80 bins, energy: 81 dimensions) -- by HIP events, with and 
 ctcn_cmvn_accumulate on its output; beside it the float32 numpy restatement (tests/fbank_ref.py) on the host's threads.
 
     python tools/fbank_bench.py [--reps 50] [--rounds 5] [--batch 32] [--seconds 8] [--cpu-threads 16] [--mfcc] [--spectrogram] [--logspec]
+                                [--resample]
 
 --mfcc adds ctcn_mfcc on the same batch to the alternating rounds of the same process: Kaldi's MFCC defaults (23 bins, 13 cepstra) and 80
 bins / 64 cepstra under the filterbank leg's frame options, and ctcn_fbank with the MFCC defaults' 23 bins.
@@ -10,6 +11,10 @@ bins / 64 cepstra under the filterbank leg's frame options, and ctcn_fbank with 
 --spectrogram adds ctcn_spectrogram (Kaldi's defaults: 257 columns, three times the filterbank's output) with and without the fused
 normalisation; --logspec adds ctcn_logspec (the recipe's 400-point STFT, 201 columns) raw and normalised -- the normalisation reads and
 writes its output once more, which its algorithmic bytes count.
+
+--resample adds ctcn_resample on the same int16 batch read at 14400, 17600 (speed factors 0.9 and 1.1) and 44100 Hz, each to 16 kHz, and
+the chain resample + filterbank (0.9: the float32 output fed to ctcn_fbank with its lengths); beside the bytes, the LDS reads the sums
+need (two 4-byte reads per tap and lane) and the float32 numpy restatement of the three pairs on the host's threads.
 
 Per round, alternating: `--reps` back-to-back launches of each variant after a warm-up of all; prints one JSON line with the median and
 the spread of the per-call time over the rounds, the bytes the algorithm has to move (bytes(wave) + 4 F T B) and the rate that makes of
@@ -29,6 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import fbank_ref                                                   # noqa: E402
+import resample_ref                                                # noqa: E402
 from ctc_pytorch_amd import ops                                    # noqa: E402
 from ctc_pytorch_amd.utils import features                         # noqa: E402
 
@@ -58,6 +64,7 @@ def main():
     ap.add_argument("--mfcc", action="store_true", help="time ops.mfcc next to ops.fbank in the same rounds")
     ap.add_argument("--spectrogram", action="store_true", help="time ops.spectrogram (Kaldi's defaults) in the same rounds")
     ap.add_argument("--logspec", action="store_true", help="time ops.log_spectrum (the recipe's defaults), raw and normalised, in the same rounds")
+    ap.add_argument("--resample", action="store_true", help="time ops.resample (14400, 17600, 44100 -> 16000 Hz) and resample + fbank in the same rounds")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "fbank_bench.py measures on the GPU only"
     dev = torch.device("cuda:0")
@@ -102,6 +109,22 @@ def main():
             fns[key] = lambda plan=ls.plan: ops.log_spectrum(w16, lens, plan)
             out_bytes = 4 * ls.feat_dim * ls.num_frames(N) * B
             algo_extra[key] = 2 * B * N + out_bytes * (3 if normalize else 1)       # normalised: written, read and written again
+    lds_reads = {}
+    if args.resample:
+        plans = {fin: ops.ResamplePlan(fin, 16000) for fin in (14400, 17600, 44100)}
+        for fin, plan in plans.items():
+            key = "resample_int16_%d_16000" % fin
+            fns[key] = lambda plan=plan: ops.resample(w16, lens, plan)
+            outs = [plan.num_samples(n) for n in lens]
+            algo_extra[key] = 2 * sum(lens) + 4 * B * max(outs)                     # the samples once, the padded output once
+            lds_reads[key] = 8 * int(sum((m // plan.ou) * int(plan.ntaps.sum()) + int(plan.ntaps[:m % plan.ou].sum()) for m in outs))
+
+        def chain(plan=plans[14400]):
+            w, wl = ops.resample(w16, lens, plan)
+            return ops.fbank(w, wl, fb.plan)
+        fns["resample_14400_16000_then_fbank"] = chain
+        m09 = plans[14400].num_samples(N)
+        algo_extra["resample_14400_16000_then_fbank"] = algo_extra["resample_int16_14400_16000"] + 4 * B * m09 + 4 * F * fb.num_frames(m09) * B
     for fn in fns.values():
         for _ in range(3):
             fn()
@@ -118,6 +141,22 @@ def main():
     algo.update(algo_extra)
     out["algorithmic_bytes"] = algo
     out["algorithmic_GBps_at_median"] = {k: round(algo[k] / (out["us_per_call"][k]["median"] * 1e-6) / 1e9, 1) for k in algo}
+    if lds_reads:
+        out["resample_lds_read_bytes"] = lds_reads
+        out["resample_lds_read_TBps_at_median"] = {k: round(v / (out["us_per_call"][k]["median"] * 1e-6) / 1e12, 2) for k, v in lds_reads.items()}
+    if args.resample and not args.no_cpu:
+        cpu = {}
+        with ThreadPoolExecutor(max_workers=args.cpu_threads) as pool:
+            for fin, plan in plans.items():
+                one = lambda b: resample_ref.resample(host[b, :lens[b]], fin, 16000, plan.first, plan.ntaps, plan.weights)
+                list(pool.map(one, range(min(B, args.cpu_threads))))                 # warm-up
+                ts = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    list(pool.map(one, range(B)))
+                    ts.append((time.perf_counter() - t0) * 1e6)
+                cpu["resample_int16_%d_16000" % fin] = spread(ts)
+        out["cpu_resample_restatement_us"] = dict(cpu, threads=args.cpu_threads)
     if not args.no_cpu:
         o = fbank_ref.options(**kw)
         waves = [host[b, :lens[b]].astype(np.float32) for b in range(B)]
