@@ -119,6 +119,11 @@ _SIGS = {
     "ctcn_resample_plan": (I, [P, P, Z]),
     "ctcn_resample": (I, [P, I, P, P, P, P, I, I, I, P]),
     "ctcn_resample_host": (I, [P, I, I, P, P, P, I]),
+    "ctcn_context_frames": (I, [I, I, I]),
+    "ctcn_delta_scales": (I, [I, I, P]),
+    "ctcn_frame_context_tile": (I, [P, I]),
+    "ctcn_frame_context": (I, [P, P, P, P, P, P, I, I, I, I, P]),
+    "ctcn_frame_context_host": (I, [P, I, I, P, P, I, P]),
     "ctcn_cmvn_accumulate_ws_bytes": (Z, [I, I, I]),
     "ctcn_cmvn_accumulate": (I, [P, P, P, I, I, I, P, Z, P]),
     "ctcn_comm_unique_id": (I, [P]),
@@ -179,6 +184,11 @@ class LogSpecOpts(ctypes.Structure):
 class ResampleOpts(ctypes.Structure):
     """ctcn_resample_opts of include/ctcn.h: the rates, cutoff and zero crossings of Kaldi's LinearResample (utils/features.Resampler fills it)."""
     _fields_ = [("cutoff", ctypes.c_double)] + [(k, ctypes.c_int32) for k in ("orig_freq", "new_freq", "num_zeros")]
+
+
+class ContextOpts(ctypes.Structure):
+    """ctcn_context_opts of include/ctcn.h: splice, skip, downsample pad and deltas (utils/features.FrameContext fills it)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("left", "right", "skip", "n_downsample", "delta_order", "delta_window")]
 
 
 def sources():

@@ -2110,6 +2110,72 @@ def resample(wave, lengths, plan):
     return out, out_lens
 
 
+# deltas, splice, skip and the downsample pad behind the feature kernels (context.hip): base features -> the batch the model consumes
+def context_frames(num_frames, skip=1, n_downsample=1):
+    """Rows an utterance of num_frames frames has after frame skipping and the pad to a multiple of n_downsample (ctcn_context_frames:
+    ceil(T / skip) rounded up; skip 0 and 1 keep every frame).  Host arithmetic, no device.  ValueError for bad arguments."""
+    r = _lib.lib().ctcn_context_frames(int(num_frames), int(skip), int(n_downsample))
+    if r < 0:
+        raise ValueError("ctc_pytorch_amd.context_frames: bad arguments (frames %r, skip %r, n_downsample %r)" % (num_frames, skip, n_downsample))
+    return r
+
+
+def delta_scales(order, window=2):
+    """Kaldi's delta filter of one order (ctcn_delta_scales): 2 * order * window + 1 float32 values, built on the host as DeltaFeatures builds
+    them.  No device."""
+    buf = np.zeros(2 * max(int(order), 0) * max(int(window), 0) + 1, dtype=np.float32)
+    r = _lib.lib().ctcn_delta_scales(int(order), int(window), buf.ctypes.data_as(ctypes.c_void_p))
+    if r < 0:
+        _lib.check(r, "delta_scales")
+    return buf
+
+
+def _context_opts(left, right, skip, n_downsample, delta_order, delta_window):
+    return _lib.ContextOpts(left=int(left), right=int(right), skip=int(skip), n_downsample=int(n_downsample), delta_order=int(delta_order),
+                            delta_window=int(delta_window))
+
+
+def frame_context_tile(feat_dim, left=0, right=0, skip=1, n_downsample=1, delta_order=0, delta_window=2):
+    """Output rows one workgroup of frame_context writes under these options (ctcn_frame_context_tile).  RuntimeError for options outside the
+    kernel's limits.  No device."""
+    r = _lib.lib().ctcn_frame_context_tile(ctypes.byref(_context_opts(left, right, skip, n_downsample, delta_order, delta_window)), int(feat_dim))
+    if r < 0:
+        _lib.check(r, "frame_context_tile")
+    return r
+
+
+def frame_context(feats, frames, left=0, right=0, skip=1, n_downsample=1, delta_order=0, delta_window=2):
+    """Deltas, frame splicing, frame skipping and the downsample pad of a zero-padded base batch in one launch (ctcn_frame_context; the
+    computation, step by step, in include/ctcn.h): feats (B, Tin_max, F) float32, frames (B) the utterances' frame counts -- a list or a
+    device tensor (what Fbank returns), clamped to [0, Tin_max]; rows at or beyond them are never read.  Returns (out (B, Tout_max, F2)
+    float32, out_frames (B) int32, fractions (B) float32 = out_frames / Tout_max as the host collate stores them) on the device, with
+    F2 = (left + 1 + right) * F * (delta_order + 1) and Tout_max = context_frames(Tin_max, skip, n_downsample): sized from the input's
+    shape, nothing is read back from the device.  No autograd; device tensors only (no CPU fallback)."""
+    if not torch.is_tensor(feats) or feats.dim() != 3:
+        raise ValueError("ctc_pytorch_amd.frame_context: expected feats (B, Tin_max, F), got %s" % (tuple(feats.shape) if torch.is_tensor(feats) else type(feats).__name__,))
+    _need_gpu(feats, frames if torch.is_tensor(frames) else None)
+    if feats.dtype != torch.float32:
+        raise TypeError("ctc_pytorch_amd.frame_context: expected float32 features, got %s" % feats.dtype)
+    B, Tin_max, F = feats.shape
+    dev = feats.device
+    if torch.is_tensor(frames):
+        frames = frames.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        frames = torch.as_tensor([int(v) for v in frames], dtype=torch.int32).to(dev)
+    if frames.numel() != B or B == 0 or F == 0:
+        raise ValueError("ctc_pytorch_amd.frame_context: %d frame counts for a batch of %s" % (frames.numel(), tuple(feats.shape)))
+    opts = _context_opts(left, right, skip, n_downsample, delta_order, delta_window)
+    _lib.check(min(_lib.lib().ctcn_frame_context_tile(ctypes.byref(opts), F), 0), "frame_context")     # the limits, before anything is allocated
+    Tout_max = context_frames(Tin_max, skip, n_downsample)
+    feats = feats.contiguous()
+    out = torch.empty((B, Tout_max, (opts.left + 1 + opts.right) * F * (opts.delta_order + 1)), dtype=torch.float32, device=dev)
+    out_frames = torch.empty(B, dtype=torch.int32, device=dev)
+    fractions = torch.empty(B, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().ctcn_frame_context(_ptr(feats) if Tin_max else None, _ptr(frames), ctypes.byref(opts), _ptr(out) if Tout_max else None,
+                                             _ptr(out_frames), _ptr(fractions), B, Tin_max, F, Tout_max, _lib.stream_ptr()), "frame_context")
+    return out, out_frames, fractions
+
+
 def cmvn_accumulate(feats, frames, stats):
     """Adds the rows t < frames[b] of feats (B, Tmax, F) float32 to stats (2, F + 1) float64 on the device, Kaldi's CMVN statistics layout
     (sums | count; sums of squares | 0): ctcn_cmvn_accumulate.  Rows at or beyond frames[b] are never read; float64 partial sums combined

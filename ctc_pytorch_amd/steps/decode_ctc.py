@@ -25,6 +25,10 @@ keeps the entries and hands the loop the strings put together from their tokens 
 `_recorded` notes the loader's utterance ids in loader order, which is decode order.  A token's frames are output frames times `input_frames_per_output_frame(model)` (the front-end geometry
 CTC_Model.output_lengths uses) times the loader's frame skip (`n_skip_frame`).  Under torchrun rank r writes PATH.r (its own minibatches).
 The CER / WER lines and the return value do not change.
+
+Key `device_context` (--device-context; default off): the test archive is read as BASE features and left_ctx / right_ctx / n_skip_frame /
+n_downsample are applied on the GPU (utils/data_loader.DeviceContext: one launch per batch on the copy stream); the loop sees the batches the
+host loader would have made, bit for bit.
 """
 import argparse
 import os
@@ -39,7 +43,7 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from ctc_pytorch_amd.steps import test_ctc  # noqa: E402
-from ctc_pytorch_amd.steps.train_ctc import epoch_options, input_frames_from_fraction, report_options  # noqa: E402
+from ctc_pytorch_amd.steps.train_ctc import device_context, epoch_options, input_frames_from_fraction, report_options  # noqa: E402
 
 
 class _Batch(torch.Tensor):
@@ -82,6 +86,13 @@ def _length_aware_batches(model, loader):
 def length_aware(model, loader):
     """(model, loader) for steps/test_ctc.decode_and_score[_sharded] with the utterance lengths passed to the model (module docstring)."""
     return _LengthAwareModel(model), _length_aware_batches(model, loader)
+
+
+def _labels_on_host(loader):
+    """A device-staged loader as the scoring loop reads it: inputs stay on the device, the length fractions and the labels (a few hundred
+    bytes, which the loop turns into strings on the host) come back."""
+    for batch in loader:
+        yield (batch[0], batch[1].cpu(), batch[2].cpu(), batch[3].cpu()) + tuple(batch[4:])
 
 
 class _ScoringDecoder(object):
@@ -232,6 +243,8 @@ def apply_argv(conf, a):
         conf["ctm"] = a.ctm
     if a.ctm_frame_shift is not None:
         conf["ctm_frame_shift"] = a.ctm_frame_shift
+    if a.device_context:
+        conf["device_context"] = True
     return conf
 
 
@@ -244,6 +257,7 @@ def arg_parser():
     ap.add_argument("--score-map-cols", default=None, choices=["60-48", "60-39", "48-39"], help="which fold of the table (default: the YAML's score_map_cols, else 48-39)")
     ap.add_argument("--ctm", default=None, metavar="PATH", help="write the recognised tokens with start, duration and confidence to this NIST CTM file (default: the YAML's ctm, else off)")
     ap.add_argument("--ctm-frame-shift", default=None, type=float, help="seconds per model input frame (default: the YAML's ctm_frame_shift, else 0.01)")
+    ap.add_argument("--device-context", action="store_true", help="read the archive as base features and splice / skip / pad on the GPU (default: the YAML's device_context, else off)")
     return ap
 
 
@@ -256,7 +270,8 @@ def main(conf, test_loader=None, index2word=None, log=print):
         setattr(opts, k, v)
     report = bool(getattr(opts, "error_report", False))
     ctm = ctm_options(opts)
-    if not epoch_options(opts) and not report and not ctm:
+    context = device_context(opts)
+    if not epoch_options(opts) and not report and not ctm and context is None:
         return test_ctc.main(conf, test_loader=test_loader, index2word=index2word, log=log)
     if not getattr(opts, "use_gpu", True):
         raise RuntimeError("ctc_pytorch_amd: use_gpu must be True -- the HIP path has no CPU fallback")
@@ -267,8 +282,16 @@ def main(conf, test_loader=None, index2word=None, log=print):
         from ctc_pytorch_amd.utils.data_loader import SpeechDataLoader, SpeechDataset, Vocab
         vocab = Vocab(opts.vocab_file)
         index2word = vocab.index2word
-        test_loader = SpeechDataLoader(SpeechDataset(vocab, opts.test_scp_path, opts.test_lab_path, opts), batch_size=opts.batch_size,
-                                       shuffle=False, num_workers=opts.num_workers)
+        if context is None:
+            test_loader = SpeechDataLoader(SpeechDataset(vocab, opts.test_scp_path, opts.test_lab_path, opts), batch_size=opts.batch_size,
+                                           shuffle=False, num_workers=opts.num_workers)
+        else:
+            from ctc_pytorch_amd.utils.data_loader import BaseFeatureLoader
+            test_loader = BaseFeatureLoader(SpeechDataset(vocab, opts.test_scp_path, opts.test_lab_path, opts, base_features=True),
+                                            batch_size=opts.batch_size, shuffle=False, num_workers=opts.num_workers)
+    if context is not None:                                # (a loader handed in must be a base-feature loader too)
+        from ctc_pytorch_amd.utils.data_loader import DeviceContext
+        test_loader = _labels_on_host(DeviceContext(test_loader, device, context))
     decoder = test_ctc.make_decoder(opts, index2word)
     stats = class_map = None
     if report:

@@ -9,6 +9,7 @@ deviation, so --compute-cmvn and --cmvn-stats are refused.
 
     make_feat.py --conf fbank.conf --wav-scp train/wav.scp --out-dir DIR [--cmvn-stats FILE] [--compute-cmvn]
                  [--feat-type {fbank,mfcc,spectrogram,logspec}] [--speed-perturb 0.9,1.0,1.1] [--text FILE]
+                 [--delta-order N [--delta-window W]]
 
 wav.scp: one `<utterance> <path>` per line (RIFF PCM-16 mono or uncompressed SPHERE; piped commands are not run).  Writes DIR/feats.ark and
 DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDataset and both drivers read them unchanged.
@@ -21,6 +22,10 @@ DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDatase
                    accumulates over all copies
   --text           with --speed-perturb: the label file the loader reads (`<utterance> <labels>` lines), rewritten to DIR/text with the same
                    key prefixes -- SpeechDataset looks labels up by key, so a perturbed archive needs it
+  --delta-order    Kaldi's add-deltas (its option names; --delta-window defaults to 2): N orders of delta features are appended to every frame,
+                   13 cepstra becoming the usual 39 with N = 2.  As in Kaldi's pipelines they are taken AFTER the normalisation, from the
+                   normalised base features, on the device (utils/features.FrameContext with no splice); the CMVN statistics are those of
+                   the base features.  0 (the default): none
 A file whose sample rate differs from the configuration's is resampled on the device first (utils/features.Resampler, one plan per rate) when
 the conf file holds Kaldi's --allow-downsample (file rate above the configured one) / --allow-upsample (below); otherwise it is an error.
 Utterances are sorted by length and batched under --max-samples padded samples per launch.  Dither is the conf file's (Kaldi's default is
@@ -37,8 +42,8 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from ctc_pytorch_amd.utils.data_loader import write_kaldi_ark  # noqa: E402
-from ctc_pytorch_amd.utils.features import (Fbank, FbankConfig, GlobalCMVN, LogSpecConfig, LogSpectrum, Mfcc, MfccConfig, Spectrogram,  # noqa: E402
-                                            Resampler, SpectrogramConfig, read_wave)
+from ctc_pytorch_amd.utils.features import (Fbank, FbankConfig, FrameContext, GlobalCMVN, LogSpecConfig, LogSpectrum, Mfcc, MfccConfig,  # noqa: E402
+                                            Spectrogram, Resampler, SpectrogramConfig, read_wave)
 
 FEAT_TYPES = {"fbank": (FbankConfig, Fbank), "mfcc": (MfccConfig, Mfcc), "spectrogram": (SpectrogramConfig, Spectrogram),
               "logspec": (LogSpecConfig, LogSpectrum)}
@@ -141,9 +146,9 @@ def resample_waves(waves, source_rates, target, device, max_samples):
     return out
 
 
-def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=None):
+def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=None, deltas=None):
     """Features of `waves` (list of int16 arrays), batch by batch: {index: (T, F) float32 ndarray}, or -- with `cmvn` -- nothing kept, the raw
-    features accumulated into it."""
+    features accumulated into it.  deltas (a FrameContext without splice or skip): applied to the normalised features that are kept."""
     mats, place = {}, 0
     for idx in batches:
         if isinstance(fbank, LogSpectrum):                             # normalised per utterance by the call itself; no dither
@@ -154,6 +159,8 @@ def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=Non
         if cmvn is not None:
             cmvn.accumulate(feats, frames)
             continue
+        if deltas is not None:
+            feats, frames, _ = deltas(feats, frames)
         host, n = feats.cpu().numpy(), frames.cpu().numpy()
         for b, i in enumerate(idx):
             mats[i] = host[b, :n[b]].copy()
@@ -174,6 +181,8 @@ def main(argv=None, log=print):
     ap.add_argument("--speed-perturb", default=None, metavar="FACTORS", help="comma-separated speed factors (Kaldi's 0.9,1.0,1.1): every utterance "
                     "once per factor under the key sp<factor>-<utterance>")
     ap.add_argument("--text", default=None, help="with --speed-perturb: label file to rewrite to OUT_DIR/text with the perturbed keys")
+    ap.add_argument("--delta-order", type=int, default=0, help="append this many orders of delta features (Kaldi's add-deltas; 0: none)")
+    ap.add_argument("--delta-window", type=int, default=2, help="add-deltas' window: the delta filter reaches this many frames to either side")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
 
@@ -182,6 +191,9 @@ def main(argv=None, log=print):
                          "--compute-cmvn and --cmvn-stats do not apply to it")
     if args.text and not args.speed_perturb:
         raise ValueError("--text rewrites the label file for --speed-perturb's keys: it needs --speed-perturb")
+    if not 0 <= args.delta_order <= 2 or not 1 <= args.delta_window <= 5:
+        raise ValueError("--delta-order takes 0, 1 or 2 and --delta-window 1 to 5, got %d and %d" % (args.delta_order, args.delta_window))
+    deltas = FrameContext(delta_order=args.delta_order, delta_window=args.delta_window) if args.delta_order else None
     factors = parse_factors(args.speed_perturb) if args.speed_perturb else None
     config_type, frontend_type = FEAT_TYPES[args.feat_type]
     config = config_type.from_kaldi_conf(args.conf)
@@ -219,10 +231,11 @@ def main(argv=None, log=print):
         if cmvn.feat_dim != fbank.feat_dim:
             raise ValueError("%s holds statistics of %d dimensions, the configuration gives %d" % (args.cmvn_stats, cmvn.feat_dim, fbank.feat_dim))
         mean, scale = cmvn.mean_scale(device)
-    mats = make_features(fbank, waves, batches, mean=mean, scale=scale, seed=args.seed)
+    mats = make_features(fbank, waves, batches, mean=mean, scale=scale, seed=args.seed, deltas=deltas)
     ark, scp = os.path.join(args.out_dir, "feats.ark"), os.path.join(args.out_dir, "feats.scp")
     write_kaldi_ark(ark, scp, {utt: mats[i] for i, (utt, _) in enumerate(entries)})
-    log("wrote %d utterances, %d frames of %d dimensions to %s" % (len(entries), sum(m.shape[0] for m in mats.values()), fbank.feat_dim, ark))
+    log("wrote %d utterances, %d frames of %d dimensions to %s" % (len(entries), sum(m.shape[0] for m in mats.values()),
+                                                                          fbank.feat_dim if deltas is None else deltas.out_dim(fbank.feat_dim), ark))
     if args.text:
         with open(args.text) as f:
             lines = perturb_text(f.readlines(), factors)

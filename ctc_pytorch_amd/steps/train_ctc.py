@@ -195,6 +195,16 @@ def epoch_options(opts):
     return {"mask_padding": True} if bool(getattr(opts, "mask_padding", False)) else {}
 
 
+def device_context(opts):
+    """The driver key `device_context` (default off): a utils.features.FrameContext of the loader keys left_ctx / right_ctx / n_skip_frame /
+    n_downsample -- the archives are then read as BASE features and spliced, frame-skipped and padded on the GPU (utils/data_loader
+    DeviceContext) -- or None with the key absent or false: the host loader, exactly as before."""
+    if not bool(getattr(opts, "device_context", False)):
+        return None
+    from ctc_pytorch_amd.utils.features import FrameContext
+    return FrameContext.from_opts(opts)
+
+
 def report_options(opts, index2word=None):
     """run_epoch's error-breakdown keywords from the driver options `error_report` (bool), `score_map` (path of a three-column phone table)
     and `score_map_cols` ("60-48", "60-39" or "48-39"); absent (or false) keys pass nothing.  A score map needs the vocabulary's names."""
@@ -294,15 +304,18 @@ def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print, in
     torch.set_num_threads(max(1, int(os.environ.get("CTCN_HOST_THREADS", "4"))))       # (restored when main returns)
     torch.manual_seed(opts.seed)
     np.random.seed(opts.seed)
+    context = device_context(opts)                        # (None: the host loader; loaders handed in must then be base-feature loaders too)
     if train_loader is None:
-        from ctc_pytorch_amd.utils.data_loader import Vocab, SpeechDataset, SpeechDataLoader
+        from ctc_pytorch_amd.utils.data_loader import BaseFeatureLoader, Vocab, SpeechDataset, SpeechDataLoader
         vocab = Vocab(opts.vocab_file)
         num_class = vocab.n_words
         index2word = vocab.index2word
-        train_loader = SpeechDataLoader(SpeechDataset(vocab, opts.train_scp_path, opts.train_lab_path, opts),
-                                        batch_size=opts.batch_size, shuffle=opts.shuffle_train, num_workers=opts.num_workers)
-        dev_loader = SpeechDataLoader(SpeechDataset(vocab, opts.valid_scp_path, opts.valid_lab_path, opts),
-                                      batch_size=opts.batch_size, shuffle=False, num_workers=opts.num_workers)
+        loader_type = SpeechDataLoader if context is None else BaseFeatureLoader
+        base = {} if context is None else {"base_features": True}
+        train_loader = loader_type(SpeechDataset(vocab, opts.train_scp_path, opts.train_lab_path, opts, **base),
+                                   batch_size=opts.batch_size, shuffle=opts.shuffle_train, num_workers=opts.num_workers)
+        dev_loader = loader_type(SpeechDataset(vocab, opts.valid_scp_path, opts.valid_lab_path, opts, **base),
+                                 batch_size=opts.batch_size, shuffle=False, num_workers=opts.num_workers)
     if world > 1:
         # data parallel: `batch_size` stays the GLOBAL minibatch (the optimisation trajectory of the 1-GPU run); every rank
         # walks the same loader (same seed / shuffle) and keeps its contiguous shard of each batch, padded to the global T_max
@@ -312,7 +325,10 @@ def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print, in
         parallel.enable_overlap(True)                     # run_epoch does one backward pass per optimiser step
     if rank != 0:
         log = lambda *_a, **_k: None                      # one log stream: every rank holds the same all-reduced statistics
-    if device.type == "cuda":
+    if context is not None:
+        from ctc_pytorch_amd.utils.data_loader import DeviceContext
+        train_loader, dev_loader = DeviceContext(train_loader, device, context), DeviceContext(dev_loader, device, context)
+    elif device.type == "cuda":
         from ctc_pytorch_amd.utils.data_loader import DevicePrefetcher
         train_loader, dev_loader = DevicePrefetcher(train_loader, device), DevicePrefetcher(dev_loader, device)   # async double-buffered H2D
     model = build_model_from_opts(opts, num_class).to(device)
@@ -373,6 +389,7 @@ if __name__ == "__main__":
     ap.add_argument("--max-grad-norm", type=float, default=None, help="clip the global gradient norm to this value (default: the YAML's max_grad_norm, else off)")
     ap.add_argument("--skip-nonfinite-steps", action="store_true", help="drop optimiser steps whose gradient holds NaN / Inf (default: the YAML's skip_nonfinite_steps, else off)")
     ap.add_argument("--mask-padding", action="store_true", help="tell the model every utterance's real frames: padding reaches no BatchNorm statistic and no recurrence (default: the YAML's mask_padding, else off)")
+    ap.add_argument("--device-context", action="store_true", help="read the archives as base features and apply left_ctx / right_ctx / n_skip_frame / n_downsample on the GPU (default: the YAML's device_context, else off)")
     ap.add_argument("--error-report", action="store_true", help="log the error breakdown (sub / del / ins, top confusions) of every validation pass (default: the YAML's error_report, else off)")
     ap.add_argument("--score-map", default=None, help="three-column phone table the breakdown is scored under (default: the YAML's score_map, else none)")
     ap.add_argument("--score-map-cols", default=None, choices=["60-48", "60-39", "48-39"], help="which fold of the table (default: the YAML's score_map_cols, else 48-39)")
@@ -386,6 +403,8 @@ if __name__ == "__main__":
         conf["score_map_cols"] = a.score_map_cols
     if a.mask_padding:
         conf["mask_padding"] = True
+    if a.device_context:
+        conf["device_context"] = True
     if a.max_grad_norm is not None:
         conf["max_grad_norm"] = a.max_grad_norm
     if a.skip_nonfinite_steps:

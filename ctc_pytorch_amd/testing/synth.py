@@ -55,6 +55,18 @@ def make_batch(seed, B, T, F, V, min_len=None, lab_lo=30, lab_hi=60, full_length
     return dict(x=x, lens=lens, frac=frac, targets=targets, tgt_len=tl)
 
 
+def make_waves(seed, lengths, sample_rate=16000.0):
+    """Waveforms for the feature front-ends: per utterance a tone of a seeded frequency (200 .. 3000 Hz, amplitude 6000) over noise of
+    sigma 300, float32 on Kaldi's scale (the int16 range).  lengths: samples per utterance."""
+    rs = np.random.RandomState(seed)
+    out = []
+    for n in lengths:
+        t = np.arange(int(n)) / float(sample_rate)
+        out.append((6000.0 * np.sin(2 * np.pi * rs.uniform(200.0, 3000.0) * t + rs.uniform(0, 2 * np.pi))
+                    + 300.0 * rs.standard_normal(int(n))).astype(np.float32))
+    return out
+
+
 def fill_state_dict(shapes, seed):
     """Deterministic parameter values for a CTC_Model state_dict.
 

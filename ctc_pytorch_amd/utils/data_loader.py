@@ -6,6 +6,10 @@ kaldiio is not available, so Kaldi archives are read by the small binary reader 
 double matrices, `scp` entries of the form `utt path:offset`).  Batches have exactly the reference layout:
 (inputs (B,Tmax,F) float32 zero-padded, input_sizes (B) float32 FRACTIONS len/Tmax, targets (B,Lmax) int64
 zero-padded, target_sizes (B) int64, utt_list).
+
+Base-feature mode (SpeechDataset(base_features=True), create_base_input, BaseFeatureLoader, DeviceContext): the archive's matrices are collated
+and staged as they are, with their int32 frame counts, and the splice / frame skip / downsample pad run on the GPU (ops.frame_context); the
+batches that come out are the ones above, bit for bit.
 """
 import struct
 
@@ -124,8 +128,12 @@ class Vocab(object):
 
 
 class SpeechDataset(Dataset):
-    def __init__(self, vocab, scp_path, lab_path, opts):
+    """base_features=True: an item is the matrix as the archive holds it -- no splice, no frame skip, no pad; create_base_input collates
+    those and DeviceContext expands them on the GPU with the same four options."""
+
+    def __init__(self, vocab, scp_path, lab_path, opts, base_features=False):
         self.vocab = vocab
+        self.base_features = bool(base_features)
         self.left_ctx = opts.left_ctx
         self.right_ctx = opts.right_ctx
         self.n_skip_frame = opts.n_skip_frame
@@ -146,6 +154,8 @@ class SpeechDataset(Dataset):
 
     def __getitem__(self, idx):
         path, label, utt = self.item[idx]
+        if self.base_features:
+            return torch.from_numpy(read_kaldi_matrix(path)), torch.LongTensor(label), utt
         # (the spliced / frame-skipped matrix stays a strided view of the matrix just read -- an array of its own -- until create_input copies
         # it into the batch: one pass over the 9x larger spliced data instead of three)
         feat = skip_feat(make_context(read_kaldi_matrix(path), self.left_ctx, self.right_ctx, as_view=True), self.n_skip_frame)
@@ -189,6 +199,24 @@ class SpeechDataLoader(DataLoader):
         self.collate_fn = create_input
 
 
+def create_base_input(batch):
+    """create_input for base features (SpeechDataset(base_features=True)): the same 5-tuple, with the utterances' exact FRAME COUNTS, int32,
+    where create_input puts the float32 fractions -- the device stage clamps delta and splice windows against them, and a fraction gives a
+    count back only up to 2000 frames (steps/train_ctc.input_frames_from_fraction)."""
+    data, _, label, target_sizes, utt_list = create_input(batch)
+    return data, torch.tensor([x[0].size(0) for x in batch], dtype=torch.int32), label, target_sizes, utt_list
+
+
+class BaseFeatureLoader(DataLoader):
+    """SpeechDataLoader's counterpart over SpeechDataset(base_features=True): batches of create_base_input, for DeviceContext."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if not getattr(self.dataset, "base_features", False):
+            raise ValueError("BaseFeatureLoader: the dataset splices on the host; build it with base_features=True")
+        self.collate_fn = create_base_input
+
+
 class DevicePrefetcher(object):
     """Double-buffered asynchronous host->device staging of the batches of a SpeechDataLoader.
 
@@ -230,10 +258,15 @@ class DevicePrefetcher(object):
         sizes = input_sizes if torch.is_tensor(input_sizes) else torch.as_tensor(np.asarray(input_sizes, dtype=np.float32))
         with torch.cuda.stream(stream):
             dev = [self._pinned(slot, k, t).to(self.device, non_blocking=True) for k, t in enumerate((inputs, sizes, targets, target_sizes))]
+            dev = self._on_device(dev)
             ready = torch.cuda.Event()
             ready.record(stream)
         slot["copied"] = ready
         return (dev[0], dev[1], dev[2], dev[3], utt_list) + tuple(batch[5:]), ready   # (+ the global batch size of a DP shard)
+
+    def _on_device(self, dev):
+        """What a subclass does with the staged [inputs, sizes, targets, target_sizes] on the copy stream, before the batch counts as ready."""
+        return dev
 
     def __iter__(self):
         if self.device.type != "cuda":
@@ -255,3 +288,22 @@ class DevicePrefetcher(object):
             for t in batch[:4]:
                 t.record_stream(cur)
             yield batch
+
+
+class DeviceContext(DevicePrefetcher):
+    """DevicePrefetcher over a loader of BASE features (BaseFeatureLoader, or parallel.ShardedBatches around one): the batch is staged as the
+    archive holds it -- (left + 1 + right) / skip times fewer bytes over PCIe and through the pinned copy -- and spliced, frame-skipped and padded
+    on the device by one launch on the copy stream (utils/features.FrameContext: ops.frame_context), which also writes the float32 length
+    fractions.  Yields what DevicePrefetcher yields over the host path, bit for bit: (inputs (B, T', F'), input_sizes fractions, targets,
+    target_sizes, utt_list[, B_global]).  The frame counts reach the kernel as the loader's int32 values.  A shard of a global batch is padded to
+    the global T_max and its output is sized from that, so its fractions are the global batch's."""
+
+    def __init__(self, loader, device, context):
+        super().__init__(loader, device)
+        self.context = context
+
+    def _on_device(self, dev):
+        if dev[1].dtype != torch.int32:
+            raise TypeError("DeviceContext: the loader must carry int32 frame counts (create_base_input), got %s" % dev[1].dtype)
+        out, _, fractions = self.context(dev[0], dev[1])
+        return [out, fractions, dev[2], dev[3]]

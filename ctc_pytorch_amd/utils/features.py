@@ -13,9 +13,11 @@ binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --conf
   GlobalCMVN    Kaldi's 2 x (F + 1) statistics, accumulated on the device (ops.cmvn_accumulate), its text file, mean and 1 / stddev
   Resampler     a waveform batch at another sample rate (ops.resample: Kaldi's LinearResample, what its binaries run under --allow-downsample /
                 --allow-upsample); SpeedPerturb: the recipe's three-way speed perturbation (perturb_data_dir_speed.sh) as one Resampler per factor
+  FrameContext  the stage behind them: Kaldi's add-deltas, frame splicing, frame skipping and the pad to a multiple of n_downsample on the
+                device (ops.frame_context) -- what utils/data_loader.py does per utterance on the host; its output is the model's input
   read_wave     RIFF PCM-16 mono and uncompressed NIST SPHERE (TIMIT's) -> int16 samples
 
-Not here: pitch, VTLN, deltas, per-speaker CMVN, compressed SPHERE."""
+Not here: pitch, VTLN, per-speaker CMVN, compressed SPHERE."""
 import struct
 
 import numpy as np
@@ -316,6 +318,40 @@ class SpeedPerturb(object):
         if r is None:
             raise ValueError("SpeedPerturb: factor %r is not one of %r" % (factor, self.factors))
         return r(waves, lengths)
+
+
+class FrameContext(object):
+    """Deltas, splice, skip and downsample pad of a base batch on the device (ops.frame_context): the loader keys left_ctx, right_ctx,
+    n_skip_frame, n_downsample under the names left, right, skip, n_downsample, plus Kaldi's add-deltas (delta_order 0: none).  Holds no
+    device state: the batch's device is the call's.  Options outside the kernel's limits raise RuntimeError at the first out_dim / call."""
+
+    def __init__(self, left=0, right=0, skip=1, n_downsample=1, delta_order=0, delta_window=2):
+        self.left, self.right, self.skip, self.n_downsample = int(left), int(right), int(skip), int(n_downsample)
+        self.delta_order, self.delta_window = int(delta_order), int(delta_window)
+
+    @classmethod
+    def from_opts(cls, opts):
+        """From a driver's options object: the keys SpeechDataset reads."""
+        return cls(opts.left_ctx, opts.right_ctx, opts.n_skip_frame, opts.n_downsample)
+
+    def _kw(self):
+        return dict(left=self.left, right=self.right, skip=self.skip, n_downsample=self.n_downsample, delta_order=self.delta_order,
+                    delta_window=self.delta_window)
+
+    def out_dim(self, feat_dim):
+        """Columns of the output for base features of feat_dim columns: (left + 1 + right) * feat_dim * (delta_order + 1)."""
+        ops.frame_context_tile(feat_dim, **self._kw())                 # (the limits)
+        return (self.left + 1 + self.right) * int(feat_dim) * (self.delta_order + 1)
+
+    def out_frames(self, num_frames):
+        """Rows of an utterance of num_frames base frames: kept frames, padded to a multiple of n_downsample."""
+        return ops.context_frames(num_frames, self.skip, self.n_downsample)
+
+    def __call__(self, feats, frames):
+        """feats (B, Tin_max, F) float32 on the device, frames (B) a list or a device tensor -- a front-end's return values as they are.
+        Returns (out (B, Tout_max, out_dim(F)) float32: the model's input, out_frames (B) int32, fractions (B) float32: the loader's
+        input_sizes) on the same device."""
+        return ops.frame_context(feats, frames, **self._kw())
 
 
 class GlobalCMVN(object):

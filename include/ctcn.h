@@ -576,7 +576,7 @@ int ctcn_step_stats(const float *loss, const int32_t *dist, const int64_t *tgt_l
  * binaries of timit/steps/make_feat.sh (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true).
  * The computation is Kaldi's, as its feature-window, feature-fbank and mel-computations sources document it; option names and defaults are
  * Kaldi's.  window_type: 0 hamming, 1 hanning, 2 povey (Kaldi's default), 3 rectangular, 4 blackman.  high_freq <= 0 is an offset from Nyquist.
- * Not here: VTLN, deltas (MFCC: ctcn_mfcc below; the spectrogram types: ctcn_spectrogram, ctcn_logspec below; resampling in front of them: ctcn_resample below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
+ * Not here: VTLN (deltas, splicing and frame skipping: ctcn_frame_context below; MFCC: ctcn_mfcc below; the spectrogram types: ctcn_spectrogram, ctcn_logspec below; resampling in front of them: ctcn_resample below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
  * defaults). */
 typedef struct ctcn_fbank_opts {
   float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff, blackman_coeff, low_freq, high_freq, energy_floor;
@@ -759,6 +759,54 @@ int ctcn_resample(const void *wave, int wave_is_int16, const int32_t *lens, cons
                   int Nmax, int Mmax, void *stream);
 int ctcn_resample_host(const void *wave, int wave_is_int16, int num_samples, const ctcn_resample_opts *opts, const void *plan, float *out,
                        int out_cap);
+/* Deltas, frame splicing, frame skipping and the downsample pad behind the feature kernels (context.hip): the stage between a zero-padded
+ * base batch and the (B, T, F') batch the model consumes -- Kaldi's add-deltas (feature-functions' DeltaFeatures) followed by what the
+ * reference's loader does per utterance on the host (timit/utils/tools.py make_context :66-75 and skip_feat :77-86, the zero rows of
+ * SpeechDataset.__getitem__, data_loader.py:100-104, and the length fractions of create_input :119-140).  Options: left, right (context
+ * frames), skip (0 and 1 both keep every frame), n_downsample, delta_order (0: no deltas), delta_window.  For an utterance of T frames of F
+ * columns:
+ *   1. the delta scales, on the host in float32 as Kaldi builds them: s_0 = [1]; for i = 1 .. delta_order, s_i has 2 i window + 1 entries,
+ *      s_i[j + k + i window] += (float) j * s_{i-1}[k + (i - 1) window] for j = -window .. window (outer loop), k = -(i - 1) window ..
+ *      (i - 1) window (a float32 multiplication, then a float32 addition), then every entry times the float32 of 1.0 / sum j^2
+ *      (ctcn_delta_scales; window 2: s_1 = [-0.2, -0.1, 0, 0.1, 0.2]);
+ *   2. delta'd frame u, F1 = F (delta_order + 1) columns [static F | order 1 F | order 2 F]: column f of order i is
+ *      sum_j s_i[j + i window] x[clamp(u + j, 0, T - 1)][f], j = -i window .. i window ascending, entries that are zero skipped (as Kaldi
+ *      skips them), clamped against the utterance's OWN length; accumulated in float64 -- the product of two float32 values is exact
+ *      there, so the sum is one number with or without fused multiply-adds -- and rounded once to float32 (Kaldi adds the terms in
+ *      float32, one AddVec per offset; the difference is the rounding of that sum);
+ *   3. spliced row t, F2 = (left + 1 + right) F1 columns: the delta'd frames clamp(t - left, 0, T - 1) .. clamp(t + right, 0, T - 1) back
+ *      to back, the oldest first;
+ *   4. kept rows: t = 0, skip, 2 skip, ...: n_kept = ceil(T / skip);
+ *   5. n_out = n_kept rounded up to a multiple of n_downsample (ctcn_context_frames; 0 for T = 0); rows n_kept .. n_out - 1 are zeros and
+ *      count as frames.
+ * ctcn_frame_context: feats (B, Tin_max, F) float32, frames (B) int32 in DEVICE memory, clamped to [0, Tin_max]; base rows at or beyond
+ * frames[b] are never read.  out (B, Tout_max, F2) float32, Tout_max = ctcn_context_frames(Tin_max, skip, n_downsample) (the count is
+ * monotone in T, so this is the largest n_out of any batch padded to Tin_max, a data-parallel shard of one included; another value:
+ * CTCN_EINVAL): EVERY element is written -- frames, pad rows, zeros from n_out on -- the caller need not clear it.  out_frames (B) int32 =
+ * n_out; fractions (B) float32 = (float)((double) n_out / (double) Tout_max), what create_input stores (0 where Tout_max is 0).
+ * One launch on the caller's stream, grid (tiles of output rows, B): the workgroup stages the tile's run of base frames -- (rows - 1) skip +
+ * left + 1 + right + 2 delta_order delta_window of them -- in LDS, forms every delta'd frame of it once, and writes the output rows from
+ * LDS with consecutive lanes on consecutive floats.  No atomics, no workspace, no host synchronisation.  A row depends on its own
+ * utterance alone, not on B, Tin_max or its neighbours.
+ * ctcn_frame_context_tile: the output rows of one workgroup (at most 16; fewer where that span exceeds 64 KB of LDS), or an error code.
+ * Limits, from every entry point that takes the options, before any launch: CTCN_EINVAL for NULL, a negative left / right / skip /
+ * delta_order, n_downsample, delta_window or F below 1, B outside [1, 65 535], Tin_max beyond 2^30; CTCN_EUNSUPPORTED for left or right
+ * beyond 64, skip or n_downsample beyond 1024, delta_order beyond 2, delta_window beyond 5, F beyond 65 536, or a single output row whose
+ * span of frames exceeds 144 KB of LDS (F = 257 with two delta orders of window 5 fits with up to 14 context frames a side).
+ * ctcn_frame_context_host: the same computation for ONE utterance on the HOST (no HIP call; works without a GPU): feats (num_frames, F),
+ * out (out_rows, F2) written in full as the kernel writes a row of the batch with Tout_max = out_rows, *fraction (or NULL) = n_out /
+ * out_rows; returns n_out (out_rows must hold it) or an error code. */
+typedef struct ctcn_context_opts {
+  int32_t left, right, skip, n_downsample, delta_order, delta_window;
+} ctcn_context_opts;
+int ctcn_context_frames(int num_frames, int skip, int n_downsample);
+/* scales: room for 2 order window + 1 floats; returns that count. */
+int ctcn_delta_scales(int order, int window, float *scales);
+int ctcn_frame_context_tile(const ctcn_context_opts *opts, int F);
+int ctcn_frame_context(const float *feats, const int32_t *frames, const ctcn_context_opts *opts, float *out, int32_t *out_frames,
+                       float *fractions, int B, int Tin_max, int F, int Tout_max, void *stream);
+int ctcn_frame_context_host(const float *feats, int num_frames, int F, const ctcn_context_opts *opts, float *out, int out_rows,
+                            float *fraction);
 
 /* ---------------------------------------------------------------------------------------------------
  * CTC prefix beam search with bigram LM; replaces BeamDecoder.decode -> ctcBeamSearch.decode
