@@ -23,9 +23,8 @@
 
 namespace {
 
-// Widest beam of the generic kernel (round 6: 1 024, was 256 -- the reference takes any beam_width, ctcDecoder.py:170 / BeamSearch.py:96).  The
-// beam state lives in DYNAMIC LDS sized for the call's width (120 B per beam slot + 12 B per selection survivor: 42 KB at W <= 256, 146 KB
-// at W = 1 024, which gfx950's 160 KB per workgroup still hold); beyond that the state would have to live in global memory.
+// Widest beam of the generic kernel: its beam state lives in dynamic LDS sized for the call's width (GenericLds: 146 KB at W = 1 024, which
+// gfx950's 160 KB per workgroup still hold); beyond that the state would have to live in global memory.
 constexpr int BEAM_WMAX = 1024;
 constexpr double LOG_ZERO = -99999999.0;
 constexpr unsigned long long HT_EMPTY = ~0ull;
@@ -83,18 +82,137 @@ struct BeamArgs {
 #endif
 };
 #ifdef CTCN_BEAM_STATS
-#define GSTAMP(i) do { if (b == 0 && tid == 0) { const long long now_ = clock64(); gst[i] += now_ - glast; glast = now_; } } while (0)
+#define GSTAMP(i) do { if (c.b == 0 && c.tid == 0) { const long long now_ = clock64(); c.gst[i] += now_ - c.glast; c.glast = now_; } } while (0)
 #else
 #define GSTAMP(i) do { } while (0)
 #endif
 
+// ---- What both kernels share: candidate order and columns, key maps, arg-max rounds, the final step, the two dynamic-LDS layouts ----
 __device__ __forceinline__ bool cand_better(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
-// order-preserving map double -> uint64 for the selection's bound (v > w <=> dkey(v) > dkey(w); -0.0 folded onto +0.0, which compare equal; no NaN
-// among the scores); never 0 for a finite value
-__device__ __forceinline__ unsigned long long dkey(double v) {
-  const unsigned long long bts = (unsigned long long)__double_as_longlong(v == 0.0 ? 0.0 : v);
-  return (bts >> 63) ? ~bts : (bts | 0x8000000000000000ull);
+// a beam slot's row of the candidate table: column 0 = the stay entry, column kk >= 1 = the kk-th non-blank class; cand_class(0, blank) = -1
+__device__ __forceinline__ int cand_class(int kk, int blank) { return (kk - 1 < blank) ? kk - 1 : kk; }
+__device__ __forceinline__ int class_col(int k, int blank) { return (k < blank) ? k + 1 : k; }
+// Order-preserving maps double -> uint64 (v > w <=> key(v) > key(w); no NaN among the scores; never 0 for a finite value), in two forms:
+//   f64_key / key_f64  a bijection.  The fast kernel carries its candidates as keys and reads the SCORES back with key_f64: folding a zero
+//                      there would change result bits.  The generic kernel turns its pruning bound back into a double with it.
+//   dkey               folds -0.0 onto +0.0, which compare equal as doubles.  The generic kernel compares keys with keys (bound search,
+//                      bitonic ranks) and reads every score from the candidate table, never from a key.
+__device__ __forceinline__ unsigned long long f64_key(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
+__device__ __forceinline__ double key_f64(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+__device__ __forceinline__ unsigned long long dkey(double v) { return f64_key(v == 0.0 ? 0.0 : v); }
+// W block-wide arg-max rounds over the candidate table under cand_better(): the selection's fallback in both kernels (more survivors than
+// their list holds: exact ties by the hundred).  All NT threads; `barrier` and `wave` are the kernel's own; red_i has NT / 64 + 1 entries.
+// Round r's winner goes to sel[r] / selv[r] and on_pick(r).  `v != -inf` selects what `v > -inf` does: a NaN never passes cand_better().
+template <int NT, typename Barrier, typename OnPick>
+__device__ __forceinline__ int arg_max_rounds(double *cand, int ncand, int W, double *red_v, int *red_i, int *sel, double *selv, int wave,
+                                              Barrier barrier, OnPick on_pick) {
+  constexpr int NWV = NT / 64, NONE = 0x7fffffff;
+  const int tid = threadIdx.x, lane = tid & 63;
+  int got = 0;
+  for (int r = 0; r < W; ++r) {
+    double bv = -INFINITY; int bi = NONE;
+    for (int c = tid; c < ncand; c += NT) {
+      const double v = cand[c];
+      if (v != -INFINITY && cand_better(v, c, bv, bi)) { bv = v; bi = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (oi != NONE && (bi == NONE || cand_better(ov, oi, bv, bi))) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
+    barrier();
+    if (tid == 0) {
+      double v = red_v[0]; int ix = red_i[0];
+      for (int w = 1; w < NWV; ++w)
+        if (red_i[w] != NONE && (ix == NONE || cand_better(red_v[w], red_i[w], v, ix))) { v = red_v[w]; ix = red_i[w]; }
+      red_i[NWV] = ix;
+      if (ix != NONE) { sel[r] = ix; selv[r] = v; on_pick(r); cand[ix] = -INFINITY; }
+    }
+    barrier();
+    if (red_i[NWV] == NONE) break;
+    ++got;
+  }
+  return got;
+}
+// The final step (BeamSearch.py:130-151), thread 0: the end-of-sentence LM term, length normalisation (:147), then `last.sort()[0:nbest]`
+// (:150, the reference keeps [0]) -- a stable descending sort: among equal scores the earlier entry of BHat comes first -- and every picked
+// labelling read back through the trie: walk(n) returns the last class of node n and moves n to its parent.  pT is reused for the scores and
+// `taken` for the picks (it may be `last`: entry r's last class is read before taken[r] is written).  Status 1 / 3 or != 0: outputs zeroed.
+template <typename Args, typename Walk>
+__device__ __forceinline__ void beam_finish(const Args &a, int b, int status, bool too_many_nodes, int nb, const int *len, const int *last,
+                                            const int *node, double *pT, int *taken, const double *lm, Walk walk) {
+  if (threadIdx.x != 0) return;
+  const int NB = a.nbest, V = a.V, T = a.T;
+  int nout = 0;
+  if (status == 0) {
+    for (int r = 0; r < nb; ++r) if (len[r] == 0) status = 1;         // classes[y[-1]] on () -> IndexError
+    if (too_many_nodes) status = 3;
+  }
+  if (status == 0) {
+    for (int r = 0; r < nb; ++r) {
+      // (the reference's log_add_prob(LOG_ZERO, pr): its first test returns the second argument, BeamSearch.py:44-45)
+      const double tot = pT[r] + lm_scaled(lm[(size_t)last[r] * (V + 1) + V], a.alpha);
+      const int ln = len[r];
+      pT[r] = tot * (1.0 / (ln ? ln : 1));
+      taken[r] = 0;
+    }
+    nout = min(NB, nb);
+    for (int k = 0; k < nout; ++k) {
+      int best = -1; double bestv = 0.0;
+      for (int r = 0; r < nb; ++r)
+        if (!taken[r] && (best < 0 || pT[r] > bestv)) { best = r; bestv = pT[r]; }
+      taken[best] = 1;
+      const int ln = len[best];
+      const size_t o = (size_t)b * NB + k;
+      a.out_len[o] = ln; a.out_score[o] = bestv;
+      int n = node[best];
+      for (int i = ln - 1; i >= 0; --i) a.out_ids[o * T + i] = walk(n);
+    }
+  }
+  for (int k = nout; k < NB; ++k) { a.out_len[(size_t)b * NB + k] = 0; a.out_score[(size_t)b * NB + k] = 0.0; }
+  if (a.out_count) a.out_count[b] = nout;
+  a.status[b] = status;
+}
+// Dynamic LDS of beam_kernel, byte offsets: lg[V] doubles | cand[W * V] doubles (cand_in_lds) | STATE x wcap + smax doubles | as many ints |
+// LM table (lm_in_lds).  Doubles: 2 x {pB, pNB, pT}, sNB, sB, sT, selv (wcap each), sv_v (smax); ints: 2 x {node, len, last, par}, mfrom, sel,
+// sv_i -- BeamCtx::carve names them.
+struct GenericLds {
+  static constexpr int STATE = 10;
+  size_t cand, dbl, ints, lm, total;
+  __host__ __device__ GenericLds(int V, int W, int wcap, int smax, bool cand_in_lds, bool lm_in_lds) {
+    size_t off = (size_t)V * sizeof(double);
+    cand = off; off += cand_in_lds ? (size_t)W * V * sizeof(double) : 0;
+    dbl = off;  off += ((size_t)STATE * wcap + smax) * sizeof(double);
+    ints = off; off += ((size_t)STATE * wcap + smax) * sizeof(int);
+    lm = (off + 7) & ~(size_t)7;                                     // (8 bytes of room for that rounding)
+    total = off + (lm_in_lds ? table_bytes(V) : 0);
+  }
+  static __host__ __device__ size_t table_bytes(int V) { return (size_t)(V + 1) * (V + 1) * sizeof(double) + 8; }
+};
+// Dynamic LDS of the fast kernel: alpha * LM (V+1)^2 doubles (lm_lds) | cand[W * V] doubles | lg[2][V] doubles (by frame parity) |
+// mslot[W * V] ints | flist[T] ints | trie[trie_slots] uints.  Off: size_t in the plan, which sizes any shape; unsigned in the kernel, which
+// sits at its register limit and takes W <= 60, V <= 256, T < 2^22 only.
+template <typename Off>
+struct FastLdsT {
+  Off cand, lg2, mslot, flist, trie, total;
+  __host__ __device__ FastLdsT(int T, int V, int W, bool lm_lds, int trie_slots) {
+    Off off = lm_lds ? (Off)table_bytes(V) : 0;
+    cand = off;  off += (Off)W * V * (Off)sizeof(double);
+    lg2 = off;   off += (Off)2 * V * (Off)sizeof(double);
+    mslot = off; off += (Off)W * V * (Off)sizeof(int);
+    flist = off; off += (Off)T * (Off)sizeof(int);
+    trie = off;  off += (Off)trie_slots * (Off)sizeof(unsigned);
+    total = off;
+  }
+  static __host__ __device__ size_t table_bytes(int V) { return (size_t)(V + 1) * (V + 1) * sizeof(double); }
+};
 
 // Sum / 64-bit maximum over each row of 16 lanes by DPP (no LDS crossbar: a ds_bpermute butterfly is a chain of ~150-cycle hops under load);
 // afterwards every lane of a row holds the row's result
@@ -118,6 +236,20 @@ __device__ __forceinline__ unsigned long long row16_max_u64(unsigned long long x
   x = dpp_max_u64_step<0x141>(x);
   x = dpp_max_u64_step<0x140>(x);
   return x;
+}
+// 32-bit maximum over each row of 16 lanes (row_shr 1 / 2 / 4 / 8: lanes without a source keep their own value); only LANE 15 of a row holds
+// the row's result
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_umax_step(unsigned v) {
+  const unsigned s = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, 0xf, 0xf, false);
+  return max(v, s);
+}
+__device__ __forceinline__ unsigned row16_umax(unsigned v) {
+  v = dpp_umax_step<0x111>(v);
+  v = dpp_umax_step<0x112>(v);
+  v = dpp_umax_step<0x114>(v);
+  v = dpp_umax_step<0x118>(v);
+  return v;
 }
 __device__ __forceinline__ int wave_sum_rows(int v) {               // wave-wide sum, uniform result
   v = row16_sum(v);
@@ -158,75 +290,435 @@ __device__ __forceinline__ void bitonic_step(unsigned &khi, unsigned &klo, int &
   khi = take ? ohi : khi; klo = take ? olo : klo; ix = take ? oi : ix;
 }
 
-// NT threads per utterance: 256 for small tables, 1 024 beyond W = 64 or 3 500 candidates per frame (round 5: every phase of a frame is a loop over nb * V candidates or over the beam, and the
-// kernel ran one wave per SIMD -- nothing hid an LDS or L2 latency)
+// ---- The generic kernel: NT threads per utterance (every phase of a frame is a loop over nb * V candidates or over the beam, and one wave per
+// SIMD hides neither an LDS nor an L2 latency).  beam_kernel, at the end, is the reference's loop over the phase functions before it. ----
+template <int NWV>
+struct SelectShared {                            // static LDS of the selection
+  double red_v[NWV]; int red_i[NWV + 1];         // arg-max rounds; before them red_i[w] = wave w's number of valid candidates
+  unsigned long long wthr[NWV];                  // every wave's bound
+  int wcnt[NWV][NWV];                            // ... and how many of wave w's maxima reach wave j's
+  int scnt, ovf;                                 // survivors compacted so far | they did not fit the list
+};
+struct BeamCtx {                                 // what the phases of a frame work on, next to the kernel's arguments `a`
+  const BeamArgs &a;
+  int tid, lane, wave, b, htmask;
+  int nb;                                        // entries of the beam L
+  BeamState L, N;                                // this frame's beam and the one it builds
+  double *lg, *cand;                             // ln p of the frame | candidate table (LDS or workspace)
+  double *dbl; int *ints;                        // the state arrays of GenericLds
+  double *sNB, *sB, *sT;                         // this frame's stay / merged entry of every slot
+  double *selv, *sv_v; int *sel, *sv_i;          // the selection: candidate and score by rank | survivors of the pruning bound (value | candidate index)
+  int *mfrom;                                    // slot that holds the slot's parent labelling (-1: none)
+  const double *lm;                              // raw ln-probs (LDS copy or global); lm_scaled() forms the product with alpha per use
+  unsigned long long *keys; int *ids, *npar, *nsym;       // trie: hash table, node parents and symbols
+  // Lookups instead of scans of the beam:
+  //   nslot[node] = beam slot that holds trie node `node` -- written for every entry of a new beam, read by find_parents of the next frame;
+  //   cown[c]     = beam slot whose labelling merges with extension candidate c -- written by merge_stays, read by materialise.
+  // Neither table is initialised or stamped: a value is USED only if the slot it names passes the very test a scan would apply (L.node[s] ==
+  // pnode; mfrom[s] == i && L.last[s] == k), which at most one slot of a beam can pass -- and for a node / candidate that does have such a
+  // slot the table was written this frame.  Anything else (stale, never written) fails the test exactly as a scan finds nothing.
+  int *nslot, *cown;
+  // c / V for candidate indices c < W * V: one multiply-high by ceil(2^32 / V) (exact while c * V < 2^32) -- the runtime division hipcc
+  // emits is ~25 instructions, and score_extensions pays it per candidate: the kernel's parallel phases are instruction-issue bound
+  unsigned vmagic; bool vmagic_ok;
+#ifdef CTCN_BEAM_STATS
+  long long gst[16], glast;
+#endif
+  __device__ __forceinline__ void carve(unsigned char *lds_base) {
+    tid = threadIdx.x; lane = tid & 63; wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (scalar: per-wave decisions are scalar branches)
+    b = blockIdx.x; htmask = a.ht_size - 1;
+    const int V = a.V, W = a.W, wcap = a.wcap;
+    const GenericLds l(V, W, wcap, a.smax, a.cand_in_lds, a.lm_in_lds);
+    lg = reinterpret_cast<double *>(lds_base);
+    cand = a.cand_in_lds ? reinterpret_cast<double *>(lds_base + l.cand) : a.cand_global + (size_t)b * W * V;
+    dbl = reinterpret_cast<double *>(lds_base + l.dbl);
+    ints = reinterpret_cast<int *>(lds_base + l.ints);
+    sNB = dbl + 6 * wcap; sB = sNB + wcap; sT = sB + wcap; selv = sT + wcap; sv_v = selv + wcap;
+    mfrom = ints + 8 * wcap; sel = mfrom + wcap; sv_i = sel + wcap;
+    lm = a.lm_in_lds ? reinterpret_cast<const double *>(lds_base + l.lm) : a.lm;
+    keys = a.ht_keys + (size_t)b * a.ht_size; ids = a.ht_ids + (size_t)b * a.ht_size;
+    npar = a.node_par + (size_t)b * a.max_nodes; nsym = a.node_sym + (size_t)b * a.max_nodes;
+    nslot = a.node_slot + (size_t)b * a.max_nodes; cown = a.cand_owner + (size_t)b * W * V;
+    vmagic = 0xffffffffu / (unsigned)V + 1u;
+    vmagic_ok = (unsigned long long)W * V * V < (1ull << 32);          // (a vocabulary of thousands: the plain division)
+  }
+  __device__ __forceinline__ BeamState state(int k) const {
+    BeamState st;
+    st.pB = dbl + (3 * k) * a.wcap; st.pNB = st.pB + a.wcap; st.pT = st.pNB + a.wcap;
+    st.node = ints + (4 * k) * a.wcap; st.len = st.node + a.wcap; st.last = st.len + a.wcap; st.par = st.last + a.wcap;
+    return st;
+  }
+  __device__ __forceinline__ int div_v(int c) const { return vmagic_ok ? (int)__umulhi((unsigned)c, vmagic) : c / a.V; }
+};
+
+// 2. which beam slot (if any) holds the parent labelling of slot i' -> its extension by last(i') merges with i'
+__device__ __forceinline__ void find_parents(BeamCtx &c) {
+  if (c.tid >= c.nb) return;
+  const BeamState &L = c.L;
+  int m = -1;
+  if (L.len[c.tid] > 0) {
+    const int pnode = L.par[c.tid];
+    if ((unsigned)pnode < (unsigned)c.a.max_nodes) {
+      const int sl = c.nslot[pnode];
+      if ((unsigned)sl < (unsigned)c.nb && L.node[sl] == pnode) m = sl;
+    }
+  }
+  c.mfrom[c.tid] = m;
+}
+// 3a. extension scores (calcExtPr) into the candidate table, slot c = i * V + class_col(k).  EU candidates per trip: the slot reads, then the
+// LM reads (a round trip to L2 unless the table is in LDS) of all of them are issued before the first is used.
+template <int NT>
+__device__ __forceinline__ void score_extensions(BeamCtx &c, bool rep_ok) {
+  constexpr int EU = 4;
+  const BeamState &L = c.L;
+  const int V = c.a.V, ncand = c.nb * V;
+  for (int c0 = c.tid; c0 < ncand; c0 += EU * NT) {
+    int ci[EU], ck[EU], cl[EU], cln[EU];
+    double lmv[EU];
+#pragma unroll
+    for (int u = 0; u < EU; ++u) {
+      const int cc = min(c0 + u * NT, ncand - 1);
+      ci[u] = c.div_v(cc);
+      ck[u] = cand_class(cc - ci[u] * V, c.a.blank);                    // (-1: the stay column)
+      cln[u] = L.len[ci[u]]; cl[u] = L.last[ci[u]];
+    }
+#pragma unroll
+    for (int u = 0; u < EU; ++u) {
+      const int c1 = cln[u] > 0 ? cl[u] : V;
+      lmv[u] = c.lm[(size_t)c1 * (V + 1) + max(ck[u], 0)];
+    }
+#pragma unroll
+    for (int u = 0; u < EU; ++u) {
+      const int cc = c0 + u * NT;
+      if (cc < ncand && ck[u] >= 0) {
+        const int i = ci[u], k = ck[u];
+        const double bigram = lm_scaled(lmv[u], c.a.alpha);
+        const double base = (cln[u] > 0 && cl[u] == k && rep_ok) ? L.pB[i] : L.pT[i];
+        c.cand[cc] = c.lg[k] + bigram + base;
+      }
+    }
+  }
+}
+// 3b. stay entries, merged with the matching extension in the reference's visiting order
+__device__ __forceinline__ void merge_stays(BeamCtx &c) {
+  if (c.tid >= c.nb) return;
+  const BeamState &L = c.L;
+  const int ip = c.tid, V = c.a.V;
+  double s_nb = LOG_ZERO;
+  if (L.len[ip] > 0) s_nb = L.pNB[ip] + c.lg[L.last[ip]];         // BeamSearch.py:102-103
+  const double s_b = L.pT[ip] + c.lg[c.a.blank];                    // :106
+  Fields e{LOG_ZERO, LOG_ZERO, LOG_ZERO};
+  const int i = c.mfrom[ip];
+  if (i >= 0) {
+    const int ce = i * V + class_col(L.last[ip], c.a.blank);
+    c.cown[ce] = ip;
+    const double pr = c.cand[ce];
+    if (i < ip) { apply_ext(e, pr); apply_stay(e, s_nb, s_b); c.cand[ce] = e.t; c.cand[ip * V] = -INFINITY; }
+    else        { apply_stay(e, s_nb, s_b); apply_ext(e, pr); c.cand[ip * V] = e.t; c.cand[ce] = -INFINITY; }
+  } else {
+    apply_stay(e, s_nb, s_b);
+    c.cand[ip * V] = e.t;
+  }
+  c.sNB[ip] = e.nb; c.sB[ip] = e.b; c.sT[ip] = e.t;
+}
+
+// 4. BHat = top-W by (prTotal desc, insertion index asc) without W scans of the table: (a) a lower bound of the W-th best candidate, (b) the
+// candidates that reach it into the survivor list, (c) every survivor's rank under cand_better().  Same set and order as W arg-max rounds.
+// every thread's candidates, SU loads in flight per thread (a table in global memory would otherwise be a chain of L2 round trips)
+template <int NT, typename Visit>
+__device__ __forceinline__ void scan_cands(const double *cand, int ncand, int tid, Visit &&visit) {
+  constexpr int SU = NT >= 1024 ? 4 : 8;          // (1 024 threads: 128 registers each, and a fourth of the candidates per thread)
+  int c = tid;
+  for (; c + (SU - 1) * NT < ncand; c += SU * NT) {
+    double v[SU];
+#pragma unroll
+    for (int u = 0; u < SU; ++u) v[u] = cand[c + NT * u];
+#pragma unroll
+    for (int u = 0; u < SU; ++u) visit(v[u], c + NT * u);
+  }
+  for (; c < ncand; c += NT) visit(cand[c], c);
+}
+// (a) Every thread keeps the best of its candidates (two with 256 threads); every WAVE finds the k-th largest of its maxima, k = ceil(W /
+// waves), by a bitwise search on the keys (ballot + popcount: no LDS, no barrier).  The smallest of the waves' values is always a valid bound
+// (waves * k >= W candidates reach it); a larger one is valid whenever W of ALL the maxima reach it, so every wave counts its maxima against
+// every wave's value and the largest value with a block-wide count >= W wins.  theta = the bound as a key (0: none), total = valid candidates.
+template <int NT>
+__device__ __forceinline__ void selection_bound(BeamCtx &c, SelectShared<NT / 64> &ss, int ncand, unsigned long long &theta, int &total) {
+  constexpr int NWV = NT / 64;
+  constexpr int NH = NT >= 1024 ? 1 : 2;                   // maxima per thread
+  const int tid = c.tid, lane = c.lane, wave = c.wave, W = c.a.W;
+  unsigned long long tk[NH];
+  int nval = 0;
+  {
+    // the maxima in the double domain (one v_max_f64 per candidate; fmax drops a NaN as "v > -inf" does) and ONE conversion to the key at the
+    // end: the scans are instruction-issue bound
+    double mx[NH];
+#pragma unroll
+    for (int h = 0; h < NH; ++h) mx[h] = -INFINITY;
+    scan_cands<NT>(c.cand, ncand, tid, [&](double v, int cc) {
+      nval += v > -INFINITY ? 1 : 0;
+      if (NH == 2 && ((cc / NT) & 1)) mx[NH - 1] = fmax(mx[NH - 1], v);
+      else mx[0] = fmax(mx[0], v);
+    });
+#pragma unroll
+    for (int h = 0; h < NH; ++h) tk[h] = mx[h] > -INFINITY ? dkey(mx[h]) : 0ull;      // (no candidate: below every key of a finite value)
+  }
+  GSTAMP(8);
+  nval = wave_sum_rows(nval);
+  if (lane == 0) ss.red_i[wave] = nval;
+  {
+    const int kth = (W + NWV - 1) / NWV;
+    unsigned long long p = 0ull;
+    // two bits per step (the three thresholds of a step are independent ballots), bits 63 .. 36 only: the result is a LOWER bound of the
+    // wave's k-th largest maximum either way, 2^-16 relative below it at most, and the search is the most instruction-heavy part of this phase
+    for (int bit = 62; bit >= 36; bit -= 2) {
+      const unsigned long long t1 = p | (1ull << bit), t2 = p | (2ull << bit), t3 = p | (3ull << bit);
+      int c1 = __popcll(__ballot(tk[0] >= t1)), c2 = __popcll(__ballot(tk[0] >= t2)), c3 = __popcll(__ballot(tk[0] >= t3));
+      if (NH == 2) {
+        c1 += __popcll(__ballot(tk[NH - 1] >= t1)); c2 += __popcll(__ballot(tk[NH - 1] >= t2)); c3 += __popcll(__ballot(tk[NH - 1] >= t3));
+      }
+      p = c3 >= kth ? t3 : (c2 >= kth ? t2 : (c1 >= kth ? t1 : p));
+    }
+    if (lane == 0) ss.wthr[wave] = p;
+  }
+  if (tid == 0) { ss.scnt = 0; ss.ovf = 0; }
+  GSTAMP(12);
+  __syncthreads();
+  GSTAMP(13);
+  // lane j keeps wave j's value in registers and v_readlane broadcasts it (no chain of dependent LDS reads); every wave forms the block-wide
+  // counts itself from the waves' rows: two barriers, not three
+  const unsigned long long tj = ss.wthr[lane < NWV ? lane : 0];
+  const int tj_lo = (int)(unsigned)(tj & 0xffffffffull), tj_hi = (int)(unsigned)(tj >> 32);
+  int mycnt = 0;
+  for (int j = 0; j < NWV; ++j) {
+    const unsigned long long t = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(tj_hi, j) << 32) | (unsigned)__builtin_amdgcn_readlane(tj_lo, j);
+    int cnt = __popcll(__ballot(tk[0] >= t));
+    if (NH == 2) cnt += __popcll(__ballot(tk[NH - 1] >= t));
+    mycnt = lane == j ? (t != 0ull ? cnt : 0) : mycnt;
+  }
+  if (lane < NWV) ss.wcnt[wave][lane] = mycnt;
+  GSTAMP(14);
+  __syncthreads();
+  int reach = 0;
+  {
+    const int jl = lane < NWV ? lane : 0;
+#pragma unroll
+    for (int w = 0; w < NWV; ++w) reach += ss.wcnt[w][jl];
+    total = lane < NWV ? ss.red_i[jl] : 0;
+  }
+  theta = (lane < NWV && reach >= W) ? tj : 0ull;
+  static_assert(NWV <= 16, "the waves' bounds sit in the first row of 16 lanes");
+  total = __builtin_amdgcn_readfirstlane(row16_sum(total));
+  theta = row16_max_u64(theta);
+  theta = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(theta >> 32)) << 32) |
+          (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(theta & 0xffffffffull));
+  GSTAMP(9);
+}
+// (b) the candidates v >= thd into sv_v / sv_i.  One scan: the INDICES of a thread's first two survivors wait in registers, a second scan
+// only for a thread with more.  One atomic per WAVE for the position (two ballots; per-thread atomics only with a three-survivor thread).
+template <int NT>
+__device__ __forceinline__ void compact_survivors(BeamCtx &c, SelectShared<NT / 64> &ss, int ncand, double thd) {
+  int cnt = 0, kc0 = 0, kc1 = 0;
+  scan_cands<NT>(c.cand, ncand, c.tid, [&](double v, int cc) {
+    if (v >= thd) {
+      kc0 = cnt == 0 ? cc : kc0;
+      kc1 = cnt == 1 ? cc : kc1;
+      ++cnt;
+    }
+  });
+  int pos = 0;
+  {
+    const unsigned long long b1 = __ballot(cnt >= 1), b2 = __ballot(cnt >= 2), b3 = __ballot(cnt >= 3);
+    if (b3 == 0ull) {
+      const unsigned long long below = (1ull << c.lane) - 1ull;
+      const int wtot = __popcll(b1) + __popcll(b2);
+      int wbase = 0;
+      if (c.lane == 0 && wtot > 0) wbase = atomicAdd(&ss.scnt, wtot);
+      pos = __builtin_amdgcn_readfirstlane(wbase) + __popcll(b1 & below) + __popcll(b2 & below);
+    } else {
+      pos = cnt ? atomicAdd(&ss.scnt, cnt) : 0;
+    }
+  }
+  if (cnt && pos + cnt > c.a.smax) ss.ovf = 1;
+  else if (cnt <= 2) {
+    if (cnt > 0) { c.sv_v[pos] = c.cand[kc0]; c.sv_i[pos] = kc0; }
+    if (cnt > 1) { c.sv_v[pos + 1] = c.cand[kc1]; c.sv_i[pos + 1] = kc1; }
+  } else scan_cands<NT>(c.cand, ncand, c.tid, [&](double v, int cc) { if (v >= thd) { c.sv_v[pos] = v; c.sv_i[pos] = cc; ++pos; } });
+}
+// (c) S <= 256 survivors SORTED, one per thread of waves 0-3, by a bitonic network under the strict order of cand_better() (the padding
+// compares equal to itself and worse than every survivor): 36 compare-exchange steps, 33 inside a wave.  Position r of the row IS rank r.
+template <int NT>
+__device__ __forceinline__ void rank_bitonic(BeamCtx &c, int S) {
+  const int tid = c.tid, lane = c.lane;
+  unsigned khi = 0u, klo = 0u; int ix = 0x7fffffff;       // (padding: key 0 is below the key of every finite value)
+  const bool act = c.wave < 4;                             // (scalar: the other waves only join the barriers of the three cross-wave steps)
+  if (act && tid < S) { const unsigned long long k0 = dkey(c.sv_v[tid]); khi = (unsigned)(k0 >> 32); klo = (unsigned)k0; ix = c.sv_i[tid]; }
+  const bool pick_shl = (unsigned)__builtin_amdgcn_update_dpp(-1, lane, 0x104, 0xf, 0xf, false) == (unsigned)(lane ^ 4);
+  unsigned *const xk = reinterpret_cast<unsigned *>(c.sv_v);     // cross-wave steps: (key hi, key lo) pairs | indices in the survivor arrays
+  int *const xi = c.sv_i;
+  // element tid of a K-block keeps the better of a pair iff (it is the lower partner) == (its block ends best-first)
+#define CTCN_BSTEP(J, K) bitonic_step<J>(khi, klo, ix, ((tid & (J)) == 0) == ((tid & (K)) == 0), lane, pick_shl)
+  auto lds_step = [&](int j, int k) {
+    if (act) { xk[2 * tid] = khi; xk[2 * tid + 1] = klo; xi[tid] = ix; }
+    __syncthreads();
+    if (act) {
+      const int pt = tid ^ j;
+      const unsigned ohi = xk[2 * pt], olo = xk[2 * pt + 1]; const int oi = xi[pt];
+      const bool take = elem_before(ohi, olo, oi, khi, klo, ix) == (((tid & j) == 0) == ((tid & k) == 0));
+      khi = take ? ohi : khi; klo = take ? olo : klo; ix = take ? oi : ix;
+    }
+    __syncthreads();
+  };
+  auto tail = [&](int k) {                           // the in-wave steps j = 32 .. 1 of block size k >= 64
+    if (act) { CTCN_BSTEP(32, k); CTCN_BSTEP(16, k); CTCN_BSTEP(8, k); CTCN_BSTEP(4, k); CTCN_BSTEP(2, k); CTCN_BSTEP(1, k); }
+  };
+  if (act) {
+    CTCN_BSTEP(1, 2);
+    CTCN_BSTEP(2, 4); CTCN_BSTEP(1, 4);
+    CTCN_BSTEP(4, 8); CTCN_BSTEP(2, 8); CTCN_BSTEP(1, 8);
+    CTCN_BSTEP(8, 16); CTCN_BSTEP(4, 16); CTCN_BSTEP(2, 16); CTCN_BSTEP(1, 16);
+    CTCN_BSTEP(16, 32); CTCN_BSTEP(8, 32); CTCN_BSTEP(4, 32); CTCN_BSTEP(2, 32); CTCN_BSTEP(1, 32);
+  }
+  tail(64);
+  lds_step(64, 128); tail(128);
+  lds_step(128, 256); lds_step(64, 256); tail(256);
+#undef CTCN_BSTEP
+  // (lds_step ends with a barrier: the exchange area is free again; the value is read back from the candidate table, which this path
+  // leaves untouched -- bit for bit the double that was scored, where inverting dkey would fold -0.0 onto +0.0)
+  if (act && tid < S && tid < c.a.W) { c.sel[tid] = ix; c.selv[tid] = c.cand[ix]; }
+}
+// (c) any S: a survivor's rank = the survivors that beat it, counted by P neighbouring threads (part p: survivors p, p + P, ...; RU entries
+// are read before they are compared: dependent LDS reads cost a full latency each), butterfly sum over the P lanes
+template <int NT>
+__device__ __forceinline__ void rank_pair_count(BeamCtx &c, int S) {
+  const int tid = c.tid;
+  int P = 1, lgP = 0;
+  while (2 * P * S <= NT && P < 16) { P *= 2; ++lgP; }
+  for (int e0 = 0; e0 < S; e0 += NT >> lgP) {
+    const int e = e0 + (tid >> lgP), part = tid & (P - 1);
+    const bool have = e < S;
+    const double mv = c.sv_v[have ? e : 0]; const int mi = c.sv_i[have ? e : 0];
+    constexpr int RU = NT >= 1024 ? 4 : 8;
+    int rank = 0, q = part;
+    for (; q + (RU - 1) * P < S; q += RU * P) {
+      double qv[RU]; int qi[RU];
+#pragma unroll
+      for (int u = 0; u < RU; ++u) { qv[u] = c.sv_v[q + u * P]; qi[u] = c.sv_i[q + u * P]; }
+#pragma unroll
+      for (int u = 0; u < RU; ++u) rank += cand_better(qv[u], qi[u], mv, mi) ? 1 : 0;
+    }
+    for (; q < S; q += P) rank += cand_better(c.sv_v[q], c.sv_i[q], mv, mi) ? 1 : 0;
+    for (int o = 1; o < P; o <<= 1) rank += __shfl_xor(rank, o, 64);
+    if (have && part == 0 && rank < c.a.W) { c.sel[rank] = mi; c.selv[rank] = mv; }
+  }
+}
+// the selection: sel[r] / selv[r] = candidate and score of rank r; returns the size of the new beam
+template <int NT>
+__device__ __forceinline__ int select_top_w(BeamCtx &c, SelectShared<NT / 64> &ss) {
+  const int ncand = c.nb * c.a.V, W = c.a.W;
+  unsigned long long theta;
+  int total;
+  selection_bound<NT>(c, ss, ncand, theta, total);
+  // (no bound that W maxima reach: then everything valid is ranked, if it fits)
+  const bool prune = total > W && theta != 0ull;
+  bool ranked = false;
+  if (prune || total <= c.a.smax) {
+    // The bound as a double: f64_key is an order-preserving bijection of the finite values, so key(v) >= theta <=> v >= thd (one
+    // v_cmp_ge_f64; a NaN fails both; theta >= 2^52 > key(-inf) whenever a finite maximum produced it, so "v > -inf" is implied).  Without
+    // a bound every finite candidate is ranked: v >= -DBL_MAX.
+    const double thd = prune ? key_f64(theta) : -1.7976931348623157e308;
+    compact_survivors<NT>(c, ss, ncand, thd);
+    __syncthreads();
+    GSTAMP(10);
+#ifdef CTCN_BEAM_STATS
+    if (c.b == 0 && c.tid == 0) { c.gst[6] += ss.scnt; c.gst[7] += ss.ovf ? 1 : 0; }
+#endif
+    if (!ss.ovf) {
+      const int S = ss.scnt;
+      if (S <= 256 && c.a.bitonic) rank_bitonic<NT>(c, S);
+      else rank_pair_count<NT>(c, S);
+      ranked = true;
+    }
+    __syncthreads();
+    GSTAMP(11);
+  }
+  if (ranked) return min(W, total);
+  // (the rounds reuse red_i[], which every thread has just summed into `total`: when the ranking block was skipped no barrier separates those
+  // reads from round 0's writes; `ranked` is uniform)
+  __syncthreads();
+  return arg_max_rounds<NT>(c.cand, ncand, W, ss.red_v, ss.red_i, c.sel, c.selv, c.wave, [] { __syncthreads(); }, [](int) {});
+}
+// 5. materialise the new beam N: entry r <- candidate sel[r]
+__device__ __forceinline__ void materialise(BeamCtx &c, int m, int *s_nodes) {
+  if (c.tid >= m) return;
+  const BeamState &L = c.L, &N = c.N;
+  const int tid = c.tid, cs = c.sel[tid];
+  const int i = c.div_v(cs), kk = cs - i * c.a.V;
+  auto copy_slot = [&](int s) {
+    N.node[tid] = L.node[s]; N.len[tid] = L.len[s]; N.last[tid] = L.last[s]; N.par[tid] = L.par[s];
+    N.pNB[tid] = c.sNB[s]; N.pB[tid] = c.sB[s]; N.pT[tid] = c.sT[s];
+  };
+  if (kk == 0) {
+    copy_slot(i);
+  } else {
+    const int k = cand_class(kk, c.a.blank);
+    int ip = -1;
+    {
+      const int ow = c.cown[cs];
+      if ((unsigned)ow < (unsigned)c.nb && c.mfrom[ow] == i && L.last[ow] == k) ip = ow;
+    }
+    if (ip >= 0) {   // this slot holds the merged entry of existing labelling ip (first touched as an extension)
+      copy_slot(ip);
+    } else {
+      // trie child lookup / insert: key = (parent node, symbol)
+      const int parent = L.node[i];
+      const unsigned long long key = ((unsigned long long)(unsigned)parent << 32) | (unsigned)k;
+      unsigned h = (unsigned)mix64(key) & c.htmask;
+      int id = -1;
+      for (int probe = 0; probe <= c.htmask; ++probe) {
+        const unsigned long long prev = atomicCAS(&c.keys[h], HT_EMPTY, key);
+        if (prev == HT_EMPTY) {
+          id = atomicAdd(s_nodes, 1);
+          if (id < c.a.max_nodes) { c.npar[id] = parent; c.nsym[id] = k; }
+          c.ids[h] = id;
+          break;
+        }
+        if (prev == key) { id = c.ids[h]; break; }
+        h = (h + 1) & c.htmask;
+      }
+      N.node[tid] = id; N.len[tid] = L.len[i] + 1; N.last[tid] = k; N.par[tid] = parent;
+      const double pr = c.selv[tid];
+      N.pNB[tid] = pr; N.pB[tid] = LOG_ZERO; N.pT[tid] = pr;
+    }
+  }
+  const int nd = N.node[tid];
+  if ((unsigned)nd < (unsigned)c.a.max_nodes) c.nslot[nd] = tid;     // (find_parents of the next frame finds a parent labelling's slot here)
+}
+
 template <int NT>
 __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
-  constexpr int NWV = NT / 64;
-  extern __shared__ __attribute__((aligned(16))) double dsm[];   // lg[V] | cand[W*V] (if it fits) | beam state, selection lists (below)
-  __shared__ double red_v[NWV];
-  __shared__ int red_i[NWV];
-  __shared__ unsigned long long wthr[NWV];                     // selection: every wave's bound
-  __shared__ int wcnt[NWV][NWV];                               //            ... and how many of wave w's maxima reach wave j's
-  __shared__ int s_flag, s_nodes, s_best;
-  __shared__ int s_scnt, s_ovf;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (scalar: per-wave decisions are scalar branches)
-  const int b = blockIdx.x, V = a.V, W = a.W, B = a.B, T = a.T, blank = a.blank;
-  double *lg = dsm;
-  double *cand = a.cand_in_lds ? dsm + V : a.cand_global + (size_t)b * W * V;
-  // dynamic LDS behind lg / cand: doubles first (2 x {pB, pNB, pT}, sNB, sB, sT, selv: 10 x wcap; sv_v: smax), then ints (2 x {node, len,
-  // last, par}, mfrom, sel: 10 x wcap; sv_i: smax) -- the host sizes the launch with the same formula (beam_state_lds)
-  const int wcap = a.wcap, SEL_SMAX = a.smax;
-  double *const dbase = dsm + V + (a.cand_in_lds ? W * V : 0);
-  int *const ibase = reinterpret_cast<int *>(dbase + 10 * wcap + SEL_SMAX);
-  auto beam_state = [&](int k) {
-    BeamState st;
-    st.pB = dbase + (3 * k) * wcap; st.pNB = st.pB + wcap; st.pT = st.pNB + wcap;
-    st.node = ibase + (4 * k) * wcap; st.len = st.node + wcap; st.last = st.len + wcap; st.par = st.last + wcap;
-    return st;
-  };
-  double *const sNB = dbase + 6 * wcap, *const sB = sNB + wcap, *const sT = sB + wcap, *const selv = sT + wcap;
-  double *const sv_v = selv + wcap;                            // selection: survivors of the pruning bound (value | candidate index)
-  int *const mfrom = ibase + 8 * wcap, *const sel = mfrom + wcap, *const sv_i = sel + wcap;
-  // (round 6) the LM table in LDS when the launch has room for it: one LDS read instead of a global gather per candidate and frame; the raw
-  // ln-probs are copied, the product with alpha is formed per use by lm_scaled() (rounded on its own: never re-inline the multiply, the compiler fuses it into the sum)
-  const double *lmt = a.lm;
-  if (a.lm_in_lds) {
-    double *lml = reinterpret_cast<double *>(reinterpret_cast<char *>(sv_i + SEL_SMAX) + ((8 - ((size_t)(10 * wcap + SEL_SMAX) * 4) % 8) % 8));
-    for (int i = tid; i < (V + 1) * (V + 1); i += NT) lml[i] = a.lm[i];
-    lmt = lml;
-  }
-  unsigned long long *keys = a.ht_keys + (size_t)b * a.ht_size;
-  int *ids = a.ht_ids + (size_t)b * a.ht_size;
-  int *npar = a.node_par + (size_t)b * a.max_nodes;
-  int *nsym = a.node_sym + (size_t)b * a.max_nodes;
-  // Lookups instead of scans of the beam (last session of round 6; both were ~200 LDS reads per thread and frame at the reference's W = 200):
-  //   nslot[node] = beam slot that holds trie node `node` -- written for every entry of a new beam, read by step 2 of the next frame;
-  //   cown[c]     = beam slot whose labelling merges with extension candidate c -- written by step 3b, read by step 5 of the same frame.
-  // Neither table is initialised or stamped: a value is USED only if the slot it names passes the very test the scan applied (L.node[s] ==
-  // pnode; mfrom[s] == i && L.last[s] == k), which at most one slot of a beam can pass -- and for a node / candidate that does have such a
-  // slot the table was written this frame.  Anything else (stale, never written) fails the test exactly as the scan found nothing.
-  // c / V for candidate indices c < W * V: one multiply-high by ceil(2^32 / V) (exact while c * V < 2^32: W * V * V = 2^20 at the reference's width and vocabulary) -- the runtime
-  // division hipcc emits is ~25 instructions, and step 3a pays it per candidate: the kernel's parallel phases are instruction-issue bound
-  const unsigned vmagic = 0xffffffffu / (unsigned)V + 1u;
-  const bool vmagic_ok = (unsigned long long)W * V * V < (1ull << 32);         // (a vocabulary of thousands: the plain division)
-  auto div_v = [&](int c) { return vmagic_ok ? (int)__umulhi((unsigned)c, vmagic) : c / V; };
-  int *nslot = a.node_slot + (size_t)b * a.max_nodes;
-  int *cown = a.cand_owner + (size_t)b * W * V;
-  const int htmask = a.ht_size - 1;
-
-  int cur = 0, nb = 1, status = 0;
+  extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];   // GenericLds
+  __shared__ SelectShared<NT / 64> ss;
+  __shared__ int s_flag, s_nodes;
+  BeamCtx c = {a};
+  c.carve(dsm);
+  const int tid = c.tid, lane = c.lane, b = c.b, V = a.V, B = a.B, T = a.T, blank = a.blank;
+  if (a.lm_in_lds)                                               // (the raw ln-probs: lm_scaled() rounds the product with alpha on its own per use)
+    for (int i = tid; i < (V + 1) * (V + 1); i += NT) const_cast<double *>(c.lm)[i] = a.lm[i];
+  int cur = 0, status = 0;
+  c.nb = 1;
 #ifdef CTCN_BEAM_STATS
-  long long gst[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, glast = clock64(), gframes = 0;
+  for (int i = 0; i < 16; ++i) c.gst[i] = 0;
+  c.glast = clock64();
+  long long gframes = 0;
 #endif
   if (tid == 0) {
-    const BeamState S0 = beam_state(0);
+    const BeamState S0 = c.state(0);
     S0.node[0] = 0; S0.len[0] = 0; S0.last[0] = -1; S0.par[0] = -1;
     S0.pB[0] = 0.0; S0.pNB[0] = LOG_ZERO; S0.pT[0] = 0.0;   // BeamSearch.py:83-87
     s_nodes = 1; s_flag = 0;
-    npar[0] = -1; nsym[0] = -1;
-    nslot[0] = 0;
+    c.npar[0] = -1; c.nsym[0] = -1;
+    c.nslot[0] = 0;
   }
   __syncthreads();
   const int nframes = min(max(a.lens[b], 0), T);
@@ -235,7 +727,6 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
   float pb_lane = 0.0f, pb_before = 0.0f;
   int chunk0 = -64;
   for (int t = 0; t < nframes; ++t) {
-    const float *row = a.x + ((size_t)t * B + b) * V;
     if (t >= chunk0 + 64) {
       chunk0 = t;
       const int tl = min(t + lane, nframes - 1);
@@ -246,438 +737,48 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
     const float pprev = pb_before;
     pb_before = pblank;
     if ((1.0f - pblank) < 0.1f) continue;                         // BeamSearch.py:93-94 (float32 compare)
-    const BeamState L = beam_state(cur), N = beam_state(cur ^ 1);
+    const bool rep_ok = t > 0 && pprev < 0.9f;                    // BeamSearch.py:63 (float32 compare)
+    c.L = c.state(cur); c.N = c.state(cur ^ 1);
     GSTAMP(0);
 #ifdef CTCN_BEAM_STATS
     ++gframes;
 #endif
-    // 1. ln of the frame's probabilities (math.log of the float32 value widened to double)
-    for (int k = tid; k < V; k += NT) {
-      const float p = a.input_is_prob ? row[k] : expf(row[k]);
+    for (int k = tid; k < V; k += NT) {                            // 1. ln of the frame (math.log of the float32 value widened to double)
+      const float xk = a.x[((size_t)t * B + b) * V + k], p = a.input_is_prob ? xk : expf(xk);
       if (!(p > 0.0f)) s_flag = 2;
-      lg[k] = log((double)p);
+      c.lg[k] = log((double)p);
     }
-    const bool rep_ok = t > 0 && pprev < 0.9f;                     // BeamSearch.py:63 (float32 compare)
-    // 2. which beam (if any) is the parent labelling of beam i' -> its extension by last(i') merges with i'
-    if (tid < nb) {
-      int m = -1;
-      if (L.len[tid] > 0) {
-        const int pnode = L.par[tid];
-        if ((unsigned)pnode < (unsigned)a.max_nodes) {
-          const int sl = nslot[pnode];
-          if ((unsigned)sl < (unsigned)nb && L.node[sl] == pnode) m = sl;
-        }
-      }
-      mfrom[tid] = m;
-    }
+    find_parents(c);
     __syncthreads();
     if (s_flag == 2) { status = 2; break; }
     GSTAMP(1);
-    // 3a. extension scores (calcExtPr), candidate slot c = i*V + 1 + kk  (kk enumerates k != blank in order)
-    const int ncand = nb * V;
-    // (four candidates per trip with 256 threads -- two with 1 024 --: the slot reads, then the LM gathers -- global memory -- of all four are issued before the first is used; the same
-    // expression per candidate)
-    constexpr int EU = 4;                 // (candidates per trip: a trip is one round trip to the LM table in L2; W = 200 at 1 024 threads: 4 trips, was 7 with two per trip)
-    for (int c0 = tid; c0 < ncand; c0 += EU * NT) {
-      int ci[EU], ck[EU], cl[EU], cln[EU];
-      double lmv[EU];
-#pragma unroll
-      for (int u = 0; u < EU; ++u) {
-        const int c = min(c0 + u * NT, ncand - 1);
-        ci[u] = div_v(c);
-        const int kk = c - ci[u] * V;
-        ck[u] = kk == 0 ? -1 : ((kk - 1 < blank) ? kk - 1 : kk);
-        cln[u] = L.len[ci[u]]; cl[u] = L.last[ci[u]];
-      }
-#pragma unroll
-      for (int u = 0; u < EU; ++u) {
-        const int c1 = cln[u] > 0 ? cl[u] : V;
-        lmv[u] = lmt[(size_t)c1 * (V + 1) + max(ck[u], 0)];
-      }
-#pragma unroll
-      for (int u = 0; u < EU; ++u) {
-        const int c = c0 + u * NT;
-        if (c < ncand && ck[u] >= 0) {
-          const int i = ci[u], k = ck[u];
-          const double bigram = lm_scaled(lmv[u], a.alpha);
-          const double base = (cln[u] > 0 && cl[u] == k && rep_ok) ? L.pB[i] : L.pT[i];
-          cand[c] = lg[k] + bigram + base;
-        }
-      }
-    }
+    score_extensions<NT>(c, rep_ok);
     __syncthreads();
     GSTAMP(2);
-    // 3b. stay entries, merged with the matching extension in the reference's visiting order
-    if (tid < nb) {
-      const int ip = tid;
-      double s_nb = LOG_ZERO;
-      if (L.len[ip] > 0) s_nb = L.pNB[ip] + lg[L.last[ip]];         // BeamSearch.py:102-103
-      const double s_b = L.pT[ip] + lg[blank];                      // :106
-      Fields e{LOG_ZERO, LOG_ZERO, LOG_ZERO};
-      const int i = mfrom[ip];
-      if (i >= 0) {
-        const int k = L.last[ip];
-        const int kk = (k < blank) ? k + 1 : k;
-        const int ce = i * V + kk;
-        cown[ce] = ip;
-        const double pr = cand[ce];
-        if (i < ip) { apply_ext(e, pr); apply_stay(e, s_nb, s_b); cand[ce] = e.t; cand[ip * V] = -INFINITY; }
-        else        { apply_stay(e, s_nb, s_b); apply_ext(e, pr); cand[ip * V] = e.t; cand[ce] = -INFINITY; }
-      } else {
-        apply_stay(e, s_nb, s_b);
-        cand[ip * V] = e.t;
-      }
-      sNB[ip] = e.nb; sB[ip] = e.b; sT[ip] = e.t;
-    }
+    merge_stays(c);
     __syncthreads();
     GSTAMP(3);
-    // 4. BHat = top-W by (prTotal desc, insertion index asc).
-    // Round 5 (wide beams: the reference's class default is W = 200, ctcDecoder.py:170): NOT W block-wide arg-max rounds any more -- each a scan
-    // of all nb * V candidates (99 KB of global memory at W = 200, V = 62), a shuffle tree and two barriers -- but the selection scheme of the
-    // fast kernel in its plainest form:
-    //  (a) a lower bound of the W-th best candidate: every thread keeps the best of its candidates (two, of disjoint halves of its share, with
-    //      256 threads), every WAVE finds the k-th largest of its maxima, k = ceil(W / waves), by a bitwise binary search on the order-preserving
-    //      64-bit keys (ballot + popcount: no LDS, no barrier), and the bound is the smallest of the waves' values -- at least waves * k >= W
-    //      distinct candidates reach it, so the true top W all do (exact pruning; a tighter bound only means fewer survivors);
-    //  (b) the survivors (about W, more when values tie at the bound) are compacted into LDS;
-    //  (c) each is ranked by counting the survivors that beat it under the same explicit order cand_better() the rounds used.
-    // Same set, same order.  The rounds remain as the fallback (a wave with fewer than k candidates, or more than SEL_SMAX survivors: exact ties
-    // by the hundred).
-    int m = 0;
-    bool ranked = false;
-    {
-      // (the candidate table is in global memory from W * V > 4 096 on: eight loads in flight per thread, or every scan is a chain of L2 round trips)
-      auto scan = [&](auto &&visit) {
-        constexpr int SU = NT >= 1024 ? 4 : 8;          // (1 024 threads: 128 registers each, and a fourth of the candidates per thread)
-        int c = tid;
-        for (; c + (SU - 1) * NT < ncand; c += SU * NT) {
-          double v[SU];
-#pragma unroll
-          for (int u = 0; u < SU; ++u) v[u] = cand[c + NT * u];
-#pragma unroll
-          for (int u = 0; u < SU; ++u) visit(v[u], c + NT * u);
-        }
-        for (; c < ncand; c += NT) visit(cand[c], c);
-      };
-      constexpr int NH = NT >= 1024 ? 1 : 2;                   // maxima per thread
-      unsigned long long tk[NH];
-      int nval = 0;
-      {
-        // (last session of round 6: the maxima in the double domain -- one v_max_f64 per candidate; fmax drops a NaN as "v > -inf" does -- and
-        // ONE conversion to the order-preserving key at the end: the scans are instruction-issue bound, ~25 -> ~8 instructions per candidate)
-        double mx[NH];
-#pragma unroll
-        for (int h = 0; h < NH; ++h) mx[h] = -INFINITY;
-        scan([&](double v, int c) {
-          nval += v > -INFINITY ? 1 : 0;
-          if (NH == 2 && ((c / NT) & 1)) mx[NH - 1] = fmax(mx[NH - 1], v);
-          else mx[0] = fmax(mx[0], v);
-        });
-#pragma unroll
-        for (int h = 0; h < NH; ++h) tk[h] = mx[h] > -INFINITY ? dkey(mx[h]) : 0ull;      // (no candidate: below every key of a finite value)
-      }
-      GSTAMP(8);
-      nval = wave_sum_rows(nval);
-      if (lane == 0) red_i[wave] = nval;
-      {
-        const int kth = (W + NWV - 1) / NWV;
-        unsigned long long p = 0ull;
-        // Bitwise search, two bits per step (the three thresholds of a step are independent ballots), bits 63 .. 36 only: the result is a LOWER
-        // bound of the wave's k-th largest maximum either way, 2^-16 relative below it at most -- the survivor count did not move (225 | 207 per
-        // frame at W = 200) while the search is the most instruction-heavy part of the bound phase, which is issue-bound (sixteen waves at once:
-        // the first barrier waits ~3 000 cycles for the slowest wave's scan + search): 14 steps instead of 18, 44 in round 5.
-        for (int bit = 62; bit >= 36; bit -= 2) {
-          const unsigned long long t1 = p | (1ull << bit), t2 = p | (2ull << bit), t3 = p | (3ull << bit);
-          int c1 = __popcll(__ballot(tk[0] >= t1)), c2 = __popcll(__ballot(tk[0] >= t2)), c3 = __popcll(__ballot(tk[0] >= t3));
-          if (NH == 2) {
-            c1 += __popcll(__ballot(tk[NH - 1] >= t1)); c2 += __popcll(__ballot(tk[NH - 1] >= t2)); c3 += __popcll(__ballot(tk[NH - 1] >= t3));
-          }
-          p = c3 >= kth ? t3 : (c2 >= kth ? t2 : (c1 >= kth ? t1 : p));
-        }
-        if (lane == 0) wthr[wave] = p;
-      }
-      if (tid == 0) { s_scnt = 0; s_ovf = 0; }
-      GSTAMP(12);
-      __syncthreads();
-      GSTAMP(13);
-      // the waves' values are NWV candidate bounds; the smallest is always valid, a larger one is valid whenever W of ALL the maxima still reach
-      // it: every wave counts its own maxima against every candidate (NWV ballots), the largest candidate with a block-wide count >= W wins --
-      // the survivors drop from ~1.9 W to ~1.2 W at W = 200, and a wave that has no k candidates (narrow beam) no longer voids the bound.
-      // (round 6: lane j keeps candidate j in registers and v_readlane broadcasts it -- no chain of dependent LDS reads; every wave forms the
-      // block-wide counts itself from the waves' rows, so two barriers instead of three)
-      const unsigned long long tj = wthr[lane < NWV ? lane : 0];
-      const int tj_lo = (int)(unsigned)(tj & 0xffffffffull), tj_hi = (int)(unsigned)(tj >> 32);
-      int mycnt = 0;
-      for (int j = 0; j < NWV; ++j) {
-        const unsigned long long t = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(tj_hi, j) << 32) | (unsigned)__builtin_amdgcn_readlane(tj_lo, j);
-        int cnt = __popcll(__ballot(tk[0] >= t));
-        if (NH == 2) cnt += __popcll(__ballot(tk[NH - 1] >= t));
-        mycnt = lane == j ? (t != 0ull ? cnt : 0) : mycnt;
-      }
-      if (lane < NWV) wcnt[wave][lane] = mycnt;
-      GSTAMP(14);
-      __syncthreads();
-      int reach = 0, total = 0;
-      {
-        const int jl = lane < NWV ? lane : 0;
-#pragma unroll
-        for (int w = 0; w < NWV; ++w) reach += wcnt[w][jl];
-        total = lane < NWV ? red_i[jl] : 0;
-      }
-      unsigned long long theta = (lane < NWV && reach >= W) ? tj : 0ull;
-      static_assert(NWV <= 16, "the waves' bounds sit in the first row of 16 lanes");
-      total = __builtin_amdgcn_readfirstlane(row16_sum(total));
-      theta = row16_max_u64(theta);
-      theta = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(theta >> 32)) << 32) |
-              (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(theta & 0xffffffffull));
-      GSTAMP(9);
-      // (no candidate bound that W maxima reach -- the first frames, when the beam is still narrow --: then everything valid is ranked, if it fits)
-      const bool prune = total > W && theta != 0ull;
-      if (prune || total <= SEL_SMAX) {
-        // one scan: a thread's first two survivors wait in registers (it rarely has more than one), a second scan only for a thread with more
-        // The bound as a double: dkey is an order-preserving bijection of the finite values, so dkey(v) >= theta <=> v >= thd (one
-        // v_cmp_ge_f64; a NaN fails both; theta >= 2^52 > dkey(-inf) whenever a finite maximum produced it, so "v > -inf" is implied).  Without
-        // a bound every finite candidate is ranked: v >= -DBL_MAX.  Only the INDICES of a thread's first two survivors wait in registers; their
-        // values are read again when they are stored.
-        double thd = -1.7976931348623157e308;
-        if (prune) {
-          const unsigned long long tb = (theta >> 63) ? (theta & 0x7fffffffffffffffull) : ~theta;
-          thd = __longlong_as_double((long long)tb);
-        }
-        int cnt = 0, kc0 = 0, kc1 = 0;
-        scan([&](double v, int c) {
-          if (v >= thd) {
-            kc0 = cnt == 0 ? c : kc0;
-            kc1 = cnt == 1 ? c : kc1;
-            ++cnt;
-          }
-        });
-        // one atomic per WAVE (a thread rarely keeps more than two survivors: then its position follows from two ballots; a wave with such a
-        // thread takes the per-thread atomics) -- ~225 same-address LDS atomics per frame were a serial chain in front of the barrier
-        int pos = 0;
-        {
-          const unsigned long long b1 = __ballot(cnt >= 1), b2 = __ballot(cnt >= 2), b3 = __ballot(cnt >= 3);
-          if (b3 == 0ull) {
-            const unsigned long long below = (1ull << lane) - 1ull;
-            const int wtot = __popcll(b1) + __popcll(b2);
-            int wbase = 0;
-            if (lane == 0 && wtot > 0) wbase = atomicAdd(&s_scnt, wtot);
-            pos = __builtin_amdgcn_readfirstlane(wbase) + __popcll(b1 & below) + __popcll(b2 & below);
-          } else {
-            pos = cnt ? atomicAdd(&s_scnt, cnt) : 0;
-          }
-        }
-        if (cnt && pos + cnt > SEL_SMAX) s_ovf = 1;
-        else if (cnt <= 2) {
-          if (cnt > 0) { sv_v[pos] = cand[kc0]; sv_i[pos] = kc0; }
-          if (cnt > 1) { sv_v[pos + 1] = cand[kc1]; sv_i[pos + 1] = kc1; }
-        } else scan([&](double v, int c) { if (v >= thd) { sv_v[pos] = v; sv_i[pos] = c; ++pos; } });
-        __syncthreads();
-        GSTAMP(10);
-#ifdef CTCN_BEAM_STATS
-        if (b == 0 && tid == 0) { gst[6] += s_scnt; gst[7] += s_ovf ? 1 : 0; }
-#endif
-        if (!s_ovf) {
-          // P threads per survivor (a power of two, neighbouring lanes), thread part p counts among the survivors p, p + P, ...; eight entries
-          // are read before they are compared (a loop of dependent LDS reads costs a full LDS latency per entry); butterfly sum over the P lanes
-          const int S = s_scnt;
-          if (S <= 256 && a.bitonic) {
-            // (last session of round 6) Up to 256 survivors -- the reference's W = 200 leaves ~1.1 W -- are SORTED, one per thread of waves 0-3, by a
-            // bitonic network under the same strict order cand_better() (value descending, candidate index ascending; the padding compares
-            // equal to itself and worse than every survivor, so it never moves in front of one): 36 compare-exchange steps, 33 of them inside a
-            // wave, instead of S^2 = 50 000 comparisons through ~1 800 LDS reads per frame.  Position r of the sorted row IS rank r.
-            unsigned khi = 0u, klo = 0u; int ix = 0x7fffffff;       // (padding: key 0 is below the key of every finite value)
-            const bool act = wave < 4;                          // (scalar: the other waves only join the barriers of the three cross-wave steps)
-            if (act && tid < S) { const unsigned long long k0 = dkey(sv_v[tid]); khi = (unsigned)(k0 >> 32); klo = (unsigned)k0; ix = sv_i[tid]; }
-            const bool pick_shl = (unsigned)__builtin_amdgcn_update_dpp(-1, lane, 0x104, 0xf, 0xf, false) == (unsigned)(lane ^ 4);
-            unsigned *const xk = reinterpret_cast<unsigned *>(sv_v);     // cross-wave steps: (key hi, key lo) pairs | indices in the survivor arrays
-            // element tid of a K-block keeps the better of a pair iff (it is the lower partner) == (its block ends best-first)
-#define CTCN_BSTEP(J, K) bitonic_step<J>(khi, klo, ix, ((tid & (J)) == 0) == ((tid & (K)) == 0), lane, pick_shl)
-            auto lds_step = [&](int j, int k) {
-              if (act) { xk[2 * tid] = khi; xk[2 * tid + 1] = klo; sv_i[tid] = ix; }
-              __syncthreads();
-              if (act) {
-                const int pt = tid ^ j;
-                const unsigned ohi = xk[2 * pt], olo = xk[2 * pt + 1]; const int oi = sv_i[pt];
-                const bool take = elem_before(ohi, olo, oi, khi, klo, ix) == (((tid & j) == 0) == ((tid & k) == 0));
-                khi = take ? ohi : khi; klo = take ? olo : klo; ix = take ? oi : ix;
-              }
-              __syncthreads();
-            };
-            auto tail = [&](int k) {                           // the in-wave steps j = 32 .. 1 of block size k >= 64
-              if (act) { CTCN_BSTEP(32, k); CTCN_BSTEP(16, k); CTCN_BSTEP(8, k); CTCN_BSTEP(4, k); CTCN_BSTEP(2, k); CTCN_BSTEP(1, k); }
-            };
-            if (act) {
-              CTCN_BSTEP(1, 2);
-              CTCN_BSTEP(2, 4); CTCN_BSTEP(1, 4);
-              CTCN_BSTEP(4, 8); CTCN_BSTEP(2, 8); CTCN_BSTEP(1, 8);
-              CTCN_BSTEP(8, 16); CTCN_BSTEP(4, 16); CTCN_BSTEP(2, 16); CTCN_BSTEP(1, 16);
-              CTCN_BSTEP(16, 32); CTCN_BSTEP(8, 32); CTCN_BSTEP(4, 32); CTCN_BSTEP(2, 32); CTCN_BSTEP(1, 32);
-            }
-            tail(64);
-            lds_step(64, 128); tail(128);
-            lds_step(128, 256); lds_step(64, 256); tail(256);
-#undef CTCN_BSTEP
-            // (lds_step ends with a barrier: the exchange area is free again; the value is read back from the candidate table, which this
-            // path leaves untouched -- bit for bit the double that was scored, where inverting the key would fold -0.0 onto +0.0)
-            if (act && tid < S && tid < W) { sel[tid] = ix; selv[tid] = cand[ix]; }
-          } else {
-          int P = 1, lgP = 0;
-          while (2 * P * S <= NT && P < 16) { P *= 2; ++lgP; }
-          for (int e0 = 0; e0 < S; e0 += NT >> lgP) {
-            const int e = e0 + (tid >> lgP), part = tid & (P - 1);
-            const bool have = e < S;
-            const double mv = sv_v[have ? e : 0]; const int mi = sv_i[have ? e : 0];
-            constexpr int RU = NT >= 1024 ? 4 : 8;
-            int rank = 0, q = part;
-            for (; q + (RU - 1) * P < S; q += RU * P) {
-              double qv[RU]; int qi[RU];
-#pragma unroll
-              for (int u = 0; u < RU; ++u) { qv[u] = sv_v[q + u * P]; qi[u] = sv_i[q + u * P]; }
-#pragma unroll
-              for (int u = 0; u < RU; ++u) rank += cand_better(qv[u], qi[u], mv, mi) ? 1 : 0;
-            }
-            for (; q < S; q += P) rank += cand_better(sv_v[q], sv_i[q], mv, mi) ? 1 : 0;
-            for (int o = 1; o < P; o <<= 1) rank += __shfl_xor(rank, o, 64);
-            if (have && part == 0 && rank < W) { sel[rank] = mi; selv[rank] = mv; }
-          }
-          }
-          m = min(W, total);
-          ranked = true;
-        }
-        __syncthreads();
-        GSTAMP(11);
-      }
-    }
-    // (the rounds reuse red_i[], which every thread has just summed into `total` -- when the ranking block was skipped no barrier
-    // separates those reads from round 0's writes; `ranked` is uniform.  A NaN score counts as "no candidate" everywhere (v > -inf).)
-    if (!ranked) __syncthreads();
-    for (int r = 0; r < W && !ranked; ++r) {
-      double bv = -INFINITY; int bi = 0x7fffffff;
-      for (int c = tid; c < ncand; c += NT) {
-        const double v = cand[c];
-        if (v > -INFINITY && cand_better(v, c, bv, bi)) { bv = v; bi = c; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || cand_better(ov, oi, bv, bi))) { bv = ov; bi = oi; }
-      }
-      if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
-      __syncthreads();
-      if (tid == 0) {
-        double v = red_v[0]; int ix = red_i[0];
-        for (int w = 1; w < NWV; ++w)
-          if (red_i[w] != 0x7fffffff && (ix == 0x7fffffff || cand_better(red_v[w], red_i[w], v, ix))) { v = red_v[w]; ix = red_i[w]; }
-        s_best = ix;
-        if (ix != 0x7fffffff) { sel[r] = ix; selv[r] = v; cand[ix] = -INFINITY; }
-      }
-      __syncthreads();
-      if (s_best == 0x7fffffff) break;
-      ++m;
-    }
+    const int m = select_top_w<NT>(c, ss);
     GSTAMP(4);
-    // 5. materialise the new beam
-    if (tid < m) {
-      const int c = sel[tid];
-      const int i = div_v(c), kk = c - i * V;
-      if (kk == 0) {
-        N.node[tid] = L.node[i]; N.len[tid] = L.len[i]; N.last[tid] = L.last[i]; N.par[tid] = L.par[i];
-        N.pNB[tid] = sNB[i]; N.pB[tid] = sB[i]; N.pT[tid] = sT[i];
-      } else {
-        const int k = (kk - 1 < blank) ? kk - 1 : kk;
-        int ip = -1;
-        {
-          const int ow = cown[c];
-          if ((unsigned)ow < (unsigned)nb && mfrom[ow] == i && L.last[ow] == k) ip = ow;
-        }
-        if (ip >= 0) {   // this slot holds the merged entry of existing labelling ip (first touched as an extension)
-          N.node[tid] = L.node[ip]; N.len[tid] = L.len[ip]; N.last[tid] = L.last[ip]; N.par[tid] = L.par[ip];
-          N.pNB[tid] = sNB[ip]; N.pB[tid] = sB[ip]; N.pT[tid] = sT[ip];
-        } else {
-          // trie child lookup / insert: key = (parent node, symbol)
-          const int parent = L.node[i];
-          const unsigned long long key = ((unsigned long long)(unsigned)parent << 32) | (unsigned)k;
-          unsigned h = (unsigned)mix64(key) & htmask;
-          int id = -1;
-          for (int probe = 0; probe <= htmask; ++probe) {
-            const unsigned long long prev = atomicCAS(&keys[h], HT_EMPTY, key);
-            if (prev == HT_EMPTY) {
-              id = atomicAdd(&s_nodes, 1);
-              if (id < a.max_nodes) { npar[id] = parent; nsym[id] = k; }
-              ids[h] = id;
-              break;
-            }
-            if (prev == key) { id = ids[h]; break; }
-            h = (h + 1) & htmask;
-          }
-          N.node[tid] = id; N.len[tid] = L.len[i] + 1; N.last[tid] = k; N.par[tid] = parent;
-          const double pr = selv[tid];
-          N.pNB[tid] = pr; N.pB[tid] = LOG_ZERO; N.pT[tid] = pr;
-        }
-      }
-      const int nd = N.node[tid];
-      if ((unsigned)nd < (unsigned)a.max_nodes) nslot[nd] = tid;     // (step 2 of the next frame finds a parent labelling's slot here)
-    }
+    materialise(c, m, &s_nodes);
     __syncthreads();
     GSTAMP(5);
-    nb = m;
+    c.nb = m;
     cur ^= 1;
   }
   __syncthreads();
 #ifdef CTCN_BEAM_STATS
-  if (a.stats && b == 0 && tid == 0) { for (int i = 0; i < 16; ++i) a.stats[32 + i] = gst[i]; a.stats[48] = gframes; }
+  if (a.stats && b == 0 && tid == 0) { for (int i = 0; i < 16; ++i) a.stats[32 + i] = c.gst[i]; a.stats[48] = gframes; }
 #endif
-  // final LM step, length normalisation and best labelling (BeamSearch.py:130-151)
-  const BeamState L = beam_state(cur);
-  if (status == 0 && tid == 0) {
-    int st = 0;
-    for (int r = 0; r < nb; ++r) if (L.len[r] == 0) st = 1;          // classes[y[-1]] on () -> IndexError
-    if (s_nodes > a.max_nodes) st = 3;
-    const int NB = a.nbest;
-    if (st == 0) {
-      // normalised scores (BeamSearch.py:147: prTotal / labelling length), then `last.sort()[0:nbest]` (:150, the reference keeps [0]): a stable
-      // descending sort -- among equal scores the earlier entry (the order of BHat) comes first.  L.pT is reused for the scores, L.par as "taken"
-      for (int r = 0; r < nb; ++r) {
-        const double pr = L.pT[r] + lm_scaled(lmt[(size_t)L.last[r] * (V + 1) + V], a.alpha);
-        const double tot = log_add_prob(LOG_ZERO, pr);
-        const int ln = L.len[r];
-        L.pT[r] = tot * (1.0 / (ln ? ln : 1));
-        L.par[r] = 0;
-      }
-      const int nout = min(NB, nb);
-      for (int k = 0; k < nout; ++k) {
-        int best = -1; double bestv = 0.0;
-        for (int r = 0; r < nb; ++r)
-          if (!L.par[r] && (best < 0 || L.pT[r] > bestv)) { best = r; bestv = L.pT[r]; }
-        L.par[best] = 1;
-        const int ln = L.len[best];
-        const size_t o = (size_t)b * NB + k;
-        a.out_len[o] = ln; a.out_score[o] = bestv;
-        int n = L.node[best];
-        for (int i = ln - 1; i >= 0; --i) { a.out_ids[o * T + i] = nsym[n]; n = npar[n]; }
-      }
-      for (int k = nout; k < NB; ++k) { a.out_len[(size_t)b * NB + k] = 0; a.out_score[(size_t)b * NB + k] = 0.0; }
-      if (a.out_count) a.out_count[b] = nout;
-    } else {
-      for (int k = 0; k < NB; ++k) { a.out_len[(size_t)b * NB + k] = 0; a.out_score[(size_t)b * NB + k] = 0.0; }
-      if (a.out_count) a.out_count[b] = 0;
-    }
-    a.status[b] = st;
-  } else if (tid == 0) {
-    for (int k = 0; k < a.nbest; ++k) { a.out_len[(size_t)b * a.nbest + k] = 0; a.out_score[(size_t)b * a.nbest + k] = 0.0; }
-    if (a.out_count) a.out_count[b] = 0;
-    a.status[b] = status;
-  }
+  const BeamState L = c.state(cur);
+  beam_finish(a, b, status, s_nodes > a.max_nodes, c.nb, L.len, L.last, L.node, L.pT, L.par, c.lm,
+              [&](int &n) { const int sym = c.nsym[n]; n = c.npar[n]; return sym; });
 }
 
-
 // =====================================================================================================================
-// Fast path (W <= 60, W*V <= 3328, V <= 256): the same search, restructured around the per-frame latency chain.
-// The generic kernel above spends ~39 us per processed frame (cfg5): W block-wide arg-max rounds (two __syncthreads + a
-// serial 4-way compare each), the double-precision log of the frame, LM gathers from global memory, trie CAS round trips
-// to L2 (~1.9 us each), and -- everywhere -- chains of dependent LDS reads (~100 cycles per hop).  Here:
+// Fast path (W <= 60, W*V <= 3328, V <= 256): the same search, restructured around the per-frame latency chain -- the
+// double-precision log of the frame, LM gathers from global memory, trie CAS round trips to L2 (~1.9 us each) and chains
+// of dependent LDS reads (~100 cycles per hop) of the generic kernel.  Here:
 //   * beam_prep_kernel (fully parallel, one wave per (frame, utterance) row) takes everything that does not depend on the
 //     beam state out of the chain: ln p as double for every class, p(blank), the "some p is not > 0" flag;
 //   * the workgroup compacts its list of processed frames once (the skip rule 1 - p_blank < 0.1 needs no beam state), keeps
@@ -691,15 +792,22 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
 //   * trie: a 16K-slot table IN LDS (node id = slot + 1, entry = {parent id + 1 : 15 | symbol : 17}, double hashing, one ds_cmpst
 //     per probe); only when it fills beyond 3/4 do new labellings go to the global-memory table of the generic kernel (64-bit
 //     entries {parent : 24 | symbol : 16 | id : 24});
-//   * round 4: the per-frame serial chain is split over three waves.  Wave 1 owns the trie (a node id is needed a frame later, as
+//   * the per-frame serial chain is split over three waves.  Wave 1 owns the trie (a node id is needed a frame later, as
 //     the parent id of the labelling's children); wave 0 recognises "this slot's parent labelling was created in this frame" from
 //     (grandparent id, parent's last class) keys, which need old ids only.  Wave 2 computes the first level of the stay entries'
 //     log-adds (it needs no parent slot) next to wave 0's new-beam work; wave 0 publishes the beam record through an LDS flag, not a
-//     barrier.  cfg5 batch 1 300 -> 1 098 us (peaky), 3 949 -> 2 796 us (flat), labellings and scores bit-equal to the round-3 kernel.
+//     barrier.
 // Every score is computed by the same expressions on the same operands as in beam_kernel: bit-identical results.  (Against the
 // C oracle: identical labellings; float64 scores bit-equal on the golden sets and within 2 ulp elsewhere -- ocml's exp / log vs glibc's.)
 // =====================================================================================================================
 constexpr int FAST_WMAX = 64;
+// a word of the frame list: the frame's number | the repeat rule holds on it (p_blank of the previous frame < 0.9) | one of its p is not > 0
+constexpr int FW_ZERO = 1 << 29, FW_REP = 1 << 30, FW_FRAME = FW_ZERO - 1;
+// An extension candidate whose labelling is already a beam slot's: mslot[candidate] = {frame tag << MS_TAG_SHIFT | MS_HOLDS |
+// slot}.  MS_HOLDS: the candidate holds the slot's merged entry (clear: the entry lives in the slot's stay candidate and this one is
+// removed).  selm[] and Survivor::pad carry the low byte, MS_HOLDS | slot, or 0; selm[] = -1 sends decode_sel to mslot[].  TOTS_MASK: a
+// survivor's position in tots[].  (Constants only: accessor functions, or cand_class / class_col, in beam_fast_body cost it up to 1.5 %.)
+constexpr int MS_HOLDS = 128, MS_SLOT = 63, MS_TAG_SHIFT = 8, TOTS_MASK = 63;
 
 struct FastArgs {
   const double *lgd; const float *pb; const unsigned char *zf;
@@ -735,44 +843,6 @@ __global__ __launch_bounds__(256) void beam_prep_kernel(const float *__restrict_
   if (lane == 0) zf[row] = any_bad ? 1 : 0;
 }
 
-// order-preserving map double -> uint64 (total order of the IEEE values; -0.0 / NaN do not occur among the scores)
-__device__ __forceinline__ unsigned long long f64_key(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_f64(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_umax_step(unsigned v) {
-  const unsigned s = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
-  return max(v, s);
-}
-// max over the 64 lanes on the DPP network: row_shr 1/2/4/8 leave each row's maximum in its lane 15, row_bcast15 / row_bcast31
-// carry it across the rows; lane 63 holds the result (max is idempotent: lanes without a source keep their own value)
-__device__ __forceinline__ unsigned wave_umax(unsigned v) {
-  v = dpp_umax_step<0x111, 0xf>(v);   // row_shr:1
-  v = dpp_umax_step<0x112, 0xf>(v);   // row_shr:2
-  v = dpp_umax_step<0x114, 0xf>(v);   // row_shr:4
-  v = dpp_umax_step<0x118, 0xf>(v);   // row_shr:8
-  v = dpp_umax_step<0x142, 0xa>(v);   // row_bcast:15 into rows 1, 3
-  v = dpp_umax_step<0x143, 0xc>(v);   // row_bcast:31 into rows 2, 3
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_umin_step(unsigned v) {
-  const unsigned s = (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xf, false);
-  return min(v, s);
-}
-__device__ __forceinline__ unsigned wave_umin(unsigned v) {
-  v = dpp_umin_step<0x111, 0xf>(v);
-  v = dpp_umin_step<0x112, 0xf>(v);
-  v = dpp_umin_step<0x114, 0xf>(v);
-  v = dpp_umin_step<0x118, 0xf>(v);
-  v = dpp_umin_step<0x142, 0xa>(v);
-  v = dpp_umin_step<0x143, 0xc>(v);
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
 __device__ __forceinline__ int lane_gather(int v, int src_lane) { return __builtin_amdgcn_ds_bpermute(src_lane << 2, v); }
 __device__ __forceinline__ double lane_gather(double v, int src_lane) {
   return __hiloint2double(__builtin_amdgcn_ds_bpermute(src_lane << 2, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(src_lane << 2, __double2loint(v)));
@@ -787,8 +857,7 @@ constexpr int FAST_NTH = 1024, FAST_NWV = FAST_NTH / 64;      // 16 waves: the p
 template <int NPT, bool LM_LDS>
 __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   constexpr int NTH = FAST_NTH, NWV = FAST_NWV;
-  // dynamic LDS: [alpha*LM (V+1)^2 doubles] | cand[W*V] doubles | lg[2][V] doubles (by frame parity) | mslot[W*V] ints | flist[T] ints | trie[slots] uints
-  extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
+  extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];   // FastLdsT
   __shared__ Survivor surv[SURV_MAX];                                 // candidates above the pruning bound (order-preserving key, index)
   __shared__ double red_v[NWV];
   __shared__ int red_i[NWV + 1];
@@ -814,20 +883,20 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x, V = a.V, W = a.W, B = a.B, T = a.T, blank = a.blank;
   const int V1 = V + 1;
-  double *lmA = reinterpret_cast<double *>(fsm);
-  double *cand = lmA + (LM_LDS ? V1 * V1 : 0);
-  double *lg2 = cand + W * V;
-  int *mslot = reinterpret_cast<int *>(lg2 + 2 * V);
-  int *flist = mslot + W * V;
-  unsigned *trie = reinterpret_cast<unsigned *>(flist + T);
   const int TS = a.trie_slots;
+  const FastLdsT<unsigned> lds(T, V, W, LM_LDS, TS);
+  double *lmA = reinterpret_cast<double *>(fsm);
+  double *cand = reinterpret_cast<double *>(fsm + lds.cand);
+  double *lg2 = reinterpret_cast<double *>(fsm + lds.lg2);
+  int *mslot = reinterpret_cast<int *>(fsm + lds.mslot);
+  int *flist = reinterpret_cast<int *>(fsm + lds.flist);
+  unsigned *trie = reinterpret_cast<unsigned *>(fsm + lds.trie);
   const unsigned tmask = (unsigned)TS - 1u;
   const int tshift = 32 - (31 - __builtin_clz((unsigned)TS));      // top log2(TS) bits of a 32-bit hash
   unsigned long long *ht = a.ht + (size_t)b * a.ht_size;
   int *npar = a.node_par + (size_t)b * a.max_nodes;
   int *nsym = a.node_sym + (size_t)b * a.max_nodes;
   const unsigned htmask = (unsigned)a.ht_size - 1u;
-  constexpr int TMASK = (1 << 29) - 1;
 
   if (LM_LDS)
     for (int i = tid; i < V1 * V1; i += NTH) lmA[i] = a.lm[i] * a.alpha;        // rounded by the store: the same product lm_scaled() gives the generic kernel and the global-memory variant per use
@@ -851,7 +920,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
       const float pbl = a.pb[(size_t)t * B + b];
       keep = !((1.0f - pbl) < 0.1f);
       const bool rep = t > 0 && a.pb[(size_t)(t - 1) * B + b] < 0.9f;
-      word = t | (rep ? 1 << 30 : 0) | (a.zf[(size_t)t * B + b] ? 1 << 29 : 0);
+      word = t | (rep ? FW_REP : 0) | (a.zf[(size_t)t * B + b] ? FW_ZERO : 0);
     }
     const unsigned long long mask = __ballot(keep);
     if (lane == 0) woff[wave] = __popcll(mask);
@@ -866,14 +935,12 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   const int nfl = s_nfl;
 
   // Wave 0 owns the beam (lane = slot) and the serial chain, wave 1 the prefix trie (node ids are only needed a frame later), wave 2 the
-  // log-add of every slot's stay entry that needs no parent slot (round 4); waves 3..15 (832 threads) own the candidates.
+  // log-add of every slot's stay entry that needs no parent slot; waves 3..15 (832 threads) own the candidates.
   // That log-add -- exp and log in f64, ~1.8 k cycles of one wave -- is the longest link of the frame.  Wave 2 forms it for every SURVIVOR of
   // the pruning bound (at most 64, one per lane) while the candidate waves still rank them: up to 1 + exp(.) before the barrier that ends the
   // rank count, the logarithm behind it; wave 0 picks the totals of the selected survivors up by their position (selp[] -> tots[]).  With
-  // more than 64 survivors the total is formed behind the decode of the selection as before (totv[]).  (Measured and not kept: a counter
-  // instead of that barrier so that wave 2 need not hold it up -- thirteen LDS atomics and two polling waves cost more than the barrier;
-  // the logarithm's reciprocal / quotient stage before the barrier as well: the barrier is late, +3 %; a logarithm with the parts that are
-  // constant on [1, 2] folded -- bit-equal to the library's on 2^24 values -- behind the barrier: no faster, 912 vs 908 us.)
+  // more than 64 survivors the total is formed behind the decode of the selection (totv[]).  The split point is where it is because the
+  // barrier must not wait for wave 2 (DESIGN_HISTORY.md, "decode.hip: tried and not kept").
   // Every role runs ITS OWN frame loop below (same barriers, in the same order): the kernel sits at its register limit, and with the roles
   // interleaved phase by phase in one loop every role's state was live everywhere -- the allocator spilled loop-invariant addresses to
   // scratch and re-loaded them inside the frame's critical path.  In separate branches the live ranges do not overlap.
@@ -884,7 +951,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   double nlg = 0.0;
   const int lgk = tid - 128;
   auto fetch_lg = [&](int fword) {
-    if (lgk >= 0 && lgk < V) nlg = a.lgd[((size_t)(fword & TMASK) * B + b) * V + lgk];
+    if (lgk >= 0 && lgk < V) nlg = a.lgd[((size_t)(fword & FW_FRAME) * B + b) * V + lgk];
   };
   if (nfl > 0) fetch_lg(flist[0]);
   if (lgk >= 0 && lgk < V) lg2[lgk] = nlg;
@@ -896,50 +963,20 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   int nb = 1, status = 0;
   // the serial chain (wave 0) and its two helpers win the issue arbitration of their SIMDs against the scoring waves they share them with (0.3-0.9 %)
   if (wave == 0) __builtin_amdgcn_s_setprio(3); else if (wave == 2) __builtin_amdgcn_s_setprio(2); else if (wave == 1) __builtin_amdgcn_s_setprio(1);
-  // (round 4, measured on one box against the interleaved build -- cfg5 batch 1 098 us peaky / 2 796 us flat -- and NOT kept: the pruning bound
-  // formed by the scoring waves in the shadow of wave 0's chain, with a barrier of their own or ranked by the last wave to arrive: 1 167-1 230 /
-  // 2 804-2 903 (13 waves x the extra instructions are issue-bound and end up BEHIND wave 0); candidate state packed into one word + opaque
-  // indices so that nothing spills: 1 158 / 2 929 (the unpacking costs the parallel phases more than the scratch re-loads did); the bound ranked
-  // by waves 0..3 only: 1 192 / 2 987.  The parallel phases cost (instructions per wave) x (waves per SIMD) x ~4.5 cycles whatever their
-  // dependences are.  The bound in the scoring phase again ON this role-split build (995 / 2 552): 991 / 2 402, with wave 2 publishing the beam
-  // record early 998 / 2 410, with a second bound from the stay totals 979 / 2 434 -- the scoring waves' own barrier waits for the slowest of
-  // thirteen issue-bound waves, 1.6 k cycles in the very phase the bound was meant to hide in; not kept for 5 % of the flat regime.)
+  // The pruning bound is formed in the selection, behind the scoring phase, not inside it: the parallel phases are issue-bound, and extra
+  // instructions in thirteen waves end up behind wave 0's chain (DESIGN_HISTORY.md, "decode.hip: tried and not kept").
   __syncthreads();
 #ifdef CTCN_BEAM_STATS
   long long zst[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, zlast = clock64(), zrounds = 0, ziters = 0;
   const long long zt0 = zlast;
 #endif
-  // more than SURV_MAX candidates above the bound (never seen on the synthetic regimes): W block-wide arg-max rounds over the candidate
+  // more than SURV_MAX candidates above the bound (exact ties: synth's ties16 at W = 52; never on the benchmark's regimes): W block-wide arg-max rounds over the candidate
   // table (wave 0 patches it first so that it holds this frame's stay / merged entries), exactly as the generic kernel does.  All threads.
-  auto arg_max_rounds = [&]() -> int {
-    const int ncand = nb * V;
-    int got = 0;
-    for (int r = 0; r < W; ++r) {
-      double bv = -INFINITY; int bi = 0x7fffffff;
-      for (int c = tid; c < ncand; c += NTH) {
-        const double v = cand[c];
-        if (v != -INFINITY && cand_better(v, c, bv, bi)) { bv = v; bi = c; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || cand_better(ov, oi, bv, bi))) { bv = ov; bi = oi; }
-      }
-      if (lane == 0) { red_v[wave] = bv; red_i[wave] = bi; }
-      lds_barrier();
-      if (tid == 0) {
-        double v = red_v[0]; int ix = red_i[0];
-        for (int w = 1; w < NWV; ++w)
-          if (red_i[w] != 0x7fffffff && (ix == 0x7fffffff || cand_better(red_v[w], red_i[w], v, ix))) { v = red_v[w]; ix = red_i[w]; }
-        red_i[NWV] = ix;
-        if (ix != 0x7fffffff) { sel[r] = ix; selv[r] = v; selm[r] = -1; cand[ix] = -INFINITY; }
-      }
-      lds_barrier();
-      if (red_i[NWV] == 0x7fffffff) break;
-      ++got;
-    }
-    return got;
+  auto rounds = [&]() -> int {
+#ifdef CTCN_BEAM_STATS
+    ++zrounds;
+#endif
+    return arg_max_rounds<NTH>(cand, nb * V, W, red_v, red_i, sel, selv, wave, [] { lds_barrier(); }, [&](int r) { selm[r] = -1; });
   };
   // waves 0..2: decode of the selection -- new slot `lane` <- candidate sel[lane]: which old slot it comes from, fresh labelling or copy
   struct Dec { bool act, fresh; int src, sym; double sv; };
@@ -955,14 +992,14 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
     // does this candidate hold the merged entry of a slot?  The candidate's thread looked that up when it loaded the value (selm[]: one LDS
     // round trip less on the serial chain); -1: the selection came from the arg-max rounds, mslot[] has it
     int sm = selm[rr];
-    if (sm < 0) { const int ms = mslot[d.act ? c : 0]; sm = (kk != 0 && ms >= 0 && (ms >> 8) == j && (ms & 128)) ? (128 | (ms & 63)) : 0; }
-    const bool merged = d.act && (sm & 128);
+    if (sm < 0) { const int ms = mslot[d.act ? c : 0]; sm = (kk != 0 && ms >= 0 && (ms >> MS_TAG_SHIFT) == j && (ms & MS_HOLDS)) ? (MS_HOLDS | (ms & MS_SLOT)) : 0; }
+    const bool merged = d.act && (sm & MS_HOLDS);
     d.fresh = d.act && kk != 0 && !merged;
-    d.src = merged ? (sm & 63) : i;
+    d.src = merged ? (sm & MS_SLOT) : i;
     return d;
   };
-  const bool first_ok = nfl > 0 && !(flist[0] & (1 << 29));
-  const bool rep0 = nfl > 0 && ((flist[0] >> 30) & 1);
+  const bool first_ok = nfl > 0 && !(flist[0] & FW_ZERO);
+  const bool rep0 = nfl > 0 && (flist[0] & FW_REP) != 0;
 
   if (wave >= 3) {
     // ======================================= waves 3..15: the candidates =======================================================
@@ -1007,7 +1044,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
     if (first_ok) score_extensions(rep0, 0);
     lds_barrier();
     for (int j = 0, fw = nfl > 0 ? flist[0] : 0; j < nfl; ++j) {  // (fw: the frame's word, read one frame ahead)
-      if (fw & (1 << 29)) { status = 2; break; }                   // math.log(0) in the reference: ValueError
+      if (fw & FW_ZERO) { status = 2; break; }                   // math.log(0) in the reference: ValueError
       frame_top(j);
       BSTAMP(0);
       // P3: BHat = top-W by (prTotal desc, candidate index asc), without sorting.
@@ -1016,24 +1053,21 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
       //  2. the survivors (typically W + a few) are compacted into LDS and ranked by counting, the candidate threads sharing the compares.
       unsigned long long key[NPT];
       bool val[NPT];
-      unsigned mhi = 0u, mpack = 0u;                                // mpack: byte i = 128 | slot when candidate i holds that slot's merged entry
+      unsigned mhi = 0u, mpack = 0u;                                // mpack: byte i = MS_HOLDS | slot when candidate i holds that slot's merged entry
 #pragma unroll
       for (int i = 0; i < NPT; ++i) {
         const int bi = min(ci[i], FAST_WMAX - 1);
         double v = ck[i] < 0 ? stayv[bi] : cand[cc[i]];
         const int ms = mslot[cc[i]];
-        if (ck[i] >= 0 && ms >= 0 && (ms >> 8) == j) {
-          v = (ms & 128) ? homev[ms & 63] : -INFINITY;
-          if (ms & 128) mpack |= (unsigned)(128 | (ms & 63)) << (8 * i);
+        if (ck[i] >= 0 && ms >= 0 && (ms >> MS_TAG_SHIFT) == j) {
+          v = (ms & MS_HOLDS) ? homev[ms & MS_SLOT] : -INFINITY;
+          if (ms & MS_HOLDS) mpack |= (unsigned)(MS_HOLDS | (ms & MS_SLOT)) << (8 * i);
         }
         key[i] = f64_key(v);
         val[i] = ci[i] < nb && v != -INFINITY;
         mhi = max(mhi, val[i] ? (unsigned)(key[i] >> 32) : 0u);
       }
-      mhi = dpp_umax_step<0x111, 0xf>(mhi);
-      mhi = dpp_umax_step<0x112, 0xf>(mhi);
-      mhi = dpp_umax_step<0x114, 0xf>(mhi);
-      mhi = dpp_umax_step<0x118, 0xf>(mhi);
+      mhi = row16_umax(mhi);
       if ((lane & 15) == 15) gmax[u >> 4] = mhi;
       BSTAMP(8);
       lds_barrier();
@@ -1048,10 +1082,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
           const unsigned o = gmax[q];
           cnt += (o > mine || (o == mine && q < e)) ? 1 : 0;
         }
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0xB1, 0xf, 0xf, true);     // quad_perm [1,0,3,2]
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x4E, 0xf, 0xf, true);     // quad_perm [2,3,0,1]
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x141, 0xf, 0xf, true);    // row_half_mirror
-        cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x140, 0xf, 0xf, true);    // row_mirror
+        cnt = row16_sum(cnt);
         if (part == 0 && cnt == W - 1) s_theta = mine;                        // (no such row when fewer than W rows hold a candidate: 0)
       }
       lds_barrier();
@@ -1098,10 +1129,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
 #pragma unroll
           for (int q4 = 0; q4 < 4; ++q4)
             cnt += (part + 16 * q4 < S && (oe16[q4].k > me16.k || (oe16[q4].k == me16.k && oe16[q4].idx < me16.idx))) ? 1 : 0;
-          cnt += __builtin_amdgcn_update_dpp(0, cnt, 0xB1, 0xf, 0xf, true);                  // quad_perm [1,0,3,2]
-          cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x4E, 0xf, 0xf, true);                  // quad_perm [2,3,0,1]
-          cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x141, 0xf, 0xf, true);                 // row_half_mirror
-          cnt += __builtin_amdgcn_update_dpp(0, cnt, 0x140, 0xf, 0xf, true);                 // row_mirror
+          cnt = row16_sum(cnt);
           if (e < S && part == 0 && cnt < W) { sel[cnt] = me16.idx; selv[cnt] = key_f64(me16.k); selm[cnt] = me16.pad; selp[cnt] = e; }
         }
       } else if (S <= SURV_MAX) {
@@ -1127,13 +1155,13 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
         }
       } else {
         lds_barrier();                                             // (wave 0 has patched the candidate table)
-        total = arg_max_rounds();
+        total = rounds();
       }
       lds_barrier();
       BSTAMP(4);
       nb = min(W, total);
       const int fwn = flist[min(j + 1, nfl - 1)];
-      const bool more = j + 1 < nfl && !(fwn & (1 << 29));
+      const bool more = j + 1 < nfl && !(fwn & FW_ZERO);
       if (more) {
         // the new beam's record (context class, prBlank, prTotal of every slot) comes from wave 0 through a flag, not a barrier
         for (int spins = 0; __hip_atomic_load(&s_beamflag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != j + 1; ++spins) {
@@ -1141,7 +1169,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
           __builtin_amdgcn_s_sleep(2);
         }
         BSTAMP(6);
-        score_extensions((fwn >> 30) & 1, j + 1);
+        score_extensions((fwn & FW_REP) != 0, j + 1);
         BSTAMP(9);
       }
       fw = fwn;
@@ -1213,17 +1241,14 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
         e_nb = r_nb; e_b = s_b; e_t = r_t;
         homev[ip] = r_t; enbv[ip] = r_nb;
         stayv[ip] = ext_first ? -INFINITY : r_t;
-        if (mi >= 0) {
-          const int kkl = (z_last < blank) ? z_last + 1 : z_last;
-          mslot[mi * V + kkl] = (jf << 8) | (ext_first ? 128 : 0) | ip;
-        }
+        if (mi >= 0) mslot[mi * V + ((z_last < blank) ? z_last + 1 : z_last)] = (jf << MS_TAG_SHIFT) | (ext_first ? MS_HOLDS : 0) | ip;
       }
       if (lane == 0) { s_theta = 0u; s_cnt = 0; }
     };
     if (first_ok) stay_and_merge(rep0, 0, -1);
     lds_barrier();
     for (int j = 0, fw = nfl > 0 ? flist[0] : 0; j < nfl; ++j) {
-      if (fw & (1 << 29)) { status = 2; break; }
+      if (fw & FW_ZERO) { status = 2; break; }
       BSTAMP(0);
       lds_barrier();                                               // (row maxima)
       lds_barrier();                                               // (pruning bound)
@@ -1234,20 +1259,20 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
       if (S > SURV_MAX) {
         if (lane < nb) {
           cand[lane * V] = stayv[lane];
-          if (z_mf >= 0) { const int kkl = (z_last < blank) ? z_last + 1 : z_last; cand[z_mf * V + kkl] = (z_mf < lane) ? homev[lane] : -INFINITY; }
+          if (z_mf >= 0) cand[z_mf * V + ((z_last < blank) ? z_last + 1 : z_last)] = (z_mf < lane) ? homev[lane] : -INFINITY;
         }
         lds_barrier();
-        total = arg_max_rounds();
+        total = rounds();
       }
       lds_barrier();                                               // (selection ranked)
       BSTAMP(4);
       const int m = min(W, total);
       const int fwn = flist[min(j + 1, nfl - 1)];
-      const bool more = j + 1 < nfl && !(fwn & (1 << 29));
-      const bool rep_next = (fwn >> 30) & 1;
+      const bool more = j + 1 < nfl && !(fwn & FW_ZERO);
+      const bool rep_next = (fwn & FW_REP) != 0;
       // P4a: the new beam in rank order; the record the next frame's extension scores need goes out through s_beamflag (wave 0 does not stop)
       const Dec d = decode_sel(j, m);
-      const int tsrc = (more && S <= 64) ? (selp[min(lane, FAST_WMAX - 1)] & 63) : -1;   // where wave 2 leaves this slot's stay total (tots[]; -1: totv[])
+      const int tsrc = (more && S <= 64) ? (selp[min(lane, FAST_WMAX - 1)] & TOTS_MASK) : -1;   // where wave 2 leaves this slot's stay total (tots[]; -1: totv[])
       const bool act = d.act, fresh = d.fresh;
       const int src = d.src, sym = d.sym;
       ns[lane] = -1;
@@ -1323,7 +1348,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
     if (first_ok && wave == 2) stay_totals(0, lane == 0, V, LOG_ZERO, 0.0);       // the empty labelling
     lds_barrier();
     for (int j = 0, fw = nfl > 0 ? flist[0] : 0; j < nfl; ++j) {
-      if (fw & (1 << 29)) { status = 2; break; }
+      if (fw & FW_ZERO) { status = 2; break; }
       frame_top(j);
       BSTAMP(0);
       lds_barrier();
@@ -1332,7 +1357,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
       const int S = s_cnt;
       int total = S;
       const int fwn = flist[min(j + 1, nfl - 1)];
-      const bool more = j + 1 < nfl && !(fwn & (1 << 29));
+      const bool more = j + 1 < nfl && !(fwn & FW_ZERO);
       // wave 2, while the candidate waves rank the survivors: the next frame's stay total of EVERY survivor (at most 64: one per lane), from
       // what its new slot would carry -- a fresh labelling its candidate's score, a copy the stay / merged entry of the slot it comes from --
       // so that the log-add is over when wave 0 asks for it, instead of starting behind the decode of the selection
@@ -1346,9 +1371,9 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
         const int i = (int)(((float)c + 0.5f) * (1.0f / (float)V));
         const int kk = c - i * V;
         const int sym = (kk - 1 < blank) ? kk - 1 : kk;
-        const bool merged = on && (sv.pad & 128);
+        const bool merged = on && (sv.pad & MS_HOLDS);
         const bool fresh = on && kk != 0 && !merged;
-        const int src = merged ? (sv.pad & 63) : i;
+        const int src = merged ? (sv.pad & MS_SLOT) : i;
         const double v = key_f64(sv.k);
         const int o_c1 = bm_c1[j & 1][src];
         const double o_nb = enbv[src], o_t = homev[src];
@@ -1370,7 +1395,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
         }
         tots[lane] = sp_s;
       }
-      if (S > SURV_MAX) { lds_barrier(); total = arg_max_rounds(); }
+      if (S > SURV_MAX) { lds_barrier(); total = rounds(); }
       lds_barrier();
       BSTAMP(4);
       const int m = min(W, total);
@@ -1455,146 +1480,130 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   if (wave == 0) f_node[lane] = nid[nfl & 1][lane];
   __syncthreads();
   if (status == 0 && s_fault) status = 4;
-  // final LM step, length normalisation and best labelling (BeamSearch.py:130-151)
-  if (status == 0 && tid == 0) {
-    int st = 0;
-    for (int r = 0; r < nb; ++r) if (f_len[r] == 0) st = 1;          // classes[y[-1]] on () -> IndexError
-    if (s_gnodes > a.max_nodes) st = 3;
-    const int NB = a.nbest;
-    if (st == 0) {
-      // as in beam_kernel: normalised scores, then the first `nbest` of a stable descending sort (f_pT is reused for the scores, f_last as "taken")
-      for (int r = 0; r < nb; ++r) {
-        const double pr = f_pT[r] + lm_scaled(a.lm[(size_t)f_last[r] * V1 + V], a.alpha);
-        const double tot = pr;                      // == log_add_prob(LOG_ZERO, pr): its first test returns the second argument (BeamSearch.py:44-45)
-        const int ln = f_len[r];
-        f_pT[r] = tot * (1.0 / (ln ? ln : 1));
-        f_last[r] = 0;
-      }
-      const int nout = min(NB, nb);
-      for (int k = 0; k < nout; ++k) {
-        int best = -1; double bestv = 0.0;
-        for (int r = 0; r < nb; ++r)
-          if (!f_last[r] && (best < 0 || f_pT[r] > bestv)) { best = r; bestv = f_pT[r]; }
-        f_last[best] = 1;
-        const int ln = f_len[best];
-        const size_t o = (size_t)b * NB + k;
-        a.out_len[o] = ln; a.out_score[o] = bestv;
-        int n = f_node[best];
-        for (int i = ln - 1; i >= 0; --i) {
-          if (n <= TS) { const unsigned e = trie[n - 1]; a.out_ids[o * T + i] = (int)(e & 0x1FFFFu); n = (int)(e >> 17) - 1; }
-          else { const int gq = n - TS - 1; a.out_ids[o * T + i] = nsym[gq]; n = npar[gq]; }
-        }
-      }
-      for (int k = nout; k < NB; ++k) { a.out_len[(size_t)b * NB + k] = 0; a.out_score[(size_t)b * NB + k] = 0.0; }
-      if (a.out_count) a.out_count[b] = nout;
-    } else {
-      for (int k = 0; k < NB; ++k) { a.out_len[(size_t)b * NB + k] = 0; a.out_score[(size_t)b * NB + k] = 0.0; }
-      if (a.out_count) a.out_count[b] = 0;
-    }
-    a.status[b] = st;
-  } else if (tid == 0) {
-    for (int k = 0; k < a.nbest; ++k) { a.out_len[(size_t)b * a.nbest + k] = 0; a.out_score[(size_t)b * a.nbest + k] = 0.0; }
-    if (a.out_count) a.out_count[b] = 0;
-    a.status[b] = status;
-  }
+  // (f_pT is reused for the scores and f_last for the picks; a node is an LDS trie slot up to TS, an entry of the global table beyond)
+  beam_finish(a, b, status, s_gnodes > a.max_nodes, nb, f_len, f_last, f_node, f_pT, f_last, a.lm, [&](int &n) {
+    if (n <= TS) { const unsigned e = trie[n - 1]; n = (int)(e >> 17) - 1; return (int)(e & 0x1FFFFu); }
+    const int gq = n - TS - 1;
+    n = npar[gq];
+    return nsym[gq];
+  });
 }
 
 // the two launch forms of the fast search.  beam_fast_kernel: one workgroup per CU (120 VGPRs, up to 144 KB of dynamic LDS: the 16 K-slot
-// trie).  beam_fast_kernel_occ2 (round 5, option "beam_occ2"): the same body compiled for eight waves per SIMD (<= 64 VGPRs) and launched
-// with <= 68 KB of dynamic LDS, so that TWO utterances share a CU and each one's serial chain runs in the other's shadow -- the body is
-// latency-bound (wave 0's ~2 k-cycle chain per frame), so the second workgroup costs the first little as long as more than one workgroup per
-// CU is in flight (three 128-utterance batches on three streams: 384 workgroups on 256 CUs).
+// trie).  beam_fast_kernel_occ2 (option "beam_occ2"): the same body compiled for eight waves per SIMD (<= 64 VGPRs) and launched with <= 68 KB
+// of dynamic LDS, so that TWO utterances share a CU and each one's latency-bound serial chain runs in the other's shadow.
 template <int NPT, bool LM_LDS>
 __global__ __launch_bounds__(FAST_NTH) void beam_fast_kernel(FastArgs a) { beam_fast_body<NPT, LM_LDS>(a); }
 template <int NPT, bool LM_LDS>
 __global__ __launch_bounds__(FAST_NTH) __attribute__((amdgpu_waves_per_eu(8, 8))) void beam_fast_kernel_occ2(FastArgs a) { beam_fast_body<NPT, LM_LDS>(a); }
 
-struct BeamLayout { size_t keys, ids, npar, nsym, cand, nslot, cown, total; int ht_size, max_nodes; };
-BeamLayout beam_layout(int T, int B, int V, int W) {
-  BeamLayout l;
-  l.max_nodes = W * T + 2;
-  int ht = 1024;
-  while (ht < 2 * l.max_nodes) ht <<= 1;
-  l.ht_size = ht;
+// ---- Host side: plan_beam decides a call by arithmetic alone (ctcn_diag_beam_plan shows it to the CPU tests); the entry is check, plan, fill, launch ----
+struct BeamOptions { int fast, occ2, generic_threads, cand_global; };
+BeamOptions beam_options() {
+  return {ctcn_get_option("beam_fast"), ctcn_get_option("beam_occ2"), ctcn_get_option("beam_generic_threads"), ctcn_get_option("beam_cand_global")};
+}
+enum BeamPath { BP_FAST = 0, BP_FAST_OCC2 = 1, BP_GENERIC = 2 };
+// workspace, generic: [hash keys | hash ids | node parents | node symbols | candidate table | node_slot | cand_owner]
+//            fast:    [hash table | node parents | node symbols | ln p (T,B,V) double | p_blank (T,B) | log(0) flags (T,B)]
+struct BeamWorkspace { size_t ht, ids, npar, nsym, cand, nslot, cown, lgd, pb, zf, total; };
+struct BeamPlan {
+  BeamPath path;
+  int max_nodes, ht_size;                                  // trie nodes per utterance, slots of its global hash table
+  int fast_ok, npt, lm_lds, trie_slots; size_t fast_lds;   // the fast kernel's fit and dynamic LDS, whichever path is taken
+  int threads, wcap, smax, cand_in_lds, lm_in_lds;         // the generic kernel
+  size_t generic_lds; int generic_fits;                    // its dynamic LDS; with its static LDS within lds_max
+  BeamWorkspace fast_ws, generic_ws;                       // (ctcn_beam_ws_bytes promises the larger, whatever the options are at decode time)
+  size_t lds() const { return path == BP_GENERIC ? generic_lds : fast_lds; }
+  const BeamWorkspace &ws() const { return path == BP_GENERIC ? generic_ws : fast_ws; }
+};
+// (path, threads and the workspaces depend on neither lds_max nor generic_static_lds: the entry plans without them, then asks the device)
+BeamPlan plan_beam(int T, int B, int V, int W, const BeamOptions &o, int lds_max, int generic_static_lds) {
+  BeamPlan p = {};
+  p.max_nodes = W * T + 2;
+  p.ht_size = 1024;
+  while (p.ht_size < 2 * p.max_nodes) p.ht_size <<= 1;
+  // Fast kernel: of the CU's 160 KB (it also has ~12 KB of static LDS) one workgroup gets 144 KB; occ2: two workgroups per CU, 68 KB each.
+  // The LDS trie takes as many slots as fit, at most 16 K (its node ids must fit 14 bits); then the LM if it still fits (occ2 == 2: the LM
+  // stays in global memory and the trie gets its share).
+  typedef FastLdsT<size_t> Lds;
+  p.npt = ceil_div(W * V, FAST_NCT);                       // candidate slots per thread of waves 3..15 (1..4: W * V <= 3 328)
+  if (p.npt > 4) p.npt = 0;
+  const size_t core = Lds(T, V, W, false, 0).total, lm = Lds::table_bytes(V), budget = o.occ2 ? 68 * 1024 : 144 * 1024;
+  const bool want_lm = lm <= 40 * 1024 && o.occ2 != 2;
+  p.trie_slots = 16384;
+  while (p.trie_slots > 1024 && core + (size_t)p.trie_slots * 4 + (want_lm ? lm : 0) > budget) p.trie_slots >>= 1;
+  p.lm_lds = o.occ2 != 2 && core + (size_t)p.trie_slots * 4 + lm <= budget;
+  p.fast_lds = Lds(T, V, W, p.lm_lds, p.trie_slots).total;
+  p.fast_ok = W <= 60 && p.npt > 0 && V <= 256 && p.max_nodes < (1 << 24) && T < (1 << 22) && p.fast_lds <= budget;
+  p.path = (p.fast_ok && o.fast != 0) ? (o.occ2 ? BP_FAST_OCC2 : BP_FAST) : BP_GENERIC;
+  // Generic kernel: threads by beam width and candidates per frame, or forced (option beam_generic_threads, for measurements) and then raised
+  // to the smallest instantiation >= W -- every beam slot has a thread of its own, so the option never changes a result.  Its dynamic LDS
+  // holds what the device's LDS per workgroup leaves room for: the candidate table first (in the workspace otherwise), then the LM table.
+  const int need = o.generic_threads == 0 ? ((W > 64 || (long)W * V > 3500) ? 1024 : 256) : std::max(o.generic_threads, W);
+  p.threads = need > 512 ? 1024 : need > 256 ? 512 : 256;
+  p.wcap = (W + 63) / 64 * 64;
+  p.smax = std::max(1024, 2 * p.wcap);
+  const size_t cand_bytes = (size_t)W * V * sizeof(double);
+  const size_t fixed = (size_t)generic_static_lds + GenericLds(V, W, p.wcap, p.smax, false, false).total + 256;
+  p.cand_in_lds = fixed + cand_bytes <= (size_t)lds_max && !o.cand_global;
+  p.lm_in_lds = fixed + (p.cand_in_lds ? cand_bytes : 0) + GenericLds::table_bytes(V) <= (size_t)lds_max;
+  p.generic_lds = GenericLds(V, W, p.wcap, p.smax, p.cand_in_lds, p.lm_in_lds).total;
+  p.generic_fits = (size_t)generic_static_lds + p.generic_lds <= (size_t)lds_max;
+  // workspaces
+  const size_t nodes = (size_t)B * p.max_nodes * sizeof(int), slots = (size_t)B * p.ht_size, tb = (size_t)T * B, wv = (size_t)B * W * V;
   size_t off = 0;
-  l.keys = off; off += align_up((size_t)B * ht * sizeof(unsigned long long), 256);
-  l.ids = off;  off += align_up((size_t)B * ht * sizeof(int), 256);
-  l.npar = off; off += align_up((size_t)B * l.max_nodes * sizeof(int), 256);
-  l.nsym = off; off += align_up((size_t)B * l.max_nodes * sizeof(int), 256);
-  l.cand = off; off += align_up((size_t)B * W * V * sizeof(double), 256);
-  l.nslot = off; off += align_up((size_t)B * l.max_nodes * sizeof(int), 256);
-  l.cown = off; off += align_up((size_t)B * W * V * sizeof(int), 256);
-  l.total = off;
-  return l;
+  auto take = [&](size_t bytes) { const size_t at = off; off += align_up(bytes, 256); return at; };
+  BeamWorkspace &f = p.fast_ws, &g = p.generic_ws;
+  f.ht = take(slots * 8); f.npar = take(nodes); f.nsym = take(nodes); f.lgd = take(tb * V * sizeof(double)); f.pb = take(tb * sizeof(float));
+  f.zf = take(tb); f.total = off;
+  off = 0;
+  g.ht = take(slots * 8); g.ids = take(slots * sizeof(int)); g.npar = take(nodes); g.nsym = take(nodes); g.cand = take(wv * sizeof(double));
+  g.nslot = take(nodes); g.cown = take(wv * sizeof(int)); g.total = off;
+  return p;
+}
+int lds_refused(const BeamPlan &p, int lds_max, int static_lds) {      // the generic kernel is taken and does not fit the device
+  if (p.path != BP_GENERIC || p.generic_fits) return CTCN_OK;
+  ctcn_set_error("ctcn_beam_decode: %zu B of LDS per workgroup needed, the device gives %d", (size_t)static_lds + p.generic_lds, lds_max);
+  return CTCN_EUNSUPPORTED;
 }
 
-// fast path: [hash table | node parents | node symbols | ln p (T,B,V) double | p_blank (T,B) | log(0) flags (T,B)]
-struct FastLayout { size_t ht, npar, nsym, lgd, pb, zf, total; int ht_size, max_nodes, npt, trie_slots; bool ok, lm_lds; size_t lds; };
-FastLayout fast_layout(int T, int B, int V, int W, int occ2 = 0) {
-  FastLayout l = {};
-  l.max_nodes = W * T + 2;
-  int ht = 1024;
-  while (ht < 2 * l.max_nodes) ht <<= 1;
-  l.ht_size = ht;
-  size_t off = 0;
-  l.ht = off;   off += align_up((size_t)B * ht * sizeof(unsigned long long), 256);
-  l.npar = off; off += align_up((size_t)B * l.max_nodes * sizeof(int), 256);
-  l.nsym = off; off += align_up((size_t)B * l.max_nodes * sizeof(int), 256);
-  l.lgd = off;  off += align_up((size_t)T * B * V * sizeof(double), 256);
-  l.pb = off;   off += align_up((size_t)T * B * sizeof(float), 256);
-  l.zf = off;   off += align_up((size_t)T * B, 256);
-  l.total = off;
-  l.npt = ceil_div(W * V, FAST_NCT);                     // candidate slots per thread of waves 3..15 (1..4: W * V <= 3 328)
-  if (l.npt > 4) l.npt = 0;
-  const size_t core = ((size_t)W * V + 2 * V) * sizeof(double) + ((size_t)W * V + T) * sizeof(int);   // cand, lg[2] | mslot, flist
-  const size_t lm = (size_t)(V + 1) * (V + 1) * sizeof(double);
-  // of the CU's 160 KB (the kernel also has ~12 KB of static LDS); occ2: two workgroups per CU, 80 KB each
-  const size_t budget = occ2 ? 68 * 1024 : 144 * 1024;
-  // LDS trie: as many slots as fit, at most 16 K (node ids of the LDS table must fit 14 bits); then the LM if it still fits
-  // (occ2 == 2: the LM stays in global memory -- L1 / L2 gathers in the parallel scoring phase -- and the trie gets its share)
-  const bool want_lm = lm <= 40 * 1024 && occ2 != 2;
-  l.trie_slots = 16384;
-  while (l.trie_slots > 1024 && core + (size_t)l.trie_slots * 4 + (want_lm ? lm : 0) > budget) l.trie_slots >>= 1;
-  l.lm_lds = occ2 != 2 && core + (size_t)l.trie_slots * 4 + lm <= budget;
-  l.lds = core + (size_t)l.trie_slots * 4 + (l.lm_lds ? lm : 0);
-  l.ok = W <= 60 && l.npt > 0 && V <= 256 && l.max_nodes < (1 << 24) && T < (1 << 22) && l.lds <= budget;
-  return l;
-}
-
+// instantiations: fast [occ2][lm_lds][npt - 1], generic by thread count; one launch site
+#define CTCN_NPT_ROW(K, LM) {K<1, LM>, K<2, LM>, K<3, LM>, K<4, LM>}
+void (*const fast_kernels[2][2][4])(FastArgs) = {{CTCN_NPT_ROW(beam_fast_kernel, false), CTCN_NPT_ROW(beam_fast_kernel, true)},
+                                                 {CTCN_NPT_ROW(beam_fast_kernel_occ2, false), CTCN_NPT_ROW(beam_fast_kernel_occ2, true)}};
+#undef CTCN_NPT_ROW
+void (*const generic_kernels[3])(BeamArgs) = {beam_kernel<256>, beam_kernel<512>, beam_kernel<1024>};      // [threads / 512]
 #ifdef CTCN_BEAM_STATS
 long long *g_beam_stats_dev = nullptr;
 #endif
-template <int NPT>
-int launch_fast(const FastLayout &l, const FastArgs &a, hipStream_t st, int occ2) {
-  if (occ2) {
-    if (l.lm_lds) {
-      auto kern = beam_fast_kernel_occ2<NPT, true>;
-      CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
-      hipLaunchKernelGGL(kern, dim3(a.B), dim3(FAST_NTH), l.lds, st, a);
-    } else {
-      auto kern = beam_fast_kernel_occ2<NPT, false>;
-      CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
-      hipLaunchKernelGGL(kern, dim3(a.B), dim3(FAST_NTH), l.lds, st, a);
-    }
-    return CTCN_OK;
-  }
-  if (l.lm_lds) {
-    auto kern = beam_fast_kernel<NPT, true>;
-    CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(FAST_NTH), l.lds, st, a);
-  } else {
-    auto kern = beam_fast_kernel<NPT, false>;
-    CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
-    hipLaunchKernelGGL(kern, dim3(a.B), dim3(FAST_NTH), l.lds, st, a);
-  }
+template <typename Args>
+int launch_beam(void (*kern)(Args), int B, int threads, size_t lds, hipStream_t st, Args &a) {
+#ifdef CTCN_BEAM_STATS
+  if (!g_beam_stats_dev) { CTCN_HIP(hipMalloc(&g_beam_stats_dev, 64 * sizeof(long long))); }
+  CTCN_HIP(hipMemsetAsync(g_beam_stats_dev, 0, 64 * sizeof(long long), st));
+  a.stats = g_beam_stats_dev;
+#endif
+  CTCN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3(B), dim3(threads), lds, st, a);
+  CTCN_LAUNCH_CHECK();
   return CTCN_OK;
 }
-
 }  // namespace
 
 extern "C" size_t ctcn_beam_ws_bytes(int T, int B, int V, int W) {
   if (T <= 0 || B <= 0 || V <= 0 || W <= 0) return 0;
-  return std::max(beam_layout(T, B, V, W).total, fast_layout(T, B, V, W).total);
+  const BeamPlan p = plan_beam(T, B, V, W, beam_options(), 0, 0);
+  return std::max(p.generic_ws.total, p.fast_ws.total);
+}
+extern "C" int ctcn_diag_beam_plan(int T, int B, int V, int W, int lds_max, int generic_static_lds, int *out) {
+  CTCN_REQUIRE(out && T > 0 && B > 0 && V > 1 && W >= 1 && W <= BEAM_WMAX && lds_max > 0 && generic_static_lds >= 0, "ctcn_diag_beam_plan: bad args");
+  const BeamPlan p = plan_beam(T, B, V, W, beam_options(), lds_max, generic_static_lds);
+  const size_t wf = p.fast_ws.total, wg = p.generic_ws.total;
+  const int v[CTCN_BEAM_PLAN_INTS] = {(int)p.path, p.fast_ok, p.npt, p.lm_lds, p.trie_slots, (int)std::min(p.fast_lds, (size_t)INT32_MAX), p.threads, p.wcap,
+                                      p.smax, p.cand_in_lds, p.lm_in_lds, (int)std::min(p.generic_lds, (size_t)INT32_MAX), p.generic_fits, p.max_nodes,
+                                      p.ht_size, (int)(wf & 0x7fffffff), (int)(wf >> 31), (int)(wg & 0x7fffffff), (int)(wg >> 31)};
+  memcpy(out, v, sizeof(v));
+  return lds_refused(p, lds_max, generic_static_lds);
 }
 
 extern "C" int ctcn_beam_decode_nbest(const float *x, int input_is_prob, const int32_t *lens, const double *lm, double alpha, int W,
@@ -1606,93 +1615,45 @@ extern "C" int ctcn_beam_decode_nbest(const float *x, int input_is_prob, const i
   CTCN_REQUIRE(nbest >= 1 && nbest <= W, "ctcn_beam_decode_nbest: nbest %d outside [1, beam width %d]", nbest, W);
   hipStream_t st = (hipStream_t)stream;
   char *base = (char *)ws;
-  const int occ2 = ctcn_get_option("beam_occ2");
-  const FastLayout fl = fast_layout(T, B, V, W, occ2);
-  if (fl.ok && ctcn_get_option("beam_fast") != 0) {
-    if (ws_bytes < fl.total) { ctcn_set_error("ctcn_beam_decode: workspace too small (%zu < %zu)", ws_bytes, fl.total); return CTCN_EWORKSPACE; }
-    CTCN_HIP(hipMemsetAsync(base + fl.ht, 0xFF, (size_t)B * fl.ht_size * sizeof(unsigned long long), st));
-    FastArgs a;
-    a.lgd = (const double *)(base + fl.lgd); a.pb = (const float *)(base + fl.pb); a.zf = (const unsigned char *)(base + fl.zf);
+  const BeamOptions o = beam_options();
+  BeamPlan p = plan_beam(T, B, V, W, o, 0, 0);
+  int lds_max = 64 * 1024, static_lds = 0;
+  if (p.path == BP_GENERIC) {      // its LDS placement needs two facts of the device: what one workgroup gets, what the instantiation takes statically
+    hipFuncAttributes fa;
+    CTCN_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(generic_kernels[p.threads / 512])));
+    int dev_id = 0;
+    CTCN_HIP(hipGetDevice(&dev_id));
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id) != hipSuccess) lds_max = 64 * 1024;
+    static_lds = (int)fa.sharedSizeBytes;
+    p = plan_beam(T, B, V, W, o, lds_max, static_lds);
+  }
+  const BeamWorkspace &w = p.ws();
+  if (ws_bytes < w.total) { ctcn_set_error("ctcn_beam_decode: workspace too small (%zu < %zu)", ws_bytes, w.total); return CTCN_EWORKSPACE; }
+  if (const int rc = lds_refused(p, lds_max, static_lds)) return rc;
+  CTCN_HIP(hipMemsetAsync(base + w.ht, 0xFF, (size_t)B * p.ht_size * sizeof(unsigned long long), st));
+  auto fill = [&](auto &a) {                     // what both kernels take
     a.lens = lens; a.lm = lm; a.alpha = alpha; a.W = W; a.blank = blank;
     a.out_ids = out_ids; a.out_len = out_len; a.out_score = out_score; a.status = status; a.T = T; a.B = B; a.V = V;
     a.nbest = nbest; a.out_count = out_count;
-    a.ht = (unsigned long long *)(base + fl.ht); a.node_par = (int *)(base + fl.npar); a.node_sym = (int *)(base + fl.nsym);
-    a.ht_size = fl.ht_size; a.max_nodes = fl.max_nodes; a.trie_slots = fl.trie_slots;
-#ifdef CTCN_BEAM_STATS
-    if (!g_beam_stats_dev) { CTCN_HIP(hipMalloc(&g_beam_stats_dev, 64 * sizeof(long long))); }
-    CTCN_HIP(hipMemsetAsync(g_beam_stats_dev, 0, 64 * sizeof(long long), st));
-    a.stats = g_beam_stats_dev;
-#endif
+    a.node_par = (int *)(base + w.npar); a.node_sym = (int *)(base + w.nsym); a.ht_size = p.ht_size; a.max_nodes = p.max_nodes;
+  };
+  if (p.path != BP_GENERIC) {
+    FastArgs a;
+    fill(a);
+    a.lgd = (const double *)(base + w.lgd); a.pb = (const float *)(base + w.pb); a.zf = (const unsigned char *)(base + w.zf);
+    a.ht = (unsigned long long *)(base + w.ht); a.trie_slots = p.trie_slots;
     const size_t rows = (size_t)T * B;
-    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)ceil_div_z(rows, 4)), dim3(256), 0, st, x, input_is_prob, (double *)(base + fl.lgd),
-                       (float *)(base + fl.pb), (unsigned char *)(base + fl.zf), rows, V, blank);
+    hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)ceil_div_z(rows, 4)), dim3(256), 0, st, x, input_is_prob, (double *)(base + w.lgd),
+                       (float *)(base + w.pb), (unsigned char *)(base + w.zf), rows, V, blank);
     CTCN_LAUNCH_CHECK();
-    int rc;
-    switch (fl.npt) {
-      case 1: rc = launch_fast<1>(fl, a, st, occ2); break;
-      case 2: rc = launch_fast<2>(fl, a, st, occ2); break;
-      case 3: rc = launch_fast<3>(fl, a, st, occ2); break;
-      default: rc = launch_fast<4>(fl, a, st, occ2); break;
-    }
-    if (rc) return rc;
-    CTCN_LAUNCH_CHECK();
-    return CTCN_OK;
+    return launch_beam(fast_kernels[p.path == BP_FAST_OCC2][p.lm_lds][p.npt - 1], B, FAST_NTH, p.lds(), st, a);
   }
-  const BeamLayout l = beam_layout(T, B, V, W);
-  if (ws_bytes < l.total) { ctcn_set_error("ctcn_beam_decode: workspace too small (%zu < %zu)", ws_bytes, l.total); return CTCN_EWORKSPACE; }
-  CTCN_HIP(hipMemsetAsync(base + l.keys, 0xFF, (size_t)B * l.ht_size * sizeof(unsigned long long), st));
   BeamArgs a;
-  a.x = x; a.input_is_prob = input_is_prob; a.lens = lens; a.lm = lm; a.alpha = alpha; a.W = W; a.blank = blank;
-  a.out_ids = out_ids; a.out_len = out_len; a.out_score = out_score; a.status = status; a.T = T; a.B = B; a.V = V;
-    a.nbest = nbest; a.out_count = out_count;
-  a.ht_keys = (unsigned long long *)(base + l.keys); a.ht_ids = (int *)(base + l.ids);
-  a.node_par = (int *)(base + l.npar); a.node_sym = (int *)(base + l.nsym); a.cand_global = (double *)(base + l.cand);
-  a.node_slot = (int *)(base + l.nslot); a.cand_owner = (int *)(base + l.cown);
-  a.ht_size = l.ht_size; a.max_nodes = l.max_nodes;
-#ifdef CTCN_BEAM_STATS
-  if (!g_beam_stats_dev) { CTCN_HIP(hipMalloc(&g_beam_stats_dev, 64 * sizeof(long long))); }
-  CTCN_HIP(hipMemsetAsync(g_beam_stats_dev, 0, 64 * sizeof(long long), st));
-  a.stats = g_beam_stats_dev;
-#endif
-  const size_t cand_bytes = (size_t)W * V * sizeof(double);
-  const int gthreads = ctcn_get_option("beam_generic_threads");          // 0 (default): by beam width; 256 / 512 / 1024: forced (measurements)
-  // (measured, tools/beam_generic_probe.py, 128 x 800 batches: 3 720 candidates per frame 7.9 -> 6.3 ms with 1 024 threads, 12 000: 21 -> 16 ms; 1 240: 4.7 -> 4.9)
-  // The kernel gives every beam slot one thread (merge, stay entries, materialisation): a forced count is raised to the smallest instantiated
-  // one >= W, so the option never changes a result (256 threads at W = 300 left slots 256.. un-merged and read stale LDS).
-  const int need = gthreads == 0 ? ((W > 64 || (long)W * V > 3500) ? 1024 : 256) : std::max(gthreads, W);
-  const bool wide = need > 512;
-  const bool mid = !wide && need > 256;
-  const void *kern = wide ? reinterpret_cast<const void *>(beam_kernel<1024>) : mid ? reinterpret_cast<const void *>(beam_kernel<512>) : reinterpret_cast<const void *>(beam_kernel<256>);
-  // The kernel's STATIC LDS is ~46 KB since the selection holds its survivors there; the candidate table joins it in LDS only if the
-  // whole block then fits what this device gives one workgroup (160 KB on gfx950; a 64-KB device falls back to the global table
-  // instead of failing the launch).
-  hipFuncAttributes fa;
-  CTCN_HIP(hipFuncGetAttributes(&fa, kern));
-  int dev_id = 0, lds_max = 64 * 1024;
-  CTCN_HIP(hipGetDevice(&dev_id));
-  if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id) != hipSuccess) lds_max = 64 * 1024;
-  a.wcap = (W + 63) / 64 * 64;
-  a.smax = std::max(1024, 2 * a.wcap);                         // (W <= 256: the 1 024 survivors of round 5; W = 1 024: 2 048)
-  const size_t state_bytes = (size_t)a.wcap * (10 * sizeof(double) + 10 * sizeof(int)) + (size_t)a.smax * (sizeof(double) + sizeof(int));
-  const size_t row_bytes = (size_t)V * sizeof(double);
-  // (round 6) whatever the 160 KB hold: the candidate table first (three scans per frame: W = 200 at V = 62 is 99 KB -- in global memory until
-  // round 5, whose rule was 32 KB), then the LM table (31.7 KB at V = 62)
-  const size_t lm_bytes = (size_t)(V + 1) * (V + 1) * sizeof(double) + 8;
-  const size_t fixed = fa.sharedSizeBytes + row_bytes + state_bytes + 256;
-  a.bitonic = ctcn_get_option("beam_bitonic");
-  a.cand_in_lds = (fixed + cand_bytes <= (size_t)lds_max && !ctcn_get_option("beam_cand_global")) ? 1 : 0;
-  a.lm_in_lds = fixed + (a.cand_in_lds ? cand_bytes : 0) + lm_bytes <= (size_t)lds_max ? 1 : 0;
-  const size_t sm = row_bytes + state_bytes + (a.cand_in_lds ? cand_bytes : 0) + (a.lm_in_lds ? lm_bytes : 0);
-  if (fa.sharedSizeBytes + sm > (size_t)lds_max) {
-    ctcn_set_error("ctcn_beam_decode: %zu B of LDS per workgroup needed, the device gives %d", fa.sharedSizeBytes + sm, lds_max);
-    return CTCN_EUNSUPPORTED;
-  }
-  CTCN_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-  if (wide) hipLaunchKernelGGL(beam_kernel<1024>, dim3(B), dim3(1024), sm, st, a);
-  else if (mid) hipLaunchKernelGGL(beam_kernel<512>, dim3(B), dim3(512), sm, st, a);
-  else hipLaunchKernelGGL(beam_kernel<256>, dim3(B), dim3(256), sm, st, a);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
+  fill(a);
+  a.x = x; a.input_is_prob = input_is_prob; a.ht_keys = (unsigned long long *)(base + w.ht); a.ht_ids = (int *)(base + w.ids);
+  a.cand_global = (double *)(base + w.cand); a.node_slot = (int *)(base + w.nslot); a.cand_owner = (int *)(base + w.cown);
+  a.wcap = p.wcap; a.smax = p.smax; a.cand_in_lds = p.cand_in_lds; a.lm_in_lds = p.lm_in_lds; a.bitonic = ctcn_get_option("beam_bitonic");
+  return launch_beam(generic_kernels[p.threads / 512], B, p.threads, p.lds(), st, a);
 }
 
 extern "C" int ctcn_beam_decode(const float *x, int input_is_prob, const int32_t *lens, const double *lm, double alpha, int W,

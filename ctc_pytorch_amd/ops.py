@@ -1564,6 +1564,23 @@ def step_stats(loss, dist, tgt_len):
     return out
 
 
+BEAM_PLAN_FIELDS = ("path", "ok", "npt", "lm_lds", "trie_slots", "lds", "threads", "wcap", "smax", "cand_in_lds", "lm_in_lds", "generic_lds",
+                    "generic_fits", "max_nodes", "ht_size")
+
+
+def beam_plan(T, B, V, W, lds_max=160 * 1024, generic_static_lds=0):
+    """ctcn_diag_beam_plan as a dict: the path ctcn_beam_decode takes under the current options (0 fast, 1 fast occ2, 2 generic), the fast
+    kernel's fit (ok, npt, lm_lds, trie_slots, lds), the generic kernel's plan, the two workspace totals and rc (0, or -3 = CTCN_EUNSUPPORTED
+    where the decode call answers that).  Pure arithmetic: no device needed."""
+    out = (ctypes.c_int * 19)()
+    rc = _lib.lib().ctcn_diag_beam_plan(int(T), int(B), int(V), int(W), int(lds_max), int(generic_static_lds), ctypes.cast(out, ctypes.c_void_p))
+    if rc not in (0, -3):
+        _lib.check(rc, "diag_beam_plan")
+    d = dict(zip(BEAM_PLAN_FIELDS, out))
+    d.update(ws_fast=out[15] | (out[16] << 31), ws_generic=out[17] | (out[18] << 31), rc=rc)
+    return d
+
+
 def beam_decode_device(x_tbv, lens, lm_table, alpha, beam_width, blank=0, input_is_prob=False):
     """Enqueue the prefix beam search (ctcn_beam_decode) on the current stream; returns DEVICE tensors
     (out_ids (B,T) int32, out_len (B) int32, score (B) float64, status (B) int32) without synchronising."""

@@ -867,6 +867,17 @@ int ctcn_diag_gemm_on_xcds(int transA, int transB, int M, int N, int K, const fl
  * Pure arithmetic, no device needed. */
 #define CTCN_DX_PLAN_INTS 4
 int ctcn_diag_dx_plan(int M, int N, int K, int lda, int precision, int a_mod16, int has_ws, size_t ws_bytes, int cus, int *out);
+/* ctcn_diag_beam_plan: what ctcn_beam_decode would do with a (T,B,V) batch at beam width W under the current options (beam_fast, beam_occ2,
+ * beam_generic_threads, beam_cand_global) on a device that gives one workgroup `lds_max` bytes of LDS, the generic kernel taking
+ * `generic_static_lds` of them as static LDS (the decode call asks the runtime for both) -- the plan of decode.hip's plan_beam.
+ * out[CTCN_BEAM_PLAN_INTS] = path (0 fast kernel, 1 its occ2 build, 2 generic kernel); the fast kernel's fit whichever path is taken: fits,
+ * candidate slots per thread (0: too many), LM table in LDS, LDS trie slots, dynamic LDS bytes; the generic kernel: threads, beam-state
+ * capacity, survivor-list capacity, candidate table in LDS, LM table in LDS, dynamic LDS bytes, static + dynamic LDS within lds_max; trie
+ * nodes per utterance, slots of the global hash table; the workspace of the fast and of the generic path, each as (bytes & 0x7fffffff,
+ * bytes >> 31) -- ctcn_beam_ws_bytes is the larger.  CTCN_EINVAL on bad arguments, CTCN_EUNSUPPORTED (out filled) where the decode call
+ * answers it: the generic kernel is taken and its LDS does not fit.  Pure arithmetic, no device needed. */
+#define CTCN_BEAM_PLAN_INTS 19
+int ctcn_diag_beam_plan(int T, int B, int V, int W, int lds_max, int generic_static_lds, int *out);
 const char *ctcn_rnn_last_kernel(int which);
 
 /* ---- host end of the decoders (hostjoin.hip; no kernel, no HIP call: works without a GPU) -------------------------------------------------

@@ -54,30 +54,15 @@ def paths(W):
     return FAST + [("generic", {"beam_fast": 0})] if W <= 60 else GENERIC
 
 
-def _fast_layout(T, V, W, occ2):
-    """decode.hip's fast_layout rule (as tests/test_gpu_kernels.py restates it): false = ctcn_beam_decode takes the generic kernel instead."""
-    npt = -(-W * V // 832)
-    core = (W * V + 2 * V) * 8 + (W * V + T) * 4
-    lm = (V + 1) * (V + 1) * 8
-    budget = (68 if occ2 else 144) * 1024
-    want_lm = lm <= 40 * 1024 and occ2 != 2
-    slots = 16384
-    while slots > 1024 and core + slots * 4 + (lm if want_lm else 0) > budget:
-        slots >>= 1
-    lm_lds = occ2 != 2 and core + slots * 4 + lm <= budget
-    lds = core + slots * 4 + (lm if lm_lds else 0)
-    return W <= 60 and 0 < npt <= 4 and V <= 256 and W * T + 2 < (1 << 24) and T < (1 << 22) and lds <= budget
-
-
 def run(x, lens, lm, alpha, W, blank, opts, is_prob=True, nbest=0):
     """One search with the options of `opts` set and every beam option back at its default afterwards."""
     from ctc_pytorch_amd import ops
-    T, _, V = x.shape
-    if opts.get("beam_fast", 1) == 1 and W <= 60:
-        assert _fast_layout(T, V, W, opts.get("beam_occ2", 0)), "this case was meant for the fast kernel"
+    T, B, V = x.shape
     try:
         for k, v in opts.items():
             ops.set_option(k, v)
+        if opts.get("beam_fast", 1) == 1 and W <= 60:       # (the library's own plan under these options: 0 / 1 = the fast kernel / its occ2 build)
+            assert ops.beam_plan(T, B, V, W)["path"] == (1 if opts.get("beam_occ2", 0) else 0), "this case was meant for the fast kernel"
         if nbest:
             ids, score, st = ops.beam_decode_nbest(x, lens, lm, alpha, W, nbest, blank, input_is_prob=is_prob)
         else:

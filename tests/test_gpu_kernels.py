@@ -2507,21 +2507,17 @@ def test_beam_generic_kernel_occupancy_options(dev, regime, W, threads, cand_glo
     assert got == base[0] and np.array_equal(np.asarray(score), np.asarray(base[1])) and list(st) == list(base[2])
 
 
-def _fast_layout(T, V, W, occ2):
-    """Test-side restatement of decode.hip's fast_layout rule: (ok, lm_lds, trie_slots).  ok false = ctcn_beam_decode silently takes the
-    generic kernel instead, so the occ2 cases assert the branch they are meant to cover with it."""
-    npt = -(-W * V // 832)                                          # FAST_NCT = 1 024 - 192 candidate threads
-    core = (W * V + 2 * V) * 8 + (W * V + T) * 4
-    lm = (V + 1) * (V + 1) * 8
-    budget = (68 if occ2 else 144) * 1024
-    want_lm = lm <= 40 * 1024 and occ2 != 2
-    slots = 16384
-    while slots > 1024 and core + slots * 4 + (lm if want_lm else 0) > budget:
-        slots >>= 1
-    lm_lds = occ2 != 2 and core + slots * 4 + lm <= budget
-    lds = core + slots * 4 + (lm if lm_lds else 0)
-    ok = W <= 60 and 0 < npt <= 4 and V <= 256 and W * T + 2 < (1 << 24) and T < (1 << 22) and lds <= budget
-    return ok, lm_lds, slots
+def _fast_plan(T, B, V, W, occ2):
+    """The library's own plan (ops.beam_plan; tests/test_beam_plan_host.py holds it to the rule) with beam_occ2 = occ2: (takes the fast kernel,
+    lm_lds, trie_slots).  False = ctcn_beam_decode silently takes the generic kernel instead, so the occ2 cases assert the branch they are
+    meant to cover with it."""
+    from ctc_pytorch_amd import ops
+    ops.set_option("beam_occ2", occ2)
+    try:
+        p = ops.beam_plan(T, B, V, W)
+    finally:
+        ops.set_option("beam_occ2", 0)
+    return p["path"] == (1 if occ2 else 0), bool(p["lm_lds"]), p["trie_slots"]
 
 
 _OCC2_ORACLE = {}
@@ -2545,11 +2541,11 @@ def test_beam_occ2_variants_vs_c_oracle(dev, case, occ2):
     8 192-slot LDS trie (16 384 by default), so that it spills to the global node table far earlier.  Labellings and status equal the C
     restatement of BeamSearch.py, float64 scores within 4 ulp, and everything bit for bit equal to beam_occ2 = 0.  Cases: a cfg5-shaped flat
     batch (the trie overflows), W = 52 where occ2 = 1 leaves the LM in global memory, small alphabets with beams wider than V and 0 / 1 / T
-    frame utterances (test_beam_fuzz_small_alphabets_vs_c_oracle's), an n-best output.  Every case must take the fast kernel (_fast_layout)."""
+    frame utterances (test_beam_fuzz_small_alphabets_vs_c_oracle's), an n-best output.  Every case must take the fast kernel (_fast_plan)."""
     from ctc_pytorch_amd import ops
     from ctc_pytorch_amd.utils.NgramLM import LanguageModel
     V, T, B, W, regime, alpha, nbest, expect = OCC2_CASES[case]
-    ok, lm_lds, slots = _fast_layout(T, V, W, occ2)
+    ok, lm_lds, slots = _fast_plan(T, B, V, W, occ2)
     assert ok, case
     if expect is not None:
         assert (lm_lds, slots) == expect[occ2], (case, lm_lds, slots)
