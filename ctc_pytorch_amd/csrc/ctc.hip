@@ -12,11 +12,15 @@
 // Kernels (all HBM/latency-bound, no MFMA):
 //   log_softmax fwd : one wave per row, lanes over classes, max / sum-exp by wave shuffles; the arg-max
 //                     (lowest index on ties) is taken on the produced log-probs in the same pass.
-//   ctc_alpha/beta  : one workgroup per utterance; the S = 2L+1 lattice states live across the threads,
-//                     alpha_{t-1} / beta_{t+1} in a double-buffered LDS row (neighbour states s-1, s-2 are
-//                     LDS reads), one barrier per frame; the log-prob gather lp[t, ext(s)] of the NEXT frame
-//                     is issued before the current frame's recursion so its latency is hidden.
-//                     alpha is stored (T,B,S) for the backward; beta is folded into it (alpha+beta).
+//   ctc_alpha/beta  : one workgroup per utterance.  Lattices of up to 256 states (labels up to 127 symbols) run wave-skewed
+//                     (ctc_lattices_skew_kernel): one state per lane, the row in a register, neighbour states s-1, s-2
+//                     by DPP wave shifts, the waves a pipeline that hands its edge states on through a small LDS ring
+//                     once per 4-frame chunk -- no LDS trip and no barrier on a frame's chain (0.107 us per frame).
+//                     Longer labels, the in-place beta pass and option "ctc_lattice_skew" = 0 take the classic kernels:
+//                     the states live across 256 threads, alpha_{t-1} / beta_{t+1} in a double-buffered LDS row
+//                     (neighbour states are LDS reads), one barrier per frame (0.233 us per frame).  Either way the
+//                     log-prob gathers lp[t, ext(s)] are issued 4 frames ahead and the lattice stores never waited for.
+//                     alpha is stored (T,B,S) for the backward, beta beside it (or folded into it: alpha+beta).
 //   ctc_grad        : fully parallel over (t,b): one wave per frame; blank occupancy by a wave-wide
 //                     log-sum-exp over the even states, label occupancy by a per-class scan of the label
 //                     string (deterministic: fixed order, no atomics).
@@ -230,6 +234,223 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_lattice_kernel(const float *_
 // two-term lse for the blank states: 195 us, the same as the 193-195 us of this kernel (round 2).  With lse3 replaced by a max the
 // wave version takes 101 us: a step is ~280 cycles of quarter-rate transcendentals (5 exp2 + 2 log2 per lane holding two states)
 // + ~300 cycles of everything else, and neither is the exchange.)
+
+// ---- The wave-skewed lattice (option "ctc_lattice_skew", plan_ctc_lattice) ----
+// ONE state per lane, s = 64 w + lane, on Wl = ceil(Smax / 64) <= 4 waves (the workgroup is 64 Wl threads), the lattice row in a register:
+// the arithmetic of a frame is the classic body's (lse3 of the same three operands in the same order, then + the gathered log-prob), so every
+// stored value has the classic kernel's bits; what changes is where the neighbour states come from.
+//   inside a wave   : s -/+ 1 is one DPP wave shift of the row register (wave_shr:1 for alpha, wave_shl:1 for beta), s -/+ 2 the shift applied
+//                     to the shifted row.  The shifts run with all 64 lanes enabled (the frame loop is wave-uniform); states past the
+//                     utterance's S, and the skip rule, are selects on the VALUES: a lane with s >= S adds 0 instead of a log-prob, so it
+//                     holds -inf for ever, which is what the classic `s + 1 < S` test substitutes.
+//   across waves    : alpha needs lower states only and beta higher ones, so the waves form a pipeline.  Frames 1 .. Tb - 1 (counted from the
+//                     pass's first frame) go in chunks of CTC_CHUNK = 4, C = ceil((Tb - 1) / 4) of them; one loop trip is one chunk and ends in
+//                     `s_waitcnt lgkmcnt(0); s_barrier`.  With Wb = ceil(S / 64) the waves that hold a state of THIS utterance, rank r = w (alpha)
+//                     or Wb - 1 - w (beta), the wave of rank r computes chunk c in trip c + r K, K = CTC_SKEW = 3 trips behind its predecessor.
+//                     The two edge values (lanes 63, 62 for alpha; 0, 1 for beta) of the four frames that chunk c STARTS from -- frames 4 c ..
+//                     4 c + 3, kept in registers while the chunk runs -- go to the successor through LDS slot `ring[w][c % CTC_RING]`.
+// Measured (profiles/ctc_lattice_ab.txt; cfg2's lattice, T = 800, B = 32, S <= 121, two waves; cycles at 2.4 GHz):
+//   classic kernel                                   186 us  0.233 us = 560 cycles per frame
+//   a trip (ring accesses + barrier) per FRAME, K = 2 161 us  0.202 us = 485 cycles; cfg4's four waves 361 us against the classic 292: the ring
+//                                                    accesses were off the chain, but the barrier's arrive-and-release is on every wave's chain
+//                                                    and grows with the waves that meet at it; + two exec toggles around the ring write and the store
+//   a trip per CHUNK of four frames, K = 3 (built)    86 us  0.107 us = 257 cycles; cfg4 139 us (0.116 us per frame), cfg1 30 us against 64
+// A frame of the built loop is 24 VALU instructions (13 on the dependent chain: 2 DPP moves, select, max3, sub, mul, exp2, 2 adds, log2, fma,
+// select, add; the other two sub / mul / exp2 share the issue: 4 quarter-rate transcendentals), ~8 scalar instructions that step the two row
+// pointers and their buffer resources, one buffer store and one buffer load, no branch, no exec change and no wait on anything issued in the
+// same chunk; a chunk adds two 16-byte ring reads, one 16-byte ring write, the wait and the barrier.  The two things the per-frame variant
+// taught: a store under `if (s < S)` is an exec toggle and a branch per frame AND makes the compiler's vmcnt count inexact across the loop (it
+// then waits for the youngest lattice store before the next gather is used) -- the range check of a buffer resource that ends at S drops
+// those lanes instead; and a prefetched register must be reloaded in place, never copied at the loop's end while its load is in flight.
+// Hand-off rule (barrier and ring depth only -- no flags, no spins, nothing rests on which wave is faster).  Both ring accesses of a trip are
+// issued at its START and complete at its barrier, so neither is waited for on the arithmetic chain:
+//   write : rank r stores slot c at the start of the trip after chunk c, trip c + 1 + r K (its first drain trip after the last chunk).
+//   read  : rank r + 1 loads slot c one trip before it computes chunk c, in trip c - 1 + (r + 1) K.
+//   read after write : c - 1 + (r + 1) K >  c + 1 + r K                       <=>  K >= 3.
+//   slot reuse       : slot c + CTC_RING is written in trip c + CTC_RING + 1 + r K, after the read's trip  <=>  CTC_RING >= K - 1.
+// CTC_RING = 4 >= K - 1 = 2 (a power of two: the slot is `c & 3`).
+// Barrier count: every wave of the workgroup executes NT = C + (Wb - 1) K loop barriers -- r K fill trips (the last one issues the first
+// read), C chunk trips, (Wb - 1 - r) K drain trips; a wave w >= Wb holds no state and only arrives NT times -- plus, in the alpha pass, one
+// __syncthreads before thread 0 reads the two final states for nll.  NT depends on in_len[b] and tgt_len[b] alone.
+// Cells written: exactly the classic kernel's (t < in_len[b], s < 2 L_b + 1); the length checks are the classic ones and return before any barrier.
+// Serves CTC_ALPHA and CTC_ALPHA_BETA.  CTC_BETA_INTO_ALPHA (ctcn_ctc_bwd's in-place reserve) stays on ctc_lattice_kernel: its prefetch of
+// the old alpha values is a second register stream with no counterpart here, and no product path launches it.
+// SLOW (option "ctc_slow_wave", a bit per wave; parity harness as "rnn_slow_items"): the named waves sleep CTC_SLOW_SLEEP x 64 cycles before
+// their ring read and after their ring write in every trip; the product instantiation carries no code for it.
+constexpr int CTC_CHUNK = 4, CTC_SKEW = 3, CTC_RING = 4, CTC_SKEW_WAVES = 4, CTC_SLOW_SLEEP = 32;
+
+__device__ __forceinline__ float lse3_select(float x0, float x1, float x2) {     // lse3 with the -inf case as a select: the same bits
+  const float m = fmaxf(x0, fmaxf(x1, x2));
+  const float L2E = 1.4426950408889634f;
+  const float sum = __builtin_amdgcn_exp2f((x0 - m) * L2E) + __builtin_amdgcn_exp2f((x1 - m) * L2E) + __builtin_amdgcn_exp2f((x2 - m) * L2E);
+  const float r = m + __builtin_amdgcn_logf(sum) * 0.6931471805599453f;
+  return m == -INFINITY ? -INFINITY : r;
+}
+
+// lds_barrier() with the wait as an instruction the compiler's own s_waitcnt placement sees: behind an opaque asm wait it waits again, with
+// lgkmcnt(0), at the first use of a ring value loaded a trip earlier -- and so for the ring accesses just issued, on the chain.
+__device__ __forceinline__ void skew_barrier() {
+  __builtin_amdgcn_s_waitcnt(0xc07f);                                // lgkmcnt(0) only (gfx9 encoding: vmcnt 63, expcnt 7)
+  asm volatile("s_barrier" ::: "memory");
+}
+
+// the row register shifted by one state towards the pass's direction; the lane with no source in this wave (0 / 63) takes `edge`
+template <int DIR>
+__device__ __forceinline__ float wave_shift1(float edge, float v) {
+  return __int_as_float(DIR > 0 ? __builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, false)
+                                : __builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
+}
+
+template <int DIR, bool SLOW>
+__device__ __forceinline__ void ctc_lattice_skew_body(float *smem, const float *__restrict__ lp, const int64_t *__restrict__ targets,
+                                                      const int64_t *__restrict__ in_len, const int64_t *__restrict__ tgt_len,
+                                                      float *__restrict__ out, float *__restrict__ nll, int T, int B, int V, int Lmax, int blank,
+                                                      int slow_mask) {
+  constexpr int PF = 4, K = CTC_SKEW;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);           // wave-uniform for the compiler too: the trip loops are scalar loops
+  const int Smax = 2 * Lmax + 1;
+  const int Tb = (int)in_len[b], L = (int)tgt_len[b];
+  if (in_len[b] < 0 || in_len[b] > T || tgt_len[b] < 0 || tgt_len[b] > Lmax) {
+    if (DIR > 0 && tid == 0) nll[b] = __uint_as_float(0x7fc00000u);
+    return;
+  }
+  if (Tb <= 0) {
+    if (DIR > 0 && tid == 0) nll[b] = L == 0 ? 0.0f : INFINITY;
+    return;
+  }
+  const int S = 2 * L + 1, Wb = (S + 63) >> 6;
+  const int C = (Tb - 1 + PF - 1) / PF;                             // chunks of frames 1 .. Tb - 1
+  const int NT = C + (Wb - 1) * K;
+  float4 *ring = reinterpret_cast<float4 *>(smem);                  // [waves][CTC_RING][2]: edge 0 / edge 1 of a chunk's four start frames
+  float *fin = smem + 8 * CTC_RING * (int)(blockDim.x >> 6);        // the two final alpha states
+  if (w < Wb) {
+    const int s = tid;
+    const bool live = s < S;
+    const bool slow = SLOW && ((slow_mask >> w) & 1);
+    const int r = DIR > 0 ? w : Wb - 1 - w;
+    const bool has_pred = r > 0;
+    const int prow = (has_pred ? w - DIR : w) * CTC_RING;            // the predecessor's ring row (rank 0: its own, the value is dropped)
+    const int edge = DIR > 0 ? 63 - lane : lane;                      // 0 / 1 in the two lanes whose states the successor reads
+    // static state info straight from the label string (one state per lane: no ext[] row in LDS)
+    const int64_t *tg = targets + (size_t)b * Lmax;
+    unsigned my_ext = (unsigned)blank;                                // (as a byte offset below: 32-bit lane offsets on wave-uniform row pointers)
+    bool my_skip = false;
+    if (live && (s & 1)) {
+      const int j = s >> 1;
+      my_ext = (unsigned)(int)tg[j];
+      if (DIR > 0) my_skip = s >= 2 && (int)tg[j] != (int)tg[j - 1];
+      else my_skip = s + 2 < S && (int)tg[j] != (int)tg[j + 1];
+    }
+    const ptrdiff_t lp_step = (ptrdiff_t)DIR * B * V, out_step = (ptrdiff_t)DIR * B * Smax;
+    const int t_first = DIR > 0 ? 0 : Tb - 1;
+    const float *lpt = lp + ((size_t)t_first * B + b) * V;           // wave-uniform row pointers, stepped once per frame
+    float *orow = out + ((size_t)t_first * B + b) * Smax;
+    const unsigned ext_off = my_ext * 4u, s_off = (unsigned)s * 4u;
+    // Rows through buffer resources built from the wave-uniform row pointer: no per-lane 64-bit address, and the lattice row's resource ends at
+    // the utterance's S, so the store of a lane past it is dropped by the range check -- no branch (and no exec toggling) around the store, which
+    // also keeps the compiler's vmcnt counting exact across the loop.  (A label outside [0, V) gathers 0.0 instead of reading past the row.)
+    auto gather = [&](const float *row) {
+      return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(__builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(row), 0, V * 4, 0x00020000), ext_off, 0, 0));
+    };
+    auto put = [&](float *row, float v) {
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), __builtin_amdgcn_make_buffer_rsrc(row, 0, S * 4, 0x00020000), s_off, 0, 0);
+    };
+    float a = -INFINITY;                                             // the lattice row: this lane's state of the last frame done
+    if (live && (DIR > 0 ? s <= 1 : s >= S - 2)) a = gather(lpt);
+    put(orow, a);
+    // log-prob gathers PF frames ahead; the pointer stops at the last frame (its extra loads are not used).  A lane past S loads the blank's
+    // log-prob and adds 0 instead.
+    float q[PF];                                                     // q[i]: frame n + i of the running chunk, reloaded in place for frame n + i + PF
+    const float *lpn = lpt;
+#pragma unroll
+    for (int i = 0; i < PF; ++i) {
+      if (1 + i < Tb) lpn += lp_step;
+      q[i] = gather(lpn);
+    }
+    const float4 ninf4 = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    auto ring_read = [&](int c, float4 &x, float4 &y) {
+      if (slow) __builtin_amdgcn_s_sleep(CTC_SLOW_SLEEP);
+      const float4 *slot = ring + 2 * (prow + (c & (CTC_RING - 1)));
+      x = slot[0]; y = slot[1];
+      if (!has_pred) { x = ninf4; y = ninf4; }
+    };
+    auto ring_write = [&](int c, const float (&h)[PF]) {
+      if (edge <= 1) ring[2 * (w * CTC_RING + (c & (CTC_RING - 1))) + edge] = make_float4(h[0], h[1], h[2], h[3]);
+      if (slow) __builtin_amdgcn_s_sleep(CTC_SLOW_SLEEP);
+    };
+    // fill: r K trips; the last one issues the read of the predecessor's slot 0
+    float4 ex = ninf4, ey = ninf4;                                   // the predecessor's edges of this chunk's start frames
+    for (int j = 0; j < r * K; ++j) {
+      if (j == r * K - 1) ring_read(0, ex, ey);
+      skew_barrier();
+    }
+    float hist[PF] = {a, a, a, a};                                   // this lane's state at the chunk's four start frames
+    auto frame = [&](float e0, float e1, float q) {
+      const float x1 = wave_shift1<DIR>(e0, a);
+      const float x2r = wave_shift1<DIR>(e1, x1);
+      const float v = lse3_select(a, x1, my_skip ? x2r : -INFINITY) + q;
+      orow += out_step;
+      put(orow, v);
+      a = v;
+    };
+    // One chunk.  FAST: its four frames and the four it prefetches all exist -- no checks, plain pointer steps.  A log-prob register is
+    // reloaded in place right after its frame (no copy of a register with a load in flight, which would be waited for with everything
+    // younger, the lattice stores included); the select for lanes past S sits at the use, four frames after the load.
+    auto chunk = [&](int c, auto fast) {
+      constexpr bool FAST = decltype(fast)::value;
+      // ring traffic first, off the chain: my edges of chunk c - 1's start frames, the predecessor's of chunk c + 1's
+      float4 nx, ny;
+      if (c > 0) ring_write(c - 1, hist);
+      ring_read(c + 1, nx, ny);
+      const int n = 1 + c * PF;
+      const float e0[PF] = {ex.x, ex.y, ex.z, ex.w}, e1[PF] = {ey.x, ey.y, ey.z, ey.w};
+#pragma unroll
+      for (int i = 0; i < PF; ++i) {
+        hist[i] = a;
+        if (FAST || n + i < Tb) frame(e0[i], e1[i], live ? q[i] : 0.0f);
+        if (FAST || n + i + PF < Tb) lpn += lp_step;
+        q[i] = gather(lpn);
+      }
+      ex = nx; ey = ny;
+      skew_barrier();
+    };
+    int c = 0;
+    for (; 1 + c * PF + 2 * PF <= Tb; ++c) chunk(c, std::true_type());
+    for (; c < C; ++c) chunk(c, std::false_type());
+    if (DIR > 0) {
+      if (s == S - 1) fin[0] = a;
+      if (s == S - 2) fin[1] = a;
+    }
+    for (int j = 0; j < (Wb - 1 - r) * K; ++j) {
+      if (j == 0 && C > 0) ring_write(C - 1, hist);
+      skew_barrier();
+    }
+  } else {
+    for (int j = 0; j < NT; ++j) skew_barrier();
+  }
+  if (DIR > 0) {
+    __syncthreads();
+    if (tid == 0) {
+      const float l1 = fin[0], l2 = S > 1 ? fin[1] : -INFINITY;
+      const float m = fmaxf(l1, l2);
+      nll[b] = m == -INFINITY ? INFINITY : -(m + logf(expf(l1 - m) + expf(l2 - m)));
+    }
+  }
+}
+
+// grid (B) with beta == nullptr: alpha alone; grid (B, 2): alpha (y = 0) and beta (y = 1) side by side, as ctc_lattices_kernel
+template <bool SLOW>
+__global__ __launch_bounds__(64 * CTC_SKEW_WAVES) void ctc_lattices_skew_kernel(const float *__restrict__ lp, const int64_t *__restrict__ targets,
+                                                                                const int64_t *__restrict__ in_len,
+                                                                                const int64_t *__restrict__ tgt_len, float *__restrict__ alpha,
+                                                                                float *__restrict__ beta, float *__restrict__ nll, int T, int B,
+                                                                                int V, int Lmax, int blank, int slow_mask) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  if (blockIdx.y == 0) ctc_lattice_skew_body<1, SLOW>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank, slow_mask);
+  else ctc_lattice_skew_body<-1, SLOW>(smem, lp, targets, in_len, tgt_len, beta, nll, T, B, V, Lmax, blank, slow_mask);
+}
+
 // alpha (blockIdx.y = 0) and beta (blockIdx.y = 1) of every utterance in one launch: the two passes are independent chains of
 // T dependent steps, so running them side by side halves the latency of the loss (2B workgroups instead of B twice).
 template <int NS>
@@ -819,12 +1040,52 @@ extern "C" int ctcn_log_softmax_bwd(const float *lp, const float *dlp, float *dl
 // The lattice passes of every CTC entry point: alpha alone (ctcn_ctc_fwd, ctcn_ctc_fwd_ex without beta), the beta pass added into alpha
 // in place (ctcn_ctc_bwd's one-buffer reserve), or alpha and beta side by side in one launch (ctcn_ctc_fwd_both, ctcn_ctc_fwd_ex).
 enum CtcPasses { CTC_ALPHA, CTC_BETA_INTO_ALPHA, CTC_ALPHA_BETA };
+
+// The launch of a lattice pass, by arithmetic alone (ctcn_diag_ctc_lattice_plan shows it to the CPU tests).  Skewed (ctc_lattices_skew_kernel: a
+// state per lane on `waves` waves of 64, the ring and the two final states in LDS) where the lattice fits CTC_SKEW_WAVES waves and option
+// "ctc_lattice_skew" is on; otherwise the classic kernels: CTC_THREADS threads, ns states per thread, three lattice rows of LDS.
+struct CtcLatticeOptions { int skew; };
+struct CtcLatticePlan { int skewed, waves, ns, threads; size_t lds; };
+CtcLatticePlan plan_ctc_lattice(int Lmax, const CtcLatticeOptions &o) {
+  const int S = 2 * Lmax + 1;
+  CtcLatticePlan p;
+  p.waves = ceil_div(S, 64);
+  p.skewed = o.skew && p.waves <= CTC_SKEW_WAVES;
+  if (p.skewed) {
+    p.ns = 1;
+    p.threads = 64 * p.waves;
+    p.lds = (size_t)(8 * CTC_RING * p.waves + 2) * sizeof(float);
+  } else {
+    const int ns = ceil_div(S, CTC_THREADS);
+    p.ns = ns <= 1 ? 1 : ns <= 2 ? 2 : ns <= 4 ? 4 : ns <= 8 ? 8 : 16;
+    p.threads = CTC_THREADS;
+    p.lds = (size_t)(3 * S) * sizeof(float);
+  }
+  return p;
+}
+
+extern "C" int ctcn_diag_ctc_lattice_plan(int Lmax, int *out) {
+  CTCN_REQUIRE(out && Lmax >= 0 && 2 * (int64_t)Lmax + 1 <= CTC_THREADS * CTC_NS, "ctcn_diag_ctc_lattice_plan: bad args");
+  const CtcLatticePlan p = plan_ctc_lattice(Lmax, CtcLatticeOptions{ctcn_get_option("ctc_lattice_skew")});
+  out[0] = p.skewed; out[1] = p.waves; out[2] = p.ns; out[3] = p.threads; out[4] = (int)p.lds; out[5] = CTC_SKEW * CTC_CHUNK;
+  return CTCN_OK;
+}
+
 static int ctc_lattices(const char *who, CtcPasses passes, const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len,
                         float *alpha, float *beta, float *nll, int T, int B, int V, int Lmax, int blank, hipStream_t st) {
   if (2 * Lmax + 1 > CTC_THREADS * CTC_NS) { ctcn_set_error("%s: label length %d > %d unsupported", who, Lmax, (CTC_THREADS * CTC_NS - 1) / 2); return CTCN_EUNSUPPORTED; }
-  const size_t sm = (size_t)(3 * (2 * Lmax + 1)) * sizeof(float);
-  const int ns = ceil_div(2 * Lmax + 1, CTC_THREADS);
-  if (passes == CTC_ALPHA) {
+  CtcLatticeOptions opt{ctcn_get_option("ctc_lattice_skew")};
+  if (passes == CTC_BETA_INTO_ALPHA) opt.skew = 0;          // the in-place beta pass has no skewed body
+  const CtcLatticePlan plan = plan_ctc_lattice(Lmax, opt);
+  const size_t sm = plan.lds;
+  const int ns = plan.ns;
+  if (plan.skewed) {
+    const int slow = ctcn_get_option("ctc_slow_wave");
+    const dim3 grid(B, passes == CTC_ALPHA_BETA ? 2 : 1);
+#define CTC_LAUNCH(SLOW) hipLaunchKernelGGL((ctc_lattices_skew_kernel<SLOW>), grid, dim3(plan.threads), sm, st, lp, targets, in_len, tgt_len, alpha, beta, nll, T, B, V, Lmax, blank, slow)
+    if (slow) CTC_LAUNCH(true); else CTC_LAUNCH(false);
+#undef CTC_LAUNCH
+  } else if (passes == CTC_ALPHA) {
 #define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattice_kernel<1, NS>), dim3(B), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank)
     if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
 #undef CTC_LAUNCH

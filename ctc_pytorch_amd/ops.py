@@ -1581,6 +1581,18 @@ def beam_plan(T, B, V, W, lds_max=160 * 1024, generic_static_lds=0):
     return d
 
 
+CTC_LATTICE_PLAN_FIELDS = ("skewed", "waves", "ns", "threads", "lds", "skew")
+
+
+def ctc_lattice_plan(Lmax):
+    """ctcn_diag_ctc_lattice_plan as a dict: the launch of a CTC lattice pass over label rows of Lmax symbols under the current
+    `ctc_lattice_skew` (skewed or classic kernel, waves of 64 states that cover the lattice, states per thread, threads, dynamic LDS bytes, and
+    the skewed kernel's skew in frames per wave).  Pure arithmetic: no device needed."""
+    out = (ctypes.c_int * 6)()
+    _lib.check(_lib.lib().ctcn_diag_ctc_lattice_plan(int(Lmax), ctypes.cast(out, ctypes.c_void_p)), "diag_ctc_lattice_plan")
+    return dict(zip(CTC_LATTICE_PLAN_FIELDS, out))
+
+
 def beam_decode_device(x_tbv, lens, lm_table, alpha, beam_width, blank=0, input_is_prob=False):
     """Enqueue the prefix beam search (ctcn_beam_decode) on the current stream; returns DEVICE tensors
     (out_ids (B,T) int32, out_len (B) int32, score (B) float64, status (B) int32) without synchronising."""

@@ -94,6 +94,14 @@ int ctcn_device_xcds(void);
  * rest on barriers and buffer parity only, never on which wave is faster.  "rnn_slow_exchange" = N: the same for the exchange waves; both options also select
  * the SLOW instantiations of rnn_bwd_scatter / rnn_bwd_scatter2 (item waves sleep before they read the parked tiles / start their gather, exchange waves
  * behind the barrier before they read the staged operand): test_rnn_bwd_with_slow_waves.
+ * "ctc_lattice_skew" = 1 (default): the CTC lattice passes of ctcn_ctc_fwd / ctcn_ctc_fwd_both / ctcn_ctc_fwd_ex run wave-skewed where the lattice
+ * has at most 256 states (label rows of up to 127 symbols): one state per lane, neighbour states by DPP wave shifts, the waves a pipeline three
+ * four-frame chunks apart that hands its edge states on through a small LDS ring (ctc.hip: ctc_lattices_skew_kernel: one barrier per chunk); 0: the classic kernels
+ * (lattice row in LDS, an LDS round trip and a barrier on every frame's chain).  Every stored value is bit-identical either way (test_ctc_lattice_skew.py);
+ * longer label rows and ctcn_ctc_bwd's in-place beta pass take the classic kernels whatever the option says.  ctcn_diag_ctc_lattice_plan shows
+ * the choice.  "ctc_slow_wave" = 0 (parity harness): a bit per wave (0..15; other values clamp) selects the SLOW instantiation of the skewed
+ * kernel, whose named waves sleep 32 x 64 cycles before their ring read and after their ring write in every chunk.  Results must not change:
+ * the hand-off rests on the barrier and the ring's depth, never on which wave is faster.
  * "bn_rows4" = 1 (default, round 5): BatchNorm over (rows, C) with C % 4 == 0 forms its column sums with 16-B loads, sixteen row phases per
  * workgroup (colreduce_rows4_kernel, behind the dense and the length-aware entry points alike); 0: the dword kernel (colreduce_rows_kernel).  Same chunks, same element values, float64 partials grouped differently: the float32
  * results agreed bit for bit wherever compared (tools/bn_rows_probe.py).  cfg2 13.33 -> 13.25 ms per step, cfg4 53.2 -> 52.8.
@@ -878,6 +886,12 @@ int ctcn_diag_dx_plan(int M, int N, int K, int lda, int precision, int a_mod16, 
  * answers it: the generic kernel is taken and its LDS does not fit.  Pure arithmetic, no device needed. */
 #define CTCN_BEAM_PLAN_INTS 19
 int ctcn_diag_beam_plan(int T, int B, int V, int W, int lds_max, int generic_static_lds, int *out);
+/* ctcn_diag_ctc_lattice_plan: the launch of a CTC lattice pass over label rows of Lmax symbols (S = 2 Lmax + 1 states) under the current
+ * "ctc_lattice_skew" -- the plan of ctc.hip's plan_ctc_lattice.  out[CTCN_CTC_LATTICE_PLAN_INTS] = skewed (1) or classic (0) kernel, waves of
+ * 64 states that cover the lattice (ceil(S / 64)), states per thread, threads per workgroup, dynamic LDS bytes, and the skew of the skewed
+ * kernel in frames per wave (a constant of the build).  CTCN_EINVAL on bad arguments.  Pure arithmetic, no device needed. */
+#define CTCN_CTC_LATTICE_PLAN_INTS 6
+int ctcn_diag_ctc_lattice_plan(int Lmax, int *out);
 const char *ctcn_rnn_last_kernel(int which);
 
 /* ---- host end of the decoders (hostjoin.hip; no kernel, no HIP call: works without a GPU) -------------------------------------------------
