@@ -124,6 +124,9 @@ _SIGS = {
     "ctcn_frame_context_tile": (I, [P, I]),
     "ctcn_frame_context": (I, [P, P, P, P, P, P, I, I, I, I, P]),
     "ctcn_frame_context_host": (I, [P, I, I, P, P, I, P]),
+    "ctcn_spec_augment": (I, [P, P, P, U, U, P, I, I, I, P]),
+    "ctcn_spec_augment_plan": (I, [P, U, U, I, I, P, P, P]),
+    "ctcn_spec_augment_host": (I, [P, I, I, P, U, U, P]),
     "ctcn_cmvn_accumulate_ws_bytes": (Z, [I, I, I]),
     "ctcn_cmvn_accumulate": (I, [P, P, P, I, I, I, P, Z, P]),
     "ctcn_comm_unique_id": (I, [P]),
@@ -191,6 +194,12 @@ class ResampleOpts(ctypes.Structure):
 class ContextOpts(ctypes.Structure):
     """ctcn_context_opts of include/ctcn.h: splice, skip, downsample pad and deltas (utils/features.FrameContext fills it)."""
     _fields_ = [(k, ctypes.c_int32) for k in ("left", "right", "skip", "n_downsample", "delta_order", "delta_window")]
+
+
+class SpecAugOpts(ctypes.Structure):
+    """ctcn_specaug_opts of include/ctcn.h: time warp, frequency masks and time masks (utils/features.SpecAugment fills it)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("warp_window", "num_freq_masks", "freq_width", "num_time_masks", "time_width")] + \
+               [(k, ctypes.c_float) for k in ("time_ratio", "fill")]
 
 
 def sources():

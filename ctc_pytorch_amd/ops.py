@@ -2205,6 +2205,74 @@ def frame_context(feats, frames, left=0, right=0, skip=1, n_downsample=1, delta_
     return out, out_frames, fractions
 
 
+# SpecAugment on the base features, in front of frame_context (specaug.hip): time warp, frequency masks, time masks
+SPEC_AUGMENT_OPTIONS = ("warp_window", "num_freq_masks", "freq_width", "num_time_masks", "time_width", "time_ratio", "fill")
+_U64 = (1 << 64) - 1
+
+
+def _specaug_opts(who, warp_window=0, num_freq_masks=0, freq_width=0, num_time_masks=0, time_width=0, time_ratio=1.0, fill=0.0, **unknown):
+    if unknown:
+        raise TypeError("ctc_pytorch_amd.%s: unknown option(s) %s (known: %s)" % (who, ", ".join(sorted(unknown)), ", ".join(SPEC_AUGMENT_OPTIONS)))
+    return _lib.SpecAugOpts(warp_window=int(warp_window), num_freq_masks=int(num_freq_masks), freq_width=int(freq_width),
+                            num_time_masks=int(num_time_masks), time_width=int(time_width), time_ratio=float(time_ratio), fill=float(fill))
+
+
+def spec_augment_plan(T, F, seed, utt_index, **opts):
+    """The intervals spec_augment uses for the utterance `utt_index` of T frames and F columns under `seed` (ctcn_spec_augment_plan):
+    {"warp": (c, w) or None, "freq": [(f0, len), ...], "time": [(t0, len), ...]}.  Host arithmetic, no device.  RuntimeError for options
+    outside the limits of include/ctcn.h."""
+    o = _specaug_opts("spec_augment_plan", **opts)
+    warp = (ctypes.c_int32 * 2)()
+    freq = (ctypes.c_int32 * (2 * max(o.num_freq_masks, 1)))()
+    time = (ctypes.c_int32 * (2 * max(o.num_time_masks, 1)))()
+    _lib.check(_lib.lib().ctcn_spec_augment_plan(ctypes.byref(o), int(seed) & _U64, int(utt_index) & _U64, int(T), int(F), warp, freq, time),
+               "spec_augment_plan")
+    return {"warp": (warp[0], warp[1]) if warp[1] > 0 else None,
+            "freq": [(freq[2 * k], freq[2 * k + 1]) for k in range(o.num_freq_masks)],
+            "time": [(time[2 * k], time[2 * k + 1]) for k in range(o.num_time_masks)]}
+
+
+def spec_augment_host(feats_np, seed, utt_index, **opts):
+    """spec_augment for ONE utterance on the host (ctcn_spec_augment_host: the interval and interpolation code the kernel is compiled
+    from): feats_np (T, F) float32 numpy -> a new (T, F) float32 array.  No device."""
+    x = np.ascontiguousarray(feats_np, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("ctc_pytorch_amd.spec_augment_host: expected feats (T, F), got %s" % (x.shape,))
+    T, F = x.shape
+    o = _specaug_opts("spec_augment_host", **opts)
+    out = np.empty_like(x)
+    _lib.check(_lib.lib().ctcn_spec_augment_host(x.ctypes.data_as(ctypes.c_void_p) if T else None, T, F, ctypes.byref(o), int(seed) & _U64,
+                                                 int(utt_index) & _U64, out.ctypes.data_as(ctypes.c_void_p) if T else None), "spec_augment_host")
+    return out
+
+
+def spec_augment(feats, frames, seed, utt_offset=0, **opts):
+    """SpecAugment of a zero-padded base batch in one launch (ctcn_spec_augment; the computation, step by step, in include/ctcn.h): feats
+    (B, Tmax, F) float32, frames (B) the utterances' frame counts -- a list or a device tensor, clamped to [0, Tmax]; rows at or beyond
+    them are never read and come out as zeros.  Utterance b draws its warp and masks from (seed, utt_offset + b) alone.  Options:
+    warp_window, num_freq_masks, freq_width, num_time_masks, time_width, time_ratio, fill (all off by default: the identity on the
+    utterances' rows).  Returns out (B, Tmax, F) float32, a new tensor.  No autograd; device tensors only (no CPU fallback)."""
+    if not torch.is_tensor(feats) or feats.dim() != 3:
+        raise ValueError("ctc_pytorch_amd.spec_augment: expected feats (B, Tmax, F), got %s" % (tuple(feats.shape) if torch.is_tensor(feats) else type(feats).__name__,))
+    _need_gpu(feats, frames if torch.is_tensor(frames) else None)
+    if feats.dtype != torch.float32:
+        raise TypeError("ctc_pytorch_amd.spec_augment: expected float32 features, got %s" % feats.dtype)
+    B, Tmax, F = feats.shape
+    dev = feats.device
+    if torch.is_tensor(frames):
+        frames = frames.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        frames = torch.as_tensor([int(v) for v in frames], dtype=torch.int32).to(dev)
+    if frames.numel() != B or B == 0 or F == 0:
+        raise ValueError("ctc_pytorch_amd.spec_augment: %d frame counts for a batch of %s" % (frames.numel(), tuple(feats.shape)))
+    o = _specaug_opts("spec_augment", **opts)
+    feats = feats.contiguous()
+    out = torch.empty((B, Tmax, F), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().ctcn_spec_augment(_ptr(feats) if Tmax else None, _ptr(frames), ctypes.byref(o), int(seed) & _U64, int(utt_offset) & _U64,
+                                            _ptr(out) if Tmax else None, B, Tmax, F, _lib.stream_ptr()), "spec_augment")
+    return out
+
+
 def cmvn_accumulate(feats, frames, stats):
     """Adds the rows t < frames[b] of feats (B, Tmax, F) float32 to stats (2, F + 1) float64 on the device, Kaldi's CMVN statistics layout
     (sums | count; sums of squares | 0): ctcn_cmvn_accumulate.  Rows at or beyond frames[b] are never read; float64 partial sums combined

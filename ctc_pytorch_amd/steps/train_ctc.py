@@ -205,6 +205,22 @@ def device_context(opts):
     return FrameContext.from_opts(opts)
 
 
+def spec_augment(opts):
+    """The driver key `spec_augment` (default off): a utils.features.SpecAugment for the TRAINING DeviceContext -- `true` for its DEFAULTS
+    (warp_window 5, two frequency masks of up to 15 columns, two time masks of up to 40 frames and a fifth of the utterance: the paper's
+    LD policy scaled to 81-column, three-second utterances; no error rate has been measured with them here), or a mapping of the option
+    names -- seeded with opts.seed; None with the key absent or false.  It works on the base features the device stage holds, so it needs
+    `device_context`: without it this raises, it does not fall back to an unaugmented run."""
+    value = getattr(opts, "spec_augment", None)
+    if value is None or value is False:
+        return None
+    if not bool(getattr(opts, "device_context", False)):
+        raise ValueError("spec_augment needs device_context: true (the masks and the warp are applied to the base features on the GPU, "
+                         "in front of the splice); set both keys or neither")
+    from ctc_pytorch_amd.utils.features import SpecAugment
+    return SpecAugment.from_opts(value, seed=int(getattr(opts, "seed", 0)))
+
+
 def report_options(opts, index2word=None):
     """run_epoch's error-breakdown keywords from the driver options `error_report` (bool), `score_map` (path of a three-column phone table)
     and `score_map_cols` ("60-48", "60-39" or "48-39"); absent (or false) keys pass nothing.  A score map needs the vocabulary's names."""
@@ -295,6 +311,7 @@ def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print, in
     opts = Config()
     for k, v in conf.items():
         setattr(opts, k, v)
+    augment = spec_augment(opts)                          # (None: the key is absent; training batches only; raises before anything is set up)
     rank, world, local = parallel.init_from_env()
     device = torch.device("cuda", local)
     # The host side of a step is collation and a 4 MB staging copy: a torch CPU op that fans out to every core (128 OpenMP
@@ -327,7 +344,7 @@ def main(conf, train_loader=None, dev_loader=None, num_class=None, log=print, in
         log = lambda *_a, **_k: None                      # one log stream: every rank holds the same all-reduced statistics
     if context is not None:
         from ctc_pytorch_amd.utils.data_loader import DeviceContext
-        train_loader, dev_loader = DeviceContext(train_loader, device, context), DeviceContext(dev_loader, device, context)
+        train_loader, dev_loader = DeviceContext(train_loader, device, context, augment=augment), DeviceContext(dev_loader, device, context)
     elif device.type == "cuda":
         from ctc_pytorch_amd.utils.data_loader import DevicePrefetcher
         train_loader, dev_loader = DevicePrefetcher(train_loader, device), DevicePrefetcher(dev_loader, device)   # async double-buffered H2D
@@ -390,6 +407,7 @@ if __name__ == "__main__":
     ap.add_argument("--skip-nonfinite-steps", action="store_true", help="drop optimiser steps whose gradient holds NaN / Inf (default: the YAML's skip_nonfinite_steps, else off)")
     ap.add_argument("--mask-padding", action="store_true", help="tell the model every utterance's real frames: padding reaches no BatchNorm statistic and no recurrence (default: the YAML's mask_padding, else off)")
     ap.add_argument("--device-context", action="store_true", help="read the archives as base features and apply left_ctx / right_ctx / n_skip_frame / n_downsample on the GPU (default: the YAML's device_context, else off)")
+    ap.add_argument("--spec-augment", action="store_true", help="SpecAugment the training batches on the GPU with the default policy; needs --device-context (default: the YAML's spec_augment, else off)")
     ap.add_argument("--error-report", action="store_true", help="log the error breakdown (sub / del / ins, top confusions) of every validation pass (default: the YAML's error_report, else off)")
     ap.add_argument("--score-map", default=None, help="three-column phone table the breakdown is scored under (default: the YAML's score_map, else none)")
     ap.add_argument("--score-map-cols", default=None, choices=["60-48", "60-39", "48-39"], help="which fold of the table (default: the YAML's score_map_cols, else 48-39)")
@@ -405,6 +423,8 @@ if __name__ == "__main__":
         conf["mask_padding"] = True
     if a.device_context:
         conf["device_context"] = True
+    if a.spec_augment and not conf.get("spec_augment"):
+        conf["spec_augment"] = True
     if a.max_grad_norm is not None:
         conf["max_grad_norm"] = a.max_grad_norm
     if a.skip_nonfinite_steps:

@@ -296,14 +296,35 @@ class DeviceContext(DevicePrefetcher):
     on the device by one launch on the copy stream (utils/features.FrameContext: ops.frame_context), which also writes the float32 length
     fractions.  Yields what DevicePrefetcher yields over the host path, bit for bit: (inputs (B, T', F'), input_sizes fractions, targets,
     target_sizes, utt_list[, B_global]).  The frame counts reach the kernel as the loader's int32 values.  A shard of a global batch is padded to
-    the global T_max and its output is sized from that, so its fractions are the global batch's."""
+    the global T_max and its output is sized from that, so its fractions are the global batch's.
 
-    def __init__(self, loader, device, context):
+    augment (utils/features.SpecAugment, or None): run on the staged base batch on the copy stream, in front of the context stage.  Utterance
+    b of a batch is number `seen + b` of the stream, `seen` the utterances of the GLOBAL batches staged before it -- counted across epochs, so
+    every epoch draws new masks -- plus, under parallel.ShardedBatches (the batch carries B_global, the loader .rank / .world), the shard's
+    first row: N ranks augment a global batch exactly as one process does.  None: the path above, untouched."""
+
+    def __init__(self, loader, device, context, augment=None):
         super().__init__(loader, device)
         self.context = context
+        self.augment = augment
+        self._seen = 0                    # utterances of the global batches staged so far
+        self._offset = 0                  # the batch being staged: its first utterance's number
+
+    def _stage(self, batch, stream):
+        if self.augment is not None:
+            n = int(batch[0].shape[0])
+            n_global = int(batch[5]) if len(batch) > 5 else n
+            lo = 0
+            if len(batch) > 5:
+                from ..parallel import shard_range
+                lo = shard_range(n_global, self.loader.rank, self.loader.world)[0]
+            self._offset = self._seen + lo
+            self._seen += n_global
+        return super()._stage(batch, stream)
 
     def _on_device(self, dev):
         if dev[1].dtype != torch.int32:
             raise TypeError("DeviceContext: the loader must carry int32 frame counts (create_base_input), got %s" % dev[1].dtype)
-        out, _, fractions = self.context(dev[0], dev[1])
+        feats = dev[0] if self.augment is None else self.augment(dev[0], dev[1], utt_offset=self._offset)
+        out, _, fractions = self.context(feats, dev[1])
         return [out, fractions, dev[2], dev[3]]

@@ -815,6 +815,49 @@ int ctcn_frame_context(const float *feats, const int32_t *frames, const ctcn_con
                        float *fractions, int B, int Tin_max, int F, int Tout_max, void *stream);
 int ctcn_frame_context_host(const float *feats, int num_frames, int F, const ctcn_context_opts *opts, float *out, int out_rows,
                             float *fraction);
+/* SpecAugment on the base features, in front of ctcn_frame_context (specaug.hip): time warp, frequency masks and time masks (Park et al.,
+ * Interspeech 2019), drawn per utterance from a counter-based generator so that host, device and a numpy restatement agree bit for bit.
+ * Options: warp_window (W; 0: no warp), num_freq_masks, freq_width, num_time_masks, time_width, time_ratio, fill.  For utterance b of a
+ * padded base batch feats (B, Tmax, F) float32:
+ *   T = clamp(frames[b], 0, Tmax); the utterance's 64-bit index is u = utt_offset + b;
+ *   draw(d) = the four words r0 .. r3 of philox4(seed, (u << 8) | d) of common.h: counter (low 32 bits, high 32 bits, 0, 0), key = seed --
+ *   the dropout kernels' convention;
+ *   rnd(word, n) = ((uint64)(word >> 8) * n) >> 24, an integer in [0, n): integer arithmetic only.
+ *   1. time warp, d = 0, active when W > 0 and T > 2 W: c = W + rnd(r0, T - 2 W), w = c + rnd(r1, 2 W - 1) - (W - 1), so c in [W, T - W) and
+ *      w in [1, T - 1].  Output row t < T reads a source position in integers: for t < w, num = t c, den = w, base = 0; otherwise
+ *      num = (t - w) (T - c), den = T - w, base = c.  In int64: i0 = base + num / den, rem = num % den, i1 = min(i0 + 1, T - 1).  With
+ *      rem = 0 the element is x[i0] itself; otherwise a = (double) rem / (double) den and the element is
+ *      (float)((1.0 - a) * x[i0] + a * x[i1]), every float64 operation rounded on its own (no fused multiply-add);
+ *   2. frequency masks, d = 1 .. num_freq_masks: len = rnd(r0, min(freq_width, F) + 1), f0 = rnd(r1, F - len + 1); columns [f0, f0 + len)
+ *      of every row < T become fill;
+ *   3. time masks, d = 9 + k, k < num_time_masks: cap = min(time_width, T, (int) floor((double) time_ratio * (double) T)),
+ *      len = rnd(r0, cap + 1), t0 = rnd(r1, T - len + 1); rows [t0, t0 + len) become fill.
+ * Warp first, then masks: the masks are positions in the WARPED output, so the whole is one gather, out[t][f] = masked ? fill :
+ * warped(t, f).  Rows t >= T of the output are zeros; input rows at or beyond frames[b] are never read; every output element is written.
+ * With all three parts off the output equals the input on rows < T, bit for bit.  An utterance's result depends on (seed, u, T, F, the
+ * options, its own frames) alone, not on B, Tmax or its neighbours.
+ * ctcn_spec_augment: feats, frames (B) int32 and out (B, Tmax, F) in DEVICE memory; out must not alias feats (the warp gathers).  One
+ * launch on the caller's stream, grid (tiles of 32 rows, B): one wave computes the utterance's draws, one Philox call per lane, and parks
+ * the intervals in LDS; every row of the tile is classified once (zero, fill, copy, interpolate) with its source rows and weight; then
+ * consecutive lanes write consecutive floats, and a row inside a time mask is written without reading its source.  No atomics, no
+ * workspace, no host synchronisation.
+ * ctcn_spec_augment_plan: the intervals the kernel uses for ONE utterance of T frames, on the HOST (no HIP call): warp[2] = (c, w) or
+ * (0, 0) without a warp, freq[2 num_freq_masks] = (f0, len) pairs, time[2 num_time_masks] = (t0, len) pairs (a pointer may be NULL where
+ * its count is 0).
+ * ctcn_spec_augment_host: the same computation for ONE utterance on the HOST (no HIP call; works without a GPU), through the interval and
+ * interpolation functions the kernel is compiled from: feats, out (T, F).
+ * Limits, from every entry point before any launch: CTCN_EINVAL for NULL, a negative count, width or window, a time_ratio outside [0, 1]
+ * or NaN, a fill that is not finite, F below 1, B outside [1, 65 535], Tmax (T) negative or beyond 2^30; CTCN_EUNSUPPORTED for
+ * num_freq_masks beyond 8, num_time_masks beyond 32, F beyond 65 536. */
+typedef struct ctcn_specaug_opts {
+  int32_t warp_window, num_freq_masks, freq_width, num_time_masks, time_width;
+  float time_ratio, fill;
+} ctcn_specaug_opts;
+int ctcn_spec_augment(const float *feats, const int32_t *frames, const ctcn_specaug_opts *opts, uint64_t seed, uint64_t utt_offset, float *out,
+                      int B, int Tmax, int F, void *stream);
+int ctcn_spec_augment_plan(const ctcn_specaug_opts *opts, uint64_t seed, uint64_t utt_index, int T, int F, int32_t *warp, int32_t *freq,
+                           int32_t *time);
+int ctcn_spec_augment_host(const float *feats, int T, int F, const ctcn_specaug_opts *opts, uint64_t seed, uint64_t utt_index, float *out);
 
 /* ---------------------------------------------------------------------------------------------------
  * CTC prefix beam search with bigram LM; replaces BeamDecoder.decode -> ctcBeamSearch.decode
