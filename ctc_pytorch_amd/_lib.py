@@ -127,6 +127,13 @@ _SIGS = {
     "ctcn_spec_augment": (I, [P, P, P, U, U, P, I, I, I, P]),
     "ctcn_spec_augment_plan": (I, [P, U, U, I, I, P, P, P]),
     "ctcn_spec_augment_host": (I, [P, I, I, P, U, U, P]),
+    "ctcn_reverb_limits": (I, [P]),
+    "ctcn_reverb_bank_bytes": (Z, [I, I, I, I, I]),
+    "ctcn_reverb_bank": (I, [P, P, I, I, P, P, I, I, P, I, D, P, Z]),
+    "ctcn_reverb_plan": (I, [P, P, U, U, P]),
+    "ctcn_reverb_ws_bytes": (Z, [P, I, I]),
+    "ctcn_reverb": (I, [P, I, P, P, P, P, U, U, P, I, I, P, Z, P]),
+    "ctcn_reverb_host": (I, [P, I, I, P, P, U, U, P]),
     "ctcn_cmvn_accumulate_ws_bytes": (Z, [I, I, I]),
     "ctcn_cmvn_accumulate": (I, [P, P, P, I, I, I, P, Z, P]),
     "ctcn_comm_unique_id": (I, [P]),
@@ -200,6 +207,11 @@ class SpecAugOpts(ctypes.Structure):
     """ctcn_specaug_opts of include/ctcn.h: time warp, frequency masks and time masks (utils/features.SpecAugment fills it)."""
     _fields_ = [(k, ctypes.c_int32) for k in ("warp_window", "num_freq_masks", "freq_width", "num_time_masks", "time_width")] + \
                [(k, ctypes.c_float) for k in ("time_ratio", "fill")]
+
+
+class ReverbOpts(ctypes.Structure):
+    """ctcn_reverb_opts of include/ctcn.h: the two probabilities and the output normalisation (utils/features.Reverberate fills it)."""
+    _fields_ = [("rir_prob", ctypes.c_float), ("noise_prob", ctypes.c_float), ("normalize", ctypes.c_int32)]
 
 
 def sources():

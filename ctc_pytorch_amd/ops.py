@@ -2273,6 +2273,150 @@ def spec_augment(feats, frames, seed, utt_offset=0, **opts):
     return out
 
 
+# reverberation and additive noise on the waveform (reverb.hip): multi-condition data in front of the feature kernels
+REVERB_LIMIT_FIELDS = ("tile", "tap_chunk", "power_chunk", "max_taps", "max_snrs", "run")
+
+
+def reverb_limits():
+    """The constants of reverb.hip (ctcn_reverb_limits): outputs per tile, taps per staged chunk, elements per power-sum chunk, the longest
+    impulse response, the most SNRs, outputs per lane.  No device."""
+    buf = (ctypes.c_int32 * len(REVERB_LIMIT_FIELDS))()
+    _lib.check(_lib.lib().ctcn_reverb_limits(buf), "reverb_limits")
+    return dict(zip(REVERB_LIMIT_FIELDS, (int(v) for v in buf)))
+
+
+def _rows(who, what, arrays):
+    """A list of 1-D arrays as (padded (rows, stride) float32, lengths int32); int16 rows are converted exactly."""
+    rows = [np.ascontiguousarray(a, dtype=np.float32) for a in arrays]
+    if any(r.ndim != 1 for r in rows):
+        raise ValueError("ctc_pytorch_amd.%s: every %s must be a 1-D array" % (who, what))
+    lens = np.asarray([r.shape[0] for r in rows], dtype=np.int32)
+    out = np.zeros((len(rows), max([1] + [int(v) for v in lens])), dtype=np.float32)
+    for i, r in enumerate(rows):
+        out[i, :r.shape[0]] = r
+    return out, lens
+
+
+class ReverbBank(object):
+    """The bank reverberate draws from (ctcn_reverb_bank): `rirs` and `noises`, lists of 1-D arrays (float32, or int16 converted exactly) on
+    the scale of the waveforms they will meet, `snrs` the SNRs in dB a noise is added at (at most 16).  Either list may be empty.  Built on
+    the host when the object is made -- the noise powers P_m, every impulse response's peak and early window, G_j = 10^(-snr_j / 10) -- with
+    a RuntimeError here, before any launch, for what the kernel does not take (an empty row, an impulse response beyond `reverb_limits()
+    ["max_taps"]`, more than 16 SNRs, a value that is not finite); uploaded once per device, at once when `device` is given.  `host` is the
+    block as uint32 words (layout in include/ctcn.h); `rir_meta` (R, 4) = (K, peak, lo, hi), `noise_len` (N), `noise_power` (N), `snr_gain`
+    (J) are numpy views of it."""
+
+    def __init__(self, rirs, noises, sample_frequency, snrs=(20, 15, 10, 5, 0), device=None):
+        L = _lib.lib()
+        h, hl = _rows("ReverbBank", "impulse response", rirs)
+        q, ql = _rows("ReverbBank", "noise", noises)
+        self.R, self.N = len(hl), len(ql)
+        self.snrs = np.asarray([float(v) for v in snrs], dtype=np.float64)
+        self.J = int(self.snrs.shape[0]) if self.N else 0
+        self.sample_frequency = float(sample_frequency)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None      # noqa: E731
+        nbytes = L.ctcn_reverb_bank_bytes(self.R, h.shape[1] if self.R else 0, self.N, q.shape[1] if self.N else 0, self.J)
+        buf = np.zeros(max(nbytes // 4, 16), dtype=np.uint32)
+        _lib.check(L.ctcn_reverb_bank(ptr(h) if self.R else None, ptr(hl), self.R, h.shape[1] if self.R else 0, ptr(q) if self.N else None, ptr(ql),
+                                      self.N, q.shape[1] if self.N else 0, ptr(self.snrs) if self.J else None, self.J, self.sample_frequency,
+                                      buf.ctypes.data_as(ctypes.c_void_p), nbytes), "reverb_bank")
+        self.host = buf
+        w = buf.view(np.int32)
+        self.rir_stride, self.noise_stride, self.max_early = int(w[4]), int(w[5]), int(w[6])
+        self.rir_meta = w[w[8]:w[8] + 4 * self.R].reshape(self.R, 4)
+        self.noise_len = w[w[9]:w[9] + self.N]
+        dbl = buf[w[10]:w[10] + 2 * (self.N + 16)].view(np.float64)
+        self.noise_power, self.snr_gain = dbl[:self.N], dbl[self.N:self.N + self.J]
+        self._dev = {}
+        if device is not None:
+            self.on(torch.device(device))
+
+    def on(self, device):
+        """The block in the memory of `device`, uploaded on first use."""
+        key = (device.type, device.index)
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.host.view(np.int32)).to(device)
+        return t
+
+    def _host_ptr(self):
+        return self.host.ctypes.data_as(ctypes.c_void_p)
+
+
+def _reverb_opts(who, rir_prob, noise_prob, normalize):
+    return _lib.ReverbOpts(rir_prob=float(rir_prob), noise_prob=float(noise_prob), normalize=int(bool(normalize)))
+
+
+def _reverb_bank(who, bank):
+    if not isinstance(bank, ReverbBank):
+        raise TypeError("ctc_pytorch_amd.%s: expected a ReverbBank, got %s" % (who, type(bank).__name__))
+    return bank
+
+
+def reverb_plan(bank, seed, utt_index, rir_prob=1.0, noise_prob=1.0):
+    """The draws reverberate makes for utterance `utt_index` under `seed` (ctcn_reverb_plan): {"rir": r or None, "noise": m or None,
+    "snr": the index into bank.snrs or None, "offset": the first noise sample or None}.  Host arithmetic, no device."""
+    bank = _reverb_bank("reverb_plan", bank)
+    o = _reverb_opts("reverb_plan", rir_prob, noise_prob, True)
+    d = (ctypes.c_int32 * 4)()
+    _lib.check(_lib.lib().ctcn_reverb_plan(bank._host_ptr(), ctypes.byref(o), int(seed) & _U64, int(utt_index) & _U64, d), "reverb_plan")
+    noise = d[1] >= 0
+    return {"rir": int(d[0]) if d[0] >= 0 else None, "noise": int(d[1]) if noise else None, "snr": int(d[2]) if noise else None,
+            "offset": int(d[3]) if noise else None}
+
+
+def reverberate_host(wave_np, bank, seed, utt_index, rir_prob=1.0, noise_prob=1.0, normalize=True):
+    """reverberate for ONE utterance on the host (ctcn_reverb_host: the draw, gain, mix and scale code the kernels are compiled from):
+    wave_np (n) int16 or float32 numpy -> a new (n) float32 array.  No device."""
+    bank = _reverb_bank("reverberate_host", bank)
+    x = np.ascontiguousarray(wave_np)
+    if x.dtype != np.int16:
+        x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 1:
+        raise ValueError("ctc_pytorch_amd.reverberate_host: expected wave (n), got %s" % (x.shape,))
+    n = x.shape[0]
+    o = _reverb_opts("reverberate_host", rir_prob, noise_prob, normalize)
+    out = np.zeros(n, dtype=np.float32)
+    _lib.check(_lib.lib().ctcn_reverb_host(x.ctypes.data_as(ctypes.c_void_p) if n else None, int(x.dtype == np.int16), n, bank._host_ptr(),
+                                           ctypes.byref(o), int(seed) & _U64, int(utt_index) & _U64, out.ctypes.data_as(ctypes.c_void_p) if n else None),
+               "reverberate_host")
+    return out
+
+
+def reverberate(wave, lengths, bank, seed, utt_offset=0, rir_prob=1.0, noise_prob=1.0, normalize=True):
+    """Reverberation and additive noise of a padded batch of waveforms (ctcn_reverb; the computation, step by step, in include/ctcn.h): wave
+    (B, Nmax) float32 or int16, lengths (B) samples -- a list or a device tensor, clamped to [0, Nmax]; samples at or beyond them are never
+    read and come out as zeros.  Utterance b draws from (seed, utt_offset + b) alone: with probability rir_prob one impulse response of
+    the bank is convolved into it, with probability noise_prob one noise of the bank, from a drawn offset and repeated as often as needed,
+    is added at one of the bank's SNRs against the early part of the reverberated signal; normalize scales the result back to the
+    input's power.  Returns out (B, Nmax) float32 on the input's scale, a new tensor.  No autograd; device tensors only (no CPU
+    fallback)."""
+    bank = _reverb_bank("reverberate", bank)
+    if not torch.is_tensor(wave) or wave.dim() != 2:
+        raise ValueError("ctc_pytorch_amd.reverberate: expected wave (B, Nmax), got %s" % (tuple(wave.shape) if torch.is_tensor(wave) else type(wave).__name__,))
+    _need_gpu(wave, lengths if torch.is_tensor(lengths) else None)
+    if wave.dtype not in (torch.float32, torch.int16):
+        raise TypeError("ctc_pytorch_amd.reverberate: expected float32 or int16 samples, got %s" % wave.dtype)
+    B, Nmax = wave.shape
+    dev = wave.device
+    if torch.is_tensor(lengths):
+        lens = lengths.to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        lens = torch.as_tensor([int(v) for v in lengths], dtype=torch.int32).to(dev)
+    if lens.numel() != B or B == 0:
+        raise ValueError("ctc_pytorch_amd.reverberate: %d lengths for a batch of %d" % (lens.numel(), B))
+    o = _reverb_opts("reverberate", rir_prob, noise_prob, normalize)
+    L = _lib.lib()
+    wave = wave.contiguous()
+    out = torch.empty((B, Nmax), dtype=torch.float32, device=dev)
+    need = L.ctcn_reverb_ws_bytes(bank._host_ptr(), B, Nmax)
+    ws = _lib.workspace(dev, nbytes=max(need, 8), tag="reverb")
+    _lib.check(L.ctcn_reverb(_ptr(wave) if Nmax else None, int(wave.dtype == torch.int16), _ptr(lens), bank._host_ptr(), _ptr(bank.on(dev)),
+                             ctypes.byref(o), int(seed) & _U64, int(utt_offset) & _U64, _ptr(out) if Nmax else None, B, Nmax, _ptr(ws), ws.numel(),
+                             _lib.stream_ptr()), "reverberate")
+    return out
+
+
 def cmvn_accumulate(feats, frames, stats):
     """Adds the rows t < frames[b] of feats (B, Tmax, F) float32 to stats (2, F + 1) float64 on the device, Kaldi's CMVN statistics layout
     (sums | count; sums of squares | 0): ctcn_cmvn_accumulate.  Rows at or beyond frames[b] are never read; float64 partial sums combined

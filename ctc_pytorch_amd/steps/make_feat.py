@@ -10,6 +10,7 @@ deviation, so --compute-cmvn and --cmvn-stats are refused.
     make_feat.py --conf fbank.conf --wav-scp train/wav.scp --out-dir DIR [--cmvn-stats FILE] [--compute-cmvn]
                  [--feat-type {fbank,mfcc,spectrogram,logspec}] [--speed-perturb 0.9,1.0,1.1] [--text FILE]
                  [--delta-order N [--delta-window W]]
+                 [--reverb-copies N --rir-list FILE --noise-list FILE [--snrs 20,15,10,5,0] [--rir-prob P] [--noise-prob P] [--reverb-seed S]]
 
 wav.scp: one `<utterance> <path>` per line (RIFF PCM-16 mono or uncompressed SPHERE; piped commands are not run).  Writes DIR/feats.ark and
 DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDataset and both drivers read them unchanged.
@@ -20,12 +21,21 @@ DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDatase
                    sp<factor as typed>-<utterance>, in wav.scp order with the factors in the order given; factor f resamples on the device
                    from round(rate * f) to the configured rate (utils/features.SpeedPerturb), 1.0 resamples nothing; --compute-cmvn
                    accumulates over all copies
-  --text           with --speed-perturb: the label file the loader reads (`<utterance> <labels>` lines), rewritten to DIR/text with the same
+  --text           with --speed-perturb or --reverb-copies: the label file the loader reads (`<utterance> <labels>` lines), rewritten to DIR/text with the same
                    key prefixes -- SpeechDataset looks labels up by key, so a perturbed archive needs it
   --delta-order    Kaldi's add-deltas (its option names; --delta-window defaults to 2): N orders of delta features are appended to every frame,
                    13 cepstra becoming the usual 39 with N = 2.  As in Kaldi's pipelines they are taken AFTER the normalisation, from the
                    normalised base features, on the device (utils/features.FrameContext with no splice); the CMVN statistics are those of
                    the base features.  0 (the default): none
+  --reverb-copies  multi-condition data (Kaldi's reverberate_data_dir.py / wav-reverberate; utils/features.Reverberate): next to every
+                   utterance N copies with a room impulse response convolved in and background noise added, under the keys rev1-<utterance>
+                   .. revN-<utterance> -- after resampling and speed perturbation, so rev1-sp0.9-<utterance> exists when both are on.
+                   --rir-list / --noise-list (at least one): files naming one wave per line (`<path>` or `<name> <path>`, what read_wave
+                   opens; resampled to the configured rate where they differ) on the scale of the data.  With probability --rir-prob
+                   (default 1) one impulse response is convolved into a copy, with probability --noise-prob (default 1) one noise is
+                   added at one of --snrs (dB, at most 16, default 20,15,10,5,0); a copy keeps its utterance's power and length.  The
+                   draws are keyed by --reverb-seed and the copy's place in the length-sorted list, copy k continuing the count of
+                   copy k - 1.  --text repeats the labels under the new keys; --compute-cmvn accumulates over the copies too
 A file whose sample rate differs from the configuration's is resampled on the device first (utils/features.Resampler, one plan per rate) when
 the conf file holds Kaldi's --allow-downsample (file rate above the configured one) / --allow-upsample (below); otherwise it is an error.
 Utterances are sorted by length and batched under --max-samples padded samples per launch.  Dither is the conf file's (Kaldi's default is
@@ -43,7 +53,7 @@ if _ROOT not in sys.path:
 
 from ctc_pytorch_amd.utils.data_loader import write_kaldi_ark  # noqa: E402
 from ctc_pytorch_amd.utils.features import (Fbank, FbankConfig, FrameContext, GlobalCMVN, LogSpecConfig, LogSpectrum, Mfcc, MfccConfig,  # noqa: E402
-                                            Spectrogram, Resampler, SpectrogramConfig, read_wave)
+                                            Reverberate, Spectrogram, Resampler, SpectrogramConfig, read_wave)
 
 FEAT_TYPES = {"fbank": (FbankConfig, Fbank), "mfcc": (MfccConfig, Mfcc), "spectrogram": (SpectrogramConfig, Spectrogram),
               "logspec": (LogSpecConfig, LogSpectrum)}
@@ -114,6 +124,71 @@ def perturb_text(lines, factors):
     return out
 
 
+def parse_snrs(text):
+    """--snrs' value: at most 16 finite numbers of dB, in the order given."""
+    try:
+        out = [float(part) for part in text.split(",")]
+    except ValueError:
+        out = []
+    if not out or len(out) > 16 or any(v != v or abs(v) == float("inf") for v in out):
+        raise ValueError("--snrs: expected 1 to 16 finite SNRs in dB separated by commas (20,15,10,5,0), got %r" % text)
+    return out
+
+
+def reverb_keys(keys, copies):
+    """The keys of a list with reverberated copies: every key followed by rev1-<key> .. rev<copies>-<key>; 0 copies: the list as it is."""
+    return [k for key in keys for k in [key] + ["rev%d-%s" % (c, key) for c in range(1, copies + 1)]]
+
+
+def rewrite_text(lines, factors, copies):
+    """The lines of a label file for the keys of the archive: perturb_text's lines, each followed by its reverberated copies' lines."""
+    out = []
+    for line in perturb_text(lines, factors):
+        parts = line.rstrip("\n").split(None, 1)
+        for key in reverb_keys([parts[0]], copies):
+            out.append(key + (" " + parts[1] if len(parts) > 1 else "") + "\n")
+    return out
+
+
+def read_wave_list(path, target, device, max_samples):
+    """The waves a list file names, one per line as `<path>` or `<name> <path>`, as arrays at `target` Hz: int16 as read, or float32 where
+    the file's rate differs and the wave went through the Resampler."""
+    paths = []
+    with open(path) as f:
+        for line in f:
+            parts = line.split()
+            if parts:
+                paths.append(parts[-1])
+    if not paths:
+        raise ValueError("%s: no waves" % path)
+    waves, rates = [], []
+    for p in paths:
+        samples, rate = read_wave(p)
+        if samples.shape[0] < 1:
+            raise ValueError("%s: %s holds no samples" % (path, p))
+        waves.append(samples)
+        rates.append(int(rate))
+    if any(r != target for r in rates):
+        waves = resample_waves(waves, rates, target, device, max_samples)
+    return waves
+
+
+def reverberate_waves(reverb, waves, copies, max_samples):
+    """`copies` reverberated copies of every waveform: [copy 1 of all, copy 2 of all, ...] as float32 arrays, in length-sorted batches; the
+    running utterance index of `reverb` follows the batches."""
+    out = []
+    batches = length_batches([w.shape[0] for w in waves], max_samples)
+    for _ in range(copies):
+        done = [None] * len(waves)
+        for idx in batches:
+            res, lens = reverb([waves[i] for i in idx])
+            host = res.cpu().numpy()
+            for b, i in enumerate(idx):
+                done[i] = host[b, :lens[b]].copy()
+        out.append(done)
+    return out
+
+
 def source_rate(utt, path, rate, config):
     """The rate a file is to be read at: its own, after the check of Kaldi's binaries -- a rate other than the configuration's needs
     allow_downsample (file rate higher) or allow_upsample (lower) in the configuration, else ValueError."""
@@ -180,17 +255,39 @@ def main(argv=None, log=print):
     ap.add_argument("--seed", type=int, default=0, help="dither seed")
     ap.add_argument("--speed-perturb", default=None, metavar="FACTORS", help="comma-separated speed factors (Kaldi's 0.9,1.0,1.1): every utterance "
                     "once per factor under the key sp<factor>-<utterance>")
-    ap.add_argument("--text", default=None, help="with --speed-perturb: label file to rewrite to OUT_DIR/text with the perturbed keys")
+    ap.add_argument("--text", default=None, help="with --speed-perturb or --reverb-copies: label file to rewrite to OUT_DIR/text with the new keys")
     ap.add_argument("--delta-order", type=int, default=0, help="append this many orders of delta features (Kaldi's add-deltas; 0: none)")
     ap.add_argument("--delta-window", type=int, default=2, help="add-deltas' window: the delta filter reaches this many frames to either side")
+    ap.add_argument("--reverb-copies", type=int, default=None, metavar="N", help="write N reverberated / noisy copies of every utterance under "
+                    "the keys rev<k>-<utterance> (needs --rir-list or --noise-list)")
+    ap.add_argument("--rir-list", default=None, metavar="FILE", help="room impulse responses: one wave file per line")
+    ap.add_argument("--noise-list", default=None, metavar="FILE", help="background noises: one wave file per line")
+    ap.add_argument("--snrs", default=None, help="comma-separated SNRs in dB a noise is added at (default 20,15,10,5,0)")
+    ap.add_argument("--rir-prob", type=float, default=None, help="probability that a copy is reverberated (default 1)")
+    ap.add_argument("--noise-prob", type=float, default=None, help="probability that a copy gets noise (default 1)")
+    ap.add_argument("--reverb-seed", type=int, default=None, help="seed of the copies' draws (default 0)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
 
     if args.feat_type == "logspec" and (args.compute_cmvn or args.cmvn_stats):
         raise ValueError("--feat-type logspec normalises every utterance by its own mean and standard deviation (normalize in --conf): "
                          "--compute-cmvn and --cmvn-stats do not apply to it")
-    if args.text and not args.speed_perturb:
-        raise ValueError("--text rewrites the label file for --speed-perturb's keys: it needs --speed-perturb")
+    reverb_given = [n for n in ("rir_list", "noise_list", "snrs", "rir_prob", "noise_prob", "reverb_seed") if getattr(args, n) is not None]
+    copies = args.reverb_copies or 0
+    if args.reverb_copies is not None and args.reverb_copies < 1:
+        raise ValueError("--reverb-copies takes a positive count, got %d" % args.reverb_copies)
+    if copies and not (args.rir_list or args.noise_list):
+        raise ValueError("--reverb-copies needs --rir-list or --noise-list")
+    if reverb_given and not copies:
+        raise ValueError("--%s belongs to --reverb-copies, which is not given" % reverb_given[0].replace("_", "-"))
+    if args.snrs is not None and not args.noise_list:
+        raise ValueError("--snrs belongs to --noise-list, which is not given")
+    snrs = parse_snrs(args.snrs if args.snrs is not None else "20,15,10,5,0")
+    rir_prob, noise_prob = (1.0 if p is None else p for p in (args.rir_prob, args.noise_prob))
+    if not (0.0 <= rir_prob <= 1.0 and 0.0 <= noise_prob <= 1.0):
+        raise ValueError("--rir-prob and --noise-prob are probabilities, got %g and %g" % (rir_prob, noise_prob))
+    if args.text and not (args.speed_perturb or copies):
+        raise ValueError("--text rewrites the label file for the keys of --speed-perturb or --reverb-copies: it needs one of them")
     if not 0 <= args.delta_order <= 2 or not 1 <= args.delta_window <= 5:
         raise ValueError("--delta-order takes 0, 1 or 2 and --delta-window 1 to 5, got %d and %d" % (args.delta_order, args.delta_window))
     deltas = FrameContext(delta_order=args.delta_order, delta_window=args.delta_window) if args.delta_order else None
@@ -215,6 +312,17 @@ def main(argv=None, log=print):
         entries = [(key, path) for utt, path in entries for key in perturbed_keys([utt], factors)]
     if any(float(r) != float(config.sample_frequency) for r in rates):
         waves = resample_waves(waves, rates, int(config.sample_frequency), device, args.max_samples)
+    if copies:                                                         # the copies stand behind their utterance
+        rate = int(config.sample_frequency)
+        if float(config.sample_frequency) != rate:
+            raise ValueError("--reverb-copies needs a whole number of Hz as the configured rate, got %g" % config.sample_frequency)
+        rirs = read_wave_list(args.rir_list, rate, device, args.max_samples) if args.rir_list else []
+        noises = read_wave_list(args.noise_list, rate, device, args.max_samples) if args.noise_list else []
+        reverb = Reverberate((rirs, noises, rate, snrs), rir_prob=rir_prob, noise_prob=noise_prob, seed=args.reverb_seed or 0, device=device)
+        made = reverberate_waves(reverb, waves, copies, args.max_samples)
+        waves = [w for i, clean in enumerate(waves) for w in [clean] + [made[c][i] for c in range(copies)]]
+        entries = [(key, path) for utt, path in entries for key in reverb_keys([utt], copies)]
+        log("made %d reverberated copies of %d utterances from %d impulse responses and %d noises" % (copies, len(made[0]), len(rirs), len(noises)))
     batches = length_batches([w.shape[0] for w in waves], args.max_samples)
     os.makedirs(args.out_dir, exist_ok=True)
 
@@ -238,7 +346,7 @@ def main(argv=None, log=print):
                                                                           fbank.feat_dim if deltas is None else deltas.out_dim(fbank.feat_dim), ark))
     if args.text:
         with open(args.text) as f:
-            lines = perturb_text(f.readlines(), factors)
+            lines = rewrite_text(f.readlines(), factors, copies)
         with open(os.path.join(args.out_dir, "text"), "w") as f:
             f.writelines(lines)
         log("wrote %d label lines to %s" % (len(lines), os.path.join(args.out_dir, "text")))

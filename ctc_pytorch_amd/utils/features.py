@@ -17,6 +17,8 @@ binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --conf
                 device (ops.frame_context) -- what utils/data_loader.py does per utterance on the host; its output is the model's input
   SpecAugment   the online augmentation between the two: time warp, frequency masks and time masks of the base batch (ops.spec_augment),
                 redrawn for every utterance of every epoch from (seed, running utterance index)
+  Reverberate   multi-condition data on the waveform, in front of any of the front-ends: a room impulse response convolved into the utterance
+                and background noise added at a drawn SNR (ops.reverberate; Kaldi's wav-reverberate), drawn from (seed, running index)
   read_wave     RIFF PCM-16 mono and uncompressed NIST SPHERE (TIMIT's) -> int16 samples
 
 Not here: pitch, VTLN, per-speaker CMVN, compressed SPHERE."""
@@ -398,6 +400,37 @@ class SpecAugment(object):
         if utt_offset is None:
             self.index += int(feats.shape[0])
         return out
+
+
+class Reverberate(object):
+    """Multi-condition data on the waveform (ops.reverberate; Kaldi's wav-reverberate): with probability rir_prob one room impulse response
+    of the bank is convolved into an utterance, with probability noise_prob one noise of the bank is added at one of its SNRs, and
+    normalize keeps the utterance's power.  `bank`: an ops.ReverbBank, or (rirs, noises, sample_frequency[, snrs]) to build one from lists
+    of 1-D arrays on the waveforms' scale.  Utterance number i of the stream draws from (seed, i) alone: the object keeps the running index
+    -- start_index, advanced by B at every call without utt_offset -- as SpecAugment does.  The result is float32 on the input's scale:
+    any front-end takes it as its waveform batch."""
+
+    def __init__(self, bank, rir_prob=1.0, noise_prob=1.0, normalize=True, seed=0, device="cuda:0", start_index=0):
+        self.device = torch.device(device)
+        self.bank = bank if isinstance(bank, ops.ReverbBank) else ops.ReverbBank(*bank)
+        self.rir_prob, self.noise_prob, self.normalize = float(rir_prob), float(noise_prob), bool(normalize)
+        self.seed, self.index = int(seed), int(start_index)
+        ops.reverb_plan(self.bank, self.seed, 0, self.rir_prob, self.noise_prob)       # (the probabilities' limits, before any launch)
+
+    def plan(self, utt_index):
+        """The draws of utterance utt_index (ops.reverb_plan; no device)."""
+        return ops.reverb_plan(self.bank, self.seed, utt_index, self.rir_prob, self.noise_prob)
+
+    def __call__(self, waves, lengths=None, utt_offset=None):
+        """waves as Fbank takes them: a list of 1-D waveforms, or a padded (B, Nmax) batch with `lengths`.  Utterance b is number
+        utt_offset + b of the stream; without utt_offset, the running index, which then advances by B.  Returns (out (B, Nmax) float32
+        zero-padded on the device, lengths): any front-end's (waves, lengths) form."""
+        waves, lengths = _batch("Reverberate", waves, lengths)
+        out = ops.reverberate(waves.to(self.device), lengths, self.bank, self.seed, self.index if utt_offset is None else utt_offset,
+                              rir_prob=self.rir_prob, noise_prob=self.noise_prob, normalize=self.normalize)
+        if utt_offset is None:
+            self.index += int(out.shape[0])
+        return out, lengths
 
 
 class GlobalCMVN(object):

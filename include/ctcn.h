@@ -858,6 +858,78 @@ int ctcn_spec_augment(const float *feats, const int32_t *frames, const ctcn_spec
 int ctcn_spec_augment_plan(const ctcn_specaug_opts *opts, uint64_t seed, uint64_t utt_index, int T, int F, int32_t *warp, int32_t *freq,
                            int32_t *time);
 int ctcn_spec_augment_host(const float *feats, int T, int F, const ctcn_specaug_opts *opts, uint64_t seed, uint64_t utt_index, float *out);
+/* Reverberation and additive noise on the waveform (reverb.hip): multi-condition data, the one augmentation that touches the samples
+ * themselves -- a room impulse response (RIR) convolved into the utterance and background noise added at a drawn signal-to-noise ratio
+ * (SNR).  The project's own definition, modelled on Kaldi's wav-reverberate with --shift-output=false --normalize-output=true (one RIR, one
+ * background noise repeated over the whole utterance, the SNR taken against the early part of the reverberated signal); host, device and a
+ * numpy restatement agree bit for bit.
+ * Inputs: utterance b of a padded batch wave (B, Nmax), float32 or int16 (converted to float32 exactly, as ctcn_resample does), has
+ * n = clamp(lens[b], 0, Nmax) samples x[0 .. n) and the 64-bit running index u = utt_offset + b; a bank of R impulse responses h_r[0 .. K_r)
+ * and N noises q_m[0 .. L_m), float32, and of J <= 16 SNRs in dB.  Either bank may be empty (not both); a row with K_r < 1 or L_m < 1, or
+ * with a value that is not finite, is refused.
+ *   Power sum S(v) of a float32 vector of len elements, in float64 ((double) v[i] squared is exact there): the elements are cut into chunks of
+ *   1024 consecutive ones, the last chunk filled with zeros; a chunk is reduced by the halving tree t[j] += t[j + 512] for j < 512, then
+ *   t[j] += t[j + 256] for j < 256, ... down to t[0] += t[1]; the chunk sums t[0] are added in ascending order, starting from 0.  The value
+ *   depends on the vector alone -- not on the grid, the batch or a tile -- and no floating-point atomic is involved.
+ *   Draws, integer arithmetic only, philox4 and rnd(word, n) as for ctcn_spec_augment: draw 0 = philox4(seed, (u << 8) | 0): reverberation
+ *   is on if R > 0 and rnd(w0, 1 << 24) < floor((double) rir_prob * 2^24), and then r = rnd(w1, R); draw 1 = philox4(seed, (u << 8) | 1): noise
+ *   is on if N > 0 and rnd(w0, 1 << 24) < floor((double) noise_prob * 2^24), and then m = rnd(w1, N), the SNR index j = rnd(w2, J) and the
+ *   offset off = rnd(w3, L_m).
+ *   Fixed once per bank, on the host (ctcn_reverb_bank): per noise row P_m = S(q_m) / L_m; per RIR the peak p = the first index of the
+ *   largest value of h_r and the early window [lo, hi) with lo = max(0, p - floor(0.001 fs)), hi = min(K, p + floor(0.05 fs)) (fs =
+ *   sample_frequency, the products in double; an empty window -- fs below 20 Hz -- is refused); per SNR G_j = pow(10, -snr_j / 10) in double
+ *   from the host's pow: no pow runs on the device.
+ * Per utterance:
+ *   1. P_in = S(x) / n.
+ *   2. With an RIR: y[i] = fl32(sum_{k = 0 .. min(i, K - 1)} (double) h[k] * (double) x[i - k]) for i in [0, n), k ascending, the sum
+ *      starting from +0.0 (a float32 x float32 product is exact in float64, so the sum is one number with or without fused multiply-adds;
+ *      a result of zero is +0.0); the early signal e = x * h[lo .. hi) over its FULL length n + (hi - lo) - 1, by the same sum (only taps
+ *      that meet a sample take part) and the same rounding; P_sig = S(e) / len(e).  Without an RIR: y = x and P_sig = P_in.
+ *   3. With a noise row whose P_m > 0: g = sqrt((G_j * P_sig) / P_m) and z[i] = fl32((double) y[i] + g * (double) q[(off + i) mod L_m]) --
+ *      the multiplication, the division, the square root, the product and the sum are float64 operations rounded one by one (no fused
+ *      multiply-add on the device or the host).  Otherwise (noise off, or an all-zero row) z = y.
+ *   4. With normalize: if P_out = S(z) / n > 0, s = sqrt(P_in / P_out) and out[i] = fl32(s * (double) z[i]); otherwise out = z.
+ *   5. out[n .. Nmax) are zeros; nothing behind an utterance in its padded row, or behind a bank row's length, is ever read; n = 0 gives
+ *      a row of zeros.
+ * With both probabilities 0 the output has the input's bits (s = sqrt(P / P) = 1).  An utterance's result
+ * depends on (seed, u, the options, the bank, its own samples) alone, not on B, Nmax or its neighbours.
+ * The bank block (host, 4-byte words, 8-byte aligned): [0, 16) int32 a tag, R, N, J, the RIR row stride, the noise row stride, the longest
+ * early window, 0, then the word offsets of the four tables and the block's size; R x (K, p, lo, hi) int32; N x L_m int32; (8-byte
+ * aligned) N float64 P_m and 16 float64 G_j; R x stride float32 the impulse responses, zeros behind K; N x stride float32 the noises.
+ * ctcn_reverb_bank_bytes: the block's size, 0 for shapes ctcn_reverb_bank refuses.  ctcn_reverb_bank: rirs (R, rir_stride) and noises
+ * (N, noise_stride) padded rows on the HOST with their lengths; builds the block (no HIP call).
+ * ctcn_reverb_plan: the draws of ONE utterance on the host from the host block: draws[4] = r or -1, m or -1, j, off (0, 0 without noise).
+ * ctcn_reverb: wave, lens (B) int32, out (B, Nmax) float32 and ws in DEVICE memory, bank_host the block on the host (its header is read
+ * there), bank_dev its copy in device memory; out must not alias wave.  Launches on the caller's stream, a launch boundary in front of each
+ * phase that needs a sum over a whole utterance, no grid-wide barrier, no flag, no host synchronisation: the convolution (grid: tiles of
+ * 2048 outputs and of the early signal x B; taps staged in LDS 1024 at a time, ascending, every lane owning eight consecutive outputs
+ * with the input window sliding through its registers; the early signal is reduced to its power sums and never stored), the per-utterance
+ * sums (P_in, P_sig, g), the noise addition with the sums of z^2, the sum to s, the scaling -- the last three only where the options need
+ * them.  ws: ctcn_reverb_ws_bytes(bank_host, B, Nmax) bytes, 8-byte aligned (0 for bad arguments); too small: CTCN_EWORKSPACE.
+ * ctcn_reverb_host: the same computation for ONE utterance on the HOST (no HIP call; works without a GPU), through the draw, gain, mix and
+ * scale functions the kernels are compiled from: out (num_samples).
+ * ctcn_reverb_limits: out[6] = outputs per tile (2048), taps per staged chunk (1024), elements per power-sum chunk (1024), the longest
+ * impulse response (16 384), the most SNRs (16), outputs per lane (8).
+ * Limits, from the bank builder before any launch: CTCN_EUNSUPPORTED for an RIR row stride beyond 16 384 taps, more than 16 SNRs, a noise
+ * row beyond 2^30 samples, more than 2^20 rows; CTCN_EINVAL for NULL, both banks empty, a row length outside [1, stride], a value or an SNR
+ * that is not finite, a noise bank without an SNR, a sample_frequency outside (0, 2^24].  From every entry point that takes the options:
+ * CTCN_EINVAL for NULL or a probability outside [0, 1] (NaN included); from ctcn_reverb and ctcn_reverb_host: CTCN_EINVAL for a block
+ * ctcn_reverb_bank did not build, B outside [1, 65 535], Nmax (num_samples) negative or beyond 2^30. */
+typedef struct ctcn_reverb_opts {
+  float rir_prob, noise_prob;
+  int32_t normalize;
+} ctcn_reverb_opts;
+int ctcn_reverb_limits(int32_t *out);
+size_t ctcn_reverb_bank_bytes(int R, int rir_stride, int N, int noise_stride, int num_snrs);
+int ctcn_reverb_bank(const float *rirs, const int32_t *rir_len, int R, int rir_stride, const float *noises, const int32_t *noise_len, int N,
+                     int noise_stride, const double *snrs, int num_snrs, double sample_frequency, void *bank, size_t bank_bytes);
+int ctcn_reverb_plan(const void *bank, const ctcn_reverb_opts *opts, uint64_t seed, uint64_t utt_index, int32_t *draws);
+size_t ctcn_reverb_ws_bytes(const void *bank_host, int B, int Nmax);
+int ctcn_reverb(const void *wave, int wave_is_int16, const int32_t *lens, const void *bank_host, const void *bank_dev,
+                const ctcn_reverb_opts *opts, uint64_t seed, uint64_t utt_offset, float *out, int B, int Nmax, void *ws, size_t ws_bytes,
+                void *stream);
+int ctcn_reverb_host(const void *wave, int wave_is_int16, int num_samples, const void *bank, const ctcn_reverb_opts *opts, uint64_t seed,
+                     uint64_t utt_index, float *out);
 
 /* ---------------------------------------------------------------------------------------------------
  * CTC prefix beam search with bigram LM; replaces BeamDecoder.decode -> ctcBeamSearch.decode
