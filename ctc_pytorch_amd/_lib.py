@@ -136,6 +136,13 @@ _SIGS = {
     "ctcn_reverb_host": (I, [P, I, I, P, P, U, U, P]),
     "ctcn_cmvn_accumulate_ws_bytes": (Z, [I, I, I]),
     "ctcn_cmvn_accumulate": (I, [P, P, P, I, I, I, P, Z, P]),
+    "ctcn_cmvn_accumulate_groups": (I, [P, P, P, P, I, I, I, I, P, Z, P]),
+    "ctcn_cmvn_apply": (I, [P, P, P, P, P, I, I, I, I, I, P]),
+    "ctcn_cmvn_sliding": (I, [P, P, P, I, I, I, P, P]),
+    "ctcn_cmvn_sliding_run": (I, [P]),
+    "ctcn_cmvn_sliding_window": (I, [I, I, P, P, P]),
+    "ctcn_cmvn_sliding_host": (I, [P, I, I, P, P]),
+    "ctcn_cmvn_norm_host": (I, [P, I, I, P, P]),
     "ctcn_comm_unique_id": (I, [P]),
     "ctcn_comm_init": (I, [P, I, I, ctypes.POINTER(ctypes.c_void_p)]),
     "ctcn_comm_allreduce_sum_f32": (I, [P, P, Z, P]),
@@ -212,6 +219,11 @@ class SpecAugOpts(ctypes.Structure):
 class ReverbOpts(ctypes.Structure):
     """ctcn_reverb_opts of include/ctcn.h: the two probabilities and the output normalisation (utils/features.Reverberate fills it)."""
     _fields_ = [("rir_prob", ctypes.c_float), ("noise_prob", ctypes.c_float), ("normalize", ctypes.c_int32)]
+
+
+class SlidingCmnOpts(ctypes.Structure):
+    """ctcn_sliding_cmn_opts of include/ctcn.h: Kaldi's SlidingWindowCmnOptions (utils/features.SlidingCMVN fills it)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("cmn_window", "min_cmn_window", "normalize_variance", "center")]
 
 
 def sources():

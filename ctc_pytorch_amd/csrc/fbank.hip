@@ -25,6 +25,7 @@
 //   Waves of a workgroup never wait for each other after the staging barrier: the FFT buffers are per wave, ordered by wave_lds_sync.
 // cmvn_partial_kernel / cmvn_finish_kernel: float64 column sums of 64-row blocks into the workspace, then one thread per statistic adds the
 //   partials in index order into the caller's block (norm.hip's scheme: no atomics, a function of the input bits).
+//   cmvn_finish_groups_kernel: the second step per group of utterances (ctcn_cmvn_accumulate_groups; the apply side is cmvn.hip).
 #include <algorithm>
 #include <vector>
 
@@ -287,6 +288,31 @@ __global__ __launch_bounds__(256) void cmvn_finish_kernel(const double *__restri
   }
 }
 
+// The same sums per group of utterances (ctcn_cmvn_accumulate_groups): grid (statistics / 256, groups).  Thread i < 2F of group g adds its
+// column of the partials of the utterances with group[b] == g, in ascending (utterance, block) order, into stats[g]; thread 2F their frame
+// counts in ascending utterance order.  One group holding every utterance: cmvn_finish_kernel's additions in cmvn_finish_kernel's order.
+__global__ __launch_bounds__(256) void cmvn_finish_groups_kernel(const double *__restrict__ ws, const int32_t *__restrict__ frames,
+                                                                 const int32_t *__restrict__ group, double *__restrict__ stats, int B, int Tmax, int F,
+                                                                 int chunks) {
+  const int i = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
+  double *st = stats + (size_t)g * 2 * (F + 1);
+  if (i < 2 * F) {
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) {
+      if (group[b] != g) continue;
+      const double *p = ws + (size_t)b * chunks * 2 * F + i;
+#pragma unroll 8
+      for (int c = 0; c < chunks; ++c) s += p[(size_t)c * 2 * F];   // the loads do not wait for the sum: eight in flight, added in order
+    }
+    st[i < F ? i : i + 1] += s;
+  } else if (i == 2 * F) {
+    double cnt = 0.0;
+    for (int b = 0; b < B; ++b)
+      if (group[b] == g) cnt += (double)min(max(frames[b], 0), Tmax);
+    st[F] += cnt;
+  }
+}
+
 // ---- the recipe's log-magnitude STFT (ctcn_logspec) -------------------------------------------------------------------------------------------
 // logspec_kernel<N>: the filterbank kernel's shape -- grid (frame blocks, utterances), four waves, one wave per frame, the plan and the sample
 //   span of `fpw` (<= 8) neighbouring frames staged once (numpy's reflection and input_scale applied there) -- with P = ceil(N / 64) registers
@@ -524,6 +550,24 @@ extern "C" int ctcn_cmvn_accumulate(const float *feats, const int32_t *frames, d
   hipLaunchKernelGGL(cmvn_partial_kernel, dim3(chunks, B), dim3(256), 0, st, feats, frames, static_cast<double *>(ws), Tmax, F);
   CTCN_LAUNCH_CHECK();
   hipLaunchKernelGGL(cmvn_finish_kernel, dim3(ceil_div(2 * F + 1, 256)), dim3(256), 0, st, static_cast<const double *>(ws), frames, stats, B, Tmax, F, chunks);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_cmvn_accumulate_groups(const float *feats, const int32_t *frames, const int32_t *group, double *stats, int B, int Tmax, int F,
+                                           int G, void *ws, size_t ws_bytes, void *stream) {
+  CTCN_REQUIRE(feats && frames && group && stats && B > 0 && Tmax > 0 && F > 0 && B <= 65535 && G > 0 && G <= 65535,
+               "ctcn_cmvn_accumulate_groups: bad args (B %d and G %d at most 65 535)", B, G);
+  const size_t need = ctcn_cmvn_accumulate_ws_bytes(B, Tmax, F);
+  CTCN_REQUIRE(ws && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)stats & 7) == 0,
+               "ctcn_cmvn_accumulate_groups: workspace of ctcn_cmvn_accumulate_ws_bytes needed, 8-byte aligned");
+  if (ws_bytes < need) { ctcn_set_error("ctcn_cmvn_accumulate_groups: workspace %zu < %zu bytes", ws_bytes, need); return CTCN_EWORKSPACE; }
+  const int chunks = ceil_div(Tmax, CMVN_ROWS);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(cmvn_partial_kernel, dim3(chunks, B), dim3(256), 0, st, feats, frames, static_cast<double *>(ws), Tmax, F);
+  CTCN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cmvn_finish_groups_kernel, dim3(ceil_div(2 * F + 1, 256), G), dim3(256), 0, st, static_cast<const double *>(ws), frames, group,
+                     stats, B, Tmax, F, chunks);
   CTCN_LAUNCH_CHECK();
   return CTCN_OK;
 }

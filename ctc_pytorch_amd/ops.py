@@ -2436,3 +2436,162 @@ def cmvn_accumulate(feats, frames, stats):
     _lib.check(_lib.lib().ctcn_cmvn_accumulate(_ptr(feats), _ptr(frames), _ptr(stats), B, Tmax, F, _ptr(ws), ws.numel(), _lib.stream_ptr()),
                "cmvn_accumulate")
     return stats
+
+
+# normalisation per group of utterances and over a sliding window (fbank.hip, cmvn.hip): Kaldi's per-speaker CMVN and apply-cmvn-sliding
+def _cmvn_batch(who, feats, frames):
+    if not torch.is_tensor(feats) or feats.dim() != 3 or feats.dtype != torch.float32:
+        raise ValueError("ctc_pytorch_amd.%s: expected feats (B, Tmax, F) float32, got %s" % (
+            who, "%s %s" % (tuple(feats.shape), feats.dtype) if torch.is_tensor(feats) else type(feats).__name__))
+    _need_gpu(feats, frames if torch.is_tensor(frames) else None)
+    B = feats.shape[0]
+    if torch.is_tensor(frames):
+        frames = frames.to(device=feats.device, dtype=torch.int32).contiguous()
+    else:
+        frames = torch.as_tensor([int(v) for v in frames], dtype=torch.int32).to(feats.device)
+    if frames.numel() != B:
+        raise ValueError("ctc_pytorch_amd.%s: %d frame counts for a batch of %d" % (who, frames.numel(), B))
+    return frames
+
+
+def _cmvn_groups(who, groups, B, G, device):
+    """Group ids as an int32 device tensor; a host sequence is range-checked here, a device tensor is taken as it is (ids outside [0, G)
+    are skipped by the kernels)."""
+    if torch.is_tensor(groups) and groups.is_cuda:
+        ids = groups.to(device=device, dtype=torch.int32).contiguous()
+    else:
+        host = [int(v) for v in (groups.tolist() if torch.is_tensor(groups) else groups)]
+        bad = [v for v in host if not 0 <= v < G]
+        if bad:
+            raise ValueError("ctc_pytorch_amd.%s: group id %d outside [0, %d)" % (who, bad[0], G))
+        ids = torch.as_tensor(host, dtype=torch.int32).to(device)
+    if ids.numel() != B:
+        raise ValueError("ctc_pytorch_amd.%s: %d group ids for a batch of %d" % (who, ids.numel(), B))
+    return ids
+
+
+def cmvn_accumulate_groups(feats, frames, groups, stats):
+    """Adds the rows t < frames[b] of utterance b of feats (B, Tmax, F) float32 to stats[groups[b]]; stats (G, 2, F + 1) float64 on the device,
+    one Kaldi statistics matrix per group (a speaker; or the utterance itself): ctcn_cmvn_accumulate_groups.  groups: B ids as a host
+    sequence (range-checked here) or a device tensor (an id outside [0, G) contributes nothing).  Rows at or beyond frames[b] are never
+    read; float64 partial sums combined in a fixed order.  Returns stats."""
+    frames = _cmvn_batch("cmvn_accumulate_groups", feats, frames)
+    _need_gpu(stats)
+    B, Tmax, F = feats.shape
+    if stats.dtype != torch.float64 or stats.dim() != 3 or tuple(stats.shape[1:]) != (2, F + 1) or stats.shape[0] < 1 or not stats.is_contiguous():
+        raise ValueError("ctc_pytorch_amd.cmvn_accumulate_groups: expected contiguous float64 stats (G, 2, %d), got %s %s" % (F + 1, tuple(stats.shape), stats.dtype))
+    G = stats.shape[0]
+    ids = _cmvn_groups("cmvn_accumulate_groups", groups, B, G, feats.device)
+    if B == 0 or Tmax == 0:
+        return stats
+    feats = feats.contiguous()
+    need = _lib.lib().ctcn_cmvn_accumulate_ws_bytes(B, Tmax, F)
+    ws = _lib.workspace(feats.device, nbytes=need, tag="cmvn")
+    _lib.check(_lib.lib().ctcn_cmvn_accumulate_groups(_ptr(feats), _ptr(frames), _ptr(ids), _ptr(stats), B, Tmax, F, G, _ptr(ws), ws.numel(),
+                                                      _lib.stream_ptr()), "cmvn_accumulate_groups")
+    return stats
+
+
+def cmvn_apply(feats, frames, stats, groups=None, norm_vars=True, out=None):
+    """(x - mean) * scale with the mean and 1 / stddev of the utterance's group, formed on the device from stats (ctcn_cmvn_apply; the
+    formulas of GlobalCMVN.mean_scale): feats (B, Tmax, F) float32, stats (G, 2, F + 1) float64 or one (2, F + 1) matrix.  groups: B ids
+    (host sequence, range-checked; or device tensor, an id outside [0, G) copies its utterance through); None: group 0 for all.
+    norm_vars False: means only.  Rows at or beyond frames[b] are never read and come out as zeros.  out: a contiguous tensor of
+    feats' shape, which may be feats itself (in place); None: a new tensor.  Returns out."""
+    frames = _cmvn_batch("cmvn_apply", feats, frames)
+    _need_gpu(stats, out)
+    B, Tmax, F = feats.shape
+    if stats.dim() == 2:
+        stats = stats.unsqueeze(0)
+    if stats.dtype != torch.float64 or stats.dim() != 3 or tuple(stats.shape[1:]) != (2, F + 1) or stats.shape[0] < 1 or not stats.is_contiguous():
+        raise ValueError("ctc_pytorch_amd.cmvn_apply: expected contiguous float64 stats (G, 2, %d) or (2, %d), got %s %s" % (F + 1, F + 1, tuple(stats.shape), stats.dtype))
+    G = stats.shape[0]
+    ids = None if groups is None else _cmvn_groups("cmvn_apply", groups, B, G, feats.device)
+    if out is None:
+        out = torch.empty((B, Tmax, F), dtype=torch.float32, device=feats.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Tmax, F) or not out.is_contiguous() or out.device != feats.device:
+        raise ValueError("ctc_pytorch_amd.cmvn_apply: out must be a contiguous float32 tensor of feats' shape %s on its device" % (tuple(feats.shape),))
+    if B == 0 or Tmax == 0 or F == 0:
+        return out
+    if out.data_ptr() == feats.data_ptr() and not feats.is_contiguous():
+        raise ValueError("ctc_pytorch_amd.cmvn_apply: in-place use needs contiguous feats")
+    feats = feats.contiguous()
+    _lib.check(_lib.lib().ctcn_cmvn_apply(_ptr(feats), _ptr(frames), _ptr(ids), _ptr(stats), _ptr(out), B, Tmax, F, G, int(bool(norm_vars)),
+                                          _lib.stream_ptr()), "cmvn_apply")
+    return out
+
+
+def _sliding_opts(cmn_window, min_cmn_window, normalize_variance, center):
+    return _lib.SlidingCmnOpts(cmn_window=int(cmn_window), min_cmn_window=int(min_cmn_window), normalize_variance=int(bool(normalize_variance)),
+                               center=int(bool(center)))
+
+
+def cmvn_sliding_run(cmn_window=600, min_cmn_window=100, normalize_variance=False, center=False):
+    """Frames the sliding-window kernel stages at a time under these options (ctcn_cmvn_sliding_run).  RuntimeError for options the kernel
+    refuses.  No device."""
+    r = _lib.lib().ctcn_cmvn_sliding_run(ctypes.byref(_sliding_opts(cmn_window, min_cmn_window, normalize_variance, center)))
+    if r < 0:
+        _lib.check(r, "cmvn_sliding_run")
+    return r
+
+
+def cmvn_sliding_window(t, n, cmn_window=600, min_cmn_window=100, center=False):
+    """(start, end) of the window of frame t in an utterance of n frames, Kaldi's SlidingWindowCmn rule (ctcn_cmvn_sliding_window).  Host
+    arithmetic, no device.  RuntimeError for bad arguments."""
+    s, e = ctypes.c_int32(), ctypes.c_int32()
+    _lib.check(_lib.lib().ctcn_cmvn_sliding_window(int(t), int(n), ctypes.byref(_sliding_opts(cmn_window, min_cmn_window, False, center)),
+                                                   ctypes.byref(s), ctypes.byref(e)), "cmvn_sliding_window")
+    return s.value, e.value
+
+
+def cmvn_sliding_host(feats_np, cmn_window=600, min_cmn_window=100, normalize_variance=False, center=False, out=None):
+    """cmvn_sliding for ONE utterance on the host (ctcn_cmvn_sliding_host: the arithmetic the kernel is compiled from): feats_np (T, F)
+    float32 numpy -> a (T, F) float32 array (`out`, which must not overlap the input, or a new one).  No device."""
+    x = np.ascontiguousarray(feats_np, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] == 0:
+        raise ValueError("ctc_pytorch_amd.cmvn_sliding_host: expected feats (T, F), got %s" % (x.shape,))
+    T, F = x.shape
+    if out is None:
+        out = np.empty_like(x)
+    elif not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != x.shape or not out.flags.c_contiguous:
+        raise ValueError("ctc_pytorch_amd.cmvn_sliding_host: out must be a contiguous float32 array of shape %s" % (x.shape,))
+    _lib.check(_lib.lib().ctcn_cmvn_sliding_host(x.ctypes.data_as(ctypes.c_void_p) if T else None, T, F,
+                                                 ctypes.byref(_sliding_opts(cmn_window, min_cmn_window, normalize_variance, center)),
+                                                 out.ctypes.data_as(ctypes.c_void_p) if T else None), "cmvn_sliding_host")
+    return out
+
+
+def cmvn_norm_host(stats_np, norm_vars=True):
+    """(mean, scale) float32 arrays of ONE statistics matrix (2, F + 1) on the host (ctcn_cmvn_norm_host: the arithmetic cmvn_apply is
+    compiled from).  No device.  RuntimeError where no frames are accumulated."""
+    s = np.ascontiguousarray(stats_np, dtype=np.float64)
+    if s.ndim != 2 or s.shape[0] != 2 or s.shape[1] < 2:
+        raise ValueError("ctc_pytorch_amd.cmvn_norm_host: expected stats (2, F + 1), got %s" % (s.shape,))
+    F = s.shape[1] - 1
+    mean, scale = np.empty(F, dtype=np.float32), np.empty(F, dtype=np.float32)
+    _lib.check(_lib.lib().ctcn_cmvn_norm_host(s.ctypes.data_as(ctypes.c_void_p), F, int(bool(norm_vars)), mean.ctypes.data_as(ctypes.c_void_p),
+                                              scale.ctypes.data_as(ctypes.c_void_p)), "cmvn_norm_host")
+    return mean, scale
+
+
+def cmvn_sliding(feats, frames, cmn_window=600, min_cmn_window=100, normalize_variance=False, center=False, out=None):
+    """Kaldi's apply-cmvn-sliding on a zero-padded batch in one launch (ctcn_cmvn_sliding; the window rule and the running sums, step by
+    step, in include/ctcn.h): feats (B, Tmax, F) float32, frames (B) the utterances' frame counts -- a list or a device tensor, clamped to
+    [0, Tmax]; rows at or beyond them are never read and come out as zeros.  Options and defaults are Kaldi's.  Returns out (B, Tmax, F)
+    float32: a new tensor, or `out`, which must not overlap feats.  No autograd; device tensors only (no CPU fallback)."""
+    frames = _cmvn_batch("cmvn_sliding", feats, frames)
+    _need_gpu(out)
+    B, Tmax, F = feats.shape
+    opts = _sliding_opts(cmn_window, min_cmn_window, normalize_variance, center)
+    if opts.cmn_window < 1 or not 1 <= opts.min_cmn_window <= opts.cmn_window:
+        raise ValueError("ctc_pytorch_amd.cmvn_sliding: cmn_window >= 1 and 1 <= min_cmn_window <= cmn_window needed, got %d and %d"
+                         % (opts.cmn_window, opts.min_cmn_window))
+    if out is None:
+        out = torch.empty((B, Tmax, F), dtype=torch.float32, device=feats.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, Tmax, F) or not out.is_contiguous() or out.device != feats.device:
+        raise ValueError("ctc_pytorch_amd.cmvn_sliding: out must be a contiguous float32 tensor of feats' shape %s on its device" % (tuple(feats.shape),))
+    if B == 0 or Tmax == 0 or F == 0:
+        return out
+    feats = feats.contiguous()
+    _lib.check(_lib.lib().ctcn_cmvn_sliding(_ptr(feats), _ptr(frames), _ptr(out), B, Tmax, F, ctypes.byref(opts), _lib.stream_ptr()), "cmvn_sliding")
+    return out

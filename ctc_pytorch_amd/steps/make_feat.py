@@ -5,11 +5,12 @@ utils/features.Mfcc, --feat-type spectrogram is feat_type=spectrogram: compute-s
 columns under Kaldi's defaults), with the same global CMVN.  --feat-type logspec is the recipe's own local/make_spectrum.py
 (utils/features.LogSpectrum): --conf holds `--key=value` lines after its audio_conf (sample-rate, window-size, window-stride, window,
 normalize, input-scale; an empty file gives its defaults: 201 columns); it normalises every utterance by its own mean and standard
-deviation, so --compute-cmvn and --cmvn-stats are refused.
+deviation, so every CMVN flag is refused.
 
     make_feat.py --conf fbank.conf --wav-scp train/wav.scp --out-dir DIR [--cmvn-stats FILE] [--compute-cmvn]
                  [--feat-type {fbank,mfcc,spectrogram,logspec}] [--speed-perturb 0.9,1.0,1.1] [--text FILE]
                  [--delta-order N [--delta-window W]]
+                 [--utt2spk FILE | --cmvn-per-utt | --cmvn-sliding [--cmn-window N] [--min-cmn-window N] [--cmn-center]] [--norm-vars true|false]
                  [--reverb-copies N --rir-list FILE --noise-list FILE [--snrs 20,15,10,5,0] [--rir-prob P] [--noise-prob P] [--reverb-seed S]]
 
 wav.scp: one `<utterance> <path>` per line (RIFF PCM-16 mono or uncompressed SPHERE; piped commands are not run).  Writes DIR/feats.ark and
@@ -17,6 +18,18 @@ DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDatase
   --compute-cmvn   two passes: the first accumulates the global statistics on the device and writes them as Kaldi's text matrix
                    (--cmvn-stats, default DIR/global_<feat type>_cmvn.txt), the second writes features normalised with them (in the kernel)
   --cmvn-stats     without --compute-cmvn: statistics to apply (the training set's, for dev and test data); none: raw features
+  --utt2spk        per-speaker CMVN, the normalisation of the standard Kaldi recipes (compute-cmvn-stats --spk2utt, apply-cmvn --utt2spk;
+                   utils/features.SpeakerCMVN): FILE holds one `<utterance> <speaker>` per line; two passes over this list, the first
+                   accumulates one statistics matrix per speaker on the device and writes them as Kaldi's text archive (--cmvn-stats,
+                   default DIR/cmvn.ark.txt), the second normalises every utterance with its speaker's; DIR/utt2spk is written for the keys
+                   of the archive.  A speed-perturbed or reverberated copy gets its speaker prefixed like its key (sp0.9-<speaker>,
+                   rev1-<speaker>: Kaldi's convention), so copies never share statistics with the original
+  --cmvn-per-utt   the same with every utterance its own speaker (apply-cmvn without --utt2spk)
+  --cmvn-sliding   Kaldi's apply-cmvn-sliding (utils/features.SlidingCMVN) under its option names and defaults: --cmn-window 600,
+                   --min-cmn-window 100, --cmn-center; one pass, no statistics file
+  --norm-vars      for the three modes above: normalise the variance too; default true for speakers and utterances (the recipe's
+                   apply-cmvn --norm-vars=true), false for the sliding window (Kaldi's default).  The three modes exclude each other,
+                   --compute-cmvn and, except as the place to write the archive, --cmvn-stats
   --speed-perturb  Kaldi's speed perturbation (utils/perturb_data_dir_speed.sh): every utterance is written once per factor, under the key
                    sp<factor as typed>-<utterance>, in wav.scp order with the factors in the order given; factor f resamples on the device
                    from round(rate * f) to the configured rate (utils/features.SpeedPerturb), 1.0 resamples nothing; --compute-cmvn
@@ -53,7 +66,8 @@ if _ROOT not in sys.path:
 
 from ctc_pytorch_amd.utils.data_loader import write_kaldi_ark  # noqa: E402
 from ctc_pytorch_amd.utils.features import (Fbank, FbankConfig, FrameContext, GlobalCMVN, LogSpecConfig, LogSpectrum, Mfcc, MfccConfig,  # noqa: E402
-                                            Reverberate, Spectrogram, Resampler, SpectrogramConfig, read_wave)
+                                            Reverberate, Spectrogram, Resampler, SlidingCMVN, SpeakerCMVN, SpectrogramConfig, read_utt2spk,
+                                            read_wave)
 
 FEAT_TYPES = {"fbank": (FbankConfig, Fbank), "mfcc": (MfccConfig, Mfcc), "spectrogram": (SpectrogramConfig, Spectrogram),
               "logspec": (LogSpecConfig, LogSpectrum)}
@@ -221,9 +235,21 @@ def resample_waves(waves, source_rates, target, device, max_samples):
     return out
 
 
-def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=None, deltas=None):
+def copy_speakers(keys, bases, utt2spk):
+    """The speaker of every key of the archive: the speaker of its base utterance behind the prefix the key carries in front of it
+    (sp0.9-, rev1-, rev1-sp0.9-: Kaldi's convention for copies).  utt2spk None: every key is its own speaker."""
+    if utt2spk is None:
+        return list(keys)
+    missing = [b for b in bases if b not in utt2spk]
+    if missing:
+        raise ValueError("--utt2spk names no speaker for %s" % missing[0])
+    return [key[:len(key) - len(base)] + utt2spk[base] for key, base in zip(keys, bases)]
+
+
+def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=None, deltas=None, speakers=None, normalise=None):
     """Features of `waves` (list of int16 arrays), batch by batch: {index: (T, F) float32 ndarray}, or -- with `cmvn` -- nothing kept, the raw
-    features accumulated into it.  deltas (a FrameContext without splice or skip): applied to the normalised features that are kept."""
+    features accumulated into it (a SpeakerCMVN: under `speakers`, the speaker of every index).  normalise: called as (feats, frames,
+    indices of the batch) on the features that are kept.  deltas (a FrameContext without splice or skip): applied behind it."""
     mats, place = {}, 0
     for idx in batches:
         if isinstance(fbank, LogSpectrum):                             # normalised per utterance by the call itself; no dither
@@ -232,8 +258,13 @@ def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=Non
             feats, frames = fbank([waves[i] for i in idx], mean=mean, scale=scale, seed=seed, utt_offset=place)
         place += len(idx)
         if cmvn is not None:
-            cmvn.accumulate(feats, frames)
+            if speakers is not None:
+                cmvn.accumulate(feats, frames, [speakers[i] for i in idx])
+            else:
+                cmvn.accumulate(feats, frames)
             continue
+        if normalise is not None:
+            feats = normalise(feats, frames, idx)
         if deltas is not None:
             feats, frames, _ = deltas(feats, frames)
         host, n = feats.cpu().numpy(), frames.cpu().numpy()
@@ -242,7 +273,8 @@ def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=Non
     return mats
 
 
-def main(argv=None, log=print):
+def parse_args(argv=None):
+    """The command line, with the checks that need no file: the CMVN modes exclude each other."""
     ap = argparse.ArgumentParser(description="waveforms -> (normalised) filterbank features as a Kaldi archive, computed on the MI355X")
     ap.add_argument("--conf", required=True, help="Kaldi fbank config file (--key=value lines), e.g. the reference's conf/fbank.conf")
     ap.add_argument("--feat-type", choices=sorted(FEAT_TYPES), default="fbank", help="mfcc, spectrogram: --conf is read as that Kaldi config (conf/mfcc.conf, conf/spectrogram.conf); "
@@ -266,12 +298,42 @@ def main(argv=None, log=print):
     ap.add_argument("--rir-prob", type=float, default=None, help="probability that a copy is reverberated (default 1)")
     ap.add_argument("--noise-prob", type=float, default=None, help="probability that a copy gets noise (default 1)")
     ap.add_argument("--reverb-seed", type=int, default=None, help="seed of the copies' draws (default 0)")
+    ap.add_argument("--utt2spk", default=None, metavar="FILE", help="per-speaker CMVN: '<utterance> <speaker>' lines; statistics per speaker are "
+                    "accumulated over this list, written to --cmvn-stats (default OUT_DIR/cmvn.ark.txt) and applied")
+    ap.add_argument("--cmvn-per-utt", action="store_true", help="per-utterance CMVN: every utterance is its own speaker")
+    ap.add_argument("--cmvn-sliding", action="store_true", help="sliding-window CMVN (Kaldi's apply-cmvn-sliding)")
+    ap.add_argument("--cmn-window", type=int, default=None, help="with --cmvn-sliding: window in frames (default 600)")
+    ap.add_argument("--min-cmn-window", type=int, default=None, help="with --cmvn-sliding: smallest window at the start of an utterance (default 100)")
+    ap.add_argument("--cmn-center", action="store_true", help="with --cmvn-sliding: centre the window on the frame")
+    ap.add_argument("--norm-vars", choices=("true", "false"), default=None, help="with --utt2spk, --cmvn-per-utt (default true) or --cmvn-sliding "
+                    "(default false): normalise the variance as well as the mean")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
 
-    if args.feat_type == "logspec" and (args.compute_cmvn or args.cmvn_stats):
+    modes = [flag for flag, on in (("--utt2spk", args.utt2spk is not None), ("--cmvn-per-utt", args.cmvn_per_utt), ("--cmvn-sliding", args.cmvn_sliding),
+                                   ("--compute-cmvn", args.compute_cmvn)) if on]
+    if args.feat_type == "logspec" and (modes or args.cmvn_stats or args.norm_vars is not None):
         raise ValueError("--feat-type logspec normalises every utterance by its own mean and standard deviation (normalize in --conf): "
-                         "--compute-cmvn and --cmvn-stats do not apply to it")
+                         "--compute-cmvn, --cmvn-stats, --utt2spk, --cmvn-per-utt, --cmvn-sliding and --norm-vars do not apply to it")
+    if len(modes) > 1:
+        raise ValueError("%s and %s exclude each other: one normalisation per archive" % (modes[0], modes[1]))
+    if args.cmvn_sliding and args.cmvn_stats:
+        raise ValueError("--cmvn-sliding keeps no statistics: --cmvn-stats does not apply to it")
+    sliding_given = [n for n in ("cmn_window", "min_cmn_window") if getattr(args, n) is not None] + (["cmn_center"] if args.cmn_center else [])
+    if sliding_given and not args.cmvn_sliding:
+        raise ValueError("--%s belongs to --cmvn-sliding, which is not given" % sliding_given[0].replace("_", "-"))
+    if args.norm_vars is not None and not (args.utt2spk is not None or args.cmvn_per_utt or args.cmvn_sliding):
+        raise ValueError("--norm-vars belongs to --utt2spk, --cmvn-per-utt or --cmvn-sliding; --compute-cmvn and --cmvn-stats always normalise the variance")
+    args.cmn_window = 600 if args.cmn_window is None else args.cmn_window
+    args.min_cmn_window = 100 if args.min_cmn_window is None else args.min_cmn_window
+    if args.cmvn_sliding and (args.cmn_window < 1 or not 1 <= args.min_cmn_window <= args.cmn_window):
+        raise ValueError("--cmn-window takes at least 1 and --min-cmn-window 1 to --cmn-window, got %d and %d" % (args.cmn_window, args.min_cmn_window))
+    args.norm_vars = (not args.cmvn_sliding) if args.norm_vars is None else args.norm_vars == "true"
+    return args
+
+
+def main(argv=None, log=print):
+    args = parse_args(argv)
     reverb_given = [n for n in ("rir_list", "noise_list", "snrs", "rir_prob", "noise_prob", "reverb_seed") if getattr(args, n) is not None]
     copies = args.reverb_copies or 0
     if args.reverb_copies is not None and args.reverb_copies < 1:
@@ -299,6 +361,7 @@ def main(argv=None, log=print):
     entries = read_wav_scp(args.wav_scp)
     if not entries:
         raise ValueError("%s: no utterances" % args.wav_scp)
+    bases = [utt for utt, _ in entries]                                # the utterance of wav.scp behind every key of the archive
     waves, rates = [], []
     for utt, path in entries:
         samples, rate = read_wave(path)
@@ -310,6 +373,7 @@ def main(argv=None, log=print):
         waves = [w for w in waves for _ in factors]
         rates = [int(round(r * f)) for r in rates for _, f in factors]
         entries = [(key, path) for utt, path in entries for key in perturbed_keys([utt], factors)]
+        bases = [b for b in bases for _ in factors]
     if any(float(r) != float(config.sample_frequency) for r in rates):
         waves = resample_waves(waves, rates, int(config.sample_frequency), device, args.max_samples)
     if copies:                                                         # the copies stand behind their utterance
@@ -322,12 +386,31 @@ def main(argv=None, log=print):
         made = reverberate_waves(reverb, waves, copies, args.max_samples)
         waves = [w for i, clean in enumerate(waves) for w in [clean] + [made[c][i] for c in range(copies)]]
         entries = [(key, path) for utt, path in entries for key in reverb_keys([utt], copies)]
+        bases = [b for b in bases for _ in range(copies + 1)]
         log("made %d reverberated copies of %d utterances from %d impulse responses and %d noises" % (copies, len(made[0]), len(rirs), len(noises)))
     batches = length_batches([w.shape[0] for w in waves], args.max_samples)
     os.makedirs(args.out_dir, exist_ok=True)
 
-    mean = scale = None
-    if args.compute_cmvn:
+    mean = scale = normalise = None
+    if args.utt2spk is not None or args.cmvn_per_utt:
+        speakers = copy_speakers([key for key, _ in entries], bases, read_utt2spk(args.utt2spk) if args.utt2spk is not None else None)
+        cmvn = SpeakerCMVN(fbank.feat_dim, sorted(set(speakers)), device)
+        make_features(fbank, waves, batches, seed=args.seed, cmvn=cmvn, speakers=speakers)
+        stats_path = args.cmvn_stats or os.path.join(args.out_dir, "cmvn.ark.txt")
+        cmvn.save_kaldi_text(stats_path)
+        log("wrote CMVN statistics of %d speakers to %s" % (len(cmvn.speakers), stats_path))
+        if args.utt2spk is not None:
+            with open(os.path.join(args.out_dir, "utt2spk"), "w") as f:
+                f.writelines("%s %s\n" % (key, spk) for (key, _), spk in zip(entries, speakers))
+
+        def normalise(feats, frames, idx):
+            return cmvn.apply(feats, frames, [speakers[i] for i in idx], norm_vars=args.norm_vars, out=feats)
+    elif args.cmvn_sliding:
+        sliding = SlidingCMVN(args.cmn_window, args.min_cmn_window, normalize_variance=args.norm_vars, center=args.cmn_center)
+
+        def normalise(feats, frames, idx):
+            return sliding(feats, frames)
+    elif args.compute_cmvn:
         cmvn = GlobalCMVN(fbank.feat_dim, device)
         make_features(fbank, waves, batches, seed=args.seed, cmvn=cmvn)
         stats_path = args.cmvn_stats or os.path.join(args.out_dir, "global_%s_cmvn.txt" % args.feat_type)
@@ -339,7 +422,7 @@ def main(argv=None, log=print):
         if cmvn.feat_dim != fbank.feat_dim:
             raise ValueError("%s holds statistics of %d dimensions, the configuration gives %d" % (args.cmvn_stats, cmvn.feat_dim, fbank.feat_dim))
         mean, scale = cmvn.mean_scale(device)
-    mats = make_features(fbank, waves, batches, mean=mean, scale=scale, seed=args.seed, deltas=deltas)
+    mats = make_features(fbank, waves, batches, mean=mean, scale=scale, seed=args.seed, deltas=deltas, normalise=normalise)
     ark, scp = os.path.join(args.out_dir, "feats.ark"), os.path.join(args.out_dir, "feats.scp")
     write_kaldi_ark(ark, scp, {utt: mats[i] for i, (utt, _) in enumerate(entries)})
     log("wrote %d utterances, %d frames of %d dimensions to %s" % (len(entries), sum(m.shape[0] for m in mats.values()),

@@ -11,6 +11,9 @@ binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --conf
   LogSpecConfig / LogSpectrum       the recipe's own spectrogram (local/make_spectrum.py: a centred STFT of 400 points, log1p of the magnitude,
                 one mean and standard deviation per utterance; ops.log_spectrum)
   GlobalCMVN    Kaldi's 2 x (F + 1) statistics, accumulated on the device (ops.cmvn_accumulate), its text file, mean and 1 / stddev
+  SpeakerCMVN   the same statistics per speaker (compute-cmvn-stats --spk2utt, apply-cmvn --utt2spk; one speaker per utterance: per-utterance
+                CMVN), accumulated and applied on the device (ops.cmvn_accumulate_groups, ops.cmvn_apply), its text archive; read_utt2spk
+  SlidingCMVN   Kaldi's apply-cmvn-sliding (ops.cmvn_sliding): normalisation over a running window, for data without speaker labels
   Resampler     a waveform batch at another sample rate (ops.resample: Kaldi's LinearResample, what its binaries run under --allow-downsample /
                 --allow-upsample); SpeedPerturb: the recipe's three-way speed perturbation (perturb_data_dir_speed.sh) as one Resampler per factor
   FrameContext  the stage behind them: Kaldi's add-deltas, frame splicing, frame skipping and the pad to a multiple of n_downsample on the
@@ -21,7 +24,7 @@ binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --conf
                 and background noise added at a drawn SNR (ops.reverberate; Kaldi's wav-reverberate), drawn from (seed, running index)
   read_wave     RIFF PCM-16 mono and uncompressed NIST SPHERE (TIMIT's) -> int16 samples
 
-Not here: pitch, VTLN, per-speaker CMVN, compressed SPHERE."""
+Not here: pitch, VTLN, compressed SPHERE."""
 import struct
 
 import numpy as np
@@ -482,6 +485,113 @@ class GlobalCMVN(object):
         out = cls(len(rows[0]) - 1, device)
         out.stats.copy_(torch.tensor(rows, dtype=torch.float64))
         return out
+
+
+def read_utt2spk(path):
+    """Kaldi's utt2spk file, one `<utterance> <speaker>` per line: {utterance: speaker}, in file order.  ValueError for a line with another
+    number of fields or an utterance given twice."""
+    out = {}
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts:
+                continue
+            if len(parts) != 2:
+                raise ValueError("%s:%d: expected '<utterance> <speaker>'" % (path, ln))
+            if parts[0] in out:
+                raise ValueError("%s:%d: utterance %s is given twice" % (path, ln, parts[0]))
+            out[parts[0]] = parts[1]
+    return out
+
+
+class SpeakerCMVN(object):
+    """Mean / variance normalisation per speaker: one Kaldi statistics matrix per name of `speakers`, (G, 2, F + 1) doubles kept on `device`
+    -- compute-cmvn-stats --spk2utt and apply-cmvn --utt2spk.  With every utterance its own speaker it is per-utterance CMVN.  A CPU
+    device serves loading and saving; accumulate and apply need the GPU.  Statistics are formed into mean and scale on the device by the
+    apply call itself: nothing comes back to the host in between."""
+
+    def __init__(self, feat_dim, speakers, device="cpu"):
+        self.feat_dim = int(feat_dim)
+        self.speakers = [str(s) for s in speakers]
+        self.index = {s: g for g, s in enumerate(self.speakers)}
+        if not self.speakers or len(self.index) != len(self.speakers):
+            raise ValueError("SpeakerCMVN: expected at least one speaker and every name once")
+        self.stats = torch.zeros((len(self.speakers), 2, self.feat_dim + 1), dtype=torch.float64, device=device)
+
+    def _ids(self, speakers_of_batch):
+        try:
+            return [self.index[str(s)] for s in speakers_of_batch]
+        except KeyError as e:
+            raise ValueError("SpeakerCMVN: unknown speaker %s" % e)
+
+    def accumulate(self, feats, frames, speakers_of_batch):
+        ops.cmvn_accumulate_groups(feats, frames, self._ids(speakers_of_batch), self.stats)
+        return self
+
+    def apply(self, feats, frames, speakers_of_batch, norm_vars=True, out=None):
+        """feats (B, Tmax, F) normalised with the statistics of each utterance's speaker (apply-cmvn --norm-vars=<norm_vars>); rows at or
+        beyond frames[b] come out as zeros.  A speaker without accumulated frames leaves its utterances as they are."""
+        return ops.cmvn_apply(feats, frames, self.stats, self._ids(speakers_of_batch), norm_vars=norm_vars, out=out)
+
+    def save_kaldi_text(self, path):
+        """The text archive of `compute-cmvn-stats --spk2utt=... ark,t:`: per speaker `<speaker>  [`, one indented row per line, `]`.  Values
+        carry 17 significant digits, as GlobalCMVN's."""
+        s = self.stats.cpu().numpy()
+        with open(path, "w") as f:
+            for name, mat in zip(self.speakers, s):
+                f.write(name + "  [")
+                for row in mat:
+                    f.write("\n  " + "".join("%.17g " % v for v in row))
+                f.write("]\n")
+
+    @classmethod
+    def load_kaldi_text(cls, path, device="cpu"):
+        """Reads save_kaldi_text's layout (and Kaldi's own, which keeps fewer digits): speakers in file order."""
+        names, mats, cur = [], [], None
+        with open(path) as f:
+            for ln, line in enumerate(f, 1):
+                parts = line.split()
+                if not parts:
+                    continue
+                if cur is None:
+                    if len(parts) < 2 or parts[1] != "[":
+                        raise ValueError("%s:%d: expected '<speaker>  ['" % (path, ln))
+                    names.append(parts[0])
+                    cur, parts = [], parts[2:]
+                    if not parts:
+                        continue
+                closed = parts[-1] == "]"
+                if closed:
+                    parts = parts[:-1]
+                if parts:
+                    cur.append([float(v) for v in parts])
+                if closed:
+                    if len(cur) != 2 or len(cur[0]) != len(cur[1]) or len(cur[0]) < 2 or (mats and len(cur[0]) != len(mats[0][0])):
+                        raise ValueError("%s:%d: expected a 2 x (F + 1) CMVN statistics matrix for %s" % (path, ln, names[-1]))
+                    mats.append(cur)
+                    cur = None
+        if cur is not None or not mats:
+            raise ValueError("%s: not a Kaldi text archive of CMVN statistics" % path)
+        out = cls(len(mats[0][0]) - 1, names, device)
+        out.stats.copy_(torch.tensor(mats, dtype=torch.float64))
+        return out
+
+
+class SlidingCMVN(object):
+    """Kaldi's apply-cmvn-sliding under its option names and defaults: every frame normalised by the mean (and, with normalize_variance,
+    the variance) of a window of cmn_window frames around (center) or before it.  Called as (feats, frames) on a zero-padded device batch;
+    returns a new (B, Tmax, F) tensor (ops.cmvn_sliding)."""
+
+    def __init__(self, cmn_window=600, min_cmn_window=100, normalize_variance=False, center=False):
+        self.cmn_window, self.min_cmn_window = int(cmn_window), int(min_cmn_window)
+        self.normalize_variance, self.center = bool(normalize_variance), bool(center)
+        if self.cmn_window < 1 or not 1 <= self.min_cmn_window <= self.cmn_window:
+            raise ValueError("SlidingCMVN: cmn_window >= 1 and 1 <= min_cmn_window <= cmn_window needed, got %d and %d"
+                             % (self.cmn_window, self.min_cmn_window))
+
+    def __call__(self, feats, frames):
+        return ops.cmvn_sliding(feats, frames, cmn_window=self.cmn_window, min_cmn_window=self.min_cmn_window,
+                                normalize_variance=self.normalize_variance, center=self.center)
 
 
 def _riff(path, data):

@@ -584,7 +584,7 @@ int ctcn_step_stats(const float *loss, const int32_t *dist, const int64_t *tgt_l
  * binaries of timit/steps/make_feat.sh (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true).
  * The computation is Kaldi's, as its feature-window, feature-fbank and mel-computations sources document it; option names and defaults are
  * Kaldi's.  window_type: 0 hamming, 1 hanning, 2 povey (Kaldi's default), 3 rectangular, 4 blackman.  high_freq <= 0 is an offset from Nyquist.
- * Not here: VTLN (deltas, splicing and frame skipping: ctcn_frame_context below; MFCC: ctcn_mfcc below; the spectrogram types: ctcn_spectrogram, ctcn_logspec below; resampling in front of them: ctcn_resample below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
+ * Not here: VTLN and pitch (per-speaker, per-utterance and sliding-window normalisation: ctcn_cmvn_accumulate_groups, ctcn_cmvn_apply, ctcn_cmvn_sliding below; deltas, splicing and frame skipping: ctcn_frame_context below; MFCC: ctcn_mfcc below; the spectrogram types: ctcn_spectrogram, ctcn_logspec below; resampling in front of them: ctcn_resample below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
  * defaults). */
 typedef struct ctcn_fbank_opts {
   float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff, blackman_coeff, low_freq, high_freq, energy_floor;
@@ -930,6 +930,66 @@ int ctcn_reverb(const void *wave, int wave_is_int16, const int32_t *lens, const 
                 void *stream);
 int ctcn_reverb_host(const void *wave, int wave_is_int16, int num_samples, const void *bank, const ctcn_reverb_opts *opts, uint64_t seed,
                      uint64_t utt_index, float *out);
+/* Mean / variance normalisation per group of utterances and over a sliding window (fbank.hip, cmvn.hip): the three Kaldi calls of a standard
+ * recipe that ctcn_cmvn_accumulate and the mean / scale arguments of the feature kernels do not cover -- compute-cmvn-stats --spk2utt
+ * (statistics per speaker), apply-cmvn --utt2spk (applied per utterance) and apply-cmvn-sliding.  A group is a speaker, or, with one id
+ * per utterance, the utterance itself.  Kaldi's binaries do not run here; the definitions below restate its sources (transform/cmvn,
+ * feat/feature-functions' SlidingWindowCmn) and fix the arithmetic, so that host, device and a numpy restatement agree bit for bit.
+ * ctcn_cmvn_accumulate_groups: stats (G, 2, F + 1) DEVICE doubles, one statistics matrix of ctcn_cmvn_accumulate's layout per group; group
+ * (B) int32 in DEVICE memory.  ADDS the rows t < frames[b] (clamped to [0, Tmax]) of utterance b to stats[group[b]]; an utterance whose id
+ * is outside [0, G) contributes nothing, and nothing at or beyond frames[b] is read.  The 64-row float64 partial sums are those of
+ * ctcn_cmvn_accumulate (the same kernel, the same workspace: ctcn_cmvn_accumulate_ws_bytes); a second launch with one thread per (group,
+ * statistic) adds the partials of the group's utterances in ascending (utterance, block) order, starting from 0, and then that sum to
+ * stats; the frame counts likewise in ascending utterance order.  A function of the input bits; with G = 1 and every id 0 it writes what
+ * ctcn_cmvn_accumulate writes, bit for bit.  G at most 65 535.
+ * ctcn_cmvn_apply: out (B, Tmax, F) = the rows of feats normalised with the statistics of the utterance's group, formed on the device (no
+ * host round trip between accumulation and use).  Per group, with n = stats[g][0][F], in double, every operation rounded on its own (no
+ * fused multiply-add) -- the formulas of utils/features.GlobalCMVN.mean_scale:
+ *   m = sum / n, mean = fl32(m); v = max(sumsq / n - m * m, 1e-20), scale = fl32(1 / sqrt(v)), or 1.0f with norm_vars = 0;
+ *   out = (x - mean) * scale, a float32 subtraction followed by a float32 multiplication: the feature kernels' expression.
+ * Rows at or beyond frames[b] are written as zeros and never read, as in the padded batch the feature kernels return.  out may be feats
+ * itself (in place), not a shifted overlap of it.  group == NULL: group 0 for every utterance.  An utterance whose id is outside [0, G), or
+ * whose group has no frames (n <= 0), is copied through unnormalised.
+ * ctcn_cmvn_sliding: Kaldi's SlidingWindowCmnOptions under their names with their defaults: cmn_window (600), min_cmn_window (100),
+ * normalize_variance (false), center (false).  The window [s, e) of frame t in an utterance of n frames (SlidingWindowCmn's rule;
+ * ctcn_cmvn_sliding_window states it on the host):
+ *   1. center: s = t - cmn_window / 2, e = s + cmn_window; otherwise s = t - cmn_window, e = t + 1;
+ *   2. s < 0: e -= s, s = 0;
+ *   3. not center and e > t: e = max(t + 1, min_cmn_window);
+ *   4. e > n: s -= e - n, e = n, s = max(s, 0).
+ * So 0 <= s <= t < e <= n without center (a frame in the middle of a long utterance sees the cmn_window frames before it and itself:
+ * cmn_window + 1 frames, as in Kaldi), and from one frame to the next either bound stays or advances by one.  Per (utterance, column), in
+ * double: S and Q, the sums of x and of x * x ((double) x squared is exact) over the window.  At t = 0 they are summed over [s_0, e_0) in
+ * ascending order from 0.  At t > 0, first frame s_{t-1} is subtracted if the start advanced, then frame e_{t-1} is added if the end
+ * advanced.  With w = e - s and m = S / w:
+ *   means only: out = fl32((double) x_t - m);
+ *   normalize_variance and w > 1: v = max(Q / w - m * m, 1e-10), out = fl32(((double) x_t - m) * (1.0 / sqrt(v)));
+ *   normalize_variance and w = 1: variance 1, out = fl32((double) x_t - m).
+ * Every operation is rounded on its own; nothing is fused.  (Kaldi keeps the output in float32 and updates it as x + (-1 / w) S, and forms
+ * the variance as Q / w - S^2 / w^2 followed by pow(-0.5): the same quantities, rounded at other points.)  Rows at or beyond frames[b] are
+ * written as zeros and never read.  out must not overlap feats: the window reads frames behind the one it writes (CTCN_EINVAL).
+ * cmn_window >= 1 and 1 <= min_cmn_window <= cmn_window are required in both modes (CTCN_EINVAL) -- stricter than Kaldi, which checks only
+ * when centred.  One wave per (64 columns, utterance), lanes on the contiguous columns of a row; the chain in time is two float64
+ * additions per frame, and the row loads are kept off it: the frames of ctcn_cmvn_sliding_run consecutive steps -- the frame itself, the one
+ * leaving and the one entering the window -- are loaded into registers one run ahead of their use.
+ * ctcn_cmvn_sliding_run: the frames of one such run under these options (16), or an error code.
+ * ctcn_cmvn_sliding_window: the window of frame t < n on the HOST.  ctcn_cmvn_sliding_host: the computation for ONE utterance, feats and out
+ * (num_frames, F), and ctcn_cmvn_norm_host: mean[F] and scale[F] of ONE statistics matrix (2, F + 1) with a positive count -- both on the
+ * HOST (no HIP call; work without a GPU), through the functions the kernels are compiled from (cmvn_core.h).
+ * Limits: CTCN_EINVAL for NULL, B outside [1, 65 535], Tmax outside [1, 2^30] (the host twin takes 0 frames), F or G below 1. */
+typedef struct ctcn_sliding_cmn_opts {
+  int32_t cmn_window, min_cmn_window, normalize_variance, center;
+} ctcn_sliding_cmn_opts;
+int ctcn_cmvn_accumulate_groups(const float *feats, const int32_t *frames, const int32_t *group, double *stats, int B, int Tmax, int F, int G,
+                                void *ws, size_t ws_bytes, void *stream);
+int ctcn_cmvn_apply(const float *feats, const int32_t *frames, const int32_t *group, const double *stats, float *out, int B, int Tmax, int F,
+                    int G, int norm_vars, void *stream);
+int ctcn_cmvn_sliding(const float *feats, const int32_t *frames, float *out, int B, int Tmax, int F, const ctcn_sliding_cmn_opts *opts,
+                      void *stream);
+int ctcn_cmvn_sliding_run(const ctcn_sliding_cmn_opts *opts);
+int ctcn_cmvn_sliding_window(int t, int n, const ctcn_sliding_cmn_opts *opts, int32_t *start, int32_t *end);
+int ctcn_cmvn_sliding_host(const float *feats, int num_frames, int F, const ctcn_sliding_cmn_opts *opts, float *out);
+int ctcn_cmvn_norm_host(const double *stats, int F, int norm_vars, float *mean, float *scale);
 
 /* ---------------------------------------------------------------------------------------------------
  * CTC prefix beam search with bigram LM; replaces BeamDecoder.decode -> ctcBeamSearch.decode
