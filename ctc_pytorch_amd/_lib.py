@@ -143,6 +143,14 @@ _SIGS = {
     "ctcn_cmvn_sliding_window": (I, [I, I, P, P, P]),
     "ctcn_cmvn_sliding_host": (I, [P, I, I, P, P]),
     "ctcn_cmvn_norm_host": (I, [P, I, I, P, P]),
+    "ctcn_pitch_frames": (I, [ctypes.c_longlong, P]),
+    "ctcn_pitch_plan_bytes": (Z, [P]),
+    "ctcn_pitch_plan": (I, [P, P, Z]),
+    "ctcn_pitch_workspace_bytes": (Z, [P, I, I]),
+    "ctcn_pitch": (I, [P, P, P, P, P, P, P, I, I, I, P, Z, P]),
+    "ctcn_pitch_host": (I, [P, I, P, P, P, P, I]),
+    "ctcn_pitch_process": (I, [P, P, P, P, I, I, U, U, P]),
+    "ctcn_pitch_process_host": (I, [P, I, P, U, U, P]),
     "ctcn_comm_unique_id": (I, [P]),
     "ctcn_comm_init": (I, [P, I, I, ctypes.POINTER(ctypes.c_void_p)]),
     "ctcn_comm_allreduce_sum_f32": (I, [P, P, Z, P]),
@@ -224,6 +232,21 @@ class ReverbOpts(ctypes.Structure):
 class SlidingCmnOpts(ctypes.Structure):
     """ctcn_sliding_cmn_opts of include/ctcn.h: Kaldi's SlidingWindowCmnOptions (utils/features.SlidingCMVN fills it)."""
     _fields_ = [(k, ctypes.c_int32) for k in ("cmn_window", "min_cmn_window", "normalize_variance", "center")]
+
+
+class PitchOpts(ctypes.Structure):
+    """ctcn_pitch_opts of include/ctcn.h: Kaldi's PitchExtractionOptions (utils/features.PitchConfig fills it)."""
+    _fields_ = [(k, ctypes.c_float) for k in ("sample_frequency", "frame_length", "frame_shift", "preemphasis_coefficient", "min_f0", "max_f0",
+                                              "soft_min_f0", "penalty_factor", "lowpass_cutoff", "resample_frequency", "delta_pitch",
+                                              "nccf_ballast")] + \
+               [(k, ctypes.c_int32) for k in ("lowpass_filter_width", "upsample_filter_width", "snip_edges")]
+
+
+class PitchProcessOpts(ctypes.Structure):
+    """ctcn_pitch_process_opts of include/ctcn.h: Kaldi's ProcessPitchOptions (utils/features.ProcessPitchConfig fills it)."""
+    _fields_ = [(k, ctypes.c_float) for k in ("pitch_scale", "pov_scale", "pov_offset", "delta_pitch_scale", "delta_pitch_noise_stddev")] + \
+               [(k, ctypes.c_int32) for k in ("normalization_left_context", "normalization_right_context", "delta_window", "delay",
+                                              "add_pov_feature", "add_normalized_log_pitch", "add_delta_pitch", "add_raw_log_pitch")]
 
 
 def sources():

@@ -2595,3 +2595,173 @@ def cmvn_sliding(feats, frames, cmn_window=600, min_cmn_window=100, normalize_va
     feats = feats.contiguous()
     _lib.check(_lib.lib().ctcn_cmvn_sliding(_ptr(feats), _ptr(frames), _ptr(out), B, Tmax, F, ctypes.byref(opts), _lib.stream_ptr()), "cmvn_sliding")
     return out
+
+
+# pitch features (pitch.hip): Kaldi's compute-kaldi-pitch-feats and process-kaldi-pitch-feats
+PITCH_OPTIONS = dict(sample_frequency=16000.0, frame_length=25.0, frame_shift=10.0, preemphasis_coefficient=0.0, min_f0=50.0, max_f0=400.0,
+                     soft_min_f0=10.0, penalty_factor=0.1, lowpass_cutoff=1000.0, resample_frequency=4000.0, delta_pitch=0.005,
+                     nccf_ballast=7000.0, lowpass_filter_width=1, upsample_filter_width=5, snip_edges=True)
+PITCH_PROCESS_OPTIONS = dict(pitch_scale=2.0, pov_scale=2.0, pov_offset=0.0, delta_pitch_scale=10.0, delta_pitch_noise_stddev=0.005,
+                             normalization_left_context=75, normalization_right_context=75, delta_window=2, delay=0, add_pov_feature=True,
+                             add_normalized_log_pitch=True, add_delta_pitch=True, add_raw_log_pitch=False)
+
+
+def _struct_from(who, struct, defaults, kw):
+    unknown = sorted(set(kw) - set(defaults))
+    if unknown:
+        raise ValueError("ctc_pytorch_amd.%s: unknown option(s) %s (known: %s)" % (who, ", ".join(unknown), ", ".join(defaults)))
+    s = struct()
+    for k, d in defaults.items():
+        v = kw.get(k, d)
+        setattr(s, k, float(v) if isinstance(d, float) else int(v))
+    return s
+
+
+class PitchPlan(object):
+    """The plan of one pitch configuration (ctcn_pitch_plan; Kaldi's PitchExtractionOptions under their names, PITCH_OPTIONS the defaults):
+    the geometric lags, the sparse upsampling table and the Viterbi's penalty table, built on the host when the object is made -- a
+    RuntimeError here, before any launch, for what the kernels do not take (snip_edges=false, min_f0 >= max_f0, more than 1024 lags, a
+    lowpass_cutoff above the lower Nyquist frequency, a preemphasis) -- with the ResamplePlan of step 1, and uploaded once per device on
+    first use.  `host` is the block as uint32 words (layout in include/ctcn.h); lags, pitch (S) float32, tap_first, tap_count (S) int32,
+    weights (S, stride) float32, soft_lag, penalty (S) float64 are numpy views of it; first_lag, last_lag, window, shift, run as there."""
+
+    def __init__(self, **options):
+        L = _lib.lib()
+        self.opts = opts = _struct_from("PitchPlan", _lib.PitchOpts, PITCH_OPTIONS, options)
+        nbytes = L.ctcn_pitch_plan_bytes(ctypes.byref(opts))
+        buf = np.zeros(max(nbytes // 8, 8), dtype=np.uint64).view(np.uint32)                 # (8-byte aligned: the block holds doubles)
+        _lib.check(L.ctcn_pitch_plan(ctypes.byref(opts), buf.ctypes.data_as(ctypes.c_void_p), nbytes), "pitch_plan")
+        self.host = buf
+        hdr = buf[:16].view(np.int32)
+        self.num_lags, self.first_lag, self.last_lag, self.window, self.shift, self.stride, self.run = (int(v) for v in hdr[:7])
+        S, p = self.num_lags, 16
+        self.lags = buf[p:p + S].view(np.float32); p += S
+        self.pitch = buf[p:p + S].view(np.float32); p += S
+        self.tap_first = buf[p:p + S].view(np.int32); p += S
+        self.tap_count = buf[p:p + S].view(np.int32); p += S
+        self.weights = buf[p:p + S * self.stride].view(np.float32).reshape(S, self.stride); p += S * self.stride
+        p += p & 1
+        self.soft_lag = buf[p:p + 2 * S].view(np.float64); p += 2 * S
+        self.penalty = buf[p:p + 2 * S].view(np.float64)
+        self.sample_frequency, self.resample_frequency = int(opts.sample_frequency), int(opts.resample_frequency)
+        self.resample_plan = ResamplePlan(self.sample_frequency, self.resample_frequency, num_zeros=int(opts.lowpass_filter_width),
+                                          cutoff=float(opts.lowpass_cutoff))
+        self._dev = {}
+
+    def num_frames(self, num_samples):
+        return pitch_frames(num_samples, self)
+
+    def on(self, device):
+        key = (device.type, device.index)
+        t = self._dev.get(key)
+        if t is None:
+            t = self._dev[key] = torch.from_numpy(self.host.view(np.int64)).to(device)      # (int64: the allocation is 8-byte aligned)
+        return t
+
+
+def _pitch_plan(who, plan):
+    if not isinstance(plan, PitchPlan):
+        raise TypeError("ctc_pytorch_amd.%s: expected a PitchPlan, got %s" % (who, type(plan).__name__))
+
+
+def pitch_frames(num_samples, plan):
+    """Pitch frames of a signal of num_samples samples at plan.sample_frequency (ctcn_pitch_frames: M = ceil(N rf / fs) downsampled samples,
+    0 frames for M < W, else (M - W) / shift + 1 -- up to one more than the filterbank's count).  Host arithmetic, no device."""
+    _pitch_plan("pitch_frames", plan)
+    r = _lib.lib().ctcn_pitch_frames(int(num_samples), ctypes.byref(plan.opts))
+    if r < 0:
+        raise ValueError("ctc_pytorch_amd.pitch_frames: bad sample count %r" % (num_samples,))
+    return r
+
+
+def pitch(wave, lengths, plan, return_lags=False):
+    """Kaldi's compute-kaldi-pitch-feats on a padded batch (ctcn_resample, then ctcn_pitch; the computation, step by step, in
+    include/ctcn.h): wave (B, Nmax) float32 or int16 at plan.sample_frequency, lengths (B) samples, a list or a tensor (read on the host),
+    plan a PitchPlan.  Returns (raw (B, Tmax, 2) float32: [NCCF for the probability of voicing, pitch in Hz] per frame, rows from frames[b]
+    on zero; frames (B) int32) and, with return_lags, the chosen lag index per frame (B, Tmax) int32.  No autograd; device tensors only (no
+    CPU fallback)."""
+    _pitch_plan("pitch", plan)
+    down, lens = resample(wave, lengths, plan.resample_plan)
+    dev = down.device
+    B, Mmax = down.shape
+    Tmax = max((m - plan.window) // plan.shift + 1 if m >= plan.window else 0 for m in lens)
+    lens_t = torch.as_tensor(lens, dtype=torch.int32).to(dev)
+    raw = torch.empty((B, Tmax, 2), dtype=torch.float32, device=dev)
+    lags = torch.empty((B, Tmax), dtype=torch.int32, device=dev) if return_lags else None
+    frames = torch.empty(B, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    need = L.ctcn_pitch_workspace_bytes(ctypes.byref(plan.opts), B, Tmax)
+    ws = _lib.workspace(dev, nbytes=need, tag="pitch")
+    _lib.check(L.ctcn_pitch(_ptr(down) if Mmax else None, _ptr(lens_t), ctypes.byref(plan.opts), _ptr(plan.on(dev)), _ptr(raw) if Tmax else None,
+                            _ptr(lags) if return_lags and Tmax else None, _ptr(frames), B, Mmax, Tmax, _ptr(ws), ws.numel(), _lib.stream_ptr()),
+               "pitch")
+    return (raw, frames, lags) if return_lags else (raw, frames)
+
+
+def pitch_host(wave_np, plan, return_lags=False):
+    """compute-kaldi-pitch-feats for ONE utterance on the host (ctcn_resample_host, then ctcn_pitch_host: the arithmetic the kernels are
+    compiled from): wave_np (N) float32 or int16 numpy at plan.sample_frequency -> raw (T, 2) float32 (and the lag indices (T) int32).
+    No device."""
+    _pitch_plan("pitch_host", plan)
+    x = np.ascontiguousarray(wave_np)
+    if x.ndim != 1 or x.dtype not in (np.float32, np.int16):
+        raise ValueError("ctc_pytorch_amd.pitch_host: expected a 1-D float32 or int16 waveform")
+    L, rp = _lib.lib(), plan.resample_plan
+    M = rp.num_samples(x.shape[0])
+    down = np.zeros(max(M, 1), dtype=np.float32)
+    r = L.ctcn_resample_host(x.ctypes.data_as(ctypes.c_void_p) if x.shape[0] else None, int(x.dtype == np.int16), x.shape[0], ctypes.byref(rp.opts),
+                             rp.host.ctypes.data_as(ctypes.c_void_p), down.ctypes.data_as(ctypes.c_void_p), down.shape[0])
+    if r < 0:
+        _lib.check(r, "resample_host")
+    T = (M - plan.window) // plan.shift + 1 if M >= plan.window else 0
+    raw, lags = np.zeros((T, 2), dtype=np.float32), np.zeros(T, dtype=np.int32)
+    r = L.ctcn_pitch_host(down.ctypes.data_as(ctypes.c_void_p), M, ctypes.byref(plan.opts), plan.host.ctypes.data_as(ctypes.c_void_p),
+                          raw.ctypes.data_as(ctypes.c_void_p) if T else None, lags.ctypes.data_as(ctypes.c_void_p) if T else None, T)
+    if r < 0:
+        _lib.check(r, "pitch_host")
+    return (raw, lags) if return_lags else raw
+
+
+def _process_opts(who, options):
+    opts = _struct_from(who, _lib.PitchProcessOpts, PITCH_PROCESS_OPTIONS, options)
+    cols = sum(int(bool(getattr(opts, k))) for k in ("add_pov_feature", "add_normalized_log_pitch", "add_delta_pitch", "add_raw_log_pitch"))
+    if cols == 0:
+        raise ValueError("ctc_pytorch_amd.%s: every column is switched off" % who)
+    if not float(opts.delta_pitch_noise_stddev) >= 0.0:
+        raise ValueError("ctc_pytorch_amd.%s: delta_pitch_noise_stddev must not be negative" % who)
+    return opts, cols
+
+
+def pitch_process(raw, frames, seed=0, utt_offset=0, **options):
+    """Kaldi's process-kaldi-pitch-feats on a zero-padded batch in one launch (ctcn_pitch_process; Kaldi's ProcessPitchOptions under their
+    names, PITCH_PROCESS_OPTIONS the defaults): raw (B, Tmax, 2) float32 as pitch returns it, frames (B) a list or a device tensor.
+    Returns (B, Tmax, C) float32, C = 3 under the defaults: POV feature, normalised log pitch, delta log pitch (, raw log pitch); rows at or
+    beyond frames[b] zero.  The delta's noise is a function of (seed, b + utt_offset, frame) alone.  RuntimeError for a delay."""
+    opts, cols = _process_opts("pitch_process", options)
+    if raw.dim() != 3 or raw.shape[2] != 2 or raw.dtype != torch.float32:
+        raise ValueError("ctc_pytorch_amd.pitch_process: expected raw (B, Tmax, 2) float32, got %s %s" % (tuple(raw.shape), raw.dtype))
+    frames = _cmvn_batch("pitch_process", raw, frames)
+    B, Tmax, _ = raw.shape
+    out = torch.empty((B, Tmax, cols), dtype=torch.float32, device=raw.device)
+    if Tmax == 0:
+        _lib.check(_lib.lib().ctcn_pitch_process_host(None, 0, ctypes.byref(opts), 0, 0, None) - cols, "pitch_process")      # (the refusals)
+        return out
+    raw = raw.contiguous()
+    _lib.check(_lib.lib().ctcn_pitch_process(_ptr(raw), _ptr(frames), ctypes.byref(opts), _ptr(out), B, Tmax, int(seed) & (2 ** 64 - 1),
+                                             int(utt_offset), _lib.stream_ptr()), "pitch_process")
+    return out
+
+
+def pitch_process_host(raw_np, seed=0, utt_index=0, **options):
+    """pitch_process for ONE utterance on the host (ctcn_pitch_process_host): raw_np (T, 2) float32 numpy -> (T, C) float32.  No device."""
+    opts, cols = _process_opts("pitch_process_host", options)
+    x = np.ascontiguousarray(raw_np, dtype=np.float32)
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise ValueError("ctc_pytorch_amd.pitch_process_host: expected raw (T, 2), got %s" % (x.shape,))
+    T = x.shape[0]
+    out = np.zeros((T, cols), dtype=np.float32)
+    r = _lib.lib().ctcn_pitch_process_host(x.ctypes.data_as(ctypes.c_void_p) if T else None, T, ctypes.byref(opts), int(seed) & (2 ** 64 - 1),
+                                           int(utt_index), out.ctypes.data_as(ctypes.c_void_p) if T else None)
+    if r < 0:
+        _lib.check(r, "pitch_process_host")
+    return out

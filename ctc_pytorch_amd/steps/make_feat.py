@@ -12,6 +12,7 @@ deviation, so every CMVN flag is refused.
                  [--delta-order N [--delta-window W]]
                  [--utt2spk FILE | --cmvn-per-utt | --cmvn-sliding [--cmn-window N] [--min-cmn-window N] [--cmn-center]] [--norm-vars true|false]
                  [--reverb-copies N --rir-list FILE --noise-list FILE [--snrs 20,15,10,5,0] [--rir-prob P] [--noise-prob P] [--reverb-seed S]]
+                 [--add-pitch [--pitch-conf FILE] [--pitch-process-conf FILE] [--paste-length-tolerance N]]
 
 wav.scp: one `<utterance> <path>` per line (RIFF PCM-16 mono or uncompressed SPHERE; piped commands are not run).  Writes DIR/feats.ark and
 DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDataset and both drivers read them unchanged.
@@ -49,6 +50,14 @@ DIR/feats.scp through write_kaldi_ark, utterances in wav.scp order: SpeechDatase
                    added at one of --snrs (dB, at most 16, default 20,15,10,5,0); a copy keeps its utterance's power and length.  The
                    draws are keyed by --reverb-seed and the copy's place in the length-sorted list, copy k continuing the count of
                    copy k - 1.  --text repeats the labels under the new keys; --compute-cmvn accumulates over the copies too
+  --add-pitch      Kaldi's make_fbank_pitch.sh / make_mfcc_pitch.sh: the columns of compute-kaldi-pitch-feats | process-kaldi-pitch-feats
+                   (utils/features.Pitch; three under Kaldi's defaults: 40 mel bins become 43 columns) pasted behind the base features
+                   with paste-feats --length-tolerance=N (--paste-length-tolerance, default 2): both cut to the shorter frame count, an
+                   error beyond the tolerance.  --pitch-conf / --pitch-process-conf: Kaldi's `--key=value` files for the two binaries;
+                   without them Kaldi's defaults.  Pitch is taken from the waveform the base features see (resampled, perturbed,
+                   reverberated) and its sample-frequency must be the base configuration's.  Every kind of CMVN is computed over and
+                   applied to the pasted matrix, as in Kaldi's recipes, the statistics file holding all columns; deltas come behind it.
+                   The noise on the delta-pitch column is keyed like the dither.  Refused with --feat-type logspec
 A file whose sample rate differs from the configuration's is resampled on the device first (utils/features.Resampler, one plan per rate) when
 the conf file holds Kaldi's --allow-downsample (file rate above the configured one) / --allow-upsample (below); otherwise it is an error.
 Utterances are sorted by length and batched under --max-samples padded samples per launch.  Dither is the conf file's (Kaldi's default is
@@ -65,9 +74,10 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from ctc_pytorch_amd.utils.data_loader import write_kaldi_ark  # noqa: E402
+from ctc_pytorch_amd import ops  # noqa: E402
 from ctc_pytorch_amd.utils.features import (Fbank, FbankConfig, FrameContext, GlobalCMVN, LogSpecConfig, LogSpectrum, Mfcc, MfccConfig,  # noqa: E402
-                                            Reverberate, Spectrogram, Resampler, SlidingCMVN, SpeakerCMVN, SpectrogramConfig, read_utt2spk,
-                                            read_wave)
+                                            Pitch, PitchConfig, ProcessPitchConfig, Reverberate, Spectrogram, Resampler, SlidingCMVN,
+                                            SpeakerCMVN, SpectrogramConfig, paste_features, read_utt2spk, read_wave)
 
 FEAT_TYPES = {"fbank": (FbankConfig, Fbank), "mfcc": (MfccConfig, Mfcc), "spectrogram": (SpectrogramConfig, Spectrogram),
               "logspec": (LogSpecConfig, LogSpectrum)}
@@ -246,18 +256,59 @@ def copy_speakers(keys, bases, utt2spk):
     return [key[:len(key) - len(base)] + utt2spk[base] for key, base in zip(keys, bases)]
 
 
-def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=None, deltas=None, speakers=None, normalise=None):
+class PitchColumns(object):
+    """--add-pitch: the pitch front-end, the tolerance of the paste and the normalisation of its columns.  cmvn: where a statistics pass
+    accumulates the pitch columns (a GlobalCMVN or SpeakerCMVN of the front-end's feat_dim); stats: what the writing pass applies to them
+    ((2, C + 1) or (G, 2, C + 1) float64 on the device, with `groups` the group of every index, or None)."""
+
+    def __init__(self, front, tolerance):
+        self.front, self.tolerance = front, int(tolerance)
+        self.cmvn = self.stats = self.groups = None
+        self.norm_vars = True
+
+    def __call__(self, waves, seed, place):
+        return self.front(waves, seed=seed, utt_offset=place)
+
+    def normalised(self, pitch, frames, idx):
+        if self.stats is None:
+            return pitch
+        groups = None if self.groups is None else [self.groups[i] for i in idx]
+        return ops.cmvn_apply(pitch, frames, self.stats, groups, norm_vars=self.norm_vars)
+
+
+def joined_stats(base, pitch):
+    """One Kaldi statistics matrix (or one per speaker) over the pasted columns from the two that were accumulated side by side over the
+    same frames: sums of the base columns, sums of the pitch columns, the count."""
+    a, b = base.stats.cpu(), pitch.stats.cpu()
+    if not torch.equal(a[..., 0, -1], b[..., 0, -1]):
+        raise RuntimeError("CMVN statistics of the base and the pitch columns were accumulated over different frame counts")
+    return torch.cat([a[..., :-1], b[..., :-1], a[..., -1:]], dim=-1)
+
+
+def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=None, deltas=None, speakers=None, normalise=None, pitch=None,
+                  normalise_pasted=None):
     """Features of `waves` (list of int16 arrays), batch by batch: {index: (T, F) float32 ndarray}, or -- with `cmvn` -- nothing kept, the raw
     features accumulated into it (a SpeakerCMVN: under `speakers`, the speaker of every index).  normalise: called as (feats, frames,
-    indices of the batch) on the features that are kept.  deltas (a FrameContext without splice or skip): applied behind it."""
+    indices of the batch) on the features that are kept.  deltas (a FrameContext without splice or skip): applied behind it.  pitch (a
+    PitchColumns): its columns are pasted behind the base features, both cut to the shorter frame count; statistics are accumulated over
+    those frames, the pitch columns into pitch.cmvn; normalise_pasted: called like normalise on the pasted matrix."""
     mats, place = {}, 0
     for idx in batches:
         if isinstance(fbank, LogSpectrum):                             # normalised per utterance by the call itself; no dither
             feats, frames, _ = fbank([waves[i] for i in idx])
         else:
             feats, frames = fbank([waves[i] for i in idx], mean=mean, scale=scale, seed=seed, utt_offset=place)
+        if pitch is not None:
+            pcols, pframes = pitch([waves[i] for i in idx], seed, place)
+            _, cut = paste_features(feats, frames, pcols, pframes, pitch.tolerance)    # (the tolerance, and the shorter counts)
         place += len(idx)
         if cmvn is not None:
+            if pitch is not None:
+                frames = cut
+                if speakers is not None:
+                    pitch.cmvn.accumulate(pcols, frames, [speakers[i] for i in idx])
+                else:
+                    pitch.cmvn.accumulate(pcols, frames)
             if speakers is not None:
                 cmvn.accumulate(feats, frames, [speakers[i] for i in idx])
             else:
@@ -265,6 +316,10 @@ def make_features(fbank, waves, batches, mean=None, scale=None, seed=0, cmvn=Non
             continue
         if normalise is not None:
             feats = normalise(feats, frames, idx)
+        if pitch is not None:
+            feats, frames = paste_features(feats, cut, pitch.normalised(pcols, cut, idx), cut, 0)
+            if normalise_pasted is not None:
+                feats = normalise_pasted(feats, frames, idx)
         if deltas is not None:
             feats, frames, _ = deltas(feats, frames)
         host, n = feats.cpu().numpy(), frames.cpu().numpy()
@@ -307,8 +362,22 @@ def parse_args(argv=None):
     ap.add_argument("--cmn-center", action="store_true", help="with --cmvn-sliding: centre the window on the frame")
     ap.add_argument("--norm-vars", choices=("true", "false"), default=None, help="with --utt2spk, --cmvn-per-utt (default true) or --cmvn-sliding "
                     "(default false): normalise the variance as well as the mean")
+    ap.add_argument("--add-pitch", action="store_true", help="paste Kaldi's pitch columns (compute-kaldi-pitch-feats | process-kaldi-pitch-feats) "
+                    "behind the base features")
+    ap.add_argument("--pitch-conf", default=None, metavar="FILE", help="with --add-pitch: Kaldi config of compute-kaldi-pitch-feats (default: Kaldi's defaults)")
+    ap.add_argument("--pitch-process-conf", default=None, metavar="FILE", help="with --add-pitch: Kaldi config of process-kaldi-pitch-feats "
+                    "(default: Kaldi's defaults)")
+    ap.add_argument("--paste-length-tolerance", type=int, default=None, metavar="N", help="with --add-pitch: paste-feats --length-tolerance (default 2)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
+
+    pitch_given = [n for n in ("pitch_conf", "pitch_process_conf", "paste_length_tolerance") if getattr(args, n) is not None]
+    if pitch_given and not args.add_pitch:
+        raise ValueError("--%s belongs to --add-pitch, which is not given" % pitch_given[0].replace("_", "-"))
+    if args.add_pitch and args.feat_type == "logspec":
+        raise ValueError("--add-pitch pastes Kaldi's pitch columns behind Kaldi's features: it does not apply to --feat-type logspec")
+    if args.paste_length_tolerance is not None and args.paste_length_tolerance < 0:
+        raise ValueError("--paste-length-tolerance takes a count of frames, got %d" % args.paste_length_tolerance)
 
     modes = [flag for flag, on in (("--utt2spk", args.utt2spk is not None), ("--cmvn-per-utt", args.cmvn_per_utt), ("--cmvn-sliding", args.cmvn_sliding),
                                    ("--compute-cmvn", args.compute_cmvn)) if on]
@@ -358,6 +427,14 @@ def main(argv=None, log=print):
     config = config_type.from_kaldi_conf(args.conf)
     device = torch.device(args.device)
     fbank = frontend_type(config, device)
+    pitch = None
+    if args.add_pitch:
+        pitch_config = PitchConfig.from_kaldi_conf(args.pitch_conf) if args.pitch_conf else PitchConfig()
+        process_config = ProcessPitchConfig.from_kaldi_conf(args.pitch_process_conf) if args.pitch_process_conf else ProcessPitchConfig()
+        if float(pitch_config.sample_frequency) != float(config.sample_frequency):
+            raise ValueError("--pitch-conf says %g Hz, --conf %g: both read the same waveform" % (pitch_config.sample_frequency, config.sample_frequency))
+        pitch = PitchColumns(Pitch(pitch_config, process_config, device), 2 if args.paste_length_tolerance is None else args.paste_length_tolerance)
+    pitch_dim = pitch.front.feat_dim if pitch is not None else 0
     entries = read_wav_scp(args.wav_scp)
     if not entries:
         raise ValueError("%s: no utterances" % args.wav_scp)
@@ -391,13 +468,20 @@ def main(argv=None, log=print):
     batches = length_batches([w.shape[0] for w in waves], args.max_samples)
     os.makedirs(args.out_dir, exist_ok=True)
 
-    mean = scale = normalise = None
+    mean = scale = normalise = normalise_pasted = None
     if args.utt2spk is not None or args.cmvn_per_utt:
         speakers = copy_speakers([key for key, _ in entries], bases, read_utt2spk(args.utt2spk) if args.utt2spk is not None else None)
         cmvn = SpeakerCMVN(fbank.feat_dim, sorted(set(speakers)), device)
-        make_features(fbank, waves, batches, seed=args.seed, cmvn=cmvn, speakers=speakers)
+        if pitch is not None:
+            pitch.cmvn = SpeakerCMVN(pitch_dim, cmvn.speakers, device)
+        make_features(fbank, waves, batches, seed=args.seed, cmvn=cmvn, speakers=speakers, pitch=pitch)
         stats_path = args.cmvn_stats or os.path.join(args.out_dir, "cmvn.ark.txt")
-        cmvn.save_kaldi_text(stats_path)
+        written = cmvn
+        if pitch is not None:                                          # one matrix per speaker over the pasted columns, as Kaldi writes it
+            written = SpeakerCMVN(fbank.feat_dim + pitch_dim, cmvn.speakers)
+            written.stats.copy_(joined_stats(cmvn, pitch.cmvn))
+            pitch.stats, pitch.groups, pitch.norm_vars = pitch.cmvn.stats, [cmvn.index[s] for s in speakers], args.norm_vars
+        written.save_kaldi_text(stats_path)
         log("wrote CMVN statistics of %d speakers to %s" % (len(cmvn.speakers), stats_path))
         if args.utt2spk is not None:
             with open(os.path.join(args.out_dir, "utt2spk"), "w") as f:
@@ -408,25 +492,42 @@ def main(argv=None, log=print):
     elif args.cmvn_sliding:
         sliding = SlidingCMVN(args.cmn_window, args.min_cmn_window, normalize_variance=args.norm_vars, center=args.cmn_center)
 
-        def normalise(feats, frames, idx):
+        def slide(feats, frames, idx):
             return sliding(feats, frames)
+        normalise, normalise_pasted = (slide, None) if pitch is None else (None, slide)      # over the pasted matrix, column by column
     elif args.compute_cmvn:
         cmvn = GlobalCMVN(fbank.feat_dim, device)
-        make_features(fbank, waves, batches, seed=args.seed, cmvn=cmvn)
+        if pitch is not None:
+            pitch.cmvn = GlobalCMVN(pitch_dim, device)
+        make_features(fbank, waves, batches, seed=args.seed, cmvn=cmvn, pitch=pitch)
         stats_path = args.cmvn_stats or os.path.join(args.out_dir, "global_%s_cmvn.txt" % args.feat_type)
-        cmvn.save_kaldi_text(stats_path)
+        written = cmvn
+        if pitch is not None:
+            written = GlobalCMVN(fbank.feat_dim + pitch_dim)
+            written.stats.copy_(joined_stats(cmvn, pitch.cmvn))
+            pitch.stats = pitch.cmvn.stats
+        written.save_kaldi_text(stats_path)
         log("wrote CMVN statistics of %d frames to %s" % (int(cmvn.stats[0, -1].item()), stats_path))
         mean, scale = cmvn.mean_scale(device)
     elif args.cmvn_stats:
         cmvn = GlobalCMVN.load_kaldi_text(args.cmvn_stats)
-        if cmvn.feat_dim != fbank.feat_dim:
-            raise ValueError("%s holds statistics of %d dimensions, the configuration gives %d" % (args.cmvn_stats, cmvn.feat_dim, fbank.feat_dim))
+        if cmvn.feat_dim != fbank.feat_dim + pitch_dim:
+            raise ValueError("%s holds statistics of %d dimensions, the configuration gives %d" % (args.cmvn_stats, cmvn.feat_dim,
+                                                                                                 fbank.feat_dim + pitch_dim))
+        if pitch is not None:                                          # the matrix over the pasted columns: base sums | pitch sums | count
+            F = fbank.feat_dim
+            pitch.stats = torch.cat([cmvn.stats[:, F:-1], cmvn.stats[:, -1:]], dim=1).contiguous().to(device)
+            base = GlobalCMVN(F)
+            base.stats.copy_(torch.cat([cmvn.stats[:, :F], cmvn.stats[:, -1:]], dim=1))
+            cmvn = base
         mean, scale = cmvn.mean_scale(device)
-    mats = make_features(fbank, waves, batches, mean=mean, scale=scale, seed=args.seed, deltas=deltas, normalise=normalise)
+    mats = make_features(fbank, waves, batches, mean=mean, scale=scale, seed=args.seed, deltas=deltas, normalise=normalise, pitch=pitch,
+                         normalise_pasted=normalise_pasted)
     ark, scp = os.path.join(args.out_dir, "feats.ark"), os.path.join(args.out_dir, "feats.scp")
     write_kaldi_ark(ark, scp, {utt: mats[i] for i, (utt, _) in enumerate(entries)})
+    out_dim = fbank.feat_dim + pitch_dim
     log("wrote %d utterances, %d frames of %d dimensions to %s" % (len(entries), sum(m.shape[0] for m in mats.values()),
-                                                                          fbank.feat_dim if deltas is None else deltas.out_dim(fbank.feat_dim), ark))
+                                                                          out_dim if deltas is None else deltas.out_dim(out_dim), ark))
     if args.text:
         with open(args.text) as f:
             lines = rewrite_text(f.readlines(), factors, copies)

@@ -22,9 +22,12 @@ binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --conf
                 redrawn for every utterance of every epoch from (seed, running utterance index)
   Reverberate   multi-condition data on the waveform, in front of any of the front-ends: a room impulse response convolved into the utterance
                 and background noise added at a drawn SNR (ops.reverberate; Kaldi's wav-reverberate), drawn from (seed, running index)
+  PitchConfig / ProcessPitchConfig / Pitch   Kaldi's pitch features (compute-kaldi-pitch-feats, process-kaldi-pitch-feats: ops.pitch,
+                ops.pitch_process): NCCF over geometric lags, a Viterbi search, the probability of voicing; three columns under the defaults.
+                paste_features: paste-feats --length-tolerance, the `fbank + pitch` of Kaldi's make_fbank_pitch.sh
   read_wave     RIFF PCM-16 mono and uncompressed NIST SPHERE (TIMIT's) -> int16 samples
 
-Not here: pitch, VTLN, compressed SPHERE."""
+Not here: VTLN, compressed SPHERE, online (chunked) pitch."""
 import struct
 
 import numpy as np
@@ -274,6 +277,92 @@ class LogSpectrum(object):
         standard deviation of each utterance) on the device."""
         waves, lengths = _batch("LogSpectrum", waves, lengths)
         return ops.log_spectrum(waves.to(self.device), lengths, self.plan)
+
+
+class PitchConfig(_KaldiConfig):
+    """The options of Kaldi's compute-kaldi-pitch-feats (PitchExtractionOptions) under Kaldi's names and with Kaldi's defaults.  The offline
+    computation only: the chunking and latency options of the online extractor are unknown options.  snip_edges=false, a preemphasis and
+    what else the kernels do not take are read and kept, and refused when the plan is built."""
+    DEFAULTS = dict(ops.PITCH_OPTIONS)
+    DRIVER_OPTIONS = {}
+
+    def _check_window(self):
+        pass
+
+    def plan(self):
+        return ops.PitchPlan(**{k: getattr(self, k) for k in self.DEFAULTS})
+
+
+class ProcessPitchConfig(_KaldiConfig):
+    """The options of Kaldi's process-kaldi-pitch-feats (ProcessPitchOptions) under Kaldi's names and with Kaldi's defaults: three columns
+    (POV feature, normalised log pitch, delta log pitch).  A delay other than 0 is read and kept, and refused at the first call."""
+    DEFAULTS = dict(ops.PITCH_PROCESS_OPTIONS)
+    DRIVER_OPTIONS = {}
+
+    def _check_window(self):
+        pass
+
+    @property
+    def feat_dim(self):
+        return sum(bool(getattr(self, k)) for k in ("add_pov_feature", "add_normalized_log_pitch", "add_delta_pitch", "add_raw_log_pitch"))
+
+    def kw(self):
+        return {k: getattr(self, k) for k in self.DEFAULTS}
+
+
+class Pitch(object):
+    """Kaldi's pitch features of one PitchConfig and one ProcessPitchConfig on one device (ops.pitch, ops.pitch_process; Kaldi's
+    make_fbank_pitch.sh pipes the same two binaries).  Building it builds the plan: a configuration outside the kernels' range raises
+    RuntimeError here.  feat_dim: 3 under the defaults."""
+
+    def __init__(self, config=None, process_config=None, device="cuda:0"):
+        self.config = config if config is not None else PitchConfig()
+        self.process_config = process_config if process_config is not None else ProcessPitchConfig()
+        self.device = torch.device(device)
+        self.plan = self.config.plan()
+        self.feat_dim = self.process_config.feat_dim
+        if self.feat_dim == 0:
+            raise ValueError("Pitch: every column of the post-processing is switched off")
+        if self.process_config.delay != 0:
+            raise RuntimeError("Pitch: a delay other than 0 is not built")
+
+    def num_frames(self, num_samples):
+        return self.plan.num_frames(num_samples)
+
+    def raw(self, waves, lengths=None):
+        """compute-kaldi-pitch-feats alone: (raw (B, Tmax, 2) float32: NCCF and pitch in Hz, frames (B) int32)."""
+        waves, lengths = _batch("Pitch", waves, lengths)
+        return ops.pitch(waves.to(self.device), lengths, self.plan)
+
+    def __call__(self, waves, lengths=None, seed=0, utt_offset=0):
+        """waves as Fbank takes them, at config.sample_frequency.  Returns (feats (B, Tmax, feat_dim) float32 zero-padded, frames (B)
+        int32) on the device.  The noise on the delta column is keyed by (seed, b + utt_offset), as Fbank's dither."""
+        raw, frames = self.raw(waves, lengths)
+        return ops.pitch_process(raw, frames, seed=seed, utt_offset=utt_offset, **self.process_config.kw()), frames
+
+
+def paste_features(a, frames_a, b, frames_b, length_tolerance=2):
+    """Kaldi's paste-feats --length-tolerance on two zero-padded device batches of the same utterances: a (B, Ta, Fa), b (B, Tb, Fb) float32
+    with their frame counts (lists or tensors) -> (out (B, T, Fa + Fb) float32, frames (B) int32): both cut to the shorter frame count of
+    every utterance, rows beyond it zero.  ValueError where the counts of an utterance differ by more than length_tolerance."""
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.dtype != torch.float32 or b.dtype != torch.float32 or a.device != b.device:
+        raise ValueError("paste_features: expected two float32 batches (B, T, F) of the same B on one device")
+    fa = [int(v) for v in (frames_a.tolist() if torch.is_tensor(frames_a) else frames_a)]
+    fb = [int(v) for v in (frames_b.tolist() if torch.is_tensor(frames_b) else frames_b)]
+    B = a.shape[0]
+    if len(fa) != B or len(fb) != B:
+        raise ValueError("paste_features: %d and %d frame counts for a batch of %d" % (len(fa), len(fb), B))
+    for i, (x, y) in enumerate(zip(fa, fb)):
+        if abs(x - y) > int(length_tolerance):
+            raise ValueError("paste_features: utterance %d has %d and %d frames, more than the tolerance of %d apart" % (i, x, y, int(length_tolerance)))
+        if not (0 <= x <= a.shape[1] and 0 <= y <= b.shape[1]):
+            raise ValueError("paste_features: frame counts %d and %d of utterance %d outside the batches" % (x, y, i))
+    frames = torch.tensor([min(x, y) for x, y in zip(fa, fb)], dtype=torch.int32)
+    T = int(frames.max()) if B else 0
+    frames = frames.to(a.device)
+    out = torch.cat([a[:, :T], b[:, :T]], dim=2)
+    keep = torch.arange(T, device=a.device)[None, :] < frames[:, None]
+    return torch.where(keep[:, :, None], out, torch.zeros((), dtype=out.dtype, device=out.device)), frames
 
 
 class Resampler(object):

@@ -584,7 +584,7 @@ int ctcn_step_stats(const float *loss, const int32_t *dist, const int64_t *tgt_l
  * binaries of timit/steps/make_feat.sh (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true).
  * The computation is Kaldi's, as its feature-window, feature-fbank and mel-computations sources document it; option names and defaults are
  * Kaldi's.  window_type: 0 hamming, 1 hanning, 2 povey (Kaldi's default), 3 rectangular, 4 blackman.  high_freq <= 0 is an offset from Nyquist.
- * Not here: VTLN and pitch (per-speaker, per-utterance and sliding-window normalisation: ctcn_cmvn_accumulate_groups, ctcn_cmvn_apply, ctcn_cmvn_sliding below; deltas, splicing and frame skipping: ctcn_frame_context below; MFCC: ctcn_mfcc below; the spectrogram types: ctcn_spectrogram, ctcn_logspec below; resampling in front of them: ctcn_resample below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
+ * Not here: VTLN (pitch: ctcn_pitch below; per-speaker, per-utterance and sliding-window normalisation: ctcn_cmvn_accumulate_groups, ctcn_cmvn_apply, ctcn_cmvn_sliding below; deltas, splicing and frame skipping: ctcn_frame_context below; MFCC: ctcn_mfcc below; the spectrogram types: ctcn_spectrogram, ctcn_logspec below; resampling in front of them: ctcn_resample below).  Zero-initialise the struct and fill every field (ctc_pytorch_amd/utils/features.py holds the
  * defaults). */
 typedef struct ctcn_fbank_opts {
   float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff, blackman_coeff, low_freq, high_freq, energy_floor;
@@ -990,6 +990,81 @@ int ctcn_cmvn_sliding_run(const ctcn_sliding_cmn_opts *opts);
 int ctcn_cmvn_sliding_window(int t, int n, const ctcn_sliding_cmn_opts *opts, int32_t *start, int32_t *end);
 int ctcn_cmvn_sliding_host(const float *feats, int num_frames, int F, const ctcn_sliding_cmn_opts *opts, float *out);
 int ctcn_cmvn_norm_host(const double *stats, int F, int norm_vars, float *mean, float *scale);
+/* Pitch features (pitch.hip, pitch_core.h): Kaldi's compute-kaldi-pitch-feats followed by process-kaldi-pitch-feats (Ghahremani et al.,
+ * ICASSP 2014), the offline computation under Kaldi's option names and defaults (frames_per_chunk = 0, max_frames_latency = 0,
+ * simulate_first_pass_online = false, nccf_ballast_online = false).  utils/features.PitchConfig / ProcessPitchConfig hold the defaults.
+ * Refused by the plan builder with CTCN_EUNSUPPORTED (plan_bytes: 0) and again by every entry before any launch: snip_edges = false, a
+ * preemphasis_coefficient other than 0, rates that are not whole numbers of Hz, min_f0 >= max_f0, more than 1024 lags, a lowpass_cutoff above
+ * the Nyquist frequency of the lower rate, W + last lag beyond 8192 samples, more than 16 upsampling taps.  With fs = sample_frequency,
+ * rf = resample_frequency:
+ *   1. downsample: the waveform goes through ctcn_resample with orig_freq = fs, new_freq = rf, num_zeros = lowpass_filter_width, cutoff =
+ *      lowpass_cutoff (LinearResample, flushed): M = ceil(N rf / fs) float32 samples.  ctcn_pitch takes THAT batch; ops.pitch does both.
+ *   2. lags, in float32 as Kaldi's BaseFloat loop: lag = float(1 / max_f0); while lag <= float(1 / min_f0): keep it, lag = float(double(lag)
+ *      (1 + double(delta_pitch))).  S lags (417 under the defaults).  Integer lags measured: first = ceil(rf (1 / max_f0 - ufw / (2 rf))) ..
+ *      last = floor(rf (1 / min_f0 + ufw / (2 rf))), ufw = upsample_filter_width (8 .. 82).  W = int(rf frame_length / 1000), shift =
+ *      int(rf frame_shift / 1000) (100, 40).
+ *   3. frames: T = 0 for M < W, else (M - W) / shift + 1 (ctcn_pitch_frames takes N, the count at fs).  Frame t reads W + last samples from
+ *      t shift; samples behind the utterance are zeros.  T may exceed the filterbank's count by one.
+ *   4. correlation, in float64, sample order, every operation rounded on its own: mean = (sum of the first W samples) / W; v[i] = x[i] - mean
+ *      over the whole window; e1 = sum v[i]^2, i < W; per integer lag l: e2 = sum v[l + i]^2, inner = sum v[i] v[l + i]; prod = e1 e2;
+ *      nccf_pitch[l] = inner / sqrt(prod + ballast), nccf_pov[l] = inner / sqrt(prod), 0 where the square root is 0.  ballast =
+ *      (var W)^2 nccf_ballast with var = Q / M - (S / M)^2 over the utterance's M downsampled samples, S and Q (sum, sum of squares) formed
+ *      as 256 partial sums -- partial i takes samples i, i + 256, ... in order -- added in ascending order: one shape, no atomics.
+ *   5. upsampling (Kaldi's ArbitraryResample: input rate rf, cutoff rf / 2, num_zeros = ufw): for lag i, t = double(lags[i]) - first / rf,
+ *      fw = ufw / rf; taps j = max(ceil(rf (t - fw)), 0) .. min(floor(rf (t + fw)), last - first); d = t - j / rf; weight = filt(d) win(d)
+ *      / rf rounded once to float32, win(d) = 0.5 (1 + cos(2 pi (rf / 2) / ufw d)) for |d| < fw, else 0, filt(d) = sin(2 pi (rf / 2) d) /
+ *      (pi d), rf at 0.  Both rows: sum over the taps in order of double(weight) * nccf[j] (float64 product, then float64 sum), rounded to
+ *      float32 ONCE -- the rows of step 4 stay float64 until here.
+ *   6. Viterbi over the frames, float64: local[i] = (1 - n) + (soft_min_f0 lags[i]) n with n = double(nccf_pitch[i]); forward[i] =
+ *      local[i] + min_j (prev[j] + pen[|i - j|]), pen[d] = d^2 c, c = log(1 + delta_pitch)^2 penalty_factor; prev = 0 before the first
+ *      frame; the frame's minimum is subtracted from forward after every frame; backpointer = the LOWEST j that attains the minimum (the
+ *      minimum and that j do not depend on the order of evaluation; Kaldi's bound-tightening search reaches the same minimum, its choice
+ *      among exact float ties is not reproduced).  After the last frame the lowest-index arg-min of forward starts the walk back.
+ *   7. raw output, one row per frame: [nccf_pov at the chosen lag, float32(1) / lags[chosen]].
+ *   8. post-processing (ctcn_pitch_process) in float64, rounded once; columns in this order, each if asked for:
+ *      POV feature: pov_scale (pow(1.0001 - n, 0.15) - 1) + pov_offset, n clipped to [-1, 1];
+ *      normalised log pitch: pitch_scale (log p_t - sum_w(pov log p) / sum_w(pov)) over the frames [t - left, t + right] inside the
+ *        utterance in ascending order, pov = 1 / (1 + exp(-r)), r = -5.2 + 5.4 exp(7.5 (a - 1)) + 4.8 a - 2 exp(-10 a) + 4.2 exp(20 (a - 1)),
+ *        a = min(|n|, 1);
+ *      delta log pitch: delta_pitch_scale (sum_k s[k] log p[clamp(t + k)] + delta_pitch_noise_stddev g), s = ctcn_delta_scales of order 1 and
+ *        delta_window, g a unit Gaussian from Philox keyed by (seed, utterance index, frame) as the filterbank's dither (sample 0);
+ *      raw log pitch.
+ *      Refused: delay other than 0, a context beyond 1500 frames, delta_window outside [1, 5] (CTCN_EUNSUPPORTED); no column (CTCN_EINVAL).
+ *   9. pasting to base features (paste-feats --length-tolerance) is host glue: utils/features.paste_features.
+ * Steps 4 to 7 agree bit for bit between the kernels, ctcn_pitch_host and the restatement tests/pitch_ref.py; step 8 goes through pow, exp
+ * and log and is held to a tolerance.
+ * The plan block (host, 4-byte words, 8-byte aligned): [0, 16) int32 S, first, last, W, shift, the tap row stride, the frames of
+ * backpointers the walk back stages at a time, last - first + 1, zeros; then S float lags; S float 1 / lag; S int32 first tap (relative to
+ * `first`); S int32 tap counts; S x stride float weights; a pad word if needed for alignment; S double soft_min_f0 lags[i]; S double pen[d].
+ * ctcn_pitch: wave (B, Mmax) float32 at rf, lens (B) int32 clamped to [0, Mmax]; plan in DEVICE memory; out (B, Tmax, 2) float32, rows at
+ * or beyond frames[b] zero; lag_index (B, Tmax) int32 or NULL: the chosen state per frame; frames (B) int32; ws of
+ * ctcn_pitch_workspace_bytes (256-byte aligned: the ballast, the two float32 correlation planes, 16-bit backpointers).  Tmax at most the
+ * frames Mmax samples hold.  Three launches: the sums, the correlation and upsampling, the search with its walk back (one workgroup per utterance).
+ * ctcn_pitch_host: ONE utterance on the host (no HIP call), plan the host block; returns the frame count.  ctcn_pitch_process: raw
+ * (B, Tmax, 2) -> out (B, Tmax, C), C the number of columns asked for, rows at or beyond frames[b] zero; utterance b draws its noise from
+ * (seed, b + utt_offset).  ctcn_pitch_process_host: one utterance of num_frames frames; returns C. */
+typedef struct ctcn_pitch_opts {
+  float sample_frequency, frame_length, frame_shift, preemphasis_coefficient, min_f0, max_f0, soft_min_f0, penalty_factor, lowpass_cutoff,
+      resample_frequency, delta_pitch, nccf_ballast;
+  int32_t lowpass_filter_width, upsample_filter_width, snip_edges;
+} ctcn_pitch_opts;
+typedef struct ctcn_pitch_process_opts {
+  float pitch_scale, pov_scale, pov_offset, delta_pitch_scale, delta_pitch_noise_stddev;
+  int32_t normalization_left_context, normalization_right_context, delta_window, delay, add_pov_feature, add_normalized_log_pitch,
+      add_delta_pitch, add_raw_log_pitch;
+} ctcn_pitch_process_opts;
+int ctcn_pitch_frames(long long num_samples, const ctcn_pitch_opts *opts);
+size_t ctcn_pitch_plan_bytes(const ctcn_pitch_opts *opts);
+int ctcn_pitch_plan(const ctcn_pitch_opts *opts, void *plan, size_t plan_bytes);
+size_t ctcn_pitch_workspace_bytes(const ctcn_pitch_opts *opts, int B, int Tmax);
+int ctcn_pitch(const float *wave, const int32_t *lens, const ctcn_pitch_opts *opts, const void *plan, float *out, int32_t *lag_index,
+               int32_t *frames, int B, int Mmax, int Tmax, void *ws, size_t ws_bytes, void *stream);
+int ctcn_pitch_host(const float *wave, int num_samples, const ctcn_pitch_opts *opts, const void *plan, float *out, int32_t *lag_index,
+                    int out_cap);
+int ctcn_pitch_process(const float *raw, const int32_t *frames, const ctcn_pitch_process_opts *opts, float *out, int B, int Tmax,
+                       uint64_t seed, uint64_t utt_offset, void *stream);
+int ctcn_pitch_process_host(const float *raw, int num_frames, const ctcn_pitch_process_opts *opts, uint64_t seed, uint64_t utt_index,
+                            float *out);
 
 /* ---------------------------------------------------------------------------------------------------
  * CTC prefix beam search with bigram LM; replaces BeamDecoder.decode -> ctcBeamSearch.decode
