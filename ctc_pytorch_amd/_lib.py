@@ -162,6 +162,7 @@ _SIGS = {
     "ctcn_diag_beam_plan": (I, [I, I, I, I, I, I, P]),
     "ctcn_diag_ctc_lattice_plan": (I, [I, P]),
     "ctcn_diag_gemm_on_xcds": (I, [I, I, I, I, I, P, I, P, I, P, I, F, I, P, Z, P, ctypes.c_uint]),
+    "ctcn_diag_gemm_shift_b_pair": (I, [I, I, I, I, P, I, P, I, P, I, P, P, I, P, I, F, I, P, Z, P, ctypes.c_uint, I, I]),
     "ctcn_rnn_last_kernel": (ctypes.c_char_p, [I]),
     "ctcn_levenshtein": (ctypes.c_longlong, [P, ctypes.c_longlong, P, ctypes.c_longlong]),
     "ctcn_levenshtein_ops": (ctypes.c_longlong, [P, ctypes.c_longlong, P, ctypes.c_longlong, P, P]),

@@ -2102,6 +2102,20 @@ int ctcn_gemm_shift_b(int M, int N, int K, const float *A, int lda, const float 
   return gemm_core(1, 0, M, N, K, A, lda, B, ldb, C, ldc, beta, precision, ws, ws_bytes, stream, xcd_allow, planes, shift);
 }
 
+// The dW_ih / dW_hh pair of ctcn_rnn_bwd_weights as one call, for tests: C1 = A^T B1 through ctcn_gemm_on_xcds, then C2 = A2^T shift_k(B2)
+// through ctcn_gemm_shift_b, both with one GemmPlanes; reuse != 0 sets same_a in between as the layer does (A2 == A there; an A2 that differs
+// must be refused by the guard and split again).  reuse == 2 also fills A's K x M window with 0xFF bytes (NaN) between the two products: a
+// second product that reads A instead of the planes the first one left shows it in every output.
+extern "C" int ctcn_diag_gemm_shift_b_pair(int M, int N1, int N2, int K, const float *A, int lda, const float *B1, int ldb1, float *C1, int ldc1,
+                                           const float *A2, const float *B2, int ldb2, float *C2, int ldc2, float beta, int precision, void *ws,
+                                           size_t ws_bytes, void *stream, unsigned xcd_allow, int shift, int reuse) {
+  GemmPlanes pl;
+  if (const int rc = ctcn_gemm_on_xcds(1, 0, M, N1, K, A, lda, B1, ldb1, C1, ldc1, beta, precision, ws, ws_bytes, stream, xcd_allow, &pl)) return rc;
+  if (reuse) pl.same_a = true;
+  if (reuse == 2) CTCN_HIP(hipMemset2DAsync(const_cast<float *>(A), (size_t)lda * sizeof(float), 0xFF, (size_t)M * sizeof(float), (size_t)K, (hipStream_t)stream));
+  return ctcn_gemm_shift_b(M, N2, K, A2, lda, B2, ldb2, C2, ldc2, beta, precision, ws, ws_bytes, stream, xcd_allow, shift, &pl);
+}
+
 extern "C" int ctcn_gemm(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B,
                          int ldb, float *C, int ldc, float beta, int precision, void *ws, size_t ws_bytes,
                          void *stream) {

@@ -479,6 +479,18 @@ def gemm(transA, transB, M, N, K, A, lda, Bm, ldb, C, ldc, beta=0.0, xcd_allow=0
     return C
 
 
+def gemm_shift_b_pair(M, N1, N2, K, A, lda, B1, ldb1, C1, ldc1, A2, B2, ldb2, C2, ldc2, shift, beta=0.0, xcd_allow=0, reuse=False, ws=None):
+    """C1 = A^T B1, then C2 = A2^T shift_k(B2) with one plane record, as a recurrent layer's weight gradients run (ctcn_diag_gemm_shift_b_pair;
+    tests).  reuse: 1 asks the second product for A's planes of the first, 2 also overwrites A with NaN in between (pass A2 = A).  ws: a uint8
+    tensor to use as the workspace instead of the stream's own."""
+    _need_gpu(A, B1, C1, A2, B2, C2)
+    wp, wn = (_ptr(ws), ws.numel()) if ws is not None else _ws(C1)[1:]
+    _lib.check(_lib.lib().ctcn_diag_gemm_shift_b_pair(M, N1, N2, K, _ptr(A), lda, _ptr(B1), ldb1, _ptr(C1), ldc1, _ptr(A2), _ptr(B2), ldb2, _ptr(C2), ldc2,
+                                                      float(beta), get_precision(), wp, wn, _lib.stream_ptr(), int(xcd_allow), int(shift), int(reuse)),
+               "gemm_shift_b_pair")
+    return C1, C2
+
+
 def gemm_dx(M, N, K, A, lda, Bm, ldb, C, ldc, beta=0.0):
     """C = A B for a row-major A (M x K) and a row-major B (K x N) through ctcn_gemm_dx, the entry of a recurrent layer's dx product (tests)."""
     _need_gpu(A, Bm, C)

@@ -1114,12 +1114,19 @@ int ctcn_diag_pipeline_chunks(int cell, int T, int B, int I, int H, int dirs, in
  * 1 rows, 2 transposing, 3 transposing queued), grid x, grid y, 16-B loads of A, of B (direct kernels).  CTCN_EINVAL on the arguments
  * ctcn_gemm refuses.  Pure arithmetic, no device needed.
  * ctcn_diag_gemm_on_xcds: ctcn_gemm with its workgroups confined to the XCDs of `xcd_allow` (0: ctcn_gemm itself) -- the side-stream forms
- * the recurrent layer uses, for tests. */
+ * the recurrent layer uses, for tests.
+ * ctcn_diag_gemm_shift_b_pair: the weight-gradient pair of a recurrent layer, for tests: C1 (M x N1) = A^T B1, then C2 (M x N2) =
+ * A2^T shift_k(B2) with B2's rows delayed (shift > 0) or advanced (shift < 0) by |shift| < K contraction steps, zeros shifted in; A, A2
+ * (K x M, lda), B1, B2 (K x N). Both run in one sequence; reuse != 0 asks the second product to take A's bf16 planes from the first;
+ * reuse == 2 also overwrites A's K x M window with NaN between the two products (the second then must not read A: pass A2 == A). */
 #define CTCN_GEMM_PLAN_INTS 12
 int ctcn_diag_gemm_plan(int transA, int transB, int M, int N, int K, int lda, int ldb, int ldc, int precision, int b_shift, int a_mod16,
                         int b_mod16, int has_ws, size_t ws_bytes, unsigned xcd_allow, int same_a, int same_b, int cus, int xcds, int *out);
 int ctcn_diag_gemm_on_xcds(int transA, int transB, int M, int N, int K, const float *A, int lda, const float *B, int ldb, float *C, int ldc,
                            float beta, int precision, void *ws, size_t ws_bytes, void *stream, unsigned xcd_allow);
+int ctcn_diag_gemm_shift_b_pair(int M, int N1, int N2, int K, const float *A, int lda, const float *B1, int ldb1, float *C1, int ldc1,
+                                const float *A2, const float *B2, int ldb2, float *C2, int ldc2, float beta, int precision, void *ws,
+                                size_t ws_bytes, void *stream, unsigned xcd_allow, int shift, int reuse);
 /* ctcn_diag_dx_plan: what ctcn_gemm_dx would do on a device of `cus` CUs under the current options, given A modulo 16 bytes and the
  * workspace's size: out[CTCN_DX_PLAN_INTS] = eligible for the 256 x 320 tile, takes it, tiles_wide (0 when not eligible), tiles_128.
  * Pure arithmetic, no device needed. */
