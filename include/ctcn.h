@@ -411,6 +411,7 @@ int ctcn_sum_f32(const float *x, float *out, int n, void *stream);
  *   scaled by gscale[b * gscale_stride] (stride 0: the DEVICE scalar upstream gradient of 'sum' / 'mean'; 1: the (B) upstream
  *   gradient of 'none'), divided by B * max(tgt_len[b], 1) when reduction == CTCN_REDUCTION_MEAN.  zero_infinity != 0: the rows
  *   of an utterance with nll = +inf are 0 instead of NaN.  Rows of utterances with lengths outside the tensors stay NaN.
+ *   A -inf log-prob gives NaN at that cell of a feasible utterance's gradient, as torch does, and finite values elsewhere.
  * reduce: nll' = nll with +inf replaced by 0 if zero_infinity; NONE: out (B) = nll'; SUM: out[0] = sum_b nll'_b; MEAN:
  *   out[0] = (1/B) sum_b nll'_b / max(tgt_len[b], 1) (tgt_len may be NULL unless MEAN).  One workgroup, fixed order, double
  *   partials; NaN (every output) while the status word of ctcn_set_status_buffer is set, as ctcn_sum_f32.
