@@ -170,6 +170,8 @@ _SIGS = {
     "ctcn_beam_ws_bytes": (Z, [I, I, I, I]),
     "ctcn_beam_decode": (I, [P, I, P, P, D, I, I, P, P, P, P, I, I, I, P, Z, P]),
     "ctcn_beam_decode_nbest": (I, [P, I, P, P, D, I, I, I, P, P, P, P, P, I, I, I, P, Z, P]),
+    "ctcn_beam_decode_lm": (I, [P, I, P, P, I, D, I, I, I, P, P, P, P, P, I, I, I, P, Z, P]),
+    "ctcn_diag_beam_plan_lm": (I, [I, I, I, I, I, I, I, P]),
 }
 
 

@@ -1,4 +1,4 @@
-// decode.hip -- CTC prefix beam search with a bigram LM, one workgroup per utterance (gfx950).
+// decode.hip -- CTC prefix beam search with a bigram or trigram LM, one workgroup per utterance (gfx950).
 //
 // replaces: BeamDecoder.decode -> ctcBeamSearch.decode (reference timit/utils/ctcDecoder.py:181-192,
 // timit/utils/BeamSearch.py:73-153 with log_add_prob :43-50, calcExtPr :52-66, BeamState.sort :29-33,
@@ -15,6 +15,14 @@
 //   * the reference's two failure modes are reported, not hidden: status 1 = an empty labelling reaches the
 //     final LM step (python IndexError at BeamSearch.py:135), status 2 = log of a zero probability
 //     (python ValueError).
+// LM order (ctcn_beam_decode_lm): the order is a property of the call and a template parameter of the kernels.  Order 2 is the reference's
+// term lm[c1][k]; order 3 -- which the reference's LanguageModel(n_gram=3) accepts and never evaluates -- replaces it, in calcExtPr and in
+// the final step, by tri[c0][c1][k] over a dense (V+1)^3 table (index V = '<s>' for c0 / c1, '</s>' for k): tri[V][V][k] for the empty
+// labelling, tri[V][y[0]][k] for one class, tri[y[-2]][y[-1]][k] beyond.  Every beam slot therefore carries the class before its last
+// (generic kernel: BeamState::prev; fast kernel: z_plast, mirrored to bm_c0 for the candidate waves), and the fast kernel's wave 0 one
+// more (z_pplast) because it recomputes the PARENT's extension term.  The order-3 table is read from global memory on every path and the
+// product with alpha is rounded on its own (lm_scaled), so all paths agree to the bit; the order-2 instantiations compile to the code they
+// were (same VGPRs, SGPRs, LDS and scratch: DESIGN.md section 7s).
 // Parallelism: utterances across workgroups (replicas, no collective), candidates (beam x class) across the
 // 256 lanes of the workgroup; every per-step quantity lives in LDS (beam state, log-probs, candidate scores).
 #include <algorithm>
@@ -65,6 +73,7 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
 struct BeamState {   // one copy of the beam (BHat) in LDS: arrays of `wcap` entries carved out of the kernel's dynamic shared memory
   int *node, *len, *last, *par;
   double *pB, *pNB, *pT;
+  int *prev;   // order 3 only: the class before `last` (y[-2]; meaningful where len >= 2)
 };
 
 struct BeamArgs {
@@ -145,9 +154,10 @@ __device__ __forceinline__ int arg_max_rounds(double *cand, int ncand, int W, do
 // (:150, the reference keeps [0]) -- a stable descending sort: among equal scores the earlier entry of BHat comes first -- and every picked
 // labelling read back through the trie: walk(n) returns the last class of node n and moves n to its parent.  pT is reused for the scores and
 // `taken` for the picks (it may be `last`: entry r's last class is read before taken[r] is written).  Status 1 / 3 or != 0: outputs zeroed.
-template <typename Args, typename Walk>
+// ORDER 3: the end term is tri[c0][last][V], c0 = prev[r] (the class before the last) for a labelling of two classes or more, V (<s>) for one.
+template <int ORDER = 2, typename Args, typename Walk>
 __device__ __forceinline__ void beam_finish(const Args &a, int b, int status, bool too_many_nodes, int nb, const int *len, const int *last,
-                                            const int *node, double *pT, int *taken, const double *lm, Walk walk) {
+                                            const int *node, double *pT, int *taken, const double *lm, Walk walk, const int *prev = nullptr) {
   if (threadIdx.x != 0) return;
   const int NB = a.nbest, V = a.V, T = a.T;
   int nout = 0;
@@ -158,8 +168,10 @@ __device__ __forceinline__ void beam_finish(const Args &a, int b, int status, bo
   if (status == 0) {
     for (int r = 0; r < nb; ++r) {
       // (the reference's log_add_prob(LOG_ZERO, pr): its first test returns the second argument, BeamSearch.py:44-45)
-      const double tot = pT[r] + lm_scaled(lm[(size_t)last[r] * (V + 1) + V], a.alpha);
       const int ln = len[r];
+      size_t row = (size_t)last[r];
+      if (ORDER == 3) row += (size_t)(ln > 1 ? prev[r] : V) * (V + 1);
+      const double tot = pT[r] + lm_scaled(lm[row * (V + 1) + V], a.alpha);
       pT[r] = tot * (1.0 / (ln ? ln : 1));
       taken[r] = 0;
     }
@@ -182,15 +194,16 @@ __device__ __forceinline__ void beam_finish(const Args &a, int b, int status, bo
 }
 // Dynamic LDS of beam_kernel, byte offsets: lg[V] doubles | cand[W * V] doubles (cand_in_lds) | STATE x wcap + smax doubles | as many ints |
 // LM table (lm_in_lds).  Doubles: 2 x {pB, pNB, pT}, sNB, sB, sT, selv (wcap each), sv_v (smax); ints: 2 x {node, len, last, par}, mfrom, sel,
-// sv_i -- BeamCtx::carve names them.
+// sv_i -- BeamCtx::carve names them.  Order 3 adds 2 x prev (wcap ints each) behind sv_i and keeps its (V+1)^3 table in global memory.
 struct GenericLds {
   static constexpr int STATE = 10;
   size_t cand, dbl, ints, lm, total;
-  __host__ __device__ GenericLds(int V, int W, int wcap, int smax, bool cand_in_lds, bool lm_in_lds) {
+  __host__ __device__ GenericLds(int V, int W, int wcap, int smax, bool cand_in_lds, bool lm_in_lds, int order = 2) {
     size_t off = (size_t)V * sizeof(double);
     cand = off; off += cand_in_lds ? (size_t)W * V * sizeof(double) : 0;
     dbl = off;  off += ((size_t)STATE * wcap + smax) * sizeof(double);
     ints = off; off += ((size_t)STATE * wcap + smax) * sizeof(int);
+    if (order == 3) off += (size_t)2 * wcap * sizeof(int);
     lm = (off + 7) & ~(size_t)7;                                     // (8 bytes of room for that rounding)
     total = off + (lm_in_lds ? table_bytes(V) : 0);
   }
@@ -324,11 +337,12 @@ struct BeamCtx {                                 // what the phases of a frame w
 #ifdef CTCN_BEAM_STATS
   long long gst[16], glast;
 #endif
+  template <int ORDER>
   __device__ __forceinline__ void carve(unsigned char *lds_base) {
     tid = threadIdx.x; lane = tid & 63; wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (scalar: per-wave decisions are scalar branches)
     b = blockIdx.x; htmask = a.ht_size - 1;
     const int V = a.V, W = a.W, wcap = a.wcap;
-    const GenericLds l(V, W, wcap, a.smax, a.cand_in_lds, a.lm_in_lds);
+    const GenericLds l(V, W, wcap, a.smax, a.cand_in_lds, a.lm_in_lds, ORDER);
     lg = reinterpret_cast<double *>(lds_base);
     cand = a.cand_in_lds ? reinterpret_cast<double *>(lds_base + l.cand) : a.cand_global + (size_t)b * W * V;
     dbl = reinterpret_cast<double *>(lds_base + l.dbl);
@@ -342,8 +356,10 @@ struct BeamCtx {                                 // what the phases of a frame w
     vmagic = 0xffffffffu / (unsigned)V + 1u;
     vmagic_ok = (unsigned long long)W * V * V < (1ull << 32);          // (a vocabulary of thousands: the plain division)
   }
+  template <int ORDER>
   __device__ __forceinline__ BeamState state(int k) const {
     BeamState st;
+    st.prev = ORDER == 3 ? sv_i + a.smax + k * a.wcap : nullptr;
     st.pB = dbl + (3 * k) * a.wcap; st.pNB = st.pB + a.wcap; st.pT = st.pNB + a.wcap;
     st.node = ints + (4 * k) * a.wcap; st.len = st.node + a.wcap; st.last = st.len + a.wcap; st.par = st.last + a.wcap;
     return st;
@@ -367,7 +383,8 @@ __device__ __forceinline__ void find_parents(BeamCtx &c) {
 }
 // 3a. extension scores (calcExtPr) into the candidate table, slot c = i * V + class_col(k).  EU candidates per trip: the slot reads, then the
 // LM reads (a round trip to L2 unless the table is in LDS) of all of them are issued before the first is used.
-template <int NT>
+// ORDER 3: the LM term is tri[c0][c1][k] with (c0, c1) = (<s>, <s>) for the empty labelling, (<s>, y[0]) for one class, (y[-2], y[-1]) beyond.
+template <int NT, int ORDER>
 __device__ __forceinline__ void score_extensions(BeamCtx &c, bool rep_ok) {
   constexpr int EU = 4;
   const BeamState &L = c.L;
@@ -385,7 +402,9 @@ __device__ __forceinline__ void score_extensions(BeamCtx &c, bool rep_ok) {
 #pragma unroll
     for (int u = 0; u < EU; ++u) {
       const int c1 = cln[u] > 0 ? cl[u] : V;
-      lmv[u] = c.lm[(size_t)c1 * (V + 1) + max(ck[u], 0)];
+      size_t row = (size_t)c1;
+      if (ORDER == 3) row += (size_t)(cln[u] > 1 ? L.prev[ci[u]] : V) * (V + 1);
+      lmv[u] = c.lm[row * (V + 1) + max(ck[u], 0)];
     }
 #pragma unroll
     for (int u = 0; u < EU; ++u) {
@@ -649,6 +668,7 @@ __device__ __forceinline__ int select_top_w(BeamCtx &c, SelectShared<NT / 64> &s
   return arg_max_rounds<NT>(c.cand, ncand, W, ss.red_v, ss.red_i, c.sel, c.selv, c.wave, [] { __syncthreads(); }, [](int) {});
 }
 // 5. materialise the new beam N: entry r <- candidate sel[r]
+template <int ORDER>
 __device__ __forceinline__ void materialise(BeamCtx &c, int m, int *s_nodes) {
   if (c.tid >= m) return;
   const BeamState &L = c.L, &N = c.N;
@@ -657,6 +677,7 @@ __device__ __forceinline__ void materialise(BeamCtx &c, int m, int *s_nodes) {
   auto copy_slot = [&](int s) {
     N.node[tid] = L.node[s]; N.len[tid] = L.len[s]; N.last[tid] = L.last[s]; N.par[tid] = L.par[s];
     N.pNB[tid] = c.sNB[s]; N.pB[tid] = c.sB[s]; N.pT[tid] = c.sT[s];
+    if (ORDER == 3) N.prev[tid] = L.prev[s];
   };
   if (kk == 0) {
     copy_slot(i);
@@ -687,6 +708,7 @@ __device__ __forceinline__ void materialise(BeamCtx &c, int m, int *s_nodes) {
         h = (h + 1) & c.htmask;
       }
       N.node[tid] = id; N.len[tid] = L.len[i] + 1; N.last[tid] = k; N.par[tid] = parent;
+      if (ORDER == 3) N.prev[tid] = L.last[i];
       const double pr = c.selv[tid];
       N.pNB[tid] = pr; N.pB[tid] = LOG_ZERO; N.pT[tid] = pr;
     }
@@ -695,13 +717,13 @@ __device__ __forceinline__ void materialise(BeamCtx &c, int m, int *s_nodes) {
   if ((unsigned)nd < (unsigned)c.a.max_nodes) c.nslot[nd] = tid;     // (find_parents of the next frame finds a parent labelling's slot here)
 }
 
-template <int NT>
+template <int NT, int ORDER>
 __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];   // GenericLds
   __shared__ SelectShared<NT / 64> ss;
   __shared__ int s_flag, s_nodes;
   BeamCtx c = {a};
-  c.carve(dsm);
+  c.carve<ORDER>(dsm);
   const int tid = c.tid, lane = c.lane, b = c.b, V = a.V, B = a.B, T = a.T, blank = a.blank;
   if (a.lm_in_lds)                                               // (the raw ln-probs: lm_scaled() rounds the product with alpha on its own per use)
     for (int i = tid; i < (V + 1) * (V + 1); i += NT) const_cast<double *>(c.lm)[i] = a.lm[i];
@@ -713,8 +735,9 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
   long long gframes = 0;
 #endif
   if (tid == 0) {
-    const BeamState S0 = c.state(0);
+    const BeamState S0 = c.state<ORDER>(0);
     S0.node[0] = 0; S0.len[0] = 0; S0.last[0] = -1; S0.par[0] = -1;
+    if (ORDER == 3) S0.prev[0] = -1;
     S0.pB[0] = 0.0; S0.pNB[0] = LOG_ZERO; S0.pT[0] = 0.0;   // BeamSearch.py:83-87
     s_nodes = 1; s_flag = 0;
     c.npar[0] = -1; c.nsym[0] = -1;
@@ -738,7 +761,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
     pb_before = pblank;
     if ((1.0f - pblank) < 0.1f) continue;                         // BeamSearch.py:93-94 (float32 compare)
     const bool rep_ok = t > 0 && pprev < 0.9f;                    // BeamSearch.py:63 (float32 compare)
-    c.L = c.state(cur); c.N = c.state(cur ^ 1);
+    c.L = c.state<ORDER>(cur); c.N = c.state<ORDER>(cur ^ 1);
     GSTAMP(0);
 #ifdef CTCN_BEAM_STATS
     ++gframes;
@@ -752,7 +775,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
     __syncthreads();
     if (s_flag == 2) { status = 2; break; }
     GSTAMP(1);
-    score_extensions<NT>(c, rep_ok);
+    score_extensions<NT, ORDER>(c, rep_ok);
     __syncthreads();
     GSTAMP(2);
     merge_stays(c);
@@ -760,7 +783,7 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
     GSTAMP(3);
     const int m = select_top_w<NT>(c, ss);
     GSTAMP(4);
-    materialise(c, m, &s_nodes);
+    materialise<ORDER>(c, m, &s_nodes);
     __syncthreads();
     GSTAMP(5);
     c.nb = m;
@@ -770,9 +793,9 @@ __global__ __launch_bounds__(NT) void beam_kernel(BeamArgs a) {
 #ifdef CTCN_BEAM_STATS
   if (a.stats && b == 0 && tid == 0) { for (int i = 0; i < 16; ++i) a.stats[32 + i] = c.gst[i]; a.stats[48] = gframes; }
 #endif
-  const BeamState L = c.state(cur);
-  beam_finish(a, b, status, s_nodes > a.max_nodes, c.nb, L.len, L.last, L.node, L.pT, L.par, c.lm,
-              [&](int &n) { const int sym = c.nsym[n]; n = c.npar[n]; return sym; });
+  const BeamState L = c.state<ORDER>(cur);
+  beam_finish<ORDER>(a, b, status, s_nodes > a.max_nodes, c.nb, L.len, L.last, L.node, L.pT, L.par, c.lm,
+                     [&](int &n) { const int sym = c.nsym[n]; n = c.npar[n]; return sym; }, L.prev);
 }
 
 // =====================================================================================================================
@@ -854,8 +877,11 @@ constexpr int SURV_MAX = 256;
 constexpr int FAST_NCT = 1024 - 192;                           // candidate threads: waves 3..15
 constexpr int FAST_NTH = 1024, FAST_NWV = FAST_NTH / 64;      // 16 waves: the parallel phases are instruction-issue bound (~10 cycles per
                                                                // dependent instruction and wave), so more waves per SIMD is what shortens them
-template <int NPT, bool LM_LDS>
+// ORDER 3 (LM_LDS false: the (V+1)^3 table is read from global memory): every slot's record gets the class before the context class
+// (bm_c0 beside bm_c1), and wave 0 carries one class more per slot (z_pplast, y[-3]) for the parent's extension term in stay_and_merge.
+template <int NPT, bool LM_LDS, int ORDER = 2>
 __device__ __forceinline__ void beam_fast_body(FastArgs a) {
+  static_assert(ORDER == 2 || (ORDER == 3 && !LM_LDS), "the order-3 table stays in global memory");
   constexpr int NTH = FAST_NTH, NWV = FAST_NWV;
   extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];   // FastLdsT
   __shared__ Survivor surv[SURV_MAX];                                 // candidates above the pruning bound (order-preserving key, index)
@@ -867,6 +893,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   __shared__ double tots[64];                                         // per survivor: log_add(prBlank', prNonBlank') of the next frame if it is selected (wave 2)
   __shared__ int selm[FAST_WMAX];                                     // per selected candidate: 128 | slot whose merged entry it holds, 0: none, -1: see mslot[]
   __shared__ int bm_c1[2][FAST_WMAX], sel[FAST_WMAX];                 // context class of every slot, by frame parity
+  __shared__ int bm_c0[2][ORDER == 3 ? FAST_WMAX : 1], f_c0[ORDER == 3 ? FAST_WMAX : 1];   // order 3: the class before it (V: '<s>') | of the final beam
   __shared__ int f_node[FAST_WMAX], f_len[FAST_WMAX], f_last[FAST_WMAX];   // final beam (dumped once, after the last frame)
   __shared__ double f_pT[FAST_WMAX];
   __shared__ int woff[NWV];
@@ -905,6 +932,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   const int nframes = min(max(a.lens[b], 0), T);
   if (tid == 0) {
     bm_c1[0][0] = V; bm_pB[0] = 0.0; bm_pT[0] = 0.0;                             // the empty labelling: prBlank = prTotal = 0 (BeamSearch.py:83-87)
+    if (ORDER == 3) bm_c0[0][0] = V;
     s_nfl = 0; s_gnodes = 0; s_totflag = 0; s_beamflag = 0; s_decflag = 0; s_fault = 0;
   }
   if (tid < 64) gmax[tid] = 0u;                                                  // (rows 52..63 belong to no candidate wave: they stay 0)
@@ -1020,15 +1048,20 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
     // read of a hop issued before the first use (clamped addresses, selects afterwards)
     auto score_extensions = [&](bool rep_ok, int jf) {
       const double *lg = lg2 + (jf & 1) * V;
-      int c1[NPT];
+      int c1[NPT], c0[NPT];
 #pragma unroll
-      for (int i = 0; i < NPT; ++i) c1[i] = bm_c1[jf & 1][min(ci[i], FAST_WMAX - 1)];
+      for (int i = 0; i < NPT; ++i) {
+        c1[i] = bm_c1[jf & 1][min(ci[i], FAST_WMAX - 1)];
+        c0[i] = ORDER == 3 ? bm_c0[jf & 1][min(ci[i], FAST_WMAX - 1)] : 0;
+      }
       double lmv[NPT], pbv[NPT], ptv[NPT], lk[NPT];
 #pragma unroll
       for (int i = 0; i < NPT; ++i) {
         const int bi = min(ci[i], FAST_WMAX - 1), k = max(ck[i], 0);
         const int c1c = min(max(c1[i], 0), V);
-        lmv[i] = LM_LDS ? lmA[c1c * V1 + k] : lm_scaled(a.lm[(size_t)c1c * V1 + k], a.alpha);
+        size_t row = (size_t)c1c;
+        if (ORDER == 3) row += (size_t)min(max(c0[i], 0), V) * V1;
+        lmv[i] = LM_LDS ? lmA[c1c * V1 + k] : lm_scaled(a.lm[row * V1 + k], a.alpha);
         lk[i] = lg[k];
         pbv[i] = bm_pB[bi];
         ptv[i] = bm_pT[bi];
@@ -1185,6 +1218,7 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
     // grandparent labelling, last class of the parent labelling): a labelling created in this frame as (parent id p, class k) IS the
     // parent of slot r exactly when p == z_gpar[r] and k == z_plast[r] (ids are unique per (parent, class)), which needs old ids only.
     int z_len = 0, z_last = -1, z_par = -1, z_mf = -1, z_gpar = -2, z_plast = -1;
+    int z_pplast = -1;                                             // order 3: the class before z_plast (y[-3])
     double z_pB = 0.0, z_pNB = LOG_ZERO, z_pT = 0.0;
     double e_nb = LOG_ZERO, e_b = LOG_ZERO, e_t = LOG_ZERO;        // this frame's stay / merged entry of the slot (BeamSearch.py:99-113)
     // stay entries of every slot, merged with the extension of the parent slot that equals the labelling (same expression, same operands
@@ -1201,7 +1235,9 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
       // (context class of the parent labelling: its last class travels with the slot -- z_plast -- and its length is this one's minus one:
       // the LM term is read next to the ln p terms, not behind the parent slot)
       const int c1 = z_len > 1 ? max(z_plast, 0) : V, k = max(z_last, 0);
-      const double lmv = LM_LDS ? lmA[c1 * V1 + k] : lm_scaled(a.lm[(size_t)c1 * V1 + k], a.alpha);
+      size_t row = (size_t)c1;
+      if (ORDER == 3) row += (size_t)(z_len > 2 ? max(z_pplast, 0) : V) * V1;
+      const double lmv = LM_LDS ? lmA[c1 * V1 + k] : lm_scaled(a.lm[row * V1 + k], a.alpha);
       const double base = (c1 == k && rep_ok) ? p_pB : p_pT;
       const double pr = lgl + lmv + base;                           // == cand[mi * V + kk(z_last)]
       double s_nb = LOG_ZERO;
@@ -1278,16 +1314,20 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
       ns[lane] = -1;
       const int g_len = lane_gather(z_len, src), g_last = lane_gather(z_last, src), g_par = lane_gather(z_par, src);
       const int g_gpar = lane_gather(z_gpar, src), g_plast = lane_gather(z_plast, src);
+      const int g_pplast = ORDER == 3 ? lane_gather(z_pplast, src) : -1;
       const int g_nid = nid[j & 1][src];                           // id of the old slot's labelling (wave 1, previous frame)
       const int g_mf = lane_gather(z_mf, src);
       const double g_nb = lane_gather(e_nb, src), g_b = lane_gather(e_b, src), g_t = lane_gather(e_t, src);
       int n_len = g_len, n_last = g_last, n_par = g_par, n_gpar = g_gpar, n_plast = g_plast, n_mf = -1;
+      int n_pplast = g_pplast;
       double n_pNB = g_nb, n_pB = g_b, n_pT = g_t;
       if (fresh) {
         n_len = g_len + 1; n_last = sym; n_par = g_nid; n_gpar = g_len > 0 ? g_par : -2; n_plast = g_last;
+        n_pplast = g_plast;
         n_pNB = d.sv; n_pB = LOG_ZERO; n_pT = d.sv;
       }
       if (act) { bm_c1[(j + 1) & 1][lane] = n_len > 0 ? n_last : V; bm_pB[lane] = n_pB; bm_pT[lane] = n_pT; }
+      if (ORDER == 3 && act) bm_c0[(j + 1) & 1][lane] = n_len > 1 ? n_plast : V;
       if (act && !fresh) ns[src] = lane;                           // where the old slot's labelling went
       __hip_atomic_store(&s_beamflag, j + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       BSTAMP(5);
@@ -1321,12 +1361,14 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
         }
       }
       z_len = n_len; z_last = n_last; z_par = n_par; z_gpar = n_gpar; z_plast = n_plast; z_mf = n_mf; z_pNB = n_pNB; z_pB = n_pB; z_pT = n_pT;
+      if (ORDER == 3) z_pplast = n_pplast;
       if (more) stay_and_merge(rep_next, j + 1, tsrc);
       fw = fwn;
       lds_barrier();
       BSTAMP(2);
     }
     f_len[lane] = z_len; f_last[lane] = z_last; f_pT[lane] = z_pT;
+    if (ORDER == 3 && lane < FAST_WMAX) f_c0[lane] = z_plast;
   } else {
     // ======================================= waves 1 and 2: the trie | the stay totals ==========================================
     int y_node = 0, y_lnodes = 0;                                  // wave 1: node id of slot `lane`; LDS trie nodes so far (wave-uniform)
@@ -1481,12 +1523,12 @@ __device__ __forceinline__ void beam_fast_body(FastArgs a) {
   __syncthreads();
   if (status == 0 && s_fault) status = 4;
   // (f_pT is reused for the scores and f_last for the picks; a node is an LDS trie slot up to TS, an entry of the global table beyond)
-  beam_finish(a, b, status, s_gnodes > a.max_nodes, nb, f_len, f_last, f_node, f_pT, f_last, a.lm, [&](int &n) {
+  beam_finish<ORDER>(a, b, status, s_gnodes > a.max_nodes, nb, f_len, f_last, f_node, f_pT, f_last, a.lm, [&](int &n) {
     if (n <= TS) { const unsigned e = trie[n - 1]; n = (int)(e >> 17) - 1; return (int)(e & 0x1FFFFu); }
     const int gq = n - TS - 1;
     n = npar[gq];
     return nsym[gq];
-  });
+  }, f_c0);
 }
 
 // the two launch forms of the fast search.  beam_fast_kernel: one workgroup per CU (120 VGPRs, up to 144 KB of dynamic LDS: the 16 K-slot
@@ -1496,6 +1538,10 @@ template <int NPT, bool LM_LDS>
 __global__ __launch_bounds__(FAST_NTH) void beam_fast_kernel(FastArgs a) { beam_fast_body<NPT, LM_LDS>(a); }
 template <int NPT, bool LM_LDS>
 __global__ __launch_bounds__(FAST_NTH) __attribute__((amdgpu_waves_per_eu(8, 8))) void beam_fast_kernel_occ2(FastArgs a) { beam_fast_body<NPT, LM_LDS>(a); }
+template <int NPT>
+__global__ __launch_bounds__(FAST_NTH) void beam_fast_kernel_tri(FastArgs a) { beam_fast_body<NPT, false, 3>(a); }
+template <int NPT>
+__global__ __launch_bounds__(FAST_NTH) __attribute__((amdgpu_waves_per_eu(8, 8))) void beam_fast_kernel_tri_occ2(FastArgs a) { beam_fast_body<NPT, false, 3>(a); }
 
 // ---- Host side: plan_beam decides a call by arithmetic alone (ctcn_diag_beam_plan shows it to the CPU tests); the entry is check, plan, fill, launch ----
 struct BeamOptions { int fast, occ2, generic_threads, cand_global; };
@@ -1517,7 +1563,10 @@ struct BeamPlan {
   const BeamWorkspace &ws() const { return path == BP_GENERIC ? generic_ws : fast_ws; }
 };
 // (path, threads and the workspaces depend on neither lds_max nor generic_static_lds: the entry plans without them, then asks the device)
-BeamPlan plan_beam(int T, int B, int V, int W, const BeamOptions &o, int lds_max, int generic_static_lds) {
+// order 3: the (V+1)^3 table stays in global memory on every path (lm_lds = lm_in_lds = 0); the fast kernel's order-3 builds have 768 B
+// more static LDS, which the occ2 budget gives back so that two workgroups still share a CU; the generic kernel carries one class more
+// per beam slot (GenericLds).
+BeamPlan plan_beam(int T, int B, int V, int W, const BeamOptions &o, int lds_max, int generic_static_lds, int order = 2) {
   BeamPlan p = {};
   p.max_nodes = W * T + 2;
   p.ht_size = 1024;
@@ -1528,11 +1577,11 @@ BeamPlan plan_beam(int T, int B, int V, int W, const BeamOptions &o, int lds_max
   typedef FastLdsT<size_t> Lds;
   p.npt = ceil_div(W * V, FAST_NCT);                       // candidate slots per thread of waves 3..15 (1..4: W * V <= 3 328)
   if (p.npt > 4) p.npt = 0;
-  const size_t core = Lds(T, V, W, false, 0).total, lm = Lds::table_bytes(V), budget = o.occ2 ? 68 * 1024 : 144 * 1024;
-  const bool want_lm = lm <= 40 * 1024 && o.occ2 != 2;
+  const size_t core = Lds(T, V, W, false, 0).total, lm = Lds::table_bytes(V), budget = o.occ2 ? (order == 3 ? 67 : 68) * 1024 : 144 * 1024;
+  const bool want_lm = lm <= 40 * 1024 && o.occ2 != 2 && order == 2;
   p.trie_slots = 16384;
   while (p.trie_slots > 1024 && core + (size_t)p.trie_slots * 4 + (want_lm ? lm : 0) > budget) p.trie_slots >>= 1;
-  p.lm_lds = o.occ2 != 2 && core + (size_t)p.trie_slots * 4 + lm <= budget;
+  p.lm_lds = o.occ2 != 2 && order == 2 && core + (size_t)p.trie_slots * 4 + lm <= budget;
   p.fast_lds = Lds(T, V, W, p.lm_lds, p.trie_slots).total;
   p.fast_ok = W <= 60 && p.npt > 0 && V <= 256 && p.max_nodes < (1 << 24) && T < (1 << 22) && p.fast_lds <= budget;
   p.path = (p.fast_ok && o.fast != 0) ? (o.occ2 ? BP_FAST_OCC2 : BP_FAST) : BP_GENERIC;
@@ -1544,10 +1593,10 @@ BeamPlan plan_beam(int T, int B, int V, int W, const BeamOptions &o, int lds_max
   p.wcap = (W + 63) / 64 * 64;
   p.smax = std::max(1024, 2 * p.wcap);
   const size_t cand_bytes = (size_t)W * V * sizeof(double);
-  const size_t fixed = (size_t)generic_static_lds + GenericLds(V, W, p.wcap, p.smax, false, false).total + 256;
+  const size_t fixed = (size_t)generic_static_lds + GenericLds(V, W, p.wcap, p.smax, false, false, order).total + 256;
   p.cand_in_lds = fixed + cand_bytes <= (size_t)lds_max && !o.cand_global;
-  p.lm_in_lds = fixed + (p.cand_in_lds ? cand_bytes : 0) + GenericLds::table_bytes(V) <= (size_t)lds_max;
-  p.generic_lds = GenericLds(V, W, p.wcap, p.smax, p.cand_in_lds, p.lm_in_lds).total;
+  p.lm_in_lds = order == 2 && fixed + (p.cand_in_lds ? cand_bytes : 0) + GenericLds::table_bytes(V) <= (size_t)lds_max;
+  p.generic_lds = GenericLds(V, W, p.wcap, p.smax, p.cand_in_lds, p.lm_in_lds, order).total;
   p.generic_fits = (size_t)generic_static_lds + p.generic_lds <= (size_t)lds_max;
   // workspaces
   const size_t nodes = (size_t)B * p.max_nodes * sizeof(int), slots = (size_t)B * p.ht_size, tb = (size_t)T * B, wv = (size_t)B * W * V;
@@ -1572,7 +1621,11 @@ int lds_refused(const BeamPlan &p, int lds_max, int static_lds) {      // the ge
 void (*const fast_kernels[2][2][4])(FastArgs) = {{CTCN_NPT_ROW(beam_fast_kernel, false), CTCN_NPT_ROW(beam_fast_kernel, true)},
                                                  {CTCN_NPT_ROW(beam_fast_kernel_occ2, false), CTCN_NPT_ROW(beam_fast_kernel_occ2, true)}};
 #undef CTCN_NPT_ROW
-void (*const generic_kernels[3])(BeamArgs) = {beam_kernel<256>, beam_kernel<512>, beam_kernel<1024>};      // [threads / 512]
+void (*const fast_kernels_tri[2][4])(FastArgs) = {{beam_fast_kernel_tri<1>, beam_fast_kernel_tri<2>, beam_fast_kernel_tri<3>, beam_fast_kernel_tri<4>},
+                                                  {beam_fast_kernel_tri_occ2<1>, beam_fast_kernel_tri_occ2<2>, beam_fast_kernel_tri_occ2<3>,
+                                                   beam_fast_kernel_tri_occ2<4>}};       // [occ2][npt - 1]
+void (*const generic_kernels[2][3])(BeamArgs) = {{beam_kernel<256, 2>, beam_kernel<512, 2>, beam_kernel<1024, 2>},       // [order - 2][threads / 512]
+                                                 {beam_kernel<256, 3>, beam_kernel<512, 3>, beam_kernel<1024, 3>}};
 #ifdef CTCN_BEAM_STATS
 long long *g_beam_stats_dev = nullptr;
 #endif
@@ -1595,9 +1648,21 @@ extern "C" size_t ctcn_beam_ws_bytes(int T, int B, int V, int W) {
   const BeamPlan p = plan_beam(T, B, V, W, beam_options(), 0, 0);
   return std::max(p.generic_ws.total, p.fast_ws.total);
 }
-extern "C" int ctcn_diag_beam_plan(int T, int B, int V, int W, int lds_max, int generic_static_lds, int *out) {
+// Order of the LM table: 2 = (V+1)^2, 3 = (V+1)^3 of at most TRI_TABLE_MAX bytes (V <= 202; V = 128 is 17 MB).  Refused before any launch.
+constexpr size_t TRI_TABLE_MAX = (size_t)64 << 20;
+static int order_refused(int lm_order, int V) {
+  if (lm_order != 2 && lm_order != 3) { ctcn_set_error("ctcn_beam_decode: LM order %d (2 or 3 are built)", lm_order); return CTCN_EUNSUPPORTED; }
+  const size_t bytes = (size_t)(V + 1) * (V + 1) * (V + 1) * sizeof(double);
+  if (lm_order == 3 && bytes > TRI_TABLE_MAX) {
+    ctcn_set_error("ctcn_beam_decode: an order-3 table of %zu B at V = %d is beyond the cap of %zu B", bytes, V, TRI_TABLE_MAX);
+    return CTCN_EUNSUPPORTED;
+  }
+  return CTCN_OK;
+}
+extern "C" int ctcn_diag_beam_plan_lm(int T, int B, int V, int W, int lm_order, int lds_max, int generic_static_lds, int *out) {
   CTCN_REQUIRE(out && T > 0 && B > 0 && V > 1 && W >= 1 && W <= BEAM_WMAX && lds_max > 0 && generic_static_lds >= 0, "ctcn_diag_beam_plan: bad args");
-  const BeamPlan p = plan_beam(T, B, V, W, beam_options(), lds_max, generic_static_lds);
+  if (const int rc = order_refused(lm_order, V)) return rc;
+  const BeamPlan p = plan_beam(T, B, V, W, beam_options(), lds_max, generic_static_lds, lm_order);
   const size_t wf = p.fast_ws.total, wg = p.generic_ws.total;
   const int v[CTCN_BEAM_PLAN_INTS] = {(int)p.path, p.fast_ok, p.npt, p.lm_lds, p.trie_slots, (int)std::min(p.fast_lds, (size_t)INT32_MAX), p.threads, p.wcap,
                                       p.smax, p.cand_in_lds, p.lm_in_lds, (int)std::min(p.generic_lds, (size_t)INT32_MAX), p.generic_fits, p.max_nodes,
@@ -1605,27 +1670,31 @@ extern "C" int ctcn_diag_beam_plan(int T, int B, int V, int W, int lds_max, int 
   memcpy(out, v, sizeof(v));
   return lds_refused(p, lds_max, generic_static_lds);
 }
+extern "C" int ctcn_diag_beam_plan(int T, int B, int V, int W, int lds_max, int generic_static_lds, int *out) {
+  return ctcn_diag_beam_plan_lm(T, B, V, W, 2, lds_max, generic_static_lds, out);
+}
 
-extern "C" int ctcn_beam_decode_nbest(const float *x, int input_is_prob, const int32_t *lens, const double *lm, double alpha, int W,
-                                      int blank, int nbest, int32_t *out_ids, int32_t *out_len, double *out_score, int32_t *out_count,
-                                      int32_t *status, int T, int B, int V, void *ws, size_t ws_bytes, void *stream) {
+extern "C" int ctcn_beam_decode_lm(const float *x, int input_is_prob, const int32_t *lens, const double *lm, int lm_order, double alpha, int W,
+                                   int blank, int nbest, int32_t *out_ids, int32_t *out_len, double *out_score, int32_t *out_count,
+                                   int32_t *status, int T, int B, int V, void *ws, size_t ws_bytes, void *stream) {
   CTCN_REQUIRE(x && lens && lm && out_ids && out_len && out_score && status && ws, "ctcn_beam_decode: null pointer");
   CTCN_REQUIRE(T > 0 && B > 0 && V > 1 && blank >= 0 && blank < V, "ctcn_beam_decode: bad dims");
   if (W < 1 || W > BEAM_WMAX) { ctcn_set_error("ctcn_beam_decode: beam width %d outside [1,%d]", W, BEAM_WMAX); return CTCN_EUNSUPPORTED; }
   CTCN_REQUIRE(nbest >= 1 && nbest <= W, "ctcn_beam_decode_nbest: nbest %d outside [1, beam width %d]", nbest, W);
+  if (const int rc = order_refused(lm_order, V)) return rc;
   hipStream_t st = (hipStream_t)stream;
   char *base = (char *)ws;
   const BeamOptions o = beam_options();
-  BeamPlan p = plan_beam(T, B, V, W, o, 0, 0);
+  BeamPlan p = plan_beam(T, B, V, W, o, 0, 0, lm_order);
   int lds_max = 64 * 1024, static_lds = 0;
   if (p.path == BP_GENERIC) {      // its LDS placement needs two facts of the device: what one workgroup gets, what the instantiation takes statically
     hipFuncAttributes fa;
-    CTCN_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(generic_kernels[p.threads / 512])));
+    CTCN_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(generic_kernels[lm_order - 2][p.threads / 512])));
     int dev_id = 0;
     CTCN_HIP(hipGetDevice(&dev_id));
     if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id) != hipSuccess) lds_max = 64 * 1024;
     static_lds = (int)fa.sharedSizeBytes;
-    p = plan_beam(T, B, V, W, o, lds_max, static_lds);
+    p = plan_beam(T, B, V, W, o, lds_max, static_lds, lm_order);
   }
   const BeamWorkspace &w = p.ws();
   if (ws_bytes < w.total) { ctcn_set_error("ctcn_beam_decode: workspace too small (%zu < %zu)", ws_bytes, w.total); return CTCN_EWORKSPACE; }
@@ -1646,6 +1715,7 @@ extern "C" int ctcn_beam_decode_nbest(const float *x, int input_is_prob, const i
     hipLaunchKernelGGL(beam_prep_kernel, dim3((unsigned)ceil_div_z(rows, 4)), dim3(256), 0, st, x, input_is_prob, (double *)(base + w.lgd),
                        (float *)(base + w.pb), (unsigned char *)(base + w.zf), rows, V, blank);
     CTCN_LAUNCH_CHECK();
+    if (lm_order == 3) return launch_beam(fast_kernels_tri[p.path == BP_FAST_OCC2][p.npt - 1], B, FAST_NTH, p.lds(), st, a);
     return launch_beam(fast_kernels[p.path == BP_FAST_OCC2][p.lm_lds][p.npt - 1], B, FAST_NTH, p.lds(), st, a);
   }
   BeamArgs a;
@@ -1653,7 +1723,13 @@ extern "C" int ctcn_beam_decode_nbest(const float *x, int input_is_prob, const i
   a.x = x; a.input_is_prob = input_is_prob; a.ht_keys = (unsigned long long *)(base + w.ht); a.ht_ids = (int *)(base + w.ids);
   a.cand_global = (double *)(base + w.cand); a.node_slot = (int *)(base + w.nslot); a.cand_owner = (int *)(base + w.cown);
   a.wcap = p.wcap; a.smax = p.smax; a.cand_in_lds = p.cand_in_lds; a.lm_in_lds = p.lm_in_lds; a.bitonic = ctcn_get_option("beam_bitonic");
-  return launch_beam(generic_kernels[p.threads / 512], B, p.threads, p.lds(), st, a);
+  return launch_beam(generic_kernels[lm_order - 2][p.threads / 512], B, p.threads, p.lds(), st, a);
+}
+
+extern "C" int ctcn_beam_decode_nbest(const float *x, int input_is_prob, const int32_t *lens, const double *lm, double alpha, int W,
+                                      int blank, int nbest, int32_t *out_ids, int32_t *out_len, double *out_score, int32_t *out_count,
+                                      int32_t *status, int T, int B, int V, void *ws, size_t ws_bytes, void *stream) {
+  return ctcn_beam_decode_lm(x, input_is_prob, lens, lm, 2, alpha, W, blank, nbest, out_ids, out_len, out_score, out_count, status, T, B, V, ws, ws_bytes, stream);
 }
 
 extern "C" int ctcn_beam_decode(const float *x, int input_is_prob, const int32_t *lens, const double *lm, double alpha, int W,

@@ -1580,12 +1580,17 @@ BEAM_PLAN_FIELDS = ("path", "ok", "npt", "lm_lds", "trie_slots", "lds", "threads
                     "generic_fits", "max_nodes", "ht_size")
 
 
-def beam_plan(T, B, V, W, lds_max=160 * 1024, generic_static_lds=0):
+def beam_plan(T, B, V, W, lds_max=160 * 1024, generic_static_lds=0, lm_order=2):
     """ctcn_diag_beam_plan as a dict: the path ctcn_beam_decode takes under the current options (0 fast, 1 fast occ2, 2 generic), the fast
     kernel's fit (ok, npt, lm_lds, trie_slots, lds), the generic kernel's plan, the two workspace totals and rc (0, or -3 = CTCN_EUNSUPPORTED
-    where the decode call answers that).  Pure arithmetic: no device needed."""
+    where the decode call answers that).  lm_order = 3: the plan of a search with a (V+1)^3 table (ctcn_diag_beam_plan_lm).  Pure
+    arithmetic: no device needed."""
     out = (ctypes.c_int * 19)()
-    rc = _lib.lib().ctcn_diag_beam_plan(int(T), int(B), int(V), int(W), int(lds_max), int(generic_static_lds), ctypes.cast(out, ctypes.c_void_p))
+    if lm_order == 2:
+        rc = _lib.lib().ctcn_diag_beam_plan(int(T), int(B), int(V), int(W), int(lds_max), int(generic_static_lds), ctypes.cast(out, ctypes.c_void_p))
+    else:
+        rc = _lib.lib().ctcn_diag_beam_plan_lm(int(T), int(B), int(V), int(W), int(lm_order), int(lds_max), int(generic_static_lds),
+                                               ctypes.cast(out, ctypes.c_void_p))
     if rc not in (0, -3):
         _lib.check(rc, "diag_beam_plan")
     d = dict(zip(BEAM_PLAN_FIELDS, out))
@@ -1605,9 +1610,22 @@ def ctc_lattice_plan(Lmax):
     return dict(zip(CTC_LATTICE_PLAN_FIELDS, out))
 
 
+def _lm_order(lm_table, V):
+    """Order of the search's LM from the rank of its table: 2 for (V+1)^2 (any shape of that many elements, as ever), 3 for a 3-D table,
+    which must be (V+1, V+1, V+1).  Looks at the shape alone: a wrong table is a ValueError before anything is uploaded or launched."""
+    shape = tuple(lm_table.shape) if hasattr(lm_table, "shape") else np.shape(lm_table)
+    if len(shape) != 3:
+        return 2
+    if shape != (V + 1,) * 3:
+        raise ValueError("a 3-D lm table must be (V+1, V+1, V+1) = %s, got %s" % ((V + 1,) * 3, shape))
+    return 3
+
+
 def beam_decode_device(x_tbv, lens, lm_table, alpha, beam_width, blank=0, input_is_prob=False):
     """Enqueue the prefix beam search (ctcn_beam_decode) on the current stream; returns DEVICE tensors
-    (out_ids (B,T) int32, out_len (B) int32, score (B) float64, status (B) int32) without synchronising."""
+    (out_ids (B,T) int32, out_len (B) int32, score (B) float64, status (B) int32) without synchronising.
+    lm_table: (V+1, V+1) = a bigram LM, or (V+1, V+1, V+1) = a trigram LM (ctcn_beam_decode_lm, order 3)."""
+    order = _lm_order(lm_table, x_tbv.shape[-1])
     _need_gpu(x_tbv)
     x = _f32c(x_tbv.detach())
     T, B, V = x.shape
@@ -1618,7 +1636,7 @@ def beam_decode_device(x_tbv, lens, lm_table, alpha, beam_width, blank=0, input_
         lens_h = torch.as_tensor(lens, dtype=torch.int32).contiguous().pin_memory()
         lens_t = lens_h.to(dev, non_blocking=True)
     lm = torch.as_tensor(lm_table, dtype=torch.float64, device=dev).contiguous()
-    if lm.numel() != (V + 1) * (V + 1):
+    if order == 2 and lm.numel() != (V + 1) * (V + 1):
         raise ValueError("lm table must be (V+1)x(V+1)")
     L = _lib.lib()
     nb = L.ctcn_beam_ws_bytes(T, B, V, int(beam_width))
@@ -1629,6 +1647,11 @@ def beam_decode_device(x_tbv, lens, lm_table, alpha, beam_width, blank=0, input_
     out_ids = out[8 * B: 8 * B + 4 * B * T].view(torch.int32).view(B, T)
     out_len = out[8 * B + 4 * B * T: 8 * B + 4 * B * T + 4 * B].view(torch.int32)
     status = out[8 * B + 4 * B * T + 4 * B:].view(torch.int32)
+    if order == 3:
+        _lib.check(L.ctcn_beam_decode_lm(_ptr(x), int(bool(input_is_prob)), _ptr(lens_t), _ptr(lm), 3, float(alpha), int(beam_width), int(blank), 1,
+                                         _ptr(out_ids), _ptr(out_len), _ptr(score), None, _ptr(status), T, B, V, _ptr(ws), ws.numel(),
+                                         _lib.stream_ptr()), "beam_decode_lm")
+        return out_ids, out_len, score, status
     _lib.check(L.ctcn_beam_decode(_ptr(x), int(bool(input_is_prob)), _ptr(lens_t), _ptr(lm), float(alpha), int(beam_width), int(blank),
                                   _ptr(out_ids), _ptr(out_len), _ptr(score), _ptr(status), T, B, V, _ptr(ws), ws.numel(),
                                   _lib.stream_ptr()), "beam_decode")
@@ -1769,6 +1792,7 @@ def beam_decode_nbest(x_tbv, lens, lm_table, alpha, beam_width, nbest, blank=0, 
     """The `nbest` best labellings of every utterance (ctcn_beam_decode_nbest: the first nbest entries of the reference's final `last.sort()`,
     BeamSearch.py:150 keeps [0]).  Returns CPU (ids: per utterance a list of up to nbest label lists, best first; scores (B, nbest) float64,
     0 past the labellings returned; status (B,) int32).  Synchronises."""
+    order = _lm_order(lm_table, x_tbv.shape[-1])
     _need_gpu(x_tbv)
     x = _f32c(x_tbv.detach())
     T, B, V = x.shape
@@ -1778,7 +1802,7 @@ def beam_decode_nbest(x_tbv, lens, lm_table, alpha, beam_width, nbest, blank=0, 
         raise ValueError("nbest must lie in [1, beam_width]")
     lens_t = lens.to(device=dev, dtype=torch.int32).contiguous() if torch.is_tensor(lens) else torch.as_tensor(lens, dtype=torch.int32).to(dev)
     lm = torch.as_tensor(lm_table, dtype=torch.float64, device=dev).contiguous()
-    if lm.numel() != (V + 1) * (V + 1):
+    if order == 2 and lm.numel() != (V + 1) * (V + 1):
         raise ValueError("lm table must be (V+1)x(V+1)")
     L = _lib.lib()
     ws = torch.empty(max(L.ctcn_beam_ws_bytes(T, B, V, int(beam_width)), 1), dtype=torch.uint8, device=dev)
@@ -1787,9 +1811,14 @@ def beam_decode_nbest(x_tbv, lens, lm_table, alpha, beam_width, nbest, blank=0, 
     score = torch.zeros((B, nbest), dtype=torch.float64, device=dev)
     count = torch.zeros(B, dtype=torch.int32, device=dev)
     status = torch.zeros(B, dtype=torch.int32, device=dev)
-    _lib.check(L.ctcn_beam_decode_nbest(_ptr(x), int(bool(input_is_prob)), _ptr(lens_t), _ptr(lm), float(alpha), int(beam_width), int(blank), nbest,
-                                        _ptr(out_ids), _ptr(out_len), _ptr(score), _ptr(count), _ptr(status), T, B, V, _ptr(ws), ws.numel(),
-                                        _lib.stream_ptr()), "beam_decode_nbest")
+    if order == 3:
+        _lib.check(L.ctcn_beam_decode_lm(_ptr(x), int(bool(input_is_prob)), _ptr(lens_t), _ptr(lm), 3, float(alpha), int(beam_width), int(blank), nbest,
+                                         _ptr(out_ids), _ptr(out_len), _ptr(score), _ptr(count), _ptr(status), T, B, V, _ptr(ws), ws.numel(),
+                                         _lib.stream_ptr()), "beam_decode_lm")
+    else:
+        _lib.check(L.ctcn_beam_decode_nbest(_ptr(x), int(bool(input_is_prob)), _ptr(lens_t), _ptr(lm), float(alpha), int(beam_width), int(blank), nbest,
+                                            _ptr(out_ids), _ptr(out_len), _ptr(score), _ptr(count), _ptr(status), T, B, V, _ptr(ws), ws.numel(),
+                                            _lib.stream_ptr()), "beam_decode_nbest")
     ids_c, len_c, cnt = out_ids.cpu().numpy(), out_len.cpu().numpy(), count.cpu().numpy()
     ids = [[list(map(int, ids_c[b, k, : len_c[b, k]])) for k in range(cnt[b])] for b in range(B)]
     return ids, score.cpu().numpy(), status.cpu().numpy()

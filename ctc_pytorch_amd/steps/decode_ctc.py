@@ -229,6 +229,24 @@ def ctm_options(opts):
     return {"ctm": str(path), "ctm_frame_shift": float(getattr(opts, "ctm_frame_shift", 0.01))}
 
 
+def lm_order_option(opts):
+    """The key `lm_order` of a Config: 2 (the default: the reference's bigram search) or 3 (the ARPA file's \\3-grams: section is used)."""
+    order = int(getattr(opts, "lm_order", 2) or 2)
+    if order not in (2, 3):
+        raise ValueError("lm_order must be 2 or 3, got %r" % (order,))
+    return order
+
+
+def make_decoder(opts, index2word):
+    """test_ctc.make_decoder; with lm_order 3 and a beam decode_type the BeamDecoder is built with a trigram LM."""
+    order = lm_order_option(opts)
+    if order == 2 or opts.decode_type == "Greedy":
+        return test_ctc.make_decoder(opts, index2word)
+    from ctc_pytorch_amd.utils.ctcDecoder import BeamDecoder
+    return BeamDecoder(index2word, beam_width=opts.beam_width, blank_index=0, space_idx=-1, lm_path=opts.lm_path, lm_alpha=opts.lm_alpha,
+                       lm_order=order)
+
+
 def apply_argv(conf, a):
     """The command line's switches laid over the YAML's keys; a switch that was not given leaves its key alone."""
     if a.error_report:
@@ -245,6 +263,8 @@ def apply_argv(conf, a):
         conf["ctm_frame_shift"] = a.ctm_frame_shift
     if a.device_context:
         conf["device_context"] = True
+    if a.lm_order is not None:
+        conf["lm_order"] = a.lm_order
     return conf
 
 
@@ -258,6 +278,7 @@ def arg_parser():
     ap.add_argument("--ctm", default=None, metavar="PATH", help="write the recognised tokens with start, duration and confidence to this NIST CTM file (default: the YAML's ctm, else off)")
     ap.add_argument("--ctm-frame-shift", default=None, type=float, help="seconds per model input frame (default: the YAML's ctm_frame_shift, else 0.01)")
     ap.add_argument("--device-context", action="store_true", help="read the archive as base features and splice / skip / pad on the GPU (default: the YAML's device_context, else off)")
+    ap.add_argument("--lm-order", default=None, type=int, choices=[2, 3], help="order of the beam search's LM: 3 reads the ARPA file's 3-gram section (default: the YAML's lm_order, else 2)")
     return ap
 
 
@@ -271,7 +292,7 @@ def main(conf, test_loader=None, index2word=None, log=print):
     report = bool(getattr(opts, "error_report", False))
     ctm = ctm_options(opts)
     context = device_context(opts)
-    if not epoch_options(opts) and not report and not ctm and context is None:
+    if not epoch_options(opts) and not report and not ctm and context is None and lm_order_option(opts) == 2:
         return test_ctc.main(conf, test_loader=test_loader, index2word=index2word, log=log)
     if not getattr(opts, "use_gpu", True):
         raise RuntimeError("ctc_pytorch_amd: use_gpu must be True -- the HIP path has no CPU fallback")
@@ -292,7 +313,7 @@ def main(conf, test_loader=None, index2word=None, log=print):
     if context is not None:                                # (a loader handed in must be a base-feature loader too)
         from ctc_pytorch_amd.utils.data_loader import DeviceContext
         test_loader = _labels_on_host(DeviceContext(test_loader, device, context))
-    decoder = test_ctc.make_decoder(opts, index2word)
+    decoder = make_decoder(opts, index2word)
     stats = class_map = None
     if report:
         from ctc_pytorch_amd.utils.scoring import ErrorStats

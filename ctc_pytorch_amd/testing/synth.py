@@ -101,13 +101,21 @@ def fill_state_dict(shapes, seed):
     return out
 
 
-def write_arpa(path, units, seed=7, n_bigrams=600):
+def write_arpa(path, units, seed=7, n_bigrams=600, n_trigrams=0):
     """Synthetic phone bigram LM in the exact text format NgramLM.initngrams parses
     (/root/reference/timit/utils/NgramLM.py:38-56): header lines ``\\1-grams:`` /
-    ``\\2-grams:``, TAB-separated ``log10prob<TAB>token[<TAB>log10backoff]``."""
+    ``\\2-grams:``, TAB-separated ``log10prob<TAB>token[<TAB>log10backoff]``.
+    n_trigrams > 0: every bigram that can open a trigram (its second token is not ``</s>``) gets a back-off weight and a
+    ``\\3-grams:`` section of that many entries follows; about a third of them extend a pair that is NO bigram entry (back-off
+    through an absent bigram), and ``<s>`` only ever stands first.  The trigram draws come from a stream of their own, so the
+    unigram and bigram lines are the ones n_trigrams = 0 writes, but for the added back-off column."""
     rs = np.random.RandomState(seed)
+    rs3 = np.random.RandomState(seed + 1000003)
     toks = ["<s>", "</s>", "<unk>"] + list(units)
-    lines = ["", "\\data\\", "ngram 1=%d" % len(toks), "ngram 2=%d" % n_bigrams, "", "\\1-grams:"]
+    lines = ["", "\\data\\", "ngram 1=%d" % len(toks), "ngram 2=%d" % n_bigrams]
+    if n_trigrams:
+        lines.append("ngram 3=%d" % n_trigrams)
+    lines += ["", "\\1-grams:"]
     for t in toks:
         p = -3.0 * rs.random_sample()
         if t == "</s>":
@@ -125,7 +133,25 @@ def write_arpa(path, units, seed=7, n_bigrams=600):
         if (a, b) in seen:
             continue
         seen.add((a, b))
-        lines.append("%.6f\t%s %s" % (-3.0 * rs.random_sample(), a, b))
+        if n_trigrams and b != "</s>":
+            lines.append("%.6f\t%s %s\t%.6f" % (-3.0 * rs.random_sample(), a, b, -1.0 * rs3.random_sample()))
+        else:
+            lines.append("%.6f\t%s %s" % (-3.0 * rs.random_sample(), a, b))
+    if n_trigrams:
+        lines += ["", "\\3-grams:"]
+        heads = sorted(ab for ab in seen if ab[1] != "</s>")
+        mids = [t for t in toks if t not in ("<s>", "</s>")]
+        seen3 = set()
+        while len(seen3) < n_trigrams:
+            if rs3.random_sample() < 2.0 / 3.0:
+                a, b = heads[rs3.randint(len(heads))]
+            else:
+                a, b = firsts[rs3.randint(len(firsts))], mids[rs3.randint(len(mids))]
+            c = seconds[rs3.randint(len(seconds))]
+            if (a, b, c) in seen3:
+                continue
+            seen3.add((a, b, c))
+            lines.append("%.6f\t%s %s %s" % (-3.0 * rs3.random_sample(), a, b, c))
     lines += ["", "\\end\\", ""]
     with open(path, "w") as f:
         f.write("\n".join(lines))

@@ -10,6 +10,7 @@ LOG_ONE = 0.0
 
 class ctcBeamSearch(object):
     def __init__(self, classes, beam_width, lm, lm_alpha=0.01, blank_index=0):
+        """lm: a LanguageModel, whose n_gram (2 or 3) is the order of the search: its table() is (V+1)^2 or (V+1)^3."""
         self.classes = classes
         self.beamWidth = beam_width
         self.lm_alpha = lm_alpha
@@ -24,7 +25,7 @@ class ctcBeamSearch(object):
         return self._table
 
     def _lm_table_on(self, device):
-        """The (V+1) x (V+1) table as a float64 tensor on `device`, uploaded once."""
+        """The LM table ((V+1)^2, or (V+1)^3 for a trigram LM) as a float64 tensor on `device`, uploaded once."""
         key = (device.type, device.index)
         if getattr(self, "_table_dev", None) is None or self._table_dev[0] != key:
             self._table_dev = (key, torch.as_tensor(self._lm_table(), dtype=torch.float64).to(device))

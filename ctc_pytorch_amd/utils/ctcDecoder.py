@@ -262,12 +262,13 @@ class GreedyDecoder(Decoder):
 
 
 class BeamDecoder(Decoder):
-    def __init__(self, int2char, beam_width=200, blank_index=0, space_idx=-1, lm_path=None, lm_alpha=0.01):
+    def __init__(self, int2char, beam_width=200, blank_index=0, space_idx=-1, lm_path=None, lm_alpha=0.01, lm_order=2):
+        """lm_order: 2 = the reference's bigram search; 3 = the ARPA file's \\3-grams: section joins it (LanguageModel(n_gram=3))."""
         self.beam_width = beam_width
         super().__init__(int2char, space_idx=space_idx, blank_index=blank_index)
         from ctc_pytorch_amd.utils import BeamSearch as uBeam
         from ctc_pytorch_amd.utils import NgramLM as uNgram
-        lm = uNgram.LanguageModel(arpa_file=lm_path)
+        lm = uNgram.LanguageModel(arpa_file=lm_path, n_gram=lm_order)
         self._decoder = uBeam.ctcBeamSearch(int2char, beam_width, lm, lm_alpha=lm_alpha, blank_index=blank_index)
 
     def decode(self, prob_tensor, frame_seq_len=None):

@@ -1091,6 +1091,19 @@ int ctcn_beam_decode(const float *x, int input_is_prob, const int32_t *lens, con
 int ctcn_beam_decode_nbest(const float *x, int input_is_prob, const int32_t *lens, const double *lm, double alpha,
                            int W, int blank, int nbest, int32_t *out_ids, int32_t *out_len, double *out_score,
                            int32_t *out_count, int32_t *status, int T, int B, int V, void *ws, size_t ws_bytes, void *stream);
+/* The same search with a language model of order `lm_order`:
+ *   2: lm is the (V+1)^2 table above -- the launches and the bits of ctcn_beam_decode_nbest (which is this call with lm_order = 2);
+ *   3: lm is ((V+1)^3) float64 ln-probs tri[c0][c1][k] = ln P(k | c0, c1); index V = '<s>' for c0 and c1, '</s>' for k.  The LM term of an
+ *      extension of labelling y by class k (and of the final step, k = V) is tri[V][V][k] for len(y) == 0, tri[V][y[0]][k] for len(y) == 1,
+ *      tri[y[-2]][y[-1]][k] beyond; everything else is the search above, on the same paths (the fast kernel and its occ2 builds where
+ *      order 2 takes them, the generic kernel elsewhere: every width 1..1 024; the order is a template parameter of both).  The table
+ *      stays in global memory (63^3 doubles = 2.0 MB sit in an XCD's L2); every beam slot carries one class more (154 KB of LDS at
+ *      W = 1 024).  All paths return the same bits, and a context-free table (tri[c0] = lm for every c0) the bits of order 2.  A table
+ *      beyond 64 MiB (V > 202) and any other order: CTCN_EUNSUPPORTED before any launch.  Cost: DESIGN section 7s.
+ *   ws: >= ctcn_beam_ws_bytes(T,B,V,W) for either order; out_count may be NULL; nbest = 1 gives ctcn_beam_decode's outputs. */
+int ctcn_beam_decode_lm(const float *x, int input_is_prob, const int32_t *lens, const double *lm, int lm_order, double alpha,
+                        int W, int blank, int nbest, int32_t *out_ids, int32_t *out_len, double *out_score,
+                        int32_t *out_count, int32_t *status, int T, int B, int V, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Diagnostics (not on the compute path).
@@ -1144,6 +1157,9 @@ int ctcn_diag_dx_plan(int M, int N, int K, int lda, int precision, int a_mod16, 
  * answers it: the generic kernel is taken and its LDS does not fit.  Pure arithmetic, no device needed. */
 #define CTCN_BEAM_PLAN_INTS 19
 int ctcn_diag_beam_plan(int T, int B, int V, int W, int lds_max, int generic_static_lds, int *out);
+/* ... of ctcn_beam_decode_lm at LM order `lm_order`; 2 gives ctcn_diag_beam_plan's answer.  CTCN_EUNSUPPORTED (out untouched) for an order
+ * other than 2 or 3 and for an order-3 table beyond the cap. */
+int ctcn_diag_beam_plan_lm(int T, int B, int V, int W, int lm_order, int lds_max, int generic_static_lds, int *out);
 /* ctcn_diag_ctc_lattice_plan: the launch of a CTC lattice pass over label rows of Lmax symbols (S = 2 Lmax + 1 states) under the current
  * "ctc_lattice_skew" -- the plan of ctc.hip's plan_ctc_lattice.  out[CTCN_CTC_LATTICE_PLAN_INTS] = skewed (1) or classic (0) kernel, waves of
  * 64 states that cover the lattice (ceil(S / 64)), states per thread, threads per workgroup, dynamic LDS bytes, and the skew of the skewed
