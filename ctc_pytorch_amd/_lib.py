@@ -325,6 +325,17 @@ def stream_ptr():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _need_gpu(*ts):
+    for t in ts:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("ctc_pytorch_amd: tensor on %s -- the HIP path needs a ROCm device tensor "
+                               "(there is no CPU fallback)" % t.device)
+
+
 _STATUS = {}
 
 

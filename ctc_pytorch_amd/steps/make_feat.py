@@ -74,7 +74,7 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from ctc_pytorch_amd.utils.data_loader import write_kaldi_ark  # noqa: E402
-from ctc_pytorch_amd import ops  # noqa: E402
+from ctc_pytorch_amd import frontend  # noqa: E402
 from ctc_pytorch_amd.utils.features import (Fbank, FbankConfig, FrameContext, GlobalCMVN, LogSpecConfig, LogSpectrum, Mfcc, MfccConfig,  # noqa: E402
                                             Pitch, PitchConfig, ProcessPitchConfig, Reverberate, Spectrogram, Resampler, SlidingCMVN,
                                             SpeakerCMVN, SpectrogramConfig, paste_features, read_utt2spk, read_wave)
@@ -273,7 +273,7 @@ class PitchColumns(object):
         if self.stats is None:
             return pitch
         groups = None if self.groups is None else [self.groups[i] for i in idx]
-        return ops.cmvn_apply(pitch, frames, self.stats, groups, norm_vars=self.norm_vars)
+        return frontend.cmvn_apply(pitch, frames, self.stats, groups, norm_vars=self.norm_vars)
 
 
 def joined_stats(base, pitch):

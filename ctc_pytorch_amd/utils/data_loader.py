@@ -8,7 +8,7 @@ double matrices, `scp` entries of the form `utt path:offset`).  Batches have exa
 zero-padded, target_sizes (B) int64, utt_list).
 
 Base-feature mode (SpeechDataset(base_features=True), create_base_input, BaseFeatureLoader, DeviceContext): the archive's matrices are collated
-and staged as they are, with their int32 frame counts, and the splice / frame skip / downsample pad run on the GPU (ops.frame_context); the
+and staged as they are, with their int32 frame counts, and the splice / frame skip / downsample pad run on the GPU (frontend.frame_context); the
 batches that come out are the ones above, bit for bit.
 """
 import struct
@@ -293,7 +293,7 @@ class DevicePrefetcher(object):
 class DeviceContext(DevicePrefetcher):
     """DevicePrefetcher over a loader of BASE features (BaseFeatureLoader, or parallel.ShardedBatches around one): the batch is staged as the
     archive holds it -- (left + 1 + right) / skip times fewer bytes over PCIe and through the pinned copy -- and spliced, frame-skipped and padded
-    on the device by one launch on the copy stream (utils/features.FrameContext: ops.frame_context), which also writes the float32 length
+    on the device by one launch on the copy stream (utils/features.FrameContext: frontend.frame_context), which also writes the float32 length
     fractions.  Yields what DevicePrefetcher yields over the host path, bit for bit: (inputs (B, T', F'), input_sizes fractions, targets,
     target_sizes, utt_list[, B_global]).  The frame counts reach the kernel as the loader's int32 values.  A shard of a global batch is padded to
     the global T_max and its output is sized from that, so its fractions are the global batch's.

@@ -3,27 +3,27 @@ binaries of the reference's timit/steps/make_feat.sh (compute-fbank-feats --conf
 --norm-vars=true with one global mean and variance); steps/make_feat.py is the driver.
 
   FbankConfig   Kaldi's option names and defaults; from_kaldi_conf reads a `--key=value` file such as the reference's conf/fbank.conf
-  Fbank         the configured front-end on one device (ops.fbank behind it; holds the uploaded plan)
+  Fbank         the configured front-end on one device (frontend.fbank behind it; holds the uploaded plan)
   MfccConfig    the same for compute-mfcc-feats (the recipe's feat_type=mfcc, conf/mfcc.conf): Kaldi's MFCC defaults, use_energy = true
-  Mfcc          the MFCC front-end (ops.mfcc: the same kernel with the DCT, the lifter and Kaldi's column rules behind its log-mel stage)
+  Mfcc          the MFCC front-end (frontend.mfcc: the same kernel with the DCT, the lifter and Kaldi's column rules behind its log-mel stage)
   SpectrogramConfig / Spectrogram   compute-spectrogram-feats (the recipe's feat_type=spectrogram): the log power of every FFT bin, the log
-                energy in column 0 (ops.spectrogram: the same kernel without the mel bank)
+                energy in column 0 (frontend.spectrogram: the same kernel without the mel bank)
   LogSpecConfig / LogSpectrum       the recipe's own spectrogram (local/make_spectrum.py: a centred STFT of 400 points, log1p of the magnitude,
-                one mean and standard deviation per utterance; ops.log_spectrum)
-  GlobalCMVN    Kaldi's 2 x (F + 1) statistics, accumulated on the device (ops.cmvn_accumulate), its text file, mean and 1 / stddev
+                one mean and standard deviation per utterance; frontend.log_spectrum)
+  GlobalCMVN    Kaldi's 2 x (F + 1) statistics, accumulated on the device (frontend.cmvn_accumulate), its text file, mean and 1 / stddev
   SpeakerCMVN   the same statistics per speaker (compute-cmvn-stats --spk2utt, apply-cmvn --utt2spk; one speaker per utterance: per-utterance
-                CMVN), accumulated and applied on the device (ops.cmvn_accumulate_groups, ops.cmvn_apply), its text archive; read_utt2spk
-  SlidingCMVN   Kaldi's apply-cmvn-sliding (ops.cmvn_sliding): normalisation over a running window, for data without speaker labels
-  Resampler     a waveform batch at another sample rate (ops.resample: Kaldi's LinearResample, what its binaries run under --allow-downsample /
+                CMVN), accumulated and applied on the device (frontend.cmvn_accumulate_groups, frontend.cmvn_apply), its text archive; read_utt2spk
+  SlidingCMVN   Kaldi's apply-cmvn-sliding (frontend.cmvn_sliding): normalisation over a running window, for data without speaker labels
+  Resampler     a waveform batch at another sample rate (frontend.resample: Kaldi's LinearResample, what its binaries run under --allow-downsample /
                 --allow-upsample); SpeedPerturb: the recipe's three-way speed perturbation (perturb_data_dir_speed.sh) as one Resampler per factor
   FrameContext  the stage behind them: Kaldi's add-deltas, frame splicing, frame skipping and the pad to a multiple of n_downsample on the
-                device (ops.frame_context) -- what utils/data_loader.py does per utterance on the host; its output is the model's input
-  SpecAugment   the online augmentation between the two: time warp, frequency masks and time masks of the base batch (ops.spec_augment),
+                device (frontend.frame_context) -- what utils/data_loader.py does per utterance on the host; its output is the model's input
+  SpecAugment   the online augmentation between the two: time warp, frequency masks and time masks of the base batch (frontend.spec_augment),
                 redrawn for every utterance of every epoch from (seed, running utterance index)
   Reverberate   multi-condition data on the waveform, in front of any of the front-ends: a room impulse response convolved into the utterance
-                and background noise added at a drawn SNR (ops.reverberate; Kaldi's wav-reverberate), drawn from (seed, running index)
-  PitchConfig / ProcessPitchConfig / Pitch   Kaldi's pitch features (compute-kaldi-pitch-feats, process-kaldi-pitch-feats: ops.pitch,
-                ops.pitch_process): NCCF over geometric lags, a Viterbi search, the probability of voicing; three columns under the defaults.
+                and background noise added at a drawn SNR (frontend.reverberate; Kaldi's wav-reverberate), drawn from (seed, running index)
+  PitchConfig / ProcessPitchConfig / Pitch   Kaldi's pitch features (compute-kaldi-pitch-feats, process-kaldi-pitch-feats: frontend.pitch,
+                frontend.pitch_process): NCCF over geometric lags, a Viterbi search, the probability of voicing; three columns under the defaults.
                 paste_features: paste-feats --length-tolerance, the `fbank + pitch` of Kaldi's make_fbank_pitch.sh
   read_wave     RIFF PCM-16 mono and uncompressed NIST SPHERE (TIMIT's) -> int16 samples
 
@@ -33,7 +33,7 @@ import struct
 import numpy as np
 import torch
 
-from .. import _lib, ops
+from .. import _lib, frontend
 
 WINDOW_TYPES = ("hamming", "hanning", "povey", "rectangular", "blackman")     # the order of ctcn_fbank_opts.window_type
 LOGSPEC_WINDOWS = ("hamming", "hann", "blackman", "bartlett")                  # the order of ctcn_logspec_opts.window
@@ -240,33 +240,33 @@ class _FrontEnd(object):
 class Fbank(_FrontEnd):
     """The filterbank front-end of one FbankConfig on one device.  Building it builds the plan: a configuration outside the kernel's range (a
     padded frame other than 256 / 512 / 1024 samples, more than 128 mel bins, round_to_power_of_two=false) raises RuntimeError here."""
-    _plan_type = ops.FbankPlan
-    _op = staticmethod(ops.fbank)
+    _plan_type = frontend.FbankPlan
+    _op = staticmethod(frontend.fbank)
 
 
 class Mfcc(_FrontEnd):
     """The MFCC front-end of one MfccConfig on one device: Fbank's call signature and return layout with F = num_ceps.  Beyond Fbank's
     limits, num_ceps outside [1, num_mel_bins], more than 64 cepstra or a negative lifter raise RuntimeError here."""
-    _plan_type = ops.MfccPlan
-    _op = staticmethod(ops.mfcc)
+    _plan_type = frontend.MfccPlan
+    _op = staticmethod(frontend.mfcc)
 
 
 class Spectrogram(_FrontEnd):
     """The spectrogram front-end of one SpectrogramConfig on one device: Fbank's call signature and return layout with F = Npad / 2 + 1
     (257 under the defaults).  A padded frame other than 256 / 512 / 1024 samples, round_to_power_of_two=false or return_raw_fft=true raise
     RuntimeError here."""
-    _plan_type = ops.SpectrogramPlan
-    _op = staticmethod(ops.spectrogram)
+    _plan_type = frontend.SpectrogramPlan
+    _op = staticmethod(frontend.spectrogram)
 
 
 class LogSpectrum(object):
-    """The recipe's own spectrogram of one LogSpecConfig on one device (ops.log_spectrum).  Building it builds the plan: an n_fft other than
+    """The recipe's own spectrogram of one LogSpecConfig on one device (frontend.log_spectrum).  Building it builds the plan: an n_fft other than
     256, 400, 512 or 1024 raises RuntimeError here.  Normalisation is per utterance and part of the call; there is no mean / scale."""
 
     def __init__(self, config, device):
         self.config = config
         self.device = torch.device(device)
-        self.plan = ops.LogSpecPlan(config.c_opts())
+        self.plan = frontend.LogSpecPlan(config.c_opts())
         self.feat_dim = self.plan.feat_dim
 
     def num_frames(self, num_samples):
@@ -276,27 +276,27 @@ class LogSpectrum(object):
         """waves as Fbank takes them.  Returns (feats (B, Tmax, F) float32 zero-padded, frames (B) int32, stats (B, 2) float32: the mean and
         standard deviation of each utterance) on the device."""
         waves, lengths = _batch("LogSpectrum", waves, lengths)
-        return ops.log_spectrum(waves.to(self.device), lengths, self.plan)
+        return frontend.log_spectrum(waves.to(self.device), lengths, self.plan)
 
 
 class PitchConfig(_KaldiConfig):
     """The options of Kaldi's compute-kaldi-pitch-feats (PitchExtractionOptions) under Kaldi's names and with Kaldi's defaults.  The offline
     computation only: the chunking and latency options of the online extractor are unknown options.  snip_edges=false, a preemphasis and
     what else the kernels do not take are read and kept, and refused when the plan is built."""
-    DEFAULTS = dict(ops.PITCH_OPTIONS)
+    DEFAULTS = dict(frontend.PITCH_OPTIONS)
     DRIVER_OPTIONS = {}
 
     def _check_window(self):
         pass
 
     def plan(self):
-        return ops.PitchPlan(**{k: getattr(self, k) for k in self.DEFAULTS})
+        return frontend.PitchPlan(**{k: getattr(self, k) for k in self.DEFAULTS})
 
 
 class ProcessPitchConfig(_KaldiConfig):
     """The options of Kaldi's process-kaldi-pitch-feats (ProcessPitchOptions) under Kaldi's names and with Kaldi's defaults: three columns
     (POV feature, normalised log pitch, delta log pitch).  A delay other than 0 is read and kept, and refused at the first call."""
-    DEFAULTS = dict(ops.PITCH_PROCESS_OPTIONS)
+    DEFAULTS = dict(frontend.PITCH_PROCESS_OPTIONS)
     DRIVER_OPTIONS = {}
 
     def _check_window(self):
@@ -311,7 +311,7 @@ class ProcessPitchConfig(_KaldiConfig):
 
 
 class Pitch(object):
-    """Kaldi's pitch features of one PitchConfig and one ProcessPitchConfig on one device (ops.pitch, ops.pitch_process; Kaldi's
+    """Kaldi's pitch features of one PitchConfig and one ProcessPitchConfig on one device (frontend.pitch, frontend.pitch_process; Kaldi's
     make_fbank_pitch.sh pipes the same two binaries).  Building it builds the plan: a configuration outside the kernels' range raises
     RuntimeError here.  feat_dim: 3 under the defaults."""
 
@@ -332,13 +332,13 @@ class Pitch(object):
     def raw(self, waves, lengths=None):
         """compute-kaldi-pitch-feats alone: (raw (B, Tmax, 2) float32: NCCF and pitch in Hz, frames (B) int32)."""
         waves, lengths = _batch("Pitch", waves, lengths)
-        return ops.pitch(waves.to(self.device), lengths, self.plan)
+        return frontend.pitch(waves.to(self.device), lengths, self.plan)
 
     def __call__(self, waves, lengths=None, seed=0, utt_offset=0):
         """waves as Fbank takes them, at config.sample_frequency.  Returns (feats (B, Tmax, feat_dim) float32 zero-padded, frames (B)
         int32) on the device.  The noise on the delta column is keyed by (seed, b + utt_offset), as Fbank's dither."""
         raw, frames = self.raw(waves, lengths)
-        return ops.pitch_process(raw, frames, seed=seed, utt_offset=utt_offset, **self.process_config.kw()), frames
+        return frontend.pitch_process(raw, frames, seed=seed, utt_offset=utt_offset, **self.process_config.kw()), frames
 
 
 def paste_features(a, frames_a, b, frames_b, length_tolerance=2):
@@ -366,7 +366,7 @@ def paste_features(a, frames_a, b, frames_b, length_tolerance=2):
 
 
 class Resampler(object):
-    """Waveforms at orig_freq Hz -> new_freq Hz on one device (ops.resample: Kaldi's LinearResample with ResampleWaveform's parameters: a
+    """Waveforms at orig_freq Hz -> new_freq Hz on one device (frontend.resample: Kaldi's LinearResample with ResampleWaveform's parameters: a
     Hann-windowed sinc of lowpass_filter_width zero crossings, cutoff = cutoff_ratio * 0.5 * min(rates)).  Building it builds the plan: a
     pair of rates whose filter table does not fit the kernel's LDS budget raises RuntimeError here.  Equal rates build nothing and pass the
     batch through."""
@@ -378,7 +378,7 @@ class Resampler(object):
         self.device = torch.device(device)
         self.plan = None
         if self.orig_freq != self.new_freq:
-            self.plan = ops.ResamplePlan(self.orig_freq, self.new_freq, num_zeros=lowpass_filter_width,
+            self.plan = frontend.ResamplePlan(self.orig_freq, self.new_freq, num_zeros=lowpass_filter_width,
                                          cutoff=cutoff_ratio * 0.5 * min(self.orig_freq, self.new_freq))
 
     def num_samples(self, num_samples):
@@ -391,7 +391,7 @@ class Resampler(object):
         waves = waves.to(self.device)
         if self.plan is None:
             return waves, [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
-        return ops.resample(waves, lengths, self.plan)
+        return frontend.resample(waves, lengths, self.plan)
 
 
 class SpeedPerturb(object):
@@ -417,7 +417,7 @@ class SpeedPerturb(object):
 
 
 class FrameContext(object):
-    """Deltas, splice, skip and downsample pad of a base batch on the device (ops.frame_context): the loader keys left_ctx, right_ctx,
+    """Deltas, splice, skip and downsample pad of a base batch on the device (frontend.frame_context): the loader keys left_ctx, right_ctx,
     n_skip_frame, n_downsample under the names left, right, skip, n_downsample, plus Kaldi's add-deltas (delta_order 0: none).  Holds no
     device state: the batch's device is the call's.  Options outside the kernel's limits raise RuntimeError at the first out_dim / call."""
 
@@ -436,22 +436,22 @@ class FrameContext(object):
 
     def out_dim(self, feat_dim):
         """Columns of the output for base features of feat_dim columns: (left + 1 + right) * feat_dim * (delta_order + 1)."""
-        ops.frame_context_tile(feat_dim, **self._kw())                 # (the limits)
+        frontend.frame_context_tile(feat_dim, **self._kw())                 # (the limits)
         return (self.left + 1 + self.right) * int(feat_dim) * (self.delta_order + 1)
 
     def out_frames(self, num_frames):
         """Rows of an utterance of num_frames base frames: kept frames, padded to a multiple of n_downsample."""
-        return ops.context_frames(num_frames, self.skip, self.n_downsample)
+        return frontend.context_frames(num_frames, self.skip, self.n_downsample)
 
     def __call__(self, feats, frames):
         """feats (B, Tin_max, F) float32 on the device, frames (B) a list or a device tensor -- a front-end's return values as they are.
         Returns (out (B, Tout_max, out_dim(F)) float32: the model's input, out_frames (B) int32, fractions (B) float32: the loader's
         input_sizes) on the same device."""
-        return ops.frame_context(feats, frames, **self._kw())
+        return frontend.frame_context(feats, frames, **self._kw())
 
 
 class SpecAugment(object):
-    """SpecAugment (Park et al., Interspeech 2019) of a base batch on the device (ops.spec_augment): a time warp of up to warp_window frames,
+    """SpecAugment (Park et al., Interspeech 2019) of a base batch on the device (frontend.spec_augment): a time warp of up to warp_window frames,
     num_freq_masks masks of up to freq_width columns and num_time_masks masks of up to min(time_width, time_ratio * T) frames, set to `fill`.
     Utterance number i of the stream draws from (seed, i) alone: the object keeps the running index -- start_index, advanced by B at every
     call without utt_offset -- and no device state.  Everything is off by default; DEFAULTS is what the driver key `spec_augment: true`
@@ -472,53 +472,53 @@ class SpecAugment(object):
         if mapping is True:
             return cls(seed=seed, **cls.DEFAULTS)
         if not hasattr(mapping, "items"):
-            raise ValueError("spec_augment: expected true or a mapping of %s, got %r" % (", ".join(ops.SPEC_AUGMENT_OPTIONS), mapping))
-        unknown = sorted(set(mapping) - set(ops.SPEC_AUGMENT_OPTIONS))
+            raise ValueError("spec_augment: expected true or a mapping of %s, got %r" % (", ".join(frontend.SPEC_AUGMENT_OPTIONS), mapping))
+        unknown = sorted(set(mapping) - set(frontend.SPEC_AUGMENT_OPTIONS))
         if unknown:
-            raise ValueError("spec_augment: unknown option(s) %s (known: %s)" % (", ".join(unknown), ", ".join(ops.SPEC_AUGMENT_OPTIONS)))
+            raise ValueError("spec_augment: unknown option(s) %s (known: %s)" % (", ".join(unknown), ", ".join(frontend.SPEC_AUGMENT_OPTIONS)))
         return cls(seed=seed, **dict(mapping))
 
     def _kw(self):
-        return {k: getattr(self, k) for k in ops.SPEC_AUGMENT_OPTIONS}
+        return {k: getattr(self, k) for k in frontend.SPEC_AUGMENT_OPTIONS}
 
     def plan(self, T, F, utt_index):
-        """The warp and the masks of utterance utt_index with T frames of F columns (ops.spec_augment_plan; no device)."""
-        return ops.spec_augment_plan(T, F, self.seed, utt_index, **self._kw())
+        """The warp and the masks of utterance utt_index with T frames of F columns (frontend.spec_augment_plan; no device)."""
+        return frontend.spec_augment_plan(T, F, self.seed, utt_index, **self._kw())
 
     def __call__(self, feats, frames, utt_offset=None):
         """feats (B, Tmax, F) float32 on the device, frames (B) a list or a device tensor.  Utterance b is number utt_offset + b of the
         stream; without utt_offset, the running index, which then advances by B.  Returns the augmented batch, a new tensor."""
-        out = ops.spec_augment(feats, frames, self.seed, self.index if utt_offset is None else utt_offset, **self._kw())
+        out = frontend.spec_augment(feats, frames, self.seed, self.index if utt_offset is None else utt_offset, **self._kw())
         if utt_offset is None:
             self.index += int(feats.shape[0])
         return out
 
 
 class Reverberate(object):
-    """Multi-condition data on the waveform (ops.reverberate; Kaldi's wav-reverberate): with probability rir_prob one room impulse response
+    """Multi-condition data on the waveform (frontend.reverberate; Kaldi's wav-reverberate): with probability rir_prob one room impulse response
     of the bank is convolved into an utterance, with probability noise_prob one noise of the bank is added at one of its SNRs, and
-    normalize keeps the utterance's power.  `bank`: an ops.ReverbBank, or (rirs, noises, sample_frequency[, snrs]) to build one from lists
+    normalize keeps the utterance's power.  `bank`: an frontend.ReverbBank, or (rirs, noises, sample_frequency[, snrs]) to build one from lists
     of 1-D arrays on the waveforms' scale.  Utterance number i of the stream draws from (seed, i) alone: the object keeps the running index
     -- start_index, advanced by B at every call without utt_offset -- as SpecAugment does.  The result is float32 on the input's scale:
     any front-end takes it as its waveform batch."""
 
     def __init__(self, bank, rir_prob=1.0, noise_prob=1.0, normalize=True, seed=0, device="cuda:0", start_index=0):
         self.device = torch.device(device)
-        self.bank = bank if isinstance(bank, ops.ReverbBank) else ops.ReverbBank(*bank)
+        self.bank = bank if isinstance(bank, frontend.ReverbBank) else frontend.ReverbBank(*bank)
         self.rir_prob, self.noise_prob, self.normalize = float(rir_prob), float(noise_prob), bool(normalize)
         self.seed, self.index = int(seed), int(start_index)
-        ops.reverb_plan(self.bank, self.seed, 0, self.rir_prob, self.noise_prob)       # (the probabilities' limits, before any launch)
+        frontend.reverb_plan(self.bank, self.seed, 0, self.rir_prob, self.noise_prob)       # (the probabilities' limits, before any launch)
 
     def plan(self, utt_index):
-        """The draws of utterance utt_index (ops.reverb_plan; no device)."""
-        return ops.reverb_plan(self.bank, self.seed, utt_index, self.rir_prob, self.noise_prob)
+        """The draws of utterance utt_index (frontend.reverb_plan; no device)."""
+        return frontend.reverb_plan(self.bank, self.seed, utt_index, self.rir_prob, self.noise_prob)
 
     def __call__(self, waves, lengths=None, utt_offset=None):
         """waves as Fbank takes them: a list of 1-D waveforms, or a padded (B, Nmax) batch with `lengths`.  Utterance b is number
         utt_offset + b of the stream; without utt_offset, the running index, which then advances by B.  Returns (out (B, Nmax) float32
         zero-padded on the device, lengths): any front-end's (waves, lengths) form."""
         waves, lengths = _batch("Reverberate", waves, lengths)
-        out = ops.reverberate(waves.to(self.device), lengths, self.bank, self.seed, self.index if utt_offset is None else utt_offset,
+        out = frontend.reverberate(waves.to(self.device), lengths, self.bank, self.seed, self.index if utt_offset is None else utt_offset,
                               rir_prob=self.rir_prob, noise_prob=self.noise_prob, normalize=self.normalize)
         if utt_offset is None:
             self.index += int(out.shape[0])
@@ -534,7 +534,7 @@ class GlobalCMVN(object):
         self.stats = torch.zeros((2, self.feat_dim + 1), dtype=torch.float64, device=device)
 
     def accumulate(self, feats, frames):
-        ops.cmvn_accumulate(feats, frames, self.stats)
+        frontend.cmvn_accumulate(feats, frames, self.stats)
         return self
 
     def mean_scale(self, device=None):
@@ -614,13 +614,13 @@ class SpeakerCMVN(object):
             raise ValueError("SpeakerCMVN: unknown speaker %s" % e)
 
     def accumulate(self, feats, frames, speakers_of_batch):
-        ops.cmvn_accumulate_groups(feats, frames, self._ids(speakers_of_batch), self.stats)
+        frontend.cmvn_accumulate_groups(feats, frames, self._ids(speakers_of_batch), self.stats)
         return self
 
     def apply(self, feats, frames, speakers_of_batch, norm_vars=True, out=None):
         """feats (B, Tmax, F) normalised with the statistics of each utterance's speaker (apply-cmvn --norm-vars=<norm_vars>); rows at or
         beyond frames[b] come out as zeros.  A speaker without accumulated frames leaves its utterances as they are."""
-        return ops.cmvn_apply(feats, frames, self.stats, self._ids(speakers_of_batch), norm_vars=norm_vars, out=out)
+        return frontend.cmvn_apply(feats, frames, self.stats, self._ids(speakers_of_batch), norm_vars=norm_vars, out=out)
 
     def save_kaldi_text(self, path):
         """The text archive of `compute-cmvn-stats --spk2utt=... ark,t:`: per speaker `<speaker>  [`, one indented row per line, `]`.  Values
@@ -669,7 +669,7 @@ class SpeakerCMVN(object):
 class SlidingCMVN(object):
     """Kaldi's apply-cmvn-sliding under its option names and defaults: every frame normalised by the mean (and, with normalize_variance,
     the variance) of a window of cmn_window frames around (center) or before it.  Called as (feats, frames) on a zero-padded device batch;
-    returns a new (B, Tmax, F) tensor (ops.cmvn_sliding)."""
+    returns a new (B, Tmax, F) tensor (frontend.cmvn_sliding)."""
 
     def __init__(self, cmn_window=600, min_cmn_window=100, normalize_variance=False, center=False):
         self.cmn_window, self.min_cmn_window = int(cmn_window), int(min_cmn_window)
@@ -679,7 +679,7 @@ class SlidingCMVN(object):
                              % (self.cmn_window, self.min_cmn_window))
 
     def __call__(self, feats, frames):
-        return ops.cmvn_sliding(feats, frames, cmn_window=self.cmn_window, min_cmn_window=self.min_cmn_window,
+        return frontend.cmvn_sliding(feats, frames, cmn_window=self.cmn_window, min_cmn_window=self.min_cmn_window,
                                 normalize_variance=self.normalize_variance, center=self.center)
 
 
