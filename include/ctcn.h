@@ -288,6 +288,11 @@ int ctcn_rnn_bwd_weights(int cell, int T, int B, int I, int H, int dirs, const f
  * train fwd: y = gamma*(x-mean)*rstd+beta; saves mean,rstd (C each); updates running stats in place
  * (momentum 0.1 semantics: rm = (1-mom)*rm + mom*mean; rv uses the unbiased variance).
  * relu!=0 fuses nn.ReLU (model_ctc.py:64) into the apply pass and its mask into the backward pass.
+ * Accuracy: the per-channel sums (x, x^2; dy', dy' xhat) are float64; mean = s / n and var = max(ss / n - mean^2, 0) are formed in float64 and
+ * save_mean, save_rstd stored as float32; y = fma((x - save_mean) * save_rstd, gamma, beta) in float32.  Therefore y is off by about
+ * |gamma| * rstd * ulp(mean) / 2 on a channel whose mean is large against its spread (the float32 save_mean), and var by about
+ * 3 n 2^-53 mean^2 (the cancellation in ss / n - mean^2: negligible until it nears var + eps).  A constant channel is exact: save_mean is the
+ * value, var 0, y = beta.  tests/bn_ref.py derives the per-element bounds the tests hold every entry point to.
  * ws: >= ctcn_bn_ws_bytes(outer, C, inner) (0 for dims that are not positive). */
 size_t ctcn_bn_ws_bytes(int outer, int C, int inner);
 int ctcn_bn_fwd_train(const float *x, float *y, const float *gamma, const float *beta, float *running_mean,
@@ -333,7 +338,9 @@ int ctcn_bn_bwd_dropout(const float *x, const float *dy_drop, const float *gamma
  *   inner == 1 (rows = T * batch, time-major; frame must be 1): row r is valid iff r / batch < lens[r % batch]
  *   inner  > 1 (NCHW; batch must equal outer, inner = T' * frame): element i of plane (o, c) is valid iff i / frame < lens[o]
  * (lens are clamped to [0, T] on the device.)  The statistics, dgamma / dbeta and the dx reduction terms run over the valid elements with
- * n = sum(lens) * frame taken on the device (no host sync); running statistics use that n (unbiased variance: n - 1).  y and dx are 0 at
+ * n = sum(lens) * frame taken on the device (no host sync); running statistics use that n (unbiased variance: n - 1).  n = 1: var = 0 and
+ * running_var is updated with that biased value (no n / (n - 1)); n = 0 (every length 0): mean = 0, var = 0, y = dx = 0, dgamma / dbeta = 0 (or
+ * their beta_acc base), and the running statistics move towards 0 by the momentum.  y and dx are 0 at
  * invalid elements by select, and no pass reads x / y / dy there.  Otherwise the contract of ctcn_bn_fwd_train / _eval / ctcn_bn_bwd
  * (relu, num_batches_tracked, beta_acc, deterministic float64 partials).  ws: >= ctcn_bn_masked_ws_bytes(outer, C, inner).
  * ctcn_mask_frames: y = valid ? x : 0 (its own backward); y may alias x. */

@@ -14,6 +14,7 @@ import torch.nn as tnn
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import packed_ref  # noqa: E402
+from bn_ref import _valid  # noqa: E402  (the validity rule of include/ctcn.h)
 from ctc_pytorch_amd.testing import synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -335,17 +336,6 @@ def test_three_adam_steps_against_packed_reference(dev, cell, cnn, prec):
 
 
 # ---- 7. the kernels through the C ABI -------------------------------------------------------------------------------
-def _valid(layout, lens, outer, C, inner, frame):
-    """bool (outer, C, inner): the validity rule of include/ctcn.h."""
-    lens = np.asarray(lens)
-    if layout == "rows":
-        r = np.arange(outer)
-        v = (r // len(lens)) < lens[r % len(lens)]
-        return np.broadcast_to(v[:, None, None], (outer, C, 1))
-    v = (np.arange(inner)[None, :] // frame) < lens[:, None]
-    return np.broadcast_to(v[:, None, :], (outer, C, inner))
-
-
 ABI_CASES = [  # layout, lens, outer, C, inner, frame
     ("rows", [50, 1, 20, 33], 200, 24, 1, 1),                 # full-length utterance, 16-B path
     ("rows", [30, 2, 11, 29], 400, 64, 1, 1),                 # T = 100: the last 280 rows (more than four 64-row tiles) are padding
