@@ -105,31 +105,89 @@ __device__ __forceinline__ void cell_fwd(const float (&o)[4], const float (&pre)
 // Backward: dh = dy_t + (d(pre-act)_{next} W_hh), sv = the saved gates, e0 = c_t (LSTM) / W_hn h_{t-1} (GRU) / y_t (tanh), e1 = c_{t-1} (LSTM) / h_{t-1} (GRU),
 // 0 at the sequence start, state = dc (LSTM) / dh * z (GRU), carried.  Out: out = what the next step multiplies by W_hh, per gate block (GRU: out[2] =
 // dan * r, the gradient of W_hn h), and dan, the GRU's gradient of n's pre-activation -- the caller decides which of the two it publishes and stores where.
-template <int CELL>
-__device__ __forceinline__ void cell_bwd(float dh, const float (&sv)[4], float e0, float e1, float &state, float (&out)[4], float &dan) {
+// The equations are written once, in two phases.  cell_bwd_prepare holds every sub-expression that reads neither dh nor state: it needs only the step's
+// reserve values, so the scatter kernels run it while their item waves wait for the hand-off (tanh(c_t) alone is a chain of two quarter-rate
+// transcendentals).  cell_bwd_finish holds the rest, the part on the serial chain of the timestep.  Only whole sub-expressions moved, every product keeps
+// its left-to-right grouping: out[0] is ((dc g) i) (1 - i).
+// ROUND: where a product is rounded before the sum it feeds.  hipcc decided that by the shape of the code around the one-phase form, differently from
+// kernel to kernel, and once the two phases are pinned apart it decides differently again (dc loses its FMA, 1 - g^2 gains one).  So the kernels that
+// separate the phases say what they have always computed:
+//   BWD_FUSED      1 - x^2 = fma(-x, x, 1) for tc, g, n and y; dc = fma(dh o, 1 - tc^2, state)                  (rnn_bwd_scatter2; GRU and tanh cell everywhere)
+//   BWD_FUSED_BUT_G  the same, but g^2 is rounded on its own (it used to share a packed subtract with 1 - o)     (rnn_bwd_scatter, LSTM)
+//   BWD_AS_COMPILED  plain expressions, contracted as hipcc sees fit: the one-phase form, cell_bwd, as it always was  (rnn_bwd_step, rnn_bwd_persist)
+enum { BWD_AS_COMPILED, BWD_FUSED, BWD_FUSED_BUT_G };
+template <int ROUND>
+__device__ __forceinline__ float one_minus_sq(float x) {
+  if constexpr (ROUND == BWD_AS_COMPILED) return 1.0f - x * x;
+  else return __builtin_fmaf(-x, x, 1.0f);
+}
+template <int CELL> struct BwdPrep;
+template <> struct BwdPrep<CTCN_CELL_LSTM> { float tc, omtc2, omi, omf, omg2, omo; };   // tanh(c_t), 1 - tc^2, 1 - i, 1 - f, 1 - g^2, 1 - o
+template <> struct BwdPrep<CTCN_CELL_GRU> { float omz, hpn, omn2, omr; };               // 1 - z, h_{t-1} - n, 1 - n^2, 1 - r
+template <> struct BwdPrep<CTCN_CELL_TANH> { float ome2; };                             // 1 - y_t^2
+template <int CELL, int ROUND = BWD_AS_COMPILED>
+__device__ __forceinline__ BwdPrep<CELL> cell_bwd_prepare(const float (&sv)[4], float e0, float e1) {
+  BwdPrep<CELL> p;
   if constexpr (CELL == CTCN_CELL_LSTM) {
     const float i_ = sv[0], f_ = sv[1], g_ = sv[2], o_ = sv[3];
-    const float tc = act_tanh(e0);
-    const float do_ = dh * tc;
-    const float dc = dh * o_ * (1.0f - tc * tc) + state;
-    out[0] = dc * g_ * i_ * (1.0f - i_);
-    out[1] = dc * e1 * f_ * (1.0f - f_);
-    out[2] = dc * i_ * (1.0f - g_ * g_);
-    out[3] = do_ * o_ * (1.0f - o_);
+    p.tc = act_tanh(e0);
+    p.omtc2 = one_minus_sq<ROUND>(p.tc);
+    p.omi = 1.0f - i_;
+    p.omf = 1.0f - f_;
+    if constexpr (ROUND == BWD_FUSED_BUT_G) {
+      float gg = g_ * g_;
+      asm("" : "+v"(gg));                                  // a rounded product: nothing to contract with the subtraction
+      p.omg2 = 1.0f - gg;
+    } else {
+      p.omg2 = one_minus_sq<ROUND>(g_);
+    }
+    p.omo = 1.0f - o_;
+  } else if constexpr (CELL == CTCN_CELL_GRU) {
+    const float r_ = sv[0], z_ = sv[1], n_ = sv[2], hp = e1;
+    p.omz = 1.0f - z_;
+    p.hpn = hp - n_;
+    p.omn2 = one_minus_sq<ROUND>(n_);
+    p.omr = 1.0f - r_;
+  } else {
+    p.ome2 = one_minus_sq<ROUND>(e0);
+  }
+  return p;
+}
+template <int CELL, int ROUND = BWD_AS_COMPILED>
+__device__ __forceinline__ void cell_bwd_finish(float dh, const float (&sv)[4], const BwdPrep<CELL> &p, float e0, float e1, float &state, float (&out)[4], float &dan) {
+  if constexpr (CELL == CTCN_CELL_LSTM) {
+    const float i_ = sv[0], f_ = sv[1], g_ = sv[2], o_ = sv[3];
+    const float do_ = dh * p.tc;
+    float dc;
+    if constexpr (ROUND == BWD_AS_COMPILED) dc = dh * o_ * p.omtc2 + state;
+    else dc = __builtin_fmaf(dh * o_, p.omtc2, state);
+    out[0] = dc * g_ * i_ * p.omi;
+    out[1] = dc * e1 * f_ * p.omf;
+    out[2] = dc * i_ * p.omg2;
+    out[3] = do_ * o_ * p.omo;
     state = dc * f_;
   } else if constexpr (CELL == CTCN_CELL_GRU) {
     dh += state;
-    const float r_ = sv[0], z_ = sv[1], n_ = sv[2], hn = e0, hp = e1;
-    const float dn = dh * (1.0f - z_);
-    const float dz = dh * (hp - n_);
-    dan = dn * (1.0f - n_ * n_);
-    out[0] = dan * hn * r_ * (1.0f - r_);
-    out[1] = dz * z_ * (1.0f - z_);
+    const float r_ = sv[0], z_ = sv[1], hn = e0;
+    const float dn = dh * p.omz;
+    const float dz = dh * p.hpn;
+    dan = dn * p.omn2;
+    out[0] = dan * hn * r_ * p.omr;
+    out[1] = dz * z_ * p.omz;
     out[2] = dan * r_;
     state = dh * z_;
   } else {
-    out[0] = dh * (1.0f - e0 * e0);
+    out[0] = dh * p.ome2;
   }
+}
+// The prepared values as opaque registers at this point of the program: what computes them stays in front of the next barrier / sleep / volatile asm,
+// where the wave would otherwise only wait (hipcc sinks a value towards its first use)
+__device__ __forceinline__ void pin_prep(BwdPrep<CTCN_CELL_LSTM> &p) { asm volatile("" : "+v"(p.tc), "+v"(p.omtc2), "+v"(p.omi), "+v"(p.omf), "+v"(p.omg2), "+v"(p.omo)); }
+__device__ __forceinline__ void pin_prep(BwdPrep<CTCN_CELL_GRU> &p) { asm volatile("" : "+v"(p.omz), "+v"(p.hpn), "+v"(p.omn2), "+v"(p.omr)); }
+__device__ __forceinline__ void pin_prep(BwdPrep<CTCN_CELL_TANH> &p) { asm volatile("" : "+v"(p.ome2)); }
+template <int CELL>
+__device__ __forceinline__ void cell_bwd(float dh, const float (&sv)[4], float e0, float e1, float &state, float (&out)[4], float &dan) {
+  cell_bwd_finish<CELL>(dh, sv, cell_bwd_prepare<CELL>(sv, e0, e1), e0, e1, state, out, dan);
 }
 // ... and for the kernels that read the cell type from their arguments
 __device__ __forceinline__ void cell_fwd(int cell, const float (&o)[4], const float (&pre)[4], float &state, float &h, float (&sv)[4], float &sx) {
@@ -1701,7 +1759,7 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
   }
   __syncthreads();
 
-  // phases of a step: gather + park + barrier | item sum | gate math + stage writes | barrier wait | LDS reads + MFMAs + scatter issue | drain + flags | reserve traffic
+  // phases of a step: gather + park + barrier (item waves: reserve wait + cell_bwd_prepare, then the barrier) | item sum | cell_bwd_finish + stage writes | barrier wait | LDS reads + MFMAs + scatter issue | drain + flags | reserve traffic
   enum { S_GATHER, S_SUM, S_MATH, S_STAGED, S_SCATTER, S_DRAIN, S_TAIL, S_N };
   Stamps<S_N> st;
   auto step = [&](const int s, auto PSC) {
@@ -1710,6 +1768,21 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
     uint32_t dropword = 0;
     if (pa.drop_bwd && tid < 256)
       dropword = reinterpret_cast<const uint32_t *>(&dropw[wave][(s & 3) * 16 + (lane >> 4) * 4 + ((lane & 15) >> 2)])[lane & 3];
+    // Item waves, in front of the gather barrier, where they would only wait for the exchange waves: everything of the step that does not need dh.
+    // The seven reserve values of this step have landed once at most the seven loads of the NEXT step's set (issued one step later, in order behind
+    // them) are still in flight; stores, which vmcnt counts too, can only make this wait longer.  The item waves issue nothing between here and their
+    // tail, so the wait means what it meant behind the barrier.
+    float dyd = 0.0f, e1u = 0.0f;
+    BwdPrep<CELL> prep = {};
+    if (tid < 256) {
+      asm volatile("s_waitcnt vmcnt(7)" : "+v"(sv[ps][0]), "+v"(sv[ps][1]), "+v"(sv[ps][2]), "+v"(sv[ps][3]), "+v"(dyv[ps]), "+v"(e0[ps]), "+v"(e1[ps])::"memory");
+      dyd = dyv[ps];
+      if (pa.drop_bwd) dyd = drop_keep(pa, dropword, dyd);
+      e1u = (s + 1 < T && !is_tanh) ? e1[ps] : 0.0f;       // c / h of a step before the sequence start is 0
+      prep = cell_bwd_prepare<CELL, BWD_FUSED_BUT_G>(sv[ps], e0[ps], e1u);
+      pin_prep(prep);
+      asm volatile("" : "+v"(dyd), "+v"(e1u));
+    }
     float rec = 0.0f;                                      // (da_{next} W_hh)[row bl][unit jl]
     if (s > 0) {
       const int par = (s - 1) & 1;
@@ -1776,15 +1849,9 @@ __global__ __launch_bounds__(1024) void rnn_bwd_scatter(PersistArgs pa) {
 
     float out[4] = {0.f, 0.f, 0.f, 0.f};      // d(pre-activation) the next step multiplies by W_hh, per gate block
     float dan = 0.f;
-    // the seven reserve values of this step have landed once at most the seven loads of the NEXT step's set (issued one step
-    // later, in order behind them) are still in flight; stores, which vmcnt counts too, can only make this wait longer
-    asm volatile("s_waitcnt vmcnt(7)" : "+v"(sv[ps][0]), "+v"(sv[ps][1]), "+v"(sv[ps][2]), "+v"(sv[ps][3]), "+v"(dyv[ps]), "+v"(e0[ps]), "+v"(e1[ps])::"memory");
-    if (item) {
-      float dyd = dyv[ps];
-      if (pa.drop_bwd) dyd = drop_keep(pa, dropword, dyd);
+    if (item) {                                               // on the chain: only what needs dh
       const float dh = dyd + rec;
-      const float e1u = (s + 1 < T && !is_tanh) ? e1[ps] : 0.0f;   // c / h of a step before the sequence start is 0
-      cell_bwd<CELL>(dh, sv[ps], e0[ps], e1u, state, out, dan);
+      cell_bwd_finish<CELL, BWD_FUSED_BUT_G>(dh, sv[ps], prep, e0[ps], e1u, state, out, dan);
       if (s + 1 < T) {                                        // A operand of this workgroup's product, in MFMA order
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -2028,7 +2095,7 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
   // byte offset of this item lane's float inside a partial block (MFMA C layout: float ((row >> 2) * 16 + unit) * 4 + (row & 3))
   const unsigned poll_off = (unsigned)(slice * nsl) * 1024u + (unsigned)(wave & 3) * 256u + (unsigned)((lane & 15) * 16 + (lane >> 4) * 4);
   int set = 0;                                     // s % 3
-  // phases of a step: item waves: delay + poll + sum (exchange waves: vmcnt wait) | gate math + stage (LDS drained) | barrier wait | exchange waves: A fragments in
+  // phases of a step: item waves: cell_bwd_prepare + delay + poll + sum (exchange waves: vmcnt wait) | cell_bwd_finish + stage (LDS drained) | barrier wait | exchange waves: A fragments in
   // registers | chains + tags + block stores issued | after that (item waves: after the barrier).  S_ROUNDS counts the poll rounds.
   enum { S_GATHER, S_MATH, S_BARRIER, S_FRAG, S_CHAINS, S_TAIL, S_ROUNDS, S_N };
   Stamps<S_N> st;
@@ -2042,6 +2109,13 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
       if (pa.drop_bwd) dropword = reinterpret_cast<const uint32_t *>(&dropw[wave][(s & 3) * 16 + (lane >> 4) * 4 + ((lane & 15) >> 2)])[lane & 3];
       const float *rv = &resv[set][0][0] + tid;
       const float sv[4] = {rv[0], rv[256], rv[512], rv[768]}, dyv = rv[1024], e0 = rv[1280], e1 = rv[1536];
+      // everything of the step that does not need dh, in front of the pause and the polls (as rnn_bwd_scatter in front of its gather barrier)
+      float dyd = dyv;
+      if (pa.drop_bwd) dyd = drop_keep(pa, dropword, dyd);
+      float e1u = (s + 1 < T && !is_tanh) ? e1 : 0.0f;
+      BwdPrep<CELL> prep = cell_bwd_prepare<CELL, BWD_FUSED>(sv, e0, e1u);
+      pin_prep(prep);
+      asm volatile("" : "+v"(dyd), "+v"(e1u));
       float rec = 0.0f;
       if (s > 0) {
         const int par = (s - 1) & 1;
@@ -2090,12 +2164,9 @@ __global__ __launch_bounds__(256 + 64 * NEW) void rnn_bwd_scatter2(PersistArgs p
       st.at_used(S_GATHER, rec);
       float out[4] = {0.f, 0.f, 0.f, 0.f};
       float dan = 0.f;
-      if (item) {
-        float dyd = dyv;
-        if (pa.drop_bwd) dyd = drop_keep(pa, dropword, dyd);
+      if (item) {                                             // on the chain: only what needs dh
         const float dh = dyd + rec;
-        const float e1u = (s + 1 < T && !is_tanh) ? e1 : 0.0f;
-        cell_bwd<CELL>(dh, sv, e0, e1u, state, out, dan);
+        cell_bwd_finish<CELL, BWD_FUSED>(dh, sv, prep, e0, e1u, state, out, dan);
         if (s + 1 < T) {
           unsigned short *sp = reinterpret_cast<unsigned short *>(&stage[sb][0]);
 #pragma unroll
