@@ -172,6 +172,13 @@ _SIGS = {
     "ctcn_beam_decode_nbest": (I, [P, I, P, P, D, I, I, I, P, P, P, P, P, I, I, I, P, Z, P]),
     "ctcn_beam_decode_lm": (I, [P, I, P, P, I, D, I, I, I, P, P, P, P, P, I, I, I, P, Z, P]),
     "ctcn_diag_beam_plan_lm": (I, [I, I, I, I, I, I, I, P]),
+    "ctcn_embedding_fwd": (I, [P, P, P, I, I, I, I, P, P]),
+    "ctcn_embedding_bwd_ws_bytes": (Z, [I, I]),
+    "ctcn_embedding_bwd": (I, [P, P, P, I, I, I, I, F, P, Z, P]),
+    "ctcn_nll_fwd": (I, [P, P, I, I, I, I, P, P, P, P, P, P]),
+    "ctcn_xent_bwd": (I, [P, P, P, I, I, I, P, I, P, P]),
+    "ctcn_lm_pack_nbest": (I, [P, P, P, I, I, I, I, I, I, P, P, P, P]),
+    "ctcn_rescore_select": (I, [P, P, P, P, P, D, D, I, I, I, P, P, P, P, P]),
 }
 
 

@@ -252,6 +252,45 @@ class CTCLoss(_tnn.Module):
         return ops.ctc_loss(log_probs, targets, input_lengths, target_lengths, self.blank, self.reduction, self.zero_infinity)
 
 
+class Embedding(_tnn.Embedding):
+    """nn.Embedding(num_embeddings, embedding_dim, padding_idx=None): a row lookup whose backward is deterministic (per table row the sum of
+    its gradient rows in ascending position).  max_norm, sparse and scale_grad_by_freq are refused."""
+
+    def forward(self, ids):
+        if self.max_norm is not None or self.sparse or self.scale_grad_by_freq:
+            raise NotImplementedError("ctc_pytorch_amd.nn.Embedding: max_norm, sparse and scale_grad_by_freq are not supported")
+        ops._need_gpu(self.weight)
+        if torch.is_tensor(ids):
+            ops._need_gpu(ids)
+        return ops.embedding(ids, self.weight, self.padding_idx)
+
+
+class CrossEntropyLoss(_tnn.Module):
+    """nn.CrossEntropyLoss(ignore_index=-100, reduction='mean') for class-index targets: input (N, C) logits (or (C,) with a 0-d target),
+    reduction 'none' / 'sum' / 'mean' (over the rows not ignored).  weight, label_smoothing != 0 and probability targets are refused."""
+
+    def __init__(self, weight=None, size_average=None, ignore_index=-100, reduce=None, reduction="mean", label_smoothing=0.0):
+        super().__init__()
+        if weight is not None or size_average is not None or reduce is not None:
+            raise NotImplementedError("ctc_pytorch_amd.nn.CrossEntropyLoss: class weights and the legacy size_average / reduce are not supported")
+        if float(label_smoothing) != 0.0:
+            raise NotImplementedError("ctc_pytorch_amd.nn.CrossEntropyLoss: label_smoothing must be 0")
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError("%s is not a valid value for reduction" % (reduction,))
+        self.ignore_index = int(ignore_index)
+        self.reduction = reduction
+
+    def forward(self, input, target):
+        if torch.is_tensor(target) and target.is_floating_point():
+            raise NotImplementedError("ctc_pytorch_amd.nn.CrossEntropyLoss: class-index targets only (no class probabilities)")
+        ops._need_gpu(input)
+        if torch.is_tensor(target):
+            ops._need_gpu(target)
+        if input.dim() not in (1, 2):
+            raise NotImplementedError("ctc_pytorch_amd.nn.CrossEntropyLoss: input must be (N, C) or (C,)")
+        return ops.cross_entropy(input, target, self.ignore_index, self.reduction)
+
+
 class MaxPool2d(_tnn.Module):
     """nn.MaxPool2d(pooling_size) of LayerCNN (model_ctc.py:52-53): stride = kernel, no padding, floor."""
 

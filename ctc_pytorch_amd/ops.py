@@ -1778,10 +1778,10 @@ def beam_decode(x_tbv, lens, lm_table, alpha, beam_width, blank=0, input_is_prob
     return [list(map(int, ids_c[b, : len_c[b]])) for b in range(B)], score.cpu().numpy(), status.cpu().numpy()
 
 
-def beam_decode_nbest(x_tbv, lens, lm_table, alpha, beam_width, nbest, blank=0, input_is_prob=False):
-    """The `nbest` best labellings of every utterance (ctcn_beam_decode_nbest: the first nbest entries of the reference's final `last.sort()`,
-    BeamSearch.py:150 keeps [0]).  Returns CPU (ids: per utterance a list of up to nbest label lists, best first; scores (B, nbest) float64,
-    0 past the labellings returned; status (B,) int32).  Synchronises."""
+def beam_decode_nbest_device(x_tbv, lens, lm_table, alpha, beam_width, nbest, blank=0, input_is_prob=False):
+    """Enqueue the n-best prefix beam search (ctcn_beam_decode_nbest / ctcn_beam_decode_lm) on the current stream; returns DEVICE tensors
+    (out_ids (B,nbest,T) int32, out_len (B,nbest) int32, score (B,nbest) float64, count (B) int32, status (B) int32) without synchronising:
+    what rescore_nbest takes."""
     order = _lm_order(lm_table, x_tbv.shape[-1])
     _need_gpu(x_tbv)
     x = _f32c(x_tbv.detach())
@@ -1809,9 +1809,255 @@ def beam_decode_nbest(x_tbv, lens, lm_table, alpha, beam_width, nbest, blank=0, 
         _lib.check(L.ctcn_beam_decode_nbest(_ptr(x), int(bool(input_is_prob)), _ptr(lens_t), _ptr(lm), float(alpha), int(beam_width), int(blank), nbest,
                                             _ptr(out_ids), _ptr(out_len), _ptr(score), _ptr(count), _ptr(status), T, B, V, _ptr(ws), ws.numel(),
                                             _lib.stream_ptr()), "beam_decode_nbest")
+    return out_ids, out_len, score, count, status
+
+
+def beam_decode_nbest(x_tbv, lens, lm_table, alpha, beam_width, nbest, blank=0, input_is_prob=False):
+    """The `nbest` best labellings of every utterance (ctcn_beam_decode_nbest: the first nbest entries of the reference's final `last.sort()`,
+    BeamSearch.py:150 keeps [0]).  Returns CPU (ids: per utterance a list of up to nbest label lists, best first; scores (B, nbest) float64,
+    0 past the labellings returned; status (B,) int32).  Synchronises."""
+    out_ids, out_len, score, count, status = beam_decode_nbest_device(x_tbv, lens, lm_table, alpha, beam_width, nbest, blank, input_is_prob)
+    B = out_ids.shape[0]
     ids_c, len_c, cnt = out_ids.cpu().numpy(), out_len.cpu().numpy(), count.cpu().numpy()
     ids = [[list(map(int, ids_c[b, k, : len_c[b, k]])) for k in range(cnt[b])] for b in range(B)]
     return ids, score.cpu().numpy(), status.cpu().numpy()
+
+
+# --------------------------------------------------------------------------------------------------
+# RNN language model: embedding, cross-entropy over log-probs, n-best rescoring (lm.hip)
+# --------------------------------------------------------------------------------------------------
+LM_BAD_ID, LM_BAD_TARGET = 1, 2            # bits of the status word of the kernels of lm.hip
+_LM_STATUS = {}
+
+
+def lm_status(device):
+    """Per-device sticky int32 the kernels of lm.hip OR their bits into (0: every id and target was in range)."""
+    key = (device.type, device.index)
+    t = _LM_STATUS.get(key)
+    if t is None:
+        t = _LM_STATUS[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return t
+
+
+def check_lm_status(device, value=None):
+    """Raise IndexError if an embedding id or a loss target was out of range since the last check.  Synchronises (one small read) unless
+    `value`, the word as the caller has already read it, is given; callers that read results anyway call it there."""
+    t = _LM_STATUS.get((device.type, device.index))
+    if t is None:
+        return
+    v = int(t.item()) if value is None else int(value)
+    if v:
+        t.zero_()
+        what = [w for bit, w in ((LM_BAD_ID, "an embedding id outside [0, num_embeddings)"), (LM_BAD_TARGET, "a target outside [0, C)")) if v & bit]
+        raise IndexError("ctc_pytorch_amd: %s reached the device (its row was treated as zeros)" % " and ".join(what))
+
+
+def check_token_ids(host, V, what="ids", also=()):
+    """Host-resident ids are validated before they are uploaded, as check_frame_lengths does for lengths: ValueError for an id outside
+    [0, V) that is none of `also` (an ignore_index)."""
+    if host.size:
+        bad = (host < 0) | (host >= V)
+        for a in also:
+            bad &= host != a
+        if bad.any():
+            raise ValueError("%s: %d lies outside [0, %d)" % (what, int(host[bad][0]), V))
+
+
+def token_ids(ids, V, device, what="ids", also=()):
+    """`ids` (integer tensor on the host or the device, array or nested list) as the int32 device tensor the kernels read, shape kept.
+    Host-resident ids are checked (check_token_ids) and go up in one copy; a device tensor is taken as it is -- the kernels check every id
+    themselves and report through lm_status."""
+    if torch.is_tensor(ids):
+        if ids.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8, torch.int8):
+            raise ValueError("%s: expected an integer tensor, got %s" % (what, ids.dtype))
+        if ids.is_cuda:
+            return ids if ids.dtype == torch.int32 and ids.is_contiguous() else ids.to(torch.int32).contiguous()
+        host = ids.detach().numpy().astype(np.int64)
+    else:
+        host = np.asarray(ids)
+        if host.dtype.kind not in "iu":
+            raise ValueError("%s: expected integers" % what)
+        host = host.astype(np.int64)
+    check_token_ids(host, V, what, also)
+    return torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(device, non_blocking=True)
+
+
+class _Embedding(torch.autograd.Function):
+    """y = table[ids] (nn.Embedding); the backward is a deterministic scatter-add: per table row the float32 sum of its dy rows in ascending
+    position (ctcn_embedding_bwd), into the FlatAdam gradient view with beta = 1 where the table lives in one."""
+
+    @staticmethod
+    def forward(ctx, ids, table, padding_idx):
+        _need_gpu(ids, table)
+        ctx.gw_view = _gview(table)
+        table = _f32c(table)
+        V, E = table.shape
+        N = ids.numel()
+        y = torch.empty(tuple(ids.shape) + (E,), dtype=torch.float32, device=table.device)
+        if N:
+            _lib.check(_lib.lib().ctcn_embedding_fwd(_ptr(ids), _ptr(table), _ptr(y), N, V, E, padding_idx, _ptr(lm_status(table.device)),
+                                                     _lib.stream_ptr()), "embedding_fwd")
+        ctx.save_for_backward(ids)
+        ctx.dims = (N, V, E, padding_idx)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (ids,) = ctx.saved_tensors
+        N, V, E, padding_idx = ctx.dims
+        if not ctx.needs_input_grad[1]:
+            return None, None, None
+        L = _lib.lib()
+        into = ctx.gw_view
+        gw = None
+        if into is None:
+            into = gw = torch.empty((V, E), dtype=torch.float32, device=gy.device)
+        if N == 0:
+            if gw is not None:
+                gw.zero_()
+            return None, gw, None
+        gy = _f32c(gy)
+        ws = torch.empty(max(L.ctcn_embedding_bwd_ws_bytes(N, V), 4), dtype=torch.uint8, device=gy.device)
+        _lib.check(L.ctcn_embedding_bwd(_ptr(ids), _ptr(gy), _ptr(into), N, V, E, padding_idx, 0.0 if gw is not None else 1.0, _ptr(ws), ws.numel(),
+                                        _lib.stream_ptr()), "embedding_bwd")
+        return None, gw, None
+
+
+def embedding(ids, table, padding_idx=None):
+    """torch.nn.functional.embedding(ids, table, padding_idx) on the HIP kernels: ids of any shape (host ids are validated and uploaded, device
+    ids are checked by the kernel: a bad id gives a row of zeros and check_lm_status raises), table (V, E) float32 on the device."""
+    _need_gpu(table)
+    V = table.shape[0]
+    if padding_idx is None:
+        pad = -1
+    else:
+        pad = int(padding_idx) + (V if int(padding_idx) < 0 else 0)
+        if not 0 <= pad < V:
+            raise ValueError("padding_idx must lie within num_embeddings")
+    return _Embedding.apply(token_ids(ids, V, table.device, "embedding ids"), table, pad)
+
+
+_XENT_REDUCTIONS = ("none", "sum", "mean")
+
+
+def _nll(lp, tgt, T, B, V, ignore_index):
+    """ctcn_nll_fwd on (T*B, V) log-probs: (tok (T*B) float32, seq_sum (B) float64, total 0-d float64, count 0-d int32) on the device."""
+    dev = lp.device
+    tok = torch.empty(T * B, dtype=torch.float32, device=dev)
+    sums = torch.empty(B + 1, dtype=torch.float64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().ctcn_nll_fwd(_ptr(lp), _ptr(tgt), T, B, V, int(ignore_index), _ptr(tok), _ptr(sums), _ptr(sums[B:]), _ptr(count),
+                                       _ptr(lm_status(dev)), _lib.stream_ptr()), "nll_fwd")
+    return tok, sums[:B], sums[B], count
+
+
+class _CrossEntropy(torch.autograd.Function):
+    """F.cross_entropy over the last axis: ctcn_log_softmax_fwd + ctcn_nll_fwd forward, ctcn_xent_bwd backward (one read of the saved
+    log-probs, one write of dz; the upstream gradient and the 'mean' count are read on the device)."""
+
+    @staticmethod
+    def forward(ctx, z, tgt, ignore_index, reduction):
+        V = z.shape[-1]
+        N = z.numel() // V
+        lp = torch.empty_like(z)
+        _lib.check(_lib.lib().ctcn_log_softmax_fwd(_ptr(z), _ptr(lp), None, N, V, _lib.stream_ptr()), "log_softmax_fwd")
+        tok, _, total, count = _nll(lp, tgt, N, 1, V, ignore_index)
+        ctx.save_for_backward(lp, tgt, count)
+        ctx.conf = (N, V, ignore_index, reduction)
+        if reduction == "none":
+            return tok.view(tgt.shape)
+        if reduction == "sum":
+            return total.to(torch.float32)
+        return (total / count[0].clamp(min=1)).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        lp, tgt, count = ctx.saved_tensors
+        N, V, ignore_index, reduction = ctx.conf
+        g = _f32c(g)
+        dz = torch.empty_like(lp)
+        _lib.check(_lib.lib().ctcn_xent_bwd(_ptr(lp), _ptr(tgt), _ptr(dz), N, V, ignore_index, _ptr(g), 1 if reduction == "none" else 0,
+                                            _ptr(count) if reduction == "mean" else None, _lib.stream_ptr()), "xent_bwd")
+        return dz, None, None, None
+
+
+def cross_entropy(logits, target, ignore_index=-100, reduction="mean"):
+    """Cross-entropy of `logits` (..., V), classes on the LAST axis, against integer `target` (...): 'none' gives the per-row losses in
+    target's shape, 'sum' their float64 sum in ascending row order, 'mean' that sum over the rows not ignored (at least 1), both returned
+    as float32 scalars.  Rows whose target is ignore_index cost 0 and get a zero gradient."""
+    if reduction not in _XENT_REDUCTIONS:
+        raise ValueError("%s is not a valid value for reduction" % (reduction,))
+    _need_gpu(logits)
+    z = _f32c(logits)
+    if z.dim() < 1 or z.shape[-1] < 1 or z.numel() == 0:
+        raise ValueError("cross_entropy: logits must be (..., V) with at least one row")
+    tgt = token_ids(target, z.shape[-1], z.device, "cross_entropy target", also=(int(ignore_index),))
+    if tuple(tgt.shape) != tuple(z.shape[:-1]):
+        raise ValueError("cross_entropy: target %s does not match logits %s" % (tuple(tgt.shape), tuple(z.shape)))
+    return _CrossEntropy.apply(z, tgt, int(ignore_index), reduction)
+
+
+def sequence_log_prob(logits_tbv, targets_tb, ignore_index=-100):
+    """ln P of every sequence of a time-major batch: (B) float64 = - sum over t (ascending, float64) of the float32 token losses of
+    `targets_tb` (T, B) under log_softmax(logits_tbv (T, B, V)); steps whose target is ignore_index add nothing.  No gradient."""
+    _need_gpu(logits_tbv)
+    z = _f32c(logits_tbv.detach())
+    if z.dim() != 3:
+        raise ValueError("sequence_log_prob: logits must be (T, B, V)")
+    T, B, V = z.shape
+    tgt = token_ids(targets_tb, V, z.device, "sequence_log_prob targets", also=(int(ignore_index),))
+    if tuple(tgt.shape) != (T, B):
+        raise ValueError("sequence_log_prob: targets %s do not match logits %s" % (tuple(tgt.shape), tuple(z.shape)))
+    lp = torch.empty_like(z)
+    _lib.check(_lib.lib().ctcn_log_softmax_fwd(_ptr(z), _ptr(lp), None, T * B, V, _lib.stream_ptr()), "log_softmax_fwd")
+    return -_nll(lp, tgt, T, B, V, ignore_index)[1]
+
+
+def pack_nbest(out_ids, out_len, count, L, boundary=0, ignore_index=-100):
+    """ctcn_lm_pack_nbest: the n-best search's (B,N,T) ids, (B,N) lengths and (B) counts as the LM's time-major batch of B*N sequences of
+    L + 1 steps (L: the longest labelling): (in_ids (L+1, B*N), targets (L+1, B*N), lens (B*N)), int32 on the device."""
+    _need_gpu(out_ids, out_len, count)
+    B, N, T = out_ids.shape
+    L = int(L)
+    dev = out_ids.device
+    in_ids = torch.empty((L + 1, B * N), dtype=torch.int32, device=dev)
+    tgt = torch.empty((L + 1, B * N), dtype=torch.int32, device=dev)
+    lens = torch.empty(B * N, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().ctcn_lm_pack_nbest(_ptr(out_ids), _ptr(out_len), _ptr(count), B, N, T, L, int(boundary), int(ignore_index), _ptr(in_ids),
+                                             _ptr(tgt), _ptr(lens), _lib.stream_ptr()), "lm_pack_nbest")
+    return in_ids, tgt, lens
+
+
+RescoredBest = collections.namedtuple("RescoredBest", "ids lengths score k lm")
+
+
+def rescore_select(score, lm, out_len, count, out_ids, weight, len_bonus=0.0):
+    """ctcn_rescore_select: per utterance the entry k < count[b] with the largest (score + weight * lm) + len_bonus * length (float64,
+    lowest k on ties) -> (best_ids (B,T), best_len (B), best_score (B) float64, best_k (B)) on the device."""
+    _need_gpu(score, lm, out_len, count, out_ids)
+    B, N, T = out_ids.shape
+    dev = out_ids.device
+    best_ids = torch.empty((B, T), dtype=torch.int32, device=dev)
+    best_len = torch.empty(B, dtype=torch.int32, device=dev)
+    best_score = torch.empty(B, dtype=torch.float64, device=dev)
+    best_k = torch.empty(B, dtype=torch.int32, device=dev)
+    lm = lm.to(torch.float64).contiguous()
+    _lib.check(_lib.lib().ctcn_rescore_select(_ptr(score), _ptr(lm), _ptr(out_len), _ptr(count), _ptr(out_ids), float(weight), float(len_bonus), B, N, T,
+                                              _ptr(best_ids), _ptr(best_len), _ptr(best_score), _ptr(best_k), _lib.stream_ptr()), "rescore_select")
+    return best_ids, best_len, best_score, best_k
+
+
+def rescore_nbest(nbest, scorer, weight, len_bonus=0.0, L=None, boundary=0, ignore_index=-100):
+    """N-best rescoring on the device: `nbest` = the five tensors of beam_decode_nbest_device, `scorer(in_ids, targets, lens)` -> (B*N)
+    float64 ln P of every packed sequence (RNNLM.score_packed).  L: the longest labelling if the caller has read it already, else it is
+    read here (one small read).  Returns RescoredBest(ids (B,T), lengths (B), score (B) float64, k (B), lm (B,N) float64)."""
+    out_ids, out_len, score, count, _ = nbest
+    B, N, T = out_ids.shape
+    if L is None:
+        L = int(out_len.max())
+    in_ids, tgt, lens = pack_nbest(out_ids, out_len, count, min(int(L), T), boundary, ignore_index)
+    lm = scorer(in_ids, tgt, lens).view(B, N)
+    return RescoredBest(*rescore_select(score, lm, out_len, count, out_ids, weight, len_bonus), lm)
 
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step):

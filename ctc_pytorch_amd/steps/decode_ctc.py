@@ -29,6 +29,12 @@ The CER / WER lines and the return value do not change.
 Key `device_context` (--device-context; default off): the test archive is read as BASE features and left_ctx / right_ctx / n_skip_frame /
 n_downsample are applied on the GPU (utils/data_loader.DeviceContext: one launch per batch on the copy stream); the loop sees the batches the
 host loader would have made, bit for bit.
+
+Keys `rnnlm_path`, `rnnlm_weight` (0.5), `rnnlm_nbest` (10), `rnnlm_len_bonus` (0.0) (--rnnlm-path, --rnnlm-weight, --rnnlm-nbest,
+--rnnlm-len-bonus; default off): n-best rescoring of a beam decode with an RNN language model (a package of steps/train_rnnlm.py): the search
+returns its rnnlm_nbest best labellings, the LM scores them on the device and the hypothesis is the one with the largest
+(search score + rnnlm_weight * ln P_lm) + rnnlm_len_bonus * length (utils/ctcDecoder.BeamDecoder).  The loop is still test_ctc's.  A Greedy
+decode_type with rnnlm_path set is an error, not a silent plain decode.
 """
 import argparse
 import os
@@ -237,14 +243,31 @@ def lm_order_option(opts):
     return order
 
 
+def rnnlm_options(opts):
+    """The keys `rnnlm_path` / `rnnlm_weight` / `rnnlm_nbest` / `rnnlm_len_bonus` of a Config as BeamDecoder's keyword arguments; {} while
+    `rnnlm_path` is off (the default)."""
+    path = getattr(opts, "rnnlm_path", None)
+    if not path:
+        return {}
+    nbest = int(getattr(opts, "rnnlm_nbest", 10))
+    if nbest < 1:
+        raise ValueError("rnnlm_nbest must be at least 1, got %d" % nbest)
+    return {"rnnlm": str(path), "rnnlm_weight": float(getattr(opts, "rnnlm_weight", 0.5)), "rnnlm_nbest": nbest,
+            "rnnlm_len_bonus": float(getattr(opts, "rnnlm_len_bonus", 0.0))}
+
+
 def make_decoder(opts, index2word):
-    """test_ctc.make_decoder; with lm_order 3 and a beam decode_type the BeamDecoder is built with a trigram LM."""
+    """test_ctc.make_decoder; with lm_order 3 and a beam decode_type the BeamDecoder is built with a trigram LM, with rnnlm_path with an
+    RNN LM that rescores its n-best list."""
     order = lm_order_option(opts)
-    if order == 2 or opts.decode_type == "Greedy":
+    rnnlm = rnnlm_options(opts)
+    if rnnlm and opts.decode_type == "Greedy":
+        raise ValueError("rnnlm_path rescores a beam search's n-best list: decode_type must not be Greedy")
+    if (order == 2 and not rnnlm) or opts.decode_type == "Greedy":
         return test_ctc.make_decoder(opts, index2word)
     from ctc_pytorch_amd.utils.ctcDecoder import BeamDecoder
     return BeamDecoder(index2word, beam_width=opts.beam_width, blank_index=0, space_idx=-1, lm_path=opts.lm_path, lm_alpha=opts.lm_alpha,
-                       lm_order=order)
+                       lm_order=order, **rnnlm)
 
 
 def apply_argv(conf, a):
@@ -265,6 +288,9 @@ def apply_argv(conf, a):
         conf["device_context"] = True
     if a.lm_order is not None:
         conf["lm_order"] = a.lm_order
+    for key in ("rnnlm_path", "rnnlm_weight", "rnnlm_nbest", "rnnlm_len_bonus"):
+        if getattr(a, key) is not None:
+            conf[key] = getattr(a, key)
     return conf
 
 
@@ -279,6 +305,10 @@ def arg_parser():
     ap.add_argument("--ctm-frame-shift", default=None, type=float, help="seconds per model input frame (default: the YAML's ctm_frame_shift, else 0.01)")
     ap.add_argument("--device-context", action="store_true", help="read the archive as base features and splice / skip / pad on the GPU (default: the YAML's device_context, else off)")
     ap.add_argument("--lm-order", default=None, type=int, choices=[2, 3], help="order of the beam search's LM: 3 reads the ARPA file's 3-gram section (default: the YAML's lm_order, else 2)")
+    ap.add_argument("--rnnlm-path", default=None, metavar="PATH", help="rescore the beam search's n-best list with this RNN LM package (default: the YAML's rnnlm_path, else off)")
+    ap.add_argument("--rnnlm-weight", default=None, type=float, help="weight of the LM's log-probability (default: the YAML's rnnlm_weight, else 0.5)")
+    ap.add_argument("--rnnlm-nbest", default=None, type=int, help="labellings per utterance handed to the LM, at most the beam width (default: the YAML's rnnlm_nbest, else 10)")
+    ap.add_argument("--rnnlm-len-bonus", default=None, type=float, help="added per label of a labelling (default: the YAML's rnnlm_len_bonus, else 0)")
     return ap
 
 
@@ -292,7 +322,7 @@ def main(conf, test_loader=None, index2word=None, log=print):
     report = bool(getattr(opts, "error_report", False))
     ctm = ctm_options(opts)
     context = device_context(opts)
-    if not epoch_options(opts) and not report and not ctm and context is None and lm_order_option(opts) == 2:
+    if not epoch_options(opts) and not report and not ctm and context is None and lm_order_option(opts) == 2 and not rnnlm_options(opts):
         return test_ctc.main(conf, test_loader=test_loader, index2word=index2word, log=log)
     if not getattr(opts, "use_gpu", True):
         raise RuntimeError("ctc_pytorch_amd: use_gpu must be True -- the HIP path has no CPU fallback")

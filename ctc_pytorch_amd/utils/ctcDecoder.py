@@ -262,26 +262,81 @@ class GreedyDecoder(Decoder):
 
 
 class BeamDecoder(Decoder):
-    def __init__(self, int2char, beam_width=200, blank_index=0, space_idx=-1, lm_path=None, lm_alpha=0.01, lm_order=2):
-        """lm_order: 2 = the reference's bigram search; 3 = the ARPA file's \\3-grams: section joins it (LanguageModel(n_gram=3))."""
+    def __init__(self, int2char, beam_width=200, blank_index=0, space_idx=-1, lm_path=None, lm_alpha=0.01, lm_order=2, rnnlm=None,
+                 rnnlm_weight=0.5, rnnlm_nbest=10, rnnlm_len_bonus=0.0):
+        """lm_order: 2 = the reference's bigram search; 3 = the ARPA file's \\3-grams: section joins it (LanguageModel(n_gram=3)).
+        rnnlm (an RNNLM or the path of its package; None: every method takes the path it always took): the search returns its rnnlm_nbest
+        best labellings (clamped to the beam width), the LM scores them, and the hypothesis is the one with the largest
+        (search score + rnnlm_weight * ln P_lm) + rnnlm_len_bonus * length -- n-best rescoring; the search itself does not change."""
         self.beam_width = beam_width
         super().__init__(int2char, space_idx=space_idx, blank_index=blank_index)
         from ctc_pytorch_amd.utils import BeamSearch as uBeam
         from ctc_pytorch_amd.utils import NgramLM as uNgram
         lm = uNgram.LanguageModel(arpa_file=lm_path, n_gram=lm_order)
         self._decoder = uBeam.ctcBeamSearch(int2char, beam_width, lm, lm_alpha=lm_alpha, blank_index=blank_index)
+        self.rnnlm = None
+        if rnnlm is not None:
+            from ctc_pytorch_amd.models.model_rnnlm import RNNLM
+            self.rnnlm = rnnlm if isinstance(rnnlm, RNNLM) else RNNLM.load_package(rnnlm)
+            if self.rnnlm.num_class != len(int2char):
+                raise ValueError("BeamDecoder: the RNN LM has %d classes, the vocabulary %d" % (self.rnnlm.num_class, len(int2char)))
+            if int(rnnlm_nbest) < 1:
+                raise ValueError("BeamDecoder: rnnlm_nbest must be at least 1")
+            self.rnnlm_weight, self.rnnlm_len_bonus = float(rnnlm_weight), float(rnnlm_len_bonus)
+            self.rnnlm_nbest = min(int(rnnlm_nbest), int(beam_width))
+
+    def _rescored(self, lp, frame_seq_len):
+        """The rescoring pipeline on the current stream: n-best search, one small read of the longest hypothesis, pack, RNNLM forward in
+        evaluation mode, log-softmax + NLL, select.  Returns (ops.RescoredBest, status (B)), all on the device.  An utterance whose search
+        reports a status has no candidates: its hypothesis is empty."""
+        d = self._decoder
+        if next(self.rnnlm.parameters()).device != lp.device:
+            self.rnnlm.to(lp.device)
+        out_ids, out_len, score, count, status = ops.beam_decode_nbest_device(lp, frame_seq_len, d._lm_table_on(lp.device), d.lm_alpha, d.beamWidth,
+                                                                              self.rnnlm_nbest, d.blank_index, False)
+        count = torch.where(status == 0, count, torch.zeros_like(count))
+        Lmax = int(out_len.max())                                       # (the one small read)
+        best = ops.rescore_nbest((out_ids, out_len, score, count, status), self.rnnlm.score_packed, self.rnnlm_weight, self.rnnlm_len_bonus, L=Lmax,
+                                 boundary=d.blank_index)
+        return best, status
+
+    def _rescored_strings_async(self, lp, frame_seq_len):
+        """decode() through the rescoring pipeline: the results go to pinned host memory behind it; the callable waits for that copy alone,
+        raises what the plain decoder raises from the search's status and joins the strings in native host code."""
+        best, status = self._rescored(lp, frame_seq_len)
+        B, T = best.ids.shape
+        whole = torch.cat([best.ids.reshape(-1), best.lengths, status])
+        host = torch.empty(whole.shape, dtype=torch.int32, pin_memory=True)
+        host.copy_(whole, non_blocking=True)
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(lp.device))
+        keep = [whole, best]
+
+        def result():
+            event.synchronize()
+            keep.clear()
+            h = host.numpy()
+            ids_c, len_c, st = h[: B * T].reshape(B, T), h[B * T: B * T + B], h[B * T + B:]
+            self._decoder._checked(None, None, st)
+            return ops.join_tokens(ids_c, len_c, self._decoder.classes, " ")
+        return result
 
     def decode(self, prob_tensor, frame_seq_len=None):
         """prob_tensor (T,B,V) log-probs (CPU or device).  exp() is taken on the device in float32."""
         lp = _to_device(prob_tensor)
         if frame_seq_len is None:
             frame_seq_len = [lp.shape[0]] * lp.shape[1]
+        if self.rnnlm is not None:
+            return self._rescored_strings_async(lp, frame_seq_len)()
         return self._decoder.decode_strings_async(lp, frame_seq_len, input_is_prob=False)()
 
     def _device_ids(self, prob_tensor, frame_seq_len=None):
         lp = _to_device(prob_tensor)
         if frame_seq_len is None:
             frame_seq_len = [lp.shape[0]] * lp.shape[1]
+        if self.rnnlm is not None:
+            best, status = self._rescored(lp, frame_seq_len)
+            return best.ids, best.lengths, status
         d = self._decoder
         ids, out_len, _, status = ops.beam_decode_device(lp, frame_seq_len, d._lm_table_on(lp.device), d.lm_alpha, d.beamWidth, d.blank_index, False)
         return ids, out_len, status
@@ -317,4 +372,6 @@ class BeamDecoder(Decoder):
         lp = _to_device(prob_tensor)
         if frame_seq_len is None:
             frame_seq_len = [lp.shape[0]] * lp.shape[1]
+        if self.rnnlm is not None:                    # (the pipeline reads the longest hypothesis once: it is enqueued up to the result copy)
+            return self._rescored_strings_async(lp, frame_seq_len)
         return self._decoder.decode_strings_async(lp, frame_seq_len, input_is_prob=False)      # (strings assembled in native host code)

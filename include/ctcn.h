@@ -1113,6 +1113,53 @@ int ctcn_beam_decode_lm(const float *x, int input_is_prob, const int32_t *lens, 
                         int32_t *out_count, int32_t *status, int T, int B, int V, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * RNN language model and n-best rescoring (lm.hip; the reference's to-do list names both, it has neither).  The model's recurrent layers,
+ * BatchNorm, output product and log-softmax are the entry points above; these are the kernels in front of and behind them.  Integer inputs
+ * are int32; float operands need 4-byte alignment only (16-byte paths are taken where pointers and row lengths allow), float64 ones 8.
+ * `status` is ONE device int32 the kernels OR bits into (1: an embedding id outside [0, V); 2: a target outside [0, V)); the caller clears
+ * it and reads it where it synchronises anyway.  Every product, sum and quotient named below is rounded on its own (no fused multiply-add),
+ * and no float is ever added atomically: each result is a function of the inputs' bits.
+ *
+ * Embedding, forward: y (N,E) = table (V,E) rows by ids (N).  A row whose id is padding_idx (-1: none) is zeros; an id outside [0, V)
+ * never indexes the table: its row is zeros and status bit 1 is raised. */
+int ctcn_embedding_fwd(const int32_t *ids, const float *table, float *y, int N, int V, int E, int padding_idx, int32_t *status, void *stream);
+/* Embedding, backward: dtable[v,:] = beta * dtable[v,:] + s_v, where s_v = ((dy[n0,:] + dy[n1,:]) + dy[n2,:]) + ... over the rows
+ * n0 < n1 < ... with ids[n] == v, float32 additions in that order (the order is the definition: the result equals a host loop bit for bit).
+ * beta is 0 (dtable is not read: s_v, or zeros for an empty list) or 1 (accumulate, as the weight gradients of ctcn_gemm do).  The
+ * padding_idx row and rows no id names get beta * dtable[v,:]; ids outside [0, V) contribute nothing.  ws: the workspace bytes query
+ * below (a stable counting sort of the rows by id: 8 N + 4 (V + 1) + 4 ceil(N / 256) V bytes plus padding; 0 for bad arguments or beyond
+ * 2^30 counters), 4-byte aligned; too small: CTCN_EWORKSPACE. */
+size_t ctcn_embedding_bwd_ws_bytes(int N, int V);
+int ctcn_embedding_bwd(const int32_t *ids, const float *dy, float *dtable, int N, int V, int E, int padding_idx, float beta, void *ws,
+                       size_t ws_bytes, void *stream);
+/* Negative log-likelihood over log-probs: lp (T*B, V) time-major, the output of the log-softmax entry point; tgt (T*B) int32.
+ *   tok (T*B) float32 = -lp[n, tgt[n]]; 0 for tgt[n] == ignore_index; +inf for a log-prob of -inf (as torch)
+ *   seq_sum (B) float64 = sum over t ascending of (double)tok[t,b]; total (1) float64 = sum over b ascending of seq_sum[b]
+ *   count (1) int32 = rows whose target is not ignore_index
+ * A target outside [0, V) that is not ignore_index contributes 0 and raises status bit 2. */
+int ctcn_nll_fwd(const float *lp, const int32_t *tgt, int T, int B, int V, int ignore_index, float *tok, double *seq_sum, double *total,
+                 int32_t *count, int32_t *status, void *stream);
+/* Gradient of that loss with respect to the logits the log-probs came from: dz[n,v] = g_n * (exp(lp[n,v]) - [v == tgt[n]]), float32 expf,
+ * one subtraction, one product; rows that are ignored or whose target is outside [0, V) are zeros; exp(-inf) = 0, never NaN.
+ * g_n = g[n * g_stride]: stride 0 = the scalar upstream gradient of 'sum' / 'mean' (read on the device), stride 1 = reduction 'none'.
+ * count != NULL: g_n is divided by max(*count, 1) first ('mean'; the count stays on the device).  One read of lp, one write of dz; a wave
+ * per row for V <= 512, a workgroup per row above. */
+int ctcn_xent_bwd(const float *lp, const int32_t *tgt, float *dz, int N, int V, int ignore_index, const float *g, int g_stride,
+                  const int32_t *count, void *stream);
+/* From the n-best search's out_ids (B,N,T), out_len (B,N), count (B) to the LM's time-major batch of S = B*N sequences of L + 1 steps
+ * (L <= T: the longest labelling, which the caller has read): sequence s = (b,k) of length l has in_ids[:, s] = [boundary, y_1 .. y_l,
+ * 0 ...], tgt[:, s] = [y_1 .. y_l, boundary, ignore_index ...] and lens[s] = l + 1.  A slot k >= count[b] is the empty sequence
+ * (lens = 1): no sequence has zero steps.  Lengths are clamped to [0, min(L, T)]. */
+int ctcn_lm_pack_nbest(const int32_t *out_ids, const int32_t *out_len, const int32_t *count, int B, int N, int T, int L, int boundary,
+                       int ignore_index, int32_t *in_ids, int32_t *tgt, int32_t *lens, void *stream);
+/* The rescored winner per utterance: over k < count[b], in float64, t_k = (score[b,k] + weight * lm[b,k]) + len_bonus * out_len[b,k];
+ * the largest t_k wins, the lowest k on ties.  best_ids (B,T) = its ids with zeros behind its length, best_len (B), best_score (B) = t_k,
+ * best_k (B).  count[b] == 0: length 0, score 0, best_k = -1.  score, lm (B,N) float64. */
+int ctcn_rescore_select(const double *score, const double *lm, const int32_t *out_len, const int32_t *count, const int32_t *out_ids,
+                        double weight, double len_bonus, int B, int N, int T, int32_t *best_ids, int32_t *best_len, double *best_score,
+                        int32_t *best_k, void *stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Diagnostics (not on the compute path).
  * ctcn_diag_squat: `wgs_per_xcd` workgroups of `threads` threads (+ `lds_bytes` of LDS each) on every XCD that only hold their CU
  * slots for `usec` microseconds (clock-bounded, <= 5 s) -- what an RCCL kernel waiting for a slow peer looks like to the rest of the
