@@ -1,4 +1,5 @@
-// ctc.hip -- log_softmax (+arg-max), CTC alpha/beta lattice and gradient for gfx950.
+// ctc.hip -- log_softmax (+arg-max) and the CTC loss for gfx950: target packing, alpha/beta lattices, gradient, forced alignment.
+// (What is done with a path or a token string afterwards -- greedy collapse, path tokens, edit distance, step statistics -- is paths.hip.)
 //
 // replaces: nn.LogSoftmax(dim=-1) (reference timit/models/model_ctc.py:140,168,181), torch.max(out,-1)
 // (timit/steps/train_ctc.py:51, timit/utils/ctcDecoder.py:163) and nn.CTCLoss forward + autograd backward
@@ -24,7 +25,11 @@
 //   ctc_grad        : fully parallel over (t,b): one wave per frame; blank occupancy by a wave-wide
 //                     log-sum-exp over the even states, label occupancy by a per-class scan of the label
 //                     string (deterministic: fixed order, no atomics).
+//   ctc_pack_targets: concatenated 1-D targets -> the padded (B, Lmax) rows the lattices read.
+//   ctc_align       : forced alignment: the classic alpha walk in the max-plus semiring plus a back-pointer trace.
+// Then, on the host, the two launch plans (lattice passes, alignment) and the extern "C" entry points in one block at the end.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -84,47 +89,59 @@ __global__ __launch_bounds__(256) void log_softmax_bwd_kernel(const float *__res
 
 // log(e^x0 + e^x1 + e^x2) on the hardware exp2 / log2 (1 ulp each): the lattice recursion is a chain of T dependent
 // steps per utterance, so the ~100 instructions of three expf + logf per step were most of its run time.  The sum is in
-// [1, 3], so the log2 result carries an absolute error below 2e-7 per step.
+// [1, 3], so the log2 result carries an absolute error below 2e-7 per step.  All three -inf: -inf, as a select on the result and not a
+// branch around the arithmetic -- the skewed loop has no branch and no exec change, and the classic loop is shorter without one per state.
 __device__ __forceinline__ float lse3(float x0, float x1, float x2) {
   const float m = fmaxf(x0, fmaxf(x1, x2));
-  if (m == -INFINITY) return -INFINITY;
   const float L2E = 1.4426950408889634f;
   const float sum = __builtin_amdgcn_exp2f((x0 - m) * L2E) + __builtin_amdgcn_exp2f((x1 - m) * L2E) + __builtin_amdgcn_exp2f((x2 - m) * L2E);
-  return m + __builtin_amdgcn_logf(sum) * 0.6931471805599453f;
+  const float r = m + __builtin_amdgcn_logf(sum) * 0.6931471805599453f;
+  return m == -INFINITY ? -INFINITY : r;
 }
 
-// direction: +1 alpha (t = 0..Tb-1, neighbours s-1, s-2), -1 beta (t = Tb-1..0, neighbours s+1, s+2)
-// NS = lattice states per thread (host picks the smallest of 1/2/4/8 that covers S = 2L+1 with 256 threads).
-// The recursion is a chain of Tb dependent steps whose per-step work is three LDS reads, one lse3 and one LDS write, so
-// everything else is kept off that chain: the gathered log-probs (and, in the beta pass, the alpha values that
-// alpha + beta overwrites in place) are fetched PF frames ahead into registers, the barrier between steps waits for LDS
-// only, and the alpha / alpha+beta stores are never waited for.
-// ADD (beta pass only): accumulate into `alpha` in place (alpha + beta, the one-buffer reserve of ctcn_ctc_fwd / _bwd);
-// otherwise the pass writes its own lattice, which lets alpha and beta run side by side in one launch (ctcn_ctc_fwd_both).
-template <int DIR, int NS, bool ADD>
-__device__ __forceinline__ void ctc_lattice_body(float *smem, const float *__restrict__ lp, const int64_t *__restrict__ targets,
-                                                 const int64_t *__restrict__ in_len, const int64_t *__restrict__ tgt_len,
-                                                 float *__restrict__ alpha, float *__restrict__ nll, int T, int B, int V, int Lmax,
-                                                 int blank) {
+// ---- The length contract and the nll finish of every CTC kernel ----
+// in_len[b] and tgt_len[b], read once.  bad: lengths a caller must not pass (torch.nn.CTCLoss raises) -- nothing of the lattice is defined: NaN
+// loss, NaN gradient rows, no alignment; Tb, L and S then mean nothing (the kernels that go on with such an utterance, to fill its rows, take
+// them as 0).  Otherwise Tb frames, L labels and S = 2 L + 1 lattice states.  (ctc_lattice_skew_body spells the same rule out: see there.)
+struct CtcLens {
+  int64_t in, tgt;
+  int T, Lmax, Tb, L, S;
+  __device__ __forceinline__ CtcLens(const int64_t *__restrict__ in_len, const int64_t *__restrict__ tgt_len, int b, int T_, int Lmax_)
+      : in(in_len[b]), tgt(tgt_len[b]), T(T_), Lmax(Lmax_), Tb((int)in), L((int)tgt), S(2 * L + 1) {}
+  __device__ __forceinline__ bool bad() const { return in < 0 || in > T || tgt < 0 || tgt > Lmax; }
+};
+
+// nll from the two final alpha states (l2 = -inf where the lattice has one state)
+__device__ __forceinline__ float ctc_nll_from_final(float l1, float l2) {
+  const float m = fmaxf(l1, l2);
+  return m == -INFINITY ? INFINITY : -(m + logf(expf(l1 - m) + expf(l2 - m)));
+}
+
+// ---- The classic lattice walk (ctc_lattice_kernel, ctc_lattices_kernel, ctc_align_kernel's forward chain) ----
+// One workgroup of CTC_THREADS per utterance, state s = tid + k * CTC_THREADS for k < NS (the host picks the smallest of 1/2/4/8/16 that covers
+// Smax), the row of the frame before in a double-buffered LDS row (smem: two rows of Smax floats, then the ext[] row of Smax ints).
+// DIR: +1 walks t = 0 .. Tb - 1 with neighbours s - 1, s - 2 (alpha), -1 walks t = Tb - 1 .. 0 with s + 1, s + 2 (beta).
+// The recursion is a chain of Tb dependent steps whose per-step work is three LDS reads, one combine and one LDS write, so everything else is
+// kept off that chain: the gathered log-probs (and whatever else the policy wants of a frame, Policy::prefetch) are fetched PF frames ahead into
+// registers, the barrier between steps waits for LDS only, and what the policy stores to memory is never waited for.
+// What differs between the users is the Policy -- the semiring and what a frame leaves behind:
+//   float prefetch(t, s)                    a second value fetched with the gather of (t, s) and handed back to emit as `pre` (0.0f: none)
+//   void  first(t, s, v)                    the first frame's value of state s < S
+//   float combine(x0, x1, x2, q, int &tag)  the value of a state from prev[s], prev[s -/+ 1], prev[s -/+ 2] (-inf where the move does not exist)
+//                                           and the gathered log-prob q; tag (0 on entry) is a by-product that emit gets back
+//   void  emit(t, s, live, v, tag, pre)     called by EVERY lane, live = s < S (v and tag are 0 otherwise), so that it may hold wave-wide operations
+// Returns the row of the last frame; only a barrier's worth of LDS ordering stands behind it (the walk's last lds_barrier, or the
+// __syncthreads after the first frame when Tb == 1).  The caller has ruled out Tb <= 0.
+template <int DIR, int NS, class Policy>
+__device__ __forceinline__ const float *ctc_classic_walk(float *smem, const float *__restrict__ lp, const int64_t *__restrict__ targets, int Tb,
+                                                         int S, int B, int V, int Lmax, int blank, const Policy &pol) {
   constexpr int PF = 4;
-  constexpr bool ACC = DIR < 0 && ADD;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int Smax = 2 * Lmax + 1;
-  const int Tb = (int)in_len[b], L = (int)tgt_len[b];
-  // lengths a caller must not pass (torch.nn.CTCLoss raises): nothing of the lattice is defined -- NaN loss, NaN gradient rows
-  if (in_len[b] < 0 || in_len[b] > T || tgt_len[b] < 0 || tgt_len[b] > Lmax) {
-    if (DIR > 0 && tid == 0) nll[b] = __uint_as_float(0x7fc00000u);
-    return;
-  }
-  const int S = 2 * L + 1;
   float *buf0 = smem, *buf1 = smem + Smax;
   int *ext = reinterpret_cast<int *>(smem + 2 * Smax);
   for (int s = tid; s < S; s += CTC_THREADS) ext[s] = (s & 1) ? (int)targets[(size_t)b * Lmax + (s >> 1)] : blank;
   __syncthreads();
-  if (Tb <= 0) {
-    if (DIR > 0 && tid == 0) nll[b] = L == 0 ? 0.0f : INFINITY;
-    return;
-  }
   // per-thread static state info
   int my_ext[NS];
   bool my_skip[NS];
@@ -151,25 +168,26 @@ __device__ __forceinline__ void ctc_lattice_body(float *smem, const float *__res
         if (DIR > 0) { if (s <= 1) v = lpt[my_ext[k]]; }
         else { if (s >= S - 2) v = lpt[my_ext[k]]; }
         buf0[s] = v;
-        float *ap = alpha + ((size_t)t_first * B + b) * Smax + s;
-        if (ACC) *ap += v; else *ap = v;
+        pol.first(t_first, s, v);
       }
     }
   }
   __syncthreads();
   float *prev = buf0, *cur = buf1;
-  float nq[PF][NS], na[PF][NS];      // prefetched frames n0 .. n0+PF-1 of the NEXT chunk: log-prob gather / old alpha
-#pragma unroll
-  for (int i = 0; i < PF; ++i) {
-    const int t = t_first + DIR * min(1 + i, Tb - 1);
+  // frame n of the walk (the last one again past it: those loads are not used) into one slot of the prefetch ring
+  auto fetch = [&](int n, float (&q)[NS], float (&a)[NS]) {
+    const int t = t_first + DIR * min(n, Tb - 1);
     const float *lpt = lp + ((size_t)t * B + b) * V;
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
       const int s = tid + k * CTC_THREADS;
-      nq[i][k] = s < S ? lpt[my_ext[k]] : 0.0f;
-      na[i][k] = (ACC && s < S) ? alpha[((size_t)t * B + b) * Smax + s] : 0.0f;
+      q[k] = s < S ? lpt[my_ext[k]] : 0.0f;
+      a[k] = s < S ? pol.prefetch(t, s) : 0.0f;
     }
-  }
+  };
+  float nq[PF][NS], na[PF][NS];      // prefetched frames n0 .. n0+PF-1 of the NEXT chunk: log-prob gather / the policy's own value
+#pragma unroll
+  for (int i = 0; i < PF; ++i) fetch(1 + i, nq[i], na[i]);
   for (int n0 = 1; n0 < Tb; n0 += PF) {
     float cq[PF][NS], ca[PF][NS];
 #pragma unroll
@@ -178,16 +196,7 @@ __device__ __forceinline__ void ctc_lattice_body(float *smem, const float *__res
       for (int k = 0; k < NS; ++k) { cq[i][k] = nq[i][k]; ca[i][k] = na[i][k]; }
     if (n0 + PF < Tb) {
 #pragma unroll
-      for (int i = 0; i < PF; ++i) {
-        const int t = t_first + DIR * min(n0 + PF + i, Tb - 1);
-        const float *lpt = lp + ((size_t)t * B + b) * V;
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-          const int s = tid + k * CTC_THREADS;
-          nq[i][k] = s < S ? lpt[my_ext[k]] : 0.0f;
-          if (ACC) na[i][k] = s < S ? alpha[((size_t)t * B + b) * Smax + s] : 0.0f;
-        }
-      }
+      for (int i = 0; i < PF; ++i) fetch(n0 + PF + i, nq[i], na[i]);
     }
 #pragma unroll
     for (int i = 0; i < PF; ++i) {
@@ -197,41 +206,85 @@ __device__ __forceinline__ void ctc_lattice_body(float *smem, const float *__res
 #pragma unroll
         for (int k = 0; k < NS; ++k) {
           const int s = tid + k * CTC_THREADS;
+          float v = 0.0f;
+          int tag = 0;
           if (s < S) {
             const float x0 = prev[s];
             float x1, x2;
             if (DIR > 0) { x1 = s >= 1 ? prev[s - 1] : -INFINITY; x2 = my_skip[k] ? prev[s - 2] : -INFINITY; }
             else { x1 = s + 1 < S ? prev[s + 1] : -INFINITY; x2 = my_skip[k] ? prev[s + 2] : -INFINITY; }
-            const float v = lse3(x0, x1, x2) + cq[i][k];
+            v = pol.combine(x0, x1, x2, cq[i][k], tag);
             cur[s] = v;
-            alpha[((size_t)t * B + b) * Smax + s] = ACC ? ca[i][k] + v : v;
           }
+          pol.emit(t, s, s < S, v, tag, ca[i][k]);
         }
-        lds_barrier();       // LDS only: the alpha stores and the prefetches stay in flight across timesteps
+        lds_barrier();       // LDS only: the policy's stores and the prefetches stay in flight across timesteps
         float *tmp = prev; prev = cur; cur = tmp;
       }
     }
   }
-  if (DIR > 0 && tid == 0) {
-    const float l1 = prev[S - 1], l2 = S > 1 ? prev[S - 2] : -INFINITY;
-    const float m = fmaxf(l1, l2);
-    nll[b] = m == -INFINITY ? INFINITY : -(m + logf(expf(l1 - m) + expf(l2 - m)));
-  }
+  return prev;
 }
 
+// The sum semiring: alpha (DIR +1) and beta (DIR -1) into the lattice `lat` (T, B, Smax).  ACC (the beta pass of ctcn_ctc_bwd): every value is
+// added to what `lat` holds -- alpha + beta in place, the one-buffer reserve; the old values are the policy's prefetched stream.  Otherwise the pass
+// writes its own lattice, which lets alpha and beta run side by side in one launch (ctcn_ctc_fwd_both).
+template <bool ACC>
+struct CtcSumPolicy {
+  float *__restrict__ lat;
+  int B, b, Smax;
+  __device__ __forceinline__ float *at(int t, int s) const { return lat + ((size_t)t * B + b) * Smax + s; }
+  __device__ __forceinline__ float prefetch(int t, int s) const { return ACC ? *at(t, s) : 0.0f; }
+  __device__ __forceinline__ void first(int t, int s, float v) const { *at(t, s) = ACC ? *at(t, s) + v : v; }
+  __device__ __forceinline__ float combine(float x0, float x1, float x2, float q, int &) const { return lse3(x0, x1, x2) + q; }
+  __device__ __forceinline__ void emit(int t, int s, bool live, float v, int, float pre) const {
+    if (live) *at(t, s) = ACC ? pre + v : v;
+  }
+};
+
+template <int DIR, int NS, bool ACC>
+__device__ __forceinline__ void ctc_lattice_body(float *smem, const float *__restrict__ lp, const int64_t *__restrict__ targets,
+                                                 const int64_t *__restrict__ in_len, const int64_t *__restrict__ tgt_len,
+                                                 float *__restrict__ lat, float *__restrict__ nll, int T, int B, int V, int Lmax, int blank) {
+  static_assert(!ACC || DIR < 0, "only the beta pass adds into the lattice it finds");
+  const int b = blockIdx.x;
+  const CtcLens len(in_len, tgt_len, b, T, Lmax);
+  if (len.bad() || len.Tb <= 0) {          // no lattice to walk: the alpha pass answers nll -- NaN, 0 for the empty label on no frames, else +inf
+    if (DIR > 0 && threadIdx.x == 0) nll[b] = len.bad() ? __uint_as_float(0x7fc00000u) : len.L == 0 ? 0.0f : INFINITY;
+    return;                                // (before any barrier)
+  }
+  const CtcSumPolicy<ACC> pol{lat, B, b, 2 * Lmax + 1};
+  const float *last = ctc_classic_walk<DIR, NS>(smem, lp, targets, len.Tb, len.S, B, V, Lmax, blank, pol);
+  if (DIR > 0 && threadIdx.x == 0) nll[b] = ctc_nll_from_final(last[len.S - 1], len.S > 1 ? last[len.S - 2] : -INFINITY);
+}
+
+// one pass: alpha (DIR +1) into its own lattice, or beta (DIR -1) added into the alpha lattice in place (nll is not touched)
 template <int DIR, int NS>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_lattice_kernel(const float *__restrict__ lp, const int64_t *__restrict__ targets,
                                                                   const int64_t *__restrict__ in_len,
                                                                   const int64_t *__restrict__ tgt_len, float *__restrict__ alpha,
                                                                   float *__restrict__ nll, int T, int B, int V, int Lmax, int blank) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  ctc_lattice_body<DIR, NS, true>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank);
+  ctc_lattice_body<DIR, NS, (DIR < 0)>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank);
+}
+
+// alpha (blockIdx.y = 0) and beta (blockIdx.y = 1) of every utterance in one launch: the two passes are independent chains of
+// T dependent steps, so running them side by side halves the latency of the loss (2B workgroups instead of B twice).
+template <int NS>
+__global__ __launch_bounds__(CTC_THREADS) void ctc_lattices_kernel(const float *__restrict__ lp, const int64_t *__restrict__ targets,
+                                                                   const int64_t *__restrict__ in_len,
+                                                                   const int64_t *__restrict__ tgt_len, float *__restrict__ alpha,
+                                                                   float *__restrict__ beta, float *__restrict__ nll, int T, int B, int V,
+                                                                   int Lmax, int blank) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  if (blockIdx.y == 0) ctc_lattice_body<1, NS, false>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank);
+  else ctc_lattice_body<-1, NS, false>(smem, lp, targets, in_len, tgt_len, beta, nll, T, B, V, Lmax, blank);
 }
 
 // (Measured and dropped: one wave per (utterance, pass) with the lattice in registers -- lane l holding states 2l and 2l + 1,
 // no LDS, no barrier -- is bit-identical but not faster at cfg2: neighbour states through ds_bpermute 230 us (round 1); through DPP
 // wave shifts (one per alpha step), with hand-counted vmcnt for the gathers / lattice stores, pointer-stepped addressing and a
-// two-term lse for the blank states: 195 us, the same as the 193-195 us of this kernel (round 2).  With lse3 replaced by a max the
+// two-term lse for the blank states: 195 us, the same as the 193-195 us of ctc_lattice_kernel (round 2).  With lse3 replaced by a max the
 // wave version takes 101 us: a step is ~280 cycles of quarter-rate transcendentals (5 exp2 + 2 log2 per lane holding two states)
 // + ~300 cycles of everything else, and neither is the exchange.)
 
@@ -279,14 +332,6 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_lattice_kernel(const float *_
 // their ring read and after their ring write in every trip; the product instantiation carries no code for it.
 constexpr int CTC_CHUNK = 4, CTC_SKEW = 3, CTC_RING = 4, CTC_SKEW_WAVES = 4, CTC_SLOW_SLEEP = 32;
 
-__device__ __forceinline__ float lse3_select(float x0, float x1, float x2) {     // lse3 with the -inf case as a select: the same bits
-  const float m = fmaxf(x0, fmaxf(x1, x2));
-  const float L2E = 1.4426950408889634f;
-  const float sum = __builtin_amdgcn_exp2f((x0 - m) * L2E) + __builtin_amdgcn_exp2f((x1 - m) * L2E) + __builtin_amdgcn_exp2f((x2 - m) * L2E);
-  const float r = m + __builtin_amdgcn_logf(sum) * 0.6931471805599453f;
-  return m == -INFINITY ? -INFINITY : r;
-}
-
 // lds_barrier() with the wait as an instruction the compiler's own s_waitcnt placement sees: behind an opaque asm wait it waits again, with
 // lgkmcnt(0), at the first use of a ring value loaded a trip earlier -- and so for the ring accesses just issued, on the chain.
 __device__ __forceinline__ void skew_barrier() {
@@ -310,6 +355,8 @@ __device__ __forceinline__ void ctc_lattice_skew_body(float *smem, const float *
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);           // wave-uniform for the compiler too: the trip loops are scalar loops
   const int Smax = 2 * Lmax + 1;
+  // The classic body's length rule (CtcLens) spelt out: through the struct the compiler lays the kernel's blocks out differently around the same
+  // chunk loops, which measures 0.6 us per launch slower at cfg2 (86.5 against 85.9 us; profiles/ctc_refactor_checks.txt)
   const int Tb = (int)in_len[b], L = (int)tgt_len[b];
   if (in_len[b] < 0 || in_len[b] > T || tgt_len[b] < 0 || tgt_len[b] > Lmax) {
     if (DIR > 0 && tid == 0) nll[b] = __uint_as_float(0x7fc00000u);
@@ -389,7 +436,7 @@ __device__ __forceinline__ void ctc_lattice_skew_body(float *smem, const float *
     auto frame = [&](float e0, float e1, float q) {
       const float x1 = wave_shift1<DIR>(e0, a);
       const float x2r = wave_shift1<DIR>(e1, x1);
-      const float v = lse3_select(a, x1, my_skip ? x2r : -INFINITY) + q;
+      const float v = lse3(a, x1, my_skip ? x2r : -INFINITY) + q;
       orow += out_step;
       put(orow, v);
       a = v;
@@ -431,11 +478,7 @@ __device__ __forceinline__ void ctc_lattice_skew_body(float *smem, const float *
   }
   if (DIR > 0) {
     __syncthreads();
-    if (tid == 0) {
-      const float l1 = fin[0], l2 = S > 1 ? fin[1] : -INFINITY;
-      const float m = fmaxf(l1, l2);
-      nll[b] = m == -INFINITY ? INFINITY : -(m + logf(expf(l1 - m) + expf(l2 - m)));
-    }
+    if (tid == 0) nll[b] = ctc_nll_from_final(fin[0], S > 1 ? fin[1] : -INFINITY);
   }
 }
 
@@ -449,19 +492,6 @@ __global__ __launch_bounds__(64 * CTC_SKEW_WAVES) void ctc_lattices_skew_kernel(
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (blockIdx.y == 0) ctc_lattice_skew_body<1, SLOW>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank, slow_mask);
   else ctc_lattice_skew_body<-1, SLOW>(smem, lp, targets, in_len, tgt_len, beta, nll, T, B, V, Lmax, blank, slow_mask);
-}
-
-// alpha (blockIdx.y = 0) and beta (blockIdx.y = 1) of every utterance in one launch: the two passes are independent chains of
-// T dependent steps, so running them side by side halves the latency of the loss (2B workgroups instead of B twice).
-template <int NS>
-__global__ __launch_bounds__(CTC_THREADS) void ctc_lattices_kernel(const float *__restrict__ lp, const int64_t *__restrict__ targets,
-                                                                   const int64_t *__restrict__ in_len,
-                                                                   const int64_t *__restrict__ tgt_len, float *__restrict__ alpha,
-                                                                   float *__restrict__ beta, float *__restrict__ nll, int T, int B, int V,
-                                                                   int Lmax, int blank) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  if (blockIdx.y == 0) ctc_lattice_body<1, NS, false>(smem, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank);
-  else ctc_lattice_body<-1, NS, false>(smem, lp, targets, in_len, tgt_len, beta, nll, T, B, V, Lmax, blank);
 }
 
 // online log-sum-exp accumulator
@@ -495,9 +525,9 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float *__restrict__
   int *start = gsm, *pos = gsm + V + 1;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int b = blockIdx.y, t0 = blockIdx.x * GRAD_TCH, t1 = min(T, t0 + GRAD_TCH);
-  const bool bad = in_len[b] < 0 || in_len[b] > T || tgt_len[b] < 0 || tgt_len[b] > Lmax;          // see ctc_lattice_body
-  const bool zero = !bad && zinf && nll[b] == INFINITY;
-  const int Tb = bad ? 0 : zero ? 0 : (int)in_len[b], L = bad ? 0 : (int)tgt_len[b];
+  const CtcLens len(in_len, tgt_len, b, T, Lmax);
+  const bool bad = len.bad(), zero = !bad && zinf && nll[b] == INFINITY;
+  const int Tb = bad ? 0 : zero ? 0 : len.Tb, L = bad ? 0 : len.L;
   const int64_t *tg = targets + (size_t)b * Lmax;
   if (!bad && t0 < Tb) {
     // class c (thread c) counts its label positions, a serial prefix sum over the V classes, then every class writes its positions
@@ -561,217 +591,6 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float *__restrict__
   }
 }
 
-__global__ void greedy_collapse_kernel(const int32_t *__restrict__ idx, size_t st_t, size_t st_b, const int32_t *__restrict__ lens,
-                                       int32_t *__restrict__ out_ids, int32_t *__restrict__ out_len, int T, int B, int blank) {
-  // one wave per utterance: 64 frames per iteration, ballot + popcount compaction (order preserving)
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int n = min(max(lens[b], 0), T);
-  int base = 0;
-  for (int t0 = 0; t0 < n; t0 += 64) {
-    const int t = t0 + lane;
-    int k = blank;
-    bool keep = false;
-    if (t < n) {
-      k = idx[t * st_t + b * st_b];
-      keep = k != blank && (t == 0 || k != idx[(t - 1) * st_t + b * st_b]);
-    }
-    const unsigned long long mask = __ballot(keep);
-    if (keep) out_ids[(size_t)b * T + base + __popcll(mask & ((1ull << lane) - 1ull))] = k;
-    base += __popcll(mask);
-  }
-  if (lane == 0) out_len[b] = base;
-}
-
-// Tokens of a per-frame class path with their frames and scores (ctcn_path_tokens; the definition is in include/ctcn.h).  One workgroup
-// per utterance, PT_THREADS frames per chunk, two phases per chunk:
-//   A (all four waves): 16 lanes per frame gather lp[t, b, k] and, for a frame inside a token, max_{c != k} lp[t, b, c] (one pass over the
-//     row, a 4-step butterfly), into LDS.  Blank frames read their one element, ids outside [0, V) nothing.
-//   B (wave 0, 64 frames at a time): token starts by ballot (greedy_collapse_kernel's rule), the three per-token reductions by one segmented
-//     inclusive scan (a start or a blank frame raises the flag that stops the scan), the token's first frame from the highest start bit at or
-//     below the lane.  A run that is still open at lane 63 travels to the next 64 frames in wave-uniform carry registers and is added to the
-//     lanes whose scan met no flag.  The lane that holds a run's last frame writes the token.
-// -inf log-probs stay -inf in their own token only: nothing is a difference of prefix sums.
-#define PT_THREADS 256
-__device__ __forceinline__ int pt_class(const int32_t *__restrict__ path, size_t st_t, size_t st_b, int t, int b, int V) {
-  const int k = path[(size_t)t * st_t + (size_t)b * st_b];
-  return (k >= 0 && k < V) ? k : -1;
-}
-__global__ __launch_bounds__(PT_THREADS) void path_tokens_kernel(const int32_t *__restrict__ path, size_t st_t, size_t st_b, const float *__restrict__ lp,
-                                                                 const int32_t *__restrict__ lens, int32_t *__restrict__ out_ids, int32_t *__restrict__ out_len,
-                                                                 int32_t *__restrict__ starts, int32_t *__restrict__ ends, float *__restrict__ tok_mean,
-                                                                 float *__restrict__ tok_min, float *__restrict__ tok_margin, float *__restrict__ path_score,
-                                                                 int T, int B, int V, int blank) {
-  __shared__ float sx[PT_THREADS], sc[PT_THREADS];
-  __shared__ int sk[PT_THREADS];                            // the chunk's class ids (-1: outside [0, V)), so that phase B reads the path from LDS
-  __shared__ int s_base;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = min(max(lens[b], 0), T);
-  const int grp = tid >> 4, sub = tid & 15;
-  int base = 0, c_start = 0;                                // wave 0: tokens started so far; the open run's first frame and partial reductions
-  double c_sum = 0.0, c_msum = 0.0, total = 0.0;
-  float c_min = INFINITY;
-  for (int t0 = 0; t0 < n; t0 += PT_THREADS) {
-    // ---- A
-    for (int f = 0; f < PT_THREADS / 16; ++f) {
-      const int slot = f * 16 + grp, t = t0 + slot;
-      if (t >= n) continue;                                 // (uniform over the 16 lanes of a frame)
-      const int k = pt_class(path, st_t, st_b, t, b, V);
-      float x = 0.0f, m = -INFINITY;
-      if (k >= 0) {
-        const float *row = lp + ((size_t)t * B + b) * V;
-        if (k == blank) {
-          x = row[k];
-        } else {
-          for (int c = sub; c < V; c += 16) {
-            const float v = row[c];
-            if (c == k) x = v; else m = fmaxf(m, v);
-          }
-#pragma unroll
-          for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 16));
-          x = __shfl(x, k & 15, 16);
-        }
-      }
-      if (sub == 0) { sx[slot] = x; sc[slot] = m; sk[slot] = k; }
-    }
-    __syncthreads();
-    // ---- B
-    if (wave == 0) {
-      for (int s0 = 0; s0 < PT_THREADS && t0 + s0 < n; s0 += 64) {
-        const int t = t0 + s0 + lane;
-        const bool live = t < n;
-        int kn = blank, kp = blank, kx = blank;
-        float x = 0.0f, comp = 0.0f;
-        if (live) {
-          const int slot = s0 + lane;                       // (only the chunk's first and last frame look at the path itself)
-          kn = sk[slot];
-          if (t > 0) kp = slot > 0 ? sk[slot - 1] : pt_class(path, st_t, st_b, t - 1, b, V);
-          if (t + 1 < n) kx = slot + 1 < PT_THREADS ? sk[slot + 1] : pt_class(path, st_t, st_b, t + 1, b, V);
-          kn = kn < 0 ? blank : kn; kp = kp < 0 ? blank : kp; kx = kx < 0 ? blank : kx;
-          x = sx[slot];
-          comp = sc[slot];
-        }
-        total += (double)x;
-        const bool member = live && kn != blank;
-        const bool head = member && (t == 0 || kn != kp);
-        const bool last = member && (t + 1 >= n || kx != kn);
-        double sum = member ? (double)x : 0.0, msum = member ? (double)x - (double)comp : 0.0;
-        float mn = member ? x : INFINITY;
-        int flag = (head || !member) ? 1 : 0;
-        for (int o = 1; o < 64; o <<= 1) {
-          const double s2 = __shfl_up(sum, o, 64), m2 = __shfl_up(msum, o, 64);
-          const float n2 = __shfl_up(mn, o, 64);
-          const int f2 = __shfl_up(flag, o, 64);
-          if (lane >= o && !flag) { sum += s2; msum += m2; mn = fminf(mn, n2); flag = f2; }
-        }
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long le = heads & ((2ull << lane) - 1ull);
-        int start = le ? t0 + s0 + 63 - __clzll(le) : c_start;
-        if (!flag) { sum += c_sum; msum += c_msum; mn = fminf(mn, c_min); }      // no start and no blank at or below this lane: the carried run
-        if (last) {
-          const size_t j = (size_t)b * T + (base + __popcll(le) - 1);
-          const double cnt = (double)(t + 1 - start);
-          out_ids[j] = kn; starts[j] = start; ends[j] = t + 1;
-          tok_mean[j] = (float)(sum / cnt); tok_min[j] = mn; tok_margin[j] = (float)(msum / cnt);
-        }
-        base += __popcll(heads);
-        c_sum = __shfl(sum, 63, 64); c_msum = __shfl(msum, 63, 64); c_min = __shfl(mn, 63, 64); c_start = __shfl(start, 63, 64);
-      }
-    }
-    __syncthreads();
-  }
-  if (wave == 0) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o, 64);
-    if (lane == 0) { s_base = base; out_len[b] = base; path_score[b] = (float)total; }
-  }
-  __syncthreads();
-  for (int j = s_base + tid; j < T; j += PT_THREADS) {
-    const size_t o = (size_t)b * T + j;
-    out_ids[o] = -1; starts[o] = -1; ends[o] = -1;
-    tok_mean[o] = 0.0f; tok_min[o] = 0.0f; tok_margin[o] = 0.0f;
-  }
-}
-
-// Levenshtein distance between the collapsed prediction a[b,:a_len[b]] (int32) and the label b[b,:b_len[b]] (int64):
-// one lane per utterance, DP row in LDS (row stride ldrow), sequential over the O(La*Lb) cells of its utterance.
-__global__ void edit_distance_kernel(const int32_t *__restrict__ a, const int32_t *__restrict__ a_len, const int64_t *__restrict__ bl,
-                                     const int64_t *__restrict__ b_len, int32_t *__restrict__ out, int B, int lda, int ldb, int ldrow) {
-  extern __shared__ int rows[];
-  const int u = blockIdx.x * blockDim.x + threadIdx.x;
-  if (u >= B) return;
-  int *row = rows + (size_t)threadIdx.x * ldrow;
-  const int la = min(max(a_len[u], 0), lda), lb = (int)min(max(b_len[u], (int64_t)0), (int64_t)min(ldrow - 2, ldb));   // never beyond the row / the buffers
-  const int32_t *pa = a + (size_t)u * lda;
-  const int64_t *pb = bl + (size_t)u * ldb;
-  for (int j = 0; j <= lb; ++j) row[j] = j;
-  for (int i = 1; i <= la; ++i) {
-    int diag = row[0];
-    row[0] = i;
-    const int x = pa[i - 1];
-    for (int j = 1; j <= lb; ++j) {
-      const int up = row[j];
-      const int v = min(min(up + 1, row[j - 1] + 1), diag + (x != (int)pb[j - 1]));
-      diag = up;
-      row[j] = v;
-    }
-  }
-  out[u] = row[lb];
-}
-
-// The same distance on one wavefront per utterance, along anti-diagonals: lane L owns the NC label columns L*NC+1 .. (L+1)*NC and
-// at step d fills row i = d - L of them, so the only cross-lane traffic per step is one DPP shift (the right-most cell of the
-// left neighbour, which that lane finished one step earlier; its value of two steps ago is the diagonal).  la + 63 steps of ~5
-// dependent instructions instead of la*lb sequential LDS round trips: 1 230 -> ~25 us for 32 x (800 x 50) (tools/epoch_probe.py).
-template <int NC>
-__global__ __launch_bounds__(64) void edit_distance_wave_kernel(const int32_t *__restrict__ a, const int32_t *__restrict__ a_len, const int64_t *__restrict__ bl,
-                                                                const int64_t *__restrict__ b_len, int32_t *__restrict__ out, int lda, int ldb, int max_b_len) {
-  extern __shared__ int pred[];
-  const int u = blockIdx.x, L = threadIdx.x;
-  const int la = min(max(a_len[u], 0), lda), lb = (int)min(max(b_len[u], (int64_t)0), (int64_t)min(max_b_len, ldb));
-  const int32_t *pa = a + (size_t)u * lda;
-  const int64_t *pb = bl + (size_t)u * ldb;
-  for (int i = L; i < la; i += 64) pred[i] = pa[i];
-  int lab[NC], up[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int j = L * NC + c + 1;
-    lab[c] = j <= lb ? (int)pb[j - 1] : -1;
-    up[c] = j;                                          // row 0
-  }
-  int vlast = (L + 1) * NC, left_prev = L * NC;
-  __syncthreads();
-  int x = (L == 0 && la > 0) ? pred[0] : 0;             // prediction symbol of the row this lane fills at step 1
-  for (int d = 1; d <= la + 63; ++d) {
-    const int i = d - L;
-    const bool active = i >= 1 && i <= la;
-    const int xn = (i >= 0 && i < la) ? pred[i] : 0;    // next step's symbol (row i + 1), fetched off the dependent chain
-    const int recv = __builtin_amdgcn_update_dpp(0, vlast, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-    const int left = L == 0 ? i : recv, diag = L == 0 ? i - 1 : left_prev;
-    int nv[NC];
-    nv[0] = min(min(up[0] + 1, left + 1), diag + (x != lab[0] ? 1 : 0));
-#pragma unroll
-    for (int c = 1; c < NC; ++c) nv[c] = min(min(up[c] + 1, nv[c - 1] + 1), up[c - 1] + (x != lab[c] ? 1 : 0));
-    if (active) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) up[c] = nv[c];
-      vlast = nv[NC - 1];
-      left_prev = recv;
-    }
-    x = xn;
-  }
-  if (lb == 0) {
-    if (L == 0) out[u] = la;
-  } else if (L == (lb - 1) / NC) {
-    const int cc = (lb - 1) % NC;
-    int r = up[0];
-#pragma unroll
-    for (int c = 1; c < NC; ++c) r = c == cc ? up[c] : r;
-    out[u] = r;
-  }
-}
-
 // Concatenated 1-D targets (torch's second layout) -> the padded (B, Lmax) rows the lattice reads, zero-filled past each length.  One
 // workgroup per utterance; its offset is the exclusive prefix sum of the lengths before it (negative lengths count as 0: the lattice
 // answers NaN for them), summed by the workgroup in a fixed order.  Nothing past flat[n_flat) is read.
@@ -796,8 +615,8 @@ __global__ __launch_bounds__(256) void ctc_pack_targets_kernel(const int64_t *__
 //   v[t][s] = max(v[t-1][s], v[t-1][s-1], v[t-1][s-2] if the loss allows the skip) + lp[t, ext(s)]   -- ONE float32 add, never fused
 //   ties: the smallest move wins (a candidate replaces the best so far only if strictly greater), so the result is a function of the
 //   input alone and a float32 restatement on the host is bit-identical.
-// One workgroup per utterance, the forward chain laid out as ctc_lattice_body (state s = tid + k * CTC_THREADS, double-buffered LDS row,
-// gathers PF frames ahead, one LDS barrier per frame).  The move of (t, s) is a 2-bit code; the 16 lanes tid & ~15 .. tid | 15 hold 16
+// One workgroup per utterance; the forward chain is ctc_classic_walk with CtcMaxPolicy (state s = tid + k * CTC_THREADS, double-buffered LDS
+// row, gathers PF frames ahead, one LDS barrier per frame).  The move of (t, s) is a 2-bit code; the 16 lanes tid & ~15 .. tid | 15 hold 16
 // consecutive states, so two wave ballots hand the first lane of each group of 16 the packed word of its group (low bits in [0,16), high
 // bits in [16,32)): one dword store per 16 states, no sub-dword write, no LDS atomic.  Rows of W = ceil(Smax / 16) words per frame live
 //   BPLDS : in dynamic LDS behind the value rows (cfg2: 800 frames x 8 words = 25 KB), where the trace -- a chain of Tb dependent reads
@@ -812,12 +631,27 @@ constexpr int ALIGN_WALK = 8;                      // frames the walking lane ta
 constexpr int ALIGN_GWORDS = 2048;                 // workspace branch: LDS words for the rows of a chunk (>= 8 frames at Smax = 4095)
 constexpr size_t ALIGN_LDS_LIMIT = 64 * 1024;      // dynamic LDS of a launch that has not opted in to more (of the CU's 160 KB)
 
-static inline int align_row_words(int Lmax) { return ceil_div(2 * Lmax + 1, 16); }
-static inline size_t align_lds_fixed(int Lmax) { return (size_t)(3 * (2 * Lmax + 1) + ALIGN_CH + 2) * sizeof(float); }
-// host arithmetic on the shapes only: the same (T, Lmax) always takes the same branch
-static inline bool align_rows_in_lds(int T, int Lmax) {
-  return align_lds_fixed(Lmax) + (size_t)T * align_row_words(Lmax) * sizeof(uint32_t) <= ALIGN_LDS_LIMIT;
-}
+// The max-plus semiring of ctc_classic_walk: the best of the three moves (strictly greater replaces: the smallest move wins a tie) plus the
+// log-prob, the move as the tag; a frame leaves its packed back-pointer words in `rows` (LDS or workspace, W words per frame).
+struct CtcMaxPolicy {
+  uint32_t *rows;
+  int W, lane;
+  __device__ __forceinline__ float prefetch(int, int) const { return 0.0f; }
+  __device__ __forceinline__ void first(int, int, float) const {}
+  __device__ __forceinline__ float combine(float x0, float x1, float x2, float q, int &code) const {
+    float best = x0;
+    if (x1 > best) { best = x1; code = 1; }
+    if (x2 > best) { best = x2; code = 2; }
+    return __fadd_rn(best, q);
+  }
+  // the two ballots run with every lane of the wave (code 0 in a lane past S)
+  __device__ __forceinline__ void emit(int t, int s, bool live, float, int code, float) const {
+    const int wsh = lane & 48;                      // this lane's group of 16 inside the two ballots
+    const unsigned long long m0 = __ballot(code & 1), m1 = __ballot(code & 2);
+    if ((lane & 15) == 0 && live)
+      rows[(size_t)t * W + (s >> 4)] = (uint32_t)((m0 >> wsh) & 0xffffull) | ((uint32_t)((m1 >> wsh) & 0xffffull) << 16);
+  }
+};
 
 template <int NS, bool BPLDS>
 __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(const float *__restrict__ lp, const int64_t *__restrict__ targets,
@@ -827,11 +661,11 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(const float *__r
                                                                 int32_t *__restrict__ ends, uint32_t *__restrict__ ws, int T, int B, int V, int Lmax,
                                                                 int blank) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int PF = 4;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int Smax = 2 * Lmax + 1, W = (Smax + 15) >> 4;
-  const bool bad = in_len[b] < 0 || in_len[b] > T || tgt_len[b] < 0 || tgt_len[b] > Lmax;        // see ctc_lattice_body
-  const int Tb = bad ? 0 : (int)in_len[b], L = bad ? 0 : (int)tgt_len[b];
+  const CtcLens len(in_len, tgt_len, b, T, Lmax);
+  const bool bad = len.bad();
+  const int Tb = bad ? 0 : len.Tb, L = bad ? 0 : len.L;
   int32_t *prow = paths + (size_t)b * T;
   float *frow = frame_scores + (size_t)b * T;
   int32_t *srow = starts ? starts + (size_t)b * Lmax : nullptr, *erow = ends ? ends + (size_t)b * Lmax : nullptr;
@@ -855,85 +689,13 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(const float *__r
     else if (tid == 0) { score[b] = 0.0f; ok[b] = 1; }
     return;
   }
-  const int S = 2 * L + 1;
-  float *buf0 = smem, *buf1 = smem + Smax;
-  int *ext = reinterpret_cast<int *>(smem + 2 * Smax);
+  const int S = len.S;
+  int *ext = reinterpret_cast<int *>(smem + 2 * Smax);              // behind the walk's two value rows: ctc_classic_walk fills it
   int *st = ext + Smax;                                             // st[1 + i]: state at frame t0 + i of the chunk; st[0], st[n + 1]: its neighbours in time
   uint32_t *bpl = reinterpret_cast<uint32_t *>(st + ALIGN_CH + 2);  // BPLDS: row of frame t at bpl + t * W; else the rows of the current chunk
   uint32_t *bpg = BPLDS ? nullptr : ws + (size_t)b * T * W;         // row of frame t at bpg + t * W
-  for (int s = tid; s < S; s += CTC_THREADS) ext[s] = (s & 1) ? (int)targets[(size_t)b * Lmax + (s >> 1)] : blank;
-  __syncthreads();
-  int my_ext[NS];
-  bool my_skip[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const int s = tid + k * CTC_THREADS;
-    my_ext[k] = 0; my_skip[k] = false;
-    if (s < S) {
-      my_ext[k] = ext[s];
-      my_skip[k] = s >= 2 && (s & 1) && ext[s] != ext[s - 2];
-    }
-  }
-  {
-    const float *lpt = lp + (size_t)b * V;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-      const int s = tid + k * CTC_THREADS;
-      if (s < S) buf0[s] = s <= 1 ? lpt[my_ext[k]] : -INFINITY;
-    }
-  }
-  __syncthreads();
-  float *prev = buf0, *cur = buf1;
-  float nq[PF][NS];
-#pragma unroll
-  for (int i = 0; i < PF; ++i) {
-    const float *lpt = lp + ((size_t)min(1 + i, Tb - 1) * B + b) * V;
-#pragma unroll
-    for (int k = 0; k < NS; ++k) nq[i][k] = tid + k * CTC_THREADS < S ? lpt[my_ext[k]] : 0.0f;
-  }
-  const int wsh = lane & 48;                        // this lane's group of 16 inside the two ballots
-  for (int n0 = 1; n0 < Tb; n0 += PF) {
-    float cq[PF][NS];
-#pragma unroll
-    for (int i = 0; i < PF; ++i)
-#pragma unroll
-      for (int k = 0; k < NS; ++k) cq[i][k] = nq[i][k];
-    if (n0 + PF < Tb) {
-#pragma unroll
-      for (int i = 0; i < PF; ++i) {
-        const float *lpt = lp + ((size_t)min(n0 + PF + i, Tb - 1) * B + b) * V;
-#pragma unroll
-        for (int k = 0; k < NS; ++k) nq[i][k] = tid + k * CTC_THREADS < S ? lpt[my_ext[k]] : 0.0f;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < PF; ++i) {
-      const int t = n0 + i;
-      if (t < Tb) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k) {
-          const int s = tid + k * CTC_THREADS;
-          int code = 0;
-          if (s < S) {
-            float best = prev[s];
-            const float x1 = s >= 1 ? prev[s - 1] : -INFINITY;
-            const float x2 = my_skip[k] ? prev[s - 2] : -INFINITY;
-            if (x1 > best) { best = x1; code = 1; }
-            if (x2 > best) { best = x2; code = 2; }
-            cur[s] = __fadd_rn(best, cq[i][k]);
-          }
-          const unsigned long long m0 = __ballot(code & 1), m1 = __ballot(code & 2);
-          if ((lane & 15) == 0 && s < S) {
-            const uint32_t w = (uint32_t)((m0 >> wsh) & 0xffffull) | ((uint32_t)((m1 >> wsh) & 0xffffull) << 16);
-            if (BPLDS) bpl[(size_t)t * W + (s >> 4)] = w;
-            else bpg[(size_t)t * W + (s >> 4)] = w;
-          }
-        }
-        lds_barrier();       // LDS only: the row stores of the workspace branch and the prefetches stay in flight
-        float *tmp = prev; prev = cur; cur = tmp;
-      }
-    }
-  }
+  const CtcMaxPolicy pol{BPLDS ? bpl : bpg, W, tid & 63};
+  const float *prev = ctc_classic_walk<1, NS>(smem, lp, targets, Tb, S, B, V, Lmax, blank, pol);
   __syncthreads();           // the last value row, every back-pointer row (LDS or workspace) and the fills are done
   const float l1 = prev[S - 1], l2 = S > 1 ? prev[S - 2] : -INFINITY;
   const bool second = S > 1 && l2 > l1;
@@ -995,53 +757,13 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_align_kernel(const float *__r
 
 }  // namespace
 
-extern "C" int ctcn_edit_distance(const int32_t *a, const int32_t *a_len, const int64_t *b, const int64_t *b_len, int32_t *out,
-                                  int B, int lda, int ldb, int max_b_len, void *stream) {
-  CTCN_REQUIRE(a && a_len && b_len && out && (b || ldb == 0) && B > 0 && max_b_len >= 0, "ctcn_edit_distance: bad args");
-  if (max_b_len <= 512 && (size_t)lda * sizeof(int) <= 60 * 1024 && ctcn_get_option("edit_wave") != 0) {
-    const size_t sm = (size_t)std::max(lda, 1) * sizeof(int);
-    hipStream_t st = (hipStream_t)stream;
-    if (max_b_len <= 64) hipLaunchKernelGGL(edit_distance_wave_kernel<1>, dim3(B), dim3(64), sm, st, a, a_len, b, b_len, out, lda, ldb, max_b_len);
-    else if (max_b_len <= 128) hipLaunchKernelGGL(edit_distance_wave_kernel<2>, dim3(B), dim3(64), sm, st, a, a_len, b, b_len, out, lda, ldb, max_b_len);
-    else if (max_b_len <= 256) hipLaunchKernelGGL(edit_distance_wave_kernel<4>, dim3(B), dim3(64), sm, st, a, a_len, b, b_len, out, lda, ldb, max_b_len);
-    else hipLaunchKernelGGL(edit_distance_wave_kernel<8>, dim3(B), dim3(64), sm, st, a, a_len, b, b_len, out, lda, ldb, max_b_len);
-    CTCN_LAUNCH_CHECK();
-    return CTCN_OK;
-  }
-  const int ldrow = max_b_len + 2;
-  int threads = 64;
-  while (threads > 1 && (size_t)threads * ldrow * sizeof(int) > 48 * 1024) threads >>= 1;
-  if ((size_t)threads * ldrow * sizeof(int) > 48 * 1024) { ctcn_set_error("ctcn_edit_distance: label length %d too long", max_b_len); return CTCN_EUNSUPPORTED; }
-  hipLaunchKernelGGL(edit_distance_kernel, dim3(ceil_div(B, threads)), dim3(threads), (size_t)threads * ldrow * sizeof(int),
-                     (hipStream_t)stream, a, a_len, b, b_len, out, B, lda, ldb, ldrow);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-extern "C" int ctcn_log_softmax_fwd(const float *logits, float *lp, int32_t *argmax, int rows, int V, void *stream) {
-  CTCN_REQUIRE(logits && lp && rows > 0 && V > 0, "ctcn_log_softmax_fwd: bad args");
-  hipLaunchKernelGGL((log_softmax_kernel<true>), dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, lp, argmax, rows, V);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-extern "C" int ctcn_argmax(const float *lp, int32_t *argmax, int rows, int V, void *stream) {
-  CTCN_REQUIRE(lp && argmax && rows > 0 && V > 0, "ctcn_argmax: bad args");
-  hipLaunchKernelGGL((log_softmax_kernel<false>), dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, lp, (float *)nullptr, argmax, rows, V);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-extern "C" int ctcn_log_softmax_bwd(const float *lp, const float *dlp, float *dlogits, int rows, int V, void *stream) {
-  CTCN_REQUIRE(lp && dlp && dlogits && rows > 0 && V > 0, "ctcn_log_softmax_bwd: bad args");
-  hipLaunchKernelGGL(log_softmax_bwd_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, lp, dlp, dlogits, rows, V);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
+// ---- Plans: what a call launches, by arithmetic on its shapes and the options alone; the launches below only carry a plan out ----
 
 // The lattice passes of every CTC entry point: alpha alone (ctcn_ctc_fwd, ctcn_ctc_fwd_ex without beta), the beta pass added into alpha
 // in place (ctcn_ctc_bwd's one-buffer reserve), or alpha and beta side by side in one launch (ctcn_ctc_fwd_both, ctcn_ctc_fwd_ex).
 enum CtcPasses { CTC_ALPHA, CTC_BETA_INTO_ALPHA, CTC_ALPHA_BETA };
 
-// The launch of a lattice pass, by arithmetic alone (ctcn_diag_ctc_lattice_plan shows it to the CPU tests).  Skewed (ctc_lattices_skew_kernel: a
+// The launch of a lattice pass (ctcn_diag_ctc_lattice_plan shows it to the CPU tests).  Skewed (ctc_lattices_skew_kernel: a
 // state per lane on `waves` waves of 64, the ring and the two final states in LDS) where the lattice fits CTC_SKEW_WAVES waves and option
 // "ctc_lattice_skew" is on; otherwise the classic kernels: CTC_THREADS threads, ns states per thread, three lattice rows of LDS.
 struct CtcLatticeOptions { int skew; };
@@ -1064,39 +786,67 @@ CtcLatticePlan plan_ctc_lattice(int Lmax, const CtcLatticeOptions &o) {
   return p;
 }
 
-extern "C" int ctcn_diag_ctc_lattice_plan(int Lmax, int *out) {
-  CTCN_REQUIRE(out && Lmax >= 0 && 2 * (int64_t)Lmax + 1 <= CTC_THREADS * CTC_NS, "ctcn_diag_ctc_lattice_plan: bad args");
-  const CtcLatticePlan p = plan_ctc_lattice(Lmax, CtcLatticeOptions{ctcn_get_option("ctc_lattice_skew")});
-  out[0] = p.skewed; out[1] = p.waves; out[2] = p.ns; out[3] = p.threads; out[4] = (int)p.lds; out[5] = CTC_SKEW * CTC_CHUNK;
-  return CTCN_OK;
+// The launch of ctcn_ctc_align: the classic walk's ns, and where the back-pointer rows (ceil(Smax / 16) words per frame) live -- in LDS behind
+// the walk's three rows and the trace chunk's states where all T of them fit ALIGN_LDS_LIMIT, else in the caller's workspace of ws_bytes with
+// ALIGN_GWORDS words of LDS to bring them back through.  The same (T, Lmax) always takes the same branch.
+struct CtcAlignPlan { bool rows_in_lds; int ns; size_t lds, ws_bytes; };
+static CtcAlignPlan plan_ctc_align(int T, int B, int Lmax) {
+  const int S = 2 * Lmax + 1;
+  const size_t fixed = (size_t)(3 * S + ALIGN_CH + 2) * sizeof(float), rows = (size_t)T * ceil_div(S, 16) * sizeof(uint32_t);
+  CtcAlignPlan p;
+  p.rows_in_lds = fixed + rows <= ALIGN_LDS_LIMIT;
+  p.ns = plan_ctc_lattice(Lmax, CtcLatticeOptions{0}).ns;
+  p.lds = fixed + (p.rows_in_lds ? rows : (size_t)ALIGN_GWORDS * sizeof(uint32_t));
+  p.ws_bytes = p.rows_in_lds ? 0 : (size_t)B * rows;
+  return p;
+}
+
+// f(std::integral_constant<int, NS>{}) for a plan's ns: the instantiations of the classic walk (1, 2, 4, 8 or CTC_NS states per thread)
+template <class F>
+static void with_ctc_ns(int ns, F &&f) {
+  switch (ns) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: f(std::integral_constant<int, CTC_NS>{}); break;
+  }
+}
+
+static bool ctc_label_too_long(const char *who, int Lmax) {
+  if (2 * Lmax + 1 <= CTC_THREADS * CTC_NS) return false;
+  ctcn_set_error("%s: label length %d > %d unsupported", who, Lmax, (CTC_THREADS * CTC_NS - 1) / 2);
+  return true;
 }
 
 static int ctc_lattices(const char *who, CtcPasses passes, const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len,
                         float *alpha, float *beta, float *nll, int T, int B, int V, int Lmax, int blank, hipStream_t st) {
-  if (2 * Lmax + 1 > CTC_THREADS * CTC_NS) { ctcn_set_error("%s: label length %d > %d unsupported", who, Lmax, (CTC_THREADS * CTC_NS - 1) / 2); return CTCN_EUNSUPPORTED; }
+  if (ctc_label_too_long(who, Lmax)) return CTCN_EUNSUPPORTED;
   CtcLatticeOptions opt{ctcn_get_option("ctc_lattice_skew")};
   if (passes == CTC_BETA_INTO_ALPHA) opt.skew = 0;          // the in-place beta pass has no skewed body
   const CtcLatticePlan plan = plan_ctc_lattice(Lmax, opt);
-  const size_t sm = plan.lds;
-  const int ns = plan.ns;
-  if (plan.skewed) {
+  const dim3 grid(B, passes == CTC_ALPHA_BETA ? 2 : 1), block(plan.threads);
+  if (plan.skewed) {                                        // CTC_ALPHA or CTC_ALPHA_BETA, by the grid
     const int slow = ctcn_get_option("ctc_slow_wave");
-    const dim3 grid(B, passes == CTC_ALPHA_BETA ? 2 : 1);
-#define CTC_LAUNCH(SLOW) hipLaunchKernelGGL((ctc_lattices_skew_kernel<SLOW>), grid, dim3(plan.threads), sm, st, lp, targets, in_len, tgt_len, alpha, beta, nll, T, B, V, Lmax, blank, slow)
-    if (slow) CTC_LAUNCH(true); else CTC_LAUNCH(false);
-#undef CTC_LAUNCH
-  } else if (passes == CTC_ALPHA) {
-#define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattice_kernel<1, NS>), dim3(B), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank)
-    if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
-#undef CTC_LAUNCH
-  } else if (passes == CTC_BETA_INTO_ALPHA) {
-#define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattice_kernel<-1, NS>), dim3(B), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, alpha, (float *)nullptr, T, B, V, Lmax, blank)
-    if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
-#undef CTC_LAUNCH
+    hipLaunchKernelGGL(slow ? ctc_lattices_skew_kernel<true> : ctc_lattices_skew_kernel<false>, grid, block, plan.lds, st, lp, targets, in_len,
+                       tgt_len, alpha, beta, nll, T, B, V, Lmax, blank, slow);
   } else {
-#define CTC_LAUNCH(NS) hipLaunchKernelGGL((ctc_lattices_kernel<NS>), dim3(B, 2), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, alpha, beta, nll, T, B, V, Lmax, blank)
-    if (ns <= 1) CTC_LAUNCH(1); else if (ns <= 2) CTC_LAUNCH(2); else if (ns <= 4) CTC_LAUNCH(4); else if (ns <= 8) CTC_LAUNCH(8); else CTC_LAUNCH(16);
-#undef CTC_LAUNCH
+    with_ctc_ns(plan.ns, [&](auto ns) {
+      constexpr int NS = decltype(ns)::value;
+      switch (passes) {
+        case CTC_ALPHA:
+          hipLaunchKernelGGL((ctc_lattice_kernel<1, NS>), grid, block, plan.lds, st, lp, targets, in_len, tgt_len, alpha, nll, T, B, V, Lmax, blank);
+          break;
+        case CTC_BETA_INTO_ALPHA:
+          hipLaunchKernelGGL((ctc_lattice_kernel<-1, NS>), grid, block, plan.lds, st, lp, targets, in_len, tgt_len, alpha, (float *)nullptr, T, B, V,
+                             Lmax, blank);
+          break;
+        case CTC_ALPHA_BETA:
+          hipLaunchKernelGGL((ctc_lattices_kernel<NS>), grid, block, plan.lds, st, lp, targets, in_len, tgt_len, alpha, beta, nll, T, B, V, Lmax,
+                             blank);
+          break;
+      }
+    });
   }
   CTCN_LAUNCH_CHECK();
   return CTCN_OK;
@@ -1108,13 +858,44 @@ static int ctc_grad(const float *lp, const int64_t *targets, const int64_t *in_l
                     float *grad_lp, int T, int B, int V, int Lmax, hipStream_t st) {
   const size_t sm = (size_t)(V + 1 + Lmax) * sizeof(int);
   const int mean = reduction == CTCN_REDUCTION_MEAN, zinf = zero_infinity != 0;
-  if (beta == nullptr)
-    hipLaunchKernelGGL(ctc_grad_kernel<false>, dim3(ceil_div(T, GRAD_TCH), B), dim3(256), sm, st, lp, targets, in_len, tgt_len, alpha,
-                       (const float *)nullptr, nll, gscale, gs_stride, mean, zinf, blank, grad_lp, T, B, V, Lmax);
-  else
-    hipLaunchKernelGGL(ctc_grad_kernel<true>, dim3(ceil_div(T, GRAD_TCH), B), dim3(256), sm, st, lp, targets, in_len, tgt_len, alpha, beta,
-                       nll, gscale, gs_stride, mean, zinf, blank, grad_lp, T, B, V, Lmax);
+  hipLaunchKernelGGL(beta ? ctc_grad_kernel<true> : ctc_grad_kernel<false>, dim3(ceil_div(T, GRAD_TCH), B), dim3(256), sm, st, lp, targets, in_len,
+                     tgt_len, alpha, beta, nll, gscale, gs_stride, mean, zinf, blank, grad_lp, T, B, V, Lmax);
   CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+// ---- The entry points (contracts in include/ctcn.h) ----
+
+extern "C" int ctcn_log_softmax_fwd(const float *logits, float *lp, int32_t *argmax, int rows, int V, void *stream) {
+  CTCN_REQUIRE(logits && lp && rows > 0 && V > 0, "ctcn_log_softmax_fwd: bad args");
+  hipLaunchKernelGGL((log_softmax_kernel<true>), dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, lp, argmax, rows, V);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+extern "C" int ctcn_argmax(const float *lp, int32_t *argmax, int rows, int V, void *stream) {
+  CTCN_REQUIRE(lp && argmax && rows > 0 && V > 0, "ctcn_argmax: bad args");
+  hipLaunchKernelGGL((log_softmax_kernel<false>), dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, lp, (float *)nullptr, argmax, rows, V);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+extern "C" int ctcn_log_softmax_bwd(const float *lp, const float *dlp, float *dlogits, int rows, int V, void *stream) {
+  CTCN_REQUIRE(lp && dlp && dlogits && rows > 0 && V > 0, "ctcn_log_softmax_bwd: bad args");
+  hipLaunchKernelGGL(log_softmax_bwd_kernel, dim3(ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, lp, dlp, dlogits, rows, V);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_ctc_pack_targets(const int64_t *flat, int64_t n_flat, const int64_t *tgt_len, int64_t *padded, int B, int Lmax, void *stream) {
+  CTCN_REQUIRE(tgt_len && padded && (flat || n_flat == 0) && n_flat >= 0 && B > 0 && Lmax > 0, "ctcn_ctc_pack_targets: bad args");
+  hipLaunchKernelGGL(ctc_pack_targets_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, flat, n_flat, tgt_len, padded, Lmax);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
+extern "C" int ctcn_diag_ctc_lattice_plan(int Lmax, int *out) {
+  CTCN_REQUIRE(out && Lmax >= 0 && 2 * (int64_t)Lmax + 1 <= CTC_THREADS * CTC_NS, "ctcn_diag_ctc_lattice_plan: bad args");
+  const CtcLatticePlan p = plan_ctc_lattice(Lmax, CtcLatticeOptions{ctcn_get_option("ctc_lattice_skew")});
+  out[0] = p.skewed; out[1] = p.waves; out[2] = p.ns; out[3] = p.threads; out[4] = (int)p.lds; out[5] = CTC_SKEW * CTC_CHUNK;
   return CTCN_OK;
 }
 
@@ -1173,8 +954,8 @@ extern "C" int ctcn_ctc_grad_ex(const float *lp, const int64_t *targets, const i
 }
 
 extern "C" size_t ctcn_ctc_align_ws_bytes(int T, int B, int Lmax) {
-  if (T <= 0 || B <= 0 || Lmax < 0 || align_rows_in_lds(T, Lmax)) return 0;
-  return (size_t)B * (size_t)T * align_row_words(Lmax) * sizeof(uint32_t);
+  if (T <= 0 || B <= 0 || Lmax < 0) return 0;
+  return plan_ctc_align(T, B, Lmax).ws_bytes;
 }
 
 extern "C" int ctcn_ctc_align(const float *lp, const int64_t *targets, const int64_t *in_len, const int64_t *tgt_len, int32_t *paths,
@@ -1183,73 +964,19 @@ extern "C" int ctcn_ctc_align(const float *lp, const int64_t *targets, const int
   CTCN_REQUIRE(lp && in_len && tgt_len && paths && frame_scores && score && ok && (targets || Lmax == 0), "ctcn_ctc_align: null pointer");
   CTCN_REQUIRE(T > 0 && B > 0 && V > 0 && Lmax >= 0, "ctcn_ctc_align: bad dims");
   CTCN_REQUIRE(blank >= 0 && blank < V, "ctcn_ctc_align: blank %d outside [0, %d)", blank, V);
-  if (2 * Lmax + 1 > CTC_THREADS * CTC_NS) { ctcn_set_error("ctcn_ctc_align: label length %d > %d unsupported", Lmax, (CTC_THREADS * CTC_NS - 1) / 2); return CTCN_EUNSUPPORTED; }
-  const bool in_lds = align_rows_in_lds(T, Lmax);
-  const size_t need = ctcn_ctc_align_ws_bytes(T, B, Lmax);
-  if (!in_lds) {
+  if (ctc_label_too_long("ctcn_ctc_align", Lmax)) return CTCN_EUNSUPPORTED;
+  const CtcAlignPlan plan = plan_ctc_align(T, B, Lmax);
+  if (!plan.rows_in_lds) {
     CTCN_REQUIRE(ws && ((uintptr_t)ws & 3) == 0, "ctcn_ctc_align: workspace of ctcn_ctc_align_ws_bytes needed (T %d, Lmax %d), 4-byte aligned", T, Lmax);
-    if (ws_bytes < need) { ctcn_set_error("ctcn_ctc_align: workspace %zu < %zu bytes", ws_bytes, need); return CTCN_EWORKSPACE; }
+    if (ws_bytes < plan.ws_bytes) { ctcn_set_error("ctcn_ctc_align: workspace %zu < %zu bytes", ws_bytes, plan.ws_bytes); return CTCN_EWORKSPACE; }
   }
-  const size_t sm = align_lds_fixed(Lmax) + (in_lds ? (size_t)T * align_row_words(Lmax) : (size_t)ALIGN_GWORDS) * sizeof(uint32_t);
-  const int ns = ceil_div(2 * Lmax + 1, CTC_THREADS);
-  hipStream_t st = (hipStream_t)stream;
-#define CTC_LAUNCH(NS, LDS) hipLaunchKernelGGL((ctc_align_kernel<NS, LDS>), dim3(B), dim3(CTC_THREADS), sm, st, lp, targets, in_len, tgt_len, paths, frame_scores, score, ok, starts, ends, (uint32_t *)ws, T, B, V, Lmax, blank)
-  if (in_lds) {
-    if (ns <= 1) CTC_LAUNCH(1, true); else if (ns <= 2) CTC_LAUNCH(2, true); else if (ns <= 4) CTC_LAUNCH(4, true); else if (ns <= 8) CTC_LAUNCH(8, true); else CTC_LAUNCH(16, true);
-  } else {
-    if (ns <= 1) CTC_LAUNCH(1, false); else if (ns <= 2) CTC_LAUNCH(2, false); else if (ns <= 4) CTC_LAUNCH(4, false); else if (ns <= 8) CTC_LAUNCH(8, false); else CTC_LAUNCH(16, false);
-  }
-#undef CTC_LAUNCH
+  with_ctc_ns(plan.ns, [&](auto ns) {
+    constexpr int NS = decltype(ns)::value;
+    hipLaunchKernelGGL((plan.rows_in_lds ? ctc_align_kernel<NS, true> : ctc_align_kernel<NS, false>), dim3(B), dim3(CTC_THREADS), plan.lds,
+                       (hipStream_t)stream, lp, targets, in_len, tgt_len, paths, frame_scores, score, ok, starts, ends, (uint32_t *)ws, T, B, V, Lmax,
+                       blank);
+  });
   CTCN_LAUNCH_CHECK();
   return CTCN_OK;
 }
 
-extern "C" int ctcn_ctc_pack_targets(const int64_t *flat, int64_t n_flat, const int64_t *tgt_len, int64_t *padded, int B, int Lmax, void *stream) {
-  CTCN_REQUIRE(tgt_len && padded && (flat || n_flat == 0) && n_flat >= 0 && B > 0 && Lmax > 0, "ctcn_ctc_pack_targets: bad args");
-  hipLaunchKernelGGL(ctc_pack_targets_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, flat, n_flat, tgt_len, padded, Lmax);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-// (loss, sum of the edit distances, sum of the label lengths, status word) of a training step as four doubles: what
-// steps/train_ctc.run_epoch copies to the host one step behind -- one launch instead of nine small torch kernels
-__global__ void step_stats_kernel(const float *__restrict__ loss, const int32_t *__restrict__ dist, const int64_t *__restrict__ tgt_len, int B,
-                                  const int32_t *__restrict__ status, double *__restrict__ out) {
-  const int lane = threadIdx.x;
-  long long d = 0, n = 0;
-  for (int b = lane; b < B; b += 64) { d += dist[b]; n += tgt_len[b]; }
-  for (int o = 32; o > 0; o >>= 1) { d += __shfl_down(d, o, 64); n += __shfl_down(n, o, 64); }
-  if (lane == 0) {
-    out[0] = (double)loss[0];
-    out[1] = (double)d;
-    out[2] = (double)n;
-    out[3] = status ? (double)status[0] : 0.0;
-  }
-}
-extern "C" int ctcn_step_stats(const float *loss, const int32_t *dist, const int64_t *tgt_len, int B, const int32_t *status, double *out4,
-                               void *stream) {
-  CTCN_REQUIRE(loss && dist && tgt_len && out4 && B > 0, "ctcn_step_stats: bad args");
-  hipLaunchKernelGGL(step_stats_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss, dist, tgt_len, B, status, out4);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-extern "C" int ctcn_greedy_collapse(const int32_t *idx, size_t stride_t, size_t stride_b, const int32_t *lens, int32_t *out_ids,
-                                    int32_t *out_len, int T, int B, int blank, void *stream) {
-  CTCN_REQUIRE(idx && lens && out_ids && out_len && T > 0 && B > 0, "ctcn_greedy_collapse: bad args");
-  hipLaunchKernelGGL(greedy_collapse_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, (hipStream_t)stream, idx, stride_t, stride_b, lens, out_ids, out_len, T, B, blank);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}
-
-extern "C" int ctcn_path_tokens(const int32_t *path, size_t stride_t, size_t stride_b, const float *lp, const int32_t *lens, int32_t *out_ids,
-                                int32_t *out_len, int32_t *starts, int32_t *ends, float *tok_mean, float *tok_min, float *tok_margin,
-                                float *path_score, int T, int B, int V, int blank, void *stream) {
-  CTCN_REQUIRE(path && lp && lens && out_ids && out_len && starts && ends && tok_mean && tok_min && tok_margin && path_score, "ctcn_path_tokens: null pointer");
-  CTCN_REQUIRE(T > 0 && B > 0 && V > 0, "ctcn_path_tokens: bad dims");
-  CTCN_REQUIRE(blank >= 0 && blank < V, "ctcn_path_tokens: blank %d outside [0, %d)", blank, V);
-  hipLaunchKernelGGL(path_tokens_kernel, dim3(B), dim3(PT_THREADS), 0, (hipStream_t)stream, path, stride_t, stride_b, lp, lens, out_ids, out_len, starts,
-                     ends, tok_mean, tok_min, tok_margin, path_score, T, B, V, blank);
-  CTCN_LAUNCH_CHECK();
-  return CTCN_OK;
-}

@@ -1,8 +1,8 @@
 // editops.hip -- the error breakdown behind the error rate: substitutions / deletions / insertions / correct pairs, the alignment itself
-// and the confusion table (ctcn_edit_ops; contract in include/ctcn.h).  ctcn_edit_distance (ctc.hip) keeps a rolling row and answers the
+// and the confusion table (ctcn_edit_ops; contract in include/ctcn.h).  ctcn_edit_distance (paths.hip) keeps a rolling row and answers the
 // distance alone; this kernel keeps the 2-bit move of every cell and walks the chain back.
 //
-// One wavefront per utterance, the anti-diagonal scheme of edit_distance_wave_kernel: lane L owns the NC reference columns
+// One wavefront per utterance, the anti-diagonal scheme of edit_distance_wave_kernel (paths.hip): lane L owns the NC reference columns
 // L*NC+1 .. (L+1)*NC and at step d fills row i = d - L of them.  Three stages:
 //   1. both sequences pass through the class map and are compacted (ballot + popcount, order preserving): the hypothesis into `hyp`, the
 //      reference into LDS, from where every lane takes its NC columns into registers;
