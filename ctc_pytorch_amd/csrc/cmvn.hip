@@ -1,7 +1,10 @@
-// cmvn.hip -- mean / variance normalisation per group of utterances and over a sliding window (ctcn_cmvn_apply, ctcn_cmvn_sliding and the
-// host twins ctcn_cmvn_norm_host, ctcn_cmvn_sliding_window, ctcn_cmvn_sliding_host; contract in include/ctcn.h, the arithmetic in
-// cmvn_core.h).  The statistics themselves come from fbank.hip (ctcn_cmvn_accumulate, ctcn_cmvn_accumulate_groups).
+// cmvn.hip -- mean / variance normalisation: the statistics of all utterances or per group of them (ctcn_cmvn_accumulate,
+// ctcn_cmvn_accumulate_groups), their application per group and the sliding window (ctcn_cmvn_apply, ctcn_cmvn_sliding and the host twins
+// ctcn_cmvn_norm_host, ctcn_cmvn_sliding_window, ctcn_cmvn_sliding_host; contract in include/ctcn.h, the arithmetic in cmvn_core.h).
 //
+// cmvn_partial_kernel / cmvn_finish_kernel: float64 column sums of 64-row blocks into the workspace, then one thread per statistic and group
+//   adds the group's partials in index order into the caller's block (norm.hip's scheme: no atomics, a function of the input bits).  Without
+//   group ids every utterance is in group 0: the global statistics are the grouped ones at G = 1, by the same kernel.
 // cmvn_apply_kernel: grid (blocks of 64 rows, utterances), 256 threads laid out as (256 / CW rows, CW columns), CW in {64, 128, 256} chosen
 //   from F so that few lanes idle.  A thread forms mean and scale of its column from the group's statistics in double (a division, a square
 //   root and a reciprocal: ~150 instructions, against 64 / (256 / CW) elements of 3 each), then walks the block's rows of that column:
@@ -23,9 +26,56 @@
 
 namespace {
 
+constexpr int CMVN_ROWS = 64;                      // rows of a block of cmvn_partial_kernel
 constexpr int CMVN_APPLY_ROWS = 64;
 constexpr int CMVN_RUN = 16;                       // frames staged at a time by cmvn_sliding_kernel (ctcn_cmvn_sliding_run)
 constexpr int CMVN_MAX_FRAMES = 1 << 30;
+
+// Partial sums of rows [c * 64, c * 64 + 64) below frames[b] of utterance b: ws[(b * chunks + c)][2][F] doubles (zeros for an empty block).
+__global__ __launch_bounds__(256) void cmvn_partial_kernel(const float *__restrict__ feats, const int32_t *__restrict__ frames, double *__restrict__ ws,
+                                                           int Tmax, int F) {
+  const int b = blockIdx.y, c = blockIdx.x, chunks = gridDim.x;
+  const int Tb = min(max(frames[b], 0), Tmax);
+  const int t0 = c * CMVN_ROWS, t1 = min(t0 + CMVN_ROWS, Tb);
+  double *o = ws + ((size_t)b * chunks + c) * 2 * F;
+  const float *x = feats + (size_t)b * Tmax * F;
+  for (int f = threadIdx.x; f < F; f += 256) {
+    double s = 0.0, q = 0.0;
+    for (int t = t0; t < t1; ++t) {
+      const double v = (double)x[(size_t)t * F + f];
+      s += v;
+      q += v * v;
+    }
+    o[f] = s;
+    o[F + f] = q;
+  }
+}
+
+// Grid (statistics / 256, groups).  Thread i < 2F of group g adds its column of the partials of the utterances of group g (group[b] == g;
+// GROUPED == false: no ids, every utterance is in group 0), in ascending (utterance, block) order, into stats[g]; thread 2F their frame
+// counts in ascending utterance order.  (A template parameter, not a test of `group`: the walk over the utterances is one wave's dependent chain.)
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void cmvn_finish_kernel(const double *__restrict__ ws, const int32_t *__restrict__ frames,
+                                                          const int32_t *__restrict__ group, double *__restrict__ stats, int B, int Tmax, int F,
+                                                          int chunks) {
+  const int i = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
+  double *st = stats + (size_t)g * 2 * (F + 1);
+  if (i < 2 * F) {
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) {
+      if ((GROUPED ? group[b] : 0) != g) continue;
+      const double *p = ws + (size_t)b * chunks * 2 * F + i;
+#pragma unroll 8
+      for (int c = 0; c < chunks; ++c) s += p[(size_t)c * 2 * F];   // the loads do not wait for the sum: eight in flight, added in order
+    }
+    st[i < F ? i : i + 1] += s;                                       // row 1 starts at F + 1
+  } else if (i == 2 * F) {
+    double cnt = 0.0;
+    for (int b = 0; b < B; ++b)
+      if ((GROUPED ? group[b] : 0) == g) cnt += (double)min(max(frames[b], 0), Tmax);
+    st[F] += cnt;
+  }
+}
 
 __global__ __launch_bounds__(256) void cmvn_apply_kernel(const float *feats, const int32_t *__restrict__ frames, const int32_t *__restrict__ group,
                                                          const double *__restrict__ stats, float *out, int Tmax, int F, int G, int norm_vars,
@@ -138,7 +188,41 @@ int sliding_opts_ok(const ctcn_sliding_cmn_opts *opts, const char **why) {
   return CTCN_OK;
 }
 
+size_t accumulate_ws_bytes(int B, int Tmax, int F) { return (size_t)B * ceil_div(Tmax, CMVN_ROWS) * 2 * F * sizeof(double); }
+
+// Both accumulate entry points behind their own argument checks: alignment and workspace under the caller's name, the partial sums, the
+// finish per group.  group == nullptr (ctcn_cmvn_accumulate): no ids, one group (G = 1) holding every utterance.
+int cmvn_accumulate(const char *who, const float *feats, const int32_t *frames, const int32_t *group, double *stats, int B, int Tmax, int F, int G,
+                    void *ws, size_t ws_bytes, void *stream) {
+  const size_t need = accumulate_ws_bytes(B, Tmax, F);
+  CTCN_REQUIRE(ws && ((uintptr_t)ws & 7) == 0 && ((uintptr_t)stats & 7) == 0, "%s: workspace of ctcn_cmvn_accumulate_ws_bytes needed, 8-byte aligned", who);
+  if (ws_bytes < need) { ctcn_set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, need); return CTCN_EWORKSPACE; }
+  const int chunks = ceil_div(Tmax, CMVN_ROWS);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(cmvn_partial_kernel, dim3(chunks, B), dim3(256), 0, st, feats, frames, static_cast<double *>(ws), Tmax, F);
+  CTCN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(group ? cmvn_finish_kernel<true> : cmvn_finish_kernel<false>, dim3(ceil_div(2 * F + 1, 256), G), dim3(256), 0, st,
+                     static_cast<const double *>(ws), frames, group, stats, B, Tmax, F, chunks);
+  CTCN_LAUNCH_CHECK();
+  return CTCN_OK;
+}
+
 }  // namespace
+
+extern "C" size_t ctcn_cmvn_accumulate_ws_bytes(int B, int Tmax, int F) { return B <= 0 || Tmax <= 0 || F <= 0 ? 0 : accumulate_ws_bytes(B, Tmax, F); }
+
+extern "C" int ctcn_cmvn_accumulate(const float *feats, const int32_t *frames, double *stats, int B, int Tmax, int F, void *ws, size_t ws_bytes,
+                                    void *stream) {
+  CTCN_REQUIRE(feats && frames && stats && B > 0 && Tmax > 0 && F > 0 && B <= 65535, "ctcn_cmvn_accumulate: bad args");
+  return cmvn_accumulate("ctcn_cmvn_accumulate", feats, frames, nullptr, stats, B, Tmax, F, 1, ws, ws_bytes, stream);
+}
+
+extern "C" int ctcn_cmvn_accumulate_groups(const float *feats, const int32_t *frames, const int32_t *group, double *stats, int B, int Tmax, int F,
+                                           int G, void *ws, size_t ws_bytes, void *stream) {
+  CTCN_REQUIRE(feats && frames && group && stats && B > 0 && Tmax > 0 && F > 0 && B <= 65535 && G > 0 && G <= 65535,
+               "ctcn_cmvn_accumulate_groups: bad args (B %d and G %d at most 65 535)", B, G);
+  return cmvn_accumulate("ctcn_cmvn_accumulate_groups", feats, frames, group, stats, B, Tmax, F, G, ws, ws_bytes, stream);
+}
 
 extern "C" int ctcn_cmvn_apply(const float *feats, const int32_t *frames, const int32_t *group, const double *stats, float *out, int B, int Tmax,
                                int F, int G, int norm_vars, void *stream) {

@@ -83,6 +83,12 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// Sample i of a waveform batch of float32 or int16 samples (the front-end's wave / wave_is_int16 pair): int16 is converted where it is read.
+// Host callable: the host twins read their input the same way.
+__host__ __device__ __forceinline__ float wave_sample(const void *wave, int is_i16, size_t i) {
+  return is_i16 ? (float)static_cast<const int16_t *>(wave)[i] : static_cast<const float *>(wave)[i];
+}
+
 // Philox4x32-10 (Salmon et al., SC'11): counter = element-group index, key = seed.  (Host callable too: specaug.hip's host twin draws from it.)
 __host__ __device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t (&k)[2]) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;

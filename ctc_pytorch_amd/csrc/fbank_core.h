@@ -1,6 +1,6 @@
 // fbank_core.h -- the parts of the filterbank front-end (fbank.hip) that are plain arithmetic on the options or on one frame: the geometry of a
-// configuration, the host-side plan builder (filterbank, and the MFCC's DCT table and lifter behind it) and the FFT butterflies.  Everything here
-// compiles for the host too, so the plan builders and the
+// configuration, the host-side plan builder (filterbank, and the MFCC's DCT table and lifter behind it), the layout of a workgroup's LDS (what
+// the kernels read through and their launches size) and the FFT butterflies.  Everything here compiles for the host too, so the plan builders and the
 // FFT passes can be exercised by a stand-alone host program (one loop over the 64 "lanes" per pass stands in for the wave).
 #pragma once
 #include <float.h>
@@ -271,6 +271,35 @@ inline void logspec_build_plan(const ctcn_logspec_opts *o, const LogSpecGeom &g,
   }
 }
 
+// ---- the LDS of a workgroup ---------------------------------------------------------------------------------------------------------------
+// The head of each kernel's dynamic LDS is a struct: the kernel reads its regions as members and the launch sizes the allocation and the
+// frames per workgroup from its sizeof, so the two cannot drift apart.  Behind the head lie fbank_lds_table words, then lds_samples words.
+// (tests/test_spectrogram_host.py compiles this header and holds every offset and size to the kernels' earlier pointer arithmetic.)
+enum { KIND_FBANK = 0, KIND_MFCC = 1, KIND_SPEC = 2 };                 // the feature types of fbank_kernel
+
+template <int NPAD>
+struct FbankLds {
+  fbc tw[NPAD];                                        // twiddles
+  double wbuf[4][2][NPAD];                             // 4 waves x 2 buffers of NPAD / 2 complex
+  float win[NPAD];                                     // the window, 0 from L on
+  float wts[NPAD];                                     // the filters' weights, back to back
+  int ftab[3 * FBANK_MAX_BINS];                        // first | count | weight offset, FBANK_MAX_BINS each
+};
+
+template <int N>
+struct LogSpecLds {
+  fbc tw[N];                                           // twiddles
+  double wbuf[4][2][N];                                // 4 waves x 2 buffers of N / 2 complex
+  double red[8];                                       // 4 waves x (sum, sum of squares)
+  double win[(N + 63) / 64 * 64];                      // the float64 window, zeros behind N
+};
+
+// bytes of the head for a length known at run time (the lengths fbank_geom / logspec_geom admit)
+constexpr size_t fbank_lds_head(int npad) { return npad == 256 ? sizeof(FbankLds<256>) : npad == 512 ? sizeof(FbankLds<512>) : sizeof(FbankLds<1024>); }
+constexpr size_t logspec_lds_head(int n) { return n == 256 ? sizeof(LogSpecLds<256>) : n == 400 ? sizeof(LogSpecLds<400>) : n == 512 ? sizeof(LogSpecLds<512>) : sizeof(LogSpecLds<1024>); }
+FB_HD constexpr int fbank_lds_table(int nbins, int F, int kind) { return kind == KIND_MFCC ? nbins * F + F : 0; }      // DCT, nbins x F bin-major, then the lifter (F)
+FB_HD constexpr size_t lds_samples(int fpw, int shift, int L) { return (size_t)(fpw - 1) * shift + L; }                 // of fpw neighbouring frames
+
 // ---- FFT butterflies: forward DFTs of 2, 4 and 8 points, natural order in and out -------------------------------------------------------------
 FB_HD fbc fb_c(double x, double y) { fbc r; r.x = x; r.y = y; return r; }
 FB_HD fbc fb_add(fbc a, fbc b) { return fb_c(a.x + b.x, a.y + b.y); }
@@ -330,7 +359,7 @@ template <> struct FbDft<5> {
 };
 
 // The passes of the N / 2-point complex transform behind an N-point real one: three radices whose product is N / 2 (another length is one
-// line here, one instantiation in fbank.hip and one case in each of the two switches over the length).
+// line here, one instantiation in fbank.hip and one case in each of the switches and ladders over the length).
 template <int N> struct FbRadix;
 template <> struct FbRadix<256> { static constexpr int r0 = 8, r1 = 8, r2 = 2; };
 template <> struct FbRadix<400> { static constexpr int r0 = 8, r1 = 5, r2 = 5; };

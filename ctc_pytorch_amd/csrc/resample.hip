@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
     for (int i = tid; i < span_len; i += 256) {
       const long long s = s0 + i;
       float v = 0.f;
-      if (s >= 0 && s < n) v = a.is_i16 ? (float)static_cast<const int16_t *>(a.wave)[base + s] : static_cast<const float *>(a.wave)[base + s];
+      if (s >= 0 && s < n) v = wave_sample(a.wave, a.is_i16, base + s);
       span[i] = v;
     }
   }
@@ -212,7 +212,7 @@ extern "C" int ctcn_resample_host(const void *wave, int wave_is_int16, int num_s
     for (int j = 0; j < ntaps[p]; ++j) {
       const long long s = s0 + j;
       float v = 0.f;
-      if (s >= 0 && s < num_samples) v = wave_is_int16 ? (float)static_cast<const int16_t *>(wave)[s] : static_cast<const float *>(wave)[s];
+      if (s >= 0 && s < num_samples) v = wave_sample(wave, wave_is_int16, s);
       acc += (double)w[j] * (double)v;
     }
     out[k] = (float)acc;

@@ -105,10 +105,6 @@ __host__ __device__ __forceinline__ int reverb_cdiv(int a, int b) { return (a + 
 
 __host__ __device__ __forceinline__ int reverb_rnd(uint32_t word, int n) { return (int)(((uint64_t)(word >> 8) * (uint64_t)(uint32_t)n) >> 24); }
 
-__host__ __device__ __forceinline__ float reverb_sample(const void *wave, int is_i16, size_t i) {
-  return is_i16 ? (float)static_cast<const int16_t *>(wave)[i] : static_cast<const float *>(wave)[i];
-}
-
 // The draws of utterance u: r and m are -1 where that part is off; j and off are 0 without a noise row.
 struct ReverbDraw { int r, m, j, off; };
 __host__ __device__ inline ReverbDraw reverb_draw(const ReverbBank &bk, uint32_t rir_thr, uint32_t noise_thr, uint64_t seed, uint64_t u) {
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(256) void reverb_conv_kernel(ReverbArgs a) {
       const int s0 = i0 - k0 - (REVERB_TAP_CHUNK - 1);
       for (int j = tid; j < REVERB_TILE + REVERB_TAP_CHUNK; j += 256) {
         const int s = s0 + j;
-        span[j] = s >= 0 && s < n ? reverb_sample(a.wave, a.is_i16, row + s) : 0.f;
+        span[j] = s >= 0 && s < n ? wave_sample(a.wave, a.is_i16, row + s) : 0.f;
       }
       __syncthreads();
       // output o = 8 tid + r meets tap j at span[o - j + chunk - 1]; a group of eight taps from j0 needs span[8 tid + chunk - 8 - j0 + m], m < 15
@@ -299,7 +295,7 @@ __global__ __launch_bounds__(256) void reverb_conv_kernel(ReverbArgs a) {
 #pragma unroll
     for (int r = 0; r < REVERB_RUN; ++r) span[REVERB_RUN * tid + r] = i0 + REVERB_RUN * tid + r < len ? (float)acc[r] : 0.f;
   } else {                                                                   // no impulse response: y = x
-    for (int j = tid; j < REVERB_TILE; j += 256) span[j] = i0 + j < n ? reverb_sample(a.wave, a.is_i16, row + i0 + j) : 0.f;
+    for (int j = tid; j < REVERB_TILE; j += 256) span[j] = i0 + j < n ? wave_sample(a.wave, a.is_i16, row + i0 + j) : 0.f;
   }
   __syncthreads();
 
@@ -324,7 +320,7 @@ __global__ __launch_bounds__(256) void reverb_conv_kernel(ReverbArgs a) {
       x[q] = 0.f;
       if (i < n) {
         a.out[row + i] = e[q];
-        x[q] = reverb_sample(a.wave, a.is_i16, row + i);
+        x[q] = wave_sample(a.wave, a.is_i16, row + i);
       }
     }
     const double sx = reverb_chunk_sum(x[0], x[1], x[2], x[3], red, tid);
@@ -583,7 +579,7 @@ extern "C" int ctcn_reverb_host(const void *wave, int wave_is_int16, int num_sam
   if (n == 0) return CTCN_OK;
   const ReverbDraw d = reverb_draw(bk, reverb_threshold(opts->rir_prob), reverb_threshold(opts->noise_prob), seed, utt_index);
   std::vector<float> x(n);
-  for (int i = 0; i < n; ++i) x[i] = reverb_sample(wave, wave_is_int16 != 0, i);
+  for (int i = 0; i < n; ++i) x[i] = wave_sample(wave, wave_is_int16 != 0, i);
   const double p_in = reverb_power_sum(x.data(), n) / (double)n;
   double p_sig = p_in;
   if (d.r >= 0) {

@@ -156,7 +156,7 @@ class _Plan(_DeviceBlock):
 
 
 # --------------------------------------------------------------------------------------------------
-# filterbank front-end (fbank.hip): waveform -> normalised log-mel features, CMVN statistics
+# filterbank front-end (fbank.hip): waveform -> normalised log-mel features (the global CMVN statistics, cmvn.hip: cmvn_accumulate below)
 # --------------------------------------------------------------------------------------------------
 def fbank_frames(num_samples, frame_length, frame_shift, snip_edges=True):
     """Frames of a signal of num_samples samples (ctcn_fbank_frames; lengths in samples): Kaldi's two rules.  Host arithmetic, no device."""
@@ -581,7 +581,7 @@ def cmvn_accumulate(feats, frames, stats):
     return stats
 
 
-# normalisation per group of utterances and over a sliding window (fbank.hip, cmvn.hip): Kaldi's per-speaker CMVN and apply-cmvn-sliding
+# normalisation per group of utterances and over a sliding window (cmvn.hip): Kaldi's per-speaker CMVN and apply-cmvn-sliding
 SLIDING_CMN_OPTIONS = dict(cmn_window=600, min_cmn_window=100, normalize_variance=False, center=False)
 _sliding_opts = _StructFrom(_lib.SlidingCmnOpts, SLIDING_CMN_OPTIONS)
 

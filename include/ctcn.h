@@ -588,7 +588,7 @@ int ctcn_edit_ops(const int32_t *a, const int32_t *a_len, const int64_t *b, cons
 int ctcn_step_stats(const float *loss, const int32_t *dist, const int64_t *tgt_len, int B, const int32_t *status, double *out4, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
- * Filterbank front-end (fbank.hip): waveform -> log-mel features with one global mean / variance normalisation; replaces the three Kaldi
+ * Filterbank front-end (fbank.hip; the statistics of the normalisation: cmvn.hip): waveform -> log-mel features with one global mean / variance normalisation; replaces the three Kaldi
  * binaries of timit/steps/make_feat.sh (compute-fbank-feats --config=conf/fbank.conf, compute-cmvn-stats, apply-cmvn --norm-vars=true).
  * The computation is Kaldi's, as its feature-window, feature-fbank and mel-computations sources document it; option names and defaults are
  * Kaldi's.  window_type: 0 hamming, 1 hanning, 2 povey (Kaldi's default), 3 rectangular, 4 blackman.  high_freq <= 0 is an offset from Nyquist.
@@ -938,7 +938,7 @@ int ctcn_reverb(const void *wave, int wave_is_int16, const int32_t *lens, const 
                 void *stream);
 int ctcn_reverb_host(const void *wave, int wave_is_int16, int num_samples, const void *bank, const ctcn_reverb_opts *opts, uint64_t seed,
                      uint64_t utt_index, float *out);
-/* Mean / variance normalisation per group of utterances and over a sliding window (fbank.hip, cmvn.hip): the three Kaldi calls of a standard
+/* Mean / variance normalisation per group of utterances and over a sliding window (cmvn.hip): the three Kaldi calls of a standard
  * recipe that ctcn_cmvn_accumulate and the mean / scale arguments of the feature kernels do not cover -- compute-cmvn-stats --spk2utt
  * (statistics per speaker), apply-cmvn --utt2spk (applied per utterance) and apply-cmvn-sliding.  A group is a speaker, or, with one id
  * per utterance, the utterance itself.  Kaldi's binaries do not run here; the definitions below restate its sources (transform/cmvn,

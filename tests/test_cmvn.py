@@ -76,6 +76,7 @@ def test_grouped_accumulate(dev, F):
     ops.cmvn_accumulate(xd, frames, ref)
     assert same(one[0].cpu().numpy(), ref.cpu().numpy())
     assert same(one.cpu().numpy(), R.accumulate_groups(x, FRAMES, [0] * len(FRAMES), pre[:1]))
+    assert same(ref.cpu().numpy(), R.accumulate_groups(x, FRAMES, [0] * len(FRAMES), pre[:1])[0])      # the global call itself, directly
 
 
 @pytest.mark.parametrize("F", [3, 81, 300])

@@ -1,7 +1,7 @@
 """The CTC loss kernels after ctc.hip's refactor (one classic lattice walk behind a policy, one length contract, plan-then-launch): every
 output bit of every entry point must be what the commit before it computed.
 
-tests/golden/ctc_parent_bits.npz was written by tools/record_ctc_bits.py from a build of that parent commit (its hash is in the file), never
+tests/golden/ctc_parent_bits.npz was written by tools/record_parent_bits.py from a build of that parent commit (its hash is in the file), never
 from the code under test.  An output of up to FULL_MAX elements is held whole -- floats as their uint32 view, so that NaN rows compare -- a
 larger one as the SHA-256 of its bytes.  Every output buffer is pre-filled with a sentinel and compared whole: a cell that one build writes and the
 other does not is a difference.  Inputs come from seeded numpy RandomState generators on the host by arithmetic alone (no exp / log, whose last

@@ -111,6 +111,87 @@ def test_stft_frame_count_rule():
         assert L.ctcn_logspec_frames(n, 80) == SR.stft_frames(np.zeros(n), 256, 80).shape[0]
 
 
+@pytest.mark.parametrize("n_fft", [256, 400, 512, 1024])
+def test_stft_frames_per_workgroup_follow_the_lds_total(n_fft):
+    """The STFT kernel's LDS total, seen through ctcn_logspec_ws_bytes (two doubles per workgroup, so its size shows the frames of one): 4-byte
+    words of twiddles (4 n_fft), wave buffers (16 n_fft), partial sums (16), the float64 window (2 x n_fft rounded up to 64) and the samples
+    of fpw frames ((fpw - 1) hop + n_fft); eight frames where that fits in 160 KB, else four, two, one -- at the very hop where the total
+    crosses, for every length."""
+    L = _lib.lib()
+    fixed = 20 * n_fft + 16 + 2 * ((n_fft + 63) // 64 * 64) + n_fft
+    limit = 160 * 1024 // 4
+
+    def frames_per_workgroup(hop):
+        o = features.LogSpecConfig().c_opts()
+        o.window_size, o.window_stride = (n_fft + 0.5) / 16000.0, (hop + 0.5) / 16000.0
+        assert ops.LogSpecPlan(o).n_fft == n_fft and ops.LogSpecPlan(o).hop == hop
+        blocks = L.ctcn_logspec_ws_bytes(ctypes.byref(o), 1, 8) // 16
+        assert blocks in (1, 2, 4, 8) and L.ctcn_logspec_ws_bytes(ctypes.byref(o), 3, 8) == 3 * 16 * blocks
+        return 8 // blocks
+
+    assert fixed < limit and frames_per_workgroup(1) == 8 and frames_per_workgroup(160) == 8 and frames_per_workgroup(999999) == 1
+    for fpw in (8, 4, 2):
+        last = (limit - fixed) // (fpw - 1)                               # the longest hop at which fpw frames' samples still fit
+        assert fixed + (fpw - 1) * last <= limit < fixed + (fpw - 1) * (last + 1)
+        assert (frames_per_workgroup(last), frames_per_workgroup(last + 1)) == (fpw, fpw // 2), (n_fft, fpw, last)
+
+
+LDS_LAYOUT_CHECK = r"""
+#include <stddef.h>
+#include <stdio.h>
+#include "fbank_core.h"
+// the pointer arithmetic of the kernels and the size formulas of their launches before FbankLds / LogSpecLds (words of 4 bytes, a double is two)
+template <int N> static bool fbank_is() {
+  typedef FbankLds<N> T;
+  return offsetof(T, tw) == 0 && offsetof(T, wbuf) == 4 * (2 * 2 * N) && offsetof(T, win) == offsetof(T, wbuf) + 4 * (2 * 8 * N) &&
+         offsetof(T, wts) == offsetof(T, win) + 4 * N && offsetof(T, ftab) == offsetof(T, wts) + 4 * N &&
+         sizeof(T) == offsetof(T, wts) + 4 * (N + 3 * FBANK_MAX_BINS) && sizeof(T) == 4 * (22 * N + 3 * FBANK_MAX_BINS) && fbank_lds_head(N) == sizeof(T);
+}
+template <int N> static bool logspec_is() {
+  typedef LogSpecLds<N> T;
+  const int wpad = (N + 63) / 64 * 64;
+  return offsetof(T, tw) == 0 && offsetof(T, wbuf) == 4 * (2 * 2 * N) && offsetof(T, red) == offsetof(T, wbuf) + 4 * (2 * 8 * N) &&
+         offsetof(T, win) == offsetof(T, red) + 8 * 8 && sizeof(T) == offsetof(T, win) + 8 * wpad && sizeof(T) == 4 * (20 * N + 16 + 2 * wpad) &&
+         logspec_lds_head(N) == sizeof(T) && offsetof(T, red) % 8 == 0;
+}
+int main() {
+  long n = 0, bad = 0;
+  bad += !fbank_is<256>() + !fbank_is<512>() + !fbank_is<1024>() + !logspec_is<256>() + !logspec_is<400>() + !logspec_is<512>() + !logspec_is<1024>();
+  const int npads[] = {256, 512, 1024}, nffts[] = {256, 400, 512, 1024}, fpws[] = {1, 2, 4, 8}, shifts[] = {1, 80, 160, 441, 3000, 999999};
+  for (int npad : npads) for (int kind = KIND_FBANK; kind <= KIND_SPEC; ++kind) for (int fpw : fpws) for (int shift : shifts)
+    for (int L = npad / 2 + 1; L <= npad; L += 37) for (int nbins = 3; nbins <= 128; nbins += 25) for (int F = 1; F <= (nbins < 64 ? nbins : 64); F += 9, ++n) {
+      const size_t extra = kind == KIND_MFCC ? nbins * F + F : 0;         // the parent's fbank_lds_words(npad, L, shift, fpw, extra)
+      bad += fbank_lds_head(npad) / 4 + fbank_lds_table(nbins, F, kind) + lds_samples(fpw, shift, L) != (size_t)22 * npad + 3 * FBANK_MAX_BINS + extra + (size_t)(fpw - 1) * shift + L;
+    }
+  for (int N : nffts) for (int fpw : fpws) for (int hop : shifts) {    // the parent's logspec_lds_words(nfft, wpad, hop, fpw)
+    bad += logspec_lds_head(N) / 4 + lds_samples(fpw, hop, N) != (size_t)20 * N + 16 + 2 * ((N + 63) / 64 * 64) + (size_t)(fpw - 1) * hop + N;
+    ++n;
+  }
+  printf("%ld layouts, %ld differ\n", n, bad);
+  return bad != 0;
+}
+"""
+
+
+def test_lds_layouts_are_the_kernels_earlier_pointer_arithmetic(tmp_path):
+    """FbankLds and LogSpecLds of fbank_core.h (the structs the spectral kernels read their LDS through and their launches size it from),
+    compiled for the host: every member's offset and the size for every length, and the total over Npad x kind x frames per workgroup x
+    shift x L x bins x columns and N x frames x hop, equal the hand-written pointer arithmetic and size formulas they replaced -- a
+    swapped pair of regions or a miscounted one shows here."""
+    import shutil
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cxx = shutil.which("g++") or shutil.which("c++") or os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "llvm", "bin", "clang++")
+    src = tmp_path / "lds_layout_check.cpp"
+    src.write_text(LDS_LAYOUT_CHECK)
+    csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
+    built = subprocess.run([cxx, "-std=c++17", "-O1", "-I", csrc, str(src), "-o", str(tmp_path / "check")], capture_output=True, text=True)
+    assert built.returncode == 0, built.stderr
+    out = subprocess.run([str(tmp_path / "check")], capture_output=True, text=True)
+    print(out.stdout.strip())
+    assert out.returncode == 0 and " 0 differ" in out.stdout and int(out.stdout.split()[0]) > 60000, out.stdout + out.stderr
+
+
 def test_reflection_of_the_restatement_by_hand():
     y = np.arange(5.0)                                                  # period 2 (n - 1) = 8, the edge sample not repeated, folded twice
     assert np.array_equal(np.pad(y, 9, mode="reflect"), [1, 0, 1, 2, 3, 4, 3, 2, 1, 0, 1, 2, 3, 4, 3, 2, 1, 0, 1, 2, 3, 4, 3])

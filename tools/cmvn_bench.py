@@ -1,7 +1,7 @@
 """Time of the grouped and the sliding-window CMVN on the device by HIP events, at the recipe's base-feature shapes -- 32 x 800 x 81 and
 8 x 800 x 81, ragged by a few frames as a length-sorted batch is:
-  cmvn_accumulate_groups at G = 1 and G = 32 beside ctcn_cmvn_accumulate on the same batch (the partial kernel is shared: the difference is
-  the finish kernel's);
+  cmvn_accumulate_groups at G = 1 and G = 32 beside ctcn_cmvn_accumulate on the same batch (the partial kernel is shared; the global call
+  is the grouped finish without ids, so it reads what G = 1 reads -- on a parent of that change the difference is the global finish kernel's);
   cmvn_apply (out of place, into a preallocated tensor) against the bytes it has to move, and the same call on a 1 x 1 x 81 batch: the
   time of a launch that has nothing to do, i.e. the part of the call that is overhead and not the kernel;
   cmvn_sliding at Kaldi's defaults with and without the variance, also as ns per frame of the utterance (the chain in time);
